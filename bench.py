@@ -2,6 +2,7 @@
 """Headline benchmark: audio-seconds/sec of the full synthesis hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
+    python bench.py ... --dump-outputs DIR                 (+ DIR/audio.npy: what the last of the K timed steps returned)
 
 One "step" = one pass of the hot path over one batch per GPU: condition-encode -> 4-step DMD sampler
 -> codec decode of B=8 utterances x 10 s (N=75 frames, R=15 reference frames, P=30 phoneme ids:
@@ -18,6 +19,7 @@ Rank 0 prints ONE JSON line (contract in the task statement) including
 import argparse
 import json
 import os
+import subprocess
 import sys
 import time
 
@@ -75,6 +77,25 @@ def one_step(eng, inp, seed, ctx=None, gather=None, workload="dmd4", pcm16=False
             audio = eng.pcm16(audio)
         return ctx.gather_waveforms(audio, ctx.world * B, out=gather)
     return audio
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(dirname, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: every tensor of `arrays` -> <dirname>/<name>.npy, float64 kept, anything else (fp32 audio, int16 PCM of
+    --gather pcm16) as float32, which holds both exactly.  At most `limit` bytes in all: smallest first, an array larger than an
+    even split of what is left is cut to a fixed, seeded sample of its elements (sorted flat indices, the same on every run; a
+    1-D array then)."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {k: v.detach().to("cpu", torch.float64 if v.dtype == torch.float64 else torch.float32).numpy() for k, v in arrays.items()}
+    budget = limit - 128 * len(host)      # room for the .npy headers
+    for i, (name, a) in enumerate(sorted(host.items(), key=lambda kv: kv[1].nbytes)):
+        share = budget // (len(host) - i)
+        if a.nbytes > share:
+            a = a.reshape(-1)[np.sort(np.random.default_rng(0).choice(a.size, share // a.itemsize, replace=False))]
+        budget -= a.nbytes
+        np.save(os.path.join(dirname, name + ".npy"), a)
 
 
 def kernel_source_hash():
@@ -190,7 +211,10 @@ ALGO = {
 def ensure_world(n_gpus, argv):
     """`--gpus N` must describe the job that runs.  Under a launcher (RANK / WORLD_SIZE set) a mismatch is an error; without one,
     N > 1 re-executes this script under the driver's own command line (python -m torch.distributed.run --nnodes=1
-    --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...) — it never prints a world-1 line for N > 1."""
+    --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py ...) as a CHILD process and exits with its return code —
+    it never prints a world-1 line for N > 1.  The launcher is not exec'd in place: this process must not replace itself once the
+    GPU runtime may be open in it, so the device count comes from torch.cuda.device_count() alone (amdsmi where available, no
+    HIP initialisation) and the ranks start in fresh processes."""
     world = int(os.environ.get("WORLD_SIZE", "1"))
     launched = "RANK" in os.environ and "WORLD_SIZE" in os.environ
     if n_gpus < 1:
@@ -204,7 +228,7 @@ def ensure_world(n_gpus, argv):
     if n_gpus == 1:
         return
     shared = os.environ.get("SMTTS_DIST_BACKEND") == "gloo"     # tests: several gloo ranks may share one GPU
-    ndev = torch.cuda.device_count() if torch.cuda.is_available() else 0
+    ndev = torch.cuda.device_count()
     if ndev < n_gpus and not (shared and ndev >= 1):
         sys.exit(f"bench.py: --gpus {n_gpus} needs {n_gpus} visible GPUs, found {ndev} (one process per GPU over RCCL); "
                  f"refusing to print a line for fewer GPUs than asked")
@@ -215,9 +239,20 @@ def ensure_world(n_gpus, argv):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n_gpus), "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY=os.environ.get("HSA_ENABLE_IPC_MODE_LEGACY", "0"))
-    sys.stderr.write("bench.py: --gpus %d without a launcher: re-executing as\n  %s\n" % (n_gpus, " ".join(cmd)))
+    sys.stderr.write("bench.py: --gpus %d without a launcher: re-executing as a child process\n  %s\n" % (n_gpus, " ".join(cmd)))
     sys.stderr.flush()
-    os.execvpe(cmd[0], cmd, env)
+    sys.exit(subprocess.run(cmd, env=env, preexec_fn=_die_with_parent()).returncode)
+
+
+def _die_with_parent():
+    """preexec_fn for the relaunched job: the launcher gets SIGTERM (and takes its ranks down) if this process dies first, e.g.
+    killed by a caller's timeout, so no rank is left holding the GPU.  Linux only; elsewhere nothing."""
+    if not sys.platform.startswith("linux"):
+        return None
+    import ctypes
+    import signal
+    prctl = ctypes.CDLL(None, use_errno=True).prctl      # resolved before the fork: the child only makes the call
+    return lambda: prctl(1, int(signal.SIGTERM))         # PR_SET_PDEATHSIG
 
 
 def _stamped(path_json, ksha):
@@ -382,7 +417,9 @@ def _profile_block(eng, inp, args, tuning, shapes):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=300, help="timed steps (default sized so the timed region is >= 3 s)")
+    ap.add_argument("--steps", type=int, default=300,
+                    help="timed steps: the headline region and the one-batch-at-a-time leg each time exactly this many (default "
+                         "sized so the timed region is >= 3 s)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--precision", default="f16",
                     help="f16 (default: one fp16 MFMA per product on the block / encoder / codec-FFN GEMMs, split-bf16 on the "
@@ -394,8 +431,14 @@ def main():
                          "workspace (default 3; 1 = one batch at a time on one stream)")
     ap.add_argument("--no-pipeline", dest="in_flight", action="store_const", const=1, help="same as --in-flight 1")
     ap.add_argument("--gather", default="f32", choices=["f32", "pcm16"], help="dtype of the N > 1 waveform all-gather")
-    ap.add_argument("--min-seconds", type=float, default=2.0, help="repeat the timed K-step region until this much has been timed")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="opt-in: repeat the timed K-step region until this much has been timed and report the median repeat "
+                         "(default 0: the region runs once, exactly --steps steps)")
     ap.add_argument("--max-repeats", type=int, default=50)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (the waveform batch a caller receives; "
+                         "gathered over ranks at N > 1) as DIR/<name>.npy in float32, <= 64 MB in all; inputs, weights and step "
+                         "seeds depend only on the arguments, so two builds can be compared output for output")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--tuning", default="auto", choices=["auto", "latency", "throughput"],
@@ -466,9 +509,9 @@ def main():
     streams = [torch.cuda.Stream(device) for _ in range(in_flight)] if in_flight > 1 else []
     gathers = [ctx.gather_buffer(world * B, samples, gdtype) for _ in range(in_flight)] if ctx.collective else []  # one per slot
     run_steps(args.warmup, 0, in_flight, timed_tuning)
-    # The timed region is EXACTLY K steps between barrier + device sync on both sides, MAX over ranks.  The driver fixes K (20
-    # steps = 0.2 s here), so the region is REPEATED until >= --min-seconds have been timed in all (every rank takes the same
-    # decision: the elapsed time it looks at is the max over ranks); the line reports the MEDIAN repeat, min / max beside it.
+    # The timed region is EXACTLY K steps between barrier + device sync on both sides, MAX over ranks, run once.  Only when asked
+    # (--min-seconds > 0) is the region REPEATED until that much has been timed in all (every rank takes the same decision: the
+    # elapsed time it looks at is the max over ranks); the line then reports the MEDIAN repeat, min / max beside it.
     dts = []
     out = None
     while True:
@@ -480,8 +523,11 @@ def main():
         if sum(dts) >= args.min_seconds or len(dts) >= args.max_repeats:
             break
     dt = sorted(dts)[len(dts) // 2]
+    if args.dump_outputs and rank == 0:
+        # now, before anything else runs: the gather buffer of a collective run is reused by the legs below
+        dump_outputs(args.dump_outputs, {"audio": out})
     # the same K steps one batch at a time on one stream: the latency of a batch, and the strict reading of "at batch = 8"
-    ns = max(3, min(args.steps, 100))
+    ns = args.steps
     dt_seq = None
     if not args.no_sequential:
         run_steps(2, 50, 1, "latency")
@@ -544,8 +590,9 @@ def main():
         "value_sequential": round(audio_s_seq / dt_seq, 2) if dt_seq else None,
         "sequential_ms_per_step": round(1e3 * dt_seq / ns, 3) if dt_seq else None,
         "rtf_sequential": round(dt_seq / audio_s_seq, 7) if dt_seq else None,
-        # the K-step region repeated: value / ms_per_step are the median repeat
-        "timed_seconds": round(sum(dts), 3), "repeats": len(dts), "ms_per_step_min": round(1e3 * min(dts) / args.steps, 3),
+        # the K-step region, repeated only under --min-seconds: value / ms_per_step are the median repeat
+        "timed_seconds": round(sum(dts), 3), "repeats": len(dts), "timed_steps": args.steps * len(dts),
+        "ms_per_step_min": round(1e3 * min(dts) / args.steps, 3),
         "ms_per_step_max": round(1e3 * max(dts) / args.steps, 3), "spread": round((max(dts) - min(dts)) / dt, 4),
         "dist": {"backend": ctx.backend, "collective": bool(ctx.collective), "world": world},
         "config": {"workload": WORKLOADS[args.workload] + ", B=8 x 10 s per GPU "

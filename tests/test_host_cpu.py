@@ -365,6 +365,34 @@ def test_bench_codec_bytes_follow_the_spec_and_profiler_names_map_back():
         assert prof_name(k) == want, (k, prof_name(k))
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_size_limit(tmp_path):
+    """bench.py --dump-outputs: fp32 audio written as is, int16 PCM widened exactly to float32, float64 kept; over the limit the
+    large array becomes a fixed seeded sample (the same elements on every call) and the files stay within the limit in all."""
+    import importlib, sys, os
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    g = torch.Generator().manual_seed(0)
+    audio = torch.randn(8, 1, 24000, generator=g)
+    bench.dump_outputs(str(tmp_path / "a"), {"audio": audio})
+    a = np.load(tmp_path / "a" / "audio.npy")
+    assert a.dtype == np.float32 and a.shape == (8, 1, 24000) and np.array_equal(a, audio.numpy())
+    assert bench.DUMP_LIMIT_BYTES == 64 << 20
+    pcm = torch.randint(-32768, 32767, (64, 1, 24000), dtype=torch.int16, generator=g)
+    small = torch.randn(3, 5, dtype=torch.float64, generator=g)
+    limit = 1 << 20
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"audio": pcm, "x": small}, limit=limit)
+    files = sorted(os.listdir(tmp_path / "b"))
+    assert files == ["audio.npy", "x.npy"] and sum(os.path.getsize(tmp_path / "b" / f) for f in files) <= limit
+    x = np.load(tmp_path / "b" / "x.npy")
+    assert x.dtype == np.float64 and np.array_equal(x, small.numpy())        # small arrays are kept whole
+    s1, s2 = np.load(tmp_path / "b" / "audio.npy"), np.load(tmp_path / "c" / "audio.npy")
+    assert s1.dtype == np.float32 and s1.ndim == 1 and s1.size > limit // 8 and np.array_equal(s1, s2)
+    assert np.isin(s1, pcm.numpy().astype(np.float32)).all()
+
+
 def test_the_shipped_library_reads_exactly_the_ten_documented_environment_switches():
     """every getenv("SMTTS_*") left in csrc/ is one of the ten product switches DESIGN.md lists; the A/B sessions'
     switches go through lab_env(), which sees the environment in a -DSMTTS_LAB build only."""

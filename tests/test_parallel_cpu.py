@@ -136,16 +136,22 @@ def test_bench_gpus_n_disagreeing_with_the_launchers_world_is_a_hard_error():
 
 
 def test_bench_relaunch_command_is_the_drivers_launcher_line(monkeypatch):
-    """ensure_world() with enough devices execs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
-    127.0.0.1 --master-port P bench.py <same argv>` (the exec itself is stubbed out)."""
+    """ensure_world() with enough devices runs `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr
+    127.0.0.1 --master-port P bench.py <same argv>` as a child process and exits with its return code (the child itself is
+    stubbed out).  The process never replaces itself: no exec."""
+    import subprocess
     import bench
     seen = {}
     monkeypatch.setattr(bench.torch.cuda, "is_available", lambda: True)
     monkeypatch.setattr(bench.torch.cuda, "device_count", lambda: 8)
-    monkeypatch.setattr(bench.os, "execvpe", lambda f, a, e: seen.update(file=f, argv=a, env=e))
+    monkeypatch.setattr(bench.subprocess, "run", lambda a, env, **kw: seen.update(argv=a, env=env) or subprocess.CompletedProcess(a, 3))
+    for name in ("execv", "execve", "execvp", "execvpe", "execl", "execle", "execlp", "execlpe"):
+        monkeypatch.setattr(bench.os, name, lambda *a: pytest.fail("bench.py exec'd instead of starting a child process"))
     for k in ("RANK", "WORLD_SIZE"):
         monkeypatch.delenv(k, raising=False)
-    bench.ensure_world(8, ["--gpus", "8", "--steps", "20", "--warmup", "3"])
+    with pytest.raises(SystemExit) as ex:
+        bench.ensure_world(8, ["--gpus", "8", "--steps", "20", "--warmup", "3"])
+    assert ex.value.code == 3                       # the launcher's return code is bench.py's
     a = seen["argv"]
     assert a[1:6] == ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "8"] and "--master-addr" in a
     assert a[a.index("--master-addr") + 1] == "127.0.0.1" and a[-6:] == ["--gpus", "8", "--steps", "20", "--warmup", "3"]
