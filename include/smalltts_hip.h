@@ -51,7 +51,7 @@ const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation er
 const char* smtts_version(void);
 /* bumped on every signature / default change: 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
-#define SMTTS_ABI_VERSION 5
+#define SMTTS_ABI_VERSION 6
 int smtts_abi_version(void);
 
 /* ---- weights (replaces the ONNX initialisers; names/shapes = DiTModel.state_dict(),
@@ -173,6 +173,18 @@ int smtts_bench_gemm(smtts_handle h, int M, int N, int K, int epi, int split, in
 /* hot-path kernel (gemm3: split-bf16 A and W via DMA ring): C[M,N] = act(A W^T + bias); A, W fp32 on device, split internally; K % 64 == 0 */
 int smtts_test_gemm3(smtts_handle h, void* stream, const float* A, const float* W, const float* bias, int M, int N, int K,
                      int act, int split, int cfg, float* C);
+/* one LN-fold step (the AdaLN / RMSNorm between two block GEMMs, see smtts_test_set_ln_fold) on its own:
+ *   x[m] += row_mask[m] gate (A[m] Wp^T + bp)          (x [M,D] updated in place; masked rows keep x; gate / bp / row_mask may be null)
+ *   y = LN(x; eps) (1 + scale) + shift   (rms = 0)   or   y = x rsqrt(mean x^2 + eps) scale   (rms = 1, shift unused)
+ *   hid[M,F] = silu(y W1^T + b1) * (y W3^T + b3)       (fp32, decoded from the 16-bit operand image the chain writes)
+ * fold = 1: the producer / consumer epilogues with the tables of fold_vectors; 0: the norm launches.  prec 1 bf16, 2 fp16,
+ * 3 split-bf16 for every operand.  K % 64 == 0, D % 32 == 0 (fold: D % 64 == 0, and D == 960 with rms = 0), F % 32 == 0.
+ * shift_out [M] (may be null): the producers' row shift as the consumer leaves it for the next producer (the mean of the updated
+ * row, LayerNorm fold only; 0 otherwise) */
+int smtts_test_ln_fold(smtts_handle h, void* stream, const float* A, const float* Wp, const float* bp, const float* gate,
+                       const uint8_t* row_mask, const float* scale, const float* shift, const float* W1, const float* W3,
+                       const float* b1, const float* b3, int M, int K, int D, int F, float eps, int rms, int prec, int fold,
+                       float* x, float* hid, float* shift_out);
 /* codec blocks: 1 (default) = fused mixer and fused FFN kernels (C <= 256), 0 = separate norm / conv / two-GEMM path */
 int smtts_test_set_fused_ffn(smtts_handle h, int on);
 /* fused sampler: 1 (default) = the AdaLN between two DiT block GEMMs folded into their epilogues (reference dit.py:19-25,197-212

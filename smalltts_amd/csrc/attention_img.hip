@@ -533,7 +533,9 @@ hipError_t launch_cross_pack(const CrossPackArgs& p, hipStream_t st) {
 namespace {
 __global__ void split_to_f32_kernel(const bf16_t* __restrict__ hi, const bf16_t* __restrict__ lo, float* __restrict__ out, long n) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i < n) out[i] = (float)hi[i] + (float)lo[i];
+    if (i >= n) return;
+    if (sm_is_f16(lo)) out[i] = (float)__builtin_bit_cast(half_t, reinterpret_cast<const unsigned short*>(hi)[i]);
+    else out[i] = lo ? (float)hi[i] + (float)lo[i] : (float)hi[i];
 }
 }  // namespace
 hipError_t launch_split_to_f32(const bf16_t* hi, const bf16_t* lo, float* out, long n, hipStream_t st) {

@@ -166,6 +166,13 @@ int smtts_test_gemm3(smtts_handle h, void* stream, const float* A, const float* 
                      int act, int split, int cfg, float* C) { NULLCHK;
     return E.test_gemm3(ST(stream), A, W, bias, M, N, K, act, split, cfg, C);
 }
+int smtts_test_ln_fold(smtts_handle h, void* stream, const float* A, const float* Wp, const float* bp, const float* gate,
+                       const uint8_t* row_mask, const float* scale, const float* shift, const float* W1, const float* W3,
+                       const float* b1, const float* b3, int M, int K, int D, int F, float eps, int rms, int prec, int fold,
+                       float* x, float* hid, float* shift_out) { NULLCHK;
+    return E.test_ln_fold(ST(stream), A, Wp, bp, gate, row_mask, scale, shift, W1, W3, b1, b3, M, K, D, F, eps, rms, prec, fold, x, hid,
+                          shift_out);
+}
 int smtts_test_set_fused_ffn(smtts_handle h, int on) { NULLCHK; E.set_fused_ffn(on != 0); return 0; }
 int smtts_test_set_ln_fold(smtts_handle h, int on) { NULLCHK; E.set_ln_fold(on != 0); return 0; }
 int smtts_test_set_attention_mfma(smtts_handle h, int mode) { NULLCHK;   // 0: fp32 projection + qk_prep + the fp32 VALU reference kernel; else (default): producer-written operand images + the DMA / MFMA kernel

@@ -5,6 +5,11 @@
 #include <cstdio>
 #include <cstring>
 
+// LN-fold row shift (gemm.hpp LnFoldIn::cshift).  -DLN_FOLD_SHIFT=0 builds the unshifted fold of round 6 (A/B of the precision
+// tests only: tests/test_ln_fold_gpu.py measures both against fp64)
+#ifndef LN_FOLD_SHIFT
+#define LN_FOLD_SHIFT 1
+#endif
 #define HIPC(x)                                          \
     do {                                                 \
         hipError_t e__ = (x);                            \
@@ -882,7 +887,7 @@ int Engine::run_encoder(hipStream_t st, const EncoderW& e, void* wsv, int B, int
     HIPC(launch_rmsnorm(w.x, rd, nullptr, y.hi, y.lo, rd, M, D, e.eps, e.blocks[0].an, st));
     // RMSNorm fold (gemm.hpp LnFoldIn, rms): the norm between two block GEMMs lives in their epilogues — the producer writes x w and the
     // row's sum-of-squares partials, the consumer scales by rstd; the first norm (above) and the final one (feeds a plain projection) stay
-    const bool fold = ln_fold_now() && attn_img_ && attn_epi_ && D % 32 == 0;
+    const bool fold = fold_epi_on() && D % 64 == 0;   // (the consumer reads the D / 32 partials in pairs)
     LnFoldIn fin;
     fin.part = w.lnpart; fin.NP = D / 32; fin.inv_c = 1.0f / D; fin.eps = e.eps; fin.rms = 1;
     for (size_t l = 0; l < e.blocks.size(); ++l) {
@@ -1099,6 +1104,8 @@ int Engine::modulation(hipStream_t st, const float* t_dev, int rows, float* sinb
     return 0;
 }
 
+bool Engine::dit_fold_on(long rows) const { return fold_epi_on() && rows <= kFoldMaxRows; }
+
 namespace {
 struct ModWs {
     float *sinb, *t1, *temb, *e1, *semb, *mod, *ftab = nullptr;
@@ -1113,7 +1120,7 @@ struct ModWs {
     }
 };
 struct CoreWs {
-    float *h, *x, *qkvg, *part, *lnpart;
+    float *h, *x, *qkvg, *part, *lnpart, *lnc;   // lnc [M]: the LN-fold producers' row shift (gemm.hpp LnFoldIn::cshift)
     float *rope_c, *rope_s;  // cos / sin of a caller-supplied angle table: per call (several calls may be in flight on different streams)
     SplitBuf gm1, gm2, y, o, ffh;
     SplitBuf qi, ki, vti, gi;   // attention operand images of the self part: [B][8][N][128] x 2, [B][8][128][pad8(N)], [M][960]
@@ -1131,6 +1138,7 @@ struct CoreWs {
         qkvg = b.take<float>(M * 4 * kHidden);
         part = b.take<float>(M * kHidden * kSplitK);
         lnpart = b.take<float>(M * kLnGroups * 2);
+        lnc = b.take<float>(M);
         rope_c = b.take<float>((size_t)N * 64);
         rope_s = b.take<float>((size_t)N * 64);
         gm1 = take_split(b, gm_elems);
@@ -1219,8 +1227,13 @@ int Engine::denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, 
         HIPC(hipStreamWaitEvent(st, ev_join_, 0));
         join_pending_ = false;
     }
+    // LN-fold (gemm.hpp LnFoldIn): inside the fused sampler — one modulation row for the whole batch, tables from modulation() —
+    // the AdaLN between two block GEMMs lives in their epilogues; the first AdaLN of a step (here) and the final one (velocity
+    // head, SITE_COND precision) keep their ln_modulate, the first one also writes the row means the producers shift by
+    const bool fold = ftab && mod_rstride == 0 && dit_fold_on(M);   // (ftab: the tables sample() planned by the same predicate)
+    float* const lnc = fold && LN_FOLD_SHIFT ? w.lnc : nullptr;
     HIPC(launch_ln_modulate(w.x, nullptr, yb.hi, yb.lo, M, kHidden, 1e-6f, mod + 0 * kHidden, mod + 1 * kHidden, kModLd,
-                            mod_row0, mod_rstride, N, st));
+                            mod_row0, mod_rstride, N, st, lnc));
     // split-K exists to fill the chip at M = 600 (150 tiles of 64x64 for N = 960); the 3B-row CFG batches of the teacher
     // sampler (M = 1800: 435 tiles) fill it without, and the fused epilogue is cheaper than partials + reduce (495 -> 454 ms)
     // ... and so do several batches in flight (throughput tuning): there the unsplit GEMM + a separate AdaLN costs 2.3x fewer
@@ -1229,10 +1242,6 @@ int Engine::denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, 
     const bool unsplit = M > 1024 || (tuning_ == TUNE_THROUGHPUT && !splitk_tp);
     const int ks_out = unsplit ? 1 : ksplit_out_, ks_ff2 = unsplit ? 1 : ksplit_ff2_;
     if (!(attn_img_ && attn_epi_) && ensure_qkvg_unpadded()) return 1;
-    // LN-fold (gemm.hpp LnFoldIn): inside the fused sampler — one modulation row for the whole batch, tables from modulation() —
-    // the AdaLN between two block GEMMs lives in their epilogues; the first AdaLN of a step (above) and the final one (velocity
-    // head, SITE_COND precision) keep their ln_modulate
-    const bool fold = ln_fold_ && ftab && mod_rstride == 0 && attn_img_ && attn_epi_;   // (ftab: null under throughput tuning, see sample())
     const float* const mrow = mod + (long)mod_row0 * kModLd;            // this step's modulation row (fold path only)
     const float* const frow = fold ? ftab + (long)mod_row0 * 2 * kFoldNF : nullptr;   // [0]: W shift, [1]: W (1 + scale)
     auto fold_in = [&](int l, int site) {
@@ -1241,6 +1250,7 @@ int Engine::denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, 
         const long off = (long)l * kFoldPerBlock + (site ? 4L * kHeads * 128 : 0);
         f.wsh = frow + off;
         f.wc = frow + kFoldNF + off;
+        f.cshift = lnc;
         return f;
     };
     for (int l = 0; l < kBlocks; ++l) {
@@ -1309,7 +1319,7 @@ int Engine::denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, 
         NextLN ln1{m + 3 * kHidden, m + 4 * kHidden, yb.hi, yb.lo};
         const float* const mr = mrow + (long)l * kModPerBlock;
         if (fold) {
-            EpiResidLN e1{w.x, rh, nullptr, mr + 2 * kHidden, mask, mr + 4 * kHidden, yb.hi, yb.lo, kHidden, w.lnpart, kLnGroups};
+            EpiResidLN e1{w.x, rh, nullptr, mr + 2 * kHidden, mask, mr + 4 * kHidden, yb.hi, yb.lo, kHidden, w.lnpart, kLnGroups, 0, lnc};
             HIPC(gemm3_resid_ln(ops3(w.o, rh, b.out, M, pb), e1, pb, st));
         } else if (ks_out > 1) {
             HIPC(gemm3_resid_splitk(ops3(w.o, rh, b.out, M, pb), r1, w.part, ks_out, pb, st, ln1));
@@ -1330,7 +1340,7 @@ int Engine::denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, 
         NextLN ln2 = l + 1 < kBlocks ? NextLN{mn + 0 * kHidden, mn + 1 * kHidden, yb.hi, yb.lo}
                                      : NextLN{mn + kHidden, mn, yv.hi, yv.lo};
         if (fold && l + 1 < kBlocks) {
-            EpiResidLN e2{w.x, rh, b.b2, mr + 5 * kHidden, nullptr, mr + kModPerBlock + kHidden, yb.hi, yb.lo, kHidden, w.lnpart, kLnGroups};
+            EpiResidLN e2{w.x, rh, b.b2, mr + 5 * kHidden, nullptr, mr + kModPerBlock + kHidden, yb.hi, yb.lo, kHidden, w.lnpart, kLnGroups, 0, lnc};
             HIPC(gemm3_resid_ln(ops3(w.ffh, rowmap_plain(kFFp), b.ff2, M, pb), e2, pb, st));
         } else if (ks_ff2 > 1) {
             HIPC(gemm3_resid_splitk(ops3(w.ffh, rowmap_plain(kFFp), b.ff2, M, pb), r2, w.part, ks_ff2, pb, st, ln2));
@@ -1466,7 +1476,7 @@ size_t Engine::sample_ws_bytes(int B, int N, int R, int P, int n_steps, int cfg)
     SampleWs s;
     s.plan(b, B, N, n_steps, cfg);
     ModWs m;
-    m.plan(b, n_steps, ln_fold_now() && (long)(cfg ? 3 * B : B) * N <= kFoldMaxRows);
+    m.plan(b, n_steps, dit_fold_on((long)(cfg ? 3 * B : B) * N));
     return b.off + 256 + denoise_core_bytes(cfg ? 3 * B : B, N) + cross_img_bytes(cfg ? 3 * B : B, R, P);
 }
 
@@ -1487,7 +1497,7 @@ int Engine::sample(hipStream_t st, int mode, int n_steps, int cfg, float s_text,
     // (the fold replaces split-K partials + reduce; the 3B-row CFG batches of the teacher run unsplit + ln_modulate already, and there
     // the table kernel — every block weight once per four steps — and the heavier epilogue cost more than the norm launches: 239.0 vs
     // 240.6 ms per 128-step batch, profiles/r06l_ab_teacher_fold.txt)
-    m.plan(bump, n_steps, ln_fold_now() && (long)(cfg ? 3 * B : B) * N <= kFoldMaxRows);
+    m.plan(bump, n_steps, dit_fold_on((long)(cfg ? 3 * B : B) * N));
     char* core = static_cast<char*>(ws) + ((bump.off + 255) & ~size_t(255));
     const long e = (long)B * N * kLatent;
 
@@ -1983,6 +1993,103 @@ int Engine::test_gemm3(hipStream_t st, const float* A, const float* W, const flo
     (void)hipStreamSynchronize(st);
     for (void* p : {(void*)hi, (void*)lo, (void*)ahi, (void*)alo}) (void)hipFree(p);
     return e == hipSuccess ? 0 : fail_hip(e, "test_gemm3");
+}
+
+// One LN-fold step of the real chain in isolation (gemm.hpp LnFoldIn): the producer (gated residual of x, operand image, row partials),
+// the fold tables of ONE site from fold_vectors_kernel (LayerNorm only) and the SwiGLU consumer; fold = 0 runs the norm-launch path of
+// the same step (plain residual, ln_modulate / rmsnorm, plain SwiGLU).  x [M][D] is updated in place; h [M][F] = the hidden image, decoded.
+int Engine::test_ln_fold(hipStream_t st, const float* A, const float* Wp, const float* bp, const float* gate, const uint8_t* mask,
+                         const float* nscale, const float* shift, const float* W1, const float* W3, const float* b1, const float* b3,
+                         int M, int K, int D, int F, float eps, int rms, int prec, int fold, float* x, float* h, float* c_out) {
+    DeepScope deep_scope(gemm_deep_);
+    HIPC(hipSetDevice(device_));
+    if (M <= 0 || K % 64 || D % 32 || F % 32 || F <= 0) return fail("test_ln_fold: M > 0, K % 64 == 0, D % 32 == 0, F % 32 == 0");
+    if (prec != PREC_BF16 && prec != PREC_F16 && prec != PREC_BF16X3) return fail("test_ln_fold: precision must be 1, 2 or 3");
+    if (!nscale || (!rms && !shift)) return fail("test_ln_fold: scale (and, for LayerNorm, shift) required");
+    if (fold && (D / 32) % 2) return fail("test_ln_fold: LN-fold needs an even number of 32-column partial groups (D % 64 == 0)");
+    if (fold && !rms && D != kHidden) return fail("test_ln_fold: the fold-table kernel multiplies K = 960 weights");
+    const int NP = D / 32;
+    const bool f16 = prec == PREC_F16;
+    std::vector<void*> bufs;
+    bool oom = false;
+    auto take = [&](size_t bytes) { void* p = nullptr; if (hipMalloc(&p, bytes) == hipSuccess) bufs.push_back(p); else oom = true; return p; };
+    bf16_t* wp_hi = (bf16_t*)take((size_t)D * K * 2);
+    bf16_t* wp_lo = (bf16_t*)take((size_t)D * K * 2);
+    bf16_t* w13_hi = (bf16_t*)take((size_t)2 * F * D * 2);
+    bf16_t* w13_lo = (bf16_t*)take((size_t)2 * F * D * 2);
+    float* cat = (float*)take((size_t)2 * F * D * 4);
+    std::vector<int> perm = swiglu_perm(F);
+    int* dperm = (int*)take(perm.size() * sizeof(int));
+    bf16_t* a_hi = (bf16_t*)take((size_t)M * K * 2);
+    bf16_t* a_lo = (bf16_t*)take((size_t)M * K * 2);
+    bf16_t* y_hi = (bf16_t*)take((size_t)M * D * 2);
+    bf16_t* y_lo = (bf16_t*)take((size_t)M * D * 2);
+    bf16_t* f_hi = (bf16_t*)take((size_t)M * F * 2);
+    bf16_t* f_lo = (bf16_t*)take((size_t)M * F * 2);
+    float* part = (float*)take((size_t)M * NP * 2 * 4);
+    float* modrow = (float*)take((size_t)2 * D * 4);
+    float* tab = (float*)take((size_t)2 * 2 * F * 4);
+    float* cs = (float*)take((size_t)M * 4);
+    hipError_t e = oom ? hipErrorOutOfMemory : hipSuccess;
+    auto run = [&]() -> hipError_t {
+        hipError_t le;
+#define LNF(call) do { if ((le = (call)) != hipSuccess) return le; } while (0)
+        LNF(launch_split_rows(Wp, K, f16 ? nullptr : wp_hi, wp_lo, K, D, K, nullptr, st, f16 ? wp_hi : nullptr));
+        LNF(hipMemcpyAsync(cat, W1, (size_t)F * D * 4, hipMemcpyDeviceToDevice, st));
+        LNF(hipMemcpyAsync(cat + (size_t)F * D, W3, (size_t)F * D * 4, hipMemcpyDeviceToDevice, st));
+        LNF(hipMemcpyAsync(dperm, perm.data(), perm.size() * sizeof(int), hipMemcpyHostToDevice, st));
+        LNF(launch_split_rows(cat, D, f16 ? nullptr : w13_hi, w13_lo, D, 2 * F, D, dperm, st, f16 ? w13_hi : nullptr));
+        LNF(launch_to_split(A, rowmap_plain(K), a_hi, sm_lo_for(prec, a_lo), rowmap_plain(K), M, K, st));
+        PW wp, w13;
+        wp.hi = wp.h16 = wp_hi; wp.lo = wp_lo; wp.N = D; wp.K = K;
+        w13.hi = w13.h16 = w13_hi; w13.lo = w13_lo; w13.N = 2 * F; w13.K = D;
+        const RowMap rd = rowmap_plain(D);
+        const SplitBuf y = SplitBuf{y_hi, y_lo}.as(prec), ffh = SplitBuf{f_hi, f_lo}.as(prec);
+        EpiSwiGLU sw{nullptr, F, b1, b3, ffh.hi, ffh.lo};
+        if (fold) {
+            if (!rms) {   // the tables of one site: W shift and W (1 + scale) on the weights the consumer multiplies
+                LNF(hipMemcpyAsync(modrow, shift, (size_t)D * 4, hipMemcpyDeviceToDevice, st));
+                LNF(hipMemcpyAsync(modrow + D, nscale, (size_t)D * 4, hipMemcpyDeviceToDevice, st));
+                FoldSites fs{};
+                fs.n = 1;
+                fs.NF = 2 * F;
+                FoldSite& f = fs.s[0];
+                f.w = w13_hi; f.wlo = prec == PREC_BF16X3 ? w13_lo : nullptr; f.fmt = f16 ? 0 : 1; f.N = 2 * F;
+                f.shift_off = 0; f.scale_off = D; f.out_off = 0;
+                LNF(launch_fold_vectors(fs, modrow, 2 * D, 1, tab, st));
+                // the row shift as the chain has it in front of its first producer: the mean ln_modulate took of x (its image is
+                // overwritten by the producer)
+                if (LN_FOLD_SHIFT) LNF(launch_ln_modulate(x, nullptr, y.hi, y.lo, M, D, eps, shift, nscale, 0, 0, 0, M, st, cs));
+            }
+            float* const csh = !rms && LN_FOLD_SHIFT ? cs : nullptr;
+            EpiResidLN p{x, rd, bp, gate, mask, nscale, y.hi, y.lo, D, part, NP, rms, csh};
+            LNF(gemm3_resid_ln(ops3(SplitBuf{a_hi, a_lo}, rowmap_plain(K), wp, M, prec), p, prec, st));
+            LnFoldIn fin;
+            fin.part = part; fin.NP = NP; fin.inv_c = 1.0f / D; fin.eps = eps; fin.rms = rms;
+            if (!rms) { fin.wsh = tab; fin.wc = tab + 2 * F; fin.cshift = csh; }
+            sw.fold = fin;
+        } else {
+            EpiResid<0> r{x, rd, bp, gate, 0, 0, 0, M, mask};
+            LNF(gemm3_resid(ops3(SplitBuf{a_hi, a_lo}, rowmap_plain(K), wp, M, prec), gate ? 2 : 0, r, prec, st));
+            if (rms) {
+                LNF(launch_rmsnorm(x, rd, nullptr, y.hi, y.lo, rd, M, D, eps, nscale, st));
+            } else {
+                LNF(launch_ln_modulate(x, nullptr, y.hi, y.lo, M, D, eps, shift, nscale, 0, 0, 0, M, st));
+            }
+        }
+        LNF(gemm3_swiglu(ops3(y, rd, w13, M, prec), sw, prec, st));
+        LNF(launch_split_to_f32(ffh.hi, ffh.lo, h, (long)M * F, st));
+        if (c_out) {   // the row shift as the consumer left it for the next producer (0 where the step has none)
+            if (sw.fold.cshift) LNF(hipMemcpyAsync(c_out, sw.fold.cshift, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
+            else LNF(hipMemsetAsync(c_out, 0, (size_t)M * 4, st));
+        }
+#undef LNF
+        return hipSuccess;
+    };
+    if (e == hipSuccess) e = run();
+    (void)hipStreamSynchronize(st);
+    for (void* p : bufs) (void)hipFree(p);
+    return e == hipSuccess ? 0 : fail_hip(e, "test_ln_fold");
 }
 
 int Engine::test_swiglu(hipStream_t st, const float* A, const float* W1, const float* W3, const float* b1,

@@ -187,6 +187,10 @@ class Engine {
     int bench_gemm(int M, int N, int K, int epi, int split, int cfg, int iters, int ver, float* avg_us);
     int test_gemm3(hipStream_t st, const float* A, const float* W, const float* bias, int M, int N, int K, int act,
                    int split, int cfg, float* C);
+    int test_ln_fold(hipStream_t st, const float* A, const float* Wp, const float* bp, const float* gate, const uint8_t* mask,
+                     const float* nscale, const float* shift, const float* W1, const float* W3, const float* b1, const float* b3,
+                     int M, int K, int D, int F, float eps, int rms, int prec, int fold, float* x, float* h,
+                     float* c_out);
 
     // fp16 range guard: per-site count of values that fp16 producers clamped to +-65504 since the last reset (device counters,
     // common.hpp sat_note) + the static part: codec FFN blocks whose fused kernels' hidden / input bound could not be certified
@@ -294,6 +298,10 @@ class Engine {
     bool ln_fold_tp_ = false;
     bool ln_fold_now() const { return ln_fold_ && (tuning_ == TUNE_LATENCY || ln_fold_tp_); }
     bool attn_epi_ = true;   // ... written by the QKVG GEMM's own epilogue (gemm3 EpiQKV); false (SMTTS_ATTN_EPI=0): fp32 projection + qkv_pack kernel
+    // THE fold predicates: every buffer and launch of the LN-fold (tables, row partials, row shifts) follows them.  The QKV consumer is
+    // the attention epilogue (EpiQKV), so no epilogue attention, no fold
+    bool fold_epi_on() const { return ln_fold_now() && attn_img_ && attn_epi_; }
+    bool dit_fold_on(long rows) const;   // the fused sampler's DiT blocks, rows = batch rows (engine.hip)
     Profiler prof_;
     bool prof_on_ = false;
     bool finalized_ = false;

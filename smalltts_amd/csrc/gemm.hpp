@@ -219,7 +219,7 @@ struct RowCtx {
     int aux[16];
     unsigned valid;  // bit r: row in range (and not masked out, where the epilogue skips masked rows)
     int mb;          // first row of the lane's 16 (LN-fold producer: where the row partials go)
-    float mu[16], rs[16];   // LN-fold consumers: mean / rstd of the lane's rows (unused, hence no registers, everywhere else)
+    float mu[16], rs[16];   // LN-fold consumers: mean / rstd of the lane's rows; producer (EpiResidLN): mu = row shift c (unused, hence no registers, everywhere else)
 };
 
 // ------------------------------------------------------------------------------------------
@@ -230,6 +230,10 @@ struct RowCtx {
 // row and 32-column group, the partial sums (sum x, sum x^2); the CONSUMER (EpiQKV / EpiSwiGLU) reduces a row's NP partials in a
 // fixed order when its workgroup starts (gemm3_kernel -> an LDS table of (mu, rstd) per tile row) and applies
 //   rstd (acc - mu wc[n]) + wsh[n] + b[n],     wc = W (1 + scale),  wsh = W shift
+// The producer images and sums the row SHIFTED by a per-row constant c close to its mean, (x - c) (1 + scale): LayerNorm does not see
+// c, and without it both subtractions above cancel catastrophically on rows whose |mean| is large against their spread (at f16 the
+// error grows linearly with |mean| / std; a constant row came out as rstd = 1 / sqrt(eps) times the rounding of its image).  c is
+// written by the launch in front of the chain (ln_modulate: the row mean) and advanced by each consumer (c += mu of the shifted row).
 // with the two per-(step, block, site) vectors from fold_vectors_kernel (kernels.hip: one launch per sampler call, t is shared by
 // the batch).  Deterministic: fixed butterfly in the producer, fixed order in the consumer.
 // ------------------------------------------------------------------------------------------
@@ -243,6 +247,8 @@ struct LnFoldIn {
                                    //    only scales by rstd = 1 / sqrt(mean x^2 + eps) — no mean, no vectors
     const float* lstat = nullptr;  // set by the kernel: LDS table [BM][2] = (mu, rstd) of the tile's rows
     int m0 = 0;                    // set by the kernel: first row of the tile
+    float* cshift = nullptr;       // [M] the producer's row shift c (LayerNorm only, else null): the n-tile-0 workgroup adds the
+                                   //    row's mu to it, so that the NEXT producer images the row around its current mean
 };
 template <class E, class = void>
 struct epi_small_n { static constexpr bool value = false; };   // epilogues of the DiT's N = 960 residual projections: extra tile shapes / ring depths are instantiated for them only
@@ -515,7 +521,8 @@ struct EpiResid {
 
 // LN-fold producer: the gated residual of the DiT's N = 960 projections (dit.py:198,201), all batch rows sharing ONE modulation row
 // (the fused sampler: t is shared), followed by what the next AdaLN'd GEMM needs instead of a norm launch (LnFoldIn):
-//   x[m][n] += mask(m) gate[n] (acc + bias[n]);   y[m][n] = fmt(x[m][n] (1 + nscale[n]));   part[m][n / 32] = (sum_n x, sum_n x^2)
+//   x[m][n] += mask(m) gate[n] (acc + bias[n]);   y[m][n] = fmt((x[m][n] - c[m]) (1 + nscale[n]));
+//   part[m][n / 32] = (sum_n x - c[m], sum_n (x - c[m])^2)                   (c = cshift, LnFoldIn; 0 when null: the RMSNorm fold)
 // Masked rows keep x but still get their image row and partials.  N % 32 == 0 (every lane of a 32-column group takes part in the
 // group's butterfly).
 template <int W>   // one reduce-scatter step: the lane keeps W of its 2 W values and adds the partner lane's other half (static indices only)
@@ -545,10 +552,22 @@ struct EpiResidLN {
     float* part;             // [M][NP][2]
     int NP;
     int rms = 0;             // 1: the image is x nscale (RMSNorm weight), not x (1 + nscale)
+    const float* cshift = nullptr;   // [M] row shift c (LnFoldIn::cshift); null: 0
     __device__ __forceinline__ void rows(int, int mb, int M, RowCtx& rc) const {
         rc.valid = 0;
         rc.mb = mb;
         int mk[16];
+        if (cshift) {   // (requested with the mask bytes; settled with the residual loads in col(), in front of the first store: no
+                        // wait of their own — the FF2 producer has no mask bytes to share one with)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int m = epi_row(mb, r);
+                rc.mu[r] = cshift[m < M ? m : 0];
+            }
+        } else {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) rc.mu[r] = 0.f;
+        }
         epi_row_masks(rowmask, mb, M, mk);
         EPI_STAMP(154);   // mask bytes landed
 #pragma unroll
@@ -566,17 +585,21 @@ struct EpiResidLN {
         float xv[16];
 #pragma unroll
         for (int r = 0; r < 16; ++r) xv[r] = x[rc.off[r] + n];   // (rows past M: row 0's, unused)
+        float cv[16];
+#pragma unroll
+        for (int r = 0; r < 16; ++r) cv[r] = rc.mu[r];
         epi_settle(b); epi_settle(g); epi_settle(s1);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) epi_settle(xv[r]);
-        EPI_STAMP(155);   // residual / vector loads landed
+        for (int r = 0; r < 16; ++r) { epi_settle(xv[r]); epi_settle(cv[r]); }
+        EPI_STAMP(155);   // residual / vector loads (and row shifts) landed
         float v[32];
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
             const float xn = rc.aux[r] ? fmaf(g, acc[r] + b, xv[r]) : xv[r];
             if (rc.aux[r]) x[rc.off[r] + n] = xn;
-            v[2 * r] = xn;
-            v[2 * r + 1] = xn * xn;
+            const float xs = xn - cv[r];
+            v[2 * r] = xs;
+            v[2 * r + 1] = xs * xs;
         }
         if (sm_is_f16(ylo)) {   // (one format decision per column; the clamp count goes out once, behind the stores)
             unsigned sat = 0;

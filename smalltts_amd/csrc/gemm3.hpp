@@ -220,7 +220,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm3_kernel(Gemm3Operands g, Epi
         epi.fold.m0 = m0;
         if (epi.fold.part && tid < BM) {
             int m = m0 + tid;
-            m = m < g.M ? m : g.M - 1;
+            const bool live = m < g.M;
+            m = live ? m : g.M - 1;
             const float4* p = reinterpret_cast<const float4*>(epi.fold.part + (long)m * epi.fold.NP * 2);
             float s1 = 0.f, s2 = 0.f;
 #pragma unroll 5
@@ -233,6 +234,8 @@ __global__ __launch_bounds__(WM* WN * 64) void gemm3_kernel(Gemm3Operands g, Epi
             const float var = fmaf(-mu, mu, s2 * epi.fold.inv_c);
             lstat[2 * tid] = mu;
             lstat[2 * tid + 1] = 1.0f / sqrtf((var > 0.f ? var : 0.f) + epi.fold.eps);
+            // the row's shift follows its mean (LnFoldIn::cshift): one writer per row, nobody else in this launch reads it
+            if (epi.fold.cshift && n0 == 0 && z == 0 && live) epi.fold.cshift[m] += mu;
         }
     }
 

@@ -37,6 +37,7 @@ hipError_t gemm3_qkv(const Gemm3Operands& g_in, const EpiQKV& p, int split, hipS
                  (split == 3 ? 4.0 : 2.0) * ((double)g.M * g.K + (double)g.N * g.K) + (p.prec == PREC_BF16X3 ? 4.0 : 2.0) * g.M * (double)g.N,
                  gemm_bytes8d(4 * p.H * p.dh, g.K, 1));
     if (p.fold.part) {   // LN-fold consumer: its own instantiations
+        if (p.fold.NP % 2) return hipErrorInvalidValue;   // (the partials are reduced in pairs, gemm3.hpp)
         const EpiQKVFold q{p.bias, p.qw, p.kw, p.rope_cos, p.rope_sin, p.eps, p.q_scale, p.rot_dim, p.prec, p.q, p.q_lo, p.k, p.k_lo, p.vt, p.vt_lo,
                            p.g, p.g_lo, p.Nseq, p.H, p.dh, p.HW, p.Np, p.fold};
         return qkv_split(g, q, split, big, deep, st);

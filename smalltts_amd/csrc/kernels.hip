@@ -17,7 +17,8 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const float* __restric
                                                           bf16_t* __restrict__ yhi, bf16_t* __restrict__ ylo, int M,
                                                           int C, float eps, const float* __restrict__ shift,
                                                           const float* __restrict__ scale, long mod_ld,
-                                                          int mod_row0, int mod_rstride, int rpb) {
+                                                          int mod_row0, int mod_rstride, int rpb,
+                                                          float* __restrict__ mean_out) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (row >= M) return;
@@ -66,16 +67,17 @@ __global__ __launch_bounds__(256) void ln_modulate_kernel(const float* __restric
             else reinterpret_cast<float4*>(y + (long)row * C)[c] = o;
         }
     }
+    if (mean_out && lane == 0) mean_out[row] = mean;
 }
 
 hipError_t launch_ln_modulate(const float* x, float* y, bf16_t* yhi, bf16_t* ylo, int M, int C, float eps,
                               const float* shift, const float* scale, long mod_ld, int mod_row0, int mod_rstride,
-                              int rows_per_batch, hipStream_t st) {
+                              int rows_per_batch, hipStream_t st, float* mean_out) {
     if (C > 1024 || C % 4 || mod_ld % 4) return hipErrorInvalidValue;
     ProfScope ps(st, "ln_modulate", 8.0 * M * C, 8.0 * M * C);
     dim3 grid((M + 3) / 4), block(256);
     hipLaunchKernelGGL(ln_modulate_kernel<4>, grid, block, 0, st, x, y, yhi, ylo, M, C, eps, shift, scale, mod_ld,
-                       mod_row0, mod_rstride, rows_per_batch);
+                       mod_row0, mod_rstride, rows_per_batch, mean_out);
     LAUNCH_CHECK();
 }
 

@@ -8,7 +8,7 @@
 // Output: fp32 `y`, or (when yhi != null) the split bf16 pair yhi/ylo that feeds gemm3 directly.
 hipError_t launch_ln_modulate(const float* x, float* y, bf16_t* yhi, bf16_t* ylo, int M, int C, float eps,
                               const float* shift, const float* scale, long mod_ld, int mod_row0, int mod_rstride,
-                              int rows_per_batch, hipStream_t st);
+                              int rows_per_batch, hipStream_t st, float* mean_out = nullptr);   // mean_out [M]: the row means (may be null)
 
 // y[m][c] = x[m][c] * rsqrt(mean(x[m][:]^2) + eps) * w[c]   (reference dit.py:42-53, 1-D weight).
 // Rows are addressed through RowMaps so padded codec images can be normalised in place of a copy.
@@ -84,7 +84,7 @@ struct CrossPackArgs {
     int prec, L, B, H, dh, dhp, R, P, Rp, Cp;
 };
 hipError_t launch_cross_pack(const CrossPackArgs& p, hipStream_t st);
-// out[i] = hi[i] + lo[i]  (a split bf16 pair back to fp32: test hooks)
+// out[i] = hi[i] + lo[i]  (an operand image back to fp32: test hooks; lo in the format encoding of common.hpp: split pair, fp16 tag or null = bf16)
 hipError_t launch_split_to_f32(const bf16_t* hi, const bf16_t* lo, float* out, long n, hipStream_t st);
 
 // out[m][:] = table[ids[m]][:]  (phonemes.py:201)

@@ -504,6 +504,25 @@ class HipEngine:
                                            _p(out)), "test_gemm3")
         return out
 
+    def test_ln_fold(self, x, A, Wp, scale, W1, W3, shift=None, bp=None, gate=None, row_mask=None, b1=None, b3=None,
+                     rms=False, fold=True, precision="f16", eps=1e-6, return_shift=False):
+        """One LN-fold step (include/smalltts_hip.h smtts_test_ln_fold): x += row_mask gate (A Wp^T + bp), then the LayerNorm
+        (1 + scale) + shift (rms=False) or RMSNorm * scale (rms=True) of x into [W1 | W3] and SwiGLU.  fold=True: the producer /
+        consumer epilogues; False: the norm launches.  Returns (updated x [M, D], hidden [M, F]) as fp32, and with return_shift=True
+        the row shift the consumer leaves for the next producer [M] (LayerNorm fold; zeros otherwise); x itself is not modified."""
+        f = lambda t: None if t is None else self._dev(t, torch.float32)
+        A, Wp, scale, W1, W3, shift, bp, gate, b1, b3 = map(f, (A, Wp, scale, W1, W3, shift, bp, gate, b1, b3))
+        x = self._dev(x, torch.float32).clone()
+        row_mask = None if row_mask is None else self._dev(row_mask, torch.uint8)
+        M, K = A.shape
+        D, F = Wp.shape[0], W1.shape[0]
+        hid = torch.empty(M, F, device=self.device)
+        shift_out = torch.empty(M, device=self.device) if return_shift else None
+        self._ck(self.lib.smtts_test_ln_fold(self.h, self._stream(), _p(A), _p(Wp), _p(bp), _p(gate), _p(row_mask), _p(scale),
+                                             _p(shift), _p(W1), _p(W3), _p(b1), _p(b3), M, K, D, F, eps, int(bool(rms)),
+                                             PRECISION[precision], int(bool(fold)), _p(x), _p(hid), _p(shift_out)), "test_ln_fold")
+        return (x, hid, shift_out) if return_shift else (x, hid)
+
     def test_swiglu(self, A, W1, W3, b1=None, b3=None, split=3):
         A, W1, W3 = (self._dev(x, torch.float32) for x in (A, W1, W3))
         b1 = None if b1 is None else self._dev(b1, torch.float32)
