@@ -49,9 +49,9 @@ int smtts_create(int device_id, smtts_handle* out);
 int smtts_destroy(smtts_handle h);
 const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation error */
 const char* smtts_version(void);
-/* bumped on every signature / default change: 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
+/* bumped on every signature / default change: 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
-#define SMTTS_ABI_VERSION 6
+#define SMTTS_ABI_VERSION 7
 int smtts_abi_version(void);
 
 /* ---- weights (replaces the ONNX initialisers; names/shapes = DiTModel.state_dict(),
@@ -185,6 +185,18 @@ int smtts_test_ln_fold(smtts_handle h, void* stream, const float* A, const float
                        const uint8_t* row_mask, const float* scale, const float* shift, const float* W1, const float* W3,
                        const float* b1, const float* b3, int M, int K, int D, int F, float eps, int rms, int prec, int fold,
                        float* x, float* hid, float* shift_out);
+/* one codec stage of the finalized decoder (part 1) or encoder (part 2), through the same code as smtts_codec_decode / _encode and
+ * a workspace planned for the smallest whole call that contains this stage geometry (so the same kernels run).
+ *   what: 1 = the stem (stage must be 0), 2 = the resampling into `stage` (stage > 0), 4 = the stage's blocks (chain or one by one,
+ *   as the product decides), 8 = final norm (if loaded) + head (stage must be the last); bits may be combined as a run in that order.
+ *   x: device fp32, channels-last, unpadded (B, T_in, C_in): C_in = latent (decoder stem), 1 (encoder stem: T_in samples), the
+ *   previous stage's C (resampling) or the stage's C; encoder resampling needs T_in % ratio == 0.
+ *   out: (B, T_out, C_out) (decoder head: C_out = 1, the audio); out == NULL only reports T_out / C_out.
+ * Allocates its own padded images and workspace (filled with NaN first: a kernel that reads what nobody wrote shows up) and
+ * synchronises the stream.  Refuses a bad part / stage / `what` / C_in or B*T <= 0
+ * with an error and no launch. */
+int smtts_test_codec_stage(smtts_handle h, void* stream, int part, int stage, int what, const float* x, int B, int T_in, int C_in,
+                           float* out, int* T_out, int* C_out);
 /* codec blocks: 1 (default) = fused mixer and fused FFN kernels (C <= 256), 0 = separate norm / conv / two-GEMM path */
 int smtts_test_set_fused_ffn(smtts_handle h, int on);
 /* fused sampler: 1 (default) = the AdaLN between two DiT block GEMMs folded into their epilogues (reference dit.py:19-25,197-212

@@ -173,6 +173,10 @@ int smtts_test_ln_fold(smtts_handle h, void* stream, const float* A, const float
     return E.test_ln_fold(ST(stream), A, Wp, bp, gate, row_mask, scale, shift, W1, W3, b1, b3, M, K, D, F, eps, rms, prec, fold, x, hid,
                           shift_out);
 }
+int smtts_test_codec_stage(smtts_handle h, void* stream, int part, int stage, int what, const float* x, int B, int T_in, int C_in,
+                           float* out, int* T_out, int* C_out) { NULLCHK;
+    return E.test_codec_stage(ST(stream), part, stage, what, x, B, T_in, C_in, out, T_out, C_out);
+}
 int smtts_test_set_fused_ffn(smtts_handle h, int on) { NULLCHK; E.set_fused_ffn(on != 0); return 0; }
 int smtts_test_set_ln_fold(smtts_handle h, int on) { NULLCHK; E.set_ln_fold(on != 0); return 0; }
 int smtts_test_set_attention_mfma(smtts_handle h, int mode) { NULLCHK;   // 0: fp32 projection + qk_prep + the fp32 VALU reference kernel; else (default): producer-written operand images + the DMA / MFMA kernel

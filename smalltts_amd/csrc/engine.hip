@@ -1722,236 +1722,345 @@ int Engine::codec_block(hipStream_t st, const CodecBlockW& w, float** xp, float*
     return 0;
 }
 
-namespace {
-struct CodecWs {
+// Workspace of one codec call.  Every caller plans it through codec_plan() for the WHOLE call the work belongs to: the gates of
+// codec_block, conv_small_m and the resampling paths read the plan's sizes, so a part of a call (smtts_test_codec_stage) runs the
+// kernels of the whole call only if it plans the same way.
+struct Engine::CodecWs {
     float *xa, *xb, *nb, *lat;
     bf16_t *n2hi, *n2lo, *hhi, *hlo;
-    void plan(Bump& b, size_t max_img, size_t max_rows_c, size_t max_hidden, size_t lat_elems) {
-        xa = b.take<float>(max_img);
-        xb = b.take<float>(max_img);
-        nb = b.take<float>(max_img);
-        n2hi = b.take<bf16_t>(max_rows_c);
-        n2lo = b.take<bf16_t>(max_rows_c);
-        hhi = b.take<bf16_t>(max_hidden);
-        hlo = b.take<bf16_t>(max_hidden);
-        lat = b.take<float>(lat_elems);
+    size_t max_img, max_hid;
+    void plan(Bump& b, const CodecPlan& p) {
+        max_img = p.max_img;
+        max_hid = p.max_hid;
+        xa = b.take<float>(p.max_img);
+        xb = b.take<float>(p.max_img);
+        nb = b.take<float>(p.max_img);
+        n2hi = b.take<bf16_t>(p.max_img);
+        n2lo = b.take<bf16_t>(p.max_img);
+        hhi = b.take<bf16_t>(p.max_hid);
+        hlo = b.take<bf16_t>(p.max_hid);
+        lat = b.take<float>(p.lat);
     }
 };
-}  // namespace
 
-size_t Engine::decode_ws_bytes(int B, int T) const {
+Engine::CodecPlan Engine::codec_plan(bool decoder, int B, long T) const {
+    // decoder: T latent frames; encoder: T audio samples
     const CodecSpecC& s = cspec_;
     const int S = s.n_ratios + 1;
-    size_t max_img = 0, max_hid = 0;
+    CodecPlan p;
     long Ti = T;
     for (int i = 0; i < S; ++i) {
-        if (i > 0) Ti *= s.ratios[i - 1];
-        size_t C = (size_t)s.n_filters << (S - 1 - i);
+        if (i > 0) Ti = decoder ? Ti * s.ratios[i - 1] : Ti / s.ratios[s.n_ratios - i];
+        size_t C = (size_t)s.n_filters << (decoder ? S - 1 - i : i);
         size_t img = (size_t)B * (kCodecPad + Ti) * C;
-        max_img = img > max_img ? img : max_img;
+        p.max_img = img > p.max_img ? img : p.max_img;
         size_t hid = (size_t)B * Ti * C * s.ffn_mult;
-        max_hid = hid > max_hid ? hid : max_hid;
+        p.max_hid = hid > p.max_hid ? hid : p.max_hid;
     }
+    p.lat = decoder ? (size_t)B * (kCodecPad + T) * s.latent_dim : 1;
+    return p;
+}
+
+size_t Engine::codec_ws_bytes(const CodecPlan& p) const {
     Bump b(nullptr);
     CodecWs w;
-    w.plan(b, max_img, max_img, max_hid, (size_t)B * (kCodecPad + T) * s.latent_dim);
+    w.plan(b, p);
     return b.off + 256;
+}
+
+size_t Engine::decode_ws_bytes(int B, int T) const { return codec_ws_bytes(codec_plan(true, B, T)); }
+
+// latent image with causal zero pad, then stem conv k (as GEMM over K*latent contiguous floats) into w.xa; pads of the three
+// images at the stage-0 geometry
+int Engine::decode_stem(hipStream_t st, const CodecWs& w, const float* latents, int B, int T) {
+    const int pad = kCodecPad, Kc = cspec_.kernel, L = cspec_.latent_dim, C = dec_.stages[0].C;
+    const int pcv = prec_[SITE_CODEC_CONV];
+    const int pcv3 = pcv == PREC_F16 || pcv == PREC_F16X2 ? PREC_BF16X3 : pcv;  // the fp32-A kernel has no fp16 variant
+    HIPC(launch_zero_pad_frames(w.lat, B, T, L, pad, st));
+    HIPC(hipMemcpy2DAsync(w.lat + (long)pad * L, (size_t)(pad + T) * L * 4, latents, (size_t)T * L * 4, (size_t)T * L * 4, B,
+                          hipMemcpyDeviceToDevice, st));
+    HIPC(launch_zero_pad_frames3(w.xa, w.xb, w.nb, B, T, C, pad, st));
+    RowMap am = rowmap_batched(L, T, (long)(pad + T) * L, (long)(pad - (Kc - 1)) * L);
+    RowMap om = rowmap_batched(C, T, (long)(pad + T) * C, (long)pad * C);
+    HIPC(gemm_store(ops(w.lat, am, dec_.stem, B * T), ACT_NONE, store_to(w.xa, om, dec_.stem_b), 1, pcv3, st));
+    return 0;
+}
+
+// decoder stage i: the ConvTranspose into it (i > 0, what & 2), then its blocks (what & 4).  *x holds the image of (*Ti, *C) frames on
+// entry and on return; *xn is the ping-pong partner
+int Engine::decode_stage(hipStream_t st, const CodecWs& w, int i, int what, float** xp, float** xnp, int B, int* Tip, int* Cp) {
+    static const char* kDecTags[] = {"dec.s0", "dec.s1", "dec.s2", "dec.s3", "dec.s4", "dec.s5", "dec.s6", "dec.s7"};
+    ProfTag ptag(kDecTags[i < 8 ? i : 7]);
+    const int pad = kCodecPad, pcv = prec_[SITE_CODEC_CONV];
+    const int pcv3 = pcv == PREC_F16 || pcv == PREC_F16X2 ? PREC_BF16X3 : pcv;  // the fp32-A and streaming-upsample kernels have no fp16 variant
+    const CodecStageW& sg = dec_.stages[i];
+    float* x = *xp;
+    float* xn = *xnp;
+    int Ti = *Tip, C = *Cp;
+    if (i > 0 && (what & 2)) {
+        // ConvTranspose1d(k = 2r, stride r), causal trim: rows (x[t-1], x[t]) -> r output frames
+        const int r = sg.r, Cn = sg.C, Tn = Ti * r;
+        RowMap am = rowmap_batched(C, Ti, (long)(pad + Ti) * C, (long)(pad - 1) * C);
+        RowMap om = rowmap_batched((long)r * Cn, Ti, (long)(pad + Tn) * Cn, (long)pad * Cn);
+        if (fused_ffn_ && codec_upsample_wave_ok(sg.resample.K, sg.resample.N) && sg.resample.K == 2 * C && sg.resample.N == r * Cn)
+            HIPC(launch_codec_upsample_wave(x, am, sg.resample.hi, sg.resample.lo, sg.resample.K, sg.resample_bias, xn, om,
+                                            B * Ti, sg.resample.K, sg.resample.N, pcv3, st));
+        else if (pcv == PREC_F16X2 && sg.resample.l16 && sg.resample.K % 64 == 0 && sg.resample.K >= x2_mink_ && sg.resample.K <= x2_maxk_ &&
+                 C % 8 == 0 && (size_t)B * (pad + Ti) * C <= w.max_img) {
+            // two-pass fp16 product: the image once as ONE fp16 array (pads included: the causal zeros), the weights as an fp16
+            // hi + lo pair — A W_lo + A W_hi on the DMA-ring GEMM instead of three split-bf16 passes on the fp32-A kernel
+            HIPC(launch_to_split(x, rowmap_plain(C), w.n2hi, sm_lo_for(PREC_F16, nullptr, satp(SITE_CODEC_CONV)), rowmap_plain(C), B * (pad + Ti), C, st));
+            Gemm3Operands g3 = ops3(SplitBuf{w.n2hi, w.n2lo}, am, sg.resample, B * Ti, PREC_F16);
+            g3.Wlo = sg.resample.l16;
+            HIPC(gemm3_store_x2(g3, store_to(xn, om, sg.resample_bias), st));
+        } else if (fused_ffn_ && sg.resample.K % 64 == 0 && sg.resample.K >= up_g3_mink_ && C % 8 == 0 && (size_t)B * (pad + Ti) * C <= w.max_img) {
+            const int pg = pcv == PREC_F16X2 ? PREC_BF16X3 : pcv;   // (f16x2 outside its K range: split-bf16)
+            // widest stages (K >= 2048; measured: 215 -> 148 us and 216 -> 193 us, no gain at K <= 1024): split the image once (pads included: they are the causal zeros) and run the DMA-ring GEMM on
+            // the overlapping rows of the split pair (n2 is free between blocks)
+            SplitBuf xs{w.n2hi, w.n2lo};
+            HIPC(launch_to_split(x, rowmap_plain(C), xs.hi, xs.as(pg, satp(SITE_CODEC_CONV)).lo, rowmap_plain(C), B * (pad + Ti), C, st));
+            HIPC(gemm3_store(ops3(xs, am, sg.resample, B * Ti, pg), ACT_NONE, store_to(xn, om, sg.resample_bias), 1, pg, st));
+        } else
+            HIPC(gemm_store(ops(x, am, sg.resample, B * Ti), ACT_NONE, store_to(xn, om, sg.resample_bias), 1, pcv3, st));
+        float* t = x; x = xn; xn = t;
+        Ti = Tn;
+        C = Cn;
+        // zero pads of the three images at the new geometry, in one launch BEHIND the product: it writes data rows only, and its
+        // input (now the ping-pong partner) is free to be overwritten from here on
+        HIPC(launch_zero_pad_frames3(x, xn, w.nb, B, Ti, C, pad, st));
+    }
+    *Tip = Ti;
+    *Cp = C;
+    if (what & 4) {
+        if (const int ch = codec_stage_chain(st, sg, &x, &xn, B, Ti, C)) {   // > 0: the whole stage went out as one launch
+            if (ch < 0) return 1;
+        } else {
+            for (const CodecBlockW& b : sg.blocks)
+                if (codec_block(st, b, &x, &xn, w.nb, w.n2hi, w.n2lo, w.hhi, w.hlo, B, Ti, C, w.max_img)) return 1;
+        }
+    }
+    *xp = x;
+    *xnp = xn;
+    return 0;
+}
+
+// final RMSNorm (if loaded) + head conv: the image of the last stage -> (B, Ti) audio
+int Engine::decode_head(hipStream_t st, const CodecWs& w, const float* x, int B, int Ti, int C, float* audio) {
+    const int pad = kCodecPad;
+    if (dec_.final_norm_w) {   // out of place into the (zero-padded) scratch image: the head conv reads K - 1 pad frames
+        const RowMap img = rowmap_batched(C, Ti, (long)(pad + Ti) * C, (long)pad * C);
+        HIPC(launch_rmsnorm(x, img, w.nb, nullptr, nullptr, img, B * Ti, C, cspec_.eps, dec_.final_norm_w, st));
+        x = w.nb;
+    }
+    HIPC(launch_head_conv(x, dec_.head_w, dec_.head_b_host, audio, B, Ti, C, cspec_.kernel, pad, st));
+    return 0;
 }
 
 int Engine::codec_decode(hipStream_t st, const float* latents, int B, int T, float* audio, void* ws, size_t ws_bytes) {
     DeepScope deep_scope(gemm_deep_);
     PersistScope persist_scope(persist_cus_);
     if (!dec_.ready) return fail("codec_decode: decoder weights not finalized");
-    if (ws_bytes < decode_ws_bytes(B, T)) return fail("codec_decode: workspace too small");
+    const CodecPlan plan = codec_plan(true, B, T);
+    if (ws_bytes < codec_ws_bytes(plan)) return fail("codec_decode: workspace too small");
     HIPC(hipSetDevice(device_));
-    const CodecSpecC& s = cspec_;
-    const int S = s.n_ratios + 1, pad = kCodecPad, Kc = s.kernel, L = s.latent_dim;
-    const int pcv = prec_[SITE_CODEC_CONV];
-    const int pcv3 = pcv == PREC_F16 || pcv == PREC_F16X2 ? PREC_BF16X3 : pcv;  // the fp32-A and streaming-upsample kernels have no fp16 variant
-    // re-derive the plan
-    size_t max_img = 0, max_hid = 0;
-    {
-        long Ti = T;
-        for (int i = 0; i < S; ++i) {
-            if (i > 0) Ti *= s.ratios[i - 1];
-            size_t C = (size_t)s.n_filters << (S - 1 - i);
-            size_t img = (size_t)B * (pad + Ti) * C;
-            max_img = img > max_img ? img : max_img;
-            size_t hid = (size_t)B * Ti * C * s.ffn_mult;
-            max_hid = hid > max_hid ? hid : max_hid;
-        }
-    }
     Bump bump(ws);
     CodecWs w;
-    w.plan(bump, max_img, max_img, max_hid, (size_t)B * (pad + T) * L);
-
-    // latent image with causal zero pad, then stem conv k (as GEMM over K*latent contiguous floats)
-    HIPC(launch_zero_pad_frames(w.lat, B, T, L, pad, st));
-    HIPC(hipMemcpy2DAsync(w.lat + (long)pad * L, (size_t)(pad + T) * L * 4, latents, (size_t)T * L * 4, (size_t)T * L * 4, B,
-                          hipMemcpyDeviceToDevice, st));
+    w.plan(bump, plan);
+    if (decode_stem(st, w, latents, B, T)) return 1;
     float* x = w.xa;
     float* xn = w.xb;
-    int Ti = T;
-    int C = dec_.stages[0].C;
-    HIPC(launch_zero_pad_frames3(x, xn, w.nb, B, Ti, C, pad, st));
-    {
-        RowMap am = rowmap_batched(L, Ti, (long)(pad + Ti) * L, (long)(pad - (Kc - 1)) * L);
-        RowMap om = rowmap_batched(C, Ti, (long)(pad + Ti) * C, (long)pad * C);
-        HIPC(gemm_store(ops(w.lat, am, dec_.stem, B * Ti), ACT_NONE, store_to(x, om, dec_.stem_b), 1, pcv3, st));
-    }
-    static const char* kDecTags[] = {"dec.s0", "dec.s1", "dec.s2", "dec.s3", "dec.s4", "dec.s5", "dec.s6", "dec.s7"};
-    for (int i = 0; i < S; ++i) {
-        ProfTag ptag(kDecTags[i < 8 ? i : 7]);
-        const CodecStageW& sg = dec_.stages[i];
-        if (i > 0) {
-            // ConvTranspose1d(k = 2r, stride r), causal trim: rows (x[t-1], x[t]) -> r output frames
-            const int r = sg.r, Cn = sg.C, Tn = Ti * r;
-            RowMap am = rowmap_batched(C, Ti, (long)(pad + Ti) * C, (long)(pad - 1) * C);
-            RowMap om = rowmap_batched((long)r * Cn, Ti, (long)(pad + Tn) * Cn, (long)pad * Cn);
-            if (fused_ffn_ && codec_upsample_wave_ok(sg.resample.K, sg.resample.N) && sg.resample.K == 2 * C && sg.resample.N == r * Cn)
-                HIPC(launch_codec_upsample_wave(x, am, sg.resample.hi, sg.resample.lo, sg.resample.K, sg.resample_bias, xn, om,
-                                                B * Ti, sg.resample.K, sg.resample.N, pcv3, st));
-            else if (pcv == PREC_F16X2 && sg.resample.l16 && sg.resample.K % 64 == 0 && sg.resample.K >= x2_mink_ && sg.resample.K <= x2_maxk_ &&
-                     C % 8 == 0 && (size_t)B * (pad + Ti) * C <= max_img) {
-                // two-pass fp16 product: the image once as ONE fp16 array (pads included: the causal zeros), the weights as an fp16
-                // hi + lo pair — A W_lo + A W_hi on the DMA-ring GEMM instead of three split-bf16 passes on the fp32-A kernel
-                HIPC(launch_to_split(x, rowmap_plain(C), w.n2hi, sm_lo_for(PREC_F16, nullptr, satp(SITE_CODEC_CONV)), rowmap_plain(C), B * (pad + Ti), C, st));
-                Gemm3Operands g3 = ops3(SplitBuf{w.n2hi, w.n2lo}, am, sg.resample, B * Ti, PREC_F16);
-                g3.Wlo = sg.resample.l16;
-                HIPC(gemm3_store_x2(g3, store_to(xn, om, sg.resample_bias), st));
-            } else if (fused_ffn_ && sg.resample.K % 64 == 0 && sg.resample.K >= up_g3_mink_ && C % 8 == 0 && (size_t)B * (pad + Ti) * C <= max_img) {
-                const int pg = pcv == PREC_F16X2 ? PREC_BF16X3 : pcv;   // (f16x2 outside its K range: split-bf16)
-                // widest stages (K >= 2048; measured: 215 -> 148 us and 216 -> 193 us, no gain at K <= 1024): split the image once (pads included: they are the causal zeros) and run the DMA-ring GEMM on
-                // the overlapping rows of the split pair (n2 is free between blocks)
-                SplitBuf xs{w.n2hi, w.n2lo};
-                HIPC(launch_to_split(x, rowmap_plain(C), xs.hi, xs.as(pg, satp(SITE_CODEC_CONV)).lo, rowmap_plain(C), B * (pad + Ti), C, st));
-                HIPC(gemm3_store(ops3(xs, am, sg.resample, B * Ti, pg), ACT_NONE, store_to(xn, om, sg.resample_bias), 1, pg, st));
-            } else
-                HIPC(gemm_store(ops(x, am, sg.resample, B * Ti), ACT_NONE, store_to(xn, om, sg.resample_bias), 1, pcv3, st));
-            float* t = x; x = xn; xn = t;
-            Ti = Tn;
-            C = Cn;
-            // zero pads of the three images at the new geometry, in one launch BEHIND the product: it writes data rows only, and its
-            // input (now the ping-pong partner) is free to be overwritten from here on
-            HIPC(launch_zero_pad_frames3(x, xn, w.nb, B, Ti, C, pad, st));
-        }
-        if (const int ch = codec_stage_chain(st, sg, &x, &xn, B, Ti, C)) {   // > 0: the whole stage went out as one launch
-            if (ch < 0) return 1;
-            continue;
-        }
-        for (const CodecBlockW& b : sg.blocks)
-            if (codec_block(st, b, &x, &xn, w.nb, w.n2hi, w.n2lo, w.hhi, w.hlo, B, Ti, C, max_img)) return 1;
-    }
-    if (dec_.final_norm_w) {   // out of place into the (zero-padded) scratch image: the head conv reads K - 1 pad frames
-        const RowMap img = rowmap_batched(C, Ti, (long)(pad + Ti) * C, (long)pad * C);
-        HIPC(launch_rmsnorm(x, img, w.nb, nullptr, nullptr, img, B * Ti, C, cspec_.eps, dec_.final_norm_w, st));
-        x = w.nb;
-    }
-    HIPC(launch_head_conv(x, dec_.head_w, dec_.head_b_host, audio, B, Ti, C, Kc, pad, st));
+    int Ti = T, C = dec_.stages[0].C;
+    for (int i = 0; i < cspec_.n_ratios + 1; ++i)
+        if (decode_stage(st, w, i, 2 | 4, &x, &xn, B, &Ti, &C)) return 1;
+    return decode_head(st, w, x, B, Ti, C, audio);
+}
+
+size_t Engine::encode_ws_bytes(int B, int S_) const { return codec_ws_bytes(codec_plan(false, B, S_)); }
+
+// The coarse end of the encoder on short references is a handful of rows against a long K (2-s references: the last strided
+// conv is 120 x 2048 x 16384, the head 120 x 64 x 14336): as row tiles alone that is 2-32 workgroups streaming 134 MB of
+// weights (374 / 254 us).  There: convert the (small) image once to the GEMM operand format — pads included, they are the
+// causal zeros — and run gemm3 over the overlapping rows as K slices + one reduce.  Returns 1 when it took the product, 0 when
+// the caller runs it, -1 on a launch error.
+int Engine::conv_small_m(hipStream_t st, const CodecWs& w, const float* img, long img_rows, int Cin, const RowMap& am, const PW& wt,
+                         const float* bias, float* out, const RowMap& om, int M) {
+    const int pcv = prec_[SITE_CODEC_CONV];
+    const int splits = (fused_ffn_ && wt.K >= 2048) ? small_m_splits(M, wt.K, 8, 4) : 1;
+    if (splits < 2 || wt.K % 64 || Cin % 4 || wt.N % 4 || (size_t)img_rows * Cin > w.max_img || (size_t)splits * M * wt.N * 2 > w.max_hid)
+        return 0;
+    SplitBuf xs{w.n2hi, w.n2lo};
+    float* part = reinterpret_cast<float*>(w.hhi);   // max_hid bf16 = max_hid / 2 floats
+    hipError_t e = launch_to_split(img, rowmap_plain(Cin), xs.hi, xs.as(pcv, satp(SITE_CODEC_CONV)).lo, rowmap_plain(Cin), (int)img_rows, Cin, st);
+    if (e == hipSuccess) e = gemm3_store_splitk(ops3(xs, am, wt, M, pcv), part, splits, pcv, bias, out, om, st);
+    if (e != hipSuccess) { fail_hip(e, "codec_encode: split-K conv"); return -1; }
+    return 1;
+}
+
+// encoder stem: (B, S) audio -> the stage-0 image in w.xa; pads of the three images at the stage-0 geometry
+int Engine::encode_stem(hipStream_t st, const CodecWs& w, const float* audio, int B, int S_) {
+    const int C = enc_.stages[0].C;
+    HIPC(launch_zero_pad_frames3(w.xa, w.xb, w.nb, B, S_, C, kCodecPad, st));
+    HIPC(launch_stem_conv1(audio, enc_.stem_w_raw, enc_.stem_b, w.xa, B, S_, C, cspec_.kernel, kCodecPad, st));
     return 0;
 }
 
-size_t Engine::encode_ws_bytes(int B, int S_) const {
-    const CodecSpecC& s = cspec_;
-    const int S = s.n_ratios + 1;
-    size_t max_img = 0, max_hid = 0;
-    long Ti = S_;
-    for (int i = 0; i < S; ++i) {
-        if (i > 0) Ti /= s.ratios[s.n_ratios - i];
-        size_t C = (size_t)s.n_filters << i;
-        size_t img = (size_t)B * (kCodecPad + Ti) * C;
-        max_img = img > max_img ? img : max_img;
-        size_t hid = (size_t)B * Ti * C * s.ffn_mult;
-        max_hid = hid > max_hid ? hid : max_hid;
-    }
-    Bump b(nullptr);
-    CodecWs w;
-    w.plan(b, max_img, max_img, max_hid, 1);
-    return b.off + 256;
-}
-
-int Engine::codec_encode(hipStream_t st, const float* audio, int B, int S_, float* latents, void* ws, size_t ws_bytes) {
-    DeepScope deep_scope(gemm_deep_);
-    PersistScope persist_scope(persist_cus_);
-    if (!enc_.ready) return fail("codec_encode: encoder weights not finalized");
-    if (ws_bytes < encode_ws_bytes(B, S_)) return fail("codec_encode: workspace too small");
-    HIPC(hipSetDevice(device_));
-    const CodecSpecC& s = cspec_;
-    const int S = s.n_ratios + 1, pad = kCodecPad, Kc = s.kernel;
-    const int pcv3 = prec_[SITE_CODEC_CONV] == PREC_F16 || prec_[SITE_CODEC_CONV] == PREC_F16X2 ? PREC_BF16X3 : prec_[SITE_CODEC_CONV];
-    size_t max_img = 0, max_hid = 0;
-    {
-        long Ti = S_;
-        for (int i = 0; i < S; ++i) {
-            if (i > 0) Ti /= s.ratios[s.n_ratios - i];
-            size_t C = (size_t)s.n_filters << i;
-            size_t img = (size_t)B * (pad + Ti) * C;
-            max_img = img > max_img ? img : max_img;
-            size_t hid = (size_t)B * Ti * C * s.ffn_mult;
-            max_hid = hid > max_hid ? hid : max_hid;
-        }
-    }
-    Bump bump(ws);
-    CodecWs w;
-    w.plan(bump, max_img, max_img, max_hid, 1);
-    float* x = w.xa;
-    float* xn = w.xb;
-    int Ti = S_;
-    int C = enc_.stages[0].C;
-    // The coarse end of the encoder on short references is a handful of rows against a long K (2-s references: the last strided
-    // conv is 120 x 2048 x 16384, the head 120 x 64 x 14336): as row tiles alone that is 2-32 workgroups streaming 134 MB of
-    // weights (374 / 254 us).  There: convert the (small) image once to the GEMM operand format — pads included, they are the
-    // causal zeros — and run gemm3 over the overlapping rows as K slices + one reduce.  Returns true when it took the product.
-    bool conv_err = false;
-    const int pcv = prec_[SITE_CODEC_CONV];
-    auto conv_small_m = [&](const float* img, long img_rows, int Cin, const RowMap& am, const PW& wt, const float* bias, float* out,
-                            const RowMap& om, int M) -> bool {
-        const int splits = (fused_ffn_ && wt.K >= 2048) ? small_m_splits(M, wt.K, 8, 4) : 1;
-        if (splits < 2 || wt.K % 64 || Cin % 4 || wt.N % 4 || (size_t)img_rows * Cin > max_img || (size_t)splits * M * wt.N * 2 > max_hid)
-            return false;
-        SplitBuf xs{w.n2hi, w.n2lo};
-        float* part = reinterpret_cast<float*>(w.hhi);   // max_hid bf16 = max_hid / 2 floats
-        hipError_t e = launch_to_split(img, rowmap_plain(Cin), xs.hi, xs.as(pcv, satp(SITE_CODEC_CONV)).lo, rowmap_plain(Cin), (int)img_rows, Cin, st);
-        if (e == hipSuccess) e = gemm3_store_splitk(ops3(xs, am, wt, M, pcv), part, splits, pcv, bias, out, om, st);
-        if (e != hipSuccess) { fail_hip(e, "codec_encode: split-K conv"); conv_err = true; }
-        return true;
-    };
-    HIPC(launch_zero_pad_frames3(x, xn, w.nb, B, Ti, C, pad, st));
-    HIPC(launch_stem_conv1(audio, enc_.stem_w_raw, enc_.stem_b, x, B, Ti, C, Kc, pad, st));
+// encoder stage i: the strided conv into it (i > 0, what & 2), then its blocks (what & 4); arguments as decode_stage
+int Engine::encode_stage(hipStream_t st, const CodecWs& w, int i, int what, float** xp, float** xnp, int B, int* Tip, int* Cp) {
     static const char* kEncTags[] = {"cenc.s0", "cenc.s1", "cenc.s2", "cenc.s3", "cenc.s4", "cenc.s5", "cenc.s6", "cenc.s7"};
-    for (int i = 0; i < S; ++i) {
-        ProfTag ptag(kEncTags[i < 8 ? i : 7]);
-        const CodecStageW& sg = enc_.stages[i];
-        if (i > 0) {
-            // Conv1d(k = 2r, stride r), causal left pad r: out[t] reads frames [(t-1) r, (t+1) r)
-            const int r = sg.r, Cn = sg.C, Tn = Ti / r;
-            RowMap am = rowmap_batched((long)r * C, Tn, (long)(pad + Ti) * C, (long)(pad - r) * C);
-            RowMap om = rowmap_batched(Cn, Tn, (long)(pad + Tn) * Cn, (long)pad * Cn);
-            if (!conv_small_m(x, (long)B * (pad + Ti), C, am, sg.resample, sg.resample_bias, xn, om, B * Tn))
-                HIPC(gemm_store(ops(x, am, sg.resample, B * Tn), ACT_NONE, store_to(xn, om, sg.resample_bias), 1, pcv3, st));
-            if (conv_err) return 1;
-            float* t = x; x = xn; xn = t;
-            Ti = Tn;
-            C = Cn;
-            HIPC(launch_zero_pad_frames3(x, xn, w.nb, B, Ti, C, pad, st));   // (behind the product, as in the decoder)
-        }
+    ProfTag ptag(kEncTags[i < 8 ? i : 7]);
+    const int pad = kCodecPad;
+    const int pcv3 = prec_[SITE_CODEC_CONV] == PREC_F16 || prec_[SITE_CODEC_CONV] == PREC_F16X2 ? PREC_BF16X3 : prec_[SITE_CODEC_CONV];
+    const CodecStageW& sg = enc_.stages[i];
+    float* x = *xp;
+    float* xn = *xnp;
+    int Ti = *Tip, C = *Cp;
+    if (i > 0 && (what & 2)) {
+        // Conv1d(k = 2r, stride r), causal left pad r: out[t] reads frames [(t-1) r, (t+1) r)
+        const int r = sg.r, Cn = sg.C, Tn = Ti / r;
+        RowMap am = rowmap_batched((long)r * C, Tn, (long)(pad + Ti) * C, (long)(pad - r) * C);
+        RowMap om = rowmap_batched(Cn, Tn, (long)(pad + Tn) * Cn, (long)pad * Cn);
+        const int took = conv_small_m(st, w, x, (long)B * (pad + Ti), C, am, sg.resample, sg.resample_bias, xn, om, B * Tn);
+        if (took < 0) return 1;
+        if (!took) HIPC(gemm_store(ops(x, am, sg.resample, B * Tn), ACT_NONE, store_to(xn, om, sg.resample_bias), 1, pcv3, st));
+        float* t = x; x = xn; xn = t;
+        Ti = Tn;
+        C = Cn;
+        HIPC(launch_zero_pad_frames3(x, xn, w.nb, B, Ti, C, pad, st));   // (behind the product, as in the decoder)
+    }
+    *Tip = Ti;
+    *Cp = C;
+    if (what & 4) {
         if (const int ch = codec_stage_chain(st, sg, &x, &xn, B, Ti, C)) {
             if (ch < 0) return 1;
-            continue;
+        } else {
+            for (const CodecBlockW& b : sg.blocks)
+                if (codec_block(st, b, &x, &xn, w.nb, w.n2hi, w.n2lo, w.hhi, w.hlo, B, Ti, C, w.max_img)) return 1;
         }
-        for (const CodecBlockW& b : sg.blocks)
-            if (codec_block(st, b, &x, &xn, w.nb, w.n2hi, w.n2lo, w.hhi, w.hlo, B, Ti, C, max_img)) return 1;
     }
+    *xp = x;
+    *xnp = xn;
+    return 0;
+}
+
+// final RMSNorm (if loaded) + head conv: the image of the last stage -> (B, Ti, latent)
+int Engine::encode_head(hipStream_t st, const CodecWs& w, const float* x, int B, int Ti, int C, float* latents) {
+    const int pad = kCodecPad, Kc = cspec_.kernel;
+    const int pcv3 = prec_[SITE_CODEC_CONV] == PREC_F16 || prec_[SITE_CODEC_CONV] == PREC_F16X2 ? PREC_BF16X3 : prec_[SITE_CODEC_CONV];
     if (enc_.final_norm_w) {
         const RowMap img = rowmap_batched(C, Ti, (long)(pad + Ti) * C, (long)pad * C);
         HIPC(launch_rmsnorm(x, img, w.nb, nullptr, nullptr, img, B * Ti, C, cspec_.eps, enc_.final_norm_w, st));
         x = w.nb;
     }
     RowMap am = rowmap_batched(C, Ti, (long)(pad + Ti) * C, (long)(pad - (Kc - 1)) * C);
-    if (!conv_small_m(x, (long)B * (pad + Ti), C, am, enc_.head, enc_.head_b, latents, rowmap_plain(s.latent_dim), B * Ti))
-        HIPC(gemm_store(ops(x, am, enc_.head, B * Ti), ACT_NONE, store_to(latents, rowmap_plain(s.latent_dim), enc_.head_b), 1,
+    const int took = conv_small_m(st, w, x, (long)B * (pad + Ti), C, am, enc_.head, enc_.head_b, latents, rowmap_plain(cspec_.latent_dim), B * Ti);
+    if (took < 0) return 1;
+    if (!took)
+        HIPC(gemm_store(ops(x, am, enc_.head, B * Ti), ACT_NONE, store_to(latents, rowmap_plain(cspec_.latent_dim), enc_.head_b), 1,
                         pcv3, st));
-    return conv_err ? 1 : 0;
+    return 0;
+}
+
+int Engine::codec_encode(hipStream_t st, const float* audio, int B, int S_, float* latents, void* ws, size_t ws_bytes) {
+    DeepScope deep_scope(gemm_deep_);
+    PersistScope persist_scope(persist_cus_);
+    if (!enc_.ready) return fail("codec_encode: encoder weights not finalized");
+    const CodecPlan plan = codec_plan(false, B, S_);
+    if (ws_bytes < codec_ws_bytes(plan)) return fail("codec_encode: workspace too small");
+    HIPC(hipSetDevice(device_));
+    Bump bump(ws);
+    CodecWs w;
+    w.plan(bump, plan);
+    if (encode_stem(st, w, audio, B, S_)) return 1;
+    float* x = w.xa;
+    float* xn = w.xb;
+    int Ti = S_, C = enc_.stages[0].C;
+    for (int i = 0; i < cspec_.n_ratios + 1; ++i)
+        if (encode_stage(st, w, i, 2 | 4, &x, &xn, B, &Ti, &C)) return 1;
+    return encode_head(st, w, x, B, Ti, C, latents);
+}
+
+// one codec stage (or a run of the pipeline's parts at one stage) through the functions above, on a workspace planned for the
+// smallest whole call that contains this stage geometry: what that call's dispatch would run on these frames, this runs
+int Engine::test_codec_stage(hipStream_t st, int part, int stage, int what, const float* xin, int B, int T_in, int C_in, float* out,
+                             int* T_out, int* C_out) {
+    DeepScope deep_scope(gemm_deep_);
+    PersistScope persist_scope(persist_cus_);
+    if (part != 1 && part != 2) return fail("test_codec_stage: part must be 1 (decoder) or 2 (encoder)");
+    const bool dec = part == 1;
+    const CodecHalfW& h = dec ? dec_ : enc_;
+    if (!h.ready) return fail("test_codec_stage: codec half not finalized");
+    const CodecSpecC& s = cspec_;
+    const int S = s.n_ratios + 1, pad = kCodecPad;
+    if (stage < 0 || stage >= S) return fail("test_codec_stage: stage out of range");
+    // the parts in pipeline order: stem (stage 0) or resampling (stage > 0), blocks, head (last stage); set bits must be a contiguous run
+    const int seq[3] = {stage == 0 ? 1 : 2, 4, 8};
+    if (what <= 0 || (what & ~(seq[0] | 4 | 8))) return fail("test_codec_stage: `what` names a part this stage does not have");
+    {
+        int first = -1, last = -1;
+        for (int k = 0; k < 3; ++k)
+            if (what & seq[k]) { if (first < 0) first = k; last = k; }
+        for (int k = first; k <= last; ++k)
+            if (!(what & seq[k])) return fail("test_codec_stage: `what` bits are not a run in pipeline order");
+    }
+    if ((what & 8) && stage != S - 1) return fail("test_codec_stage: the head belongs to the last stage");
+    if (B <= 0 || T_in <= 0) return fail("test_codec_stage: B * T must be positive");
+    // input geometry and the whole call (T0: decoder latent frames / encoder samples) whose plan this stage runs under
+    const int r = stage > 0 ? h.stages[stage].r : 1;
+    const int c_need = (what & 1) ? (dec ? s.latent_dim : 1) : (what & 2) ? h.stages[stage - 1].C : h.stages[stage].C;
+    if (C_in != c_need) return fail("test_codec_stage: C_in " + std::to_string(C_in) + " does not match the stage (" + std::to_string(c_need) + ")");
+    if (!dec && (what & 2) && T_in % r) return fail("test_codec_stage: encoder T_in must be a multiple of the stage's stride");
+    const long Ts = (what & 2) ? (dec ? (long)T_in * r : T_in / r) : T_in;   // frames of the stage
+    long up = 1;   // frames of the stage per decoder latent frame / encoder samples per frame of the stage
+    for (int i = 1; i <= stage; ++i) up *= dec ? s.ratios[i - 1] : s.ratios[s.n_ratios - i];
+    const long T0 = dec ? (Ts + up - 1) / up : Ts * up;
+    if (T0 > (1L << 30) || Ts > (1L << 30)) return fail("test_codec_stage: too many frames");
+    const int Cs = h.stages[stage].C;
+    if (T_out) *T_out = (int)Ts;
+    if (C_out) *C_out = (what & 8) ? (dec ? 1 : s.latent_dim) : Cs;
+    if (!out) return 0;   // shape query
+    if (!xin) return fail("test_codec_stage: null input");
+
+    HIPC(hipSetDevice(device_));
+    const CodecPlan plan = codec_plan(dec, B, T0);
+    const size_t bytes = codec_ws_bytes(plan);
+    void* ws = nullptr;
+    HIPC(hipMalloc(&ws, bytes));
+    int rc = 0;
+    {
+        Bump bump(ws);
+        CodecWs w;
+        w.plan(bump, plan);
+        float* x = w.xa;
+        float* xn = w.xb;
+        int Ti = T_in, C = c_need;
+        auto run = [&]() -> int {
+            // all-ones bytes: NaN in every operand format (fp32, bf16, fp16).  The product never clears its workspace (it zeroes the
+            // causal pads itself); a kernel that read rows nobody wrote would turn this into NaN in the output instead of going unseen
+            HIPC(hipMemsetAsync(ws, 0xff, bytes, st));
+            if (what & 1) {
+                if (dec ? decode_stem(st, w, xin, B, T_in) : encode_stem(st, w, xin, B, T_in)) return 1;
+                C = Cs;
+            } else {   // the input as the image the previous part would have left: zero causal pads, data rows
+                HIPC(launch_zero_pad_frames3(x, xn, w.nb, B, Ti, C, pad, st));
+                HIPC(hipMemcpy2DAsync(x + (long)pad * C, (size_t)(pad + Ti) * C * 4, xin, (size_t)Ti * C * 4, (size_t)Ti * C * 4, B,
+                                      hipMemcpyDeviceToDevice, st));
+            }
+            if (what & (2 | 4))
+                if (dec ? decode_stage(st, w, stage, what, &x, &xn, B, &Ti, &C) : encode_stage(st, w, stage, what, &x, &xn, B, &Ti, &C))
+                    return 1;
+            if (what & 8) return dec ? decode_head(st, w, x, B, Ti, C, out) : encode_head(st, w, x, B, Ti, C, out);
+            HIPC(hipMemcpy2DAsync(out, (size_t)Ti * C * 4, x + (long)pad * C, (size_t)(pad + Ti) * C * 4, (size_t)Ti * C * 4, B,
+                                  hipMemcpyDeviceToDevice, st));
+            return 0;
+        };
+        rc = run();
+    }
+    const hipError_t es = hipStreamSynchronize(st);
+    const hipError_t ef = hipFree(ws);
+    if (rc) return rc;
+    if (es != hipSuccess) return fail_hip(es, "test_codec_stage: stream");
+    if (ef != hipSuccess) return fail_hip(ef, "test_codec_stage: free");
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -191,6 +191,9 @@ class Engine {
                      const float* nscale, const float* shift, const float* W1, const float* W3, const float* b1, const float* b3,
                      int M, int K, int D, int F, float eps, int rms, int prec, int fold, float* x, float* h,
                      float* c_out);
+    // one codec stage through the code of codec_decode (part 1) / codec_encode (part 2): include/smalltts_hip.h smtts_test_codec_stage
+    int test_codec_stage(hipStream_t st, int part, int stage, int what, const float* x, int B, int T_in, int C_in, float* out,
+                         int* T_out, int* C_out);
 
     // fp16 range guard: per-site count of values that fp16 producers clamped to +-65504 since the last reset (device counters,
     // common.hpp sat_note) + the static part: codec FFN blocks whose fused kernels' hidden / input bound could not be certified
@@ -231,6 +234,20 @@ class Engine {
     // runs one block; the result lives in *x on return (the fused mixer ping-pongs *x <-> *xalt)
     int ensure_qkvg_unpadded();   // packs DitBlockW::qkvg of every block on first use of an A/B attention path
     bool qkvg_unpadded_ready_ = false;   // ... set only after EVERY block packed (a failure half-way unlinks what was built)
+    // ---- codec: one call = stem, then per stage the resampling into it (stage > 0) and its blocks, then final norm + head.  The
+    // operators and the test hook (test_codec_stage) run the same functions on a workspace planned the same way (codec_plan).
+    struct CodecPlan { size_t max_img = 0, max_hid = 0, lat = 1; };   // elements: one image, one FFN hidden, the decoder's latent image
+    struct CodecWs;
+    CodecPlan codec_plan(bool decoder, int B, long T) const;   // T: decoder latent frames / encoder audio samples of the whole call
+    size_t codec_ws_bytes(const CodecPlan& p) const;
+    int decode_stem(hipStream_t st, const CodecWs& w, const float* latents, int B, int T);
+    int decode_stage(hipStream_t st, const CodecWs& w, int i, int what, float** x, float** xn, int B, int* Ti, int* C);
+    int decode_head(hipStream_t st, const CodecWs& w, const float* x, int B, int Ti, int C, float* audio);
+    int encode_stem(hipStream_t st, const CodecWs& w, const float* audio, int B, int S);
+    int encode_stage(hipStream_t st, const CodecWs& w, int i, int what, float** x, float** xn, int B, int* Ti, int* C);
+    int encode_head(hipStream_t st, const CodecWs& w, const float* x, int B, int Ti, int C, float* latents);
+    int conv_small_m(hipStream_t st, const CodecWs& w, const float* img, long img_rows, int Cin, const RowMap& am, const PW& wt,
+                     const float* bias, float* out, const RowMap& om, int M);
     int codec_stage_chain(hipStream_t st, const CodecStageW& sg, float** x, float** xalt, int B, int T, int C);
     int codec_block(hipStream_t st, const CodecBlockW& w, float** x, float** xalt, float* nbuf, bf16_t* n2hi, bf16_t* n2lo,
                     bf16_t* hhi, bf16_t* hlo, int B, int T, int C, size_t n2_elems /* capacity of n2hi (bf16 elements) */);

@@ -680,6 +680,7 @@ hipError_t launch_stem_conv1(const float* audio, const float* w, const float* bi
                              int K, int pad, hipStream_t st) {
     long n = (long)B * T * C;
     if (n == 0) return hipSuccess;
+    ProfScope ps(st, "stem_conv1", 2.0 * B * T * C * K, 4.0 * B * T * (C + 1));
     hipLaunchKernelGGL(stem_conv1_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, audio, w, bias, x, B, T, C, K, pad);
     LAUNCH_CHECK();
 }

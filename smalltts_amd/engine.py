@@ -523,6 +523,24 @@ class HipEngine:
                                              PRECISION[precision], int(bool(fold)), _p(x), _p(hid), _p(shift_out)), "test_ln_fold")
         return (x, hid, shift_out) if return_shift else (x, hid)
 
+    def test_codec_stage(self, part, stage: int, what: int, x) -> torch.Tensor:
+        """One codec stage through the product's code (include/smalltts_hip.h smtts_test_codec_stage).  part: "decoder" / "encoder"
+        (or 1 / 2); what: 1 stem, 2 resampling into `stage`, 4 its blocks, 8 final norm + head (a run of these bits).  x: (B, T_in, C_in)
+        channels-last (encoder stem: (B, S) or (B, S, 1) audio).  Returns the device tensor (B, T_out, C_out); the decoder head's
+        audio comes back as (B, T_out, 1)."""
+        p = {"decoder": 1, "encoder": 2}.get(part, part)
+        x = self._dev(x, torch.float32)
+        if x.dim() == 2:
+            x = x[:, :, None].contiguous()
+        B, T, Cin = x.shape
+        t_out, c_out = C.c_int(0), C.c_int(0)
+        self._ck(self.lib.smtts_test_codec_stage(self.h, self._stream(), int(p), int(stage), int(what), _p(x), B, T, Cin, None,
+                                                 C.byref(t_out), C.byref(c_out)), "test_codec_stage")
+        out = torch.empty(B, t_out.value, c_out.value, device=self.device)
+        self._ck(self.lib.smtts_test_codec_stage(self.h, self._stream(), int(p), int(stage), int(what), _p(x), B, T, Cin, _p(out),
+                                                 C.byref(t_out), C.byref(c_out)), "test_codec_stage")
+        return out
+
     def test_swiglu(self, A, W1, W3, b1=None, b3=None, split=3):
         A, W1, W3 = (self._dev(x, torch.float32) for x in (A, W1, W3))
         b1 = None if b1 is None else self._dev(b1, torch.float32)
