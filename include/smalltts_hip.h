@@ -49,9 +49,9 @@ int smtts_create(int device_id, smtts_handle* out);
 int smtts_destroy(smtts_handle h);
 const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation error */
 const char* smtts_version(void);
-/* bumped on every signature / default change: 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
+/* bumped on every signature / default change: 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
-#define SMTTS_ABI_VERSION 7
+#define SMTTS_ABI_VERSION 8
 int smtts_abi_version(void);
 
 /* ---- weights (replaces the ONNX initialisers; names/shapes = DiTModel.state_dict(),
@@ -197,6 +197,27 @@ int smtts_test_ln_fold(smtts_handle h, void* stream, const float* A, const float
  * with an error and no launch. */
 int smtts_test_codec_stage(smtts_handle h, void* stream, int part, int stage, int what, const float* x, int B, int T_in, int C_in,
                            float* out, int* T_out, int* C_out);
+/* DiT / condition-encoder stages through the code of smtts_denoise_step / smtts_sample / smtts_cond_encode.  net: 0 DiT, 1 style
+ * encoder, 2 text encoder.  what (a run of the chain bits, in pipeline order):
+ *   DiT:      1 modulation table from t[mod_rows] (otherwise `mod` [mod_rows][71040] is the table; either feeds the blocks), 2 embed
+ *             (x = latents [B][S][64] -> residual), 4 blocks [l0, l1) (x = residual [B][S][960] unless 2 ran), 8 velocity head (x = the
+ *             final AdaLN image [B][S][960] unless 4 ran; out = velocity [B][S][64]);
+ *   encoders: 1 input (style: x = ref [B][S][64]; text: x = int64 ids [B][S]), 2 blocks [l0, l1) (x = residual [B][S][512] unless 1
+ *             ran), 4 output projection (x = final norm image [B][S][512] unless 2 ran; out = ref_seq / phoneme memory [B][S][960]),
+ *             8 cross K / V of the 12 DiT blocks (x = [B][S][960] unless 4 ran; k_out, v_out [12][B][8][S][120]).
+ * path of the blocks: 0 the operator's choice (denoise_step's for the DiT), 1 LN-fold, 2 split-K + norm launches, 3 unsplit GEMM + norm
+ * launch; a path the product never takes there (fold with M > 1024 or mod_rstride != 0, split-K with M > 1024) is refused.  mask: the
+ * self / key mask [B][S]; k_ref .. ph_mask, R, P, rope: as smtts_denoise_step.  mod_row0 / mod_rstride (0 or 1): the modulation row
+ * of utterance b is mod_row0 + b mod_rstride.  Outputs (each may be NULL): x_out residual after the last embed / input / block stage,
+ * img_out the AdaLN / RMSNorm operand image the blocks leave for the next GEMM decoded to fp32 (fold: (x - shift) (1 + scale) of the
+ * next block / x weight), shift_out [B][S] the fold's row shift (zeros off the fold), mod_out the modulation table.  The workspace
+ * is planned as the operators plan it and filled with 0xff (NaN) first; twice != 0 runs everything a second time on it, as the
+ * sampler's later steps find it.  Synchronises the stream; bad arguments are refused before any launch. */
+int smtts_test_dit_stage(smtts_handle h, void* stream, int net, int what, int l0, int l1, int path, int twice, const void* x,
+                         const uint8_t* mask, int B, int S, const float* t, const float* mod, int mod_rows, int mod_row0, int mod_rstride,
+                         const float* k_ref, const float* v_ref, const uint8_t* ref_mask, int R, const float* k_text,
+                         const float* v_text, const uint8_t* ph_mask, int P, const float* rope, float* x_out, float* img_out,
+                         float* shift_out, float* out, float* k_out, float* v_out, float* mod_out);
 /* codec blocks: 1 (default) = fused mixer and fused FFN kernels (C <= 256), 0 = separate norm / conv / two-GEMM path */
 int smtts_test_set_fused_ffn(smtts_handle h, int on);
 /* fused sampler: 1 (default) = the AdaLN between two DiT block GEMMs folded into their epilogues (reference dit.py:19-25,197-212

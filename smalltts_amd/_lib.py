@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("SMTTS_LIB") or os.path.join(_HERE, "libsmalltts_hip.s
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "smalltts_hip.h")
 
 _lib = None
-ABI_VERSION = 7   # include/smalltts_hip.h SMTTS_ABI_VERSION
+ABI_VERSION = 8   # include/smalltts_hip.h SMTTS_ABI_VERSION
 
 vp, i32, i64, u64, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
 cstr = C.c_char_p
@@ -64,6 +64,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_test_ln_fold": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, f32, i32, i32, i32,
                                  vp, vp, vp]),
     "smtts_test_codec_stage": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, i32, vp, C.POINTER(i32), C.POINTER(i32)]),
+    "smtts_test_dit_stage": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp,
+                                   vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "smtts_test_set_fused_ffn": (i32, [vp, i32]),
     "smtts_test_set_ln_fold": (i32, [vp, i32]),
     "smtts_test_gemm": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32]),

@@ -177,6 +177,14 @@ int smtts_test_codec_stage(smtts_handle h, void* stream, int part, int stage, in
                            float* out, int* T_out, int* C_out) { NULLCHK;
     return E.test_codec_stage(ST(stream), part, stage, what, x, B, T_in, C_in, out, T_out, C_out);
 }
+int smtts_test_dit_stage(smtts_handle h, void* stream, int net, int what, int l0, int l1, int path, int twice, const void* x,
+                         const uint8_t* mask, int B, int S, const float* t, const float* mod, int mod_rows, int mod_row0, int mod_rstride,
+                         const float* k_ref, const float* v_ref, const uint8_t* ref_mask, int R, const float* k_text,
+                         const float* v_text, const uint8_t* ph_mask, int P, const float* rope, float* x_out, float* img_out,
+                         float* shift_out, float* out, float* k_out, float* v_out, float* mod_out) { NULLCHK;
+    return E.test_dit_stage(ST(stream), net, what, l0, l1, path, twice, x, mask, B, S, t, mod, mod_rows, mod_row0, mod_rstride, k_ref,
+                            v_ref, ref_mask, R, k_text, v_text, ph_mask, P, rope, x_out, img_out, shift_out, out, k_out, v_out, mod_out);
+}
 int smtts_test_set_fused_ffn(smtts_handle h, int on) { NULLCHK; E.set_fused_ffn(on != 0); return 0; }
 int smtts_test_set_ln_fold(smtts_handle h, int on) { NULLCHK; E.set_ln_fold(on != 0); return 0; }
 int smtts_test_set_attention_mfma(smtts_handle h, int mode) { NULLCHK;   // 0: fp32 projection + qk_prep + the fp32 VALU reference kernel; else (default): producer-written operand images + the DMA / MFMA kernel

@@ -846,8 +846,7 @@ static hipError_t gemm3_store_splitk(const Gemm3Operands& g0, float* partial, in
 // K10: encoder stack (style.py:70-105 / phonemes.py:131-167), x (fp32 residual) updated in place.
 // GEMM inputs (y, o, ffh) live as split bf16 pairs written by the producing kernel.
 // ---------------------------------------------------------------------------------------------
-namespace {
-struct EncWs {
+struct Engine::EncWs {
     float *x, *qkvg, *seq, *part, *lnpart;
     SplitBuf y, o, ffh, seqs;
     SplitBuf qi, ki, vti, gi;   // attention operand images (attention_img.hip): [B][H][S][dhp] x 2, [B][H][dhp][pad8(S)], [M][D]
@@ -872,25 +871,25 @@ struct EncWs {
         gi = take_split(b, (size_t)Mx * 512);
     }
 };
-}  // namespace
 
-int Engine::run_encoder(hipStream_t st, const EncoderW& e, void* wsv, int B, int S, const uint8_t* key_mask) {
-    // On return w.y holds RMSNorm(x; final_norm) as a split pair: every norm except the first is fused into the
+int Engine::enc_blocks(hipStream_t st, const EncoderW& e, const EncWs& w, int l0, int l1, int B, int S, const uint8_t* key_mask,
+                       bool fold, int ks) {
+    // On return w.y holds RMSNorm(x; norm of block l1, or final_norm) as a split pair: every norm except the first is fused into the
     // split-K reduction of the residual GEMM in front of it (the tiny-M projections get 4x the workgroups that way).
-    EncWs& w = *static_cast<EncWs*>(wsv);
     const int M = B * S, D = e.dim;
     const RowMap rd = rowmap_plain(D);
     if (e.blocks.empty()) return fail("encoder without blocks");
     const int pe = prec_[SITE_ENCODER];
     unsigned* const se = satp(SITE_ENCODER);
     const SplitBuf y = w.y.as(pe, se), o = w.o.as(pe, se), ffh = w.ffh.as(pe, se);  // every activation here feeds a SITE_ENCODER GEMM
-    HIPC(launch_rmsnorm(w.x, rd, nullptr, y.hi, y.lo, rd, M, D, e.eps, e.blocks[0].an, st));
+    HIPC(launch_rmsnorm(w.x, rd, nullptr, y.hi, y.lo, rd, M, D, e.eps, e.blocks[l0].an, st));
     // RMSNorm fold (gemm.hpp LnFoldIn, rms): the norm between two block GEMMs lives in their epilogues — the producer writes x w and the
     // row's sum-of-squares partials, the consumer scales by rstd; the first norm (above) and the final one (feeds a plain projection) stay
-    const bool fold = fold_epi_on() && D % 64 == 0;   // (the consumer reads the D / 32 partials in pairs)
+    // (fold needs D % 64 == 0: the consumer reads the D / 32 partials in pairs)
     LnFoldIn fin;
     fin.part = w.lnpart; fin.NP = D / 32; fin.inv_c = 1.0f / D; fin.eps = e.eps; fin.rms = 1;
-    for (size_t l = 0; l < e.blocks.size(); ++l) {
+    const size_t L = e.blocks.size();
+    for (size_t l = l0; l < (size_t)l1; ++l) {
         const EncBlockW& b = e.blocks[l];
         const bool epi = attn_img_ && attn_epi_;   // the GEMM's own epilogue writes the attention operands
         if (!epi) HIPC(gemm3_store(ops3(w.y, rd, b.qkvg, M, pe), ACT_NONE, store_to(w.qkvg, rowmap_plain(4 * D), nullptr), 1, pe, st));
@@ -911,14 +910,14 @@ int Engine::run_encoder(hipStream_t st, const EncoderW& e, void* wsv, int B, int
             pk.q = w.qi.hi; pk.q_lo = img_lo(pa, w.qi.lo); pk.k = w.ki.hi; pk.k_lo = img_lo(pa, w.ki.lo); pk.vt = w.vti.hi; pk.vt_lo = img_lo(pa, w.vti.lo);
             pk.g = w.gi.hi; pk.g_lo = img_lo(pa, w.gi.lo);
             pk.B = B; pk.N = S; pk.H = e.heads; pk.dh = e.dh; pk.dhp = e.dh <= 64 ? 64 : 128; pk.Np = Sp;
-            if (l == 0 && Sp != S) {   // pad key columns of V^T: zero once per call (the producer only writes n < S)
+            if (l == (size_t)l0 && Sp != S) {   // pad key columns of V^T: zero once per call (the producer only writes n < S)
                 HIPC(hipMemsetAsync(w.vti.hi, 0, (size_t)B * e.heads * pk.dhp * Sp * 2, st));
                 if (pa == PREC_BF16X3) HIPC(hipMemsetAsync(w.vti.lo, 0, (size_t)B * e.heads * pk.dhp * Sp * 2, st));
             }
             if (epi) {
                 EpiQKV eq{nullptr, pk.qw, pk.kw, pk.rope_cos, pk.rope_sin, pk.eps, pk.q_scale, pk.rot_dim, pa,
                           pk.q, pk.q_lo, pk.k, pk.k_lo, pk.vt, pk.vt_lo, pk.g, pk.g_lo, S, e.heads, e.dh, pk.dhp, Sp};
-                if (fold && l > 0) eq.fold = fin;   // w.y = x attention_norm.weight, written by the previous block's FF2 epilogue
+                if (fold && l > (size_t)l0) eq.fold = fin;   // w.y = x attention_norm.weight, written by the previous block's FF2 epilogue
                 HIPC(gemm3_qkv(ops3(w.y, rd, b.qkvg, M, pe), eq, pe, st));   // (both encoders' heads are 64 / 128 wide: no padding)
             } else {
                 HIPC(launch_qkv_pack(pk, st));
@@ -945,8 +944,8 @@ int Engine::run_encoder(hipStream_t st, const EncoderW& e, void* wsv, int B, int
         if (fold) {
             EpiResidLN e1{w.x, rd, nullptr, nullptr, nullptr, b.mn, y.hi, y.lo, D, w.lnpart, D / 32, 1};
             HIPC(gemm3_resid_ln(ops3(w.o, rd, b.wo, M, pe), e1, pe, st));
-        } else if (ksplit_enc_ > 1) {
-            HIPC(gemm3_resid_splitk(ops3(w.o, rd, b.wo, M, pe), r1, w.part, ksplit_enc_, pe, st, n1));
+        } else if (ks > 1) {
+            HIPC(gemm3_resid_splitk(ops3(w.o, rd, b.wo, M, pe), r1, w.part, ks, pe, st, n1));
         } else {
             HIPC(gemm3_resid(ops3(w.o, rd, b.wo, M, pe), 0, r1, pe, st));
             HIPC(launch_rmsnorm(w.x, rd, nullptr, y.hi, y.lo, rd, M, D, e.eps, n1.shift, st));
@@ -954,12 +953,12 @@ int Engine::run_encoder(hipStream_t st, const EncoderW& e, void* wsv, int B, int
         EpiSwiGLU sw{nullptr, e.ff, nullptr, nullptr, ffh.hi, ffh.lo};
         if (fold) sw.fold = fin;
         HIPC(gemm3_swiglu(ops3(w.y, rd, b.ff13, M, pe), sw, pe, st));
-        NextLN n2{l + 1 < e.blocks.size() ? e.blocks[l + 1].an : e.final_norm, nullptr, y.hi, y.lo, true, e.eps};
-        if (fold && l + 1 < e.blocks.size()) {
+        NextLN n2{l + 1 < L ? e.blocks[l + 1].an : e.final_norm, nullptr, y.hi, y.lo, true, e.eps};
+        if (fold && l + 1 < L) {
             EpiResidLN e2{w.x, rd, nullptr, nullptr, nullptr, e.blocks[l + 1].an, y.hi, y.lo, D, w.lnpart, D / 32, 1};
             HIPC(gemm3_resid_ln(ops3(w.ffh, rowmap_plain(e.ff), b.w2, M, pe), e2, pe, st));
-        } else if (ksplit_enc_ > 1) {
-            HIPC(gemm3_resid_splitk(ops3(w.ffh, rowmap_plain(e.ff), b.w2, M, pe), r1, w.part, ksplit_enc_, pe, st, n2));
+        } else if (ks > 1) {
+            HIPC(gemm3_resid_splitk(ops3(w.ffh, rowmap_plain(e.ff), b.w2, M, pe), r1, w.part, ks, pe, st, n2));
         } else {
             HIPC(gemm3_resid(ops3(w.ffh, rowmap_plain(e.ff), b.w2, M, pe), 0, r1, pe, st));
             HIPC(launch_rmsnorm(w.x, rd, nullptr, y.hi, y.lo, rd, M, D, e.eps, n2.shift, st));
@@ -1011,8 +1010,6 @@ int Engine::cond_encode(hipStream_t st, const float* ref, const int64_t* ref_len
     EncWs w, wt;
     w.plan(bump, B, R);
     wt.plan(bump, B, P);
-    const RowMap r512 = rowmap_plain(512), rh = rowmap_plain(kHidden);
-    const int pe = prec_[SITE_ENCODER], pk = prec_[SITE_CROSS_KV], pc = prec_[SITE_COND];
     const bool fork = dual_stream_ && R > 0 && P > 0;
     hipStream_t stt = st;  // stream of the text half
     if (fork) {
@@ -1023,36 +1020,53 @@ int Engine::cond_encode(hipStream_t st, const float* ref, const int64_t* ref_len
     }
 
     // ---- E2 text encoder (phonemes.py:200-207) + phoneme_proj (dit.py:293-298) ---------------
+    const bool fold = fold_epi_on();
     if (P > 0) {
-        const int M = B * P;
-        HIPC(launch_embedding(ids, rawp("phoneme_embedding.text_embedding.weight"), wt.x, M, 512, 198, stt));
-        if (run_encoder(stt, text_, &wt, B, P, ph_mask)) return 1;  // leaves RMSNorm(x; final_norm) in wt.y
+        if (text_in(stt, wt, ids, B, P)) return 1;
+        if (enc_blocks(stt, text_, wt, 0, (int)text_.blocks.size(), B, P, ph_mask, fold && text_.dim % 64 == 0, ksplit_enc_)) return 1;
         float* mem = mem_out ? mem_out : wt.seq;
-        HIPC(gemm3_store(ops3(wt.y, r512, phproj_, M, pe), ACT_NONE,
-                         store_to(mem, rh, rawp("dit.phoneme_proj.bias"), 1.f, ph_mask), 1, pe, stt));
-        HIPC(launch_to_split(mem, rh, wt.seqs.hi, wt.seqs.as(pk, satp(SITE_CROSS_KV)).lo, rh, M, kHidden, stt));
-        EpiKV kv{k_text, v_text, kvtext_b_, B, kHeads, kDh, P};
-        HIPC(gemm3_kv(ops3(wt.seqs, rh, kvtext_, M, pk), kv, pk, stt));
-        HIPC(launch_headnorm(k_text, kBlocks, B, kHeads, P, kDh, 1e-6f, knc_, stt));
+        if (enc_out(stt, true, wt, B * P, ph_mask, mem)) return 1;
+        if (enc_kv(stt, true, wt, mem, B, P, k_text, v_text)) return 1;
     }
     if (fork) HIPC(hipEventRecord(ev_join_, aux_));
     // ---- E1 style encoder (style.py:144-174) -------------------------------------------------
     if (R > 0) {
-        const int M = B * R;
         HIPC(launch_len_mask(ref_len, ref_mask, B, R, st));
-        HIPC(gemm_store(ops(ref, rowmap_plain(kLatent), style_in_, M), ACT_NONE,
-                        store_to(w.x, r512, rawp("style_encoder.in_proj.bias"), style_scale_), 1, pc, st));
-        if (run_encoder(st, style_, &w, B, R, ref_mask)) return 1;  // leaves RMSNorm(x; final_norm) in w.y
+        if (style_in(st, w, ref, B, R)) return 1;
+        if (enc_blocks(st, style_, w, 0, (int)style_.blocks.size(), B, R, ref_mask, fold && style_.dim % 64 == 0, ksplit_enc_)) return 1;
         float* seq = ref_seq_out ? ref_seq_out : w.seq;
-        HIPC(gemm3_store(ops3(w.y, r512, style_out_, M, pe), ACT_NONE,
-                         store_to(seq, rh, rawp("style_encoder.out_proj.bias"), 1.f, ref_mask), 1, pe, st));
+        if (enc_out(st, false, w, B * R, ref_mask, seq)) return 1;
         // ---- E3 cross KV for the reference tokens (dit.py:80-93) -------------------------------
-        HIPC(launch_to_split(seq, rh, w.seqs.hi, w.seqs.as(pk, satp(SITE_CROSS_KV)).lo, rh, M, kHidden, st));
-        EpiKV kv{k_ref, v_ref, kvref_b_, B, kHeads, kDh, R};
-        HIPC(gemm3_kv(ops3(w.seqs, rh, kvref_, M, pk), kv, pk, st));
-        HIPC(launch_headnorm(k_ref, kBlocks, B, kHeads, R, kDh, 1e-6f, knc_, st));
+        if (enc_kv(st, false, w, seq, B, R, k_ref, v_ref)) return 1;
     }
     if (fork) HIPC(hipStreamWaitEvent(st, ev_join_, 0));  // join: everything after cond_encode sees both halves
+    return 0;
+}
+
+// the encoders' stages (cond_encode): input, output projection, cross K / V of all 12 DiT blocks
+int Engine::style_in(hipStream_t st, const EncWs& w, const float* ref, int B, int R) {
+    HIPC(gemm_store(ops(ref, rowmap_plain(kLatent), style_in_, B * R), ACT_NONE,
+                    store_to(w.x, rowmap_plain(512), rawp("style_encoder.in_proj.bias"), style_scale_), 1, prec_[SITE_COND], st));
+    return 0;
+}
+int Engine::text_in(hipStream_t st, const EncWs& w, const int64_t* ids, int B, int P) {
+    HIPC(launch_embedding(ids, rawp("phoneme_embedding.text_embedding.weight"), w.x, B * P, 512, 198, st));
+    return 0;
+}
+int Engine::enc_out(hipStream_t st, bool text, const EncWs& w, int M, const uint8_t* key_mask, float* seq) {
+    const int pe = prec_[SITE_ENCODER];
+    HIPC(gemm3_store(ops3(w.y, rowmap_plain(512), text ? phproj_ : style_out_, M, pe), ACT_NONE,
+                     store_to(seq, rowmap_plain(kHidden), rawp(text ? "dit.phoneme_proj.bias" : "style_encoder.out_proj.bias"), 1.f,
+                              key_mask), 1, pe, st));
+    return 0;
+}
+int Engine::enc_kv(hipStream_t st, bool text, const EncWs& w, const float* seq, int B, int S, float* k, float* v) {
+    const int pk = prec_[SITE_CROSS_KV], M = B * S;
+    const RowMap rh = rowmap_plain(kHidden);
+    HIPC(launch_to_split(seq, rh, w.seqs.hi, w.seqs.as(pk, satp(SITE_CROSS_KV)).lo, rh, M, kHidden, st));
+    EpiKV kv{k, v, text ? kvtext_b_ : kvref_b_, B, kHeads, kDh, S};
+    HIPC(gemm3_kv(ops3(w.seqs, rh, text ? kvtext_ : kvref_, M, pk), kv, pk, st));
+    HIPC(launch_headnorm(k, kBlocks, B, kHeads, S, kDh, 1e-6f, knc_, st));
     return 0;
 }
 
@@ -1079,7 +1093,12 @@ int Engine::modulation(hipStream_t st, const float* t_dev, int rows, float* sinb
     HIPC(gemm_store(ops(semb, rowmap_plain(kHidden), modall_, rows), ACT_NONE,
                     store_to(mod, rowmap_plain(kModLd), modall_b_), 1, pc, st));
     HIPC(launch_tanh_gates(mod, rows, kModLd, kBlocks, kModPerBlock, kHidden, st));
-    if (ftab) {   // LN-fold tables of every (step, block, site): W shift and W (1 + scale) on the weights the block GEMMs multiply
+    return ftab ? fold_tables(st, mod, rows, ftab) : 0;
+}
+
+// LN-fold tables of every (step, block, site): W shift and W (1 + scale) on the weights the block GEMMs multiply
+int Engine::fold_tables(hipStream_t st, const float* mod, int rows, float* ftab) {
+    {
         const int pb = prec_[SITE_DIT_BLOCK];
         FoldSites fs{};
         fs.n = 0;
@@ -1119,7 +1138,8 @@ struct ModWs {
         mod = b.take<float>((size_t)rows * kModLd);
     }
 };
-struct CoreWs {
+}  // namespace
+struct Engine::CoreWs {
     float *h, *x, *qkvg, *part, *lnpart, *lnc;   // lnc [M]: the LN-fold producers' row shift (gemm.hpp LnFoldIn::cshift)
     float *rope_c, *rope_s;  // cos / sin of a caller-supplied angle table: per call (several calls may be in flight on different streams)
     SplitBuf gm1, gm2, y, o, ffh;
@@ -1148,7 +1168,6 @@ struct CoreWs {
         ffh = take_split(b, M * kFFp);
     }
 };
-}  // namespace
 
 size_t Engine::denoise_core_bytes(int B, int N) const {
     Bump b(nullptr);
@@ -1169,21 +1188,54 @@ int Engine::denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, 
     CoreWs w;
     w.plan(bump, B, N);
     const int M = B * N;
-    const RowMap rh = rowmap_plain(kHidden);
-    // operand formats: the block GEMMs run at SITE_DIT_BLOCK precision, the latent in-projection / conv pos-embed / velocity
-    // head at SITE_COND; each activation buffer is written in the format of the GEMM that reads it
-    const int pb = prec_[SITE_DIT_BLOCK], pc = prec_[SITE_COND], pcp = prec_[SITE_CONVPOS];
-    unsigned* const sb = satp(SITE_DIT_BLOCK);
-    const SplitBuf gm1 = w.gm1.as(pcp, satp(SITE_CONVPOS)), gm2 = w.gm2.as(pcp, satp(SITE_CONVPOS)), yb = w.y.as(pb, sb), ob = w.o.as(pb, sb), ffh = w.ffh.as(pb, sb);
-    // D2 input embedding (dit.py:246-253): h = proj(x); x = mask*mish(conv2(mask*mish(conv1(mask*h)))) + h
-    HIPC(gemm_store(ops(x_t, rowmap_plain(kLatent), inproj_, M), ACT_NONE,
-                    store_to(w.h, rh, rawp("dit.input_embed.proj.bias")), 1, pc, st));
-    HIPC(launch_convpos_pack(w.h, mask, gm1.hi, gm1.lo, B, N, kConvG, kConvCpg, kConvPad, kConvGs, st));
-    // zero regions that no kernel of this function writes (pad frames of the conv image, pad columns of the FF hidden, pad key
+    // zero regions that no kernel of this call writes (pad frames of the conv image, pad columns of the FF hidden, pad key
     // columns of V^T): once per workspace use — the sampler's later steps find them as the first step left them
     const bool init_ws = !ws_ready_;
     ws_ready_ = ws_keep_;
-    if (init_ws) {
+    if (dit_embed(st, w, x_t, mask, B, N, init_ws)) return 1;
+    DitRun d;
+    d.rc = rope_dit_cos_;
+    d.rs = rope_dit_sin_;
+    if (rope) {  // caller-supplied angle table (reference operator input, infer/onnx.py:42-47,122)
+        HIPC(launch_rope_cossin(rope, w.rope_c, w.rope_s, N * 64, st));
+        d.rc = w.rope_c;
+        d.rs = w.rope_s;
+    }
+    if (join_pending_) {   // the modulation table is being computed on the side stream (sample)
+        HIPC(hipStreamWaitEvent(st, ev_join_, 0));
+        join_pending_ = false;
+    }
+    // LN-fold (gemm.hpp LnFoldIn): inside the fused sampler — one modulation row for the whole batch, tables from modulation() —
+    // the AdaLN between two block GEMMs lives in their epilogues (ftab: the tables sample() planned by the same predicate)
+    const bool fold = ftab && mod_rstride == 0 && dit_fold_on(M);
+    // split-K exists to fill the chip at M = 600 (150 tiles of 64x64 for N = 960); the 3B-row CFG batches of the teacher
+    // sampler (M = 1800: 435 tiles) fill it without, and the fused epilogue is cheaper than partials + reduce (495 -> 454 ms)
+    // ... and so do several batches in flight (throughput tuning): there the unsplit GEMM + a separate AdaLN costs 2.3x fewer
+    // workgroup-microseconds than three K slices + reduce, and that is what counts when other streams want the CUs
+    static const bool splitk_tp = lab_env("SMTTS_SPLITK_TP") && atoi(lab_env("SMTTS_SPLITK_TP")) != 0;   // (A/B only)
+    const bool unsplit = M > 1024 || (tuning_ == TUNE_THROUGHPUT && !splitk_tp);
+    d.mask = mask; d.mod = mod; d.mod_row0 = mod_row0; d.mod_rstride = mod_rstride;
+    d.k_ref = k_ref; d.v_ref = v_ref; d.ref_mask = ref_mask; d.k_text = k_text; d.v_text = v_text; d.ph_mask = ph_mask;
+    d.ci = &ci;
+    d.frow = fold ? ftab + (long)mod_row0 * 2 * kFoldNF : nullptr;   // [0]: W shift, [1]: W (1 + scale)
+    d.ks_out = unsplit ? 1 : ksplit_out_;
+    d.ks_ff2 = unsplit ? 1 : ksplit_ff2_;
+    d.B = B; d.N = N; d.R = R; d.P = P;
+    d.init_ws = init_ws;
+    if (dit_blocks(st, w, d, 0, kBlocks)) return 1;
+    return dit_head(st, w, M, velocity);
+}
+
+// D2 input embedding (dit.py:246-253): h = proj(x); x = mask*mish(conv2(mask*mish(conv1(mask*h)))) + h   -> w.x (and w.h)
+int Engine::dit_embed(hipStream_t st, const CoreWs& w, const float* x_t, const uint8_t* mask, int B, int N, bool init_ws) {
+    const int M = B * N;
+    const RowMap rh = rowmap_plain(kHidden);
+    const int pc = prec_[SITE_COND], pcp = prec_[SITE_CONVPOS];
+    const SplitBuf gm1 = w.gm1.as(pcp, satp(SITE_CONVPOS)), gm2 = w.gm2.as(pcp, satp(SITE_CONVPOS));
+    HIPC(gemm_store(ops(x_t, rowmap_plain(kLatent), inproj_, M), ACT_NONE,
+                    store_to(w.h, rh, rawp("dit.input_embed.proj.bias")), 1, pc, st));
+    HIPC(launch_convpos_pack(w.h, mask, gm1.hi, gm1.lo, B, N, kConvG, kConvCpg, kConvPad, kConvGs, st));
+    if (init_ws) {   // pad frames of the second conv's image (its producer writes the data frames only)
         HIPC(hipMemsetAsync(w.gm2.hi, 0, w.gm_elems * 2, st));
         if (pcp == PREC_BF16X3) HIPC(hipMemsetAsync(w.gm2.lo, 0, w.gm_elems * 2, st));
     }
@@ -1209,41 +1261,41 @@ int Engine::denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, 
                          kConvPad, kConvGs, nullptr, nullptr, convpos_by_group_ ? 1 : 0};
         HIPC(gemm3_convpos(g, true, e2, nz, pcp, st));
     }
-    // zero the padded tail columns [2400, 2432) of the FF hidden once per call
-    if (init_ws) {
+    return 0;
+}
+
+// D5-D8: DiT blocks [l0, l1) on the residual stream w.x (dit.py:189-212, 95-135)
+int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0, int l1) {
+    const int B = d.B, N = d.N, R = d.R, P = d.P, M = B * N;
+    const uint8_t* const mask = d.mask;
+    const uint8_t *const ref_mask = d.ref_mask, *const ph_mask = d.ph_mask;
+    const float *const k_ref = d.k_ref, *const v_ref = d.v_ref, *const k_text = d.k_text, *const v_text = d.v_text;
+    const float* const mod = d.mod;
+    const int mod_row0 = d.mod_row0, mod_rstride = d.mod_rstride;
+    const CrossImg& ci = *d.ci;
+    const RowMap rh = rowmap_plain(kHidden);
+    const int pb = prec_[SITE_DIT_BLOCK], pc = prec_[SITE_COND];
+    unsigned* const sb = satp(SITE_DIT_BLOCK);
+    const SplitBuf yb = w.y.as(pb, sb), ob = w.o.as(pb, sb), ffh = w.ffh.as(pb, sb);
+    if (!(attn_img_ && attn_epi_) && ensure_qkvg_unpadded()) return 1;
+    // zero the padded tail columns [2400, 2432) of the FF hidden once per workspace use
+    if (d.init_ws) {
         HIPC(hipMemsetAsync(w.ffh.hi, 0, (size_t)M * kFFp * 2, st));
         if (pb == PREC_BF16X3) HIPC(hipMemsetAsync(w.ffh.lo, 0, (size_t)M * kFFp * 2, st));
     }
-    const float* rc = rope_dit_cos_;
-    const float* rs = rope_dit_sin_;
-    if (rope) {  // caller-supplied angle table (reference operator input, infer/onnx.py:42-47,122)
-        HIPC(launch_rope_cossin(rope, w.rope_c, w.rope_s, N * 64, st));
-        rc = w.rope_c;
-        rs = w.rope_s;
-    }
+    const float* const rc = d.rc;
+    const float* const rs = d.rs;
     // The AdaLN in front of each GEMM is fused into the kernel that produced the residual stream it normalises
-    // (split-K reduction + gated residual + LayerNorm-modulate in one pass); only the very first one runs alone.
-    if (join_pending_) {   // the modulation table is being computed on the side stream (sample)
-        HIPC(hipStreamWaitEvent(st, ev_join_, 0));
-        join_pending_ = false;
-    }
-    // LN-fold (gemm.hpp LnFoldIn): inside the fused sampler — one modulation row for the whole batch, tables from modulation() —
-    // the AdaLN between two block GEMMs lives in their epilogues; the first AdaLN of a step (here) and the final one (velocity
-    // head, SITE_COND precision) keep their ln_modulate, the first one also writes the row means the producers shift by
-    const bool fold = ftab && mod_rstride == 0 && dit_fold_on(M);   // (ftab: the tables sample() planned by the same predicate)
+    // (split-K reduction + gated residual + LayerNorm-modulate in one pass); only the first one of the range runs alone.
+    // LN-fold: the first AdaLN (here) and the final one (velocity head, SITE_COND precision) keep their ln_modulate, the first one
+    // also writes the row means the producers shift by
+    const bool fold = d.frow != nullptr;
     float* const lnc = fold && LN_FOLD_SHIFT ? w.lnc : nullptr;
-    HIPC(launch_ln_modulate(w.x, nullptr, yb.hi, yb.lo, M, kHidden, 1e-6f, mod + 0 * kHidden, mod + 1 * kHidden, kModLd,
-                            mod_row0, mod_rstride, N, st, lnc));
-    // split-K exists to fill the chip at M = 600 (150 tiles of 64x64 for N = 960); the 3B-row CFG batches of the teacher
-    // sampler (M = 1800: 435 tiles) fill it without, and the fused epilogue is cheaper than partials + reduce (495 -> 454 ms)
-    // ... and so do several batches in flight (throughput tuning): there the unsplit GEMM + a separate AdaLN costs 2.3x fewer
-    // workgroup-microseconds than three K slices + reduce, and that is what counts when other streams want the CUs
-    static const bool splitk_tp = lab_env("SMTTS_SPLITK_TP") && atoi(lab_env("SMTTS_SPLITK_TP")) != 0;   // (A/B only)
-    const bool unsplit = M > 1024 || (tuning_ == TUNE_THROUGHPUT && !splitk_tp);
-    const int ks_out = unsplit ? 1 : ksplit_out_, ks_ff2 = unsplit ? 1 : ksplit_ff2_;
-    if (!(attn_img_ && attn_epi_) && ensure_qkvg_unpadded()) return 1;
+    HIPC(launch_ln_modulate(w.x, nullptr, yb.hi, yb.lo, M, kHidden, 1e-6f, mod + (long)l0 * kModPerBlock + 0 * kHidden,
+                            mod + (long)l0 * kModPerBlock + 1 * kHidden, kModLd, mod_row0, mod_rstride, N, st, lnc));
+    const int ks_out = d.ks_out, ks_ff2 = d.ks_ff2;
     const float* const mrow = mod + (long)mod_row0 * kModLd;            // this step's modulation row (fold path only)
-    const float* const frow = fold ? ftab + (long)mod_row0 * 2 * kFoldNF : nullptr;   // [0]: W shift, [1]: W (1 + scale)
+    const float* const frow = d.frow;
     auto fold_in = [&](int l, int site) {
         LnFoldIn f;
         f.part = w.lnpart; f.NP = kLnGroups; f.inv_c = 1.0f / kHidden; f.eps = 1e-6f;
@@ -1253,7 +1305,7 @@ int Engine::denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, 
         f.cshift = lnc;
         return f;
     };
-    for (int l = 0; l < kBlocks; ++l) {
+    for (int l = l0; l < l1; ++l) {
         const DitBlockW& b = blocks_[l];
         const float* m = mod + (long)l * kModPerBlock;
         // D5 AdaLN-Zero (dit.py:19-25) already in w.y; D6 joint attention (dit.py:95-135)
@@ -1280,14 +1332,14 @@ int Engine::denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, 
             pk.q = w.qi.hi; pk.q_lo = img_lo(pa, w.qi.lo); pk.k = w.ki.hi; pk.k_lo = img_lo(pa, w.ki.lo); pk.vt = w.vti.hi; pk.vt_lo = img_lo(pa, w.vti.lo);
             pk.g = w.gi.hi; pk.g_lo = img_lo(pa, w.gi.lo);
             pk.B = B; pk.N = N; pk.H = kHeads; pk.dh = kDh; pk.dhp = 128; pk.Np = Np;
-            if (l == 0 && Np != N && init_ws) {   // pad key columns of V^T (the producer only writes n < N)
+            if (l == l0 && Np != N && d.init_ws) {   // pad key columns of V^T (the producer only writes n < N)
                 HIPC(hipMemsetAsync(w.vti.hi, 0, w.vt_elems * 2, st));
                 if (pa == PREC_BF16X3) HIPC(hipMemsetAsync(w.vti.lo, 0, w.vt_elems * 2, st));
             }
             if (epi) {
                 EpiQKV eq{b.b_qkvgp, pk.qw, pk.kw, pk.rope_cos, pk.rope_sin, pk.eps, pk.q_scale, pk.rot_dim, pa,
                           pk.q, pk.q_lo, pk.k, pk.k_lo, pk.vt, pk.vt_lo, pk.g, pk.g_lo, N, kHeads, kDh, 128, Np};
-                if (fold && l > 0) eq.fold = fold_in(l, 0);   // w.y = x (1 + scale_msa), written by the previous block's FF2 epilogue
+                if (fold && l > l0) eq.fold = fold_in(l, 0);   // w.y = x (1 + scale_msa), written by the previous block's FF2 epilogue
                 HIPC(gemm3_qkv(ops3(w.y, rh, b.qkvgp, M, pb), eq, pb, st));
             } else {
                 HIPC(launch_qkv_pack(pk, st));
@@ -1350,9 +1402,14 @@ int Engine::denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, 
                                     mod_rstride, N, st));
         }
     }
-    // velocity head (model.py:100) on the final AdaLN output
-    HIPC(gemm3_store(ops3(w.y, rh, velocity_, M, pc), ACT_NONE, store_to(velocity, rowmap_plain(kLatent), rawp("velocity.bias")),
-                     1, pc, st));
+    return 0;
+}
+
+// velocity head (model.py:100) on the final AdaLN image in w.y (SITE_COND format)
+int Engine::dit_head(hipStream_t st, const CoreWs& w, int M, float* velocity) {
+    const int pc = prec_[SITE_COND];
+    HIPC(gemm3_store(ops3(w.y, rowmap_plain(kHidden), velocity_, M, pc), ACT_NONE,
+                     store_to(velocity, rowmap_plain(kLatent), rawp("velocity.bias")), 1, pc, st));
     return 0;
 }
 
@@ -2060,6 +2117,198 @@ int Engine::test_codec_stage(hipStream_t st, int part, int stage, int what, cons
     if (rc) return rc;
     if (es != hipSuccess) return fail_hip(es, "test_codec_stage: stream");
     if (ef != hipSuccess) return fail_hip(ef, "test_codec_stage: free");
+    return 0;
+}
+
+// DiT / encoder stages through the code of denoise_step / sample / cond_encode (include/smalltts_hip.h smtts_test_dit_stage).  The
+// workspace is planned by the product's own planners (ModWs + CoreWs + the cross images, EncWs) and filled with 0xff first.
+int Engine::test_dit_stage(hipStream_t st, int net, int what, int l0, int l1, int path, int twice, const void* xin,
+                           const uint8_t* mask, int B, int S, const float* t, const float* modin, int mod_rows, int mod_row0,
+                           int mod_rstride, const float* k_ref, const float* v_ref, const uint8_t* ref_mask, int R,
+                           const float* k_text, const float* v_text, const uint8_t* ph_mask, int P, const float* rope,
+                           float* x_out, float* img_out, float* shift_out, float* out, float* k_out, float* v_out, float* mod_out) {
+    DeepScope deep_scope(gemm_deep_);
+    if (!dit_ready_) return fail("test_dit_stage: DiT weights not finalized");
+    if (net < 0 || net > 2) return fail("test_dit_stage: net must be 0 (DiT), 1 (style encoder) or 2 (text encoder)");
+    if (what <= 0 || what > 15) return fail("test_dit_stage: `what` must be a non-empty set of the bits 1, 2, 4, 8");
+    if (path < 0 || path > 3) return fail("test_dit_stage: path must be 0 (the operator's choice), 1 (fold), 2 (split-K) or 3 (unsplit)");
+    if (B <= 0 || S <= 0) return fail("test_dit_stage: B and S must be positive");
+    if (S > kMaxPos) return fail("test_dit_stage: sequence longer than the rope table (4096)");
+    if ((long)B * S > (1L << 20)) return fail("test_dit_stage: too many rows");
+    const bool dit = net == 0;
+    const EncoderW* enc = net == 1 ? &style_ : net == 2 ? &text_ : nullptr;
+    const int L = dit ? kBlocks : (int)enc->blocks.size(), M = B * S, D = dit ? kHidden : enc->dim;
+    // the chain bits (DiT: 2 embed, 4 blocks, 8 head; mod = bit 1 rides along.  Encoders: 1 in, 2 blocks, 4 out, 8 kv) form a run
+    const int chain = dit ? what & 14 : what;
+    {
+        int first = -1, last = -1;
+        for (int k = 0; k < 4; ++k)
+            if (chain & (1 << k)) { if (first < 0) first = k; last = k; }
+        for (int k = first; first >= 0 && k <= last; ++k)
+            if (!(chain & (1 << k))) return fail("test_dit_stage: `what` bits are not a run in pipeline order");
+    }
+    const int BLK = dit ? 4 : 2, FIRST = dit ? 2 : 1, AFTER = dit ? 8 : 4;
+    const bool blocks = (what & BLK) != 0;
+    if (blocks && (l0 < 0 || l0 >= l1 || l1 > L)) return fail("test_dit_stage: block range [l0, l1) outside [0, " + std::to_string(L) + ")");
+    if (blocks && (what & FIRST) && l0 != 0) return fail("test_dit_stage: the input stage feeds block 0 only");
+    if (blocks && (what & AFTER) && l1 != L) return fail("test_dit_stage: the stage after the blocks reads the last block's output only");
+    if (R < 0 || P < 0 || R > kMaxPos || P > kMaxPos) return fail("test_dit_stage: R / P outside [0, 4096]");
+    if (!xin && chain) return fail("test_dit_stage: null input");
+    // the path of the block stage: what the product runs on this call (0), or one of its paths, refused where the product never takes it
+    bool fold = false;
+    int ks = 1;
+    const int ks_dit = tuning_ == TUNE_THROUGHPUT || M > 1024 ? 1 : ksplit_out_;   // (denoise_step's choice outside the fold)
+    if (dit) {
+        if (path == 1 && !dit_fold_on(M)) return fail("test_dit_stage: no LN-fold here (M > 1024, fold off, or no epilogue attention)");
+        if (path == 1 && (mod_rstride != 0 || (what & BLK) == 0)) return fail("test_dit_stage: the fold runs blocks with one modulation row only");
+        if (path == 2 && (M > 1024 || ksplit_out_ < 2)) return fail("test_dit_stage: no split-K at M > 1024");
+        fold = path == 1;
+        ks = path == 2 ? ksplit_out_ : path == 3 ? 1 : ks_dit;   // (the fold's last FF2 leaves it: the operator's choice there)
+        if (what & (1 | 4)) {   // a modulation table: from t (bit 1) or the caller
+            if (mod_rows <= 0 || mod_row0 < 0 || mod_rstride < 0 || mod_rstride > 1 || mod_row0 + (long)(B - 1) * mod_rstride >= mod_rows)
+                return fail("test_dit_stage: modulation rows / row0 / stride do not cover the batch");
+            if ((what & 1) ? !t : !modin) return fail("test_dit_stage: null t / modulation table");
+        }
+        if ((what & 4) && !mask) return fail("test_dit_stage: null mask");
+        if ((what & 2) && !mask) return fail("test_dit_stage: null mask");
+        if ((what & 4) && ((R > 0 && (!k_ref || !v_ref || !ref_mask)) || (P > 0 && (!k_text || !v_text || !ph_mask))))
+            return fail("test_dit_stage: null cross cache / mask");
+    } else {
+        if (path == 1 && !(fold_epi_on() && D % 64 == 0)) return fail("test_dit_stage: no RMSNorm fold here");
+        if (path == 2 && ksplit_enc_ < 2) return fail("test_dit_stage: split-K is off in this build");
+        fold = path == 1 || (path == 0 && fold_epi_on() && D % 64 == 0);
+        ks = path == 3 ? 1 : ksplit_enc_;
+        if ((what & (2 | 4)) && !mask) return fail("test_dit_stage: null key mask");
+    }
+    if (!dit && (what & 8) && (!k_out || !v_out)) return fail("test_dit_stage: null K / V output");
+
+    HIPC(hipSetDevice(device_));
+    // workspace: as denoise_step / sample plan it (modulation table + LN-fold tables, core, cross images), or as cond_encode does
+    const bool need_mod = dit && (what & (1 | 4));
+    size_t bytes;
+    {
+        Bump b(nullptr);
+        if (dit) {
+            ModWs m;
+            m.plan(b, need_mod ? mod_rows : 1, fold);
+            bytes = ((b.off + 255) & ~size_t(255)) + ((denoise_core_bytes(B, S) + 255) & ~size_t(255)) + cross_img_bytes(B, R, P);
+        } else {
+            EncWs e;
+            e.plan(b, B, S);
+            bytes = b.off + 256;
+        }
+    }
+    void* ws = nullptr;
+    HIPC(hipMalloc(&ws, bytes));
+    int rc = 0;
+    {
+        ProfTag ptag(dit ? "dit" : "enc");
+        // all-ones bytes: NaN in every operand format; a kernel that read what nobody wrote would turn it into NaN in the output
+        auto run = [&](bool init_ws) -> int {
+            Bump bump(ws);
+            if (dit) {
+                ModWs m;
+                m.plan(bump, need_mod ? mod_rows : 1, fold);
+                char* core = static_cast<char*>(ws) + ((bump.off + 255) & ~size_t(255));
+                Bump cb(core);
+                CoreWs w;
+                w.plan(cb, B, S);
+                if (need_mod) {
+                    if (what & 1) {
+                        if (modulation(st, t, mod_rows, m.sinb, m.t1, m.temb, m.e1, m.semb, m.mod, fold ? m.ftab : nullptr)) return 1;
+                    } else {
+                        HIPC(hipMemcpyAsync(m.mod, modin, (size_t)mod_rows * kModLd * 4, hipMemcpyDeviceToDevice, st));
+                        if (fold && fold_tables(st, m.mod, mod_rows, m.ftab)) return 1;
+                    }
+                    if (mod_out) HIPC(hipMemcpyAsync(mod_out, m.mod, (size_t)mod_rows * kModLd * 4, hipMemcpyDeviceToDevice, st));
+                }
+                if (what & 2) {
+                    if (dit_embed(st, w, static_cast<const float*>(xin), mask, B, S, init_ws)) return 1;
+                } else if (what & 4) {
+                    HIPC(hipMemcpyAsync(w.x, xin, (size_t)M * kHidden * 4, hipMemcpyDeviceToDevice, st));
+                }
+                if (what & 4) {
+                    CrossImg ci;
+                    if (pack_cross(st, k_ref, v_ref, k_text, v_text, B, R, P, core + ((denoise_core_bytes(B, S) + 255) & ~size_t(255)), ci))
+                        return 1;
+                    DitRun d;
+                    d.rc = rope_dit_cos_;
+                    d.rs = rope_dit_sin_;
+                    if (rope) {
+                        HIPC(launch_rope_cossin(rope, w.rope_c, w.rope_s, S * 64, st));
+                        d.rc = w.rope_c;
+                        d.rs = w.rope_s;
+                    }
+                    d.mask = mask; d.mod = m.mod; d.mod_row0 = mod_row0; d.mod_rstride = mod_rstride;
+                    d.k_ref = k_ref; d.v_ref = v_ref; d.ref_mask = ref_mask; d.k_text = k_text; d.v_text = v_text; d.ph_mask = ph_mask;
+                    d.ci = &ci;
+                    d.frow = fold ? m.ftab + (long)mod_row0 * 2 * kFoldNF : nullptr;
+                    d.ks_out = ks == 1 ? 1 : ksplit_out_;
+                    d.ks_ff2 = ks == 1 ? 1 : ksplit_ff2_;
+                    d.B = B; d.N = S; d.R = R; d.P = P;
+                    d.init_ws = init_ws;
+                    if (dit_blocks(st, w, d, l0, l1)) return 1;
+                    const int pi = prec_[l1 == kBlocks ? SITE_COND : SITE_DIT_BLOCK];
+                    if (img_out) {
+                        const SplitBuf y = w.y.as(pi, nullptr);
+                        HIPC(launch_split_to_f32(y.hi, y.lo, img_out, (long)M * kHidden, st));
+                    }
+                    if (shift_out) {
+                        if (fold && LN_FOLD_SHIFT) HIPC(hipMemcpyAsync(shift_out, w.lnc, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
+                        else HIPC(hipMemsetAsync(shift_out, 0, (size_t)M * 4, st));
+                    }
+                }
+                if ((what & (2 | 4)) && x_out) HIPC(hipMemcpyAsync(x_out, w.x, (size_t)M * kHidden * 4, hipMemcpyDeviceToDevice, st));
+                if (what & 8) {
+                    if (!(what & 4)) {   // the input as the final AdaLN image the last block would have left (SITE_COND format)
+                        const SplitBuf y = w.y.as(prec_[SITE_COND], nullptr);
+                        HIPC(launch_to_split(static_cast<const float*>(xin), rowmap_plain(kHidden), y.hi, y.lo, rowmap_plain(kHidden), M,
+                                             kHidden, st));
+                    }
+                    if (out && dit_head(st, w, M, out)) return 1;
+                }
+                return 0;
+            }
+            EncWs w;
+            w.plan(bump, B, S);
+            const bool text = net == 2;
+            if (what & 1) {
+                if (text ? text_in(st, w, static_cast<const int64_t*>(xin), B, S) : style_in(st, w, static_cast<const float*>(xin), B, S))
+                    return 1;
+            } else if (what & 2) {
+                HIPC(hipMemcpyAsync(w.x, xin, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
+            }
+            if (what & 2) {
+                if (enc_blocks(st, *enc, w, l0, l1, B, S, mask, fold, ks)) return 1;
+                if (img_out) {
+                    const SplitBuf y = w.y.as(prec_[SITE_ENCODER], nullptr);
+                    HIPC(launch_split_to_f32(y.hi, y.lo, img_out, (long)M * D, st));
+                }
+            }
+            if ((what & (1 | 2)) && x_out) HIPC(hipMemcpyAsync(x_out, w.x, (size_t)M * D * 4, hipMemcpyDeviceToDevice, st));
+            float* seq = out ? out : w.seq;
+            if (what & 4) {
+                if (!(what & 2)) {   // the input as the final norm image (SITE_ENCODER format)
+                    const SplitBuf y = w.y.as(prec_[SITE_ENCODER], nullptr);
+                    HIPC(launch_to_split(static_cast<const float*>(xin), rowmap_plain(D), y.hi, y.lo, rowmap_plain(D), M, D, st));
+                }
+                if (enc_out(st, text, w, M, mask, seq)) return 1;
+            }
+            if (what & 8) {
+                const float* src = (what & 4) ? seq : static_cast<const float*>(xin);
+                if (enc_kv(st, text, w, src, B, S, k_out, v_out)) return 1;
+            }
+            return 0;
+        };
+        rc = hipMemsetAsync(ws, 0xff, bytes, st) != hipSuccess ? fail("test_dit_stage: memset") : run(true);
+        // twice: a second run on the same workspace, as the sampler's later steps find it (its never-written regions are not zeroed again)
+        if (!rc && twice) rc = run(false);
+    }
+    const hipError_t es = hipStreamSynchronize(st);
+    const hipError_t ef = hipFree(ws);
+    if (rc) return rc;
+    if (es != hipSuccess) return fail_hip(es, "test_dit_stage: stream");
+    if (ef != hipSuccess) return fail_hip(ef, "test_dit_stage: free");
     return 0;
 }
 

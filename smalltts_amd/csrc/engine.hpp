@@ -194,6 +194,12 @@ class Engine {
     // one codec stage through the code of codec_decode (part 1) / codec_encode (part 2): include/smalltts_hip.h smtts_test_codec_stage
     int test_codec_stage(hipStream_t st, int part, int stage, int what, const float* x, int B, int T_in, int C_in, float* out,
                          int* T_out, int* C_out);
+    // DiT / encoder stages through the code of denoise_step / sample / cond_encode: include/smalltts_hip.h smtts_test_dit_stage
+    int test_dit_stage(hipStream_t st, int net, int what, int l0, int l1, int path, int twice, const void* x, const uint8_t* mask, int B,
+                       int S, const float* t, const float* mod, int mod_rows, int mod_row0, int mod_rstride, const float* k_ref,
+                       const float* v_ref, const uint8_t* ref_mask, int R, const float* k_text, const float* v_text,
+                       const uint8_t* ph_mask, int P, const float* rope, float* x_out, float* img_out, float* shift_out, float* out,
+                       float* k_out, float* v_out, float* mod_out);
 
     // fp16 range guard: per-site count of values that fp16 producers clamped to +-65504 since the last reset (device counters,
     // common.hpp sat_note) + the static part: codec FFN blocks whose fused kernels' hidden / input bound could not be certified
@@ -216,10 +222,21 @@ class Engine {
     int finalize_dit();
     int finalize_codec(bool decoder);
     int build_encoder(EncoderW& e, const std::string& prefix, int dim, int heads, int ff, int layers, float eps);
-    int run_encoder(hipStream_t st, const EncoderW& e, void* enc_ws, int B, int S, const uint8_t* key_mask);
     int make_rope(int dim, float** cos_out, float** sin_out);
     int modulation(hipStream_t st, const float* t_dev, int rows, float* sinb, float* t1, float* temb, float* e1,
                    float* semb, float* mod, float* ftab = nullptr);
+    int fold_tables(hipStream_t st, const float* mod, int rows, float* ftab);   // LN-fold tables of `rows` modulation rows (fold_vectors)
+    // ---- condition encoders: one call = per encoder in, blocks [0, L), out, kv.  cond_encode and the test hook (test_dit_stage) run
+    // the same functions on workspaces planned the same way (EncWs)
+    struct EncWs;
+    int style_in(hipStream_t st, const EncWs& w, const float* ref, int B, int R);
+    int text_in(hipStream_t st, const EncWs& w, const int64_t* ids, int B, int P);
+    // blocks [l0, l1): the RMSNorm of block l0 runs as a launch; ends in the image of block l1's RMSNorm (l1 = L: the final norm) in w.y.
+    // fold: the norms between block GEMMs live in their epilogues; ks: K slices of the residual projections outside the fold (1: unsplit)
+    int enc_blocks(hipStream_t st, const EncoderW& e, const EncWs& w, int l0, int l1, int B, int S, const uint8_t* key_mask, bool fold,
+                   int ks);
+    int enc_out(hipStream_t st, bool text, const EncWs& w, int M, const uint8_t* key_mask, float* seq);
+    int enc_kv(hipStream_t st, bool text, const EncWs& w, const float* seq, int B, int S, float* k, float* v);
     struct DenoiseWs;
     // cross-KV cache of all layers in the attention kernel's operand format (attention_img.hip), built once per sampler call
     struct CrossImg { bf16_t *kc = nullptr, *kc_lo = nullptr, *vtc = nullptr, *vtc_lo = nullptr; int Rp = 0, Cp = 0; };
@@ -231,6 +248,26 @@ class Engine {
                      const float* k_text, const float* v_text, const uint8_t* ph_mask, const float* rope, int B,
                      int N, int R, int P, float* velocity, char* ws, const CrossImg& ci, const float* ftab = nullptr);
     size_t denoise_core_bytes(int B, int N) const;
+    // ---- DiT: one evaluation = embed, blocks [0, 12), head (denoise_core); the modulation table comes from modulation()
+    struct CoreWs;
+    struct DitRun {   // what the block stages read besides the residual stream
+        const uint8_t* mask = nullptr;
+        const float* mod = nullptr;
+        int mod_row0 = 0, mod_rstride = 0;
+        const float *k_ref = nullptr, *v_ref = nullptr, *k_text = nullptr, *v_text = nullptr;
+        const uint8_t *ref_mask = nullptr, *ph_mask = nullptr;
+        const float *rc = nullptr, *rs = nullptr;   // rope cos / sin [N][64]
+        const CrossImg* ci = nullptr;
+        const float* frow = nullptr;   // LN-fold tables of this step's modulation row: non-null = the fold path
+        int ks_out = 1, ks_ff2 = 1;    // K slices of the out-proj / FF2 launches outside the fold (1: unsplit GEMM + ln_modulate)
+        int B = 0, N = 0, R = 0, P = 0;
+        bool init_ws = true;           // zero the regions no kernel writes (the sampler's later steps find them as the first one left them)
+    };
+    int dit_embed(hipStream_t st, const CoreWs& w, const float* x_t, const uint8_t* mask, int B, int N, bool init_ws);
+    // blocks [l0, l1): the AdaLN of block l0 runs as the ln_modulate launch (and seeds the fold's row shift); each block ends in the
+    // next block's AdaLN image in w.y — after block 11 the final AdaLN (SITE_COND format)
+    int dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0, int l1);
+    int dit_head(hipStream_t st, const CoreWs& w, int M, float* velocity);
     // runs one block; the result lives in *x on return (the fused mixer ping-pongs *x <-> *xalt)
     int ensure_qkvg_unpadded();   // packs DitBlockW::qkvg of every block on first use of an A/B attention path
     bool qkvg_unpadded_ready_ = false;   // ... set only after EVERY block packed (a failure half-way unlinks what was built)

@@ -541,6 +541,58 @@ class HipEngine:
                                                  C.byref(t_out), C.byref(c_out)), "test_codec_stage")
         return out
 
+    def test_dit_stage(self, net: str, what: int, x=None, mask=None, l0: int = 0, l1: Optional[int] = None, path: str = "auto",
+                       twice: bool = False, t=None, mod=None, mod_row0: int = 0, mod_rstride: int = 0, k_ref=None, v_ref=None,
+                       ref_mask=None, k_text=None, v_text=None, ph_mask=None, rope=None) -> Dict[str, torch.Tensor]:
+        """DiT / condition-encoder stages through the product's code (include/smalltts_hip.h smtts_test_dit_stage).  net: "dit", "style"
+        or "text"; what: a run of the chain bits (DiT: 1 modulation from t, 2 embed, 4 blocks [l0, l1), 8 head; encoders: 1 input,
+        2 blocks, 4 output projection, 8 cross K / V).  path: "auto" (the operator's choice), "fold", "splitk" or "unsplit".
+        Returns the device tensors that apply: "x" residual, "img" the operand image the blocks leave (fp32), "shift" the fold's
+        row shift, "out" velocity / ref_seq / phoneme memory, "k" / "v", "mod" the modulation table."""
+        netc = {"dit": 0, "style": 1, "text": 2}[net]
+        pathc = {"auto": 0, "fold": 1, "splitk": 2, "unsplit": 3}[path]
+        dev, f = self.device, (lambda a: None if a is None else self._dev(a, torch.float32))
+        if x is not None:
+            x = self._dev(x, torch.int64 if (net == "text" and what & 1) else torch.float32)
+            B, S = x.shape[:2]
+        else:
+            B, S = 1, 1
+        if mask is not None:
+            mask = self._dev(mask, torch.bool)
+            B, S = mask.shape
+        t, mod, k_ref, v_ref, k_text, v_text, rope = map(f, (t, mod, k_ref, v_ref, k_text, v_text, rope))
+        ref_mask = None if ref_mask is None else self._dev(ref_mask, torch.bool)
+        ph_mask = None if ph_mask is None else self._dev(ph_mask, torch.bool)
+        rows = t.shape[0] if t is not None else mod.shape[0] if mod is not None else 0
+        R = 0 if k_ref is None else k_ref.shape[3]
+        P = 0 if k_text is None else k_text.shape[3]
+        dit = net == "dit"
+        D = 960 if dit else 512
+        if l1 is None:
+            l1 = N_LAYERS if net != "text" else 8
+        e = lambda *sh: torch.empty(*sh, device=dev)
+        res: Dict[str, torch.Tensor] = {}
+        if what & (6 if dit else 3):
+            res["x"] = e(B, S, D)
+        if what & (4 if dit else 2):
+            res["img"] = e(B, S, D)
+            if dit:
+                res["shift"] = e(B, S)
+        if dit and what & 8:
+            res["out"] = e(B, S, LATENT)
+        if not dit and what & 4:
+            res["out"] = e(B, S, 960)
+        if not dit and what & 8:
+            res["k"], res["v"] = e(N_LAYERS, B, N_HEADS, S, HEAD_DIM), e(N_LAYERS, B, N_HEADS, S, HEAD_DIM)
+        if dit and what & 1:
+            res["mod"] = e(rows, 71040)
+        self._ck(self.lib.smtts_test_dit_stage(self.h, self._stream(), netc, int(what), int(l0), int(l1), pathc, int(bool(twice)),
+                                               _p(x), _p(mask), B, S, _p(t), _p(mod), rows, int(mod_row0), int(mod_rstride),
+                                               _p(k_ref), _p(v_ref), _p(ref_mask), R, _p(k_text), _p(v_text), _p(ph_mask), P, _p(rope),
+                                               _p(res.get("x")), _p(res.get("img")), _p(res.get("shift")), _p(res.get("out")),
+                                               _p(res.get("k")), _p(res.get("v")), _p(res.get("mod"))), "test_dit_stage")
+        return res
+
     def test_swiglu(self, A, W1, W3, b1=None, b3=None, split=3):
         A, W1, W3 = (self._dev(x, torch.float32) for x in (A, W1, W3))
         b1 = None if b1 is None else self._dev(b1, torch.float32)
