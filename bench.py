@@ -3,6 +3,7 @@
 
     python bench.py --gpus N --steps K --warmup W          (N > 1: launched by torch.distributed.run)
     python bench.py ... --dump-outputs DIR                 (+ DIR/audio.npy: what the last of the K timed steps returned)
+    python bench.py ... --full                             (+ everything the headline does not need, below)
 
 One "step" = one pass of the hot path over one batch per GPU: condition-encode -> 4-step DMD sampler
 -> codec decode of B=8 utterances x 10 s (N=75 frames, R=15 reference frames, P=30 phoneme ids:
@@ -11,10 +12,14 @@ already resident in HBM, synthetic seeded weights (no released weights exist off
 every rank synthesises its own 8-utterance shard (weak scaling, no data-path collective) and the
 waveform shards are reassembled with one RCCL all-gather inside the timed step.
 
-Rank 0 prints ONE JSON line (contract in the task statement) including
-  roofline     : dominant kernel, algorithmic work / HIP-event time measured live on the launch stream
-  cpu_baseline : the CPU oracle (stand-in for the reference's ORT-CPU path, which cannot run offline)
-                 timed on this box's host cores on a bounded sample of the same workload.
+Rank 0 prints ONE JSON line (contract in the task statement).  A plain run does only what that line's headline needs: set-up,
+warm-up, the K timed steps, --dump-outputs, the line.  --full adds, after the timed steps (each leg can be left out with its
+--no-* option):
+  value_sequential : the same K steps one batch at a time on one stream (latency tuning)
+  secondary        : the other single-GPU configurations (clone, teacher128, dmd4 at R = 38 / P = 128), N = 1 only
+  roofline         : dominant kernel, algorithmic work / HIP-event time measured live on the launch stream
+  cpu_baseline     : the CPU oracle (stand-in for the reference's ORT-CPU path, which cannot run offline)
+                     timed on the host's cores on a bounded sample of the same workload, N = 1 only.
 """
 import argparse
 import json
@@ -418,8 +423,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=300,
-                    help="timed steps: the headline region and the one-batch-at-a-time leg each time exactly this many (default "
-                         "sized so the timed region is >= 3 s)")
+                    help="timed steps: the headline region and (--full) the one-batch-at-a-time leg each time exactly this many "
+                         "(default sized so the timed region is >= 3 s)")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--precision", default="f16",
                     help="f16 (default: one fp16 MFMA per product on the block / encoder / codec-FFN GEMMs, split-bf16 on the "
@@ -439,16 +444,22 @@ def main():
                     help="after the timed steps, write what the last timed step returned (the waveform batch a caller receives; "
                          "gathered over ranks at N > 1) as DIR/<name>.npy in float32, <= 64 MB in all; inputs, weights and step "
                          "seeds depend only on the arguments, so two builds can be compared output for output")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the legs the headline does not need: value_sequential, secondary, "
+                         "roofline, cpu_baseline (default off: a plain run times the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the cpu_baseline leg")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline leg")
     ap.add_argument("--tuning", default="auto", choices=["auto", "latency", "throughput"],
                     help="engine tuning of the timed region: auto = throughput with batches in flight, latency with one at a time; "
                          "forcing it lets tools/profile_round.sh trace the throughput-tuned kernels one batch at a time")
-    ap.add_argument("--no-sequential", action="store_true", help="skip the one-batch-at-a-time leg (value_sequential)")
+    ap.add_argument("--no-sequential", action="store_true", help="with --full: skip the one-batch-at-a-time leg (value_sequential)")
     ap.add_argument("--no-secondary", action="store_true",
-                    help="skip the `secondary` block (the other single-GPU configurations timed behind the headline in the same run: "
-                         "clone = BASELINE configs[2], teacher128 = configs[4], dmd4 at R = 38 / P = 128 = SURVEY 8(d)'s secondary point)")
+                    help="with --full: skip the `secondary` block (the other single-GPU configurations timed behind the headline in the "
+                         "same run: clone = BASELINE configs[2], teacher128 = configs[4], dmd4 at R = 38 / P = 128 = SURVEY 8(d)'s "
+                         "secondary point)")
     args = ap.parse_args()
+    if not args.full:       # a plain run: set-up, warm-up, the K timed steps, --dump-outputs and the line, nothing else
+        args.no_cpu_baseline = args.no_roofline = args.no_sequential = args.no_secondary = True
     ensure_world(args.gpus, sys.argv[1:])
 
     from smalltts_amd.parallel import ShardContext

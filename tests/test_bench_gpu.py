@@ -25,8 +25,8 @@ def _free_port():
 
 
 def test_bench_single_gpu_line_has_the_contract_fields_and_rooflines():
-    p = subprocess.run([sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--min-seconds", "2"], capture_output=True,
-                       text=True, timeout=900, cwd=ROOT)
+    p = subprocess.run([sys.executable, "bench.py", "--steps", "6", "--warmup", "2", "--min-seconds", "2", "--full"],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     r = _last_json(p.stdout)
     assert KEYS <= set(r) and r["n_gpus"] == 1 and r["steps"] == 6 and r["warmup"] == 2 and r["scaling"] == "weak"
@@ -140,19 +140,26 @@ def test_bench_gpus_2_without_a_launcher_relaunches_itself_as_two_ranks():
 def test_bench_dump_outputs_hold_the_last_of_exactly_k_timed_steps(tmp_path):
     """--dump-outputs DIR: by default the timed region is exactly --steps steps, run once, and DIR/audio.npy holds in float32 the
     waveform batch the LAST of them returned — bit for bit what bench.one_step gives for that step's seed on a fresh engine with
-    the same seeded weights and inputs under the timed region's throughput tuning, and not what the step before it gave."""
+    the same seeded weights and inputs under the timed region's throughput tuning, and not what the step before it gave.
+    Without --full the run does nothing else: no sequential, secondary, roofline or CPU leg, and at most 30 s of its wall time,
+    start to exit, lies outside the warm-up and timed steps."""
+    import time
+
     import numpy as np
     import torch
 
     import bench
     from smalltts_amd.engine import HipEngine
     K = 3
-    p = subprocess.run([sys.executable, "bench.py", "--steps", str(K), "--warmup", "1", "--no-roofline", "--no-cpu-baseline",
-                        "--no-secondary", "--no-sequential", "--dump-outputs", str(tmp_path / "out")], capture_output=True, text=True,
-                       timeout=900, cwd=ROOT)
+    t0 = time.perf_counter()
+    p = subprocess.run([sys.executable, "bench.py", "--steps", str(K), "--warmup", "1", "--dump-outputs", str(tmp_path / "out")],
+                       capture_output=True, text=True, timeout=900, cwd=ROOT)
+    wall = time.perf_counter() - t0
     assert p.returncode == 0, p.stderr[-2000:]
     r = _last_json(p.stdout)
     assert r["steps"] == K and r["repeats"] == 1 and r["timed_steps"] == K and r["config"]["tuning"] == "throughput"
+    assert r["value_sequential"] is None and not {"secondary", "roofline", "phase_roofline", "cpu_baseline"} & set(r)
+    assert wall - (K + 1) * r["ms_per_step"] * 1e-3 < 30.0, wall
     assert os.listdir(tmp_path / "out") == ["audio.npy"]
     a = np.load(tmp_path / "out" / "audio.npy")
     assert a.dtype == np.float32 and a.shape == (8, 1, 240000) and np.isfinite(a).all() and np.abs(a).max() > 0
