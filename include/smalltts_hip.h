@@ -49,9 +49,9 @@ int smtts_create(int device_id, smtts_handle* out);
 int smtts_destroy(smtts_handle h);
 const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation error */
 const char* smtts_version(void);
-/* bumped on every signature / default change: 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
+/* bumped on every signature / default change: 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
-#define SMTTS_ABI_VERSION 8
+#define SMTTS_ABI_VERSION 9
 int smtts_abi_version(void);
 
 /* ---- weights (replaces the ONNX initialisers; names/shapes = DiTModel.state_dict(),
@@ -149,6 +149,33 @@ int smtts_resample_poly(smtts_handle h, void* stream, const float* x, int channe
                         int down, int klen, int width, float* y, int64_t n_out);
 /* float [-1, 1] -> int16 PCM: clamp, x 32767, round to nearest (reference server audio.rs:22-37; CLIs write PCM_16, tryme.py:29) */
 int smtts_pcm16(smtts_handle h, void* stream, const float* x, int64_t n, int16_t* y);
+
+/* ---- long-form synthesis: one voice, many rows (DESIGN.md 'Long-form synthesis') ----------------------------------
+ * The two halves of smtts_cond_encode are independent (k_ref / v_ref depend on the reference only, k_text / v_text on the phonemes
+ * only; reference model.py:88-95, dit.py:80-93) and a half whose length is 0 is skipped: R = 0 with ref / ref_len / k_ref / v_ref /
+ * ref_mask NULL encodes the text half alone, P = 0 with phonemes / ph_mask / k_text / v_text NULL the voice half alone.  A voice is
+ * therefore encoded ONCE at B = 1, P = 0 and handed to every later batch:
+ * smtts_voice_expand gathers per-voice slabs into the batch cache smtts_sample / smtts_denoise_step take.  table: DEVICE int64
+ * [B][3] = (k_ptr, v_ptr, R_b), the device addresses of a voice's k_ref / v_ref (12,1,8,R_b,120) f32 as smtts_cond_encode(B = 1)
+ * wrote them; the same voice may appear in many rows.  -> k_ref, v_ref f32 (12,B,8,Rmax,120), ref_mask bool (B,Rmax): positions
+ * j < R_b are bit-identical copies and masked true, positions j >= R_b are zero and masked false (R_b is clamped to [0, Rmax]).
+ * One launch whatever B is; the slabs are read on `stream`, so they must stay alive and unchanged until that work has completed. */
+int smtts_voice_expand(smtts_handle h, void* stream, const int64_t* table, int B, int Rmax, float* k_ref, float* v_ref,
+                       uint8_t* ref_mask);
+/* per-row sampler noise in one launch: out f32 (n_steps,B,Nmax,64); row b of step s holds in [0, n[b] * 64) exactly what
+ * smtts_randn(n = n[b] * 64, seed = seeds[b], stream_id = s) writes, zeros behind (n[b] is clamped to [0, Nmax]) — a row's noise does
+ * not depend on its batch-mates.  seeds u64 (B) and n i64 (B) are DEVICE arrays. */
+int smtts_randn_rows(smtts_handle h, void* stream, float* out, const uint64_t* seeds, const int64_t* n, int n_steps, int B,
+                     int Nmax);
+/* joins rows of a decoded batch into one waveform: audio f32 (B,1,row_stride); len, off i64 (B) DEVICE arrays (samples of row b, its
+ * absolute offset in out); fade f32 (F) DEVICE table (F = 0: none, fade may be NULL).  For i < len[b]: out[off[b] + i] = audio[b][i] * g,
+ * F_b = min(F, len[b] / 2), g = fade[i] for i < F_b, fade[len[b] - 1 - i] for i >= len[b] - F_b, otherwise no multiply.  out has out_n
+ * elements: f32 (pcm16 = 0) or int16 (pcm16 != 0: smtts_pcm16's clamp, x 32767, round to nearest on the faded value).  Samples between
+ * rows are not written (zero-fill out once); samples outside [0, out_n) are dropped; len[b] is clamped to row_stride.  Several batches
+ * of one text write into the same out at different offsets.  One fp32 multiply by a table entry per sample: numpy reproduces it bit
+ * for bit. */
+int smtts_stitch(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* len, const int64_t* off,
+                 const float* fade, int F, void* out, int64_t out_n, int pcm16);
 
 /* cond_encode runs the text encoder on a side stream owned by the engine, one per caller stream (fork / join with events; default
  * on: shortest latency for one batch at a time).  Callers that keep several batches in flight on their own streams should turn it

@@ -4,7 +4,7 @@ src/smalltts/__init__.py:1-6: lazy attribute so importing the package stays chea
 
 
 def __getattr__(name):
-    if name in ("SmallTTS", "estimate_duration", "Encoder", "Decoder"):
+    if name in ("SmallTTS", "estimate_duration", "Encoder", "Decoder", "Voice", "split_text"):
         from . import api
         return getattr(api, name)
     raise AttributeError(name)

@@ -15,7 +15,7 @@ from __future__ import annotations
 import collections
 import hashlib
 import os
-from typing import Dict, Iterable, List, Optional, Sequence
+from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -34,6 +34,128 @@ _ENGINES: Dict[tuple, HipEngine] = {}
 
 def estimate_duration(text: str, min_sec: float = 0.5, max_sec: float = 30.0) -> float:
     return max(min_sec, min(len(text) / CHARS_PER_SECOND, max_sec))
+
+
+# ---- long-form text: pieces the model was trained for (5 - 198 phonemes, at most ~30 s per utterance) --------------------------
+_SENTENCE_END = ".!?…"
+_CLAUSE_END = ";:,—"
+
+
+def _default_count_tokens(s: str) -> int:
+    from .phonemes import get_token_ids
+    return len(get_token_ids(s))
+
+
+def _hard_cut(word: str, fits: Callable[[str], bool]) -> List[str]:
+    """A single whitespace-free run that is over budget: longest fitting prefixes, never ending inside an `[event]` tag."""
+    from .phonemes import _EVENT_RE
+    out = []
+    while word and not fits(word):
+        tags = [m.span() for m in _EVENT_RE.finditer(word)]
+        cut = 0
+        for n in range(len(word) - 1, 0, -1):
+            if any(a < n < b for a, b in tags):
+                continue
+            if fits(word[:n]):
+                cut = n
+                break
+        if cut == 0:
+            raise ValueError(f"split_text: the budgets do not admit even one character or [event] tag of {word[:24]!r}")
+        out.append(word[:cut])
+        word = word[cut:]
+    if word:
+        out.append(word)
+    return out
+
+
+def split_text(text: str, max_tokens: int = 198, max_seconds: float = 30.0,
+               count_tokens: Optional[Callable[[str], int]] = None) -> List[str]:
+    """Cuts a text into pieces that each fit one utterance: `count_tokens(piece) <= max_tokens` and
+    `len(piece) / CHARS_PER_SECOND <= max_seconds` (estimate_duration without its clamp).  Cuts prefer sentence ends (`.!?…` in
+    front of whitespace or the end), then clause punctuation (`;:,—`), then whitespace; only a whitespace-free run that is over
+    budget on its own is cut inside, and never inside an `[event]` tag.  Greedy: a piece is extended while the next unit still
+    fits, so short sentences share a piece.  " ".join(pieces) is the text with runs of whitespace collapsed (up to hard cuts).
+    `count_tokens` defaults to len(phonemes.get_token_ids(s)), which needs espeak."""
+    count = count_tokens or _default_count_tokens
+
+    def fits(s: str) -> bool:
+        return len(s) / CHARS_PER_SECOND <= max_seconds and count(s) <= max_tokens
+
+    def pack(units: List[List[str]], level: int) -> List[List[str]]:
+        """units: runs of words that end at a boundary of `level` (0 sentence, 1 clause, 2 word).  Greedy in-order packing; a unit
+        that does not fit on its own is split at the next weaker boundary."""
+        pieces: List[List[str]] = []
+        cur: List[str] = []
+        for u in units:
+            if cur and fits(" ".join(cur + u)):
+                cur = cur + u
+                continue
+            if cur:
+                pieces.append(cur)
+                cur = []
+            if fits(" ".join(u)):
+                cur = u
+            elif level < 2:
+                sub = pack(_units(u, level + 1), level + 1)
+                pieces.extend(sub[:-1])
+                cur = sub[-1]        # the tail may still take what follows
+            else:                    # one word over budget
+                sub = [[w] for w in _hard_cut(u[0], fits)]
+                pieces.extend(sub[:-1])
+                cur = sub[-1]
+        if cur:
+            pieces.append(cur)
+        return pieces
+
+    words = text.split()   # an `[event]` tag holds no whitespace: it stays inside its word
+    if not words:
+        return []
+    return [" ".join(p) for p in pack(_units(words, 0), 0)]
+
+
+def _units(words: List[str], level: int) -> List[List[str]]:
+    """Groups words into runs that end behind a word closing with sentence (level 0) / clause (level 1) punctuation, optionally
+    followed by closing quotes or brackets; level 2: one word per unit."""
+    if level >= 2:
+        return [[w] for w in words]
+    marks = _SENTENCE_END if level == 0 else _SENTENCE_END + _CLAUSE_END
+    units, cur = [], []
+    for w in words:
+        cur.append(w)
+        if w.rstrip("\"'”’»)")[-1:] in marks:
+            units.append(cur)
+            cur = []
+    if cur:
+        units.append(cur)
+    return units
+
+
+def fade_table(fade_ms: float) -> np.ndarray:
+    """Raised-cosine fade-in weights w[i] = 0.5 - 0.5 cos(pi (i + 0.5) / F), F = round(fade_ms * 24): float64 math, rounded to fp32 once."""
+    F = int(round(fade_ms * SAMPLE_RATE / 1000.0))
+    if F <= 0:
+        return np.zeros((0,), np.float32)
+    return (0.5 - 0.5 * np.cos(np.pi * (np.arange(F, dtype=np.float64) + 0.5) / F)).astype(np.float32)
+
+
+def plan_long(ns: Sequence[int], max_batch: int = 8, gap_ms: float = 120.0, hop: int = HOP_SIZE) -> Tuple[List[List[int]], List[int], int]:
+    """The host-side plan of synthesize_long for pieces of `ns` frames: consecutive groups of at most `max_batch` pieces (the
+    splitter bounds every piece by the model's utterance limits, so a count is the only budget needed), every piece's sample
+    offset in the joined waveform, and its length S = sum(hop * n_i) + (len - 1) * round(gap_ms * 24)."""
+    if max_batch < 1:
+        raise ValueError("max_batch must be at least 1")
+    gap = max(0, int(round(gap_ms * SAMPLE_RATE / 1000.0)))
+    groups = [list(range(i, min(i + max_batch, len(ns)))) for i in range(0, len(ns), max_batch)]
+    offsets, pos = [], 0
+    for n in ns:
+        offsets.append(pos)
+        pos += hop * int(n) + gap
+    return groups, offsets, (pos - gap if len(ns) else 0)
+
+
+def piece_seed(seed: int, i: int) -> int:
+    """Seed of piece i of a long text: SeedSequence([seed, i]) reduced to 63 bits (like the replica seeds of SmallTTS)."""
+    return int(np.random.SeedSequence([int(seed), int(i)]).generate_state(1, np.uint64)[0] >> 1)
 
 
 def _split_sources(weights) -> List[str]:
@@ -129,6 +251,25 @@ def _frames(duration_sec: float) -> int:
     return max(1, int(duration_sec * SAMPLE_RATE / HOP_SIZE))  # floor, infer/onnx.py:84
 
 
+class Voice:
+    """A reference voice encoded once: the reference half of the cross-KV cache, `k_ref` / `v_ref` (12, 1, 8, R, 120) fp32 on the
+    engine's device (what cond_encode returns for this reference at B = 1), its length `R` and the `engine` it belongs to.
+    Immutable; any number of calls (and batches in flight) of that engine may read it."""
+    __slots__ = ("engine", "k_ref", "v_ref", "R")
+
+    def __init__(self, engine: HipEngine, k_ref: torch.Tensor, v_ref: torch.Tensor) -> None:
+        set_ = object.__setattr__
+        set_(self, "engine", engine)
+        set_(self, "k_ref", k_ref)
+        set_(self, "v_ref", v_ref)
+        set_(self, "R", int(k_ref.shape[3]))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Voice is immutable")
+
+    __delattr__ = __setattr__
+
+
 class SmallTTS:
     """DMD few-step synthesis: condition-encode -> n-step sampler -> codec decode, all on one MI355X."""
 
@@ -168,21 +309,53 @@ class SmallTTS:
             return int(self._rng.integers(0, 2 ** 63 - 1))
         return int(np.random.randint(0, 2 ** 31 - 1)) * 2654435761 % (2 ** 63)
 
-    def synthesize_batch(self, ref_latents: Sequence[np.ndarray], phoneme_ids: Sequence[Sequence[int]],
+    def encode_voice(self, ref_latents) -> Voice:
+        """(R, 64) reference latents -> Voice: the style encoder and the 12 reference K / V projections run once, at B = 1, without
+        a text half (cond_encode with P = 0).  Pass it to synthesize_batch(voices=...) / synthesize_long as often as needed."""
+        ref = np.asarray(ref_latents, np.float32)
+        if ref.ndim != 2 or ref.shape[1] != 64 or ref.shape[0] < 1:
+            raise ValueError(f"encode_voice: reference latents must be (R, 64) with R >= 1, got {ref.shape}")
+        cache = self.engine.cond_encode(ref[None], np.asarray([ref.shape[0]], np.int64), np.zeros((1, 0), np.int64),
+                                        np.zeros((1, 0), bool))
+        return Voice(self.engine, cache["k_ref"], cache["v_ref"])
+
+    def encode_voice_wav(self, audio, sr: int) -> Voice:
+        """Mono samples at `sr` Hz -> Voice: device resampler to 24 kHz, codec encoder (through Encoder.encode_reference and its
+        cache), then encode_voice."""
+        y = self.engine.resample(np.asarray(audio, np.float32).reshape(-1), int(sr), SAMPLE_RATE)
+        lat = Encoder(engine=self.engine).encode_reference(y.reshape(1, 1, -1))
+        return self.encode_voice(lat[0].numpy())
+
+    def synthesize_batch(self, ref_latents: Optional[Sequence[np.ndarray]], phoneme_ids: Sequence[Sequence[int]],
                          durations, *, noise: Optional[np.ndarray] = None, return_latents: bool = False,
-                         frames: Optional[Sequence[int]] = None, _defer: bool = False):
+                         frames: Optional[Sequence[int]] = None, _defer: bool = False,
+                         voices: Optional[Sequence[Voice]] = None, seeds: Optional[Sequence[int]] = None):
         """Batched synthesize: per-utterance (R_i,64) refs, token lists and durations -> list of (1, samples).
         `frames` overrides the per-utterance frame counts (default floor(duration * 7.5), infer/onnx.py:84; the HTTP server
-        rounds up like the reference's Rust server, pipeline.rs:66)."""
+        rounds up like the reference's Rust server, pipeline.rs:66).
+        `voices`: B Voice objects (encode_voice) instead of `ref_latents` (pass None): only the text half of the condition encoder
+        runs, the reference half is gathered from the voices.  `seeds`: B integers; row b's noise is the (seeds[b], step) Philox
+        stream, so its latents do not depend on its batch-mates' seeds, lengths or order (not together with `noise`)."""
+        if voices is not None:
+            if ref_latents is not None:
+                raise ValueError("synthesize_batch: pass either ref_latents or voices (with ref_latents=None), not both")
+            if any(v.engine is not self.engine for v in voices):
+                raise ValueError("synthesize_batch: a Voice belongs to another engine")
+            ref_latents = [np.zeros((0, 64), np.float32)] * len(voices)   # the text half alone: cond_encode skips R = 0
+        if seeds is not None and noise is not None:
+            raise ValueError("synthesize_batch: noise= and seeds= exclude each other")
         B = len(ref_latents)
         if B == 0:
             return []
+        if (voices is not None and len(phoneme_ids) != B) or (seeds is not None and len(seeds) != B):
+            raise ValueError(f"synthesize_batch: {B} rows, {len(phoneme_ids)} token lists"
+                             + (f", {len(seeds)} seeds" if seeds is not None else ""))
         if np.isscalar(durations):
             durations = [float(durations)] * B
         ns = [int(f) for f in frames] if frames is not None else [_frames(d) for d in durations]
         rs = [int(np.asarray(r).shape[0]) for r in ref_latents]
         ps = [len(p) for p in phoneme_ids]
-        Rm, Pm, Nm = max(max(rs), 1), max(max(ps), 1), max(ns)
+        Rm, Pm, Nm = (0 if voices is not None else max(max(rs), 1)), max(max(ps), 1), max(ns)
         ref = np.zeros((B, Rm, 64), np.float32)
         ids = np.zeros((B, Pm), np.int64)
         pm = np.zeros((B, Pm), bool)
@@ -193,11 +366,15 @@ class SmallTTS:
             pm[b, :ps[b]] = True
             mask[b, :ns[b]] = True
         eng = self.engine
-        seed = self._next_seed()
+        seed = self._next_seed() if seeds is None else 0
+        voices = None if voices is None else list(voices)      # run() keeps them alive while the batch is in flight
 
         def run():
             cache = eng.cond_encode(ref, np.asarray(rs, np.int64), ids, pm)
-            x_ = eng.sample(cache, mask, num_steps=self.num_steps, noise=noise, seed=seed)
+            if voices is not None:
+                cache.update(eng.voice_expand(voices))
+            nz = noise if seeds is None else eng.randn_rows(seeds, ns, self.num_steps, n_max=Nm)
+            x_ = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed)
             return eng.codec_decode(x_), x_                    # (B, 1, HOP * Nm); causal => prefixes are exact
 
         audio, x = run()
@@ -220,31 +397,10 @@ class SmallTTS:
         i % in_flight with its own workspace, so one batch's latency-bound phases (condition encoders, DiT) fill the
         CUs another batch's kernels leave idle (bench.py: 16 ms per 8 x 10 s batch against 20 ms one at a time).
         The engine runs in throughput tuning meanwhile; results equal a loop of synthesize_batch under that tuning bit for bit."""
-        eng = self.engine
         if in_flight <= 1 or len(batches) <= 1:
             return [self.synthesize_batch(*b) for b in batches]
-        dev = eng.device
-        cur = torch.cuda.current_stream(dev)
-        streams = [torch.cuda.Stream(dev) for _ in range(min(in_flight, len(batches)))]
-        for st in streams:
-            st.wait_stream(cur)
-        pending = []
-        # throughput tuning: unsplit GEMMs, capped persistent codec grids, no engine side stream (it would serialise the text encoders of all
-        # batches in flight); the caller's mode is restored afterwards
-        prev_tuning = eng.set_tuning("throughput")
-        try:
-            for i, (refs, toks, durs) in enumerate(batches):
-                with torch.cuda.stream(streams[i % len(streams)]):
-                    eng.use_workspace(f"batch{i % len(streams)}")
-                    pending.append(self.synthesize_batch(refs, toks, durs, _defer=True))
-        finally:
-            eng.use_workspace(None)
-            eng.set_tuning(prev_tuning)
-        for st in streams:
-            cur.wait_stream(st)
-        torch.cuda.synchronize(dev)
-        if eng.check_fp16_range("synthesize_batches"):         # clipped somewhere: every batch again, one at a time, at the demoted precision
-            pending = [(*run(), ns, run) for _a, _x, ns, run in pending]
+        eng, dev = self.engine, self.engine.device
+        pending = self._run_in_flight([lambda b=b: self.synthesize_batch(*b, _defer=True) for b in batches], in_flight)
         outs = []
         for audio, _, ns, _run in pending:
             a = audio.cpu().numpy()
@@ -253,6 +409,83 @@ class SmallTTS:
             torch.cuda.synchronize(dev)
             eng.release_workspaces()
         return outs
+
+    def _run_in_flight(self, calls: Sequence[Callable[[], tuple]], in_flight: int) -> List[tuple]:
+        """The machinery of synthesize_batches: calls[i]() enqueues one deferred synthesize_batch; call i runs whole on HIP stream
+        i % in_flight with its own workspace under throughput tuning.  Returns the finished (audio, latents, ns, run) tuples, on the
+        device, after the fp16 range guard has been honoured."""
+        eng = self.engine
+        dev = eng.device
+        cur = torch.cuda.current_stream(dev)
+        streams = [torch.cuda.Stream(dev) for _ in range(max(1, min(in_flight, len(calls))))]
+        for st in streams:
+            st.wait_stream(cur)
+        pending = []
+        # throughput tuning: unsplit GEMMs, capped persistent codec grids, no engine side stream (it would serialise the text encoders of all
+        # batches in flight); the caller's mode is restored afterwards
+        prev_tuning = eng.set_tuning("throughput")
+        try:
+            for i, call in enumerate(calls):
+                with torch.cuda.stream(streams[i % len(streams)]):
+                    eng.use_workspace(f"batch{i % len(streams)}")
+                    pending.append(call())
+        finally:
+            eng.use_workspace(None)
+            eng.set_tuning(prev_tuning)
+        for st in streams:
+            cur.wait_stream(st)
+        torch.cuda.synchronize(dev)
+        if eng.check_fp16_range("synthesize_batches"):         # clipped somewhere: every batch again, one at a time, at the demoted precision
+            pending = [(*run(), ns, run) for _a, _x, ns, run in pending]
+        return pending
+
+    def synthesize_long(self, voice: Voice, text: Optional[str] = None, *, token_lists: Optional[Sequence[Sequence[int]]] = None,
+                        durations: Optional[Sequence[float]] = None, seed: Optional[int] = None, gap_ms: float = 120.0,
+                        fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3, pcm16: bool = False,
+                        prefix_tokens: Optional[Sequence[int]] = None) -> np.ndarray:
+        """A whole text in one voice -> one waveform (1, S), fp32 or (pcm16=True) int16 PCM, S = sum(3200 * n_i) + (pieces - 1) *
+        round(gap_ms * 24).
+
+        Either `text` (cut by split_text, phonemised, durations from estimate_duration per piece) or pre-split `token_lists` with
+        `durations`.  Consecutive pieces ride in batches of at most `max_batch`, `in_flight` batches overlapping on the GPU under
+        throughput tuning (the synthesize_batches machinery; always, also for a single batch, so that the result does not depend
+        on how the text was grouped beyond the engine's batch-shape tolerance).  Only the text half of the condition encoder runs
+        per batch; the voice was encoded once.  Piece i draws its noise from seed SeedSequence([seed, i]) -> 63 bits.  The rows are
+        joined on the device (engine.stitch: `gap_ms` of silence between pieces, a raised-cosine fade of `fade_ms` at both ends of
+        each, fade_table) and copied to the host once.  `prefix_tokens` (the reference clip's transcription) is prepended to every
+        piece's tokens, as forward() prepends the transcription; the splitter's token budget shrinks by its length."""
+        if voice.engine is not self.engine:
+            raise ValueError("synthesize_long: the Voice belongs to another engine")
+        prefix = [int(t) for t in (prefix_tokens or [])]
+        if (text is None) == (token_lists is None):
+            raise ValueError("synthesize_long: pass either text or token_lists (with durations)")
+        if text is not None:
+            from .phonemes import get_token_ids
+            pieces = split_text(text, max_tokens=198 - len(prefix))
+            token_lists = [get_token_ids(p) for p in pieces]
+            durations = [estimate_duration(p) for p in pieces]
+        else:
+            if durations is None or (not np.isscalar(durations) and len(durations) != len(token_lists)):
+                raise ValueError("synthesize_long: token_lists needs one duration per piece")
+            if np.isscalar(durations):
+                durations = [float(durations)] * len(token_lists)
+        toks = [prefix + [int(t) for t in p] for p in token_lists]
+        ns = [_frames(d) for d in durations]
+        eng = self.engine
+        groups, offsets, S = plan_long(ns, max_batch, gap_ms)
+        if not toks:
+            return np.zeros((1, 0), np.int16 if pcm16 else np.float32)
+        base = self._next_seed() if seed is None else int(seed)
+        seeds = [piece_seed(base, i) for i in range(len(toks))]
+        calls = [lambda g=g: self.synthesize_batch(None, [toks[i] for i in g], None, frames=[ns[i] for i in g], voices=[voice] * len(g),
+                                                   seeds=[seeds[i] for i in g], _defer=True) for g in groups]
+        pending = self._run_in_flight(calls, in_flight)
+        out = torch.zeros(S, dtype=torch.int16 if pcm16 else torch.float32, device=eng.device)
+        w = fade_table(fade_ms)
+        fade = torch.from_numpy(w).to(eng.device) if w.size else None
+        for g, (audio, _x, g_ns, _run) in zip(groups, pending):
+            eng.stitch(audio, g_ns, [offsets[i] for i in g], fade, out)
+        return out.cpu().numpy()[None]
 
     def synthesize_sharded(self, ref_latents: Sequence[np.ndarray], phoneme_ids: Sequence[Sequence[int]],
                            duration_sec: float, *, max_batch: int = 8) -> np.ndarray:

@@ -145,6 +145,30 @@ int smtts_pcm16(smtts_handle h, void* stream, const float* x, int64_t n, int16_t
     hipError_t e = launch_pcm16(x, y, n, ST(stream));
     return e == hipSuccess ? 0 : E.fail_hip(e, "pcm16");
 }
+int smtts_voice_expand(smtts_handle h, void* stream, const int64_t* table, int B, int Rmax, float* k_ref, float* v_ref,
+                       uint8_t* ref_mask) { NULLCHK;
+    if (B <= 0 || Rmax <= 0 || !table || !k_ref || !v_ref || !ref_mask) return E.fail("voice_expand: bad arguments");
+    if ((((uintptr_t)k_ref | (uintptr_t)v_ref) & 15) != 0) return E.fail("voice_expand: k_ref / v_ref must be 16-byte aligned");
+    hipError_t e = launch_voice_expand(table, k_ref, v_ref, ref_mask, B, Rmax, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "voice_expand");
+}
+int smtts_randn_rows(smtts_handle h, void* stream, float* out, const uint64_t* seeds, const int64_t* n, int n_steps, int B,
+                     int Nmax) { NULLCHK;
+    if (n_steps <= 0 || B <= 0 || Nmax <= 0 || !out || !seeds || !n) return E.fail("randn_rows: bad arguments");
+    if (((uintptr_t)out & 15) != 0) return E.fail("randn_rows: out must be 16-byte aligned");
+    hipError_t e = launch_randn_rows(out, seeds, n, n_steps, B, Nmax, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "randn_rows");
+}
+int smtts_stitch(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* len, const int64_t* off,
+                 const float* fade, int F, void* out, int64_t out_n, int pcm16) { NULLCHK;
+    if (B <= 0 || row_stride <= 0 || out_n <= 0 || F < 0 || !audio || !len || !off || !out || (F > 0 && !fade))
+        return E.fail("stitch: bad arguments");
+    hipError_t e = pcm16 ? launch_stitch_pcm16(audio, (long)row_stride, len, off, fade, F, static_cast<int16_t*>(out), (long)out_n, B,
+                                               (long)row_stride, ST(stream))
+                         : launch_stitch(audio, (long)row_stride, len, off, fade, F, static_cast<float*>(out), (long)out_n, B,
+                                         (long)row_stride, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "stitch");
+}
 int smtts_set_dual_stream(smtts_handle h, int on) { NULLCHK; E.set_dual_stream(on != 0); return 0; }
 int smtts_set_tuning(smtts_handle h, int mode) { NULLCHK;
     if (mode != 0 && mode != 1) return E.fail("tuning mode must be 0 (latency) or 1 (throughput)");

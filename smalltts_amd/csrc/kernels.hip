@@ -306,12 +306,10 @@ __device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32
         k1 += 0xBB67AE85u;
     }
 }
-__global__ void randn_kernel(float* __restrict__ out, long n, uint64_t seed, uint64_t stream) {
-    long q = (long)blockIdx.x * blockDim.x + threadIdx.x;  // quad index
-    if (q * 4 >= n) return;
+// the four normals of quad q of a (seed, stream) sequence: counter = (q, stream), key = seed, two Box-Muller pairs
+__device__ __forceinline__ void randn_quad(long q, uint64_t seed, uint64_t stream, float z[4]) {
     uint32_t c[4] = {(uint32_t)q, (uint32_t)((uint64_t)q >> 32), (uint32_t)stream, (uint32_t)(stream >> 32)};
     philox4x32_10(c, (uint32_t)seed, (uint32_t)(seed >> 32));
-    float z[4];
 #pragma unroll
     for (int p = 0; p < 2; ++p) {
         float u1 = ((float)(c[2 * p] >> 8) + 0.5f) * 5.9604644775390625e-8f;      // (0,1)
@@ -321,6 +319,12 @@ __global__ void randn_kernel(float* __restrict__ out, long n, uint64_t seed, uin
         z[2 * p] = r * cosf(th);
         z[2 * p + 1] = r * sinf(th);
     }
+}
+__global__ void randn_kernel(float* __restrict__ out, long n, uint64_t seed, uint64_t stream) {
+    long q = (long)blockIdx.x * blockDim.x + threadIdx.x;  // quad index
+    if (q * 4 >= n) return;
+    float z[4];
+    randn_quad(q, seed, stream, z);
 #pragma unroll
     for (int j = 0; j < 4; ++j)
         if (q * 4 + j < n) out[q * 4 + j] = z[j];
@@ -329,6 +333,34 @@ hipError_t launch_randn(float* out, long n, uint64_t seed, uint64_t stream, hipS
     if (n == 0) return hipSuccess;
     long quads = (n + 3) / 4;
     hipLaunchKernelGGL(randn_kernel, dim3((unsigned)((quads + 255) / 256)), dim3(256), 0, st, out, n, seed, stream);
+    LAUNCH_CHECK();
+}
+
+// Per-row noise for a whole sampler call in ONE launch: out (n_steps, B, Nmax, 64); row b of step s holds in [0, n[b] * 64) exactly what
+// randn_kernel(n = n[b] * 64, seed = seeds[b], stream = s) writes (counter = quad index WITHIN the row), zeros behind.  A row's noise
+// therefore does not depend on the batch it rides in.  One thread per quad = one 16-byte store; a row is Nmax * 16 quads, 16-byte aligned.
+__global__ __launch_bounds__(256) void randn_rows_kernel(float* __restrict__ out, const uint64_t* __restrict__ seeds,
+                                                         const int64_t* __restrict__ n, int B, int Nmax) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;  // quad index within the row
+    const long rowq = (long)Nmax * 16;
+    if (q >= rowq) return;
+    const int b = blockIdx.y, s = blockIdx.z;
+    long nb = n[b];
+    nb = nb < 0 ? 0 : nb > Nmax ? Nmax : nb;
+    float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+    if (q < nb * 16) {
+        float z[4];
+        randn_quad(q, seeds[b], (uint64_t)s, z);
+        v = make_float4(z[0], z[1], z[2], z[3]);
+    }
+    reinterpret_cast<float4*>(out)[((long)s * B + b) * rowq + q] = v;
+}
+hipError_t launch_randn_rows(float* out, const uint64_t* seeds, const int64_t* n, int n_steps, int B, int Nmax, hipStream_t st) {
+    if (n_steps <= 0 || B <= 0 || Nmax <= 0) return hipSuccess;
+    const long rowq = (long)Nmax * 16;
+    ProfScope ps(st, "randn_rows", 0.0, 4.0 * 4.0 * rowq * B * n_steps);
+    hipLaunchKernelGGL(randn_rows_kernel, dim3((unsigned)((rowq + 255) / 256), (unsigned)B, (unsigned)n_steps), dim3(256), 0, st, out,
+                       seeds, n, B, Nmax);
     LAUNCH_CHECK();
 }
 
@@ -1418,6 +1450,116 @@ hipError_t launch_pcm16(const float* x, int16_t* y, long n, hipStream_t st) {
     if (n <= 0) return hipSuccess;
     hipLaunchKernelGGL(pcm16_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, x, y, n);
     LAUNCH_CHECK();
+}
+
+// ------------------------------------------------------------------------------------------
+// long-form synthesis: a voice's cross K / V gathered into a batch cache, batch rows joined into one waveform
+// ------------------------------------------------------------------------------------------
+// table [B][3] int64: (k_ptr, v_ptr, R_b), the voice's k_ref / v_ref (12, 1, 8, R_b, 120) -> k, v (12, B, 8, Rmax, 120), mask (B, Rmax).
+// A (layer, head) chunk is R_b * 120 contiguous floats at the source and Rmax * 120 at the destination, so the copy is one float4
+// per lane along the chunk (120 floats = 30 float4: every chunk starts 16-byte aligned when the slab does); float4s past R_b * 30 are
+// zero.  A slab that is not 16-byte aligned is read with scalar loads.  blockIdx.y = layer * 8 + head, blockIdx.z = row.
+__global__ __launch_bounds__(256) void voice_expand_kernel(const int64_t* __restrict__ table, float* __restrict__ k, float* __restrict__ v,
+                                                           uint8_t* __restrict__ mask, int B, int Rmax) {
+    const int q = blockIdx.x * blockDim.x + threadIdx.x;   // float4 index within the destination chunk
+    const int lh = blockIdx.y, b = blockIdx.z;
+    const int chunk4 = Rmax * 30;
+    if (q >= chunk4) return;
+    const float* ks = reinterpret_cast<const float*>(table[3 * b]);
+    const float* vs = reinterpret_cast<const float*>(table[3 * b + 1]);
+    long Rb = table[3 * b + 2];
+    Rb = Rb < 0 ? 0 : Rb > Rmax ? Rmax : Rb;
+    if (lh == 0 && q < Rmax) mask[(long)b * Rmax + q] = q < Rb ? 1 : 0;
+    float4 kv = make_float4(0.f, 0.f, 0.f, 0.f), vv = kv;
+    if (q < Rb * 30) {
+        const long src = ((long)lh * Rb * 30 + q) * 4;
+        if ((((uintptr_t)ks | (uintptr_t)vs) & 15) == 0) {
+            kv = *reinterpret_cast<const float4*>(ks + src);
+            vv = *reinterpret_cast<const float4*>(vs + src);
+        } else {
+            kv = make_float4(ks[src], ks[src + 1], ks[src + 2], ks[src + 3]);
+            vv = make_float4(vs[src], vs[src + 1], vs[src + 2], vs[src + 3]);
+        }
+    }
+    const int l = lh >> 3, h = lh & 7;
+    const long dst = (((long)l * B + b) * 8 + h) * chunk4 + q;
+    reinterpret_cast<float4*>(k)[dst] = kv;
+    reinterpret_cast<float4*>(v)[dst] = vv;
+}
+hipError_t launch_voice_expand(const int64_t* table, float* k, float* v, uint8_t* mask, int B, int Rmax, hipStream_t st) {
+    if (B <= 0 || Rmax <= 0) return hipSuccess;
+    const int chunk4 = Rmax * 30;
+    ProfScope ps(st, "voice_expand", 0.0, 2.0 * 2.0 * 16.0 * chunk4 * 96 * B);
+    hipLaunchKernelGGL(voice_expand_kernel, dim3((unsigned)((chunk4 + 255) / 256), 96u, (unsigned)B), dim3(256), 0, st, table, k, v, mask, B,
+                       Rmax);
+    LAUNCH_CHECK();
+}
+
+// y[off_b + i] = x[b][i] * g for i < len_b: g = w[i] over the first F_b = min(F, len_b / 2) samples, w[len_b - 1 - i] over the last F_b,
+// no multiply between.  The weight is a table entry and the product one fp32 multiply, so numpy reproduces the result bit for bit.
+// int16 output: pcm16_kernel's arithmetic on the faded value.  One thread per four samples of a row: 16-byte loads when the row is
+// aligned, one 16- / 8-byte store when the destination is (the row's offset decides: uniform over the row), scalar otherwise.
+// Samples outside [0, y_n) are dropped, samples between rows are not written.
+__device__ __forceinline__ void stitch_put(float* y, float v) { *y = v; }
+__device__ __forceinline__ void stitch_put(int16_t* y, float v) { *y = (int16_t)__float2int_rn(fminf(fmaxf(v, -1.0f), 1.0f) * 32767.0f); }
+__device__ __forceinline__ void stitch_put4(float* y, const float v[4]) { *reinterpret_cast<float4*>(y) = make_float4(v[0], v[1], v[2], v[3]); }
+__device__ __forceinline__ void stitch_put4(int16_t* y, const float v[4]) {
+    int16_t r[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) stitch_put(&r[j], v[j]);
+    *reinterpret_cast<short4*>(y) = make_short4(r[0], r[1], r[2], r[3]);
+}
+template <class T>
+__global__ __launch_bounds__(256) void stitch_kernel(const float* __restrict__ x, long x_stride, const int64_t* __restrict__ len,
+                                                     const int64_t* __restrict__ off, const float* __restrict__ w, int F,
+                                                     T* __restrict__ y, long y_n, long max_len) {
+    const int b = blockIdx.y;
+    const long n = len[b] < max_len ? len[b] : max_len, o = off[b];
+    const long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
+    if (i0 >= n) return;
+    const long Fb = F < n / 2 ? F : n / 2;
+    const float* xr = x + (long)b * x_stride;
+    const int m = n - i0 < 4 ? (int)(n - i0) : 4;
+    float v[4] = {0.f, 0.f, 0.f, 0.f};
+    if (m == 4 && ((uintptr_t)(xr + i0) & 15) == 0) {
+        const float4 t = *reinterpret_cast<const float4*>(xr + i0);
+        v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+    } else {
+        for (int j = 0; j < m; ++j) v[j] = xr[i0 + j];
+    }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const long i = i0 + j;
+        if (j < m) {
+            if (i < Fb) v[j] = v[j] * w[i];
+            else if (i >= n - Fb) v[j] = v[j] * w[n - 1 - i];
+        }
+    }
+    T* yp = y + o + i0;
+    if (m == 4 && o + i0 >= 0 && o + i0 + 4 <= y_n && ((uintptr_t)yp & (4 * sizeof(T) - 1)) == 0) {
+        stitch_put4(yp, v);
+    } else {
+        for (int j = 0; j < m; ++j)
+            if (o + i0 + j >= 0 && o + i0 + j < y_n) stitch_put(yp + j, v[j]);
+    }
+}
+template <class T>
+static hipError_t launch_stitch_t(const float* x, long x_stride, const int64_t* len, const int64_t* off, const float* w, int F, T* y,
+                                  long y_n, int B, long max_len, hipStream_t st) {
+    if (B <= 0 || max_len <= 0 || y_n <= 0) return hipSuccess;
+    const long quads = (max_len + 3) / 4;
+    ProfScope ps(st, "stitch", 1.0 * B * max_len, (4.0 + sizeof(T)) * B * max_len);
+    hipLaunchKernelGGL(stitch_kernel<T>, dim3((unsigned)((quads + 255) / 256), (unsigned)B), dim3(256), 0, st, x, x_stride, len, off, w, F, y,
+                       y_n, max_len);
+    LAUNCH_CHECK();
+}
+hipError_t launch_stitch(const float* x, long x_stride, const int64_t* len, const int64_t* off, const float* w, int F, float* y, long y_n,
+                         int B, long max_len, hipStream_t st) {
+    return launch_stitch_t<float>(x, x_stride, len, off, w, F, y, y_n, B, max_len, st);
+}
+hipError_t launch_stitch_pcm16(const float* x, long x_stride, const int64_t* len, const int64_t* off, const float* w, int F, int16_t* y,
+                               long y_n, int B, long max_len, hipStream_t st) {
+    return launch_stitch_t<int16_t>(x, x_stride, len, off, w, F, y, y_n, B, max_len, st);
 }
 
 // t[i] = float32(np.linspace(1, 0, n))[i]: float64 arithmetic, exact end point (reference infer/onnx.py:98)

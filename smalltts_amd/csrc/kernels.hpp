@@ -120,6 +120,8 @@ hipError_t launch_cfg_combine(const float* v3, float* v, float s_text, float s_s
 
 // Philox4x32-10 + Box-Muller standard normals; element i uses counter (i/4, stream, 0, 0), key (seed lo, hi).
 hipError_t launch_randn(float* out, long n, uint64_t seed, uint64_t stream, hipStream_t st);
+// out (n_steps, B, Nmax, 64): row b of step s = launch_randn(n[b] * 64, seeds[b], s) then zeros; seeds / n: device arrays of B entries
+hipError_t launch_randn_rows(float* out, const uint64_t* seeds, const int64_t* n, int n_steps, int B, int Nmax, hipStream_t st);
 
 // synthetic weights (smalltts_amd/weights.py recipe, bit-exact)
 hipError_t launch_synth(float* out, long n, uint64_t key, float mean, float half_range, hipStream_t st);
@@ -220,5 +222,14 @@ hipError_t launch_mixer_fused(const float* xin, float* xout, const float* norm_w
 hipError_t launch_resample_poly(const float* x, long n_in, const float* bank, int up, int down, int klen, int width, float* y,
                                 long n_out, int channels, hipStream_t st);
 hipError_t launch_pcm16(const float* x, int16_t* y, long n, hipStream_t st);
+// long-form synthesis (kernels.hip).  voice_expand: table [B][3] int64 (k_ptr, v_ptr, R_b) of per-voice (12, 1, 8, R_b, 120) slabs ->
+// k, v (12, B, 8, Rmax, 120) with zeros past R_b, mask (B, Rmax).  stitch: rows x[b][0 .. len[b]) of a decoded batch, faded at both
+// ends by the table w[F], to y[off[b] ..] (fp32, or PCM16 with launch_pcm16's arithmetic); max_len >= every len[b] sizes the grid and
+// a row never reads past it; samples outside [0, y_n) are dropped
+hipError_t launch_voice_expand(const int64_t* table, float* k, float* v, uint8_t* mask, int B, int Rmax, hipStream_t st);
+hipError_t launch_stitch(const float* x, long x_stride, const int64_t* len, const int64_t* off, const float* w, int F, float* y, long y_n,
+                         int B, long max_len, hipStream_t st);
+hipError_t launch_stitch_pcm16(const float* x, long x_stride, const int64_t* len, const int64_t* off, const float* w, int F, int16_t* y,
+                               long y_n, int B, long max_len, hipStream_t st);
 // t[i] = float32(np.linspace(1, 0, n))[i] on the device (sampler timesteps)
 hipError_t launch_linspace10(float* t, int n, hipStream_t st);

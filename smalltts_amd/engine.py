@@ -424,6 +424,74 @@ class HipEngine:
         self._ck(self.lib.smtts_randn(self.h, self._stream(), _p(out), n, C.c_uint64(seed), C.c_uint64(stream_id)), "randn")
         return out
 
+    # ---- long-form synthesis: one voice, many rows (include/smalltts_hip.h) -----------------------------
+    def _upload_i64(self, rows) -> torch.Tensor:
+        """Small per-call host table -> device int64 on the current stream, through pinned staging (no synchronising copy)."""
+        t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64))
+        return t.pin_memory().to(self.device, non_blocking=True)
+
+    def voice_expand(self, voices) -> Dict[str, torch.Tensor]:
+        """B voices (objects with k_ref / v_ref (12,1,8,R_b,120) fp32 on this device, or such pairs) -> the reference half of a
+        cross-KV cache: k_ref, v_ref (12,B,8,Rmax,120) and ref_mask (B,Rmax), bit-identical copies with zeros in the padding.
+        The voices' tensors are read on the current stream: keep them alive until that work has completed."""
+        pairs = [(v.k_ref, v.v_ref) if hasattr(v, "k_ref") else tuple(v) for v in voices]
+        B = len(pairs)
+        if B == 0:
+            raise ValueError("voice_expand: no voices")
+        rows = []
+        for k, v in pairs:
+            R = int(k.shape[3])
+            want = (N_LAYERS, 1, N_HEADS, R, HEAD_DIM)
+            for t in (k, v):
+                if (tuple(t.shape) != want or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()
+                        or R < 1):
+                    raise ValueError(f"voice_expand: a voice's k_ref / v_ref must be contiguous fp32 {want} with R >= 1 on {self.device}, "
+                                     f"got {tuple(t.shape)} {t.dtype} on {t.device}")
+            rows.append((k.data_ptr(), v.data_ptr(), R))
+        Rmax = max(r[2] for r in rows)
+        dev = self.device
+        out = {"k_ref": torch.empty(N_LAYERS, B, N_HEADS, Rmax, HEAD_DIM, device=dev),
+               "v_ref": torch.empty(N_LAYERS, B, N_HEADS, Rmax, HEAD_DIM, device=dev),
+               "ref_mask": torch.empty(B, Rmax, dtype=torch.bool, device=dev)}
+        table = self._upload_i64(rows)
+        self._ck(self.lib.smtts_voice_expand(self.h, self._stream(), _p(table), B, Rmax, _p(out["k_ref"]), _p(out["v_ref"]),
+                                             _p(out["ref_mask"])), "voice_expand")
+        return out
+
+    def randn_rows(self, seeds, ns, steps: int, n_max: Optional[int] = None) -> torch.Tensor:
+        """(steps, B, n_max, 64) sampler noise in one launch: row b of step s = randn(ns[b] * 64, seeds[b], s), zeros behind."""
+        ns = [int(n) for n in ns]
+        B = len(ns)
+        Nm = max(ns) if n_max is None else int(n_max)
+        if B == 0 or len(seeds) != B or min(ns) < 0 or max(ns) > Nm or Nm < 1 or steps < 1:
+            raise ValueError(f"randn_rows: {len(seeds)} seeds for {B} rows of {ns} frames (n_max {Nm}, {steps} steps)")
+        tab = self._upload_i64([np.asarray([int(s) & (2 ** 64 - 1) for s in seeds], np.uint64).view(np.int64), ns])
+        out = torch.empty(int(steps), B, Nm, LATENT, device=self.device)
+        self._ck(self.lib.smtts_randn_rows(self.h, self._stream(), _p(out), _p(tab[0]), _p(tab[1]), int(steps), B, Nm), "randn_rows")
+        return out
+
+    def stitch(self, audio: torch.Tensor, ns, offsets, fade: Optional[torch.Tensor], out: torch.Tensor) -> torch.Tensor:
+        """Rows of a decoded batch into one waveform: audio (B,1,hop*Nmax) fp32 on the device, ns frames per row, offsets the rows'
+        absolute sample offsets in `out` (1-D fp32 or int16 on the device, zero-filled once by the caller), fade the (F,) fp32
+        weight table on the device or None.  out[offsets[b] + i] = audio[b, 0, i] * g for i < hop * ns[b] (smtts_stitch)."""
+        B = audio.shape[0]
+        row = int(audio.shape[-1])
+        lens = [self.hop * int(n) for n in ns]
+        if (audio.dtype != torch.float32 or not audio.is_contiguous() or audio.device != self.device or len(lens) != B
+                or len(offsets) != B or max(lens) > row):
+            raise ValueError("stitch: audio must be contiguous fp32 (B,1,S) on the engine's device with hop * ns[b] <= S")
+        if out.dtype not in (torch.float32, torch.int16) or out.dim() != 1 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("stitch: out must be a contiguous 1-D fp32 or int16 tensor on the engine's device")
+        if any(int(o) < 0 or int(o) + n > out.numel() for o, n in zip(offsets, lens)):
+            raise ValueError("stitch: a row does not fit into out")
+        F = 0 if fade is None else int(fade.numel())
+        if F and (fade.dtype != torch.float32 or fade.device != self.device or not fade.is_contiguous()):
+            raise ValueError("stitch: fade must be a contiguous fp32 tensor on the engine's device")
+        tab = self._upload_i64([lens, [int(o) for o in offsets]])
+        self._ck(self.lib.smtts_stitch(self.h, self._stream(), _p(audio), B, row, _p(tab[0]), _p(tab[1]), _p(fade) if F else None, F,
+                                       _p(out), out.numel(), int(out.dtype == torch.int16)), "stitch")
+        return out
+
     # ---- device-side audio front / back end ---------------------------------------------------------
     def resample(self, audio, sr: int, target: int = 24_000) -> torch.Tensor:
         """(samples,) or (channels, samples) float -> resampled on the device (same bank as audio.resample_hq)."""

@@ -1,0 +1,60 @@
+"""python -m smalltts_amd.scripts.longform --wav ref.wav --text-file text.txt [--out out/longform.wav]
+A whole text in one cloned voice: the voice is encoded once, the text is cut into utterance-sized pieces (api.split_text), the
+pieces run as batches in flight and are joined on the device (api.SmallTTS.synthesize_long).
+Without espeak: --tokens-file (one comma-separated token list per line = one piece) with --durations (seconds, one per line)."""
+import argparse
+from pathlib import Path
+
+from ..api import SmallTTS, estimate_duration, split_text
+from ..audio import read_wav, write_wav_pcm16
+from ..phonemes import get_token_ids, parse_tokens_arg
+from ._common import add_engine_args
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--wav", required=True, help="reference audio file (the voice)")
+    ap.add_argument("--text-file", default=None, help="text to speak (any length)")
+    ap.add_argument("--tokens-file", default=None, help="pre-split pieces: one comma-separated token list per line")
+    ap.add_argument("--durations", default=None, help="seconds per piece of --tokens-file, comma-separated (one value: all pieces)")
+    ap.add_argument("--out", default="out/longform.wav")
+    ap.add_argument("--gap-ms", type=float, default=120.0, help="silence between pieces")
+    ap.add_argument("--fade-ms", type=float, default=5.0, help="raised-cosine fade at both ends of every piece")
+    ap.add_argument("--max-batch", type=int, default=8)
+    ap.add_argument("--in-flight", type=int, default=3)
+    add_engine_args(ap)
+    args = ap.parse_args(argv)
+    if (args.text_file is None) == (args.tokens_file is None):
+        ap.error("pass either --text-file or --tokens-file")
+    if args.tokens_file and not args.durations:
+        ap.error("--tokens-file needs --durations")
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    print("loading")
+    tts = SmallTTS(weights=args.weights, device=args.device, precision=args.precision, num_steps=args.steps, seed=args.seed)
+    print("encoding reference audio")
+    y, sr = read_wav(args.wav)
+    if y.ndim == 2:
+        y = y.mean(axis=1)
+    voice = tts.encode_voice_wav(y, sr)
+    kw = dict(seed=args.seed, gap_ms=args.gap_ms, fade_ms=args.fade_ms, max_batch=args.max_batch, in_flight=args.in_flight)
+    if args.tokens_file:
+        with open(args.tokens_file) as f:
+            token_lists = [parse_tokens_arg(line) for line in f if line.strip()]
+        durs = [float(d) for d in args.durations.replace(",", " ").split()]
+        if len(durs) == 1:
+            durs = durs * len(token_lists)
+        print(f"generating {len(token_lists)} pieces")
+        audio = tts.synthesize_long(voice, token_lists=token_lists, durations=durs, **kw)
+    else:
+        with open(args.text_file) as f:
+            text = f.read()
+        tok = lambda t: get_token_ids(t, backend=args.tokenizer)
+        pieces = split_text(text, count_tokens=lambda t: len(tok(t)))
+        print(f"generating {len(pieces)} pieces")
+        audio = tts.synthesize_long(voice, token_lists=[tok(p) for p in pieces], durations=[estimate_duration(p) for p in pieces], **kw)
+    write_wav_pcm16(args.out, audio.squeeze(0), 24_000)
+    print(f"{args.out} ({audio.shape[1] / 24_000:.1f}s)")
+
+
+if __name__ == "__main__":
+    main()
