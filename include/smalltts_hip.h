@@ -49,9 +49,9 @@ int smtts_create(int device_id, smtts_handle* out);
 int smtts_destroy(smtts_handle h);
 const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation error */
 const char* smtts_version(void);
-/* bumped on every signature / default change: 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
+/* bumped on every signature / default change: 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
-#define SMTTS_ABI_VERSION 9
+#define SMTTS_ABI_VERSION 10
 int smtts_abi_version(void);
 
 /* ---- weights (replaces the ONNX initialisers; names/shapes = DiTModel.state_dict(),
@@ -176,6 +176,27 @@ int smtts_randn_rows(smtts_handle h, void* stream, float* out, const uint64_t* s
  * for bit. */
 int smtts_stitch(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* len, const int64_t* off,
                  const float* fade, int F, void* out, int64_t out_n, int pcm16);
+/* endpoints of the speech in each row of a decoded batch: audio f32 (B,1,row_stride); len i64 (B) DEVICE (clamped to
+ * [0, row_stride]; nothing behind len[b] is read); e, pk f32 (B,Fmax), Fmax = ceil(row_stride / W), scratch AND output: the per-frame
+ * mean power and peak, written for f < ceil(len[b] / W), untouched behind; -> seg i64 (B,2) = (start, n), gain f32 (B), both DEVICE.
+ *   frame f covers [f W, min(len, (f + 1) W)), cnt[f] samples; e[f] = (sum x^2) / cnt[f] (fp32, a fixed order), pk[f] = max |x|;
+ *   thr = fmaxf(max_f e[f] * rel_pow, floor_pow); f is active iff e[f] > thr, speech iff it lies in a run of >= min_run active frames;
+ *   no speech: (0, 0), gain 1.  Else with a / b the first / last speech frame: start = max(0, a W - lead),
+ *   n = min(len, (b + 1) W + tail) - start;  gain = 1 if target_rms == 0, else P = (sum over speech frames of e[f] cnt[f]) / (sum of
+ *   cnt[f]), g = fminf(target_rms / sqrtf(P), max_gain), and g = peak_limit / max_f pk[f] if max_f pk[f] * g > peak_limit.
+ * Given the e returned, integer logic and single fp32 operations reproduce (start, n) exactly and gain up to the summation order of P.
+ * Two launches whatever B is; no atomics: two calls on the same input return the same bits, and a row's results do not depend on its
+ * batch-mates.  W % 4 == 0, 16 <= W <= 4096; 1 <= min_run <= 16; lead, tail >= 0; rel_pow, floor_pow, target_rms >= 0; peak_limit,
+ * max_gain > 0. */
+int smtts_endpoints(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* len, int W,
+                    float rel_pow, float floor_pow, int min_run, int lead, int tail, float target_rms, float peak_limit,
+                    float max_gain, float* e, float* pk, int64_t* seg, float* gain);
+/* smtts_stitch with a source window and a gain per row: seg i64 (B,2) DEVICE = (start, n) as smtts_endpoints writes it (clamped into
+ * [0, row_stride]), gain f32 (B) DEVICE or NULL, off i64 (B) DEVICE.  For i < n: out[off[b] + i] = ((audio[b][start + i] * gain[b]) * g),
+ * g the fade weight of smtts_stitch over the window (F_b = min(F, n / 2)); each step is one fp32 multiply, gain == NULL skips the first
+ * (it does not even round); then smtts_stitch's PCM16 arithmetic when pcm16 != 0.  seg = (0, len) with gain NULL is smtts_stitch. */
+int smtts_stitch_seg(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* seg,
+                     const float* gain, const int64_t* off, const float* fade, int F, void* out, int64_t out_n, int pcm16);
 
 /* cond_encode runs the text encoder on a side stream owned by the engine, one per caller stream (fork / join with events; default
  * on: shortest latency for one batch at a time).  Callers that keep several batches in flight on their own streams should turn it

@@ -14,7 +14,7 @@ LIB_PATH = os.environ.get("SMTTS_LIB") or os.path.join(_HERE, "libsmalltts_hip.s
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "smalltts_hip.h")
 
 _lib = None
-ABI_VERSION = 9   # include/smalltts_hip.h SMTTS_ABI_VERSION
+ABI_VERSION = 10  # include/smalltts_hip.h SMTTS_ABI_VERSION
 
 vp, i32, i64, u64, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
 cstr = C.c_char_p
@@ -59,6 +59,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_voice_expand": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
     "smtts_randn_rows": (i32, [vp, vp, vp, vp, vp, i32, i32, i32]),
     "smtts_stitch": (i32, [vp, vp, vp, i32, i64, vp, vp, vp, i32, vp, i64, i32]),
+    "smtts_endpoints": (i32, [vp, vp, vp, i32, i64, vp, i32, f32, f32, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp]),
+    "smtts_stitch_seg": (i32, [vp, vp, vp, i32, i64, vp, vp, vp, vp, i32, vp, i64, i32]),
     "smtts_alpha_sigma": (None, [f32, C.POINTER(f32), C.POINTER(f32)]),
     "smtts_profile_enable": (i32, [vp, i32]),
     "smtts_profile_report": (i32, [vp, C.c_char_p, sz]),

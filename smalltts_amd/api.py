@@ -153,6 +153,90 @@ def plan_long(ns: Sequence[int], max_batch: int = 8, gap_ms: float = 120.0, hop:
     return groups, offsets, (pos - gap if len(ns) else 0)
 
 
+def plan_packed(ns_trimmed: Sequence[int], gap_ms: float = 120.0) -> Tuple[List[int], int]:
+    """The plan of a trimmed join: pieces of `ns_trimmed` SAMPLES (what the endpoint kernels returned), in order.  A piece with n = 0
+    takes neither room nor a gap; the others lie round(gap_ms * 24) samples apart.  -> (every piece's offset in the joined waveform
+    (an empty piece: where the last non-empty one ended), S = sum(n_i) + (k - 1) gap over the k non-empty pieces; 0 when all are empty)."""
+    gap = max(0, int(round(gap_ms * SAMPLE_RATE / 1000.0)))
+    offsets, pos, k = [], 0, 0
+    for n in ns_trimmed:
+        n = int(n)
+        if n < 0:
+            raise ValueError("plan_packed: negative length")
+        if n and k:
+            pos += gap
+        offsets.append(pos)
+        if n:
+            pos += n
+            k += 1
+    return offsets, pos
+
+
+class Endpointing:
+    """How the ends of the speech in a row are found, and how the row is levelled (immutable; DESIGN 8a, include/smalltts_hip.h
+    smtts_endpoints).  frame_ms: analysis frame; a frame is active when its mean power is above both `rel_db` below the row's
+    loudest frame and `floor_dbfs`; speech = runs of at least `min_run` active frames; `lead_ms` / `tail_ms` are kept in front of the
+    first / behind the last speech frame.  level_dbfs None: no gain; else the speech frames' RMS is brought to it, by at most
+    `max_gain_db`, and never so far that the row's peak passes `peak_dbfs`."""
+    __slots__ = ("frame_ms", "rel_db", "floor_dbfs", "min_run", "lead_ms", "tail_ms", "level_dbfs", "peak_dbfs", "max_gain_db")
+
+    def __init__(self, frame_ms: float = 10.0, rel_db: float = 40.0, floor_dbfs: float = -80.0, min_run: int = 3, lead_ms: float = 30.0,
+                 tail_ms: float = 60.0, level_dbfs: Optional[float] = None, peak_dbfs: float = -1.0, max_gain_db: float = 20.0) -> None:
+        set_ = object.__setattr__
+        for k, v in (("frame_ms", float(frame_ms)), ("rel_db", float(rel_db)), ("floor_dbfs", float(floor_dbfs)), ("min_run", int(min_run)),
+                     ("lead_ms", float(lead_ms)), ("tail_ms", float(tail_ms)),
+                     ("level_dbfs", None if level_dbfs is None else float(level_dbfs)), ("peak_dbfs", float(peak_dbfs)),
+                     ("max_gain_db", float(max_gain_db))):
+            set_(self, k, v)
+        W = 4 * int(round(self.frame_ms * SAMPLE_RATE / 1000.0 / 4))
+        if not 16 <= W <= 4096:
+            raise ValueError(f"Endpointing: frame_ms = {frame_ms} gives a frame of {W} samples, outside [16, 4096]")
+        if not 1 <= self.min_run <= 16:
+            raise ValueError("Endpointing: min_run must be in [1, 16]")
+        if self.lead_ms < 0 or self.tail_ms < 0 or self.rel_db < 0:
+            raise ValueError("Endpointing: lead_ms, tail_ms and rel_db must not be negative")
+        if not all(np.isfinite(v) for v in (self.frame_ms, self.rel_db, self.floor_dbfs, self.lead_ms, self.tail_ms, self.peak_dbfs,
+                                            self.max_gain_db, 0.0 if self.level_dbfs is None else self.level_dbfs)):
+            raise ValueError("Endpointing: every parameter must be finite")
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Endpointing is immutable")
+
+    __delattr__ = __setattr__
+
+    def __repr__(self) -> str:
+        return "Endpointing(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Endpointing) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self) -> int:
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+    def kernel_params(self) -> Dict[str, object]:
+        """The kernel's parameters: float64 arithmetic, rounded to fp32 once.  W = 4 round(frame_ms * 24 / 4) samples, rel_pow =
+        10^(-rel_db / 10), floor_pow = 10^(floor_dbfs / 10), lead / tail = round(ms * 24) samples, target_rms = 10^(level_dbfs / 20)
+        (0 = no gain), peak_limit = 10^(peak_dbfs / 20), max_gain = 10^(max_gain_db / 20)."""
+        f32 = lambda v: np.float32(np.float64(v))
+        per_ms = SAMPLE_RATE / 1000.0
+        return {"W": 4 * int(round(self.frame_ms * per_ms / 4)), "rel_pow": f32(10.0 ** (-self.rel_db / 10.0)),
+                "floor_pow": f32(10.0 ** (self.floor_dbfs / 10.0)), "min_run": self.min_run,
+                "lead": int(round(self.lead_ms * per_ms)), "tail": int(round(self.tail_ms * per_ms)),
+                "target_rms": np.float32(0.0) if self.level_dbfs is None else f32(10.0 ** (self.level_dbfs / 20.0)),
+                "peak_limit": f32(10.0 ** (self.peak_dbfs / 20.0)), "max_gain": f32(10.0 ** (self.max_gain_db / 20.0))}
+
+
+def as_endpointing(trim) -> Optional["Endpointing"]:
+    """The `trim=` argument of the synthesis calls: None / False -> None (off), True -> Endpointing(), an Endpointing -> itself."""
+    if trim is None or trim is False:
+        return None
+    if trim is True:
+        return Endpointing()
+    if isinstance(trim, Endpointing):
+        return trim
+    raise TypeError(f"trim must be None, a bool or an Endpointing, got {type(trim).__name__}")
+
+
 def piece_seed(seed: int, i: int) -> int:
     """Seed of piece i of a long text: SeedSequence([seed, i]) reduced to 63 bits (like the replica seeds of SmallTTS)."""
     return int(np.random.SeedSequence([int(seed), int(i)]).generate_state(1, np.uint64)[0] >> 1)
@@ -319,23 +403,44 @@ class SmallTTS:
                                         np.zeros((1, 0), bool))
         return Voice(self.engine, cache["k_ref"], cache["v_ref"])
 
-    def encode_voice_wav(self, audio, sr: int) -> Voice:
+    def encode_voice_wav(self, audio, sr: int, trim=None) -> Voice:
         """Mono samples at `sr` Hz -> Voice: device resampler to 24 kHz, codec encoder (through Encoder.encode_reference and its
-        cache), then encode_voice."""
+        cache), then encode_voice.  `trim` (True or an Endpointing): the resampled clip is cut to the speech the endpoint kernels
+        find in it, [start, start + n) with n rounded DOWN to whole codec hops but never below one hop (a window that would then
+        pass the clip's end is moved back), so that room tone at the ends does not spend reference frames; a clip without speech
+        raises ValueError.  No gain is applied to a reference."""
         y = self.engine.resample(np.asarray(audio, np.float32).reshape(-1), int(sr), SAMPLE_RATE)
+        ep = as_endpointing(trim)
+        if ep is not None:
+            y = y.reshape(-1).contiguous()
+            total = int(y.numel())
+            if total < HOP_SIZE:
+                raise ValueError("encode_voice_wav: the clip is shorter than one codec hop")
+            seg = self.engine.endpoints(y.view(1, 1, -1), None, ep, lens=[total])[0].cpu()
+            start, n = int(seg[0, 0]), int(seg[0, 1])
+            if n == 0:
+                raise ValueError("encode_voice_wav: no speech found in the clip (an all-silent clip is not a voice)")
+            n = max(HOP_SIZE, n // HOP_SIZE * HOP_SIZE)
+            start = min(start, total - n)
+            y = y[start:start + n]
         lat = Encoder(engine=self.engine).encode_reference(y.reshape(1, 1, -1))
         return self.encode_voice(lat[0].numpy())
 
     def synthesize_batch(self, ref_latents: Optional[Sequence[np.ndarray]], phoneme_ids: Sequence[Sequence[int]],
                          durations, *, noise: Optional[np.ndarray] = None, return_latents: bool = False,
                          frames: Optional[Sequence[int]] = None, _defer: bool = False,
-                         voices: Optional[Sequence[Voice]] = None, seeds: Optional[Sequence[int]] = None):
+                         voices: Optional[Sequence[Voice]] = None, seeds: Optional[Sequence[int]] = None, trim=None):
         """Batched synthesize: per-utterance (R_i,64) refs, token lists and durations -> list of (1, samples).
         `frames` overrides the per-utterance frame counts (default floor(duration * 7.5), infer/onnx.py:84; the HTTP server
         rounds up like the reference's Rust server, pipeline.rs:66).
         `voices`: B Voice objects (encode_voice) instead of `ref_latents` (pass None): only the text half of the condition encoder
         runs, the reference half is gathered from the voices.  `seeds`: B integers; row b's noise is the (seeds[b], step) Philox
-        stream, so its latents do not depend on its batch-mates' seeds, lengths or order (not together with `noise`)."""
+        stream, so its latents do not depend on its batch-mates' seeds, lengths or order (not together with `noise`).
+        `trim` (True or an Endpointing): row b comes back as (1, n_b), the window of its speech (engine.endpoints), times the
+        row's gain when the Endpointing sets a level; cut and levelled on the device, so only the windows are copied out."""
+        ep = as_endpointing(trim)
+        if ep is not None and _defer:
+            raise ValueError("synthesize_batch: trim= and _defer exclude each other (synthesize_long trims its batches itself)")
         if voices is not None:
             if ref_latents is not None:
                 raise ValueError("synthesize_batch: pass either ref_latents or voices (with ref_latents=None), not both")
@@ -380,6 +485,22 @@ class SmallTTS:
         audio, x = run()
         if _defer:                                             # synthesize_batches: stay on the device / stream
             return audio, x, ns, run
+        if ep is not None:
+            seg, gain, _e = eng.endpoints(audio, ns, ep)
+            seg_h = seg.cpu().numpy()                          # synchronises: the saturation counters are final
+            if eng.check_fp16_range("synthesize"):
+                audio, x = run()
+                seg, gain, _e = eng.endpoints(audio, ns, ep)
+                seg_h = seg.cpu().numpy()
+            offs, S = plan_packed(seg_h[:, 1], 0.0)
+            packed = torch.zeros(S, device=eng.device)
+            eng.stitch_seg(audio, seg, gain if ep.level_dbfs is not None else None, offs, None, packed)
+            packed = packed.cpu().numpy()
+            outs = [packed[None, offs[b]: offs[b] + int(seg_h[b, 1])] for b in range(B)]
+            if return_latents:
+                xl = x.cpu().numpy()
+                return outs, [xl[b, : ns[b]] for b in range(B)]
+            return outs
         audio = audio.cpu().numpy()
         if eng.check_fp16_range("synthesize"):                 # an fp16 operand clipped: the site is split-bf16 now, run again
             audio, x = run()
@@ -442,7 +563,7 @@ class SmallTTS:
     def synthesize_long(self, voice: Voice, text: Optional[str] = None, *, token_lists: Optional[Sequence[Sequence[int]]] = None,
                         durations: Optional[Sequence[float]] = None, seed: Optional[int] = None, gap_ms: float = 120.0,
                         fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3, pcm16: bool = False,
-                        prefix_tokens: Optional[Sequence[int]] = None) -> np.ndarray:
+                        prefix_tokens: Optional[Sequence[int]] = None, trim=None, return_segments: bool = False):
         """A whole text in one voice -> one waveform (1, S), fp32 or (pcm16=True) int16 PCM, S = sum(3200 * n_i) + (pieces - 1) *
         round(gap_ms * 24).
 
@@ -453,7 +574,16 @@ class SmallTTS:
         per batch; the voice was encoded once.  Piece i draws its noise from seed SeedSequence([seed, i]) -> 63 bits.  The rows are
         joined on the device (engine.stitch: `gap_ms` of silence between pieces, a raised-cosine fade of `fade_ms` at both ends of
         each, fade_table) and copied to the host once.  `prefix_tokens` (the reference clip's transcription) is prepended to every
-        piece's tokens, as forward() prepends the transcription; the splitter's token budget shrinks by its length."""
+        piece's tokens, as forward() prepends the transcription; the splitter's token budget shrinks by its length.
+
+        `trim` (True = Endpointing(), or an Endpointing): a piece is as long as its guessed duration, whatever part of that is
+        speech, so the pause at a join is `gap_ms` plus the dead air the guess left.  With `trim` the ends of the speech of every
+        piece are found on the device (engine.endpoints, enqueued on each batch's own stream behind its decode), the table is read
+        back once, and the join puts the speech windows `gap_ms` apart (plan_packed; a piece without speech takes no room), each
+        times its gain when the Endpointing sets a level, faded over the window's own ends (engine.stitch_seg); S follows from the
+        windows.  `return_segments=True`: -> (waveform, [(offset in the waveform, n, start inside the piece, gain), ...] per piece),
+        the caller's subtitle / highlight timings (without trim: (offset, 3200 * n_i, 0, 1.0))."""
+        ep = as_endpointing(trim)
         if voice.engine is not self.engine:
             raise ValueError("synthesize_long: the Voice belongs to another engine")
         prefix = [int(t) for t in (prefix_tokens or [])]
@@ -474,18 +604,57 @@ class SmallTTS:
         eng = self.engine
         groups, offsets, S = plan_long(ns, max_batch, gap_ms)
         if not toks:
-            return np.zeros((1, 0), np.int16 if pcm16 else np.float32)
+            empty = np.zeros((1, 0), np.int16 if pcm16 else np.float32)
+            return (empty, []) if return_segments else empty
         base = self._next_seed() if seed is None else int(seed)
         seeds = [piece_seed(base, i) for i in range(len(toks))]
         calls = [lambda g=g: self.synthesize_batch(None, [toks[i] for i in g], None, frames=[ns[i] for i in g], voices=[voice] * len(g),
                                                    seeds=[seeds[i] for i in g], _defer=True) for g in groups]
+        if ep is not None:
+            return self._long_trimmed(calls, groups, ep, in_flight, gap_ms, fade_ms, pcm16, return_segments)
         pending = self._run_in_flight(calls, in_flight)
         out = torch.zeros(S, dtype=torch.int16 if pcm16 else torch.float32, device=eng.device)
         w = fade_table(fade_ms)
         fade = torch.from_numpy(w).to(eng.device) if w.size else None
         for g, (audio, _x, g_ns, _run) in zip(groups, pending):
             eng.stitch(audio, g_ns, [offsets[i] for i in g], fade, out)
-        return out.cpu().numpy()[None]
+        out = out.cpu().numpy()[None]
+        return (out, [(offsets[i], HOP_SIZE * ns[i], 0, 1.0) for i in range(len(ns))]) if return_segments else out
+
+    def _long_trimmed(self, calls, groups, ep: "Endpointing", in_flight: int, gap_ms: float, fade_ms: float, pcm16: bool,
+                      return_segments: bool):
+        """synthesize_long's trimmed join.  Every deferred batch enqueues its endpoints behind its decode, on its own stream, so they
+        overlap the other batches in flight; the fp16 range guard's re-run goes through the same wrapper and so recomputes them."""
+        eng = self.engine
+
+        def with_endpoints(run, g_ns):            # what _run_in_flight calls again when the range guard fires: (audio', latents)
+            def run2():
+                audio, x = run()
+                return (audio, eng.endpoints(audio, g_ns, ep)[:2]), x
+            return run2
+
+        def deferred(call):
+            def go():
+                audio, x, g_ns, run = call()
+                return (audio, eng.endpoints(audio, g_ns, ep)[:2]), x, g_ns, with_endpoints(run, g_ns)
+            return go
+
+        pending = self._run_in_flight([deferred(c) for c in calls], in_flight)
+        seg_d = [p[0][1][0] for p in pending]
+        gain_d = [p[0][1][1] for p in pending]
+        seg_h = torch.cat(seg_d).cpu().numpy()                  # one small read-back: 16 bytes per piece ...
+        gain_h = torch.cat(gain_d).cpu().numpy()                # ... and 4
+        offsets, S = plan_packed(seg_h[:, 1], gap_ms)
+        out = torch.zeros(S, dtype=torch.int16 if pcm16 else torch.float32, device=eng.device)
+        w = fade_table(fade_ms)
+        fade = torch.from_numpy(w).to(eng.device) if w.size else None
+        level = ep.level_dbfs is not None
+        for g, p, sd, gd in zip(groups, pending, seg_d, gain_d):
+            eng.stitch_seg(p[0][0], sd, gd if level else None, [offsets[i] for i in g], fade, out)
+        out = out.cpu().numpy()[None]
+        if not return_segments:
+            return out
+        return out, [(int(offsets[i]), int(seg_h[i, 1]), int(seg_h[i, 0]), float(gain_h[i])) for i in range(len(offsets))]
 
     def synthesize_sharded(self, ref_latents: Sequence[np.ndarray], phoneme_ids: Sequence[Sequence[int]],
                            duration_sec: float, *, max_batch: int = 8) -> np.ndarray:

@@ -169,6 +169,27 @@ int smtts_stitch(smtts_handle h, void* stream, const float* audio, int B, int64_
                                          (long)row_stride, ST(stream));
     return e == hipSuccess ? 0 : E.fail_hip(e, "stitch");
 }
+int smtts_endpoints(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* len, int W, float rel_pow,
+                    float floor_pow, int min_run, int lead, int tail, float target_rms, float peak_limit, float max_gain, float* e,
+                    float* pk, int64_t* seg, float* gain) { NULLCHK;
+    if (B <= 0 || row_stride <= 0 || !audio || !len || !e || !pk || !seg || !gain) return E.fail("endpoints: bad arguments");
+    if (W < 16 || W > 4096 || (W & 3) != 0) return E.fail("endpoints: W must be a multiple of 4 in [16, 4096]");
+    if (min_run < 1 || min_run > 16) return E.fail("endpoints: min_run must be in [1, 16]");
+    if (lead < 0 || tail < 0) return E.fail("endpoints: lead and tail must not be negative");
+    if (!(rel_pow >= 0.f) || !(floor_pow >= 0.f) || !(target_rms >= 0.f) || !(peak_limit > 0.f) || !(max_gain > 0.f))
+        return E.fail("endpoints: rel_pow, floor_pow, target_rms must be >= 0 and peak_limit, max_gain > 0");
+    hipError_t err = launch_endpoints(audio, (long)row_stride, len, W, rel_pow, floor_pow, min_run, lead, tail, target_rms, peak_limit,
+                                      max_gain, e, pk, seg, gain, B, ST(stream));
+    return err == hipSuccess ? 0 : E.fail_hip(err, "endpoints");
+}
+int smtts_stitch_seg(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* seg, const float* gain,
+                     const int64_t* off, const float* fade, int F, void* out, int64_t out_n, int pcm16) { NULLCHK;
+    if (B <= 0 || row_stride <= 0 || out_n <= 0 || F < 0 || !audio || !seg || !off || !out || (F > 0 && !fade))
+        return E.fail("stitch_seg: bad arguments");
+    hipError_t e = launch_stitch_seg(audio, (long)row_stride, seg, gain, off, fade, F, out, (long)out_n, pcm16, B, (long)row_stride,
+                                     ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "stitch_seg");
+}
 int smtts_set_dual_stream(smtts_handle h, int on) { NULLCHK; E.set_dual_stream(on != 0); return 0; }
 int smtts_set_tuning(smtts_handle h, int mode) { NULLCHK;
     if (mode != 0 && mode != 1) return E.fail("tuning mode must be 0 (latency) or 1 (throughput)");

@@ -1509,16 +1509,26 @@ __device__ __forceinline__ void stitch_put4(int16_t* y, const float v[4]) {
     for (int j = 0; j < 4; ++j) stitch_put(&r[j], v[j]);
     *reinterpret_cast<short4*>(y) = make_short4(r[0], r[1], r[2], r[3]);
 }
+// seg != null (smtts_stitch_seg): row b is the window x[b][start .. start + n) with (start, n) = seg[b], clamped into [0, max_len], and
+// len is not read; gain != null: the sample times gain[b] first (one fp32 multiply), then the fade weight (another).
 template <class T>
 __global__ __launch_bounds__(256) void stitch_kernel(const float* __restrict__ x, long x_stride, const int64_t* __restrict__ len,
+                                                     const int64_t* __restrict__ seg, const float* __restrict__ gain,
                                                      const int64_t* __restrict__ off, const float* __restrict__ w, int F,
                                                      T* __restrict__ y, long y_n, long max_len) {
     const int b = blockIdx.y;
-    const long n = len[b] < max_len ? len[b] : max_len, o = off[b];
+    long s0 = 0, n;
+    if (seg) {
+        s0 = seg[2 * b] < 0 ? 0 : seg[2 * b] > max_len ? max_len : seg[2 * b];
+        n = seg[2 * b + 1] < max_len - s0 ? seg[2 * b + 1] : max_len - s0;
+    } else {
+        n = len[b] < max_len ? len[b] : max_len;
+    }
+    const long o = off[b];
     const long i0 = ((long)blockIdx.x * blockDim.x + threadIdx.x) * 4;
     if (i0 >= n) return;
     const long Fb = F < n / 2 ? F : n / 2;
-    const float* xr = x + (long)b * x_stride;
+    const float* xr = x + (long)b * x_stride + s0;
     const int m = n - i0 < 4 ? (int)(n - i0) : 4;
     float v[4] = {0.f, 0.f, 0.f, 0.f};
     if (m == 4 && ((uintptr_t)(xr + i0) & 15) == 0) {
@@ -1526,6 +1536,11 @@ __global__ __launch_bounds__(256) void stitch_kernel(const float* __restrict__ x
         v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
     } else {
         for (int j = 0; j < m; ++j) v[j] = xr[i0 + j];
+    }
+    if (gain) {
+        const float g = gain[b];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = v[j] * g;
     }
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -1544,22 +1559,230 @@ __global__ __launch_bounds__(256) void stitch_kernel(const float* __restrict__ x
     }
 }
 template <class T>
-static hipError_t launch_stitch_t(const float* x, long x_stride, const int64_t* len, const int64_t* off, const float* w, int F, T* y,
-                                  long y_n, int B, long max_len, hipStream_t st) {
+static hipError_t launch_stitch_t(const float* x, long x_stride, const int64_t* len, const int64_t* seg, const float* gain,
+                                  const int64_t* off, const float* w, int F, T* y, long y_n, int B, long max_len, hipStream_t st) {
     if (B <= 0 || max_len <= 0 || y_n <= 0) return hipSuccess;
     const long quads = (max_len + 3) / 4;
-    ProfScope ps(st, "stitch", 1.0 * B * max_len, (4.0 + sizeof(T)) * B * max_len);
-    hipLaunchKernelGGL(stitch_kernel<T>, dim3((unsigned)((quads + 255) / 256), (unsigned)B), dim3(256), 0, st, x, x_stride, len, off, w, F, y,
-                       y_n, max_len);
+    ProfScope ps(st, seg ? "stitch_seg" : "stitch", (gain ? 2.0 : 1.0) * B * max_len, (4.0 + sizeof(T)) * B * max_len);
+    hipLaunchKernelGGL(stitch_kernel<T>, dim3((unsigned)((quads + 255) / 256), (unsigned)B), dim3(256), 0, st, x, x_stride, len, seg, gain,
+                       off, w, F, y, y_n, max_len);
     LAUNCH_CHECK();
 }
 hipError_t launch_stitch(const float* x, long x_stride, const int64_t* len, const int64_t* off, const float* w, int F, float* y, long y_n,
                          int B, long max_len, hipStream_t st) {
-    return launch_stitch_t<float>(x, x_stride, len, off, w, F, y, y_n, B, max_len, st);
+    return launch_stitch_t<float>(x, x_stride, len, nullptr, nullptr, off, w, F, y, y_n, B, max_len, st);
 }
 hipError_t launch_stitch_pcm16(const float* x, long x_stride, const int64_t* len, const int64_t* off, const float* w, int F, int16_t* y,
                                long y_n, int B, long max_len, hipStream_t st) {
-    return launch_stitch_t<int16_t>(x, x_stride, len, off, w, F, y, y_n, B, max_len, st);
+    return launch_stitch_t<int16_t>(x, x_stride, len, nullptr, nullptr, off, w, F, y, y_n, B, max_len, st);
+}
+hipError_t launch_stitch_seg(const float* x, long x_stride, const int64_t* seg, const float* gain, const int64_t* off, const float* w, int F,
+                             void* y, long y_n, int pcm16, int B, long max_len, hipStream_t st) {
+    return pcm16 ? launch_stitch_t<int16_t>(x, x_stride, nullptr, seg, gain, off, w, F, static_cast<int16_t*>(y), y_n, B, max_len, st)
+                 : launch_stitch_t<float>(x, x_stride, nullptr, seg, gain, off, w, F, static_cast<float*>(y), y_n, B, max_len, st);
+}
+
+// ------------------------------------------------------------------------------------------
+// endpoints of the speech in a decoded row: per-frame mean power, then one decision per row (include/smalltts_hip.h smtts_endpoints)
+// ------------------------------------------------------------------------------------------
+// e[b][f] = (sum of x^2 over frame f of row b) / cnt, pk[b][f] = max |x| over it; frame f covers [f W, min(len_b, (f + 1) W)).  A wave
+// owns EP_FPW consecutive frames and sweeps their span one float4 per lane (W % 4 == 0: a quad never straddles two frames), so a frame
+// of 60 quads does not idle four lanes per pass; every lane keeps one partial per frame.  The order of the sum is fixed: within a
+// quad x0^2 + x1^2 + x2^2 + x3^2 left to right, a lane's quads in ascending order, the lanes by the xor butterfly 32, 16, .. 1 (every
+// lane ends with the same value); it does not depend on B, the grid or the launch.  Nothing behind len_b is read: what a padded row
+// holds there is decoded padding.  16-byte loads where the address allows, scalar loads for an unaligned row and the row's last quad.
+constexpr int EP_FPW = 4;     // frames per wave
+constexpr int EP_WAVES = 4;   // waves per workgroup
+__global__ __launch_bounds__(64 * EP_WAVES) void frame_energy_kernel(const float* __restrict__ x, long x_stride,
+                                                                     const int64_t* __restrict__ len, int W, float* __restrict__ e,
+                                                                     float* __restrict__ pk, int Fmax) {
+    const int b = blockIdx.y, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    long n = len[b];
+    n = n < 0 ? 0 : n > x_stride ? x_stride : n;
+    const long f0 = ((long)blockIdx.x * EP_WAVES + wave) * EP_FPW;
+    const long base = f0 * W;                       // first sample of this wave's span
+    if (base >= n) return;                          // wave-uniform
+    const float* xr = x + (long)b * x_stride;
+    const int Wq = W >> 2;
+    const long end = base + (long)EP_FPW * W < n ? base + (long)EP_FPW * W : n;
+    float acc[EP_FPW], mx[EP_FPW];
+#pragma unroll
+    for (int g = 0; g < EP_FPW; ++g) { acc[g] = 0.f; mx[g] = 0.f; }
+    for (int q = lane; q < EP_FPW * Wq; q += 64) {
+        const long i0 = base + 4L * q;
+        if (i0 >= end) break;
+        const int m = end - i0 < 4 ? (int)(end - i0) : 4;
+        float v[4] = {0.f, 0.f, 0.f, 0.f};
+        if (m == 4 && ((uintptr_t)(xr + i0) & 15) == 0) {
+            const float4 t = *reinterpret_cast<const float4*>(xr + i0);
+            v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w;
+        } else {
+            for (int j = 0; j < m; ++j) v[j] = xr[i0 + j];
+        }
+        const float s = ((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]) + v[3] * v[3];
+        const float p = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+        const int g = q / Wq;
+#pragma unroll
+        for (int k = 0; k < EP_FPW; ++k)
+            if (g == k) { acc[k] += s; mx[k] = fmaxf(mx[k], p); }
+    }
+#pragma unroll
+    for (int g = 0; g < EP_FPW; ++g) {
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            acc[g] += __shfl_xor(acc[g], o, 64);
+            mx[g] = fmaxf(mx[g], __shfl_xor(mx[g], o, 64));
+        }
+    }
+    if (lane < EP_FPW) {
+        const long f = f0 + lane, lo = f * W;
+        if (lo < n && f < Fmax) {
+            const long cnt = n - lo < W ? n - lo : W;
+            float a = acc[0], m = mx[0];
+#pragma unroll
+            for (int k = 1; k < EP_FPW; ++k)
+                if (lane == k) { a = acc[k]; m = mx[k]; }
+            e[(long)b * Fmax + f] = __fdiv_rn(a, (float)cnt);
+            pk[(long)b * Fmax + f] = m;
+        }
+    }
+}
+
+// One workgroup per row over e[b][0 .. F_b), F_b = ceil(len_b / W), read from global memory in loops (a row may have thousands of
+// frames: nothing assumes that it fits LDS).  Pass 1: E = max e, the row's peak.  Pass 2, EP_CHUNK frames at a time: the chunk's
+// energies and a halo of 16 frames to either side go to LDS (-1 outside the row: never active), then frame f is speech iff it is
+// active (e > thr) and the run of active frames around it, counted up to min_run - 1 to either side, is at least min_run long; the
+// first / last speech frame and the power sum over speech frames.  The global loads of both passes are issued four at a time at
+// clamped addresses, independent of one another: a chain of dependent L2 round trips per frame is what this kernel would otherwise
+// be.  Sums: thread t adds its frames t, t + 256, .. in ascending order, then the xor butterfly inside a wave and the four waves in
+// order: fixed, and independent of the batch.  (start, n, gain) as include/smalltts_hip.h states them.
+constexpr int EP_CHUNK = 2048;   // frames per LDS chunk (a multiple of 1024)
+constexpr int EP_HALO = 16;      // >= the largest min_run
+struct EndpointParams {
+    int W, min_run, lead, tail;
+    float rel_pow, floor_pow, target_rms, peak_limit, max_gain;
+};
+__global__ __launch_bounds__(256) void endpoint_decide_kernel(const float* __restrict__ e, const float* __restrict__ pk, int Fmax,
+                                                              const int64_t* __restrict__ len, long x_stride, EndpointParams P,
+                                                              int64_t* __restrict__ seg, float* __restrict__ gain) {
+    __shared__ float s_f[2][4];
+    __shared__ int s_i[2][4];
+    __shared__ long s_c[4];
+    __shared__ float s_e[EP_CHUNK + 2 * EP_HALO];
+    const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wave = t >> 6;
+    long n = len[b];
+    n = n < 0 ? 0 : n > x_stride ? x_stride : n;
+    const int F = (int)((n + P.W - 1) / P.W);
+    const float* er = e + (long)b * Fmax;
+    const float* pr = pk + (long)b * Fmax;
+    float E = 0.f, peak = 0.f;
+    for (int f0 = t; f0 < F; f0 += 1024) {          // a frame read twice (clamped) does not change a maximum
+        float ev[4], pv[4];
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int f = f0 + 256 * j < F ? f0 + 256 * j : F - 1;
+            ev[j] = er[f];
+            pv[j] = pr[f];
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) { E = fmaxf(E, ev[j]); peak = fmaxf(peak, pv[j]); }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { E = fmaxf(E, __shfl_xor(E, o, 64)); peak = fmaxf(peak, __shfl_xor(peak, o, 64)); }
+    if (lane == 0) { s_f[0][wave] = E; s_f[1][wave] = peak; }
+    __syncthreads();
+    E = fmaxf(fmaxf(s_f[0][0], s_f[0][1]), fmaxf(s_f[0][2], s_f[0][3]));
+    peak = fmaxf(fmaxf(s_f[1][0], s_f[1][1]), fmaxf(s_f[1][2], s_f[1][3]));
+    __syncthreads();
+    const float thr = fmaxf(E * P.rel_pow, P.floor_pow);
+    int a = 0x7fffffff, z = -1;
+    float psum = 0.f;
+    long csum = 0;
+    for (int c0 = 0; c0 < F; c0 += EP_CHUNK) {
+        const int lim = (F - c0 < EP_CHUNK ? F - c0 : EP_CHUNK) + 2 * EP_HALO;     // s_e[i] holds frame c0 - EP_HALO + i
+        for (int i0 = t; i0 < lim; i0 += 1024) {
+            float ev[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int f = c0 - EP_HALO + i0 + 256 * j;
+                ev[j] = er[f < 0 ? 0 : f < F ? f : F - 1];
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int i = i0 + 256 * j, f = c0 - EP_HALO + i;
+                if (i < lim) s_e[i] = f >= 0 && f < F ? ev[j] : -1.0f;
+            }
+        }
+        __syncthreads();
+        for (int i = EP_HALO + t; i < lim - EP_HALO; i += 256) {
+            const float ef = s_e[i];
+            if (!(ef > thr)) continue;
+            int run = 1;
+            for (int k = 1; k < P.min_run && s_e[i - k] > thr; ++k) ++run;
+            for (int k = 1; k < P.min_run && s_e[i + k] > thr; ++k) ++run;
+            if (run < P.min_run) continue;
+            const int f = c0 - EP_HALO + i;
+            const long lo = (long)f * P.W, cnt = n - lo < P.W ? n - lo : P.W;
+            a = f < a ? f : a;
+            z = f > z ? f : z;
+            psum += ef * (float)cnt;
+            csum += cnt;
+        }
+        __syncthreads();
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const int a2 = __shfl_xor(a, o, 64), z2 = __shfl_xor(z, o, 64);
+        a = a2 < a ? a2 : a;
+        z = z2 > z ? z2 : z;
+        psum += __shfl_xor(psum, o, 64);
+        csum += __shfl_xor(csum, o, 64);
+    }
+    if (lane == 0) { s_i[0][wave] = a; s_i[1][wave] = z; s_f[0][wave] = psum; s_c[wave] = csum; }
+    __syncthreads();
+    if (t != 0) return;
+    for (int k = 1; k < 4; ++k) {
+        a = s_i[0][k] < a ? s_i[0][k] : a;
+        z = s_i[1][k] > z ? s_i[1][k] : z;
+    }
+    psum = ((s_f[0][0] + s_f[0][1]) + s_f[0][2]) + s_f[0][3];
+    csum = s_c[0] + s_c[1] + s_c[2] + s_c[3];
+    long start = 0, cnt = 0;
+    float g = 1.0f;
+    if (z >= 0) {
+        start = (long)a * P.W - P.lead;
+        start = start < 0 ? 0 : start;
+        long stop = (long)(z + 1) * P.W + P.tail;
+        stop = stop > n ? n : stop;
+        cnt = stop - start;
+        if (P.target_rms != 0.f) {
+            const float pw = __fdiv_rn(psum, (float)csum);
+            g = __fdiv_rn(P.target_rms, __fsqrt_rn(pw));
+            g = fminf(g, P.max_gain);
+            if (peak * g > P.peak_limit) g = __fdiv_rn(P.peak_limit, peak);
+        }
+    }
+    seg[2 * b] = start;
+    seg[2 * b + 1] = cnt;
+    gain[b] = g;
+}
+hipError_t launch_endpoints(const float* x, long x_stride, const int64_t* len, int W, float rel_pow, float floor_pow, int min_run, int lead,
+                            int tail, float target_rms, float peak_limit, float max_gain, float* e, float* pk, int64_t* seg, float* gain,
+                            int B, hipStream_t st) {
+    if (B <= 0 || x_stride <= 0) return hipSuccess;
+    const int Fmax = (int)((x_stride + W - 1) / W);
+    {
+        ProfScope ps(st, "frame_energy", 2.0 * B * x_stride, 4.0 * B * x_stride + 8.0 * B * Fmax);
+        const int per_wg = EP_WAVES * EP_FPW;
+        hipLaunchKernelGGL(frame_energy_kernel, dim3((unsigned)((Fmax + per_wg - 1) / per_wg), (unsigned)B), dim3(64 * EP_WAVES), 0, st, x,
+                           x_stride, len, W, e, pk, Fmax);
+        hipError_t err = hipGetLastError();
+        if (err != hipSuccess) return err;
+    }
+    EndpointParams P{W, min_run, lead, tail, rel_pow, floor_pow, target_rms, peak_limit, max_gain};
+    ProfScope ps(st, "endpoint_decide", 0.0, 2.0 * 8.0 * B * Fmax + 20.0 * B);
+    hipLaunchKernelGGL(endpoint_decide_kernel, dim3((unsigned)B), dim3(256), 0, st, e, pk, Fmax, len, x_stride, P, seg, gain);
+    LAUNCH_CHECK();
 }
 
 // t[i] = float32(np.linspace(1, 0, n))[i]: float64 arithmetic, exact end point (reference infer/onnx.py:98)

@@ -231,5 +231,13 @@ hipError_t launch_stitch(const float* x, long x_stride, const int64_t* len, cons
                          int B, long max_len, hipStream_t st);
 hipError_t launch_stitch_pcm16(const float* x, long x_stride, const int64_t* len, const int64_t* off, const float* w, int F, int16_t* y,
                                long y_n, int B, long max_len, hipStream_t st);
+// stitch with a source window and an optional gain per row: seg [B][2] int64 (start, n) clamped into the row, gain [B] or null
+hipError_t launch_stitch_seg(const float* x, long x_stride, const int64_t* seg, const float* gain, const int64_t* off, const float* w, int F,
+                             void* y, long y_n, int pcm16, int B, long max_len, hipStream_t st);
+// endpoints of the speech in each row (two launches: frame_energy, endpoint_decide): e, pk [B][ceil(x_stride / W)] per-frame mean power
+// and peak (written for frames of the row, untouched behind), seg [B][2] = (start, n), gain [B]; W % 4 == 0, 1 <= min_run <= 16
+hipError_t launch_endpoints(const float* x, long x_stride, const int64_t* len, int W, float rel_pow, float floor_pow, int min_run, int lead,
+                            int tail, float target_rms, float peak_limit, float max_gain, float* e, float* pk, int64_t* seg, float* gain,
+                            int B, hipStream_t st);
 // t[i] = float32(np.linspace(1, 0, n))[i] on the device (sampler timesteps)
 hipError_t launch_linspace10(float* t, int n, hipStream_t st);

@@ -492,6 +492,64 @@ class HipEngine:
                                        _p(out), out.numel(), int(out.dtype == torch.int16)), "stitch")
         return out
 
+    def endpoints(self, audio: torch.Tensor, ns, ep, *, lens=None, return_peaks: bool = False):
+        """Endpoints of the speech in each row of a decoded batch (smtts_endpoints; the definition: include/smalltts_hip.h).
+        audio (B,1,S) contiguous fp32 on the device; ns frames per row (row b is its first hop * ns[b] samples), or `lens` samples
+        per row instead (pass ns=None); ep an api.Endpointing (anything with .kernel_params()).  -> (seg, gain, e) on the device:
+        seg int64 (B,2) = (start, n), gain fp32 (B), e fp32 (B, ceil(S / W)) the per-frame mean power (row b: ceil(len_b / W) entries, NOT written behind);
+        with return_peaks=True also pk, the per-frame peaks.  Two launches on the current stream, no synchronisation."""
+        if audio.dim() != 3 or audio.shape[1] != 1:
+            raise ValueError("endpoints: audio must be (B,1,S)")
+        B, row = int(audio.shape[0]), int(audio.shape[-1])
+        if (ns is None) == (lens is None):
+            raise ValueError("endpoints: pass either ns (frames per row) or lens= (samples per row)")
+        lens = [self.hop * int(n) for n in ns] if lens is None else [int(n) for n in lens]
+        if (audio.dtype != torch.float32 or not audio.is_contiguous() or audio.device != self.device or B < 1 or row < 1
+                or len(lens) != B or min(lens) < 0 or max(lens) > row):
+            raise ValueError("endpoints: audio must be contiguous fp32 (B,1,S) on the engine's device with 0 <= len[b] <= S")
+        p = ep.kernel_params()
+        W = int(p["W"])
+        if W % 4 or not 16 <= W <= 4096 or not 1 <= int(p["min_run"]) <= 16 or int(p["lead"]) < 0 or int(p["tail"]) < 0:
+            raise ValueError(f"endpoints: W % 4 == 0, 16 <= W <= 4096, 1 <= min_run <= 16, lead, tail >= 0 (got {p})")
+        Fmax = (row + W - 1) // W
+        e = torch.empty(2, B, Fmax, device=self.device)         # [0] mean power, [1] peak: no fill launch
+        seg = torch.empty(B, 2, dtype=torch.int64, device=self.device)
+        gain = torch.empty(B, device=self.device)
+        tab = self._upload_i64([lens])
+        self._ck(self.lib.smtts_endpoints(self.h, self._stream(), _p(audio), B, row, _p(tab[0]), W, float(p["rel_pow"]),
+                                          float(p["floor_pow"]), int(p["min_run"]), int(p["lead"]), int(p["tail"]),
+                                          float(p["target_rms"]), float(p["peak_limit"]), float(p["max_gain"]), _p(e[0]), _p(e[1]),
+                                          _p(seg), _p(gain)), "endpoints")
+        return (seg, gain, e[0], e[1]) if return_peaks else (seg, gain, e[0])
+
+    def stitch_seg(self, audio: torch.Tensor, seg: torch.Tensor, gain: Optional[torch.Tensor], offsets, fade: Optional[torch.Tensor],
+                   out: torch.Tensor) -> torch.Tensor:
+        """stitch with a source window and an optional gain per row (smtts_stitch_seg): seg int64 (B,2) = (start, n) and gain fp32 (B)
+        or None, both on the device as endpoints() returns them; offsets the windows' absolute sample offsets in `out` (host
+        integers).  out[offsets[b] + i] = audio[b, 0, start_b + i] * gain[b] * g for i < n_b.  The windows are clamped into the row and
+        samples outside `out` are dropped by the kernel: the host does not know n_b here."""
+        B, row = int(audio.shape[0]), int(audio.shape[-1])
+        if audio.dtype != torch.float32 or not audio.is_contiguous() or audio.device != self.device or len(offsets) != B or row < 1:
+            raise ValueError("stitch_seg: audio must be contiguous fp32 (B,1,S) on the engine's device, one offset per row")
+        if seg.dtype != torch.int64 or tuple(seg.shape) != (B, 2) or not seg.is_contiguous() or seg.device != self.device:
+            raise ValueError("stitch_seg: seg must be a contiguous int64 (B,2) tensor on the engine's device")
+        if gain is not None and (gain.dtype != torch.float32 or tuple(gain.shape) != (B,) or not gain.is_contiguous()
+                                 or gain.device != self.device):
+            raise ValueError("stitch_seg: gain must be a contiguous fp32 (B,) tensor on the engine's device, or None")
+        if out.dtype not in (torch.float32, torch.int16) or out.dim() != 1 or not out.is_contiguous() or out.device != self.device:
+            raise ValueError("stitch_seg: out must be a contiguous 1-D fp32 or int16 tensor on the engine's device")
+        if out.numel() == 0:
+            return out
+        if any(int(o) < 0 or int(o) > out.numel() for o in offsets):
+            raise ValueError("stitch_seg: an offset lies outside out")
+        F = 0 if fade is None else int(fade.numel())
+        if F and (fade.dtype != torch.float32 or fade.device != self.device or not fade.is_contiguous()):
+            raise ValueError("stitch_seg: fade must be a contiguous fp32 tensor on the engine's device")
+        tab = self._upload_i64([[int(o) for o in offsets]])
+        self._ck(self.lib.smtts_stitch_seg(self.h, self._stream(), _p(audio), B, row, _p(seg), _p(gain), _p(tab[0]),
+                                           _p(fade) if F else None, F, _p(out), out.numel(), int(out.dtype == torch.int16)), "stitch_seg")
+        return out
+
     # ---- device-side audio front / back end ---------------------------------------------------------
     def resample(self, audio, sr: int, target: int = 24_000) -> torch.Tensor:
         """(samples,) or (channels, samples) float -> resampled on the device (same bank as audio.resample_hq)."""

@@ -1,11 +1,11 @@
-"""python -m smalltts_amd.scripts.clone --wav ref.wav --text "..." [--duration S] [--out out/clone.wav]
+"""python -m smalltts_amd.scripts.clone --wav ref.wav --text "..." [--duration S] [--out out/clone.wav] [--trim] [--trim-ref]
 (reference src/scripts/infer/clone.py: read wav -> mono -> 24 kHz -> codec encode -> synthesize)"""
 import argparse
 from pathlib import Path
 
 import torch
 
-from ..api import Encoder, SmallTTS, estimate_duration
+from ..api import HOP_SIZE, Encoder, Endpointing, SmallTTS, estimate_duration
 from ..audio import write_wav_pcm16
 from ._common import add_engine_args, load_reference_wav, tokens_for
 
@@ -16,6 +16,8 @@ def main(argv=None):
     ap.add_argument("--text", required=True, help="text to speak")
     ap.add_argument("--duration", type=float, default=None, help="duration in seconds (auto if omitted)")
     ap.add_argument("--out", default="out/clone.wav")
+    ap.add_argument("--trim", action="store_true", help="write only the speech: the ends the endpoint kernels find, not the whole duration")
+    ap.add_argument("--trim-ref", action="store_true", help="cut the reference clip to its speech (whole codec hops) before encoding it")
     add_engine_args(ap)
     args = ap.parse_args(argv)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
@@ -24,12 +26,21 @@ def main(argv=None):
     enc = Encoder(**kw)
     x = load_reference_wav(args.wav, enc.engine)
     print("encoding reference audio")
-    ref_latents = enc.encode_reference(torch.from_numpy(x))[0].numpy()
     tts = SmallTTS(num_steps=args.steps, seed=args.seed, **kw)
+    if args.trim_ref:
+        seg = enc.engine.endpoints(torch.from_numpy(x).to(enc.engine.device).contiguous(), None, Endpointing(), lens=[x.shape[-1]])[0].cpu()
+        start, n = int(seg[0, 0]), int(seg[0, 1])
+        if n == 0:
+            raise SystemExit("--trim-ref: no speech found in the reference clip")
+        n = max(HOP_SIZE, n // HOP_SIZE * HOP_SIZE)      # as SmallTTS.encode_voice_wav(trim=True) cuts it
+        start = max(0, min(start, x.shape[-1] - n))
+        x = x[..., start:start + n]
+    ref_latents = enc.encode_reference(torch.from_numpy(x))[0].numpy()
     tokens = tokens_for(args, args.text)
     duration = args.duration or estimate_duration(args.text)
     print(f"generating ({duration:.1f}s)")
-    audio = tts.synthesize(ref_latents, tokens, duration)
+    audio = (tts.synthesize_batch([ref_latents], [tokens], [duration], trim=True)[0] if args.trim
+             else tts.synthesize(ref_latents, tokens, duration))
     write_wav_pcm16(args.out, audio.squeeze(), 24_000)
     print(args.out)
 

@@ -1,11 +1,11 @@
-"""python -m smalltts_amd.scripts.longform --wav ref.wav --text-file text.txt [--out out/longform.wav]
+"""python -m smalltts_amd.scripts.longform --wav ref.wav --text-file text.txt [--out out/longform.wav] [--trim [--level DBFS]]
 A whole text in one cloned voice: the voice is encoded once, the text is cut into utterance-sized pieces (api.split_text), the
 pieces run as batches in flight and are joined on the device (api.SmallTTS.synthesize_long).
 Without espeak: --tokens-file (one comma-separated token list per line = one piece) with --durations (seconds, one per line)."""
 import argparse
 from pathlib import Path
 
-from ..api import SmallTTS, estimate_duration, split_text
+from ..api import Endpointing, SmallTTS, estimate_duration, split_text
 from ..audio import read_wav, write_wav_pcm16
 from ..phonemes import get_token_ids, parse_tokens_arg
 from ._common import add_engine_args
@@ -20,6 +20,8 @@ def main(argv=None):
     ap.add_argument("--out", default="out/longform.wav")
     ap.add_argument("--gap-ms", type=float, default=120.0, help="silence between pieces")
     ap.add_argument("--fade-ms", type=float, default=5.0, help="raised-cosine fade at both ends of every piece")
+    ap.add_argument("--trim", action="store_true", help="join the pieces at the ends of their speech, not of their guessed durations")
+    ap.add_argument("--level", type=float, default=None, metavar="DBFS", help="with --trim: bring every piece's speech to this RMS level")
     ap.add_argument("--max-batch", type=int, default=8)
     ap.add_argument("--in-flight", type=int, default=3)
     add_engine_args(ap)
@@ -28,6 +30,8 @@ def main(argv=None):
         ap.error("pass either --text-file or --tokens-file")
     if args.tokens_file and not args.durations:
         ap.error("--tokens-file needs --durations")
+    if args.level is not None and not args.trim:
+        ap.error("--level needs --trim")
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     print("loading")
     tts = SmallTTS(weights=args.weights, device=args.device, precision=args.precision, num_steps=args.steps, seed=args.seed)
@@ -36,7 +40,8 @@ def main(argv=None):
     if y.ndim == 2:
         y = y.mean(axis=1)
     voice = tts.encode_voice_wav(y, sr)
-    kw = dict(seed=args.seed, gap_ms=args.gap_ms, fade_ms=args.fade_ms, max_batch=args.max_batch, in_flight=args.in_flight)
+    kw = dict(seed=args.seed, gap_ms=args.gap_ms, fade_ms=args.fade_ms, max_batch=args.max_batch, in_flight=args.in_flight,
+              trim=Endpointing(level_dbfs=args.level) if args.trim else None)
     if args.tokens_file:
         with open(args.tokens_file) as f:
             token_lists = [parse_tokens_arg(line) for line in f if line.strip()]

@@ -15,7 +15,10 @@ single-threaded by contract) and
   * encodes each reference voice once (content-hash cache, `Encoder.encode_reference`),
 while a completer thread waits for each batch's event, copies the audio out and wakes the handlers.
 Build additions to the request: an optional `tokens` part (phoneme ids as JSON or comma separated: no espeak needed) and an
-optional `seed` query parameter (per-request noise stream, so a result does not depend on which batch the request rode in).
+optional `seed` query parameter (per-request noise stream, so a result does not depend on which batch the request rode in);
+an optional `trim=1` query parameter (and, only with it, `level=<dBFS>`): the answer is the speech window the endpoint kernels find
+(api.Endpointing defaults), levelled when asked, with its place in the untrimmed utterance in the headers `x-smtts-start` /
+`x-smtts-samples`.  Without the parameter (or with trim=0) the answer is byte for byte what it was.
 
     python -m smalltts_amd.server --port 3000 --weights assets/smalltts.smtts
 """
@@ -150,11 +153,33 @@ def validate_request(duration: float, tokens) -> int:
     return frames_for(duration)
 
 
-class Request:
-    __slots__ = ("wav", "sr", "tokens", "duration", "seed", "future", "t_in")
+def parse_trim_query(q: dict):
+    """The optional `trim` / `level` query parameters -> None (off: the answer is today's) or an api.Endpointing.  `trim` is 1 / true
+    or 0 / false; `level` (dBFS of the speech after levelling, -60 .. 0) is only accepted together with trim=1.  Anything else is a
+    400 for the offender alone, like validate_request."""
+    from .api import Endpointing
+    raw = q.get("trim", ["0"])[0].strip().lower()
+    if raw not in ("0", "1", "true", "false"):
+        raise HttpError(400, "invalid `trim`: 0 or 1")
+    on = raw in ("1", "true")
+    if "level" not in q:
+        return Endpointing() if on else None
+    if not on:
+        raise HttpError(400, "invalid `level`: only together with trim=1")
+    try:
+        level = float(q["level"][0])
+    except Exception:
+        raise HttpError(400, "invalid `level`: a number of dBFS")
+    if not math.isfinite(level) or not -60.0 <= level <= 0.0:
+        raise HttpError(400, "invalid `level`: -60 .. 0 dBFS")
+    return Endpointing(level_dbfs=level)
 
-    def __init__(self, wav, sr, tokens, duration, seed):
-        self.wav, self.sr, self.tokens, self.duration, self.seed = wav, sr, tokens, duration, seed
+
+class Request:
+    __slots__ = ("wav", "sr", "tokens", "duration", "seed", "trim", "future", "t_in")
+
+    def __init__(self, wav, sr, tokens, duration, seed, trim=None):
+        self.wav, self.sr, self.tokens, self.duration, self.seed, self.trim = wav, sr, tokens, duration, seed, trim
         self.future: Future = Future()
         self.t_in = time.perf_counter()
 
@@ -275,6 +300,8 @@ class Batcher:
                                     noise[s_, b, :g_ns[b]] = self.eng.randn(g_ns[b] * LATENT, r.seed, s_).view(g_ns[b], LATENT)
                             audio, _, _, _ = self.tts.synthesize_batch(g_refs, [r.tokens for r in g_ok], [r.duration for r in g_ok],
                                                                        noise=noise, frames=g_ns, _defer=True)
+                            # endpoints behind the decode, on the batch's stream: one pair of launches per distinct setting
+                            ends = {ep: self.eng.endpoints(audio, g_ns, ep)[:2] for ep in {r.trim for r in g_ok if r.trim is not None}}
                             ev = torch.cuda.Event()
                             ev.record()
                         self.eng.use_workspace(None)
@@ -282,7 +309,7 @@ class Batcher:
                         self.stats["batches"] += 1
                         self.stats["max_batch_seen"] = max(self.stats["max_batch_seen"], len(g_ok))
                         self.stats["max_padded_frames"] = max(self.stats.get("max_padded_frames", 0), len(g_ok) * max(g_ns))
-                        self.done_q.put((ev, audio, g_ns, g_ok))
+                        self.done_q.put((ev, audio, g_ns, g_ok, ends))
                     except Exception as e:
                         self.eng.use_workspace(None)
                         self._slots.release()
@@ -316,12 +343,21 @@ class Batcher:
             item = self.done_q.get()
             if item is None:
                 break
-            ev, audio, ns, reqs = item
+            ev, audio, ns, reqs, ends = item
             try:
                 ev.synchronize()
                 host = audio.cpu().numpy()
+                ends = {ep: (seg.cpu().numpy(), gain.cpu().numpy()) for ep, (seg, gain) in ends.items()}
                 for b, r in enumerate(reqs):
-                    r.future.set_result(host[b, 0, : HOP * ns[b]].copy())
+                    if r.trim is None:
+                        r.future.set_result(host[b, 0, : HOP * ns[b]].copy())
+                        continue
+                    seg, gain = ends[r.trim]       # a trimmed request answers (samples, start): the window, times its gain if levelled
+                    start, n = int(seg[b, 0]), int(seg[b, 1])
+                    y = host[b, 0, start:start + n].copy()
+                    if r.trim.level_dbfs is not None:
+                        y = y * np.float32(gain[b])
+                    r.future.set_result((y, start))
             except Exception as e:
                 for r in reqs:
                     if not r.future.done():
@@ -342,10 +378,12 @@ def make_handler(batcher: Batcher, tokenizer: str = "espeak"):
         def log_message(self, fmt, *args):   # quiet by default (the reference logs through tracing at info)
             pass
 
-        def _send(self, code: int, body: bytes, ctype: str = "text/plain; charset=utf-8"):
+        def _send(self, code: int, body: bytes, ctype: str = "text/plain; charset=utf-8", extra: Optional[dict] = None):
             self.send_response(code)
             self.send_header("content-type", ctype)
             self.send_header("content-length", str(len(body)))
+            for k, v in (extra or {}).items():
+                self.send_header(k, v)
             self.send_header("access-control-allow-origin", "*")   # CorsLayer Any (main.rs:88-94)
             self.end_headers()
             self.wfile.write(body)
@@ -399,10 +437,15 @@ def make_handler(batcher: Batcher, tokenizer: str = "espeak"):
                 except Exception as e:
                     raise HttpError(500, f"phonemize failed: {e}")
                 validate_request(duration, tokens)   # 400 for the offender alone, before it can join a batch
+                trim = parse_trim_query(q)
                 seed = int(q["seed"][0]) if "seed" in q else int.from_bytes(np.random.bytes(7), "little")
-                fut = batcher.submit(Request(wav, sr, tokens, duration, seed))
+                fut = batcher.submit(Request(wav, sr, tokens, duration, seed, trim))
                 audio = fut.result(timeout=120)
-                self._send(200, encode_wav(audio), "audio/wav")
+                if trim is None:
+                    self._send(200, encode_wav(audio), "audio/wav")
+                else:
+                    self._send(200, encode_wav(audio[0]), "audio/wav",
+                               {"x-smtts-start": str(audio[1]), "x-smtts-samples": str(len(audio[0]))})
             except HttpError as e:
                 self._send(e.code, e.msg.encode())
             except Exception as e:   # pragma: no cover

@@ -10,7 +10,10 @@ same batches of 8, same in_flight, same (throughput) tuning.  Both legs are warm
 a, b, a, b ... so that drift of the shared host hits both alike; every repetition ends in a host copy of the audio, so the host
 clock brackets finished device work.  Prints one JSON line: medians, min / max and the run-to-run spread of each leg.
 
-    python tools/longform_bench.py [--reps 15] [--warmup 3] [--in-flight 3] [--weights synthetic:7]
+--trim times another pair instead, the same way: (a) as above against (t) synthesize_long(trim=True), the endpoint kernels behind
+every batch's decode, one small read-back, the join over the speech windows; "trim_over_plain" is the ratio of their medians.
+
+    python tools/longform_bench.py [--reps 15] [--warmup 3] [--in-flight 3] [--weights synthetic:7] [--trim]
 """
 import argparse
 import json
@@ -33,6 +36,7 @@ def main():
     ap.add_argument("--in-flight", type=int, default=3)
     ap.add_argument("--weights", default="synthetic:7")
     ap.add_argument("--precision", default="f16")
+    ap.add_argument("--trim", action="store_true", help="time synthesize_long with and without trim=True instead of legs (a) / (b)")
     args = ap.parse_args()
     import torch
     if not torch.cuda.is_available():
@@ -67,12 +71,17 @@ def main():
                 y[0, offsets[i]:offsets[i] + r.size] = r
         return y
 
+    def leg_t():
+        voice = tts.encode_voice(ref)
+        return tts.synthesize_long(voice, token_lists=toks, durations=durs, seed=3, max_batch=MAX_BATCH, in_flight=args.in_flight, trim=True)
+
+    other = leg_t if args.trim else leg_b
     for _ in range(args.warmup):
-        a, b = leg_a(), leg_b()
-    assert a.shape == b.shape == (1, S) and np.isfinite(a).all() and np.isfinite(b).all()
+        a, b = leg_a(), other()
+    assert a.shape == (1, S) and np.isfinite(a).all() and np.isfinite(b).all() and (b.shape == a.shape or args.trim)
     ta, tb = [], []
     for _ in range(args.reps):
-        for fn, acc in ((leg_a, ta), (leg_b, tb)):
+        for fn, acc in ((leg_a, ta), (other, tb)):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             fn()
@@ -84,6 +93,12 @@ def main():
                 "spread": round(float((t.max() - t.min()) / np.median(t)), 4)}
 
     audio_s = sum(HOP_SIZE * n for n in ns) / 24000.0
+    if args.trim:
+        print(json.dumps({"tool": "longform_bench --trim", "pieces": PIECES, "max_batch": MAX_BATCH, "in_flight": args.in_flight,
+                          "audio_seconds": round(audio_s, 2), "trimmed_seconds": round(b.shape[1] / 24000.0, 2), "reps": args.reps,
+                          "warmup": args.warmup, "precision": args.precision, "synthesize_long": stats(ta),
+                          "synthesize_long_trim": stats(tb), "trim_over_plain": round(float(np.median(tb) / np.median(ta)), 4)}))
+        return
     print(json.dumps({"tool": "longform_bench", "pieces": PIECES, "max_batch": MAX_BATCH, "in_flight": args.in_flight, "ref_frames": REF_FRAMES,
                       "audio_seconds": round(audio_s, 2), "reps": args.reps, "warmup": args.warmup, "precision": args.precision,
                       "synthesize_long": stats(ta), "synthesize_batches_host_join": stats(tb),
