@@ -49,9 +49,9 @@ int smtts_create(int device_id, smtts_handle* out);
 int smtts_destroy(smtts_handle h);
 const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation error */
 const char* smtts_version(void);
-/* bumped on every signature / default change: 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
+/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass; 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
-#define SMTTS_ABI_VERSION 10
+#define SMTTS_ABI_VERSION 11
 int smtts_abi_version(void);
 
 /* ---- weights (replaces the ONNX initialisers; names/shapes = DiTModel.state_dict(),
@@ -123,6 +123,33 @@ int smtts_sample(smtts_handle h, void* stream, int mode, int n_steps, int cfg, f
                  const uint8_t* mask, const float* k_ref, const float* v_ref, const uint8_t* ref_mask,
                  const float* k_text, const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P,
                  const float* noise, uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes);
+
+/* ---- word timings (DESIGN.md 'Word timings') ---------------------------------------------------
+ * smtts_sample with the text-attention tap: for the selected (step, layer) pairs a kernel behind the joint attention re-reads its
+ * operand images and masks, recomputes each valid frame's softmax over ALL valid keys [self | reference | text] in fp32 and adds the
+ * probabilities of the text keys of the selected heads into text_mass f32 (B,N,P), DEVICE, caller-owned (cfg: the B conditional rows).
+ * The first tap stores, later ones add; on return (stream order) text_mass is the MEAN over the selected (step, layer, head) triples:
+ * every frame's row sums to at most 1.  Exactly 0 for frames outside `mask`, for text columns outside ph_mask and for rows without
+ * a valid key.  No atomics, a fixed reduction order: two calls return the same bits, whatever runs on other streams.
+ *   tap_steps: HOST array of n_steps flags, NULL = the last step only (t = 0); tap_layers: bit l = DiT block l (12); tap_heads: bit h
+ *   = head h (8); a selection without a step, layer or head is an error.  Which layers / heads align best on trained weights has not
+ *   been measured: the selection is the caller's.
+ * text_mass == NULL: exactly smtts_sample (no extra launch).  x_out is bit-identical with and without the tap.  If the attention
+ * operand-image path is switched off (smtts_test_set_attention_mfma(h, 0)) a tap request is an error, never a buffer of zeros. */
+int smtts_sample_align(smtts_handle h, void* stream, int mode, int n_steps, int cfg, float s_text, float s_spk,
+                       const uint8_t* mask, const float* k_ref, const float* v_ref, const uint8_t* ref_mask,
+                       const float* k_text, const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P,
+                       const float* noise, uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes,
+                       const uint8_t* tap_steps, uint32_t tap_layers, uint32_t tap_heads, float* text_mass);
+/* monotone alignment of mass f32 (B,N,P), one workgroup per row, on `stream`.  n_len, p0, p1: int32 (B) DEVICE arrays (clamped to the
+ * shape): frames [0, n_len[b]), tokens [p0[b], p1[b]) — p0 skips a prepended transcription.  cost c[n][p] = 1 - mass[b][n][p];
+ * D[n][p] = c[n][p] + min(D[n-1][p-1], D[n-1][p], D[n][p-1]), ties prefer the diagonal, then (n-1,p), then (n,p-1); the path runs from
+ * (0, p0) to (n_len - 1, p1 - 1).  -> spans int32 (B,P,2) = (first, last) frame of every token on the path, (-1,-1) for tokens outside
+ * the range and for empty rows; score f32 (B) = the path cost (0 for empty rows).  One resolution step = one codec frame (hop samples).
+ * Every step is a single fp32 operation in a fixed order: numpy float32 reproduces spans and score bit for bit.  1 <= N <= 225 and
+ * 1 <= P <= 198 (the API's range), anything else is an error. */
+int smtts_align_path(smtts_handle h, void* stream, const float* mass, int B, int N, int P, const int32_t* n_len, const int32_t* p0,
+                     const int32_t* p1, int32_t* spans, float* score);
 
 /* ---- codec ------------------------------------------------------------------------------------ */
 int smtts_codec_hop(smtts_handle h);
@@ -287,6 +314,12 @@ int smtts_test_attention_mfma(smtts_handle h, void* stream, const float* qkvg, c
                               const float* rope, int rot_dim, const float* k_ref, const float* v_ref, int R,
                               const float* k_text, const float* v_text, int P, const uint8_t* mask_self,
                               const uint8_t* mask_ref, const uint8_t* mask_text, int B, int N, int H, int dh, float* out);
+/* the text-attention tap (smtts_sample_align) in isolation, on the images smtts_test_attention_mfma builds from the same inputs:
+ * mass f32 (B,N,P) = the mean over all H heads of each frame's softmax probability on each text key.  P > 0. */
+int smtts_test_attn_text_mass(smtts_handle h, void* stream, const float* qkvg, const float* qw, const float* kw, float eps,
+                              const float* rope, int rot_dim, const float* k_ref, const float* v_ref, int R,
+                              const float* k_text, const float* v_text, int P, const uint8_t* mask_self,
+                              const uint8_t* mask_ref, const uint8_t* mask_text, int B, int N, int H, int dh, float* mass);
 /* engine-wide A/B switch: non-zero (default) = operand images written by the QKVG GEMM epilogue + the DMA / MFMA attention kernel;
  * 0 = fp32 projection + in-place qk_prep + the fp32 VALU reference kernel */
 int smtts_test_set_attention_mfma(smtts_handle h, int mode);

@@ -14,9 +14,10 @@ LIB_PATH = os.environ.get("SMTTS_LIB") or os.path.join(_HERE, "libsmalltts_hip.s
 HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "smalltts_hip.h")
 
 _lib = None
-ABI_VERSION = 10  # include/smalltts_hip.h SMTTS_ABI_VERSION
+ABI_VERSION = 11  # include/smalltts_hip.h SMTTS_ABI_VERSION
 
 vp, i32, i64, u64, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_float, C.c_size_t
+u32 = C.c_uint32
 cstr = C.c_char_p
 
 # name -> (restype, argtypes); kept in sync with include/smalltts_hip.h (tests/test_cabi.py checks it)
@@ -46,6 +47,9 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_sample_workspace_bytes": (sz, [vp, i32, i32, i32, i32, i32, i32]),
     "smtts_sample": (i32, [vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, u64,
                            vp, vp, vp, sz]),
+    "smtts_sample_align": (i32, [vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, u64,
+                                 vp, vp, vp, sz, vp, u32, u32, vp]),
+    "smtts_align_path": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "smtts_codec_hop": (i32, [vp]),
     "smtts_decode_workspace_bytes": (sz, [vp, i32, i32]),
     "smtts_codec_decode": (i32, [vp, vp, vp, i32, i32, vp, vp, sz]),
@@ -77,6 +81,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_test_swiglu": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "smtts_test_set_attention_mfma": (i32, [vp, i32]),
     "smtts_test_attention_mfma": (i32, [vp, vp, vp, vp, vp, f32, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32,
+                                        i32, i32, vp]),
+    "smtts_test_attn_text_mass": (i32, [vp, vp, vp, vp, vp, f32, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32,
                                         i32, i32, vp]),
     "smtts_test_attention": (i32, [vp, vp, vp, vp, vp, f32, vp, i32, vp, vp, i32, vp, vp, i32, vp, vp, vp, i32, i32,
                                    i32, i32, vp]),

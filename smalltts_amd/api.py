@@ -237,6 +237,132 @@ def as_endpointing(trim) -> Optional["Endpointing"]:
     raise TypeError(f"trim must be None, a bool or an Endpointing, got {type(trim).__name__}")
 
 
+class Alignment:
+    """Which text-attention probabilities the word timings are read from (immutable; DESIGN 'Word timings', include/smalltts_hip.h
+    smtts_sample_align).  layers: DiT blocks in [0, 12); heads: attention heads in [0, 8); steps: sampler steps, indices into
+    range(num_steps), negative from the end.  None = the default of each: ALL layers, ALL heads, the LAST step (t = 0, where x_t is
+    the current estimate itself).  The result is the mean over the selected (step, layer, head) triples.
+
+    The default is UNVALIDATED on trained weights: every weight this project has run is seeded noise, and nobody has measured in
+    which layers and heads this model's text attention is monotone and peaky.  The mechanism is verified (the probabilities, the
+    optimal monotone path, the mapping to samples); the selection is a parameter for whoever holds a trained checkpoint.
+    Resolution: one codec frame, 3200 samples = 133 ms — word highlighting and subtitles, not lip-sync."""
+    __slots__ = ("layers", "heads", "steps")
+
+    def __init__(self, layers: Optional[Sequence[int]] = None, heads: Optional[Sequence[int]] = None,
+                 steps: Optional[Sequence[int]] = None) -> None:
+        set_ = object.__setattr__
+        for k, v, n in (("layers", layers, 12), ("heads", heads, 8), ("steps", steps, None)):
+            if v is not None:
+                v = tuple(sorted(set(int(i) for i in v)))
+                if not v:
+                    raise ValueError(f"Alignment: {k} must not be empty (None = the default)")
+                if n is not None and (v[0] < 0 or v[-1] >= n):
+                    raise ValueError(f"Alignment: {k} must lie in [0, {n}), got {v}")
+            set_(self, k, v)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Alignment is immutable")
+
+    __delattr__ = __setattr__
+
+    def __repr__(self) -> str:
+        return "Alignment(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Alignment) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self) -> int:
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
+def as_alignment(align) -> Optional["Alignment"]:
+    """The `align=` argument of the synthesis calls: None / False -> None (off), True -> Alignment(), an Alignment -> itself."""
+    if align is None or align is False:
+        return None
+    if align is True:
+        return Alignment()
+    if isinstance(align, Alignment):
+        return align
+    raise TypeError(f"align must be None, a bool or an Alignment, got {type(align).__name__}")
+
+
+ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS = 225, 198   # the range of smtts_align_path: 30 s of frames, the phoneme window
+
+
+def token_groups(ids: Sequence[int]) -> List[Tuple[str, str, int, int]]:
+    """The units word timings are reported for: runs of token ids between the space symbol.  -> [(kind, phonemes, t0, t1), ...] in
+    order, [t0, t1) the run's token indices, phonemes = decode_token_ids of them.  kind "word": a run of letter / IPA symbols;
+    "punct": ONE punctuation mark (a mark glued to a word is cut off it); "event": a run of up to NV_REPEAT copies of one [event]
+    id (get_token_ids writes exactly NV_REPEAT).  Spaces, padding (0) and unknown ids separate runs and belong to none."""
+    from .phonemes import EVENTS, NV_REPEAT, PUNCTUATION, decode_token_ids, idx2p, p2idx
+    punct = {p2idx[c] for c in PUNCTUATION if c != " "}
+    events = {p2idx[f"[{e}]"] for e in EVENTS}
+    ids = [int(t) for t in ids]
+    out: List[Tuple[str, str, int, int]] = []
+    i, n = 0, len(ids)
+    while i < n:
+        t = ids[i]
+        if t == p2idx[" "] or t not in idx2p:
+            i += 1
+        elif t in punct:
+            out.append(("punct", decode_token_ids(ids[i:i + 1]), i, i + 1))
+            i += 1
+        elif t in events:
+            j = i
+            while j < n and ids[j] == t and j - i < NV_REPEAT:
+                j += 1
+            out.append(("event", decode_token_ids(ids[i:i + 1]), i, j))
+            i = j
+        else:
+            j = i
+            while j < n and ids[j] in idx2p and ids[j] != p2idx[" "] and ids[j] not in punct and ids[j] not in events:
+                j += 1
+            out.append(("word", decode_token_ids(ids[i:j]), i, j))
+            i = j
+    return out
+
+
+def word_times(groups: Sequence[Tuple[str, str, int, int]], spans, n_frames: int, *, token0: int = 0,
+               window: Optional[Tuple[int, int]] = None, offset: int = 0, index0: int = 0, hop: int = HOP_SIZE) -> List[Tuple[int, str, int, int]]:
+    """Token spans of one row -> [(group index, kind, start sample, end sample), ...].  spans[t] = (first, last) frame of token t
+    (smtts_align_path); group g covers tokens [token0 + t0, token0 + t1): start = hop * first(t0), end = hop * (last(t1 - 1) + 1),
+    both clipped to the row's hop * n_frames samples.  window = (start, n), the row's speech window (trim): the span is intersected
+    with it and counted from its start.  offset: where the row (or its window) starts on the caller's timeline; index0: the first
+    group's index.  A group whose tokens are not on the path (an empty row) collapses to (offset, offset)."""
+    total = hop * max(0, int(n_frames))
+    out = []
+    for gi, (kind, _ph, t0, t1) in enumerate(groups):
+        first, last = int(spans[token0 + t0][0]), int(spans[token0 + t1 - 1][1])
+        if first < 0 or last < 0:
+            s = e = 0
+        else:
+            s, e = min(hop * first, total), min(hop * (last + 1), total)
+        if window is not None:
+            ws, wn = int(window[0]), int(window[1])
+            s, e = min(max(s - ws, 0), wn), min(max(e - ws, 0), wn)
+        out.append((index0 + gi, kind, int(offset) + s, int(offset) + e))
+    return out
+
+
+def _srt_time(samples: int) -> str:
+    ms = (int(samples) * 1000 + SAMPLE_RATE // 2) // SAMPLE_RATE
+    return f"{ms // 3600000:02d}:{ms // 60000 % 60:02d}:{ms // 1000 % 60:02d},{ms % 1000:03d}"
+
+
+def format_srt(cues: Sequence[Tuple[int, int, str]]) -> str:
+    """[(start sample, end sample, text), ...] at 24 kHz -> the text of a SubRip file: numbered cues, times rounded to the nearest
+    millisecond, an end never before its start; cues with empty text are dropped."""
+    out, k = [], 0
+    for s, e, text in cues:
+        text = str(text).strip()
+        if not text:
+            continue
+        k += 1
+        out.append(f"{k}\n{_srt_time(s)} --> {_srt_time(max(int(s), int(e)))}\n{text}\n")
+    return "\n".join(out)
+
+
 def piece_seed(seed: int, i: int) -> int:
     """Seed of piece i of a long text: SeedSequence([seed, i]) reduced to 63 bits (like the replica seeds of SmallTTS)."""
     return int(np.random.SeedSequence([int(seed), int(i)]).generate_state(1, np.uint64)[0] >> 1)
@@ -429,7 +555,8 @@ class SmallTTS:
     def synthesize_batch(self, ref_latents: Optional[Sequence[np.ndarray]], phoneme_ids: Sequence[Sequence[int]],
                          durations, *, noise: Optional[np.ndarray] = None, return_latents: bool = False,
                          frames: Optional[Sequence[int]] = None, _defer: bool = False,
-                         voices: Optional[Sequence[Voice]] = None, seeds: Optional[Sequence[int]] = None, trim=None):
+                         voices: Optional[Sequence[Voice]] = None, seeds: Optional[Sequence[int]] = None, trim=None,
+                         align=None, prefix_lens: Optional[Sequence[int]] = None, return_alignment: bool = False):
         """Batched synthesize: per-utterance (R_i,64) refs, token lists and durations -> list of (1, samples).
         `frames` overrides the per-utterance frame counts (default floor(duration * 7.5), infer/onnx.py:84; the HTTP server
         rounds up like the reference's Rust server, pipeline.rs:66).
@@ -437,8 +564,18 @@ class SmallTTS:
         runs, the reference half is gathered from the voices.  `seeds`: B integers; row b's noise is the (seeds[b], step) Philox
         stream, so its latents do not depend on its batch-mates' seeds, lengths or order (not together with `noise`).
         `trim` (True or an Endpointing): row b comes back as (1, n_b), the window of its speech (engine.endpoints), times the
-        row's gain when the Endpointing sets a level; cut and levelled on the device, so only the windows are copied out."""
+        row's gain when the Endpointing sets a level; cut and levelled on the device, so only the windows are copied out.
+        `align` (True = Alignment(), or an Alignment; its default selection is unvalidated on trained weights): the sampler taps the
+        DiT's text attention, the monotone path is found on the device (engine.align_path) and the call additionally returns, as
+        the LAST element, per row [(group index, kind, start sample, end sample), ...] for the row's token_groups, in samples of
+        the returned row (with `trim`: intersected with the speech window and counted from its start); resolution one codec
+        frame (3200 samples).  `prefix_lens`: per row, how many leading tokens are a prepended transcription the audio does not
+        speak; they are left out of the path and of the groups.  Rows of at most 225 frames and 198 tokens.
+        `return_alignment`: one more element behind the words, per row (mass (n_b, P_b) fp32, spans (P_b, 2) int32)."""
         ep = as_endpointing(trim)
+        al = as_alignment(align)
+        if al is None and (prefix_lens is not None or return_alignment):
+            raise ValueError("synthesize_batch: prefix_lens= and return_alignment= belong to align=")
         if ep is not None and _defer:
             raise ValueError("synthesize_batch: trim= and _defer exclude each other (synthesize_long trims its batches itself)")
         if voices is not None:
@@ -473,18 +610,32 @@ class SmallTTS:
         eng = self.engine
         seed = self._next_seed() if seeds is None else 0
         voices = None if voices is None else list(voices)      # run() keeps them alive while the batch is in flight
+        p0s = [0] * B if prefix_lens is None else [int(v) for v in prefix_lens]
+        if al is not None:
+            if Nm > ALIGN_MAX_FRAMES or Pm > ALIGN_MAX_TOKENS:
+                raise ValueError(f"synthesize_batch: align= covers rows of at most {ALIGN_MAX_FRAMES} frames and {ALIGN_MAX_TOKENS} tokens "
+                                 f"(got {Nm} frames, {Pm} tokens)")
+            if len(p0s) != B or any(p < 0 or p > ps[b] for b, p in enumerate(p0s)):
+                raise ValueError("synthesize_batch: prefix_lens needs one length in [0, tokens of the row] per row")
 
         def run():
             cache = eng.cond_encode(ref, np.asarray(rs, np.int64), ids, pm)
             if voices is not None:
                 cache.update(eng.voice_expand(voices))
             nz = noise if seeds is None else eng.randn_rows(seeds, ns, self.num_steps, n_max=Nm)
-            x_ = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed)
-            return eng.codec_decode(x_), x_                    # (B, 1, HOP * Nm); causal => prefixes are exact
+            if al is None:
+                x_ = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed)
+                return eng.codec_decode(x_), x_                # (B, 1, HOP * Nm); causal => prefixes are exact
+            # the tap and the path ride on this batch's stream behind its sampler; a re-run (fp16 range guard) recomputes them
+            x_, mass = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, align=al)
+            spans = eng.align_path(mass, ns, p0s, ps)[0]
+            return eng.codec_decode(x_), (x_, mass, spans)
 
         audio, x = run()
         if _defer:                                             # synthesize_batches: stay on the device / stream
             return audio, x, ns, run
+        if al is not None:
+            return self._batch_aligned(audio, x, run, ns, ps, p0s, phoneme_ids, ep, return_latents, return_alignment)
         if ep is not None:
             seg, gain, _e = eng.endpoints(audio, ns, ep)
             seg_h = seg.cpu().numpy()                          # synchronises: the saturation counters are final
@@ -510,6 +661,46 @@ class SmallTTS:
             xl = x.cpu().numpy()
             return outs, [xl[b, : ns[b]] for b in range(B)]
         return outs
+
+    def _batch_aligned(self, audio, xa, run, ns, ps, p0s, phoneme_ids, ep, return_latents: bool, return_alignment: bool):
+        """synthesize_batch's tail with align=: the same outputs as without, plus the words (and the raw alignment)."""
+        eng = self.engine
+        B = len(ns)
+        x, mass, spans = xa
+        seg_h = None
+        if ep is not None:
+            seg, gain, _e = eng.endpoints(audio, ns, ep)
+            seg_h = seg.cpu().numpy()                          # synchronises: the saturation counters are final
+            if eng.check_fp16_range("synthesize"):
+                audio, (x, mass, spans) = run()
+                seg, gain, _e = eng.endpoints(audio, ns, ep)
+                seg_h = seg.cpu().numpy()
+            offs, S = plan_packed(seg_h[:, 1], 0.0)
+            packed = torch.zeros(S, device=eng.device)
+            eng.stitch_seg(audio, seg, gain if ep.level_dbfs is not None else None, offs, None, packed)
+            packed = packed.cpu().numpy()
+            outs = [packed[None, offs[b]: offs[b] + int(seg_h[b, 1])] for b in range(B)]
+        else:
+            audio_h = audio.cpu().numpy()
+            if eng.check_fp16_range("synthesize"):             # an fp16 operand clipped: the site is split-bf16 now, run again
+                audio, (x, mass, spans) = run()
+                audio_h = audio.cpu().numpy()
+            outs = [audio_h[b, :, : HOP_SIZE * ns[b]] for b in range(B)]
+        spans_h = spans.cpu().numpy()                          # B * P * 2 ints: the only read-back the timings need
+        words = []
+        for b in range(B):
+            groups = token_groups(list(phoneme_ids[b])[p0s[b]:ps[b]])
+            win = None if seg_h is None else (int(seg_h[b, 0]), int(seg_h[b, 1]))
+            words.append(word_times(groups, spans_h[b], ns[b], token0=p0s[b], window=win))
+        res = [outs]
+        if return_latents:
+            xl = x.cpu().numpy()
+            res.append([xl[b, : ns[b]] for b in range(B)])
+        res.append(words)
+        if return_alignment:
+            mh = mass.cpu().numpy()
+            res.append([(mh[b, : ns[b], : ps[b]], spans_h[b, : ps[b]]) for b in range(B)])
+        return tuple(res)
 
     def synthesize_batches(self, batches: Sequence[tuple], in_flight: int = 3, release_workspaces: bool = False) -> List[list]:
         """Several independent batches, `in_flight` of them overlapping on the GPU.
@@ -563,7 +754,8 @@ class SmallTTS:
     def synthesize_long(self, voice: Voice, text: Optional[str] = None, *, token_lists: Optional[Sequence[Sequence[int]]] = None,
                         durations: Optional[Sequence[float]] = None, seed: Optional[int] = None, gap_ms: float = 120.0,
                         fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3, pcm16: bool = False,
-                        prefix_tokens: Optional[Sequence[int]] = None, trim=None, return_segments: bool = False):
+                        prefix_tokens: Optional[Sequence[int]] = None, trim=None, return_segments: bool = False,
+                        return_words: bool = False, align=None):
         """A whole text in one voice -> one waveform (1, S), fp32 or (pcm16=True) int16 PCM, S = sum(3200 * n_i) + (pieces - 1) *
         round(gap_ms * 24).
 
@@ -582,8 +774,18 @@ class SmallTTS:
         back once, and the join puts the speech windows `gap_ms` apart (plan_packed; a piece without speech takes no room), each
         times its gain when the Endpointing sets a level, faded over the window's own ends (engine.stitch_seg); S follows from the
         windows.  `return_segments=True`: -> (waveform, [(offset in the waveform, n, start inside the piece, gain), ...] per piece),
-        the caller's subtitle / highlight timings (without trim: (offset, 3200 * n_i, 0, 1.0))."""
+        the caller's subtitle / highlight timings (without trim: (offset, 3200 * n_i, 0, 1.0)).
+
+        `return_words=True` (with `align`, an Alignment, to choose the tapped layers / heads / steps; the default selection is
+        unvalidated on trained weights): additionally -> [(group index, kind, start sample, end sample), ...], the token_groups of
+        every piece's own tokens (the prefix is left out) in text order, the index running through the whole text, on the joined
+        waveform's timeline: a piece's words lie inside its segment (with trim: inside its speech window).  The tap and the path
+        kernel are enqueued on each batch's own stream behind its sampler; the spans are read back once, 8 bytes per token.
+        Returns (waveform[, segments][, words]).  Resolution: one codec frame, 3200 samples."""
         ep = as_endpointing(trim)
+        al = as_alignment(align if align is not None else (True if return_words else None))
+        if al is not None and not return_words:
+            raise ValueError("synthesize_long: align= belongs to return_words=True")
         if voice.engine is not self.engine:
             raise ValueError("synthesize_long: the Voice belongs to another engine")
         prefix = [int(t) for t in (prefix_tokens or [])]
@@ -605,26 +807,45 @@ class SmallTTS:
         groups, offsets, S = plan_long(ns, max_batch, gap_ms)
         if not toks:
             empty = np.zeros((1, 0), np.int16 if pcm16 else np.float32)
-            return (empty, []) if return_segments else empty
+            res = (empty,) + (([],) if return_segments else ()) + (([],) if return_words else ())
+            return res if len(res) > 1 else empty
         base = self._next_seed() if seed is None else int(seed)
         seeds = [piece_seed(base, i) for i in range(len(toks))]
         calls = [lambda g=g: self.synthesize_batch(None, [toks[i] for i in g], None, frames=[ns[i] for i in g], voices=[voice] * len(g),
-                                                   seeds=[seeds[i] for i in g], _defer=True) for g in groups]
+                                                   seeds=[seeds[i] for i in g], _defer=True,
+                                                   **({} if al is None else {"align": al, "prefix_lens": [len(prefix)] * len(g)}))
+                 for g in groups]
         if ep is not None:
-            return self._long_trimmed(calls, groups, ep, in_flight, gap_ms, fade_ms, pcm16, return_segments)
-        pending = self._run_in_flight(calls, in_flight)
-        out = torch.zeros(S, dtype=torch.int16 if pcm16 else torch.float32, device=eng.device)
-        w = fade_table(fade_ms)
-        fade = torch.from_numpy(w).to(eng.device) if w.size else None
-        for g, (audio, _x, g_ns, _run) in zip(groups, pending):
-            eng.stitch(audio, g_ns, [offsets[i] for i in g], fade, out)
-        out = out.cpu().numpy()[None]
-        return (out, [(offsets[i], HOP_SIZE * ns[i], 0, 1.0) for i in range(len(ns))]) if return_segments else out
+            out, segs, pending = self._long_trimmed(calls, groups, ep, in_flight, gap_ms, fade_ms, pcm16)
+        else:
+            pending = self._run_in_flight(calls, in_flight)
+            out = torch.zeros(S, dtype=torch.int16 if pcm16 else torch.float32, device=eng.device)
+            w = fade_table(fade_ms)
+            fade = torch.from_numpy(w).to(eng.device) if w.size else None
+            for g, (audio, _x, g_ns, _run) in zip(groups, pending):
+                eng.stitch(audio, g_ns, [offsets[i] for i in g], fade, out)
+            out = out.cpu().numpy()[None]
+            segs = [(offsets[i], HOP_SIZE * ns[i], 0, 1.0) for i in range(len(ns))]
+        res = (out,) + ((segs,) if return_segments else ())
+        if al is not None:
+            # one small read-back for the whole text: every batch's (B, P, 2) span table, flattened
+            flat = torch.cat([p[1][2].reshape(-1) for p in pending]).cpu().numpy()
+            words, pos = [], 0
+            for g, p in zip(groups, pending):
+                Pg = int(p[1][2].shape[1])
+                sp = flat[pos: pos + len(g) * Pg * 2].reshape(len(g), Pg, 2)
+                pos += len(g) * Pg * 2
+                for r, i in enumerate(g):
+                    off, n_i, start_i, _gain = segs[i]
+                    words += word_times(token_groups(toks[i][len(prefix):]), sp[r], ns[i], token0=len(prefix),
+                                        window=(start_i, n_i) if ep is not None else None, offset=off, index0=len(words))
+            res += (words,)
+        return res if len(res) > 1 else out
 
-    def _long_trimmed(self, calls, groups, ep: "Endpointing", in_flight: int, gap_ms: float, fade_ms: float, pcm16: bool,
-                      return_segments: bool):
-        """synthesize_long's trimmed join.  Every deferred batch enqueues its endpoints behind its decode, on its own stream, so they
-        overlap the other batches in flight; the fp16 range guard's re-run goes through the same wrapper and so recomputes them."""
+    def _long_trimmed(self, calls, groups, ep: "Endpointing", in_flight: int, gap_ms: float, fade_ms: float, pcm16: bool):
+        """synthesize_long's trimmed join -> (waveform, segments, the finished batches).  Every deferred batch enqueues its endpoints
+        behind its decode, on its own stream, so they overlap the other batches in flight; the fp16 range guard's re-run goes through
+        the same wrapper and so recomputes them."""
         eng = self.engine
 
         def with_endpoints(run, g_ns):            # what _run_in_flight calls again when the range guard fires: (audio', latents)
@@ -652,9 +873,7 @@ class SmallTTS:
         for g, p, sd, gd in zip(groups, pending, seg_d, gain_d):
             eng.stitch_seg(p[0][0], sd, gd if level else None, [offsets[i] for i in g], fade, out)
         out = out.cpu().numpy()[None]
-        if not return_segments:
-            return out
-        return out, [(int(offsets[i]), int(seg_h[i, 1]), int(seg_h[i, 0]), float(gain_h[i])) for i in range(len(offsets))]
+        return out, [(int(offsets[i]), int(seg_h[i, 1]), int(seg_h[i, 0]), float(gain_h[i])) for i in range(len(offsets))], pending
 
     def synthesize_sharded(self, ref_latents: Sequence[np.ndarray], phoneme_ids: Sequence[Sequence[int]],
                            duration_sec: float, *, max_batch: int = 8) -> np.ndarray:

@@ -116,6 +116,22 @@ int smtts_sample(smtts_handle h, void* stream, int mode, int n_steps, int cfg, f
                     B, N, R, P, noise, seed, x_out, steps_out, ws, ws_bytes);
 }
 
+int smtts_sample_align(smtts_handle h, void* stream, int mode, int n_steps, int cfg, float s_text, float s_spk,
+                       const uint8_t* mask, const float* k_ref, const float* v_ref, const uint8_t* ref_mask,
+                       const float* k_text, const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P,
+                       const float* noise, uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes,
+                       const uint8_t* tap_steps, uint32_t tap_layers, uint32_t tap_heads, float* text_mass) { NULLCHK;
+    return E.sample_align(ST(stream), mode, n_steps, cfg, s_text, s_spk, mask, k_ref, v_ref, ref_mask, k_text, v_text, ph_mask,
+                          B, N, R, P, noise, seed, x_out, steps_out, ws, ws_bytes, tap_steps, tap_layers, tap_heads, text_mass);
+}
+int smtts_align_path(smtts_handle h, void* stream, const float* mass, int B, int N, int P, const int32_t* n_len, const int32_t* p0,
+                     const int32_t* p1, int32_t* spans, float* score) { NULLCHK;
+    if (B <= 0 || !mass || !n_len || !p0 || !p1 || !spans || !score) return E.fail("align_path: bad arguments");
+    if (N < 1 || P < 1 || N > 225 || P > 198) return E.fail("align_path: N must be in [1, 225] and P in [1, 198] (the back-pointers of a row live in LDS)");
+    hipError_t e = launch_align_path(mass, B, N, P, n_len, p0, p1, spans, score, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "align_path");
+}
+
 int smtts_codec_hop(smtts_handle h) { NULLCHK0; return E.codec_spec().hop(); }
 size_t smtts_decode_workspace_bytes(smtts_handle h, int B, int T) { NULLCHK0; return E.decode_ws_bytes(B, T); }
 int smtts_codec_decode(smtts_handle h, void* stream, const float* latents, int B, int T, float* audio, void* ws,
@@ -276,10 +292,14 @@ int smtts_test_attention(smtts_handle h, void* stream, const float* qkvg, const 
 #endif
 }
 
-int smtts_test_attention_mfma(smtts_handle h, void* stream, const float* qkvg, const float* qw, const float* kw, float eps,
-                              const float* rope, int rot_dim, const float* k_ref, const float* v_ref, int R,
-                              const float* k_text, const float* v_text, int P, const uint8_t* mask_self,
-                              const uint8_t* mask_ref, const uint8_t* mask_text, int B, int N, int H, int dh, float* out) { NULLCHK;
+}  // extern "C"
+
+// the product's attention path on stand-alone producers: out != null runs the DMA + MFMA kernel, mass != null the text-attention tap
+// (all heads, mean) on the very same images
+static int attn_img_hook(smtts_handle h, void* stream, const float* qkvg, const float* qw, const float* kw, float eps,
+                         const float* rope, int rot_dim, const float* k_ref, const float* v_ref, int R,
+                         const float* k_text, const float* v_text, int P, const uint8_t* mask_self,
+                         const uint8_t* mask_ref, const uint8_t* mask_text, int B, int N, int H, int dh, float* out, float* mass) {
     {
         // round-3 path: stand-alone producer (qkv_pack + cross_pack, L = 1) then the DMA + MFMA kernel, at the SITE_ATTN precision
         const int D = H * dh, dhp = dh <= 64 ? 64 : 128, Np = pad8(N), Rp = pad8(R > 0 ? R : 0), Cp = Rp + pad8(P > 0 ? P : 0);
@@ -316,12 +336,31 @@ int smtts_test_attention_mfma(smtts_handle h, void* stream, const float* qkvg, c
         ai.mask_self = mask_self; ai.mask_ref = mask_ref; ai.mask_text = mask_text;
         ai.out_hi = ob; ai.out_lo = ob + (((size_t)B * N * D + 7) & ~size_t(7)); ai.ors = D;   // split pair: hi + lo ~ fp32
         ai.B = B; ai.N = N; ai.H = H; ai.dh = dh; ai.Np = Np; ai.R = R > 0 ? R : 0; ai.P = P > 0 ? P : 0; ai.Rp = Rp; ai.Cp = Cp;
-        if (e == hipSuccess) e = launch_attention_img(ai, ST(stream));
-        if (e == hipSuccess) e = launch_split_to_f32(ai.out_hi, ai.out_lo, out, (long)B * N * D, ST(stream));
+        if (e == hipSuccess && out) e = launch_attention_img(ai, ST(stream));
+        if (e == hipSuccess && out) e = launch_split_to_f32(ai.out_hi, ai.out_lo, out, (long)B * N * D, ST(stream));
+        if (e == hipSuccess && mass) e = launch_attn_text_mass(ai, mass, B, H >= 32 ? ~0u : (1u << H) - 1u, 1.0f / (float)H, 1, ST(stream));
         (void)hipStreamSynchronize(ST(stream));
         (void)hipFree(img); (void)hipFree(rc); (void)hipFree(rs); (void)hipFree(ob);
-        return e == hipSuccess ? 0 : E.fail_hip(e, "attention_img");
+        return e == hipSuccess ? 0 : E.fail_hip(e, mass ? "attn_text_mass" : "attention_img");
     }
+}
+
+extern "C" {
+
+int smtts_test_attention_mfma(smtts_handle h, void* stream, const float* qkvg, const float* qw, const float* kw, float eps,
+                              const float* rope, int rot_dim, const float* k_ref, const float* v_ref, int R,
+                              const float* k_text, const float* v_text, int P, const uint8_t* mask_self,
+                              const uint8_t* mask_ref, const uint8_t* mask_text, int B, int N, int H, int dh, float* out) { NULLCHK;
+    return attn_img_hook(h, stream, qkvg, qw, kw, eps, rope, rot_dim, k_ref, v_ref, R, k_text, v_text, P, mask_self, mask_ref, mask_text,
+                         B, N, H, dh, out, nullptr);
+}
+int smtts_test_attn_text_mass(smtts_handle h, void* stream, const float* qkvg, const float* qw, const float* kw, float eps,
+                              const float* rope, int rot_dim, const float* k_ref, const float* v_ref, int R,
+                              const float* k_text, const float* v_text, int P, const uint8_t* mask_self,
+                              const uint8_t* mask_ref, const uint8_t* mask_text, int B, int N, int H, int dh, float* mass) { NULLCHK;
+    if (!mass || P <= 0 || !k_text || B <= 0 || N <= 0) return E.fail("test_attn_text_mass: needs text keys and an output (B, N, P > 0)");
+    return attn_img_hook(h, stream, qkvg, qw, kw, eps, rope, rot_dim, k_ref, v_ref, R, k_text, v_text, P, mask_self, mask_ref, mask_text,
+                         B, N, H, dh, nullptr, mass);
 }
 
 }  // extern "C"

@@ -1357,7 +1357,12 @@ int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0,
             ai.out_hi = ob.hi; ai.out_lo = ob.lo; ai.ors = kHidden;
             ai.B = B; ai.N = N; ai.H = kHeads; ai.dh = kDh; ai.Np = Np; ai.R = R; ai.P = P; ai.Rp = ci.Rp; ai.Cp = ci.Cp;
             HIPC(launch_attention_img(ai, st));
+            if (tap_.mass && tap_.step_on && ((tap_.layers >> l) & 1u)) {   // word timings: the text probabilities of this (step, layer)
+                HIPC(launch_attn_text_mass(ai, tap_.mass, tap_.rows, tap_.heads, tap_.scale, tap_.first ? 1 : 0, st));
+                tap_.first = false;
+            }
         } else {
+            if (tap_.mass) return fail("the text-attention tap reads the attention operand images: not available with the image path switched off");
 #ifdef SMTTS_TEST_KERNELS   // the fp32 VALU reference attention (attention.hip): test builds only
             a.prenormed = 1;
             HIPC(launch_qk_prep(a, st));
@@ -1537,15 +1542,35 @@ size_t Engine::sample_ws_bytes(int B, int N, int R, int P, int n_steps, int cfg)
     return b.off + 256 + denoise_core_bytes(cfg ? 3 * B : B, N) + cross_img_bytes(cfg ? 3 * B : B, R, P);
 }
 
-int Engine::sample(hipStream_t st, int mode, int n_steps, int cfg, float s_text, float s_spk, const uint8_t* mask,
-                   const float* k_ref, const float* v_ref, const uint8_t* ref_mask, const float* k_text,
-                   const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P, const float* noise,
-                   uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes) {
+int Engine::sample_align(hipStream_t st, int mode, int n_steps, int cfg, float s_text, float s_spk, const uint8_t* mask,
+                         const float* k_ref, const float* v_ref, const uint8_t* ref_mask, const float* k_text,
+                         const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P, const float* noise,
+                         uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes, const uint8_t* tap_steps,
+                         unsigned tap_layers, unsigned tap_heads, float* text_mass) {
     DeepScope deep_scope(gemm_deep_);
     if (!dit_ready_) return fail("sample: DiT weights not finalized");
     if (n_steps < 1) return fail("sample: n_steps must be >= 1");
     if (N > kMaxPos) return fail("sample: sequence longer than the rope table (4096)");
     if (ws_bytes < sample_ws_bytes(B, N, R, P, n_steps, cfg)) return fail("sample: workspace too small");
+    // the text-attention tap (align.hip): validated before anything is enqueued; off (text_mass == null) nothing below differs from sample()
+    struct TapGuard { Engine* e; ~TapGuard() { e->tap_ = AlignTap(); } } tap_guard{this};
+    std::vector<uint8_t> tap_on(n_steps, 0);
+    if (text_mass) {
+        if (!attn_img_) return fail("sample_align: the text-attention tap reads the attention operand images: not available with the image path switched off");
+        if (B <= 0 || N <= 0 || P <= 0) return fail("sample_align: the tap needs frames and text keys (B, N, P > 0)");
+        tap_layers &= (1u << kBlocks) - 1u;
+        tap_heads &= (1u << kHeads) - 1u;
+        int ns = 0, nl = 0, nh = 0;
+        for (int i = 0; i < n_steps; ++i) ns += (tap_on[i] = tap_steps ? (tap_steps[i] != 0) : (i + 1 == n_steps));
+        for (int l = 0; l < kBlocks; ++l) nl += (tap_layers >> l) & 1u;
+        for (int h = 0; h < kHeads; ++h) nh += (tap_heads >> h) & 1u;
+        if (!ns || !nl || !nh) return fail("sample_align: the tap selects no (step, layer, head): 12 layers (bits 0..11), 8 heads (bits 0..7)");
+        if (sizeof(float) * ((size_t)4 * (128 + pad8(N) + pad8(R > 0 ? R : 0) + pad8(P) + P) + 8) > 64 * 1024)
+            return fail("sample_align: N + R + 2 P too large for the tap kernel's LDS tile");
+        tap_.mass = text_mass; tap_.layers = tap_layers; tap_.heads = tap_heads; tap_.rows = B;
+        tap_.scale = 1.0f / (float)(ns * nl * nh);
+        tap_.first = true; tap_.step_on = false;
+    }
     HIPC(hipSetDevice(device_));
     Bump bump(ws);
     SampleWs s;
@@ -1596,6 +1621,7 @@ int Engine::sample(hipStream_t st, int mode, int n_steps, int cfg, float s_text,
     // mask for 3B rows when cfg: caller passes mask with B rows; replicate by pointer arithmetic is impossible,
     // so the cfg path expects `mask` to already hold 3B rows (documented in the header).
     auto eval_velocity = [&](int step) -> int {
+        tap_.step_on = tap_.mass && tap_on[step];
         if (!cfg)
             return denoise_core(st, s.xt, mask, m.mod, step, 0, k_ref, v_ref, ref_mask, k_text, v_text, ph_mask, nullptr,
                                 B, N, R, P, s.v, core, ci, m.ftab);

@@ -166,7 +166,19 @@ class Engine {
     int sample(hipStream_t st, int mode, int n_steps, int cfg, float s_text, float s_spk, const uint8_t* mask,
                const float* k_ref, const float* v_ref, const uint8_t* ref_mask, const float* k_text,
                const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P, const float* noise,
-               uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes);
+               uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes) {
+        return sample_align(st, mode, n_steps, cfg, s_text, s_spk, mask, k_ref, v_ref, ref_mask, k_text, v_text, ph_mask, B, N, R, P, noise,
+                            seed, x_out, steps_out, ws, ws_bytes, nullptr, 0u, 0u, nullptr);
+    }
+    // sample() plus the text-attention tap (align.hip): text_mass f32 (B, N, P), DEVICE, caller-owned, ends as the mean over the selected
+    // (step, layer, head) triples of each frame's softmax probability on each text key.  tap_steps: HOST array of n_steps flags (null: the
+    // last step only); tap_layers / tap_heads: bit masks (bit l / h).  text_mass == null: the tap is off and this is sample() — not one
+    // launch more, the latents bit for bit the same either way.
+    int sample_align(hipStream_t st, int mode, int n_steps, int cfg, float s_text, float s_spk, const uint8_t* mask,
+                     const float* k_ref, const float* v_ref, const uint8_t* ref_mask, const float* k_text,
+                     const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P, const float* noise,
+                     uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes, const uint8_t* tap_steps,
+                     unsigned tap_layers, unsigned tap_heads, float* text_mass);
 
     size_t decode_ws_bytes(int B, int T) const;
     int codec_decode(hipStream_t st, const float* latents, int B, int T, float* audio, void* ws, size_t ws_bytes);
@@ -263,6 +275,15 @@ class Engine {
         int B = 0, N = 0, R = 0, P = 0;
         bool init_ws = true;           // zero the regions no kernel writes (the sampler's later steps find them as the first one left them)
     };
+    struct AlignTap {   // the text-attention tap of the sampler call in progress (sample_align); mass == null: off
+        float* mass = nullptr;
+        unsigned layers = 0, heads = 0;
+        int rows = 0;          // batch rows tapped (the conditional rows of a CFG batch)
+        float scale = 0.f;     // 1 / selected (step, layer, head) triples
+        bool first = true;     // the next tap stores, later ones add
+        bool step_on = false;  // the step being evaluated is selected
+    };
+    AlignTap tap_;
     int dit_embed(hipStream_t st, const CoreWs& w, const float* x_t, const uint8_t* mask, int B, int N, bool init_ws);
     // blocks [l0, l1): the AdaLN of block l0 runs as the ln_modulate launch (and seeds the fold's row shift); each block ends in the
     // next block's AdaLN image in w.y — after block 11 the final AdaLN (SITE_COND format)

@@ -65,6 +65,16 @@ struct AttnImg {
     int B, N, H, dh, Np, R, P, Rp, Cp;
 };
 hipError_t launch_attention_img(const AttnImg& a, hipStream_t st);
+// ---- word timings (align.hip) ---------------------------------------------------------------------------------------------------
+// The text-attention tap: behind launch_attention_img(a), on the same images and masks.  mass f32 (rows, N, P) (+)= scale * sum over the
+// heads in `heads` (bit h) of softmax(all valid keys)[text key p], for the first `rows` batch rows of a (the conditional rows of a CFG
+// batch); first != 0 stores, else adds.  Exactly 0 for masked frames / text columns / rows without a valid key.  No atomics.
+hipError_t launch_attn_text_mass(const AttnImg& a, float* mass, int rows, unsigned heads, float scale, int first, hipStream_t st);
+// Monotone alignment of mass (B, N, P), one workgroup per row: frames [0, n_len[b]), tokens [p0[b], p1[b]) (DEVICE int32 arrays, clamped
+// to the shape) -> spans int32 (B, P, 2) = (first, last) frame of every token on the path ((-1, -1) outside the range and for empty
+// rows), score f32 (B) = the path cost (0 for empty rows).  N <= 225 and P <= 198 (back-pointers in LDS), else hipErrorInvalidValue.
+hipError_t launch_align_path(const float* mass, int B, int N, int P, const int* n_len, const int* p0, const int* p1, int* spans, float* score,
+                             hipStream_t st);
 // fp32 projection rows [B*N][4*H*dh] = [q | k | v | gate] (bias included) -> the self part of AttnImg (dit.py:95-108; the arithmetic
 // the gemm3 EpiQKV epilogue performs on its accumulators, as a stand-alone kernel: test hook + reference for the epilogue)
 struct QkvPackArgs {

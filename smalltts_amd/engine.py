@@ -24,8 +24,46 @@ SITES = {"dit_block": 0, "encoder": 1, "cross_kv": 2, "cond": 3, "codec_ffn": 4,
 DEFAULT_PRECISION = "f16"
 
 
+ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS = 225, 198   # smtts_align_path: 30 s of codec frames, the phoneme window
+
+
 def _p(t: Optional[torch.Tensor]):
     return None if t is None else C.c_void_p(t.data_ptr())
+
+
+def _index_mask(sel, n: int, what: str) -> int:
+    """None -> all n bits; else the bit mask of the indices in `sel` (each in [0, n))."""
+    if sel is None:
+        return (1 << n) - 1
+    idx = [int(i) for i in sel]
+    if not idx or any(i < 0 or i >= n for i in idx):
+        raise ValueError(f"alignment: {what} must be a non-empty selection of indices in [0, {n}), got {list(sel)}")
+    m = 0
+    for i in idx:
+        m |= 1 << i
+    return m
+
+
+def tap_selection(align, num_steps: int):
+    """The tap selection of smtts_sample_align from an `align=` value: True = every layer and head at the last step; else an object
+    with .layers / .heads / .steps (None = the default of each; steps index range(num_steps), negative from the end).
+    -> (ctypes uint8[num_steps] step flags, layer bit mask, head bit mask).  Host only."""
+    layers = None if align is True else getattr(align, "layers", None)
+    heads = None if align is True else getattr(align, "heads", None)
+    steps = None if align is True else getattr(align, "steps", None)
+    if align is not True and not all(hasattr(align, k) for k in ("layers", "heads", "steps")):
+        raise TypeError(f"align must be None, a bool or an object with layers / heads / steps, got {type(align).__name__}")
+    num_steps = int(num_steps)
+    flags = (C.c_uint8 * num_steps)()
+    if steps is None:
+        flags[num_steps - 1] = 1
+    else:
+        idx = [int(i) for i in steps]
+        if not idx or any(i < -num_steps or i >= num_steps for i in idx):
+            raise ValueError(f"alignment: steps must be a non-empty selection of indices in [-{num_steps}, {num_steps}), got {list(steps)}")
+        for i in idx:
+            flags[i % num_steps] = 1
+    return flags, _index_mask(layers, N_LAYERS, "layers"), _index_mask(heads, N_HEADS, "heads")
 
 
 class HipEngine:
@@ -363,8 +401,12 @@ class HipEngine:
         return v
 
     def sample(self, cache, mask, num_steps: int = 4, mode: str = "dmd", cfg: bool = False, s_text: float = 2.0,
-               s_spk: float = 1.5, noise=None, seed: int = 0, return_steps: bool = False):
-        """Runs the whole sampler on the GPU. mask: (B,N) (cfg: rows are replicated x3 internally)."""
+               s_spk: float = 1.5, noise=None, seed: int = 0, return_steps: bool = False, align=None):
+        """Runs the whole sampler on the GPU. mask: (B,N) (cfg: rows are replicated x3 internally).
+        align (None / False: off; True or an object with .layers / .heads / .steps, e.g. api.Alignment): the text-attention tap of
+        smtts_sample_align runs behind the selected (step, layer) attention launches and the call returns (x, mass) — with
+        return_steps (x, steps, mass) — mass fp32 (B,N,P) on the device: the mean over the selected (step, layer, head) triples of
+        each frame's softmax probability on each text key.  x is bit-identical with and without it."""
         mask = self._dev(mask, torch.bool)
         B, N = mask.shape
         rows = cache["k_ref"].shape[1]
@@ -382,12 +424,43 @@ class HipEngine:
         x = torch.empty(B, N, LATENT, device=self.device)
         steps = torch.empty(num_steps, B, N, LATENT, device=self.device) if return_steps else None
         ws = self._workspace(self.lib.smtts_sample_workspace_bytes(self.h, B, N, R, P, num_steps, int(cfg)))
+        if align is not None and align is not False:
+            flags, layers, heads = tap_selection(align, num_steps)
+            if P < 1:
+                raise ValueError("sample: align= needs text keys (P >= 1)")
+            mass = torch.empty(B, N, P, device=self.device)
+            self._ck(self.lib.smtts_sample_align(self.h, self._stream(), {"dmd": 0, "ode": 1}[mode], num_steps, int(cfg), s_text,
+                                                 s_spk, _p(mask_in), _p(cache["k_ref"]), _p(cache["v_ref"]),
+                                                 _p(cache["ref_mask"]), _p(cache["k_text"]), _p(cache["v_text"]),
+                                                 _p(cache["ph_mask"]), B, N, R, P, _p(noise), C.c_uint64(seed), _p(x), _p(steps),
+                                                 _p(ws), ws.numel(), C.cast(flags, C.c_void_p), layers, heads, _p(mass)), "sample_align")
+            return (x, steps, mass) if return_steps else (x, mass)
         self._ck(self.lib.smtts_sample(self.h, self._stream(), {"dmd": 0, "ode": 1}[mode], num_steps, int(cfg), s_text,
                                        s_spk, _p(mask_in), _p(cache["k_ref"]), _p(cache["v_ref"]),
                                        _p(cache["ref_mask"]), _p(cache["k_text"]), _p(cache["v_text"]),
                                        _p(cache["ph_mask"]), B, N, R, P, _p(noise), C.c_uint64(seed), _p(x), _p(steps),
                                        _p(ws), ws.numel()), "sample")
         return (x, steps) if return_steps else x
+
+    def align_path(self, mass: torch.Tensor, ns, p0, p1):
+        """Monotone alignment of a text-mass buffer on the device (smtts_align_path; the definition: include/smalltts_hip.h).
+        mass fp32 (B,N,P) contiguous on the device, N <= 225, P <= 198; ns frames per row, [p0[b], p1[b]) the tokens the audio
+        speaks (host integers).  -> (spans int32 (B,P,2) = (first, last) frame per token, (-1,-1) outside the path; score fp32 (B)),
+        both on the device.  One launch on the current stream, no synchronisation."""
+        if mass.dim() != 3 or mass.dtype != torch.float32 or not mass.is_contiguous() or mass.device != self.device:
+            raise ValueError("align_path: mass must be a contiguous fp32 (B,N,P) tensor on the engine's device")
+        B, N, P = (int(v) for v in mass.shape)
+        if not (1 <= N <= ALIGN_MAX_FRAMES and 1 <= P <= ALIGN_MAX_TOKENS):
+            raise ValueError(f"align_path: N = {N}, P = {P} outside the supported range N <= {ALIGN_MAX_FRAMES}, P <= {ALIGN_MAX_TOKENS}")
+        if B < 1 or len(ns) != B or len(p0) != B or len(p1) != B:
+            raise ValueError("align_path: one frame count and one token range per row")
+        tab = torch.from_numpy(np.ascontiguousarray([[int(v) for v in ns], [int(v) for v in p0], [int(v) for v in p1]], dtype=np.int32))
+        tab = tab.pin_memory().to(self.device, non_blocking=True)
+        spans = torch.empty(B, P, 2, dtype=torch.int32, device=self.device)
+        score = torch.empty(B, device=self.device)
+        self._ck(self.lib.smtts_align_path(self.h, self._stream(), _p(mass), B, N, P, _p(tab[0]), _p(tab[1]), _p(tab[2]), _p(spans),
+                                           _p(score)), "align_path")
+        return spans, score
 
     @property
     def hop(self) -> int:
@@ -751,3 +824,26 @@ class HipEngine:
         if mfma:
             self.set_precision(self.precision)
         return out
+
+    def test_attn_text_mass(self, qkvg, qw, kw, eps, rope, rot_dim, H, dh, k_ref=None, v_ref=None, k_text=None, v_text=None,
+                            mask_self=None, mask_ref=None, mask_text=None, fmt: str = "bf16x3"):
+        """The text-attention tap in isolation (smtts_test_attn_text_mass): the inputs of test_attention(mfma="img:<fmt>"), the same
+        operand images; -> mass fp32 (B,N,P), the mean over all heads of the softmax probability on each text key."""
+        qkvg = self._dev(qkvg, torch.float32)
+        B, N, _ = qkvg.shape
+        f = lambda x, dt=torch.float32: None if x is None else self._dev(x, dt)
+        qw, kw, rope, k_ref, v_ref, k_text, v_text = map(f, (qw, kw, rope, k_ref, v_ref, k_text, v_text))
+        mask_self, mask_ref, mask_text = (f(m, torch.bool) for m in (mask_self, mask_ref, mask_text))
+        if k_text is None:
+            raise ValueError("test_attn_text_mass: needs text keys")
+        R = 0 if k_ref is None else k_ref.shape[2]
+        P = k_text.shape[2]
+        mass = torch.empty(B, N, P, device=self.device)
+        self._ck(self.lib.smtts_set_site_precision(self.h, SITES["attn"], PRECISION[fmt]), "set_site_precision")
+        try:
+            self._ck(self.lib.smtts_test_attn_text_mass(self.h, self._stream(), _p(qkvg), _p(qw), _p(kw), eps, _p(rope), rot_dim,
+                                                        _p(k_ref), _p(v_ref), R, _p(k_text), _p(v_text), P, _p(mask_self),
+                                                        _p(mask_ref), _p(mask_text), B, N, H, dh, _p(mass)), "test_attn_text_mass")
+        finally:
+            self.set_precision(self.precision)
+        return mass

@@ -1,14 +1,42 @@
 """python -m smalltts_amd.scripts.longform --wav ref.wav --text-file text.txt [--out out/longform.wav] [--trim [--level DBFS]]
 A whole text in one cloned voice: the voice is encoded once, the text is cut into utterance-sized pieces (api.split_text), the
 pieces run as batches in flight and are joined on the device (api.SmallTTS.synthesize_long).
-Without espeak: --tokens-file (one comma-separated token list per line = one piece) with --durations (seconds, one per line)."""
+Without espeak: --tokens-file (one comma-separated token list per line = one piece) with --durations (seconds, one per line).
+--words out.json: when every word / punctuation mark / [event] is spoken (from the DiT's text attention: api.Alignment, default
+selection unvalidated on trained weights; resolution one codec frame = 133 ms).  --srt out.srt: one subtitle cue per piece, and
+next to it out.words.srt with one cue per word group."""
 import argparse
+import json
 from pathlib import Path
 
-from ..api import Endpointing, SmallTTS, estimate_duration, split_text
+from ..api import SAMPLE_RATE, Endpointing, SmallTTS, estimate_duration, format_srt, split_text, token_groups
 from ..audio import read_wav, write_wav_pcm16
-from ..phonemes import get_token_ids, parse_tokens_arg
+from ..phonemes import decode_token_ids, get_token_ids, parse_tokens_arg
 from ._common import add_engine_args
+
+
+def group_texts(token_lists) -> list:
+    """(piece index, kind, phonemes) of every token group of every piece, in text order: what word i of synthesize_long is."""
+    return [(i, kind, ph) for i, toks in enumerate(token_lists) for kind, ph, _t0, _t1 in token_groups(toks)]
+
+
+def words_json(words, texts) -> str:
+    """synthesize_long's words + group_texts -> the --words file: a JSON list of {index, piece, kind, phonemes, start, end (samples),
+    start_s, end_s (seconds)}."""
+    if len(words) != len(texts):
+        raise ValueError(f"{len(words)} timed groups for {len(texts)} groups of the text")
+    return json.dumps([{"index": int(gi), "piece": int(pi), "kind": kind, "phonemes": ph, "start": int(s), "end": int(e),
+                        "start_s": round(int(s) / SAMPLE_RATE, 4), "end_s": round(int(e) / SAMPLE_RATE, 4)}
+                       for (gi, kind, s, e), (pi, _k, ph) in zip(words, texts)], ensure_ascii=False, indent=1)
+
+
+def piece_cues(segments, piece_texts) -> list:
+    """return_segments + one text per piece -> SubRip cues (start, end, text); a piece without speech gives none."""
+    return [(off, off + n, txt) for (off, n, _start, _gain), txt in zip(segments, piece_texts) if n > 0]
+
+
+def word_cues(words, texts) -> list:
+    return [(s, e, ph) for (_gi, _kind, s, e), (_pi, _k, ph) in zip(words, texts)]
 
 
 def main(argv=None):
@@ -22,6 +50,8 @@ def main(argv=None):
     ap.add_argument("--fade-ms", type=float, default=5.0, help="raised-cosine fade at both ends of every piece")
     ap.add_argument("--trim", action="store_true", help="join the pieces at the ends of their speech, not of their guessed durations")
     ap.add_argument("--level", type=float, default=None, metavar="DBFS", help="with --trim: bring every piece's speech to this RMS level")
+    ap.add_argument("--words", default=None, metavar="OUT.json", help="write the time of every word / punctuation mark / [event] (133 ms resolution)")
+    ap.add_argument("--srt", default=None, metavar="OUT.srt", help="write one subtitle cue per piece, and OUT.words.srt with one cue per word group")
     ap.add_argument("--max-batch", type=int, default=8)
     ap.add_argument("--in-flight", type=int, default=3)
     add_engine_args(ap)
@@ -42,6 +72,9 @@ def main(argv=None):
     voice = tts.encode_voice_wav(y, sr)
     kw = dict(seed=args.seed, gap_ms=args.gap_ms, fade_ms=args.fade_ms, max_batch=args.max_batch, in_flight=args.in_flight,
               trim=Endpointing(level_dbfs=args.level) if args.trim else None)
+    timed = bool(args.words or args.srt)
+    if timed:
+        kw.update(return_segments=True, return_words=True)
     if args.tokens_file:
         with open(args.tokens_file) as f:
             token_lists = [parse_tokens_arg(line) for line in f if line.strip()]
@@ -49,6 +82,7 @@ def main(argv=None):
         if len(durs) == 1:
             durs = durs * len(token_lists)
         print(f"generating {len(token_lists)} pieces")
+        piece_texts = [decode_token_ids(t) for t in token_lists]
         audio = tts.synthesize_long(voice, token_lists=token_lists, durations=durs, **kw)
     else:
         with open(args.text_file) as f:
@@ -56,7 +90,21 @@ def main(argv=None):
         tok = lambda t: get_token_ids(t, backend=args.tokenizer)
         pieces = split_text(text, count_tokens=lambda t: len(tok(t)))
         print(f"generating {len(pieces)} pieces")
-        audio = tts.synthesize_long(voice, token_lists=[tok(p) for p in pieces], durations=[estimate_duration(p) for p in pieces], **kw)
+        token_lists, piece_texts = [tok(p) for p in pieces], pieces
+        audio = tts.synthesize_long(voice, token_lists=token_lists, durations=[estimate_duration(p) for p in pieces], **kw)
+    if timed:
+        audio, segments, words = audio
+        texts = group_texts(token_lists)
+        if args.words:
+            Path(args.words).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.words).write_text(words_json(words, texts), encoding="utf-8")
+            print(f"{args.words} ({len(words)} word groups)")
+        if args.srt:
+            Path(args.srt).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.srt).write_text(format_srt(piece_cues(segments, piece_texts)), encoding="utf-8")
+            wpath = str(Path(args.srt).with_suffix("")) + ".words.srt"
+            Path(wpath).write_text(format_srt(word_cues(words, texts)), encoding="utf-8")
+            print(f"{args.srt}, {wpath}")
     write_wav_pcm16(args.out, audio.squeeze(0), 24_000)
     print(f"{args.out} ({audio.shape[1] / 24_000:.1f}s)")
 

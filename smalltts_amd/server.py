@@ -19,6 +19,10 @@ optional `seed` query parameter (per-request noise stream, so a result does not 
 an optional `trim=1` query parameter (and, only with it, `level=<dBFS>`): the answer is the speech window the endpoint kernels find
 (api.Endpointing defaults), levelled when asked, with its place in the untrimmed utterance in the headers `x-smtts-start` /
 `x-smtts-samples`.  Without the parameter (or with trim=0) the answer is byte for byte what it was.
+An optional `align=1` query parameter (requests of at most 225 frames = 30 s and 198 tokens): the answer carries the header
+`x-smtts-words`, a JSON list of `[start sample, end sample]` per token group of the text (api.token_groups: words, punctuation marks,
+[event] runs, in order) in samples of the returned audio, from the DiT's text attention (api.Alignment defaults, unvalidated on trained
+weights; resolution one codec frame = 3200 samples).  A list over 6 KB is answered with 400.  Without the parameter nothing changes.
 
     python -m smalltts_amd.server --port 3000 --weights assets/smalltts.smtts
 """
@@ -175,11 +179,39 @@ def parse_trim_query(q: dict):
     return Endpointing(level_dbfs=level)
 
 
-class Request:
-    __slots__ = ("wav", "sr", "tokens", "duration", "seed", "trim", "future", "t_in")
+WORDS_HEADER_LIMIT = 6 * 1024   # bytes of the x-smtts-words header value (common proxies cap a header line at 8 KB)
+ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS = 225, 198
 
-    def __init__(self, wav, sr, tokens, duration, seed, trim=None):
+
+def parse_align_query(q: dict, duration: Optional[float] = None, tokens=None) -> bool:
+    """The optional `align` query parameter -> False (off: the answer is today's) or True.  1 / true or 0 / false; with align=1 the
+    request must fit the alignment kernel's range (225 frames, 198 tokens).  Anything else is a 400 for the offender alone."""
+    raw = q.get("align", ["0"])[0].strip().lower()
+    if raw not in ("0", "1", "true", "false"):
+        raise HttpError(400, "invalid `align`: 0 or 1")
+    on = raw in ("1", "true")
+    if on and duration is not None and frames_for(duration) > ALIGN_MAX_FRAMES:
+        raise HttpError(400, f"invalid `align`: word timings cover at most {ALIGN_MAX_FRAMES * HOP / SAMPLE_RATE:.0f} s ({ALIGN_MAX_FRAMES} frames)")
+    if on and tokens is not None and len(tokens) > ALIGN_MAX_TOKENS:
+        raise HttpError(400, f"invalid `align`: word timings cover at most {ALIGN_MAX_TOKENS} tokens, got {len(tokens)}")
+    return on
+
+
+def words_header(words) -> str:
+    """[(group index, kind, start, end), ...] -> the x-smtts-words value: a compact JSON list of [start, end] per group, in order.
+    Over WORDS_HEADER_LIMIT bytes: HttpError(400), the caller should split the text."""
+    v = json.dumps([[int(w[2]), int(w[3])] for w in words], separators=(",", ":"))
+    if len(v) > WORDS_HEADER_LIMIT:
+        raise HttpError(400, f"word timings need {len(v)} header bytes, over the {WORDS_HEADER_LIMIT} byte limit: split the text")
+    return v
+
+
+class Request:
+    __slots__ = ("wav", "sr", "tokens", "duration", "seed", "trim", "align", "future", "t_in")
+
+    def __init__(self, wav, sr, tokens, duration, seed, trim=None, align=False):
         self.wav, self.sr, self.tokens, self.duration, self.seed, self.trim = wav, sr, tokens, duration, seed, trim
+        self.align = bool(align)
         self.future: Future = Future()
         self.t_in = time.perf_counter()
 
@@ -274,6 +306,8 @@ class Batcher:
                 for r in reqs:
                     try:
                         n = validate_request(r.duration, r.tokens)   # (the handler checked already; a direct submit() may not have)
+                        if r.align:
+                            parse_align_query({"align": ["1"]}, r.duration, r.tokens)
                         refs.append(self._ref_latents(r))
                         ns.append(n)
                         ok.append(r)
@@ -285,8 +319,16 @@ class Batcher:
                     continue
                 # padded-work budgets, not a request count: one long request neither blows the workspace up for 23 batch-mates
                 # nor makes short requests wait for it (plan_batches); the groups go out back to back, each its own batch in flight
-                for grp in plan_batches(ns, [len(r.tokens) for r in ok], [int(x.shape[0]) for x in refs], self.max_pack):
+                # requests that ask for word timings ride in batches of their own: the tap covers padded shapes up to 225 x 198, which
+                # each of them fits, and the others' batches run exactly as without the feature
+                plan = []
+                for sel in ([j for j, r in enumerate(ok) if not r.align], [j for j, r in enumerate(ok) if r.align]):
+                    if sel:
+                        plan += [[sel[k] for k in g] for g in plan_batches([ns[j] for j in sel], [len(ok[j].tokens) for j in sel],
+                                                                            [int(refs[j].shape[0]) for j in sel], self.max_pack)]
+                for grp in plan:
                     g_ok, g_refs, g_ns = [ok[j] for j in grp], [refs[j] for j in grp], [ns[j] for j in grp]
+                    g_align = g_ok[0].align
                     self._slots.acquire()                       # at most in_flight batches on the GPU
                     slot = i % self.in_flight
                     i += 1
@@ -298,8 +340,10 @@ class Batcher:
                             for b, r in enumerate(g_ok):
                                 for s_ in range(self.steps):
                                     noise[s_, b, :g_ns[b]] = self.eng.randn(g_ns[b] * LATENT, r.seed, s_).view(g_ns[b], LATENT)
-                            audio, _, _, _ = self.tts.synthesize_batch(g_refs, [r.tokens for r in g_ok], [r.duration for r in g_ok],
-                                                                       noise=noise, frames=g_ns, _defer=True)
+                            audio, xa, _, _ = self.tts.synthesize_batch(g_refs, [r.tokens for r in g_ok], [r.duration for r in g_ok],
+                                                                        noise=noise, frames=g_ns, _defer=True,
+                                                                        **({"align": True} if g_align else {}))
+                            spans = xa[2] if g_align else None    # (B, P, 2) token spans, found on this stream behind the sampler
                             # endpoints behind the decode, on the batch's stream: one pair of launches per distinct setting
                             ends = {ep: self.eng.endpoints(audio, g_ns, ep)[:2] for ep in {r.trim for r in g_ok if r.trim is not None}}
                             ev = torch.cuda.Event()
@@ -309,7 +353,7 @@ class Batcher:
                         self.stats["batches"] += 1
                         self.stats["max_batch_seen"] = max(self.stats["max_batch_seen"], len(g_ok))
                         self.stats["max_padded_frames"] = max(self.stats.get("max_padded_frames", 0), len(g_ok) * max(g_ns))
-                        self.done_q.put((ev, audio, g_ns, g_ok, ends))
+                        self.done_q.put((ev, audio, g_ns, g_ok, ends, spans))
                     except Exception as e:
                         self.eng.use_workspace(None)
                         self._slots.release()
@@ -343,21 +387,28 @@ class Batcher:
             item = self.done_q.get()
             if item is None:
                 break
-            ev, audio, ns, reqs, ends = item
+            ev, audio, ns, reqs, ends, spans = item
             try:
                 ev.synchronize()
                 host = audio.cpu().numpy()
                 ends = {ep: (seg.cpu().numpy(), gain.cpu().numpy()) for ep, (seg, gain) in ends.items()}
+                spans = None if spans is None else spans.cpu().numpy()
+
+                def words_of(b, r, window):   # an aligned request answers (what it would have answered, words)
+                    from .api import token_groups, word_times
+                    return word_times(token_groups(r.tokens), spans[b], ns[b], window=window)
+
                 for b, r in enumerate(reqs):
                     if r.trim is None:
-                        r.future.set_result(host[b, 0, : HOP * ns[b]].copy())
+                        y = host[b, 0, : HOP * ns[b]].copy()
+                        r.future.set_result((y, words_of(b, r, None)) if r.align else y)
                         continue
                     seg, gain = ends[r.trim]       # a trimmed request answers (samples, start): the window, times its gain if levelled
                     start, n = int(seg[b, 0]), int(seg[b, 1])
                     y = host[b, 0, start:start + n].copy()
                     if r.trim.level_dbfs is not None:
                         y = y * np.float32(gain[b])
-                    r.future.set_result((y, start))
+                    r.future.set_result(((y, start), words_of(b, r, (start, n))) if r.align else (y, start))
             except Exception as e:
                 for r in reqs:
                     if not r.future.done():
@@ -438,14 +489,19 @@ def make_handler(batcher: Batcher, tokenizer: str = "espeak"):
                     raise HttpError(500, f"phonemize failed: {e}")
                 validate_request(duration, tokens)   # 400 for the offender alone, before it can join a batch
                 trim = parse_trim_query(q)
+                align = parse_align_query(q, duration, tokens)
                 seed = int(q["seed"][0]) if "seed" in q else int.from_bytes(np.random.bytes(7), "little")
-                fut = batcher.submit(Request(wav, sr, tokens, duration, seed, trim))
+                fut = batcher.submit(Request(wav, sr, tokens, duration, seed, trim, align))
                 audio = fut.result(timeout=120)
+                extra = {}
+                if align:
+                    audio, words = audio
+                    extra["x-smtts-words"] = words_header(words)
                 if trim is None:
-                    self._send(200, encode_wav(audio), "audio/wav")
+                    self._send(200, encode_wav(audio), "audio/wav", extra or None)
                 else:
                     self._send(200, encode_wav(audio[0]), "audio/wav",
-                               {"x-smtts-start": str(audio[1]), "x-smtts-samples": str(len(audio[0]))})
+                               {"x-smtts-start": str(audio[1]), "x-smtts-samples": str(len(audio[0])), **extra})
             except HttpError as e:
                 self._send(e.code, e.msg.encode())
             except Exception as e:   # pragma: no cover
