@@ -49,7 +49,7 @@ int smtts_create(int device_id, smtts_handle* out);
 int smtts_destroy(smtts_handle h);
 const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation error */
 const char* smtts_version(void);
-/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass; 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
+/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
 #define SMTTS_ABI_VERSION 11
 int smtts_abi_version(void);
@@ -141,7 +141,36 @@ int smtts_sample_align(smtts_handle h, void* stream, int mode, int n_steps, int 
                        const float* k_text, const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P,
                        const float* noise, uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes,
                        const uint8_t* tap_steps, uint32_t tap_layers, uint32_t tap_heads, float* text_mass);
-/* monotone alignment of mass f32 (B,N,P), one workgroup per row, on `stream`.  n_len, p0, p1: int32 (B) DEVICE arrays (clamped to the
+/* ---- pinned sampling (DESIGN.md 'Re-speaking part of an utterance') ----------------------------------
+ * smtts_sample_align that keeps pinned frames: the DMD sampler re-noises its current estimate at every step, so a frame whose
+ * estimate is overwritten with a known latent after every step stays exactly that latent, and every other frame is denoised with
+ * the known frames in view, at the right noise level, through the joint self-attention (RePaint-style conditioning for an x0
+ * sampler; no training).  x_pin f32 (B,N,64) and pin bool (B,N), both DEVICE.  With K[b][n] = pin[b][n] && mask[b][n] (pin == NULL:
+ * all false):
+ *     x = (start_step == 0) ? (K ? x_pin : 0) : x_pin
+ *     for i in start_step .. n_steps-1:
+ *         x_t = al[i] * x + sg[i] * eps_i        eps_i: noise[i], or Philox(seed, stream i): always stream i, whatever start_step is
+ *         v   = denoise(x_t, t_i)                unchanged
+ *         x   = K ? x_pin : (al[i] * x_t - sg[i] * v)
+ *         steps_out[i] = x                       slots below start_step are not written
+ *     x_out = x
+ * Mode 0 (DMD) and cfg == 0 only; 0 <= start_step < n_steps; start_step > 0 needs x_pin; pin != NULL needs x_pin; x_pin, noise and
+ * the workspace 16-byte aligned; anything else returns 1 with a message before anything is enqueued.  Workspace:
+ * smtts_sample_workspace_bytes.  The tap arguments work as in smtts_sample_align; a flagged step below start_step is not run and does
+ * not count in the tap's mean, and a selection with no step left is an error.  The select rides in the two element-wise kernels of a
+ * step (16-byte lanes, sixteen of them share a frame's pin byte): not one launch more than smtts_sample.  With x_pin given, pin all
+ * false and start_step == 0, x_out and steps_out equal smtts_sample's bit for bit; with x_pin == NULL, pin == NULL and start_step
+ * == 0 this IS smtts_sample_align, the same kernels.
+ * Only this mechanism is verified.  It is UNVALIDATED on trained weights: every weight this project has run is seeded noise, and
+ * nobody has measured how well a 4-step distilled student inpaints: whether the regenerated frames join the kept ones audibly well
+ * is for whoever holds a trained checkpoint to measure. */
+int smtts_sample_pinned(smtts_handle h, void* stream, int mode, int n_steps, int cfg, float s_text, float s_spk,
+                        const uint8_t* mask, const float* k_ref, const float* v_ref, const uint8_t* ref_mask,
+                        const float* k_text, const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P,
+                        const float* noise, uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes,
+                        const uint8_t* tap_steps, uint32_t tap_layers, uint32_t tap_heads, float* text_mass, const float* x_pin,
+                        const uint8_t* pin, int start_step);
+/* monotone alignment of mass f32 (B,N,P), one workgroup per row, on `stream`. n_len, p0, p1: int32 (B) DEVICE arrays (clamped to the
  * shape): frames [0, n_len[b]), tokens [p0[b], p1[b]) — p0 skips a prepended transcription.  cost c[n][p] = 1 - mass[b][n][p];
  * D[n][p] = c[n][p] + min(D[n-1][p-1], D[n-1][p], D[n][p-1]), ties prefer the diagonal, then (n-1,p), then (n,p-1); the path runs from
  * (0, p0) to (n_len - 1, p1 - 1).  -> spans int32 (B,P,2) = (first, last) frame of every token on the path, (-1,-1) for tokens outside

@@ -363,6 +363,154 @@ def format_srt(cues: Sequence[Tuple[int, int, str]]) -> str:
     return "\n".join(out)
 
 
+def frames_of_groups(groups: Sequence[Tuple[str, str, int, int]], spans, g0: int, g1: int, token0: int = 0) -> Tuple[int, int]:
+    """The frames token groups [g0, g1) of one row touch, by word_times' mapping: (first frame of the first token, last frame of the
+    last token + 1).  groups: token_groups of the row's own tokens; spans[t] = (first, last) frame of token t (smtts_align_path);
+    token0: the prepended tokens in front of them.  A group off the path (an empty row) raises ValueError."""
+    g0, g1 = int(g0), int(g1)
+    if not 0 <= g0 < g1 <= len(groups):
+        raise ValueError(f"frames_of_groups: groups [{g0}, {g1}) outside [0, {len(groups)}) or empty")
+    t0, t1 = int(groups[g0][2]), int(groups[g1 - 1][3])
+    if token0 + t0 < 0 or token0 + t1 > len(spans):
+        raise ValueError(f"frames_of_groups: tokens [{token0 + t0}, {token0 + t1}) outside the span table of {len(spans)} tokens")
+    first, last = int(spans[token0 + t0][0]), int(spans[token0 + t1 - 1][1])
+    if first < 0 or last < first:
+        raise ValueError(f"frames_of_groups: groups [{g0}, {g1}) are not on the alignment path")
+    return first, last + 1
+
+
+def splice_pins(latents, f0: int, f1: int, m: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
+    """The pins of a re-spoken row: frames [f0, f1) of `latents` (n, 64) are replaced by m free frames (default f1 - f0, at least
+    1).  -> (x_pin (n', 64) fp32, keep (n',) bool), n' = n - (f1 - f0) + m: the head [0, f0) and the tail [f1, n) are copied and
+    kept (the tail at its shifted place), the m rows between them are zeros and free."""
+    lat = np.asarray(latents, np.float32)
+    if lat.ndim != 2 or lat.shape[1] != 64:
+        raise ValueError(f"splice_pins: latents must be (n, 64), got {lat.shape}")
+    n, f0, f1 = int(lat.shape[0]), int(f0), int(f1)
+    if not 0 <= f0 < f1 <= n:
+        raise ValueError(f"splice_pins: frames [{f0}, {f1}) must be a non-empty range inside [0, {n})")
+    m = f1 - f0 if m is None else int(m)
+    if m < 1:
+        raise ValueError("splice_pins: at least one frame is regenerated (m >= 1)")
+    x_pin = np.zeros((n - (f1 - f0) + m, 64), np.float32)
+    keep = np.ones((x_pin.shape[0],), bool)
+    x_pin[:f0] = lat[:f0]
+    x_pin[f0 + m:] = lat[f1:]
+    keep[f0:f0 + m] = False
+    return x_pin, keep
+
+
+def _check_pins(pins, ns: Sequence[int], start_step: int, num_steps: int):
+    """synthesize_batch's pins= / start_step= -> [None | (latents (n_b, 64) fp32, keep (n_b,) bool)] per row, or None (off)."""
+    start_step = int(start_step)
+    if pins is None and start_step == 0:
+        return None
+    if not 0 <= start_step < int(num_steps):
+        raise ValueError(f"synthesize_batch: start_step must lie in [0, {int(num_steps)}), got {start_step}")
+    if pins is None or len(pins) != len(ns):
+        raise ValueError(f"synthesize_batch: pins needs one entry per row ({len(ns)}): None or (latents, keep)"
+                         + (" — start_step > 0 starts from them" if pins is None else ""))
+    out = []
+    for b, pe in enumerate(pins):
+        if pe is None:
+            if start_step > 0:
+                raise ValueError(f"synthesize_batch: start_step > 0 needs latents in every row (row {b} has none)")
+            out.append(None)
+            continue
+        if not isinstance(pe, (tuple, list)) or len(pe) != 2:
+            raise ValueError(f"synthesize_batch: pins[{b}] must be None or (latents, keep)")
+        lat, keep = np.asarray(pe[0]), np.asarray(pe[1])
+        if lat.shape != (ns[b], 64) or lat.dtype != np.float32:
+            raise ValueError(f"synthesize_batch: pins[{b}] latents must be fp32 ({ns[b]}, 64), got {lat.dtype} {lat.shape}")
+        if keep.shape != (ns[b],) or keep.dtype != np.bool_:
+            raise ValueError(f"synthesize_batch: pins[{b}] keep must be bool ({ns[b]},), got {keep.dtype} {keep.shape}")
+        out.append((lat, keep))
+    return out
+
+
+class Piece:
+    """One piece of a long take, as synthesize_long(return_pieces=True) spoke it: `tokens` (the prefix included), `prefix_len` (how
+    many of them are the prepended transcription), `latents` (n, 64) fp32 on the host, and the `seed` of its noise; `spans`
+    (len(tokens), 2) int32, the (first, last) frame of every token, when the take was aligned (return_words), else None.  Immutable;
+    render_long joins pieces again, respeak makes the latents of a replacement."""
+    __slots__ = ("tokens", "prefix_len", "latents", "seed", "spans")
+
+    def __init__(self, tokens: Sequence[int], prefix_len: int, latents, seed: int, spans=None) -> None:
+        lat = np.array(latents, np.float32)
+        if lat.ndim != 2 or lat.shape[1] != 64 or lat.shape[0] < 1:
+            raise ValueError(f"Piece: latents must be (n, 64) with n >= 1, got {lat.shape}")
+        if not 0 <= int(prefix_len) <= len(tokens):
+            raise ValueError("Piece: prefix_len must lie in [0, len(tokens)]")
+        lat.setflags(write=False)
+        set_ = object.__setattr__
+        set_(self, "tokens", tuple(int(t) for t in tokens))
+        set_(self, "prefix_len", int(prefix_len))
+        set_(self, "latents", lat)
+        set_(self, "seed", int(seed))
+        if spans is not None:
+            spans = np.array(spans, np.int32)
+            if spans.shape != (len(self.tokens), 2):
+                raise ValueError(f"Piece: spans must be ({len(self.tokens)}, 2), one (first, last) frame per token, got {spans.shape}")
+            spans.setflags(write=False)
+        set_(self, "spans", spans)
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Piece is immutable")
+
+    __delattr__ = __setattr__
+
+    def __repr__(self) -> str:
+        return f"Piece(tokens={len(self.tokens)}, prefix_len={self.prefix_len}, frames={self.latents.shape[0]}, seed={self.seed})"
+
+
+TAKE_JOIN_KEYS = ("gap_ms", "fade_ms", "max_batch", "in_flight", "trim", "level_dbfs")
+
+
+def save_take(path, pieces: Sequence["Piece"], **join) -> None:
+    """A long take -> one .npz: every Piece (tokens, prefix_len, latents, seed, spans when it has them) and the join parameters
+    (TAKE_JOIN_KEYS: gap_ms, fade_ms, max_batch, in_flight, trim as a bool, level_dbfs or None), enough for render_long to give the
+    waveform again.  Plain arrays only (no pickle)."""
+    unknown = sorted(set(join) - set(TAKE_JOIN_KEYS))
+    if unknown:
+        raise ValueError(f"save_take: unknown join parameters {unknown}")
+    level = join.get("level_dbfs")
+    arrs = {"n_pieces": np.int64(len(pieces)), "prefix_len": np.asarray([p.prefix_len for p in pieces], np.int64),
+            "seed": np.asarray([p.seed for p in pieces], np.uint64), "gap_ms": np.float64(join.get("gap_ms", 120.0)),
+            "fade_ms": np.float64(join.get("fade_ms", 5.0)), "max_batch": np.int64(join.get("max_batch", 8)),
+            "in_flight": np.int64(join.get("in_flight", 3)), "trim": np.bool_(join.get("trim", False)),
+            "level_dbfs": np.float64(np.nan if level is None else level)}
+    for i, p in enumerate(pieces):
+        arrs[f"tokens_{i}"] = np.asarray(p.tokens, np.int64)
+        arrs[f"latents_{i}"] = np.asarray(p.latents, np.float32)
+        if p.spans is not None:
+            arrs[f"spans_{i}"] = np.asarray(p.spans, np.int32)
+    with open(path, "wb") as f:
+        np.savez(f, **arrs)
+
+
+def load_take(path) -> Tuple[List["Piece"], Dict[str, object]]:
+    """save_take's file -> (pieces, join parameters as keyword arguments of save_take)."""
+    with np.load(path, allow_pickle=False) as z:
+        n = int(z["n_pieces"])
+        pieces = [Piece(z[f"tokens_{i}"].tolist(), int(z["prefix_len"][i]), z[f"latents_{i}"], int(z["seed"][i]),
+                        z[f"spans_{i}"] if f"spans_{i}" in z.files else None) for i in range(n)]
+        level = float(z["level_dbfs"])
+        join = {"gap_ms": float(z["gap_ms"]), "fade_ms": float(z["fade_ms"]), "max_batch": int(z["max_batch"]),
+                "in_flight": int(z["in_flight"]), "trim": bool(z["trim"]), "level_dbfs": None if np.isnan(level) else level}
+    return pieces, join
+
+
+def _piece_latents(pieces) -> List[np.ndarray]:
+    """render_long's input: Pieces or (n_i, 64) arrays -> fp32 arrays."""
+    out = []
+    for i, p in enumerate(pieces):
+        lat = np.asarray(p.latents if isinstance(p, Piece) else p, np.float32)
+        if lat.ndim != 2 or lat.shape[1] != 64 or lat.shape[0] < 1:
+            raise ValueError(f"render_long: piece {i} must hold (n, 64) latents with n >= 1, got {lat.shape}")
+        out.append(lat)
+    return out
+
+
 def piece_seed(seed: int, i: int) -> int:
     """Seed of piece i of a long text: SeedSequence([seed, i]) reduced to 63 bits (like the replica seeds of SmallTTS)."""
     return int(np.random.SeedSequence([int(seed), int(i)]).generate_state(1, np.uint64)[0] >> 1)
@@ -556,7 +704,8 @@ class SmallTTS:
                          durations, *, noise: Optional[np.ndarray] = None, return_latents: bool = False,
                          frames: Optional[Sequence[int]] = None, _defer: bool = False,
                          voices: Optional[Sequence[Voice]] = None, seeds: Optional[Sequence[int]] = None, trim=None,
-                         align=None, prefix_lens: Optional[Sequence[int]] = None, return_alignment: bool = False):
+                         align=None, prefix_lens: Optional[Sequence[int]] = None, return_alignment: bool = False,
+                         pins: Optional[Sequence[Optional[tuple]]] = None, start_step: int = 0):
         """Batched synthesize: per-utterance (R_i,64) refs, token lists and durations -> list of (1, samples).
         `frames` overrides the per-utterance frame counts (default floor(duration * 7.5), infer/onnx.py:84; the HTTP server
         rounds up like the reference's Rust server, pipeline.rs:66).
@@ -571,7 +720,13 @@ class SmallTTS:
         the returned row (with `trim`: intersected with the speech window and counted from its start); resolution one codec
         frame (3200 samples).  `prefix_lens`: per row, how many leading tokens are a prepended transcription the audio does not
         speak; they are left out of the path and of the groups.  Rows of at most 225 frames and 198 tokens.
-        `return_alignment`: one more element behind the words, per row (mass (n_b, P_b) fp32, spans (P_b, 2) int32)."""
+        `return_alignment`: one more element behind the words, per row (mass (n_b, P_b) fp32, spans (P_b, 2) int32).
+        `pins`: one entry per row, None or (latents (n_b, 64) fp32, keep (n_b,) bool): the kept frames come back as given, bit for
+        bit, and the sampler denoises the others with them in view (engine.sample x_pin / pin; smtts_sample_pinned).  The codec is
+        causal, so the audio in front of the first free frame is that of the kept latents.  `start_step` = k > 0 runs only the
+        sampler steps from k on, from the given latents (every row needs them then).  Works with every other argument; the fp16
+        range guard's re-run uses the same pins.  Only the mechanism is verified: how well the 4-step student inpaints is
+        UNVALIDATED on trained weights (every weight this project has run is seeded noise)."""
         ep = as_endpointing(trim)
         al = as_alignment(align)
         if al is None and (prefix_lens is not None or return_alignment):
@@ -608,6 +763,14 @@ class SmallTTS:
             pm[b, :ps[b]] = True
             mask[b, :ns[b]] = True
         eng = self.engine
+        pinned = _check_pins(pins, ns, start_step, self.num_steps)
+        pin_kw = {}
+        if pinned is not None:
+            x_pin, keep = np.zeros((B, Nm, 64), np.float32), np.zeros((B, Nm), bool)
+            for b, pe in enumerate(pinned):
+                if pe is not None:
+                    x_pin[b, :ns[b]], keep[b, :ns[b]] = pe
+            pin_kw = {"x_pin": x_pin, "pin": keep, "start_step": int(start_step)}
         seed = self._next_seed() if seeds is None else 0
         voices = None if voices is None else list(voices)      # run() keeps them alive while the batch is in flight
         p0s = [0] * B if prefix_lens is None else [int(v) for v in prefix_lens]
@@ -624,10 +787,10 @@ class SmallTTS:
                 cache.update(eng.voice_expand(voices))
             nz = noise if seeds is None else eng.randn_rows(seeds, ns, self.num_steps, n_max=Nm)
             if al is None:
-                x_ = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed)
+                x_ = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, **pin_kw)
                 return eng.codec_decode(x_), x_                # (B, 1, HOP * Nm); causal => prefixes are exact
             # the tap and the path ride on this batch's stream behind its sampler; a re-run (fp16 range guard) recomputes them
-            x_, mass = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, align=al)
+            x_, mass = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, align=al, **pin_kw)
             spans = eng.align_path(mass, ns, p0s, ps)[0]
             return eng.codec_decode(x_), (x_, mass, spans)
 
@@ -755,7 +918,7 @@ class SmallTTS:
                         durations: Optional[Sequence[float]] = None, seed: Optional[int] = None, gap_ms: float = 120.0,
                         fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3, pcm16: bool = False,
                         prefix_tokens: Optional[Sequence[int]] = None, trim=None, return_segments: bool = False,
-                        return_words: bool = False, align=None):
+                        return_words: bool = False, align=None, return_pieces: bool = False):
         """A whole text in one voice -> one waveform (1, S), fp32 or (pcm16=True) int16 PCM, S = sum(3200 * n_i) + (pieces - 1) *
         round(gap_ms * 24).
 
@@ -781,7 +944,11 @@ class SmallTTS:
         every piece's own tokens (the prefix is left out) in text order, the index running through the whole text, on the joined
         waveform's timeline: a piece's words lie inside its segment (with trim: inside its speech window).  The tap and the path
         kernel are enqueued on each batch's own stream behind its sampler; the spans are read back once, 8 bytes per token.
-        Returns (waveform[, segments][, words]).  Resolution: one codec frame, 3200 samples."""
+        Resolution: one codec frame, 3200 samples.
+
+        `return_pieces=True`: additionally -> [Piece(tokens, prefix_len, latents, seed), ...], what each piece was spoken from and
+        its latents (one read-back from the finished batches): render_long(pieces, ...) with the same join parameters reproduces the
+        waveform, and respeak makes the latents of a replacement piece.  Returns (waveform[, segments][, words][, pieces])."""
         ep = as_endpointing(trim)
         al = as_alignment(align if align is not None else (True if return_words else None))
         if al is not None and not return_words:
@@ -807,7 +974,7 @@ class SmallTTS:
         groups, offsets, S = plan_long(ns, max_batch, gap_ms)
         if not toks:
             empty = np.zeros((1, 0), np.int16 if pcm16 else np.float32)
-            res = (empty,) + (([],) if return_segments else ()) + (([],) if return_words else ())
+            res = (empty,) + (([],) if return_segments else ()) + (([],) if return_words else ()) + (([],) if return_pieces else ())
             return res if len(res) > 1 else empty
         base = self._next_seed() if seed is None else int(seed)
         seeds = [piece_seed(base, i) for i in range(len(toks))]
@@ -815,18 +982,9 @@ class SmallTTS:
                                                    seeds=[seeds[i] for i in g], _defer=True,
                                                    **({} if al is None else {"align": al, "prefix_lens": [len(prefix)] * len(g)}))
                  for g in groups]
-        if ep is not None:
-            out, segs, pending = self._long_trimmed(calls, groups, ep, in_flight, gap_ms, fade_ms, pcm16)
-        else:
-            pending = self._run_in_flight(calls, in_flight)
-            out = torch.zeros(S, dtype=torch.int16 if pcm16 else torch.float32, device=eng.device)
-            w = fade_table(fade_ms)
-            fade = torch.from_numpy(w).to(eng.device) if w.size else None
-            for g, (audio, _x, g_ns, _run) in zip(groups, pending):
-                eng.stitch(audio, g_ns, [offsets[i] for i in g], fade, out)
-            out = out.cpu().numpy()[None]
-            segs = [(offsets[i], HOP_SIZE * ns[i], 0, 1.0) for i in range(len(ns))]
+        out, segs, pending = self._join_long(calls, groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16)
         res = (out,) + ((segs,) if return_segments else ())
+        piece_spans: List[Optional[np.ndarray]] = [None] * len(toks)
         if al is not None:
             # one small read-back for the whole text: every batch's (B, P, 2) span table, flattened
             flat = torch.cat([p[1][2].reshape(-1) for p in pending]).cpu().numpy()
@@ -837,10 +995,120 @@ class SmallTTS:
                 pos += len(g) * Pg * 2
                 for r, i in enumerate(g):
                     off, n_i, start_i, _gain = segs[i]
+                    piece_spans[i] = sp[r, : len(toks[i])]
                     words += word_times(token_groups(toks[i][len(prefix):]), sp[r], ns[i], token0=len(prefix),
                                         window=(start_i, n_i) if ep is not None else None, offset=off, index0=len(words))
             res += (words,)
+        if return_pieces:
+            # one read-back for the whole text: every batch's latents, flattened
+            xs = [p[1][0] if al is not None else p[1] for p in pending]
+            flat = torch.cat([x.reshape(-1) for x in xs]).cpu().numpy()
+            made, pos = [], 0
+            for g, x in zip(groups, xs):
+                Ng = int(x.shape[1])
+                xg = flat[pos: pos + len(g) * Ng * 64].reshape(len(g), Ng, 64)
+                pos += len(g) * Ng * 64
+                made += [Piece(toks[i], len(prefix), xg[r, : ns[i]], seeds[i], piece_spans[i]) for r, i in enumerate(g)]
+            res += (made,)
         return res if len(res) > 1 else out
+
+    def _join_long(self, calls, groups, ns, offsets, S, ep: Optional["Endpointing"], in_flight: int, gap_ms: float, fade_ms: float,
+                   pcm16: bool):
+        """The tail synthesize_long and render_long share: the deferred batches `calls` (one per group) run through _run_in_flight,
+        their rows are joined on the device (with `ep`: at their speech windows) and copied out once.
+        -> (waveform (1, S), segments, the finished batches)."""
+        eng = self.engine
+        if ep is not None:
+            return self._long_trimmed(calls, groups, ep, in_flight, gap_ms, fade_ms, pcm16)
+        pending = self._run_in_flight(calls, in_flight)
+        out = torch.zeros(S, dtype=torch.int16 if pcm16 else torch.float32, device=eng.device)
+        w = fade_table(fade_ms)
+        fade = torch.from_numpy(w).to(eng.device) if w.size else None
+        for g, (audio, _x, g_ns, _run) in zip(groups, pending):
+            eng.stitch(audio, g_ns, [offsets[i] for i in g], fade, out)
+        out = out.cpu().numpy()[None]
+        return out, [(offsets[i], HOP_SIZE * ns[i], 0, 1.0) for i in range(len(ns))], pending
+
+    def render_long(self, pieces, *, gap_ms: float = 120.0, fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3,
+                    pcm16: bool = False, trim=None, return_segments: bool = False):
+        """The decode, endpoints and join half of synthesize_long for given latents: `pieces` are Pieces
+        (synthesize_long(return_pieces=True)) or (n_i, 64) arrays, in order.  They are grouped as plan_long groups them, decoded
+        through the same in-flight machinery under the same tuning and joined by the same kernels, so that the pieces of a take,
+        rendered with the take's parameters, give the take's waveform again bit for bit; with one piece replaced by a re-spoken
+        one of the same length every other piece's segment stays as it was (the decoder is causal and rows do not see each other).
+        A replacement of another length changes the shape of its group's batch: the other rows of that group then agree within the
+        engine's batch-shape tolerance, not bit for bit.  -> waveform (1, S)[, segments] as synthesize_long."""
+        ep = as_endpointing(trim)
+        lats = _piece_latents(pieces)
+        ns = [int(l.shape[0]) for l in lats]
+        groups, offsets, S = plan_long(ns, max_batch, gap_ms)
+        if not lats:
+            empty = np.zeros((1, 0), np.int16 if pcm16 else np.float32)
+            return (empty, []) if return_segments else empty
+        eng = self.engine
+
+        def deferred(g):
+            g_ns = [ns[i] for i in g]
+            lat = np.zeros((len(g), max(g_ns), 64), np.float32)
+            for r, i in enumerate(g):
+                lat[r, : ns[i]] = lats[i]
+
+            def run():
+                x = torch.from_numpy(lat).to(eng.device)
+                return eng.codec_decode(x), x
+
+            def go():
+                audio, x = run()
+                return audio, x, g_ns, run
+            return go
+
+        out, segs, _pending = self._join_long([deferred(g) for g in groups], groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16)
+        return (out, segs) if return_segments else out
+
+    def respeak(self, tokens: Sequence[int], latents, frames: Tuple[int, int], *, voice: Optional[Voice] = None, ref_latents=None,
+                new_tokens: Optional[Sequence[int]] = None, new_frames: Optional[int] = None, seed: Optional[int] = None,
+                start_step: int = 0, trim=None, align=None, prefix_len: int = 0, return_alignment: bool = False):
+        """Speaks frames [f0, f1) = `frames` of one utterance again and keeps the rest: `latents` (n, 64) are the utterance's (from
+        return_latents / a Piece), `tokens` its token list; one row through synthesize_batch(pins=splice_pins(latents, f0, f1,
+        new_frames)).  -> (audio (1, S'), latents (n', 64)[, words with align=]), n' = n - (f1 - f0) + new_frames: the frames in front
+        of f0 and behind f1 come back bit for bit (the tail at its shifted place), and so does the audio in front of sample
+        3200 * f0 when the row is decoded in a batch of the same shape (the codec is causal).  Which frames speak a word:
+        frames_of_groups on the spans of align=.
+
+        `new_tokens`: the row's WHOLE new token list when the text changes (default: `tokens`); `new_frames`: the length of the
+        regenerated region (default f1 - f0).  `voice` or `ref_latents`: the reference, one of them.  `seed`: the noise of the new
+        take — a new take needs a new seed: with the seed the row was first spoken with, the free frames see much the same noise
+        again.  None draws one.  `start_step` = k > 0 runs only the sampler steps from k on, from `latents` themselves in the
+        free region too (same length only); start_step = num_steps - 1 is nearly a no-op by the schedule (alpha(0) = 1,
+        sigma(0) = 3.1e-5).  `prefix_len`: leading tokens that are a prepended transcription (align= leaves them out).
+        `return_alignment` (with align=): one more element, (mass (n', P) fp32, spans (P, 2) int32) of the new row.
+
+        Only the mechanism is verified.  It is UNVALIDATED on trained weights: every weight this project has run is seeded noise,
+        and nobody has measured how well a 4-step distilled student inpaints."""
+        if (voice is None) == (ref_latents is None):
+            raise ValueError("respeak: pass either voice or ref_latents")
+        if not isinstance(frames, (tuple, list)) or len(frames) != 2:
+            raise ValueError("respeak: frames must be (f0, f1)")
+        f0, f1 = int(frames[0]), int(frames[1])
+        x_pin, keep = splice_pins(latents, f0, f1, new_frames)
+        start_step = int(start_step)
+        if start_step > 0:
+            if x_pin.shape[0] != np.asarray(latents).shape[0]:
+                raise ValueError("respeak: start_step > 0 starts from the given latents: new_frames must equal f1 - f0")
+            x_pin[f0:f1] = np.asarray(latents, np.float32)[f0:f1]
+        toks = [int(t) for t in (tokens if new_tokens is None else new_tokens)]
+        if not 0 <= int(prefix_len) <= len(toks):
+            raise ValueError("respeak: prefix_len must lie in [0, number of tokens]")
+        al = as_alignment(align)
+        if return_alignment and al is None:
+            raise ValueError("respeak: return_alignment= belongs to align=")
+        res = self.synthesize_batch(None if voice is not None else [np.asarray(ref_latents, np.float32)], [toks], None,
+                                    frames=[int(x_pin.shape[0])], voices=None if voice is None else [voice],
+                                    seeds=[self._next_seed() if seed is None else int(seed)], trim=trim, return_latents=True,
+                                    pins=[(x_pin, keep)], start_step=start_step,
+                                    **({} if al is None else {"align": al, "prefix_lens": [int(prefix_len)],
+                                                              "return_alignment": bool(return_alignment)}))
+        return (res[0][0], res[1][0]) + (tuple(r[0] for r in res[2:]) if al is not None else ())
 
     def _long_trimmed(self, calls, groups, ep: "Endpointing", in_flight: int, gap_ms: float, fade_ms: float, pcm16: bool):
         """synthesize_long's trimmed join -> (waveform, segments, the finished batches).  Every deferred batch enqueues its endpoints

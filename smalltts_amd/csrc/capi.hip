@@ -124,6 +124,16 @@ int smtts_sample_align(smtts_handle h, void* stream, int mode, int n_steps, int 
     return E.sample_align(ST(stream), mode, n_steps, cfg, s_text, s_spk, mask, k_ref, v_ref, ref_mask, k_text, v_text, ph_mask,
                           B, N, R, P, noise, seed, x_out, steps_out, ws, ws_bytes, tap_steps, tap_layers, tap_heads, text_mass);
 }
+int smtts_sample_pinned(smtts_handle h, void* stream, int mode, int n_steps, int cfg, float s_text, float s_spk,
+                        const uint8_t* mask, const float* k_ref, const float* v_ref, const uint8_t* ref_mask,
+                        const float* k_text, const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P,
+                        const float* noise, uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes,
+                        const uint8_t* tap_steps, uint32_t tap_layers, uint32_t tap_heads, float* text_mass, const float* x_pin,
+                        const uint8_t* pin, int start_step) { NULLCHK;
+    return E.sample_pinned(ST(stream), mode, n_steps, cfg, s_text, s_spk, mask, k_ref, v_ref, ref_mask, k_text, v_text, ph_mask,
+                           B, N, R, P, noise, seed, x_out, steps_out, ws, ws_bytes, tap_steps, tap_layers, tap_heads, text_mass, x_pin,
+                           pin, start_step);
+}
 int smtts_align_path(smtts_handle h, void* stream, const float* mass, int B, int N, int P, const int32_t* n_len, const int32_t* p0,
                      const int32_t* p1, int32_t* spans, float* score) { NULLCHK;
     if (B <= 0 || !mass || !n_len || !p0 || !p1 || !spans || !score) return E.fail("align_path: bad arguments");

@@ -1542,16 +1542,28 @@ size_t Engine::sample_ws_bytes(int B, int N, int R, int P, int n_steps, int cfg)
     return b.off + 256 + denoise_core_bytes(cfg ? 3 * B : B, N) + cross_img_bytes(cfg ? 3 * B : B, R, P);
 }
 
-int Engine::sample_align(hipStream_t st, int mode, int n_steps, int cfg, float s_text, float s_spk, const uint8_t* mask,
-                         const float* k_ref, const float* v_ref, const uint8_t* ref_mask, const float* k_text,
-                         const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P, const float* noise,
-                         uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes, const uint8_t* tap_steps,
-                         unsigned tap_layers, unsigned tap_heads, float* text_mass) {
+int Engine::sample_pinned(hipStream_t st, int mode, int n_steps, int cfg, float s_text, float s_spk, const uint8_t* mask,
+                          const float* k_ref, const float* v_ref, const uint8_t* ref_mask, const float* k_text,
+                          const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P, const float* noise,
+                          uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes, const uint8_t* tap_steps,
+                          unsigned tap_layers, unsigned tap_heads, float* text_mass, const float* x_pin, const uint8_t* pin,
+                          int start_step) {
     DeepScope deep_scope(gemm_deep_);
     if (!dit_ready_) return fail("sample: DiT weights not finalized");
     if (n_steps < 1) return fail("sample: n_steps must be >= 1");
     if (N > kMaxPos) return fail("sample: sequence longer than the rope table (4096)");
     if (ws_bytes < sample_ws_bytes(B, N, R, P, n_steps, cfg)) return fail("sample: workspace too small");
+    // pinned frames (kernels.hip pin_renoise / pin_update): validated before anything is enqueued; without them nothing below differs
+    const bool pinned = x_pin != nullptr || pin != nullptr || start_step != 0;
+    if (pinned) {
+        if (mode != 0) return fail("sample_pinned: pinned frames and start_step belong to mode 0 (the DMD sampler) only");
+        if (cfg != 0) return fail("sample_pinned: pinned frames and start_step are not available with cfg");
+        if (start_step < 0 || start_step >= n_steps) return fail("sample_pinned: start_step must lie in [0, n_steps)");
+        if (start_step > 0 && !x_pin) return fail("sample_pinned: start_step > 0 starts from x_pin, which is NULL");
+        if (pin && !x_pin) return fail("sample_pinned: pin needs x_pin");
+        if ((((uintptr_t)x_pin | (uintptr_t)noise | (uintptr_t)ws) & 15) != 0)
+            return fail("sample_pinned: x_pin, noise and the workspace must be 16-byte aligned");
+    }
     // the text-attention tap (align.hip): validated before anything is enqueued; off (text_mass == null) nothing below differs from sample()
     struct TapGuard { Engine* e; ~TapGuard() { e->tap_ = AlignTap(); } } tap_guard{this};
     std::vector<uint8_t> tap_on(n_steps, 0);
@@ -1561,7 +1573,7 @@ int Engine::sample_align(hipStream_t st, int mode, int n_steps, int cfg, float s
         tap_layers &= (1u << kBlocks) - 1u;
         tap_heads &= (1u << kHeads) - 1u;
         int ns = 0, nl = 0, nh = 0;
-        for (int i = 0; i < n_steps; ++i) ns += (tap_on[i] = tap_steps ? (tap_steps[i] != 0) : (i + 1 == n_steps));
+        for (int i = start_step; i < n_steps; ++i) ns += (tap_on[i] = tap_steps ? (tap_steps[i] != 0) : (i + 1 == n_steps));
         for (int l = 0; l < kBlocks; ++l) nl += (tap_layers >> l) & 1u;
         for (int h = 0; h < kHeads; ++h) nh += (tap_heads >> h) & 1u;
         if (!ns || !nl || !nh) return fail("sample_align: the tap selects no (step, layer, head): 12 layers (bits 0..11), 8 heads (bits 0..7)");
@@ -1634,7 +1646,17 @@ int Engine::sample_align(hipStream_t st, int mode, int n_steps, int cfg, float s
         return 0;
     };
 
-    if (mode == 0) {
+    if (pinned) {
+        // the same loop with the select in both element-wise steps; the first re-noise builds x itself (no memset, no launch more)
+        for (int i = start_step; i < n_steps; ++i) {
+            const float* nz = noise ? noise + (long)i * e : s.nz;
+            if (!noise) HIPC(launch_randn(s.nz, e, seed, (uint64_t)i, st));   // always stream i, whatever start_step is
+            HIPC(launch_pin_renoise(s.xt, s.x, x_pin, pin, mask, nz, al[i], sg[i], i > start_step ? 0 : start_step > 0 ? 2 : 1, e, st));
+            if (eval_velocity(i)) return 1;
+            HIPC(launch_pin_update(s.x, s.xt, s.v, x_pin, pin, mask, al[i], -sg[i], e, st));   // x = K ? x_pin : a x_t - s v
+            if (steps_out) HIPC(hipMemcpyAsync(steps_out + (long)i * e, s.x, e * sizeof(float), hipMemcpyDeviceToDevice, st));
+        }
+    } else if (mode == 0) {
         HIPC(hipMemsetAsync(s.x, 0, e * sizeof(float), st));
         for (int i = 0; i < n_steps; ++i) {
             const float* nz = noise ? noise + (long)i * e : s.nz;

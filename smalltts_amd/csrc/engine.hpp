@@ -178,7 +178,19 @@ class Engine {
                      const float* k_ref, const float* v_ref, const uint8_t* ref_mask, const float* k_text,
                      const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P, const float* noise,
                      uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes, const uint8_t* tap_steps,
-                     unsigned tap_layers, unsigned tap_heads, float* text_mass);
+                     unsigned tap_layers, unsigned tap_heads, float* text_mass) {
+        return sample_pinned(st, mode, n_steps, cfg, s_text, s_spk, mask, k_ref, v_ref, ref_mask, k_text, v_text, ph_mask, B, N, R, P, noise,
+                             seed, x_out, steps_out, ws, ws_bytes, tap_steps, tap_layers, tap_heads, text_mass, nullptr, nullptr, 0);
+    }
+    // sample_align() that keeps pinned frames (mode 0, cfg == 0; the definition: include/smalltts_hip.h).  x_pin f32 (B, N, 64), pin bool
+    // (B, N), both DEVICE; K = pin && mask.  The loop runs steps [start_step, n_steps) from x = x_pin (start_step == 0: K ? x_pin : 0) and
+    // writes K ? x_pin : (a x_t - s v) after every step (kernels.hip: pin_renoise / pin_update instead of axpby, no launch more).
+    // x_pin == pin == null and start_step == 0: sample_align(), the same kernels.
+    int sample_pinned(hipStream_t st, int mode, int n_steps, int cfg, float s_text, float s_spk, const uint8_t* mask,
+                      const float* k_ref, const float* v_ref, const uint8_t* ref_mask, const float* k_text,
+                      const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P, const float* noise,
+                      uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes, const uint8_t* tap_steps,
+                      unsigned tap_layers, unsigned tap_heads, float* text_mass, const float* x_pin, const uint8_t* pin, int start_step);
 
     size_t decode_ws_bytes(int B, int T) const;
     int codec_decode(hipStream_t st, const float* latents, int B, int T, float* audio, void* ws, size_t ws_bytes);

@@ -263,6 +263,89 @@ hipError_t launch_axpby(float* out, const float* x, const float* y, float a, flo
     LAUNCH_CHECK();
 }
 
+// ------------------------------------------------------------------------------------------
+// Pinned sampling (Engine::sample_pinned): the two element-wise steps of the DMD loop with a per-frame select.  A frame is 64 floats
+// = sixteen 16-byte lanes that share one pin byte and one mask byte; K = pin && mask (pin == null: K is false everywhere; mask == null:
+// every frame is valid).  One thread per 16-byte lane; when n is no multiple of 4 the thread behind the last whole lane walks the scalar
+// tail (element j belongs to frame j / 64).  The arithmetic is axpby_kernel's expression, operand for operand, so that the compiler
+// contracts it into the same multiply + fma: with K false everywhere both kernels write axpby's bits.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool pin_keep(const uint8_t* __restrict__ pin, const uint8_t* __restrict__ mask, long frame) {
+    return pin != nullptr && pin[frame] != 0 && (mask == nullptr || mask[frame] != 0);
+}
+// x_t = a x + s eps.  src 0: x is read from `x` (the update kernel left the pinned frames in it); 1: x = K ? x_pin : 0 (the first step
+// of a whole run: no memset, no x buffer read); 2: x = x_pin (the first step of a late start).
+__global__ __launch_bounds__(256) void pin_renoise_kernel(float* __restrict__ xt, const float* __restrict__ x,
+                                                          const float* __restrict__ x_pin, const uint8_t* __restrict__ pin,
+                                                          const uint8_t* __restrict__ mask, const float* __restrict__ eps, float a,
+                                                          float s, int src, long n) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long n4 = n >> 2;
+    if (q < n4) {
+        float4 xv = make_float4(0.f, 0.f, 0.f, 0.f);
+        if (src == 0) xv = reinterpret_cast<const float4*>(x)[q];
+        else if (src == 2 || pin_keep(pin, mask, q >> 4)) xv = reinterpret_cast<const float4*>(x_pin)[q];
+        const float4 e = reinterpret_cast<const float4*>(eps)[q];
+        float4 o;
+        o.x = a * xv.x + s * e.x;
+        o.y = a * xv.y + s * e.y;
+        o.z = a * xv.z + s * e.z;
+        o.w = a * xv.w + s * e.w;
+        reinterpret_cast<float4*>(xt)[q] = o;
+    } else if (q == n4) {
+        for (long j = n4 << 2; j < n; ++j) {
+            float xv = 0.f;
+            if (src == 0) xv = x[j];
+            else if (src == 2 || pin_keep(pin, mask, j >> 6)) xv = x_pin[j];
+            xt[j] = a * xv + s * eps[j];
+        }
+    }
+}
+// x = K ? x_pin : a x_t + b v   (b = -sigma)
+__global__ __launch_bounds__(256) void pin_update_kernel(float* __restrict__ x, const float* __restrict__ xt,
+                                                         const float* __restrict__ v, const float* __restrict__ x_pin,
+                                                         const uint8_t* __restrict__ pin, const uint8_t* __restrict__ mask, float a,
+                                                         float b, long n) {
+    const long q = (long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long n4 = n >> 2;
+    if (q < n4) {
+        float4 o;
+        if (pin_keep(pin, mask, q >> 4)) {
+            o = reinterpret_cast<const float4*>(x_pin)[q];
+        } else {
+            const float4 t = reinterpret_cast<const float4*>(xt)[q];
+            const float4 w = reinterpret_cast<const float4*>(v)[q];
+            o.x = a * t.x + b * w.x;
+            o.y = a * t.y + b * w.y;
+            o.z = a * t.z + b * w.z;
+            o.w = a * t.w + b * w.w;
+        }
+        reinterpret_cast<float4*>(x)[q] = o;
+    } else if (q == n4) {
+        for (long j = n4 << 2; j < n; ++j) x[j] = pin_keep(pin, mask, j >> 6) ? x_pin[j] : a * xt[j] + b * v[j];
+    }
+}
+static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
+static inline unsigned pin_grid(long n) { return (unsigned)(((n >> 2) + ((n & 3) ? 1 : 0) + 255) / 256); }   // whole lanes + one tail thread
+hipError_t launch_pin_renoise(float* xt, const float* x, const float* x_pin, const uint8_t* pin, const uint8_t* mask, const float* eps,
+                              float a, float s, int src, long n, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (!aligned16(xt) || !aligned16(x) || !aligned16(x_pin) || !aligned16(eps)) return hipErrorInvalidValue;
+    if (src < 0 || src > 2 || (src == 0 ? x == nullptr : x_pin == nullptr && (src == 2 || pin != nullptr))) return hipErrorInvalidValue;
+    ProfScope ps(st, "pin_renoise", 3.0 * n, 12.0 * n + n / 32.0);
+    hipLaunchKernelGGL(pin_renoise_kernel, dim3(pin_grid(n)), dim3(256), 0, st, xt, x, x_pin, pin, mask, eps, a, s, src, n);
+    LAUNCH_CHECK();
+}
+hipError_t launch_pin_update(float* x, const float* xt, const float* v, const float* x_pin, const uint8_t* pin, const uint8_t* mask,
+                             float a, float b, long n, hipStream_t st) {
+    if (n == 0) return hipSuccess;
+    if (!aligned16(x) || !aligned16(xt) || !aligned16(v) || !aligned16(x_pin) || (pin != nullptr && x_pin == nullptr))
+        return hipErrorInvalidValue;
+    ProfScope ps(st, "pin_update", 3.0 * n, 12.0 * n + n / 32.0);
+    hipLaunchKernelGGL(pin_update_kernel, dim3(pin_grid(n)), dim3(256), 0, st, x, xt, v, x_pin, pin, mask, a, b, n);
+    LAUNCH_CHECK();
+}
+
 __global__ void ode_step_kernel(float* __restrict__ xt, const float* __restrict__ v, float* __restrict__ x0_out,
                                 float a, float s, float a2, float s2, long n) {
     long i = (long)blockIdx.x * blockDim.x + threadIdx.x;

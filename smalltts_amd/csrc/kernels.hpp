@@ -122,6 +122,12 @@ hipError_t launch_to_split(const float* x, RowMap xmap, bf16_t* hi, bf16_t* lo, 
 
 // sampler element-wise steps (infer/onnx.py:105,125 ; teacher ODE see DESIGN.md)
 hipError_t launch_axpby(float* out, const float* x, const float* y, float a, float b, long n, hipStream_t st);
+// pinned sampling: axpby with a per-frame select (frame = 64 floats, K = pin && mask; 16-byte aligned buffers).  renoise: x_t = a x + s eps
+// with x from `x` (src 0), K ? x_pin : 0 (src 1) or x_pin (src 2); update: x = K ? x_pin : a x_t + b v.
+hipError_t launch_pin_renoise(float* xt, const float* x, const float* x_pin, const uint8_t* pin, const uint8_t* mask, const float* eps,
+                              float a, float s, int src, long n, hipStream_t st);
+hipError_t launch_pin_update(float* x, const float* xt, const float* v, const float* x_pin, const uint8_t* pin, const uint8_t* mask,
+                             float a, float b, long n, hipStream_t st);
 // x0 = a*xt - s*v ; eps = s*xt + a*v ; xt_next = a2*x0 + s2*eps    (x0 written to x0_out)
 hipError_t launch_ode_step(float* xt, const float* v, float* x0_out, float a, float s, float a2, float s2, long n,
                            hipStream_t st);

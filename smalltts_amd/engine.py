@@ -401,8 +401,14 @@ class HipEngine:
         return v
 
     def sample(self, cache, mask, num_steps: int = 4, mode: str = "dmd", cfg: bool = False, s_text: float = 2.0,
-               s_spk: float = 1.5, noise=None, seed: int = 0, return_steps: bool = False, align=None):
+               s_spk: float = 1.5, noise=None, seed: int = 0, return_steps: bool = False, align=None, x_pin=None, pin=None,
+               start_step: int = 0):
         """Runs the whole sampler on the GPU. mask: (B,N) (cfg: rows are replicated x3 internally).
+        x_pin fp32 (B,N,64), pin bool (B,N), start_step (smtts_sample_pinned; the definition: include/smalltts_hip.h; DMD mode without
+        cfg only): the frames with pin && mask come back as x_pin, bit for bit, and stay x_pin after every step, so that the other
+        frames are denoised with them in view; start_step = k > 0 starts the loop at step k from x_pin (step i always draws noise
+        stream i) and leaves the slots below k of the returned steps at zero.  Returns as without them.  Only the mechanism is
+        verified: how well the 4-step student inpaints is unvalidated on trained weights (api.SmallTTS.respeak).
         align (None / False: off; True or an object with .layers / .heads / .steps, e.g. api.Alignment): the text-attention tap of
         smtts_sample_align runs behind the selected (step, layer) attention launches and the call returns (x, mass) — with
         return_steps (x, steps, mass) — mass fp32 (B,N,P) on the device: the mean over the selected (step, layer, head) triples of
@@ -421,9 +427,46 @@ class HipEngine:
         if noise is not None:
             want = (num_steps, B, N, LATENT) if mode == "dmd" else (B, N, LATENT)
             assert tuple(noise.shape) == want, f"noise shape {tuple(noise.shape)} != {want}"
+        pinned = x_pin is not None or pin is not None or int(start_step) != 0
+        if pinned:
+            start_step = int(start_step)
+            if mode != "dmd" or cfg:
+                raise ValueError("sample: x_pin / pin / start_step belong to the DMD sampler without cfg")
+            if not 0 <= start_step < num_steps:
+                raise ValueError(f"sample: start_step must lie in [0, {num_steps}), got {start_step}")
+            if x_pin is None:
+                raise ValueError("sample: pin= and start_step > 0 need x_pin")
+            for name, t, shape, dt in (("x_pin", x_pin, (B, N, LATENT), (torch.float32, np.float32)),
+                                       ("pin", pin, (B, N), (torch.bool, np.bool_))):
+                if t is None:
+                    continue
+                if not hasattr(t, "shape") or tuple(t.shape) != shape or t.dtype not in dt:
+                    raise ValueError(f"sample: {name} must be a {'fp32' if name == 'x_pin' else 'bool'} array of shape {shape}, got "
+                                     f"{getattr(t, 'dtype', type(t).__name__)} {tuple(getattr(t, 'shape', ()))}")
+            x_pin = self._dev(x_pin, torch.float32)
+            pin = None if pin is None else self._dev(pin, torch.bool)
+            if x_pin.data_ptr() % 16:
+                x_pin = x_pin.clone()
+            if noise is not None and noise.data_ptr() % 16:
+                noise = noise.clone()
         x = torch.empty(B, N, LATENT, device=self.device)
-        steps = torch.empty(num_steps, B, N, LATENT, device=self.device) if return_steps else None
+        steps = None
+        if return_steps:   # a late start writes the slots from start_step on only: the others are zeros
+            steps = (torch.zeros if pinned and start_step > 0 else torch.empty)(num_steps, B, N, LATENT, device=self.device)
         ws = self._workspace(self.lib.smtts_sample_workspace_bytes(self.h, B, N, R, P, num_steps, int(cfg)))
+        if pinned:
+            tap = align is not None and align is not False
+            flags, layers, heads = tap_selection(align, num_steps) if tap else (None, 0, 0)
+            if tap and P < 1:
+                raise ValueError("sample: align= needs text keys (P >= 1)")
+            mass = torch.empty(B, N, P, device=self.device) if tap else None
+            self._ck(self.lib.smtts_sample_pinned(self.h, self._stream(), 0, num_steps, 0, s_text, s_spk, _p(mask_in), _p(cache["k_ref"]),
+                                                  _p(cache["v_ref"]), _p(cache["ref_mask"]), _p(cache["k_text"]), _p(cache["v_text"]),
+                                                  _p(cache["ph_mask"]), B, N, R, P, _p(noise), C.c_uint64(seed), _p(x), _p(steps),
+                                                  _p(ws), ws.numel(), C.cast(flags, C.c_void_p) if tap else None, layers, heads, _p(mass),
+                                                  _p(x_pin), _p(pin), start_step), "sample_pinned")
+            res = (x,) + ((steps,) if return_steps else ()) + ((mass,) if tap else ())
+            return res if len(res) > 1 else x
         if align is not None and align is not False:
             flags, layers, heads = tap_selection(align, num_steps)
             if P < 1:

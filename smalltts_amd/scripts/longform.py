@@ -4,12 +4,13 @@ pieces run as batches in flight and are joined on the device (api.SmallTTS.synth
 Without espeak: --tokens-file (one comma-separated token list per line = one piece) with --durations (seconds, one per line).
 --words out.json: when every word / punctuation mark / [event] is spoken (from the DiT's text attention: api.Alignment, default
 selection unvalidated on trained weights; resolution one codec frame = 133 ms).  --srt out.srt: one subtitle cue per piece, and
-next to it out.words.srt with one cue per word group."""
+next to it out.words.srt with one cue per word group.  --take OUT.npz: the pieces (tokens, latents, seeds; with --words also each
+piece's token spans) and the join parameters, what scripts/respeak.py re-speaks a span of and renders again."""
 import argparse
 import json
 from pathlib import Path
 
-from ..api import SAMPLE_RATE, Endpointing, SmallTTS, estimate_duration, format_srt, split_text, token_groups
+from ..api import SAMPLE_RATE, Endpointing, SmallTTS, estimate_duration, format_srt, save_take, split_text, token_groups
 from ..audio import read_wav, write_wav_pcm16
 from ..phonemes import decode_token_ids, get_token_ids, parse_tokens_arg
 from ._common import add_engine_args
@@ -52,6 +53,7 @@ def main(argv=None):
     ap.add_argument("--level", type=float, default=None, metavar="DBFS", help="with --trim: bring every piece's speech to this RMS level")
     ap.add_argument("--words", default=None, metavar="OUT.json", help="write the time of every word / punctuation mark / [event] (133 ms resolution)")
     ap.add_argument("--srt", default=None, metavar="OUT.srt", help="write one subtitle cue per piece, and OUT.words.srt with one cue per word group")
+    ap.add_argument("--take", default=None, metavar="OUT.npz", help="save the pieces and the join parameters (for scripts/respeak.py)")
     ap.add_argument("--max-batch", type=int, default=8)
     ap.add_argument("--in-flight", type=int, default=3)
     add_engine_args(ap)
@@ -75,6 +77,8 @@ def main(argv=None):
     timed = bool(args.words or args.srt)
     if timed:
         kw.update(return_segments=True, return_words=True)
+    if args.take:
+        kw.update(return_pieces=True)
     if args.tokens_file:
         with open(args.tokens_file) as f:
             token_lists = [parse_tokens_arg(line) for line in f if line.strip()]
@@ -92,6 +96,12 @@ def main(argv=None):
         print(f"generating {len(pieces)} pieces")
         token_lists, piece_texts = [tok(p) for p in pieces], pieces
         audio = tts.synthesize_long(voice, token_lists=token_lists, durations=[estimate_duration(p) for p in pieces], **kw)
+    if args.take:
+        audio, taken = (audio[:-1] if timed else audio[0]), audio[-1]
+        Path(args.take).parent.mkdir(parents=True, exist_ok=True)
+        save_take(args.take, taken, gap_ms=args.gap_ms, fade_ms=args.fade_ms, max_batch=args.max_batch, in_flight=args.in_flight,
+                  trim=args.trim, level_dbfs=args.level)
+        print(f"{args.take} ({len(taken)} pieces)")
     if timed:
         audio, segments, words = audio
         texts = group_texts(token_lists)

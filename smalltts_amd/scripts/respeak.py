@@ -1,0 +1,95 @@
+"""python -m smalltts_amd.scripts.respeak --take T.npz --wav ref.wav --piece I (--frames A:B | --groups A:B) [--seed S]
+    [--start-step K] --out out.wav [--take-out T2.npz]
+Speaks a span of one piece of a long take again and keeps everything else: the take (scripts/longform.py --take) holds every piece's
+tokens and latents; frames [A, B) of piece I, or the frames its token groups [A, B) touch (the spans longform --words saved), are
+regenerated with the rest of the piece pinned (api.SmallTTS.respeak), the whole take is rendered again with its own join parameters
+(api.SmallTTS.render_long) and written out, with the updated take next to it.  A new take needs a new --seed (none: one is drawn).
+--tokens: the piece's new token list when the text changes (the take's prefix is prepended); --new-frames: the length of the
+regenerated region.  Only the mechanism is verified: how well the 4-step student inpaints is unvalidated on trained weights."""
+import argparse
+from pathlib import Path
+
+from ..api import Endpointing, Piece, SmallTTS, frames_of_groups, load_take, save_take, token_groups
+from ..audio import read_wav, write_wav_pcm16
+from ..phonemes import parse_tokens_arg
+from ._common import add_engine_args
+
+
+def parse_range(text: str, what: str):
+    """'A:B' -> (A, B) with A < B."""
+    try:
+        a, b = (int(v) for v in text.split(":"))
+    except ValueError:
+        raise ValueError(f"{what} must be A:B, two integers, got {text!r}") from None
+    if not 0 <= a < b:
+        raise ValueError(f"{what}: need 0 <= A < B, got {a}:{b}")
+    return a, b
+
+
+def span_frames(piece: Piece, frames=None, groups=None):
+    """The frames to regenerate in `piece`: --frames as given, --groups through the piece's saved token spans."""
+    if (frames is None) == (groups is None):
+        raise ValueError("pass either --frames or --groups")
+    if frames is not None:
+        f0, f1 = parse_range(frames, "--frames")
+        if f1 > piece.latents.shape[0]:
+            raise ValueError(f"--frames {f0}:{f1} outside the piece's {piece.latents.shape[0]} frames")
+        return f0, f1
+    if piece.spans is None:
+        raise ValueError("--groups needs the token spans of the piece: make the take with longform --words")
+    g0, g1 = parse_range(groups, "--groups")
+    return frames_of_groups(token_groups(piece.tokens[piece.prefix_len:]), piece.spans, g0, g1, token0=piece.prefix_len)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--take", required=True, help="the take to change (longform --take)")
+    ap.add_argument("--wav", required=True, help="reference audio file (the voice the take was spoken in)")
+    ap.add_argument("--piece", type=int, required=True, help="index of the piece")
+    ap.add_argument("--frames", default=None, metavar="A:B", help="regenerate frames [A, B) of the piece (one frame = 3200 samples)")
+    ap.add_argument("--groups", default=None, metavar="A:B", help="regenerate the frames of the piece's token groups [A, B)")
+    ap.add_argument("--new-frames", type=int, default=None, help="length of the regenerated region (default: B - A frames)")
+    ap.add_argument("--start-step", type=int, default=0, help="run only the sampler steps from K on, from the take's latents")
+    ap.add_argument("--out", required=True)
+    ap.add_argument("--take-out", default=None, metavar="T2.npz", help="where the updated take goes (default: next to --out)")
+    add_engine_args(ap)
+    args = ap.parse_args(argv)
+    pieces, join = load_take(args.take)
+    if not 0 <= args.piece < len(pieces):
+        ap.error(f"--piece must lie in [0, {len(pieces)})")
+    old = pieces[args.piece]
+    try:
+        f0, f1 = span_frames(old, args.frames, args.groups)
+    except ValueError as e:
+        ap.error(str(e))
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    print("loading")
+    tts = SmallTTS(weights=args.weights, device=args.device, precision=args.precision, num_steps=args.steps, seed=args.seed)
+    print("encoding reference audio")
+    y, sr = read_wav(args.wav)
+    if y.ndim == 2:
+        y = y.mean(axis=1)
+    voice = tts.encode_voice_wav(y, sr)
+    seed = tts._next_seed() if args.seed is None else int(args.seed)
+    tokens = list(old.tokens)
+    if args.tokens:
+        tokens = tokens[:old.prefix_len] + parse_tokens_arg(args.tokens)
+    timed = old.spans is not None
+    print(f"re-speaking frames [{f0}, {f1}) of piece {args.piece} (seed {seed})")
+    res = tts.respeak(old.tokens, old.latents, (f0, f1), voice=voice, new_tokens=tokens, new_frames=args.new_frames, seed=seed,
+                      start_step=args.start_step, prefix_len=old.prefix_len,
+                      **({"align": True, "return_alignment": True} if timed else {}))
+    pieces[args.piece] = Piece(tokens, old.prefix_len, res[1], seed, res[3][1] if timed else None)
+    trim = Endpointing(level_dbfs=join["level_dbfs"]) if join["trim"] else None
+    audio = tts.render_long(pieces, gap_ms=join["gap_ms"], fade_ms=join["fade_ms"], max_batch=join["max_batch"],
+                            in_flight=join["in_flight"], trim=trim)
+    write_wav_pcm16(args.out, audio.squeeze(0), 24_000)
+    print(f"{args.out} ({audio.shape[1] / 24_000:.1f}s)")
+    take_out = args.take_out or str(Path(args.out).with_suffix(".npz"))
+    Path(take_out).parent.mkdir(parents=True, exist_ok=True)
+    save_take(take_out, pieces, **join)
+    print(f"{take_out} ({len(pieces)} pieces)")
+
+
+if __name__ == "__main__":
+    main()
