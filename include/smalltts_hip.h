@@ -19,6 +19,10 @@
  * all work is enqueued asynchronously on `stream`.  The caller owns inputs, outputs and workspace
  * (query the size first); the library owns weights only.  Return 0 = ok, non-zero = error with the
  * message available from smtts_last_error().
+ * A workspace (`ws`) must be 256-BYTE ALIGNED: the library carves it at 256-byte offsets from its base and keeps an operand-format
+ * tag in the low bits of the carved addresses.  hipMalloc and torch's allocator return such addresses; a sub-allocation of the
+ * caller's own arena must be placed on a 256-byte boundary.  Every entry that takes `ws` refuses a misaligned one (non-zero,
+ * "workspace must be 256-byte aligned") next to its "workspace too small" check, before anything is enqueued.
  *
  * Threading / streams (the same rules as smalltts_amd/csrc/engine.hpp:4-8): a handle is NOT thread-safe — one handle per GPU,
  * driven by ONE host thread (the reference also has one Session per pipeline behind a mutex, src/server/src/main.rs:24,138).
@@ -154,8 +158,8 @@ int smtts_sample_align(smtts_handle h, void* stream, int mode, int n_steps, int 
  *         x   = K ? x_pin : (al[i] * x_t - sg[i] * v)
  *         steps_out[i] = x                       slots below start_step are not written
  *     x_out = x
- * Mode 0 (DMD) and cfg == 0 only; 0 <= start_step < n_steps; start_step > 0 needs x_pin; pin != NULL needs x_pin; x_pin, noise and
- * the workspace 16-byte aligned; anything else returns 1 with a message before anything is enqueued.  Workspace:
+ * Mode 0 (DMD) and cfg == 0 only; 0 <= start_step < n_steps; start_step > 0 needs x_pin; pin != NULL needs x_pin; x_pin and noise
+ * 16-byte aligned (the workspace 256-byte, as everywhere); anything else returns 1 with a message before anything is enqueued.  Workspace:
  * smtts_sample_workspace_bytes.  The tap arguments work as in smtts_sample_align; a flagged step below start_step is not run and does
  * not count in the tap's mean, and a selection with no step left is an error.  The select rides in the two element-wise kernels of a
  * step (16-byte lanes, sixteen of them share a frame's pin byte): not one launch more than smtts_sample.  With x_pin given, pin all

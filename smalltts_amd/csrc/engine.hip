@@ -29,6 +29,9 @@ struct Bump {  // bump allocator over a caller-owned workspace (also used, with 
         return r;
     }
 };
+// Bump aligns its offsets relative to the base and the operand-format tag rides in the low bits of a carve-out's address
+// (common.hpp sm_lo_for): both hold only on a 256-byte aligned workspace.  Checked by every operator next to its size check.
+inline bool ws_misaligned(const void* ws) { return (reinterpret_cast<uintptr_t>(ws) & 255) != 0; }
 inline std::string sidx(const std::string& a, int i, const std::string& b) { return a + std::to_string(i) + b; }
 }  // namespace
 
@@ -1005,6 +1008,7 @@ int Engine::cond_encode(hipStream_t st, const float* ref, const int64_t* ref_len
     if (!dit_ready_) return fail("cond_encode: DiT weights not finalized");
     if (R > kMaxPos || P > kMaxPos) return fail("cond_encode: sequence longer than the rope table (4096)");
     if (ws_bytes < cond_ws_bytes(B, R, P)) return fail("cond_encode: workspace too small");
+    if (ws_misaligned(ws)) return fail("cond_encode: workspace must be 256-byte aligned");
     HIPC(hipSetDevice(device_));
     Bump bump(ws);
     EncWs w, wt;
@@ -1482,6 +1486,7 @@ int Engine::denoise_step(hipStream_t st, const float* x_t, const uint8_t* mask, 
     if (!dit_ready_) return fail("denoise_step: DiT weights not finalized");
     if (N > kMaxPos) return fail("denoise_step: sequence longer than the rope table (4096)");
     if (ws_bytes < denoise_ws_bytes(B, N, R, P, B)) return fail("denoise_step: workspace too small");
+    if (ws_misaligned(ws)) return fail("denoise_step: workspace must be 256-byte aligned");
     HIPC(hipSetDevice(device_));
     Bump bump(ws);
     ModWs m;
@@ -1553,6 +1558,7 @@ int Engine::sample_pinned(hipStream_t st, int mode, int n_steps, int cfg, float 
     if (n_steps < 1) return fail("sample: n_steps must be >= 1");
     if (N > kMaxPos) return fail("sample: sequence longer than the rope table (4096)");
     if (ws_bytes < sample_ws_bytes(B, N, R, P, n_steps, cfg)) return fail("sample: workspace too small");
+    if (ws_misaligned(ws)) return fail("sample: workspace must be 256-byte aligned");
     // pinned frames (kernels.hip pin_renoise / pin_update): validated before anything is enqueued; without them nothing below differs
     const bool pinned = x_pin != nullptr || pin != nullptr || start_step != 0;
     if (pinned) {
@@ -1967,6 +1973,7 @@ int Engine::codec_decode(hipStream_t st, const float* latents, int B, int T, flo
     if (!dec_.ready) return fail("codec_decode: decoder weights not finalized");
     const CodecPlan plan = codec_plan(true, B, T);
     if (ws_bytes < codec_ws_bytes(plan)) return fail("codec_decode: workspace too small");
+    if (ws_misaligned(ws)) return fail("codec_decode: workspace must be 256-byte aligned");
     HIPC(hipSetDevice(device_));
     Bump bump(ws);
     CodecWs w;
@@ -2071,6 +2078,7 @@ int Engine::codec_encode(hipStream_t st, const float* audio, int B, int S_, floa
     if (!enc_.ready) return fail("codec_encode: encoder weights not finalized");
     const CodecPlan plan = codec_plan(false, B, S_);
     if (ws_bytes < codec_ws_bytes(plan)) return fail("codec_encode: workspace too small");
+    if (ws_misaligned(ws)) return fail("codec_encode: workspace must be 256-byte aligned");
     HIPC(hipSetDevice(device_));
     Bump bump(ws);
     CodecWs w;
