@@ -15,7 +15,7 @@ from __future__ import annotations
 import collections
 import hashlib
 import os
-from typing import Callable, Dict, Iterable, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -628,6 +628,25 @@ class Voice:
     __delattr__ = __setattr__
 
 
+class _Batch(NamedTuple):
+    """One batch on the device, enqueued on the stream that was current when it was made; nothing here has been read back.
+    `rerun()` enqueues the same work again on the current stream (the fp16 range guard's second pass), the tap, the path and the
+    endpoints included when the record has them, and returns a new record; its closure keeps the batch's voices alive."""
+    audio: torch.Tensor                  # (B, 1, HOP_SIZE * Nmax) fp32; causal decoder => row b is its first HOP_SIZE * ns[b] samples
+    latents: torch.Tensor                # (B, Nmax, 64) fp32
+    mass: Optional[torch.Tensor]         # align=: the tapped text attention (engine.sample), else None
+    spans: Optional[torch.Tensor]        # align=: (B, P, 2) (first, last) frame per token (engine.align_path), else None
+    seg: Optional[torch.Tensor]          # endpoints: (B, 2) int64 (start, n) per row (engine.endpoints), else None
+    gain: Optional[torch.Tensor]         # endpoints: (B,) fp32, else None
+    ns: List[int]                        # frames per row
+    rerun: Callable[[], "_Batch"]
+
+
+def _rows(audio: np.ndarray, ns: Sequence[int]) -> List[np.ndarray]:
+    """A decoded batch on the host -> its rows (1, HOP_SIZE * n_b): the decoder is causal, so the prefixes are exact."""
+    return [audio[b, :, : HOP_SIZE * n] for b, n in enumerate(ns)]
+
+
 class SmallTTS:
     """DMD few-step synthesis: condition-encode -> n-step sampler -> codec decode, all on one MI355X."""
 
@@ -731,8 +750,6 @@ class SmallTTS:
         al = as_alignment(align)
         if al is None and (prefix_lens is not None or return_alignment):
             raise ValueError("synthesize_batch: prefix_lens= and return_alignment= belong to align=")
-        if ep is not None and _defer:
-            raise ValueError("synthesize_batch: trim= and _defer exclude each other (synthesize_long trims its batches itself)")
         if voices is not None:
             if ref_latents is not None:
                 raise ValueError("synthesize_batch: pass either ref_latents or voices (with ref_latents=None), not both")
@@ -781,89 +798,63 @@ class SmallTTS:
             if len(p0s) != B or any(p < 0 or p > ps[b] for b, p in enumerate(p0s)):
                 raise ValueError("synthesize_batch: prefix_lens needs one length in [0, tokens of the row] per row")
 
-        def run():
+        def run() -> _Batch:
             cache = eng.cond_encode(ref, np.asarray(rs, np.int64), ids, pm)
             if voices is not None:
                 cache.update(eng.voice_expand(voices))
             nz = noise if seeds is None else eng.randn_rows(seeds, ns, self.num_steps, n_max=Nm)
+            mass = spans = seg = gain = None
             if al is None:
-                x_ = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, **pin_kw)
-                return eng.codec_decode(x_), x_                # (B, 1, HOP * Nm); causal => prefixes are exact
-            # the tap and the path ride on this batch's stream behind its sampler; a re-run (fp16 range guard) recomputes them
-            x_, mass = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, align=al, **pin_kw)
-            spans = eng.align_path(mass, ns, p0s, ps)[0]
-            return eng.codec_decode(x_), (x_, mass, spans)
-
-        audio, x = run()
-        if _defer:                                             # synthesize_batches: stay on the device / stream
-            return audio, x, ns, run
-        if al is not None:
-            return self._batch_aligned(audio, x, run, ns, ps, p0s, phoneme_ids, ep, return_latents, return_alignment)
-        if ep is not None:
-            seg, gain, _e = eng.endpoints(audio, ns, ep)
-            seg_h = seg.cpu().numpy()                          # synchronises: the saturation counters are final
-            if eng.check_fp16_range("synthesize"):
-                audio, x = run()
+                x = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, **pin_kw)
+            else:
+                # the tap and the path ride on this batch's stream behind its sampler; a re-run (fp16 range guard) recomputes them
+                x, mass = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, align=al, **pin_kw)
+                spans = eng.align_path(mass, ns, p0s, ps)[0]
+            audio = eng.codec_decode(x)                        # (B, 1, HOP * Nm); causal => prefixes are exact
+            if ep is not None:                                 # behind the decode, on the same stream
                 seg, gain, _e = eng.endpoints(audio, ns, ep)
-                seg_h = seg.cpu().numpy()
-            offs, S = plan_packed(seg_h[:, 1], 0.0)
-            packed = torch.zeros(S, device=eng.device)
-            eng.stitch_seg(audio, seg, gain if ep.level_dbfs is not None else None, offs, None, packed)
-            packed = packed.cpu().numpy()
-            outs = [packed[None, offs[b]: offs[b] + int(seg_h[b, 1])] for b in range(B)]
-            if return_latents:
-                xl = x.cpu().numpy()
-                return outs, [xl[b, : ns[b]] for b in range(B)]
-            return outs
-        audio = audio.cpu().numpy()
-        if eng.check_fp16_range("synthesize"):                 # an fp16 operand clipped: the site is split-bf16 now, run again
-            audio, x = run()
-            audio = audio.cpu().numpy()
-        outs = [audio[b, :, : HOP_SIZE * ns[b]] for b in range(B)]
-        if return_latents:
-            xl = x.cpu().numpy()
-            return outs, [xl[b, : ns[b]] for b in range(B)]
-        return outs
+            return _Batch(audio, x, mass, spans, seg, gain, ns, run)
 
-    def _batch_aligned(self, audio, xa, run, ns, ps, p0s, phoneme_ids, ep, return_latents: bool, return_alignment: bool):
-        """synthesize_batch's tail with align=: the same outputs as without, plus the words (and the raw alignment)."""
+        rec = run()
+        if _defer:                                             # synthesize_batches / synthesize_long / the server: stay on the device / stream
+            return rec
+        return self._finish_batch(rec, ep, None if al is None else (phoneme_ids, p0s, ps), return_latents, return_alignment)
+
+    def _finish_batch(self, rec: _Batch, ep: Optional["Endpointing"], tokens: Optional[tuple], return_latents: bool,
+                      return_alignment: bool):
+        """synthesize_batch's tail: one batch from the device to what the call returns.  `tokens` = (token lists, prefix lengths, token
+        counts) with align=, else None.  -> rows[, latents][, words[, raw alignment]]; the rows alone are returned bare."""
         eng = self.engine
-        B = len(ns)
-        x, mass, spans = xa
-        seg_h = None
-        if ep is not None:
-            seg, gain, _e = eng.endpoints(audio, ns, ep)
-            seg_h = seg.cpu().numpy()                          # synchronises: the saturation counters are final
-            if eng.check_fp16_range("synthesize"):
-                audio, (x, mass, spans) = run()
-                seg, gain, _e = eng.endpoints(audio, ns, ep)
-                seg_h = seg.cpu().numpy()
-            offs, S = plan_packed(seg_h[:, 1], 0.0)
+        B = len(rec.ns)
+        head = (rec.audio if ep is None else rec.seg).cpu().numpy()   # synchronises: the saturation counters are final
+        if eng.check_fp16_range("synthesize"):                 # an fp16 operand clipped: the site is split-bf16 now, run again
+            rec = rec.rerun()
+            head = (rec.audio if ep is None else rec.seg).cpu().numpy()
+        if ep is None:
+            outs = _rows(head, rec.ns)
+        else:                                                  # cut and levelled on the device: only the windows are copied out
+            offs, S = plan_packed(head[:, 1], 0.0)
             packed = torch.zeros(S, device=eng.device)
-            eng.stitch_seg(audio, seg, gain if ep.level_dbfs is not None else None, offs, None, packed)
+            eng.stitch_seg(rec.audio, rec.seg, rec.gain if ep.level_dbfs is not None else None, offs, None, packed)
             packed = packed.cpu().numpy()
-            outs = [packed[None, offs[b]: offs[b] + int(seg_h[b, 1])] for b in range(B)]
-        else:
-            audio_h = audio.cpu().numpy()
-            if eng.check_fp16_range("synthesize"):             # an fp16 operand clipped: the site is split-bf16 now, run again
-                audio, (x, mass, spans) = run()
-                audio_h = audio.cpu().numpy()
-            outs = [audio_h[b, :, : HOP_SIZE * ns[b]] for b in range(B)]
-        spans_h = spans.cpu().numpy()                          # B * P * 2 ints: the only read-back the timings need
-        words = []
-        for b in range(B):
-            groups = token_groups(list(phoneme_ids[b])[p0s[b]:ps[b]])
-            win = None if seg_h is None else (int(seg_h[b, 0]), int(seg_h[b, 1]))
-            words.append(word_times(groups, spans_h[b], ns[b], token0=p0s[b], window=win))
+            outs = [packed[None, offs[b]: offs[b] + int(head[b, 1])] for b in range(B)]
         res = [outs]
         if return_latents:
-            xl = x.cpu().numpy()
-            res.append([xl[b, : ns[b]] for b in range(B)])
-        res.append(words)
-        if return_alignment:
-            mh = mass.cpu().numpy()
-            res.append([(mh[b, : ns[b], : ps[b]], spans_h[b, : ps[b]]) for b in range(B)])
-        return tuple(res)
+            xl = rec.latents.cpu().numpy()
+            res.append([xl[b, : rec.ns[b]] for b in range(B)])
+        if tokens is not None:
+            phoneme_ids, p0s, ps = tokens
+            spans_h = rec.spans.cpu().numpy()                  # B * P * 2 ints: the only read-back the timings need
+            words = []
+            for b in range(B):
+                groups = token_groups(list(phoneme_ids[b])[p0s[b]:ps[b]])
+                win = None if ep is None else (int(head[b, 0]), int(head[b, 1]))
+                words.append(word_times(groups, spans_h[b], rec.ns[b], token0=p0s[b], window=win))
+            res.append(words)
+            if return_alignment:
+                mh = rec.mass.cpu().numpy()
+                res.append([(mh[b, : rec.ns[b], : ps[b]], spans_h[b, : ps[b]]) for b in range(B)])
+        return outs if len(res) == 1 else tuple(res)
 
     def synthesize_batches(self, batches: Sequence[tuple], in_flight: int = 3, release_workspaces: bool = False) -> List[list]:
         """Several independent batches, `in_flight` of them overlapping on the GPU.
@@ -876,19 +867,17 @@ class SmallTTS:
             return [self.synthesize_batch(*b) for b in batches]
         eng, dev = self.engine, self.engine.device
         pending = self._run_in_flight([lambda b=b: self.synthesize_batch(*b, _defer=True) for b in batches], in_flight)
-        outs = []
-        for audio, _, ns, _run in pending:
-            a = audio.cpu().numpy()
-            outs.append([a[b, :, : HOP_SIZE * ns[b]] for b in range(len(ns))])
+        outs = [_rows(rec.audio.cpu().numpy(), rec.ns) for rec in pending]
         if release_workspaces:
             torch.cuda.synchronize(dev)
             eng.release_workspaces()
         return outs
 
-    def _run_in_flight(self, calls: Sequence[Callable[[], tuple]], in_flight: int) -> List[tuple]:
-        """The machinery of synthesize_batches: calls[i]() enqueues one deferred synthesize_batch; call i runs whole on HIP stream
-        i % in_flight with its own workspace under throughput tuning.  Returns the finished (audio, latents, ns, run) tuples, on the
-        device, after the fp16 range guard has been honoured."""
+    def _run_in_flight(self, calls: Sequence[Callable[[], _Batch]], in_flight: int) -> List[_Batch]:
+        """The machinery of synthesize_batches: calls[i]() enqueues one deferred batch and returns its record; call i runs whole on
+        HIP stream i % in_flight with its own workspace under throughput tuning.  Returns the finished records, on the device, after
+        the fp16 range guard has been honoured.  The guard's re-run happens after the caller's tuning and workspace have been
+        restored: every batch again, one at a time, on the current stream — under the CALLER's tuning, not under throughput."""
         eng = self.engine
         dev = eng.device
         cur = torch.cuda.current_stream(dev)
@@ -911,7 +900,7 @@ class SmallTTS:
             cur.wait_stream(st)
         torch.cuda.synchronize(dev)
         if eng.check_fp16_range("synthesize_batches"):         # clipped somewhere: every batch again, one at a time, at the demoted precision
-            pending = [(*run(), ns, run) for _a, _x, ns, run in pending]
+            pending = [rec.rerun() for rec in pending]
         return pending
 
     def synthesize_long(self, voice: Voice, text: Optional[str] = None, *, token_lists: Optional[Sequence[Sequence[int]]] = None,
@@ -972,25 +961,30 @@ class SmallTTS:
         ns = [_frames(d) for d in durations]
         eng = self.engine
         groups, offsets, S = plan_long(ns, max_batch, gap_ms)
+
+        def result(out, segs, words, made):                    # words None: not aligned
+            res = ((out,) + ((segs,) if return_segments else ()) + ((words,) if words is not None else ())
+                   + ((made,) if return_pieces else ()))
+            return res if len(res) > 1 else out
+
         if not toks:
-            empty = np.zeros((1, 0), np.int16 if pcm16 else np.float32)
-            res = (empty,) + (([],) if return_segments else ()) + (([],) if return_words else ()) + (([],) if return_pieces else ())
-            return res if len(res) > 1 else empty
+            return result(np.zeros((1, 0), np.int16 if pcm16 else np.float32), [], [] if return_words else None, [])
         base = self._next_seed() if seed is None else int(seed)
         seeds = [piece_seed(base, i) for i in range(len(toks))]
+        # with trim every batch enqueues its endpoints behind its decode, on its own stream: they overlap the other batches in flight
         calls = [lambda g=g: self.synthesize_batch(None, [toks[i] for i in g], None, frames=[ns[i] for i in g], voices=[voice] * len(g),
-                                                   seeds=[seeds[i] for i in g], _defer=True,
+                                                   seeds=[seeds[i] for i in g], trim=ep, _defer=True,
                                                    **({} if al is None else {"align": al, "prefix_lens": [len(prefix)] * len(g)}))
                  for g in groups]
         out, segs, pending = self._join_long(calls, groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16)
-        res = (out,) + ((segs,) if return_segments else ())
+        words = made = None
         piece_spans: List[Optional[np.ndarray]] = [None] * len(toks)
         if al is not None:
             # one small read-back for the whole text: every batch's (B, P, 2) span table, flattened
-            flat = torch.cat([p[1][2].reshape(-1) for p in pending]).cpu().numpy()
+            flat = torch.cat([rec.spans.reshape(-1) for rec in pending]).cpu().numpy()
             words, pos = [], 0
-            for g, p in zip(groups, pending):
-                Pg = int(p[1][2].shape[1])
+            for g, rec in zip(groups, pending):
+                Pg = int(rec.spans.shape[1])
                 sp = flat[pos: pos + len(g) * Pg * 2].reshape(len(g), Pg, 2)
                 pos += len(g) * Pg * 2
                 for r, i in enumerate(g):
@@ -998,36 +992,42 @@ class SmallTTS:
                     piece_spans[i] = sp[r, : len(toks[i])]
                     words += word_times(token_groups(toks[i][len(prefix):]), sp[r], ns[i], token0=len(prefix),
                                         window=(start_i, n_i) if ep is not None else None, offset=off, index0=len(words))
-            res += (words,)
         if return_pieces:
             # one read-back for the whole text: every batch's latents, flattened
-            xs = [p[1][0] if al is not None else p[1] for p in pending]
-            flat = torch.cat([x.reshape(-1) for x in xs]).cpu().numpy()
+            flat = torch.cat([rec.latents.reshape(-1) for rec in pending]).cpu().numpy()
             made, pos = [], 0
-            for g, x in zip(groups, xs):
-                Ng = int(x.shape[1])
+            for g, rec in zip(groups, pending):
+                Ng = int(rec.latents.shape[1])
                 xg = flat[pos: pos + len(g) * Ng * 64].reshape(len(g), Ng, 64)
                 pos += len(g) * Ng * 64
                 made += [Piece(toks[i], len(prefix), xg[r, : ns[i]], seeds[i], piece_spans[i]) for r, i in enumerate(g)]
-            res += (made,)
-        return res if len(res) > 1 else out
+        return result(out, segs, words, made)
 
     def _join_long(self, calls, groups, ns, offsets, S, ep: Optional["Endpointing"], in_flight: int, gap_ms: float, fade_ms: float,
                    pcm16: bool):
         """The tail synthesize_long and render_long share: the deferred batches `calls` (one per group) run through _run_in_flight,
-        their rows are joined on the device (with `ep`: at their speech windows) and copied out once.
-        -> (waveform (1, S), segments, the finished batches)."""
+        their rows are joined on the device and copied out once.  With `ep` the records carry their endpoints (every batch enqueued
+        them behind its decode, and so does its re-run): the tables are read back once and the join puts the speech windows `gap_ms`
+        apart, which replaces `offsets` and `S`.  -> (waveform (1, S), segments, the finished batches)."""
         eng = self.engine
-        if ep is not None:
-            return self._long_trimmed(calls, groups, ep, in_flight, gap_ms, fade_ms, pcm16)
         pending = self._run_in_flight(calls, in_flight)
+        if ep is not None:
+            seg_h = torch.cat([rec.seg for rec in pending]).cpu().numpy()     # one small read-back: 16 bytes per piece ...
+            gain_h = torch.cat([rec.gain for rec in pending]).cpu().numpy()   # ... and 4
+            offsets, S = plan_packed(seg_h[:, 1], gap_ms)
+            segs = [(int(offsets[i]), int(seg_h[i, 1]), int(seg_h[i, 0]), float(gain_h[i])) for i in range(len(ns))]
+        else:
+            segs = [(offsets[i], HOP_SIZE * ns[i], 0, 1.0) for i in range(len(ns))]
         out = torch.zeros(S, dtype=torch.int16 if pcm16 else torch.float32, device=eng.device)
         w = fade_table(fade_ms)
         fade = torch.from_numpy(w).to(eng.device) if w.size else None
-        for g, (audio, _x, g_ns, _run) in zip(groups, pending):
-            eng.stitch(audio, g_ns, [offsets[i] for i in g], fade, out)
-        out = out.cpu().numpy()[None]
-        return out, [(offsets[i], HOP_SIZE * ns[i], 0, 1.0) for i in range(len(ns))], pending
+        for g, rec in zip(groups, pending):
+            offs = [offsets[i] for i in g]
+            if ep is None:
+                eng.stitch(rec.audio, rec.ns, offs, fade, out)
+            else:
+                eng.stitch_seg(rec.audio, rec.seg, rec.gain if ep.level_dbfs is not None else None, offs, fade, out)
+        return out.cpu().numpy()[None], segs, pending
 
     def render_long(self, pieces, *, gap_ms: float = 120.0, fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3,
                     pcm16: bool = False, trim=None, return_segments: bool = False):
@@ -1047,22 +1047,20 @@ class SmallTTS:
             return (empty, []) if return_segments else empty
         eng = self.engine
 
-        def deferred(g):
+        def decode_only(g):
             g_ns = [ns[i] for i in g]
             lat = np.zeros((len(g), max(g_ns), 64), np.float32)
             for r, i in enumerate(g):
                 lat[r, : ns[i]] = lats[i]
 
-            def run():
+            def run() -> _Batch:
                 x = torch.from_numpy(lat).to(eng.device)
-                return eng.codec_decode(x), x
+                audio = eng.codec_decode(x)
+                seg, gain = eng.endpoints(audio, g_ns, ep)[:2] if ep is not None else (None, None)
+                return _Batch(audio, x, None, None, seg, gain, g_ns, run)
+            return run
 
-            def go():
-                audio, x = run()
-                return audio, x, g_ns, run
-            return go
-
-        out, segs, _pending = self._join_long([deferred(g) for g in groups], groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16)
+        out, segs, _pending = self._join_long([decode_only(g) for g in groups], groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16)
         return (out, segs) if return_segments else out
 
     def respeak(self, tokens: Sequence[int], latents, frames: Tuple[int, int], *, voice: Optional[Voice] = None, ref_latents=None,
@@ -1109,39 +1107,6 @@ class SmallTTS:
                                     **({} if al is None else {"align": al, "prefix_lens": [int(prefix_len)],
                                                               "return_alignment": bool(return_alignment)}))
         return (res[0][0], res[1][0]) + (tuple(r[0] for r in res[2:]) if al is not None else ())
-
-    def _long_trimmed(self, calls, groups, ep: "Endpointing", in_flight: int, gap_ms: float, fade_ms: float, pcm16: bool):
-        """synthesize_long's trimmed join -> (waveform, segments, the finished batches).  Every deferred batch enqueues its endpoints
-        behind its decode, on its own stream, so they overlap the other batches in flight; the fp16 range guard's re-run goes through
-        the same wrapper and so recomputes them."""
-        eng = self.engine
-
-        def with_endpoints(run, g_ns):            # what _run_in_flight calls again when the range guard fires: (audio', latents)
-            def run2():
-                audio, x = run()
-                return (audio, eng.endpoints(audio, g_ns, ep)[:2]), x
-            return run2
-
-        def deferred(call):
-            def go():
-                audio, x, g_ns, run = call()
-                return (audio, eng.endpoints(audio, g_ns, ep)[:2]), x, g_ns, with_endpoints(run, g_ns)
-            return go
-
-        pending = self._run_in_flight([deferred(c) for c in calls], in_flight)
-        seg_d = [p[0][1][0] for p in pending]
-        gain_d = [p[0][1][1] for p in pending]
-        seg_h = torch.cat(seg_d).cpu().numpy()                  # one small read-back: 16 bytes per piece ...
-        gain_h = torch.cat(gain_d).cpu().numpy()                # ... and 4
-        offsets, S = plan_packed(seg_h[:, 1], gap_ms)
-        out = torch.zeros(S, dtype=torch.int16 if pcm16 else torch.float32, device=eng.device)
-        w = fade_table(fade_ms)
-        fade = torch.from_numpy(w).to(eng.device) if w.size else None
-        level = ep.level_dbfs is not None
-        for g, p, sd, gd in zip(groups, pending, seg_d, gain_d):
-            eng.stitch_seg(p[0][0], sd, gd if level else None, [offsets[i] for i in g], fade, out)
-        out = out.cpu().numpy()[None]
-        return out, [(int(offsets[i]), int(seg_h[i, 1]), int(seg_h[i, 0]), float(gain_h[i])) for i in range(len(offsets))], pending
 
     def synthesize_sharded(self, ref_latents: Sequence[np.ndarray], phoneme_ids: Sequence[Sequence[int]],
                            duration_sec: float, *, max_batch: int = 8) -> np.ndarray:

@@ -340,10 +340,10 @@ class Batcher:
                             for b, r in enumerate(g_ok):
                                 for s_ in range(self.steps):
                                     noise[s_, b, :g_ns[b]] = self.eng.randn(g_ns[b] * LATENT, r.seed, s_).view(g_ns[b], LATENT)
-                            audio, xa, _, _ = self.tts.synthesize_batch(g_refs, [r.tokens for r in g_ok], [r.duration for r in g_ok],
-                                                                        noise=noise, frames=g_ns, _defer=True,
-                                                                        **({"align": True} if g_align else {}))
-                            spans = xa[2] if g_align else None    # (B, P, 2) token spans, found on this stream behind the sampler
+                            rec = self.tts.synthesize_batch(g_refs, [r.tokens for r in g_ok], [r.duration for r in g_ok],
+                                                            noise=noise, frames=g_ns, _defer=True,
+                                                            **({"align": True} if g_align else {}))
+                            audio, spans = rec.audio, rec.spans   # spans: (B, P, 2) per token, found on this stream behind the sampler
                             # endpoints behind the decode, on the batch's stream: one pair of launches per distinct setting
                             ends = {ep: self.eng.endpoints(audio, g_ns, ep)[:2] for ep in {r.trim for r in g_ok if r.trim is not None}}
                             ev = torch.cuda.Event()

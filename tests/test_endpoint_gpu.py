@@ -287,7 +287,7 @@ def test_synthesize_long_endpoints_of_a_decoded_batch(eng, tts, voice):
     """Check 6 on whatever the synthetic model decodes, default Endpointing and a levelled one, straight on the device batch."""
     toks = [[1, 2, 3, 4], [10, 20, 30, 40, 50, 60], [7] * 9]
     ns = [7, 16, 11]
-    audio, _x, _ns, _run = tts.synthesize_batch(None, toks, None, frames=ns, voices=[voice] * 3, seeds=[5, 6, 7], _defer=True)
+    audio = tts.synthesize_batch(None, toks, None, frames=ns, voices=[voice] * 3, seeds=[5, 6, 7], _defer=True).audio
     host = audio.cpu().numpy()
     rows = [(host[b, 0].copy(), HOP_SIZE * ns[b]) for b in range(3)]
     for ep in (Endpointing(), Endpointing(level_dbfs=-23), Endpointing(level_dbfs=-20, **SHARP)):
