@@ -137,36 +137,10 @@ def test_swiglu(eng, M, F, K):
     assert err < 3e-5, f"swiglu no-bias: {err:.3e}"
 
 
-def _attn_ref(qkvg, qw, kw, eps, rope, rot, H, dh, kr, vr, kt, vt, ms, mr, mt):
-    """torch restatement of dit.py:95-119 on raw projections (fp64)."""
-    B, N, _ = qkvg.shape
-    D = H * dh
-    x = qkvg.double()
-    q, k, v, g = (x[..., i * D:(i + 1) * D].reshape(B, N, H, dh) for i in range(4))
-    rms = lambda t, w: t * torch.rsqrt(t.pow(2).mean(-1, keepdim=True) + eps) * w.double()
-    q, k = rms(q, qw), rms(k, kw)
-
-    def rot_pairs(t):
-        a = rope.double()[:N, :rot][None, :, None, 0::2]
-        te, to = t[..., 0:rot:2], t[..., 1:rot:2]
-        out = t.clone()
-        out[..., 0:rot:2] = te * a.cos() - to * a.sin()
-        out[..., 1:rot:2] = to * a.cos() + te * a.sin()
-        return out
-    q, k = rot_pairs(q).transpose(1, 2), rot_pairs(k).transpose(1, 2)
-    v = v.transpose(1, 2)
-    keys, vals, masks = [k], [v], [ms if ms is not None else torch.ones(B, N, dtype=torch.bool)]
-    for kk, vv, mm in ((kr, vr, mr), (kt, vt, mt)):
-        if kk is not None:
-            keys.append(kk.double()); vals.append(vv.double())
-            masks.append(mm if mm is not None else torch.ones(B, kk.shape[2], dtype=torch.bool))
-    K, V, Mk = torch.cat(keys, 2), torch.cat(vals, 2), torch.cat(masks, 1)
-    s = q @ K.transpose(-1, -2) / dh ** 0.5
-    s = s.masked_fill(~Mk[:, None, None, :], float("-inf"))
-    p = torch.softmax(s, -1)
-    p = torch.nan_to_num(p, nan=0.0)
-    o = (p @ V).transpose(1, 2).reshape(B, N, D)
-    return o * torch.sigmoid(g.reshape(B, N, D))
+def _attn_ref(*args):
+    """torch restatement of dit.py:95-119 on raw projections (fp64): tests/helpers/attn_ref.py exact(), shared with the edge-case tests"""
+    from tests.helpers.attn_ref import exact
+    return exact(*args)[0]
 
 
 @pytest.mark.parametrize("B,N,H,dh,rot,R,P", [(2, 75, 8, 120, 64, 15, 30), (3, 21, 8, 64, 64, 0, 0),
@@ -174,6 +148,11 @@ def _attn_ref(qkvg, qw, kw, eps, rope, rot, H, dh, kr, vr, kt, vt, ms, mr, mt):
                                              (1, 5, 8, 120, 64, 3, 2), (16, 75, 8, 120, 64, 15, 30)])   # last: resident-K/V form
 @pytest.mark.parametrize("mfma", [False, "img:bf16x3", "img:f16", "img:bf16"])
 def test_attention(eng, B, N, H, dh, rot, R, P, mfma):
+    """The four attention kernels against the fp64 restatement, one rel-L2 over the whole tensor, on Gaussian projections with norm
+    weights near 1.  What that does NOT cover: these logits stay within about +-5 (no probability above 0.3, no rescale below e^-9),
+    the masks are valid-prefix / masked-tail only, and a single wrong row (one pad column counted as a key moves a row by ~1 / Ktot)
+    is far below the bars.  Peaked logits, dead chunks, masked decoys and pad columns are held per element, against the operands as
+    the kernel holds them, in tests/test_attention_edges_gpu.py (references and bound: tests/helpers/attn_ref.py)."""
     D = H * dh
     qkvg = _rand(B, N, 4 * D, seed=20)
     qw, kw = 1 + 0.2 * _rand(H, dh, seed=21), 1 + 0.2 * _rand(H, dh, seed=22)
