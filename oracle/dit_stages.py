@@ -30,8 +30,87 @@ def _d(w, name):
     return w[name].to(torch.float64)
 
 
-def _lin(w, name, x, bias=True):
-    y = x @ _d(w, name + ".weight").t()
+# ---- the rounding stand-in (default off) ----------------------------------------------------------------------------------------
+# Engine::Site (engine.hpp) by weight name; presets as Engine::set_precision assigns them (SITE_COND stays split-bf16 under f16)
+SITE_FMT = {"bf16x3": dict(dit_block="bf16x3", encoder="bf16x3", cross_kv="bf16x3", cond="bf16x3"),
+            "f16": dict(dit_block="f16", encoder="f16", cross_kv="f16", cond="bf16x3"),
+            "bf16": dict(dit_block="bf16", encoder="bf16", cross_kv="bf16", cond="bf16")}
+_ROUND = None   # the active Rounding, or None: _lin is the plain fp64 product
+
+
+def site_of(name: str) -> str:
+    """the Engine::Site whose GEMM reads the linear `name` (no trailing .weight)"""
+    if name.startswith("dit.transformer_blocks."):
+        leaf = name.split(".", 3)[3]
+        if leaf == "attn_norm.linear":
+            return "cond"
+        if leaf.startswith(("attn.to_k_ref", "attn.to_v_ref", "attn.to_k_text", "attn.to_v_text")):
+            return "cross_kv"
+        return "dit_block"
+    if ".blocks." in name or name in ("style_encoder.out_proj", "dit.phoneme_proj"):
+        return "encoder"
+    return "cond"   # time MLP, emb_proj, norm_out, the latent in-projection, the velocity head, the style in-projection
+
+
+class Rounding:
+    """While active (`with Rounding(preset):`) _lin rounds BOTH operands of every product to the format the preset assigns to the
+    site of that weight name (f16: RNE saturating at +-65504; bf16; split hi + lo without the lo x lo product), through round_fmt of
+    tests/helpers/attn_ref.py, and forms the product in fp64.  One instance serves one weight dict (the rounded weights are kept by
+    name); amax[site] is the largest |operand| a site has seen.
+
+    This is a CONDITIONING PROXY built from the reference alone: it says how much harder a weight family or an input makes the
+    same stage for operands of that width, relative to another family.  It is no model of the kernels: it rounds neither the
+    attention images (q, k, V^T, the gate, P) nor the conv pos-embed, knows nothing of fp32 accumulation order or of the fp32
+    residual stream, and does not form the LN-fold's (x - c)(1 + scale) image."""
+
+    def __init__(self, preset: str):
+        self.fmt = SITE_FMT[preset]
+        self.wcache: Dict[str, tuple] = {}
+        self.amax: Dict[str, float] = {}
+
+    def __enter__(self):
+        global _ROUND
+        self.prev, _ROUND = _ROUND, self
+        return self
+
+    def __exit__(self, *exc):
+        global _ROUND
+        _ROUND = self.prev
+
+    @staticmethod
+    def off():
+        """`with Rounding.off():` the plain fp64 product inside an active Rounding"""
+        return _Off()
+
+    def product(self, w, name, x):
+        from tests.helpers.attn_ref import round_fmt
+        site = site_of(name)
+        fmt = self.fmt[site]
+        if name not in self.wcache:
+            self.wcache[name] = round_fmt(_d(w, name + ".weight"), fmt)
+        wh, wl = self.wcache[name]
+        xh, xl = round_fmt(x, fmt)
+        self.amax[site] = max(self.amax.get(site, 0.0), float(x.abs().max()) if x.numel() else 0.0, float(wh.abs().max()))
+        y = xh @ wh.t()
+        return y + xl @ wh.t() + xh @ wl.t() if fmt == "bf16x3" else y
+
+
+class _Off:
+    def __enter__(self):
+        global _ROUND
+        self.prev, _ROUND = _ROUND, None
+
+    def __exit__(self, *exc):
+        global _ROUND
+        _ROUND = self.prev
+
+
+def _lin(w, name, x, bias=True, col_shift=0):
+    """col_shift != 0 (near miss): the weight image moved by that many input columns"""
+    if col_shift:
+        y = x @ _d(w, name + ".weight").roll(col_shift, 1).t()
+    else:
+        y = x @ _d(w, name + ".weight").t() if _ROUND is None else _ROUND.product(w, name, x)
     return y + _d(w, name + ".bias") if bias else y
 
 
@@ -151,6 +230,23 @@ def adaln_unshifted_f16(x, shift, scale):
     return (img - mu * (1 + scale[:, None])) * rstd + shift[:, None]
 
 
+def adaln_fold_term_dropped(x, shift, scale):
+    """near miss of the LN-fold epilogue rstd (acc - (mu - c) tab1) + tab0 + b without its (mu - c) tab1 term, c the previous row's
+    mean (row 0: its own): every product W y of the image gains rstd (mu - c) W (1 + scale), stated here on y itself"""
+    mu = x.mean(-1, keepdim=True)
+    rstd = 1 / torch.sqrt(((x - mu) ** 2).mean(-1, keepdim=True) + 1e-6)
+    c = torch.cat([mu[:, :1], mu[:, :-1]], 1)
+    return adaln(x, shift, scale) + rstd * (mu - c) * (1 + scale[:, None])
+
+
+def adaln_scale_only(x, shift, scale):
+    """near miss: scale in place of 1 + scale"""
+    return layer_norm(x) * scale[:, None] + shift[:, None]
+
+
+SLIP_NORMS = {"fold_term_dropped": adaln_fold_term_dropped, "scale_only": adaln_scale_only}
+
+
 def block_mod(rows, l):
     """(sh_a, sc_a, tanh g_a, sh_m, sc_m, tanh g_m) of block l, each (B, 960), from the per-utterance modulation rows"""
     m = rows[:, l * MOD_PER_BLOCK:(l + 1) * MOD_PER_BLOCK]
@@ -163,19 +259,25 @@ def final_mod(rows, swap=False):
     return (sc, sh) if swap else (sh, sc)
 
 
-def dit_block(w, l, x, mask, rows, cache, ang=None, q_scale=None, rope_layout="pairs", unshifted_f16=False):
+def dit_block(w, l, x, mask, rows, cache, ang=None, q_scale=None, rope_layout="pairs", unshifted_f16=False, slip=None):
     """x (B, N, 960) -> x after block l.  cache: k_ref / v_ref (L, B, H, R, 120), ref_mask (B, R), k_text / v_text, ph_mask.
-    q_scale, rope_layout, unshifted_f16: near misses"""
+    q_scale, rope_layout, unshifted_f16: near misses; slip: one more, by name (a key of SLIP_NORMS: that AdaLN; "swap_qk_norm": the
+    two head-norm weights exchanged; "abs_head_norm": |w| for w in both; "w2_col_shift": ff.w2 moved by one input column)"""
     B, N, _ = x.shape
     p = f"dit.transformer_blocks.{l}"
     sh_a, sc_a, g_a, sh_m, sc_m, g_m = block_mod(rows, l)
-    norm = adaln_unshifted_f16 if unshifted_f16 else adaln
+    norm = adaln_unshifted_f16 if unshifted_f16 else SLIP_NORMS.get(slip, adaln)
     y = norm(x, sh_a, sc_a)
     q = _lin(w, f"{p}.attn.to_q", y).reshape(B, N, HEADS, DH)
     k = _lin(w, f"{p}.attn.to_k_self", y).reshape(B, N, HEADS, DH)
     v = _lin(w, f"{p}.attn.to_v_self", y).reshape(B, N, HEADS, DH)
-    q = rms_norm(q, _d(w, f"{p}.attn.q_norm.weight"), 1e-6)
-    k = rms_norm(k, _d(w, f"{p}.attn.k_norm.weight"), 1e-6)
+    qn, kn = _d(w, f"{p}.attn.q_norm.weight"), _d(w, f"{p}.attn.k_norm.weight")
+    if slip == "swap_qk_norm":
+        qn, kn = kn, qn
+    if slip == "abs_head_norm":
+        qn, kn = qn.abs(), kn.abs()
+    q = rms_norm(q, qn, 1e-6)
+    k = rms_norm(k, kn, 1e-6)
     a = rope_half_angles(N, ROPE_DIM) if ang is None else ang
     if rope_layout == "pairs":
         rot = lambda z: torch.cat([rotate_pairs(z[..., :ROPE_DIM], a[None, :, None, :]), z[..., ROPE_DIM:]], -1)
@@ -200,7 +302,7 @@ def dit_block(w, l, x, mask, rows, cache, ang=None, q_scale=None, rope_layout="p
     o = _lin(w, f"{p}.attn.to_out.0", o, False) * mask.to(torch.float64)[..., None]
     x = x + g_a[:, None] * o
     h = norm(x, sh_m, sc_m)
-    ff = _lin(w, f"{p}.ff.w2", silu(_lin(w, f"{p}.ff.w1", h)) * _lin(w, f"{p}.ff.w3", h))
+    ff = _lin(w, f"{p}.ff.w2", silu(_lin(w, f"{p}.ff.w1", h)) * _lin(w, f"{p}.ff.w3", h), col_shift=int(slip == "w2_col_shift"))
     return x + g_m[:, None] * ff
 
 
@@ -213,8 +315,8 @@ def next_image(x, rows, l1, swap=False):
     return adaln(x, sh, sc)
 
 
-def head(w, img, bias=True):
-    return _lin(w, "velocity", img, bias)
+def head(w, img, bias=True, col_shift=0):
+    return _lin(w, "velocity", img, bias, col_shift)
 
 
 # ---- encoders ---------------------------------------------------------------------------------------------------------------
@@ -262,15 +364,16 @@ def enc_out(w, net, img, key_mask):
     return y * key_mask.to(torch.float64)[..., None]
 
 
-def cross_kv(w, net, seq, knorm=True):
-    """-> K, V (12, B, 8, S, 120): to_k / to_v of every DiT block, K through k_norm_cross (dit.py:80-93; knorm=False: near miss)"""
+def cross_kv(w, net, seq, knorm=True, knorm_name="k_norm_cross"):
+    """-> K, V (12, B, 8, S, 120): to_k / to_v of every DiT block, K through k_norm_cross (dit.py:80-93; knorm=False and
+    knorm_name="k_norm", the self keys' weight: near misses)"""
     tag = "ref" if net == "style" else "text"
     B, S, _ = seq.shape
     ks, vs = [], []
     for i in range(NBLK):
         p = f"dit.transformer_blocks.{i}.attn"
         k = _lin(w, f"{p}.to_k_{tag}", seq).reshape(B, S, HEADS, DH)
-        ks.append((rms_norm(k, _d(w, f"{p}.k_norm_cross.weight"), 1e-6) if knorm else k).transpose(1, 2))
+        ks.append((rms_norm(k, _d(w, f"{p}.{knorm_name}.weight"), 1e-6) if knorm else k).transpose(1, 2))
         vs.append(_lin(w, f"{p}.to_v_{tag}", seq).reshape(B, S, HEADS, DH).transpose(1, 2))
     return torch.stack(ks), torch.stack(vs)
 

@@ -1307,6 +1307,7 @@ int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0,
         f.wsh = frow + off;
         f.wc = frow + kFoldNF + off;
         f.cshift = lnc;
+        f.nh = kFF;
         return f;
     };
     for (int l = l0; l < l1; ++l) {
@@ -2480,7 +2481,7 @@ int Engine::test_ln_fold(hipStream_t st, const float* A, const float* Wp, const 
             LNF(gemm3_resid_ln(ops3(SplitBuf{a_hi, a_lo}, rowmap_plain(K), wp, M, prec), p, prec, st));
             LnFoldIn fin;
             fin.part = part; fin.NP = NP; fin.inv_c = 1.0f / D; fin.eps = eps; fin.rms = rms;
-            if (!rms) { fin.wsh = tab; fin.wc = tab + 2 * F; fin.cshift = csh; }
+            if (!rms) { fin.wsh = tab; fin.wc = tab + 2 * F; fin.cshift = csh; fin.nh = F; }
             sw.fold = fin;
         } else {
             EpiResid<0> r{x, rd, bp, gate, 0, 0, 0, M, mask};

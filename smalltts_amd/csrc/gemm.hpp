@@ -249,6 +249,9 @@ struct LnFoldIn {
     int m0 = 0;                    // set by the kernel: first row of the tile
     float* cshift = nullptr;       // [M] the producer's row shift c (LayerNorm only, else null): the n-tile-0 workgroup adds the
                                    //    row's mu to it, so that the NEXT producer images the row around its current mean
+    int nh = 0x7fffffff;           // SwiGLU consumer: hidden units wc / wsh hold.  The last column tile runs past them (2400 -> 2432)
+                                   //    and must not read entries past the tables: block 11's lie behind the END of wc, where
+                                   //    whatever follows in the workspace (NaN, huge) became clamp counts of columns nobody stores
 };
 template <class E, class = void>
 struct epi_small_n { static constexpr bool value = false; };   // epilogues of the DiT's N = 960 residual projections: extra tile shapes / ring depths are instantiated for them only
@@ -399,6 +402,7 @@ struct EpiSwiGLUT {
     }
     // packed [w1 | w3] column indices of hidden unit nh (32-column groups interleaved: Engine swiglu_perm)
     __device__ __forceinline__ void fold_cols(int nh, float& c1, float& c3, float& v1, float& v3) const {
+        nh = nh < fold.nh ? nh : fold.nh - 1;   // (columns past the hidden width: any entry of the table, the result is not stored)
         const int p1 = (nh >> 5) * 64 + (nh & 31);
         if (fold.wc) {   // (uniform; null for the RMSNorm fold)
             c1 = fold.wc[p1]; c3 = fold.wc[p1 + 32];
