@@ -16,7 +16,6 @@
 #include "prof.hpp"
 #include <type_traits>
 
-extern int g_persist_mask;   // engine.hip: which persistent kernels the throughput-mode grid cap applies to (1 streamed FFN, 2 one-pass / wave FFN, 4 upsample)
 
 typedef float f32x2s __attribute__((ext_vector_type(2)));
 typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
@@ -506,7 +505,7 @@ __global__ __launch_bounds__(NW * 64) void codec_ffn_stream_kernel(FfnStreamArgs
 }
 
 template <int C, int SPLIT, int NW, int S>
-static hipError_t ffn_stream_go(const FfnStreamArgs& a, hipStream_t st) {
+static hipError_t ffn_stream_go(const FfnStreamArgs& a, hipStream_t st, const LaunchTuning& tu) {
     constexpr int NARR = SPLIT == 3 ? 2 : 1;
     constexpr size_t lds = (size_t)S * NARR * 128 * C + (size_t)7 * C * 4;
     static_assert(lds <= 160 * 1024, "ring exceeds LDS");
@@ -517,7 +516,7 @@ static hipError_t ffn_stream_go(const FfnStreamArgs& a, hipStream_t st) {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }, &cus);
     if (e != hipSuccess) return e;
-    if (!(g_persist_mask & 1)) cus = once.real_cus();   // (A/B: which persistent kernels the throughput-mode grid cap applies to)
+    cus = persist_grid_cus(tu, PERSIST_FFN_STREAM, cus);
     const int npass = (a.M + NW * 32 - 1) / (NW * 32);
     // NW = 4 (one wave per SIMD per workgroup): two workgroups share a CU when the ring is small enough — their steps drift
     // freely against each other, only the four waves of one ring meet at its barrier
@@ -530,7 +529,7 @@ static hipError_t ffn_stream_go(const FfnStreamArgs& a, hipStream_t st) {
 // C in {128, 256}; w1 [F][C] split bf16, w2t tile-major [F/32][C][32] split bf16 (launch_w2_tile_pack)
 hipError_t launch_codec_ffn_stream(float* x, RowMap img, const float* norm_w, const bf16_t* w1hi, const bf16_t* w1lo,
                                    const float* b1, const bf16_t* w2thi, const bf16_t* w2tlo, const float* b2, const float* gamma,
-                                   int M, int C, int F, float eps, int split, hipStream_t st) {
+                                   int M, int C, int F, float eps, int split, hipStream_t st, const LaunchTuning& tu) {
     if (!(C == 128 || C == 256) || F != 4 * C || img.ld % 4 || img.off % 4 || (img.rpb && img.bstride % 4)) return hipErrorInvalidValue;
     if (M <= 0) return hipSuccess;
     FfnStreamArgs a{x, img, norm_w, w1hi, w1lo, b1, w2thi, w2tlo, b2, gamma, M, eps};
@@ -544,8 +543,8 @@ hipError_t launch_codec_ffn_stream(float* x, RowMap img, const float* norm_w, co
 #ifndef FS_S256
 #define FS_S256 4
 #endif
-    if (C == 128) return split == 3 ? ffn_stream_go<128, 3, 8, 4>(a, st) : split == PREC_F16 ? ffn_stream_go<128, 2, FS_NW128, FS_S128>(a, st) : ffn_stream_go<128, 1, 8, 4>(a, st);
-    return split == 3 ? ffn_stream_go<256, 3, 4, 2>(a, st) : split == PREC_F16 ? ffn_stream_go<256, 2, 4, FS_S256>(a, st) : ffn_stream_go<256, 1, 4, 4>(a, st);
+    if (C == 128) return split == 3 ? ffn_stream_go<128, 3, 8, 4>(a, st, tu) : split == PREC_F16 ? ffn_stream_go<128, 2, FS_NW128, FS_S128>(a, st, tu) : ffn_stream_go<128, 1, 8, 4>(a, st, tu);
+    return split == 3 ? ffn_stream_go<256, 3, 4, 2>(a, st, tu) : split == PREC_F16 ? ffn_stream_go<256, 2, 4, FS_S256>(a, st, tu) : ffn_stream_go<256, 1, 4, 4>(a, st, tu);
 }
 
 // out[(t * C + c) * 32 + k] = in[c * F + 32 t + k]   (W2 [C][F] -> hidden-tile-major)

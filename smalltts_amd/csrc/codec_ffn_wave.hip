@@ -18,7 +18,6 @@
 #include "prof.hpp"
 #include <type_traits>
 
-extern int g_persist_mask;   // engine.hip: which persistent kernels the throughput-mode grid cap applies to (1 streamed FFN, 2 one-pass / wave FFN, 4 upsample)
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -676,7 +675,7 @@ __global__ __launch_bounds__(NWV * 64) void codec_chain_wave_kernel(FfnChainArgs
 #define FW_NWV32 8
 #endif
 template <int C, int SPLIT, bool MIX = false>
-static hipError_t ffn_wave_go(const FfnWaveArgs& a, hipStream_t st) {
+static hipError_t ffn_wave_go(const FfnWaveArgs& a, hipStream_t st, const LaunchTuning& tu) {
     constexpr int NWV = (C == 32 && SPLIT != 3) ? FW_NWV32 : (C == 64 && SPLIT != 3) ? FW_NWV64 : 8;
     constexpr size_t lds = (size_t)(SPLIT == 3 ? 2 : 1) * 2 * (8 * C * C) + (size_t)(4 * C + 3 * C) * 4 +
                            (MIX ? (size_t)(10 * C + NWV * 38 * (C + 4)) * 4 : 0);
@@ -688,7 +687,7 @@ static hipError_t ffn_wave_go(const FfnWaveArgs& a, hipStream_t st) {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }, &cus);
     if (e != hipSuccess) return e;
-    if (!(g_persist_mask & 2)) cus = once.real_cus();   // (A/B: which persistent kernels the throughput-mode grid cap applies to)
+    cus = persist_grid_cus(tu, PERSIST_FFN_WAVE, cus);
     const int ntiles = (a.M + 31) / 32;
     // persistent: as many workgroups as fit (LDS, and 32 waves per CU), each wave walks tiles
     int per_cu = (int)((160 * 1024) / lds);
@@ -703,13 +702,13 @@ static hipError_t ffn_wave_go(const FfnWaveArgs& a, hipStream_t st) {
 // C in {32, 64}; w1 [F][ld1] (ld1 >= C, K possibly zero-padded), w2 [>= C][F]
 hipError_t launch_codec_ffn_wave(float* x, RowMap img, const float* norm_w, const bf16_t* w1hi, const bf16_t* w1lo, int ld1,
                                  const float* b1, const bf16_t* w2hi, const bf16_t* w2lo, const float* b2, const float* gamma,
-                                 int M, int C, int F, float eps, int split, hipStream_t st) {
+                                 int M, int C, int F, float eps, int split, hipStream_t st, const LaunchTuning& tu) {
     if (!(C == 32 || C == 64) || F != 4 * C || img.ld % 4 || img.off % 4 || ld1 % 8 || (img.rpb && img.bstride % 4)) return hipErrorInvalidValue;
     if (M <= 0) return hipSuccess;
     FfnWaveArgs a{x, img, norm_w, w1hi, w1lo, ld1, b1, w2hi, w2lo, b2, gamma, M, eps};
     ProfScope ps(st, C == 64 ? "codec_ffn_wave<64>" : "codec_ffn_wave<32>", 4.0 * M * (double)C * F, 8.0 * M * C + 8.0 * (double)C * F);
-    if (C == 64) return split == 3 ? ffn_wave_go<64, 3>(a, st) : split == PREC_F16 ? ffn_wave_go<64, 2>(a, st) : ffn_wave_go<64, 1>(a, st);
-    return split == 3 ? ffn_wave_go<32, 3>(a, st) : split == PREC_F16 ? ffn_wave_go<32, 2>(a, st) : ffn_wave_go<32, 1>(a, st);
+    if (C == 64) return split == 3 ? ffn_wave_go<64, 3>(a, st, tu) : split == PREC_F16 ? ffn_wave_go<64, 2>(a, st, tu) : ffn_wave_go<64, 1>(a, st, tu);
+    return split == 3 ? ffn_wave_go<32, 3>(a, st, tu) : split == PREC_F16 ? ffn_wave_go<32, 2>(a, st, tu) : ffn_wave_go<32, 1>(a, st, tu);
 }
 
 // the whole block (mixer + FFN) in one pass for C in {32, 64} at the single-array formats (and C = 32 at split-bf16):
@@ -720,7 +719,7 @@ bool codec_block_wave_ok(int C, int F, int K, int T, int split) {
 hipError_t launch_codec_block_wave(const float* xin, float* xout, RowMap img, const float* mnorm_w, const float* dw_w, const float* dw_b,
                                    const float* mgamma, const float* norm_w, const bf16_t* w1hi, const bf16_t* w1lo, int ld1,
                                    const float* b1, const bf16_t* w2hi, const bf16_t* w2lo, const float* b2, const float* gamma, int M,
-                                   int C, int F, int K, float eps, int split, hipStream_t st) {
+                                   int C, int F, int K, float eps, int split, hipStream_t st, const LaunchTuning& tu) {
     if (!codec_block_wave_ok(C, F, K, img.rpb, split) || xin == xout || img.ld != C || img.off % 4 || ld1 % 8 || img.bstride % 4 ||
         M % 32)
         return hipErrorInvalidValue;
@@ -728,8 +727,8 @@ hipError_t launch_codec_block_wave(const float* xin, float* xout, RowMap img, co
     FfnWaveArgs a{xout, img, norm_w, w1hi, w1lo, ld1, b1, w2hi, w2lo, b2, gamma, M, eps, xin, mnorm_w, dw_w, dw_b, mgamma};
     ProfScope ps(st, C == 64 ? "codec_block_wave<64>" : "codec_block_wave<32>", 4.0 * M * (double)C * F + 2.0 * M * C * (K + 4),
                  8.0 * M * C + 8.0 * (double)C * F);
-    if (C == 64) return split == PREC_F16 ? ffn_wave_go<64, 2, true>(a, st) : ffn_wave_go<64, 1, true>(a, st);
-    return split == 3 ? ffn_wave_go<32, 3, true>(a, st) : split == PREC_F16 ? ffn_wave_go<32, 2, true>(a, st) : ffn_wave_go<32, 1, true>(a, st);
+    if (C == 64) return split == PREC_F16 ? ffn_wave_go<64, 2, true>(a, st, tu) : ffn_wave_go<64, 1, true>(a, st, tu);
+    return split == 3 ? ffn_wave_go<32, 3, true>(a, st, tu) : split == PREC_F16 ? ffn_wave_go<32, 2, true>(a, st, tu) : ffn_wave_go<32, 1, true>(a, st, tu);
 }
 
 // ---- stage chain: all NB blocks of a C = 32 stage in one launch (single-array operand formats) ---------------------------------------
@@ -740,7 +739,7 @@ bool codec_chain_wave_ok(int C, int F, int K, int T, int split, int nb) {
     return C == 32 && nb >= 1 && nb <= 3 && split != 3 && codec_block_wave_ok(C, F, K, T, split);
 }
 template <int C, int SPLIT, int NB>
-static hipError_t chain_wave_go(const FfnChainArgs& c, hipStream_t st) {
+static hipError_t chain_wave_go(const FfnChainArgs& c, hipStream_t st, const LaunchTuning& tu) {
     constexpr int NWV = FW_CHAIN_NWV, F = 4 * C;
     constexpr size_t blkb = (size_t)2 * (8 * C * C) + (size_t)(F + 3 * C + 10 * C) * 4;
     constexpr size_t lds = NB * blkb + (size_t)NWV * (38 + 6 * (NB - 1)) * (C + 4) * 4;
@@ -752,7 +751,7 @@ static hipError_t chain_wave_go(const FfnChainArgs& c, hipStream_t st) {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }, &cus);
     if (e != hipSuccess) return e;
-    if (!(g_persist_mask & 2)) cus = once.real_cus();
+    cus = persist_grid_cus(tu, PERSIST_FFN_WAVE, cus);
     const int ntiles = c.b[0].M / 32;
     int grid = (ntiles + NWV - 1) / NWV;
     grid = grid < cus ? grid : cus;   // persistent: one workgroup per CU, every wave one contiguous run of tiles
@@ -762,7 +761,7 @@ static hipError_t chain_wave_go(const FfnChainArgs& c, hipStream_t st) {
 // xout = block[nb - 1](... block[0](xin)); xin != xout, both images with zero pad frames; blocks: {mixer norm, taps, conv bias, mixer
 // layer scale, FFN norm, W1, b1, W2, b2, FFN layer scale} each
 hipError_t launch_codec_chain_wave(const float* xin, float* xout, RowMap img, const CodecChainBlock* blocks, int nb, int M, int C, int F, int K,
-                                   float eps, int split, hipStream_t st) {
+                                   float eps, int split, hipStream_t st, const LaunchTuning& tu) {
     if (!codec_chain_wave_ok(C, F, K, img.rpb, split, nb) || xin == xout || img.ld != C || img.off % 4 || img.bstride % 4 || M % 32)
         return hipErrorInvalidValue;
     if (M <= 0) return hipSuccess;
@@ -774,7 +773,7 @@ hipError_t launch_codec_chain_wave(const float* xin, float* xout, RowMap img, co
     }
     c.tpu = img.rpb / 32;
     ProfScope ps(st, "codec_chain_wave<32>", nb * (4.0 * M * (double)C * F + 2.0 * M * C * (K + 4)), 8.0 * M * C + nb * 8.0 * (double)C * F);
-    if (nb == 1) return split == PREC_F16 ? chain_wave_go<32, 2, 1>(c, st) : chain_wave_go<32, 1, 1>(c, st);
-    if (nb == 2) return split == PREC_F16 ? chain_wave_go<32, 2, 2>(c, st) : chain_wave_go<32, 1, 2>(c, st);
-    return split == PREC_F16 ? chain_wave_go<32, 2, 3>(c, st) : chain_wave_go<32, 1, 3>(c, st);
+    if (nb == 1) return split == PREC_F16 ? chain_wave_go<32, 2, 1>(c, st, tu) : chain_wave_go<32, 1, 1>(c, st, tu);
+    if (nb == 2) return split == PREC_F16 ? chain_wave_go<32, 2, 2>(c, st, tu) : chain_wave_go<32, 1, 2>(c, st, tu);
+    return split == PREC_F16 ? chain_wave_go<32, 2, 3>(c, st, tu) : chain_wave_go<32, 1, 3>(c, st, tu);
 }

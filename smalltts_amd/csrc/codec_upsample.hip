@@ -12,7 +12,6 @@
 #include "kernels.hpp"
 #include "prof.hpp"
 
-extern int g_persist_mask;   // engine.hip: which persistent kernels the throughput-mode grid cap applies to (1 streamed FFN, 2 one-pass / wave FFN, 4 upsample)
 
 namespace {
 typedef float f32x2u __attribute__((ext_vector_type(2)));
@@ -151,7 +150,7 @@ __global__ __launch_bounds__(512) void codec_upsample_wave_kernel(UpsampleArgs a
 }
 
 template <int K, int N, int SPLIT>
-hipError_t upsample_go(const UpsampleArgs& a, hipStream_t st) {
+hipError_t upsample_go(const UpsampleArgs& a, hipStream_t st, const LaunchTuning& tu) {
     constexpr size_t lds = (size_t)(SPLIT == 3 ? 2 : 1) * N * 2 * K + (size_t)N * 4;
     static_assert(lds <= 160 * 1024, "weights must fit LDS");
     auto kern = codec_upsample_wave_kernel<K, N, SPLIT>;
@@ -161,7 +160,7 @@ hipError_t upsample_go(const UpsampleArgs& a, hipStream_t st) {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     }, &cus);
     if (e != hipSuccess) return e;
-    if (!(g_persist_mask & 4)) cus = once.real_cus();   // (A/B: which persistent kernels the throughput-mode grid cap applies to)
+    cus = persist_grid_cus(tu, PERSIST_UPSAMPLE, cus);
     const int ntiles = (a.M + 31) / 32;
     const int per_cu = lds * 2 <= 160 * 1024 ? 2 : 1;
     int grid = (ntiles + 7) / 8;
@@ -175,7 +174,7 @@ bool codec_upsample_wave_ok(int K, int N) { return (K == 256 && N == 128) || (K 
 
 // A rows: amap (K contiguous floats each); W [N][ldw] split bf16; out rows: omap (N contiguous floats each)
 hipError_t launch_codec_upsample_wave(const float* x, RowMap amap, const bf16_t* whi, const bf16_t* wlo, int ldw, const float* bias,
-                                      float* out, RowMap omap, int M, int K, int N, int split, hipStream_t st) {
+                                      float* out, RowMap omap, int M, int K, int N, int split, hipStream_t st, const LaunchTuning& tu) {
     if (!codec_upsample_wave_ok(K, N) || amap.ld % 4 || amap.off % 4 || omap.ld % 4 || omap.off % 4 || ldw % 8 ||
         (amap.rpb && amap.bstride % 4) || (omap.rpb && omap.bstride % 4))
         return hipErrorInvalidValue;
@@ -183,6 +182,6 @@ hipError_t launch_codec_upsample_wave(const float* x, RowMap amap, const bf16_t*
     UpsampleArgs a{x, amap, whi, wlo, ldw, bias, out, omap, M};
     ProfScope ps(st, K == 256 ? "codec_upsample_wave<256x128>" : "codec_upsample_wave<128x64>", 2.0 * M * (double)K * N,
                  4.0 * M * (K / 2 + N) + 4.0 * (double)K * N);
-    if (K == 256) return split == 3 ? upsample_go<256, 128, 3>(a, st) : upsample_go<256, 128, 1>(a, st);
-    return split == 3 ? upsample_go<128, 64, 3>(a, st) : upsample_go<128, 64, 1>(a, st);
+    if (K == 256) return split == 3 ? upsample_go<256, 128, 3>(a, st, tu) : upsample_go<256, 128, 1>(a, st, tu);
+    return split == 3 ? upsample_go<128, 64, 3>(a, st, tu) : upsample_go<128, 64, 1>(a, st, tu);
 }

@@ -39,7 +39,7 @@ struct DevOnce {
     std::atomic<unsigned> mask{0};
     int cus[16] = {};
     template <class F>
-    hipError_t ensure(F&& setup, int* cu_out = nullptr) {
+    hipError_t ensure(F&& setup, int* cu_out = nullptr /* the device's CU count */) {
         int dev = 0;
         (void)hipGetDevice(&dev);
         dev &= 15;
@@ -51,14 +51,32 @@ struct DevOnce {
             cus[dev] = n;
             mask.fetch_or(1u << dev, std::memory_order_release);
         }
-        if (cu_out) {
-            extern thread_local int g_persist_cus;   // engine.hip: cap on the grid of the persistent codec kernels (0 = every CU), installed per codec call
-            *cu_out = g_persist_cus > 0 && g_persist_cus < cus[dev] ? g_persist_cus : cus[dev];
-        }
+        if (cu_out) *cu_out = cus[dev];
         return hipSuccess;
     }
-    int real_cus() const { int dev = 0; (void)hipGetDevice(&dev); return cus[dev & 15]; }   // (after ensure) the device's CU count, uncapped
 };
+
+// Launch tuning: the choices between kernel variants and grid sizes that change speed, never results.  An Engine owns one and
+// passes it, next to the stream, to every launcher that reads it; the defaults are the shipped configuration.
+struct LaunchTuning {
+    int deep = 1;          // gemm3 ring depth for a grid that is resident at once: 0 shallow, 1 deep, 2 = 8 stages on the N = 960 residual projections (SMTTS_GEMM_DEEP)
+    // Persistent codec kernels (streamed / one-pass FFN, upsample): workgroups launched at most.  A persistent grid that covers
+    // every CU keeps all other streams' kernels out until it ends; with several batches in flight (throughput tuning) it leaves
+    // a quarter of the CUs to them.
+    int persist_cus = 0;   // 0 = one round on every CU
+    int persist_mask = 7;  // the kernels the cap applies to: PersistKernel bits (SMTTS_PERSIST_MASK)
+    int t160 = 1;          // gemm3 160x128 tiles for M = 600 x wide N (SMTTS_GEMM_T160=0: off)
+    int w4_minm = 0;       // gemm3: 4-wave 128x128 tiles (wave 64x64) for single-array products with M >= this and N >= 2048 (SMTTS_GEMM_W4_MINM; 0 = off)
+    int stage16 = 1;       // gemm3: 16-bit outputs through the LDS-staged epilogue (SMTTS_GEMM_STAGE16=0: scalar stores)
+    int group = 4;         // gemm3 tile order when neither operand fits an XCD's L2: bands of this many row tiles (SMTTS_GEMM_GROUP=1: plain N fastest)
+    int nfast = 1;         // gemm3 tile order: N fastest when M > N (SMTTS_GEMM_NFAST=0 restores M fastest everywhere)
+    int xcd = 1;           // fp32-A GEMM: XCD-aware tile order for unbatched launches (SMTTS_GEMM_XCD=0: plain blockIdx mapping)
+};
+enum PersistKernel { PERSIST_FFN_STREAM = 1, PERSIST_FFN_WAVE = 2, PERSIST_UPSAMPLE = 4 };
+// CUs a persistent codec kernel sizes its grid for: the cap where it applies to this kernel and is below the device's count
+static inline int persist_grid_cus(const LaunchTuning& tu, PersistKernel which, int real_cus) {
+    return (tu.persist_mask & which) && tu.persist_cus > 0 && tu.persist_cus < real_cus ? tu.persist_cus : real_cus;
+}
 
 // Row addressing shared by GEMM operands/outputs: logical row m -> element offset.
 // rpb == 0: off + m*ld.  rpb > 0 (batched rows with per-batch padding):

@@ -35,44 +35,28 @@ inline bool ws_misaligned(const void* ws) { return (reinterpret_cast<uintptr_t>(
 inline std::string sidx(const std::string& a, int i, const std::string& b) { return a + std::to_string(i) + b; }
 }  // namespace
 
-int g_gemm3_t160 = 1;   // gemm3 160x128 tiles for M = 600 x wide N (SMTTS_GEMM_T160=0: off)
-thread_local int g_gemm3_deep = 1;   // gemm3 ring depth for single-array operand formats: 1 = deep (latency tuning), 0 = shallow (throughput tuning);
-                                      // thread-local, installed from the calling Engine for the duration of each operator call (DeepScope)
-namespace { struct DeepScope { int prev; explicit DeepScope(int v) : prev(g_gemm3_deep) { g_gemm3_deep = v; } ~DeepScope() { g_gemm3_deep = prev; } }; }
-int g_gemm3_w4_minm = 0;  // gemm3: 4-wave 128x128 tiles (wave 64x64) for single-array products with M >= this and N >= 2048 (SMTTS_GEMM_W4_MINM; 0 = off)
-int g_gemm3_stage16 = 1;  // gemm3: 16-bit outputs through the LDS-staged epilogue (SMTTS_GEMM_STAGE16=0: scalar stores)
-// Persistent codec kernels (streamed / one-pass FFN, upsample): workgroups launched at most (0 = one per CU).  A persistent grid
-// that covers every CU keeps all other streams' kernels out until it ends; with several batches in flight (throughput tuning) it
-// leaves a quarter of the CUs to them (Engine::persist_cus_, installed per codec call like the ring depth).
-thread_local int g_persist_cus = 0;
-int g_persist_mask = 7;   // 1 streamed FFN, 2 one-pass / wave FFN, 4 upsample (SMTTS_PERSIST_MASK)
-namespace { struct PersistScope { int prev; explicit PersistScope(int v) : prev(g_persist_cus) { g_persist_cus = v; } ~PersistScope() { g_persist_cus = prev; } }; }
-int g_gemm_xcd = 1;     // fp32-A GEMM: XCD-aware tile order for unbatched launches (SMTTS_GEMM_XCD=0: plain blockIdx mapping)
-int g_gemm3_group = 4;  // gemm3 tile order when neither operand fits an XCD's L2: bands of this many row tiles (SMTTS_GEMM_GROUP=1: plain N fastest)
-int g_gemm3_nfast = 1;  // gemm3 tile order: N fastest when M > N (SMTTS_GEMM_NFAST=0 restores M fastest everywhere)
 thread_local Profiler* g_prof = nullptr;
 thread_local const char* g_prof_tag = nullptr;
 thread_local int g_prof_shapes = 0;
 
-static int g_small_m_splitk = 1;   // SMTTS_SMALLM_SPLITK=0: A/B switch for the K-sliced small-M products of the codec
 Engine::Engine(int device) : device_(device) {
     set_precision(kDefaultPrecision);
-    if (const char* nf = lab_env("SMTTS_GEMM_NFAST")) g_gemm3_nfast = atoi(nf);
-    if (const char* gg = getenv("SMTTS_GEMM_GROUP")) g_gemm3_group = atoi(gg);
-    if (const char* gx = getenv("SMTTS_GEMM_XCD")) g_gemm_xcd = atoi(gx);
+    if (const char* nf = lab_env("SMTTS_GEMM_NFAST")) tune_.nfast = atoi(nf);
+    if (const char* gg = getenv("SMTTS_GEMM_GROUP")) tune_.group = atoi(gg);
+    if (const char* gx = getenv("SMTTS_GEMM_XCD")) tune_.xcd = atoi(gx);
     if (const char* pc = getenv("SMTTS_PERSIST_CUS")) persist_cus_tp_ = atoi(pc);
-    if (const char* pm = lab_env("SMTTS_PERSIST_MASK")) g_persist_mask = atoi(pm);
-    if (const char* dp = getenv("SMTTS_GEMM_DEEP")) gemm_deep_ = atoi(dp);
-    if (const char* s16 = lab_env("SMTTS_GEMM_STAGE16")) g_gemm3_stage16 = atoi(s16);
-    if (const char* w4 = lab_env("SMTTS_GEMM_W4_MINM")) g_gemm3_w4_minm = atoi(w4);
-    if (const char* t1 = lab_env("SMTTS_GEMM_T160")) g_gemm3_t160 = atoi(t1);
+    if (const char* pm = lab_env("SMTTS_PERSIST_MASK")) tune_.persist_mask = atoi(pm);
+    if (const char* dp = getenv("SMTTS_GEMM_DEEP")) tune_.deep = atoi(dp);
+    if (const char* s16 = lab_env("SMTTS_GEMM_STAGE16")) tune_.stage16 = atoi(s16);
+    if (const char* w4 = lab_env("SMTTS_GEMM_W4_MINM")) tune_.w4_minm = atoi(w4);
+    if (const char* t1 = lab_env("SMTTS_GEMM_T160")) tune_.t160 = atoi(t1);
     const char* s = getenv("SMTTS_SINGLE_STREAM");
     if (s && *s == '1') dual_stream_ = false;
     if ((s = lab_env("SMTTS_BLOCK_WAVE"))) block_wave_ = atoi(s) != 0;
     if ((s = getenv("SMTTS_STAGE_CHAIN"))) { stage_chain_ = atoi(s) != 0; if (atoi(s) >= 2) chain_min_run_ = 0; }   // 2: the chain whatever the run length (tests)
     if ((s = lab_env("SMTTS_CHAIN_MIN"))) chain_min_blocks_ = atoi(s);
     if ((s = lab_env("SMTTS_CHAIN_MIN_RUN"))) chain_min_run_ = atoi(s);
-    if ((s = lab_env("SMTTS_SMALLM_SPLITK"))) g_small_m_splitk = atoi(s);
+    if ((s = lab_env("SMTTS_SMALLM_SPLITK"))) small_m_splitk_ = atoi(s) != 0;
     if ((s = lab_env("SMTTS_CONVPOS_BY_GROUP"))) convpos_by_group_ = atoi(s) != 0;
     if ((s = getenv("SMTTS_ATTN_EPI"))) attn_epi_ = atoi(s) != 0;
     if ((s = lab_env("SMTTS_ATTN_IMG"))) attn_img_ = atoi(s) != 0;
@@ -119,13 +103,13 @@ void Engine::set_tuning(int mode) {
         // Ring depth with batches in flight: round 2 measured shallow rings ahead (10.14 vs 10.38 ms: a workgroup holding 64-128 KiB
         // of LDS while it waits kept the other streams' kernels off its CU).  Re-measured at the end of round 3 — fp16 operand images,
         // shorter epilogues, persistent codec grids capped — deep rings win: 8.53 -> 8.42 ms (profiles/r03ag_*).
-        gemm_deep_ = getenv("SMTTS_GEMM_DEEP") ? atoi(getenv("SMTTS_GEMM_DEEP")) : 1;
-        persist_cus_ = persist_cus_tp_;
+        tune_.deep = getenv("SMTTS_GEMM_DEEP") ? atoi(getenv("SMTTS_GEMM_DEEP")) : 1;
+        tune_.persist_cus = persist_cus_tp_;
     } else {
         if (tuning_ == TUNE_THROUGHPUT) dual_stream_ = dual_stream_latency_;
         tuning_ = TUNE_LATENCY;
-        persist_cus_ = 0;
-        gemm_deep_ = getenv("SMTTS_GEMM_DEEP") ? atoi(getenv("SMTTS_GEMM_DEEP")) : 1;
+        tune_.persist_cus = 0;
+        tune_.deep = getenv("SMTTS_GEMM_DEEP") ? atoi(getenv("SMTTS_GEMM_DEEP")) : 1;
     }
 }
 
@@ -806,13 +790,13 @@ struct NextLN {  // optional: the AdaLN that follows the residual, fused into th
     float eps = 1e-6f;
 };
 static hipError_t gemm3_resid_splitk(const Gemm3Operands& g0, const EpiResid<0>& r, float* partial, int splits, int split,
-                                     hipStream_t st, const NextLN& ln = NextLN(), int cfg = G3_64x64) {
+                                     hipStream_t st, const LaunchTuning& tu, const NextLN& ln = NextLN(), int cfg = G3_64x64) {
     Gemm3Operands g = g0;
     const int nk = g.K / 64;
     g.ksplit_tiles = (nk + splits - 1) / splits;
     const int used = (nk + g.ksplit_tiles - 1) / g.ksplit_tiles;
     EpiStore<ACT_NONE> e{partial, rowmap_plain(g.N), (long)g.M * g.N, nullptr, 0, 1.f, nullptr, nullptr, nullptr};
-    hipError_t err = gemm3_store(g, ACT_NONE, e, used, split, st, cfg);
+    hipError_t err = gemm3_store(g, ACT_NONE, e, used, split, st, tu, cfg);
     if (err != hipSuccess) return err;
     if (ln.shift)
         return launch_splitk_resid_ln(partial, used, r.x, r.bias, r.gate, r.gld, r.grow0, r.grstride, r.rows_per_batch,
@@ -825,7 +809,6 @@ static hipError_t gemm3_resid_splitk(const Gemm3Operands& g0, const EpiResid<0>&
 // on M itself, so that results stay bit-identical across batch sizes inside a class (tests/test_fullsize_gpu.py: a batch of 2
 // shares its prefix with the batch of 1).  Slices of >= 16 k-tiles (>= 32 in the 513..2048-row class).  1 = leave the product alone.
 static int small_m_splits(int M, int K, int max_few, int max_some) {
-    if (!g_small_m_splitk) return 1;
     const int nk = K / 64;
     int sp = 1;
     if (M <= 512) sp = nk / 16 < max_few ? nk / 16 : max_few;
@@ -834,13 +817,13 @@ static int small_m_splits(int M, int K, int max_few, int max_some) {
 }
 // out = A x W^T + bias as K slices into fp32 partials + one fixed-order reduce pass (no residual: the reduce overwrites)
 static hipError_t gemm3_store_splitk(const Gemm3Operands& g0, float* partial, int splits, int split, const float* bias, float* out,
-                                     const RowMap& omap, hipStream_t st) {
+                                     const RowMap& omap, hipStream_t st, const LaunchTuning& tu) {
     Gemm3Operands g = g0;
     const int nk = g.K / 64;
     g.ksplit_tiles = (nk + splits - 1) / splits;
     const int used = (nk + g.ksplit_tiles - 1) / g.ksplit_tiles;
     EpiStore<ACT_NONE> e{partial, rowmap_plain(g.N), (long)g.M * g.N, nullptr, 0, 1.f, nullptr, nullptr, nullptr};
-    hipError_t err = gemm3_store(g, ACT_NONE, e, used, split, st, G3_64x64);
+    hipError_t err = gemm3_store(g, ACT_NONE, e, used, split, st, tu, G3_64x64);
     if (err != hipSuccess) return err;
     return launch_splitk_resid(partial, used, out, bias, nullptr, 0, 0, 0, 1, nullptr, g.M, g.N, st, &omap, true);
 }
@@ -895,7 +878,7 @@ int Engine::enc_blocks(hipStream_t st, const EncoderW& e, const EncWs& w, int l0
     for (size_t l = l0; l < (size_t)l1; ++l) {
         const EncBlockW& b = e.blocks[l];
         const bool epi = attn_img_ && attn_epi_;   // the GEMM's own epilogue writes the attention operands
-        if (!epi) HIPC(gemm3_store(ops3(w.y, rd, b.qkvg, M, pe), ACT_NONE, store_to(w.qkvg, rowmap_plain(4 * D), nullptr), 1, pe, st));
+        if (!epi) HIPC(gemm3_store(ops3(w.y, rd, b.qkvg, M, pe), ACT_NONE, store_to(w.qkvg, rowmap_plain(4 * D), nullptr), 1, pe, st, tune_));
         AttnArgs a{};
         a.q = w.qkvg; a.k = w.qkvg + D; a.v = w.qkvg + 2 * D; a.gate = w.qkvg + 3 * D;
         a.bs = (long)S * 4 * D; a.rs = 4 * D;
@@ -921,7 +904,7 @@ int Engine::enc_blocks(hipStream_t st, const EncoderW& e, const EncWs& w, int l0
                 EpiQKV eq{nullptr, pk.qw, pk.kw, pk.rope_cos, pk.rope_sin, pk.eps, pk.q_scale, pk.rot_dim, pa,
                           pk.q, pk.q_lo, pk.k, pk.k_lo, pk.vt, pk.vt_lo, pk.g, pk.g_lo, S, e.heads, e.dh, pk.dhp, Sp};
                 if (fold && l > (size_t)l0) eq.fold = fin;   // w.y = x attention_norm.weight, written by the previous block's FF2 epilogue
-                HIPC(gemm3_qkv(ops3(w.y, rd, b.qkvg, M, pe), eq, pe, st));   // (both encoders' heads are 64 / 128 wide: no padding)
+                HIPC(gemm3_qkv(ops3(w.y, rd, b.qkvg, M, pe), eq, pe, st, tune_));   // (both encoders' heads are 64 / 128 wide: no padding)
             } else {
                 HIPC(launch_qkv_pack(pk, st));
             }
@@ -946,24 +929,24 @@ int Engine::enc_blocks(hipStream_t st, const EncoderW& e, const EncWs& w, int l0
         NextLN n1{b.mn, nullptr, y.hi, y.lo, true, e.eps};
         if (fold) {
             EpiResidLN e1{w.x, rd, nullptr, nullptr, nullptr, b.mn, y.hi, y.lo, D, w.lnpart, D / 32, 1};
-            HIPC(gemm3_resid_ln(ops3(w.o, rd, b.wo, M, pe), e1, pe, st));
+            HIPC(gemm3_resid_ln(ops3(w.o, rd, b.wo, M, pe), e1, pe, st, tune_));
         } else if (ks > 1) {
-            HIPC(gemm3_resid_splitk(ops3(w.o, rd, b.wo, M, pe), r1, w.part, ks, pe, st, n1));
+            HIPC(gemm3_resid_splitk(ops3(w.o, rd, b.wo, M, pe), r1, w.part, ks, pe, st, tune_, n1));
         } else {
-            HIPC(gemm3_resid(ops3(w.o, rd, b.wo, M, pe), 0, r1, pe, st));
+            HIPC(gemm3_resid(ops3(w.o, rd, b.wo, M, pe), 0, r1, pe, st, tune_));
             HIPC(launch_rmsnorm(w.x, rd, nullptr, y.hi, y.lo, rd, M, D, e.eps, n1.shift, st));
         }
         EpiSwiGLU sw{nullptr, e.ff, nullptr, nullptr, ffh.hi, ffh.lo};
         if (fold) sw.fold = fin;
-        HIPC(gemm3_swiglu(ops3(w.y, rd, b.ff13, M, pe), sw, pe, st));
+        HIPC(gemm3_swiglu(ops3(w.y, rd, b.ff13, M, pe), sw, pe, st, tune_));
         NextLN n2{l + 1 < L ? e.blocks[l + 1].an : e.final_norm, nullptr, y.hi, y.lo, true, e.eps};
         if (fold && l + 1 < L) {
             EpiResidLN e2{w.x, rd, nullptr, nullptr, nullptr, e.blocks[l + 1].an, y.hi, y.lo, D, w.lnpart, D / 32, 1};
-            HIPC(gemm3_resid_ln(ops3(w.ffh, rowmap_plain(e.ff), b.w2, M, pe), e2, pe, st));
+            HIPC(gemm3_resid_ln(ops3(w.ffh, rowmap_plain(e.ff), b.w2, M, pe), e2, pe, st, tune_));
         } else if (ks > 1) {
-            HIPC(gemm3_resid_splitk(ops3(w.ffh, rowmap_plain(e.ff), b.w2, M, pe), r1, w.part, ks, pe, st, n2));
+            HIPC(gemm3_resid_splitk(ops3(w.ffh, rowmap_plain(e.ff), b.w2, M, pe), r1, w.part, ks, pe, st, tune_, n2));
         } else {
-            HIPC(gemm3_resid(ops3(w.ffh, rowmap_plain(e.ff), b.w2, M, pe), 0, r1, pe, st));
+            HIPC(gemm3_resid(ops3(w.ffh, rowmap_plain(e.ff), b.w2, M, pe), 0, r1, pe, st, tune_));
             HIPC(launch_rmsnorm(w.x, rd, nullptr, y.hi, y.lo, rd, M, D, e.eps, n2.shift, st));
         }
     }
@@ -1003,7 +986,6 @@ int Engine::ensure_aux(hipStream_t st) {
 int Engine::cond_encode(hipStream_t st, const float* ref, const int64_t* ref_len, const int64_t* ids,
                         const uint8_t* ph_mask, int B, int R, int P, float* k_ref, float* v_ref, uint8_t* ref_mask,
                         float* k_text, float* v_text, void* ws, size_t ws_bytes, float* ref_seq_out, float* mem_out) {
-    DeepScope deep_scope(gemm_deep_);
     ProfTag ptag("enc");
     if (!dit_ready_) return fail("cond_encode: DiT weights not finalized");
     if (R > kMaxPos || P > kMaxPos) return fail("cond_encode: sequence longer than the rope table (4096)");
@@ -1050,7 +1032,7 @@ int Engine::cond_encode(hipStream_t st, const float* ref, const int64_t* ref_len
 // the encoders' stages (cond_encode): input, output projection, cross K / V of all 12 DiT blocks
 int Engine::style_in(hipStream_t st, const EncWs& w, const float* ref, int B, int R) {
     HIPC(gemm_store(ops(ref, rowmap_plain(kLatent), style_in_, B * R), ACT_NONE,
-                    store_to(w.x, rowmap_plain(512), rawp("style_encoder.in_proj.bias"), style_scale_), 1, prec_[SITE_COND], st));
+                    store_to(w.x, rowmap_plain(512), rawp("style_encoder.in_proj.bias"), style_scale_), 1, prec_[SITE_COND], st, tune_));
     return 0;
 }
 int Engine::text_in(hipStream_t st, const EncWs& w, const int64_t* ids, int B, int P) {
@@ -1061,7 +1043,7 @@ int Engine::enc_out(hipStream_t st, bool text, const EncWs& w, int M, const uint
     const int pe = prec_[SITE_ENCODER];
     HIPC(gemm3_store(ops3(w.y, rowmap_plain(512), text ? phproj_ : style_out_, M, pe), ACT_NONE,
                      store_to(seq, rowmap_plain(kHidden), rawp(text ? "dit.phoneme_proj.bias" : "style_encoder.out_proj.bias"), 1.f,
-                              key_mask), 1, pe, st));
+                              key_mask), 1, pe, st, tune_));
     return 0;
 }
 int Engine::enc_kv(hipStream_t st, bool text, const EncWs& w, const float* seq, int B, int S, float* k, float* v) {
@@ -1069,7 +1051,7 @@ int Engine::enc_kv(hipStream_t st, bool text, const EncWs& w, const float* seq, 
     const RowMap rh = rowmap_plain(kHidden);
     HIPC(launch_to_split(seq, rh, w.seqs.hi, w.seqs.as(pk, satp(SITE_CROSS_KV)).lo, rh, M, kHidden, st));
     EpiKV kv{k, v, text ? kvtext_b_ : kvref_b_, B, kHeads, kDh, S};
-    HIPC(gemm3_kv(ops3(w.seqs, rh, text ? kvtext_ : kvref_, M, pk), kv, pk, st));
+    HIPC(gemm3_kv(ops3(w.seqs, rh, text ? kvtext_ : kvref_, M, pk), kv, pk, st, tune_));
     HIPC(launch_headnorm(k, kBlocks, B, kHeads, S, kDh, 1e-6f, knc_, st));
     return 0;
 }
@@ -1086,16 +1068,16 @@ int Engine::modulation(hipStream_t st, const float* t_dev, int rows, float* sinb
     const int pc = prec_[SITE_COND];  // tiny-M chain on the fp32-A kernel: always split-bf16 unless the preset is plain bf16
     HIPC(launch_time_sinusoid(t_dev, sinb, rows, st));
     HIPC(gemm_store(ops(sinb, rowmap_plain(256), time0_, rows), ACT_SILU,
-                    store_to(t1, rowmap_plain(kHidden), rawp("time_embedding.mlp.0.bias")), 1, pc, st));
+                    store_to(t1, rowmap_plain(kHidden), rawp("time_embedding.mlp.0.bias")), 1, pc, st, tune_));
     HIPC(gemm_store(ops(t1, rowmap_plain(kHidden), time2_, rows), ACT_NONE,
-                    store_to(temb, rowmap_plain(kHidden), rawp("time_embedding.mlp.2.bias")), 1, pc, st));
+                    store_to(temb, rowmap_plain(kHidden), rawp("time_embedding.mlp.2.bias")), 1, pc, st, tune_));
     HIPC(gemm_store(ops(temb, rowmap_plain(kHidden), emb0_, rows), ACT_SILU,
-                    store_to(e1, rowmap_plain(2 * kHidden), rawp("dit.emb_proj.0.bias")), 1, pc, st));
+                    store_to(e1, rowmap_plain(2 * kHidden), rawp("dit.emb_proj.0.bias")), 1, pc, st, tune_));
     // AdaLN consumes silu(emb) only (dit.py:20,36), so the SiLU is fused into this epilogue
     HIPC(gemm_store(ops(e1, rowmap_plain(2 * kHidden), emb2_, rows), ACT_SILU,
-                    store_to(semb, rowmap_plain(kHidden), rawp("dit.emb_proj.2.bias")), 1, pc, st));
+                    store_to(semb, rowmap_plain(kHidden), rawp("dit.emb_proj.2.bias")), 1, pc, st, tune_));
     HIPC(gemm_store(ops(semb, rowmap_plain(kHidden), modall_, rows), ACT_NONE,
-                    store_to(mod, rowmap_plain(kModLd), modall_b_), 1, pc, st));
+                    store_to(mod, rowmap_plain(kModLd), modall_b_), 1, pc, st, tune_));
     HIPC(launch_tanh_gates(mod, rows, kModLd, kBlocks, kModPerBlock, kHidden, st));
     return ftab ? fold_tables(st, mod, rows, ftab) : 0;
 }
@@ -1237,7 +1219,7 @@ int Engine::dit_embed(hipStream_t st, const CoreWs& w, const float* x_t, const u
     const int pc = prec_[SITE_COND], pcp = prec_[SITE_CONVPOS];
     const SplitBuf gm1 = w.gm1.as(pcp, satp(SITE_CONVPOS)), gm2 = w.gm2.as(pcp, satp(SITE_CONVPOS));
     HIPC(gemm_store(ops(x_t, rowmap_plain(kLatent), inproj_, M), ACT_NONE,
-                    store_to(w.h, rh, rawp("dit.input_embed.proj.bias")), 1, pc, st));
+                    store_to(w.h, rh, rawp("dit.input_embed.proj.bias")), 1, pc, st, tune_));
     HIPC(launch_convpos_pack(w.h, mask, gm1.hi, gm1.lo, B, N, kConvG, kConvCpg, kConvPad, kConvGs, st));
     if (init_ws) {   // pad frames of the second conv's image (its producer writes the data frames only)
         HIPC(hipMemsetAsync(w.gm2.hi, 0, w.gm_elems * 2, st));
@@ -1256,14 +1238,14 @@ int Engine::dit_embed(hipStream_t st, const CoreWs& w, const float* x_t, const u
         g.w_zmod = kConvG;
         EpiConvPos<0> e1{nullptr, nullptr, rawp("dit.input_embed.conv_pos_embed.conv1.bias"), mask, kConvG, kConvCpg, N,
                          kConvPad, kConvGs, gm2.hi, gm2.lo, convpos_by_group_ ? 1 : 0};
-        HIPC(gemm3_convpos(g, false, e1, nz, pcp, st));
+        HIPC(gemm3_convpos(g, false, e1, nz, pcp, st, tune_));
         g = ops3(w.gm2, am, conv2_, rows, pcp, 0, kConvCpg);
         g.a_z = zs;
         g.w_z = (long)kConvCpg * conv2_.K;
         g.w_zmod = kConvG;
         EpiConvPos<0> e2{w.x, w.h, rawp("dit.input_embed.conv_pos_embed.conv2.bias"), mask, kConvG, kConvCpg, N,
                          kConvPad, kConvGs, nullptr, nullptr, convpos_by_group_ ? 1 : 0};
-        HIPC(gemm3_convpos(g, true, e2, nz, pcp, st));
+        HIPC(gemm3_convpos(g, true, e2, nz, pcp, st, tune_));
     }
     return 0;
 }
@@ -1317,7 +1299,7 @@ int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0,
         const bool epi = attn_img_ && attn_epi_;   // the GEMM's own epilogue writes the attention operands
         if (!epi)
             HIPC(gemm3_store(ops3(w.y, rh, b.qkvg, M, pb), ACT_NONE, store_to(w.qkvg, rowmap_plain(4 * kHidden), b.b_qkvg), 1,
-                             pb, st));
+                             pb, st, tune_));
         AttnArgs a{};
         a.q = w.qkvg; a.k = w.qkvg + kHidden; a.v = w.qkvg + 2 * kHidden; a.gate = w.qkvg + 3 * kHidden;
         a.bs = (long)N * 4 * kHidden; a.rs = 4 * kHidden;
@@ -1345,7 +1327,7 @@ int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0,
                 EpiQKV eq{b.b_qkvgp, pk.qw, pk.kw, pk.rope_cos, pk.rope_sin, pk.eps, pk.q_scale, pk.rot_dim, pa,
                           pk.q, pk.q_lo, pk.k, pk.k_lo, pk.vt, pk.vt_lo, pk.g, pk.g_lo, N, kHeads, kDh, 128, Np};
                 if (fold && l > l0) eq.fold = fold_in(l, 0);   // w.y = x (1 + scale_msa), written by the previous block's FF2 epilogue
-                HIPC(gemm3_qkv(ops3(w.y, rh, b.qkvgp, M, pb), eq, pb, st));
+                HIPC(gemm3_qkv(ops3(w.y, rh, b.qkvgp, M, pb), eq, pb, st, tune_));
             } else {
                 HIPC(launch_qkv_pack(pk, st));
             }
@@ -1382,18 +1364,18 @@ int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0,
         const float* const mr = mrow + (long)l * kModPerBlock;
         if (fold) {
             EpiResidLN e1{w.x, rh, nullptr, mr + 2 * kHidden, mask, mr + 4 * kHidden, yb.hi, yb.lo, kHidden, w.lnpart, kLnGroups, 0, lnc};
-            HIPC(gemm3_resid_ln(ops3(w.o, rh, b.out, M, pb), e1, pb, st));
+            HIPC(gemm3_resid_ln(ops3(w.o, rh, b.out, M, pb), e1, pb, st, tune_));
         } else if (ks_out > 1) {
-            HIPC(gemm3_resid_splitk(ops3(w.o, rh, b.out, M, pb), r1, w.part, ks_out, pb, st, ln1));
+            HIPC(gemm3_resid_splitk(ops3(w.o, rh, b.out, M, pb), r1, w.part, ks_out, pb, st, tune_, ln1));
         } else {
-            HIPC(gemm3_resid(ops3(w.o, rh, b.out, M, pb), 1, r1, pb, st));
+            HIPC(gemm3_resid(ops3(w.o, rh, b.out, M, pb), 1, r1, pb, st, tune_));
             HIPC(launch_ln_modulate(w.x, nullptr, ln1.yhi, ln1.ylo, M, kHidden, 1e-6f, ln1.shift, ln1.scale, kModLd, mod_row0,
                                     mod_rstride, N, st));
         }
         // D7 feed-forward (dit.py:199-201)
         EpiSwiGLU sw{nullptr, kFFp, b.b1, b.b3, ffh.hi, ffh.lo};
         if (fold) sw.fold = fold_in(l, 1);
-        HIPC(gemm3_swiglu(ops3(w.y, rh, b.ff13, M, pb), sw, pb, st));
+        HIPC(gemm3_swiglu(ops3(w.y, rh, b.ff13, M, pb), sw, pb, st, tune_));
         // w2 + gated residual, then the next block's attention AdaLN — or D8's final AdaLN (chunk order scale, shift:
         // dit.py:37) after the last block
         EpiResid<0> r2{w.x, rh, b.b2, m + 5 * kHidden, kModLd, mod_row0, mod_rstride, N, nullptr};
@@ -1403,11 +1385,11 @@ int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0,
                                      : NextLN{mn + kHidden, mn, yv.hi, yv.lo};
         if (fold && l + 1 < kBlocks) {
             EpiResidLN e2{w.x, rh, b.b2, mr + 5 * kHidden, nullptr, mr + kModPerBlock + kHidden, yb.hi, yb.lo, kHidden, w.lnpart, kLnGroups, 0, lnc};
-            HIPC(gemm3_resid_ln(ops3(w.ffh, rowmap_plain(kFFp), b.ff2, M, pb), e2, pb, st));
+            HIPC(gemm3_resid_ln(ops3(w.ffh, rowmap_plain(kFFp), b.ff2, M, pb), e2, pb, st, tune_));
         } else if (ks_ff2 > 1) {
-            HIPC(gemm3_resid_splitk(ops3(w.ffh, rowmap_plain(kFFp), b.ff2, M, pb), r2, w.part, ks_ff2, pb, st, ln2));
+            HIPC(gemm3_resid_splitk(ops3(w.ffh, rowmap_plain(kFFp), b.ff2, M, pb), r2, w.part, ks_ff2, pb, st, tune_, ln2));
         } else {
-            HIPC(gemm3_resid(ops3(w.ffh, rowmap_plain(kFFp), b.ff2, M, pb), 1, r2, pb, st));
+            HIPC(gemm3_resid(ops3(w.ffh, rowmap_plain(kFFp), b.ff2, M, pb), 1, r2, pb, st, tune_));
             HIPC(launch_ln_modulate(w.x, nullptr, ln2.yhi, ln2.ylo, M, kHidden, 1e-6f, ln2.shift, ln2.scale, kModLd, mod_row0,
                                     mod_rstride, N, st));
         }
@@ -1419,7 +1401,7 @@ int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0,
 int Engine::dit_head(hipStream_t st, const CoreWs& w, int M, float* velocity) {
     const int pc = prec_[SITE_COND];
     HIPC(gemm3_store(ops3(w.y, rowmap_plain(kHidden), velocity_, M, pc), ACT_NONE,
-                     store_to(velocity, rowmap_plain(kLatent), rawp("velocity.bias")), 1, pc, st));
+                     store_to(velocity, rowmap_plain(kLatent), rawp("velocity.bias")), 1, pc, st, tune_));
     return 0;
 }
 
@@ -1483,7 +1465,6 @@ int Engine::denoise_step(hipStream_t st, const float* x_t, const uint8_t* mask, 
                          const float* v_ref, const uint8_t* ref_mask, const float* k_text, const float* v_text,
                          const uint8_t* ph_mask, const float* rope, int B, int N, int R, int P, float* velocity,
                          void* ws, size_t ws_bytes) {
-    DeepScope deep_scope(gemm_deep_);
     if (!dit_ready_) return fail("denoise_step: DiT weights not finalized");
     if (N > kMaxPos) return fail("denoise_step: sequence longer than the rope table (4096)");
     if (ws_bytes < denoise_ws_bytes(B, N, R, P, B)) return fail("denoise_step: workspace too small");
@@ -1554,7 +1535,6 @@ int Engine::sample_pinned(hipStream_t st, int mode, int n_steps, int cfg, float 
                           uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes, const uint8_t* tap_steps,
                           unsigned tap_layers, unsigned tap_heads, float* text_mass, const float* x_pin, const uint8_t* pin,
                           int start_step) {
-    DeepScope deep_scope(gemm_deep_);
     if (!dit_ready_) return fail("sample: DiT weights not finalized");
     if (n_steps < 1) return fail("sample: n_steps must be >= 1");
     if (N > kMaxPos) return fail("sample: sequence longer than the rope table (4096)");
@@ -1711,7 +1691,7 @@ int Engine::codec_stage_chain(hipStream_t st, const CodecStageW& sg, float** xp,
         // (small decodes: one 10 s utterance is 3 tiles per wave) the warm-up is a third of the work.  Measured (ADVICE r5,
         // profiles/r06q_chain_small_batch.txt, B x 10 s, chain vs one launch per block): B = 1 1.567 vs 1.554 ms, B = 4 (10 tiles per
         // wave) 3.538 vs 3.517, B = 8 (20) 5.923 vs 5.994 -> the chain from 16 tiles per wave up.
-        const long waves = (long)(persist_cus_ > 0 ? persist_cus_ : num_cus_) * 12;
+        const long waves = (long)(tune_.persist_cus > 0 ? tune_.persist_cus : num_cus_) * 12;
         if (chain_min_run_ > 0 && (long)B * T / 32 < chain_min_run_ * waves) return 0;
     }
     CodecChainBlock cb[3];
@@ -1721,7 +1701,7 @@ int Engine::codec_stage_chain(hipStream_t st, const CodecStageW& sg, float** xp,
                                 pf == PREC_F16 ? b.w2.h16 : b.w2.hi, b.b2, b.ffn_gamma};
     }
     const RowMap img = rowmap_batched(C, T, (long)(kCodecPad + T) * C, (long)kCodecPad * C);
-    const hipError_t e = launch_codec_chain_wave(*xp, *xaltp, img, cb, nb, B * T, C, F, cspec_.kernel, cspec_.eps, pf, st);
+    const hipError_t e = launch_codec_chain_wave(*xp, *xaltp, img, cb, nb, B * T, C, F, cspec_.kernel, cspec_.eps, pf, st, tune_);
     if (e != hipSuccess) { fail_hip(e, "codec stage chain"); return -1; }
     float* t = *xp; *xp = *xaltp; *xaltp = t;
     return 1;
@@ -1743,7 +1723,7 @@ int Engine::codec_block(hipStream_t st, const CodecBlockW& w, float** xp, float*
     // narrowest stages: the whole block in one pass over the image (mixer + FFN, codec_ffn_wave.hip MIX kernels)
     if (fused_ffn_ && block_wave_ && codec_block_wave_ok(C, F, cspec_.kernel, T, pf) && w.w1.K == C && w.w2.K == F) {
         HIPC(launch_codec_block_wave(x, *xaltp, img, w.norm_w, w.dw_w, w.dw_b, w.gamma, w.ffn_norm_w, wsel(w.w1), w.w1.lo, w.w1.K, w.b1,
-                                     wsel(w.w2), w.w2.lo, w.b2, w.ffn_gamma, M, C, F, cspec_.kernel, cspec_.eps, pf, st));
+                                     wsel(w.w2), w.w2.lo, w.b2, w.ffn_gamma, M, C, F, cspec_.kernel, cspec_.eps, pf, st, tune_));
         *xp = *xaltp;
         *xaltp = x;
         return 0;
@@ -1776,13 +1756,13 @@ int Engine::codec_block(hipStream_t st, const CodecBlockW& w, float** xp, float*
     if (fused_ffn_ && (C == 32 || C == 64) && F == 4 * C && w.w1.K == C && w.w2.K == F) {
         // narrowest stages: all weights LDS-resident, one wave per 32 frames, hidden stays in registers (codec_ffn_wave.hip)
         HIPC(launch_codec_ffn_wave(x, img, w.ffn_norm_w, wsel(w.w1), w.w1.lo, w.w1.K, w.b1, wsel(w.w2), w.w2.lo, w.b2, w.ffn_gamma, M,
-                                   C, F, cspec_.eps, pf, st));
+                                   C, F, cspec_.eps, pf, st, tune_));
         return 0;
     }
     if (w.w2t.N && fused_ffn_) {
         // C = 128 / 256: weights stream through an LDS ring, hidden in registers (codec_ffn_stream.hip)
         HIPC(launch_codec_ffn_stream(x, img, w.ffn_norm_w, wsel(w.w1), w.w1.lo, w.b1, wsel(w.w2t), w.w2t.lo, w.b2, w.ffn_gamma, M, C, F,
-                                     cspec_.eps, pf, st));
+                                     cspec_.eps, pf, st, tune_));
         return 0;
     }
     // wide stages: two gemm3 launches; n2 / hidden are split bf16 pairs
@@ -1791,46 +1771,45 @@ int Engine::codec_block(hipStream_t st, const CodecBlockW& w, float** xp, float*
         float* hf = reinterpret_cast<float*>(hhi);  // hhi/hlo are adjacent: 2 x F x M bf16 = F x M fp32
         if (reinterpret_cast<char*>(hlo) < reinterpret_cast<char*>(hhi) + (size_t)M * F * 2) return fail("codec ws layout");
         HIPC(launch_rmsnorm(x, img, nbuf, nullptr, nullptr, img, M, C, cspec_.eps, w.ffn_norm_w, st));
-        HIPC(gemm_store(ops(nbuf, img, w.w1, M), ACT_GELU, store_to(hf, rf, w.b1), 1, pf, st));
+        HIPC(gemm_store(ops(nbuf, img, w.w1, M), ACT_GELU, store_to(hf, rf, w.b1), 1, pf, st, tune_));
         EpiResid<0> r0{x, img, w.b2, w.ffn_gamma, 0, 0, 0, 1, nullptr};
-        HIPC(gemm_resid(ops(hf, rf, w.w2, M), 2, r0, pf, st));
+        HIPC(gemm_resid(ops(hf, rf, w.w2, M), 2, r0, pf, st, tune_));
         return 0;
     }
     if (C % 64 == 0) {
         SplitBuf n2{n2hi, n2lo};
         if (!n2_done) HIPC(launch_rmsnorm(x, img, nullptr, n2hi, n2lo_f, rc, M, C, cspec_.eps, w.ffn_norm_w, st));
-        HIPC(gemm3_store(ops3(n2, rc, w.w1, M, pf), ACT_GELU, store_split_to(hid.as(pf, sf), rf, w.b1), 1, pf, st));
+        HIPC(gemm3_store(ops3(n2, rc, w.w1, M, pf), ACT_GELU, store_split_to(hid.as(pf, sf), rf, w.b1), 1, pf, st, tune_));
     } else {  // K = C < 64 (last stage, C = 32): one k-tile on the fp32-A kernel, still writing the split hidden
         HIPC(launch_rmsnorm(x, img, nbuf, nullptr, nullptr, img, M, C, cspec_.eps, w.ffn_norm_w, st));
-        HIPC(gemm_store(ops(nbuf, img, w.w1, M), ACT_GELU, store_split_to(hid.as(pf, sf), rf, w.b1), 1, pf, st));
+        HIPC(gemm_store(ops(nbuf, img, w.w1, M), ACT_GELU, store_split_to(hid.as(pf, sf), rf, w.b1), 1, pf, st, tune_));
     }
     EpiResid<0> r{x, img, w.b2, w.ffn_gamma, 0, 0, 0, 1, nullptr};
     {
         // M = 600 against a wide-K second product (the coarsest stage: 600 x 2048 x 8192): 160x128 tiles cut K so that ONE round
         // of workgroups fills the chip; fp32 partials go to the (now dead) n2 buffer, one pass reduces them in a fixed order
         // and applies bias / LayerScale / residual (same deterministic scheme as the DiT projections)
-        extern int g_gemm3_t160;
         const long t160 = (long)((M + 159) / 160) * ((C + 127) / 128);
         const int nk = F / 64;
         int splits = t160 > 0 && t160 <= 128 ? (int)(256 / t160) : 1;
         if (splits > nk / 8) splits = nk / 8;
-        if (g_gemm3_t160 && M > 480 && M <= 640 && splits >= 2 && (size_t)splits * M * C * 2 <= n2_elems && C % 4 == 0) {
+        if (tune_.t160 && M > 480 && M <= 640 && splits >= 2 && (size_t)splits * M * C * 2 <= n2_elems && C % 4 == 0) {
             float* part = reinterpret_cast<float*>(n2hi);  // n2hi holds n2_elems bf16 = n2_elems / 2 floats
-            HIPC(gemm3_resid_splitk(ops3(hid, rf, w.w2, M, pf), r, part, splits, pf, st, NextLN(), G3_160x128));
+            HIPC(gemm3_resid_splitk(ops3(hid, rf, w.w2, M, pf), r, part, splits, pf, st, tune_, NextLN(), G3_160x128));
             return 0;
         }
     }
     {
         // fewer rows still (the codec ENCODER's coarse stages on 2-s references: 120 x 2048 x 8192 is 64 tiles that each walk the
         // whole K: 47 us at 0.7 TB/s of weights): K slices on 64x64 tiles + the same reduce
-        const int splits = M <= 480 ? small_m_splits(M, F, 8, 1) : 1;
+        const int splits = small_m_splitk_ && M <= 480 ? small_m_splits(M, F, 8, 1) : 1;
         if (splits >= 2 && fused_ffn_ && (size_t)splits * M * C * 2 <= n2_elems && C % 4 == 0) {
             float* part = reinterpret_cast<float*>(n2hi);
-            HIPC(gemm3_resid_splitk(ops3(hid, rf, w.w2, M, pf), r, part, splits, pf, st, NextLN(), G3_64x64));
+            HIPC(gemm3_resid_splitk(ops3(hid, rf, w.w2, M, pf), r, part, splits, pf, st, tune_, NextLN(), G3_64x64));
             return 0;
         }
     }
-    HIPC(gemm3_resid(ops3(hid, rf, w.w2, M, pf), 2, r, pf, st));
+    HIPC(gemm3_resid(ops3(hid, rf, w.w2, M, pf), 2, r, pf, st, tune_));
     return 0;
 }
 
@@ -1894,7 +1873,7 @@ int Engine::decode_stem(hipStream_t st, const CodecWs& w, const float* latents, 
     HIPC(launch_zero_pad_frames3(w.xa, w.xb, w.nb, B, T, C, pad, st));
     RowMap am = rowmap_batched(L, T, (long)(pad + T) * L, (long)(pad - (Kc - 1)) * L);
     RowMap om = rowmap_batched(C, T, (long)(pad + T) * C, (long)pad * C);
-    HIPC(gemm_store(ops(w.lat, am, dec_.stem, B * T), ACT_NONE, store_to(w.xa, om, dec_.stem_b), 1, pcv3, st));
+    HIPC(gemm_store(ops(w.lat, am, dec_.stem, B * T), ACT_NONE, store_to(w.xa, om, dec_.stem_b), 1, pcv3, st, tune_));
     return 0;
 }
 
@@ -1916,7 +1895,7 @@ int Engine::decode_stage(hipStream_t st, const CodecWs& w, int i, int what, floa
         RowMap om = rowmap_batched((long)r * Cn, Ti, (long)(pad + Tn) * Cn, (long)pad * Cn);
         if (fused_ffn_ && codec_upsample_wave_ok(sg.resample.K, sg.resample.N) && sg.resample.K == 2 * C && sg.resample.N == r * Cn)
             HIPC(launch_codec_upsample_wave(x, am, sg.resample.hi, sg.resample.lo, sg.resample.K, sg.resample_bias, xn, om,
-                                            B * Ti, sg.resample.K, sg.resample.N, pcv3, st));
+                                            B * Ti, sg.resample.K, sg.resample.N, pcv3, st, tune_));
         else if (pcv == PREC_F16X2 && sg.resample.l16 && sg.resample.K % 64 == 0 && sg.resample.K >= x2_mink_ && sg.resample.K <= x2_maxk_ &&
                  C % 8 == 0 && (size_t)B * (pad + Ti) * C <= w.max_img) {
             // two-pass fp16 product: the image once as ONE fp16 array (pads included: the causal zeros), the weights as an fp16
@@ -1924,16 +1903,16 @@ int Engine::decode_stage(hipStream_t st, const CodecWs& w, int i, int what, floa
             HIPC(launch_to_split(x, rowmap_plain(C), w.n2hi, sm_lo_for(PREC_F16, nullptr, satp(SITE_CODEC_CONV)), rowmap_plain(C), B * (pad + Ti), C, st));
             Gemm3Operands g3 = ops3(SplitBuf{w.n2hi, w.n2lo}, am, sg.resample, B * Ti, PREC_F16);
             g3.Wlo = sg.resample.l16;
-            HIPC(gemm3_store_x2(g3, store_to(xn, om, sg.resample_bias), st));
+            HIPC(gemm3_store_x2(g3, store_to(xn, om, sg.resample_bias), st, tune_));
         } else if (fused_ffn_ && sg.resample.K % 64 == 0 && sg.resample.K >= up_g3_mink_ && C % 8 == 0 && (size_t)B * (pad + Ti) * C <= w.max_img) {
             const int pg = pcv == PREC_F16X2 ? PREC_BF16X3 : pcv;   // (f16x2 outside its K range: split-bf16)
             // widest stages (K >= 2048; measured: 215 -> 148 us and 216 -> 193 us, no gain at K <= 1024): split the image once (pads included: they are the causal zeros) and run the DMA-ring GEMM on
             // the overlapping rows of the split pair (n2 is free between blocks)
             SplitBuf xs{w.n2hi, w.n2lo};
             HIPC(launch_to_split(x, rowmap_plain(C), xs.hi, xs.as(pg, satp(SITE_CODEC_CONV)).lo, rowmap_plain(C), B * (pad + Ti), C, st));
-            HIPC(gemm3_store(ops3(xs, am, sg.resample, B * Ti, pg), ACT_NONE, store_to(xn, om, sg.resample_bias), 1, pg, st));
+            HIPC(gemm3_store(ops3(xs, am, sg.resample, B * Ti, pg), ACT_NONE, store_to(xn, om, sg.resample_bias), 1, pg, st, tune_));
         } else
-            HIPC(gemm_store(ops(x, am, sg.resample, B * Ti), ACT_NONE, store_to(xn, om, sg.resample_bias), 1, pcv3, st));
+            HIPC(gemm_store(ops(x, am, sg.resample, B * Ti), ACT_NONE, store_to(xn, om, sg.resample_bias), 1, pcv3, st, tune_));
         float* t = x; x = xn; xn = t;
         Ti = Tn;
         C = Cn;
@@ -1969,8 +1948,6 @@ int Engine::decode_head(hipStream_t st, const CodecWs& w, const float* x, int B,
 }
 
 int Engine::codec_decode(hipStream_t st, const float* latents, int B, int T, float* audio, void* ws, size_t ws_bytes) {
-    DeepScope deep_scope(gemm_deep_);
-    PersistScope persist_scope(persist_cus_);
     if (!dec_.ready) return fail("codec_decode: decoder weights not finalized");
     const CodecPlan plan = codec_plan(true, B, T);
     if (ws_bytes < codec_ws_bytes(plan)) return fail("codec_decode: workspace too small");
@@ -1998,13 +1975,13 @@ size_t Engine::encode_ws_bytes(int B, int S_) const { return codec_ws_bytes(code
 int Engine::conv_small_m(hipStream_t st, const CodecWs& w, const float* img, long img_rows, int Cin, const RowMap& am, const PW& wt,
                          const float* bias, float* out, const RowMap& om, int M) {
     const int pcv = prec_[SITE_CODEC_CONV];
-    const int splits = (fused_ffn_ && wt.K >= 2048) ? small_m_splits(M, wt.K, 8, 4) : 1;
+    const int splits = (small_m_splitk_ && fused_ffn_ && wt.K >= 2048) ? small_m_splits(M, wt.K, 8, 4) : 1;
     if (splits < 2 || wt.K % 64 || Cin % 4 || wt.N % 4 || (size_t)img_rows * Cin > w.max_img || (size_t)splits * M * wt.N * 2 > w.max_hid)
         return 0;
     SplitBuf xs{w.n2hi, w.n2lo};
     float* part = reinterpret_cast<float*>(w.hhi);   // max_hid bf16 = max_hid / 2 floats
     hipError_t e = launch_to_split(img, rowmap_plain(Cin), xs.hi, xs.as(pcv, satp(SITE_CODEC_CONV)).lo, rowmap_plain(Cin), (int)img_rows, Cin, st);
-    if (e == hipSuccess) e = gemm3_store_splitk(ops3(xs, am, wt, M, pcv), part, splits, pcv, bias, out, om, st);
+    if (e == hipSuccess) e = gemm3_store_splitk(ops3(xs, am, wt, M, pcv), part, splits, pcv, bias, out, om, st, tune_);
     if (e != hipSuccess) { fail_hip(e, "codec_encode: split-K conv"); return -1; }
     return 1;
 }
@@ -2034,7 +2011,7 @@ int Engine::encode_stage(hipStream_t st, const CodecWs& w, int i, int what, floa
         RowMap om = rowmap_batched(Cn, Tn, (long)(pad + Tn) * Cn, (long)pad * Cn);
         const int took = conv_small_m(st, w, x, (long)B * (pad + Ti), C, am, sg.resample, sg.resample_bias, xn, om, B * Tn);
         if (took < 0) return 1;
-        if (!took) HIPC(gemm_store(ops(x, am, sg.resample, B * Tn), ACT_NONE, store_to(xn, om, sg.resample_bias), 1, pcv3, st));
+        if (!took) HIPC(gemm_store(ops(x, am, sg.resample, B * Tn), ACT_NONE, store_to(xn, om, sg.resample_bias), 1, pcv3, st, tune_));
         float* t = x; x = xn; xn = t;
         Ti = Tn;
         C = Cn;
@@ -2069,13 +2046,11 @@ int Engine::encode_head(hipStream_t st, const CodecWs& w, const float* x, int B,
     if (took < 0) return 1;
     if (!took)
         HIPC(gemm_store(ops(x, am, enc_.head, B * Ti), ACT_NONE, store_to(latents, rowmap_plain(cspec_.latent_dim), enc_.head_b), 1,
-                        pcv3, st));
+                        pcv3, st, tune_));
     return 0;
 }
 
 int Engine::codec_encode(hipStream_t st, const float* audio, int B, int S_, float* latents, void* ws, size_t ws_bytes) {
-    DeepScope deep_scope(gemm_deep_);
-    PersistScope persist_scope(persist_cus_);
     if (!enc_.ready) return fail("codec_encode: encoder weights not finalized");
     const CodecPlan plan = codec_plan(false, B, S_);
     if (ws_bytes < codec_ws_bytes(plan)) return fail("codec_encode: workspace too small");
@@ -2097,8 +2072,6 @@ int Engine::codec_encode(hipStream_t st, const float* audio, int B, int S_, floa
 // smallest whole call that contains this stage geometry: what that call's dispatch would run on these frames, this runs
 int Engine::test_codec_stage(hipStream_t st, int part, int stage, int what, const float* xin, int B, int T_in, int C_in, float* out,
                              int* T_out, int* C_out) {
-    DeepScope deep_scope(gemm_deep_);
-    PersistScope persist_scope(persist_cus_);
     if (part != 1 && part != 2) return fail("test_codec_stage: part must be 1 (decoder) or 2 (encoder)");
     const bool dec = part == 1;
     const CodecHalfW& h = dec ? dec_ : enc_;
@@ -2184,7 +2157,6 @@ int Engine::test_dit_stage(hipStream_t st, int net, int what, int l0, int l1, in
                            int mod_rstride, const float* k_ref, const float* v_ref, const uint8_t* ref_mask, int R,
                            const float* k_text, const float* v_text, const uint8_t* ph_mask, int P, const float* rope,
                            float* x_out, float* img_out, float* shift_out, float* out, float* k_out, float* v_out, float* mod_out) {
-    DeepScope deep_scope(gemm_deep_);
     if (!dit_ready_) return fail("test_dit_stage: DiT weights not finalized");
     if (net < 0 || net > 2) return fail("test_dit_stage: net must be 0 (DiT), 1 (style encoder) or 2 (text encoder)");
     if (what <= 0 || what > 15) return fail("test_dit_stage: `what` must be a non-empty set of the bits 1, 2, 4, 8");
@@ -2374,7 +2346,6 @@ int Engine::test_dit_stage(hipStream_t st, int net, int what, int l0, int l1, in
 // ---------------------------------------------------------------------------------------------
 int Engine::test_gemm(hipStream_t st, const float* A, int lda, const float* W, const float* bias, int M, int N, int K,
                       int act, int split, int cfg, float* C, int ldc) {
-    DeepScope deep_scope(gemm_deep_);
     HIPC(hipSetDevice(device_));
     bf16_t *hi = nullptr, *lo = nullptr;
     HIPC(hipMalloc(&hi, (size_t)N * K * 2));
@@ -2382,7 +2353,7 @@ int Engine::test_gemm(hipStream_t st, const float* A, int lda, const float* W, c
     HIPC(launch_split_rows(W, K, hi, lo, K, N, K, nullptr, st));
     PW w;
     w.hi = hi; w.lo = lo; w.N = N; w.K = K;
-    hipError_t e = gemm_store(ops(A, rowmap_plain(lda), w, M), act, store_to(C, rowmap_plain(ldc), bias), 1, split, st, cfg);
+    hipError_t e = gemm_store(ops(A, rowmap_plain(lda), w, M), act, store_to(C, rowmap_plain(ldc), bias), 1, split, st, tune_, cfg);
     (void)hipStreamSynchronize(st);
     (void)hipFree(hi);
     (void)hipFree(lo);
@@ -2391,7 +2362,6 @@ int Engine::test_gemm(hipStream_t st, const float* A, int lda, const float* W, c
 
 int Engine::test_gemm3(hipStream_t st, const float* A, const float* W, const float* bias, int M, int N, int K, int act,
                        int split, int cfg, float* C) {
-    DeepScope deep_scope(gemm_deep_);
     HIPC(hipSetDevice(device_));
     bf16_t *hi = nullptr, *lo = nullptr, *ahi = nullptr, *alo = nullptr;
     HIPC(hipMalloc(&hi, (size_t)N * K * 2));
@@ -2404,7 +2374,7 @@ int Engine::test_gemm3(hipStream_t st, const float* A, const float* W, const flo
     PW w;
     w.hi = hi; w.lo = lo; w.h16 = hi; w.N = N; w.K = K;
     hipError_t e = gemm3_store(ops3(SplitBuf{ahi, alo}, rowmap_plain(K), w, M, split), act, store_to(C, rowmap_plain(N), bias), 1,
-                               split, st, cfg);
+                               split, st, tune_, cfg);
     (void)hipStreamSynchronize(st);
     for (void* p : {(void*)hi, (void*)lo, (void*)ahi, (void*)alo}) (void)hipFree(p);
     return e == hipSuccess ? 0 : fail_hip(e, "test_gemm3");
@@ -2416,7 +2386,6 @@ int Engine::test_gemm3(hipStream_t st, const float* A, const float* W, const flo
 int Engine::test_ln_fold(hipStream_t st, const float* A, const float* Wp, const float* bp, const float* gate, const uint8_t* mask,
                          const float* nscale, const float* shift, const float* W1, const float* W3, const float* b1, const float* b3,
                          int M, int K, int D, int F, float eps, int rms, int prec, int fold, float* x, float* h, float* c_out) {
-    DeepScope deep_scope(gemm_deep_);
     HIPC(hipSetDevice(device_));
     if (M <= 0 || K % 64 || D % 32 || F % 32 || F <= 0) return fail("test_ln_fold: M > 0, K % 64 == 0, D % 32 == 0, F % 32 == 0");
     if (prec != PREC_BF16 && prec != PREC_F16 && prec != PREC_BF16X3) return fail("test_ln_fold: precision must be 1, 2 or 3");
@@ -2478,21 +2447,21 @@ int Engine::test_ln_fold(hipStream_t st, const float* A, const float* Wp, const 
             }
             float* const csh = !rms && LN_FOLD_SHIFT ? cs : nullptr;
             EpiResidLN p{x, rd, bp, gate, mask, nscale, y.hi, y.lo, D, part, NP, rms, csh};
-            LNF(gemm3_resid_ln(ops3(SplitBuf{a_hi, a_lo}, rowmap_plain(K), wp, M, prec), p, prec, st));
+            LNF(gemm3_resid_ln(ops3(SplitBuf{a_hi, a_lo}, rowmap_plain(K), wp, M, prec), p, prec, st, tune_));
             LnFoldIn fin;
             fin.part = part; fin.NP = NP; fin.inv_c = 1.0f / D; fin.eps = eps; fin.rms = rms;
             if (!rms) { fin.wsh = tab; fin.wc = tab + 2 * F; fin.cshift = csh; fin.nh = F; }
             sw.fold = fin;
         } else {
             EpiResid<0> r{x, rd, bp, gate, 0, 0, 0, M, mask};
-            LNF(gemm3_resid(ops3(SplitBuf{a_hi, a_lo}, rowmap_plain(K), wp, M, prec), gate ? 2 : 0, r, prec, st));
+            LNF(gemm3_resid(ops3(SplitBuf{a_hi, a_lo}, rowmap_plain(K), wp, M, prec), gate ? 2 : 0, r, prec, st, tune_));
             if (rms) {
                 LNF(launch_rmsnorm(x, rd, nullptr, y.hi, y.lo, rd, M, D, eps, nscale, st));
             } else {
                 LNF(launch_ln_modulate(x, nullptr, y.hi, y.lo, M, D, eps, shift, nscale, 0, 0, 0, M, st));
             }
         }
-        LNF(gemm3_swiglu(ops3(y, rd, w13, M, prec), sw, prec, st));
+        LNF(gemm3_swiglu(ops3(y, rd, w13, M, prec), sw, prec, st, tune_));
         LNF(launch_split_to_f32(ffh.hi, ffh.lo, h, (long)M * F, st));
         if (c_out) {   // the row shift as the consumer left it for the next producer (0 where the step has none)
             if (sw.fold.cshift) LNF(hipMemcpyAsync(c_out, sw.fold.cshift, (size_t)M * 4, hipMemcpyDeviceToDevice, st));
@@ -2509,7 +2478,6 @@ int Engine::test_ln_fold(hipStream_t st, const float* A, const float* Wp, const 
 
 int Engine::test_swiglu(hipStream_t st, const float* A, const float* W1, const float* W3, const float* b1,
                         const float* b3, int M, int F, int K, int split, float* out) {
-    DeepScope deep_scope(gemm_deep_);
     HIPC(hipSetDevice(device_));
     if (F % 32) return fail("test_swiglu: F must be a multiple of 32");
     float* cat = nullptr;
@@ -2528,7 +2496,7 @@ int Engine::test_swiglu(hipStream_t st, const float* A, const float* W1, const f
     w.hi = hi; w.lo = lo; w.N = 2 * F; w.K = K;
     EpiSwiGLU sw{out, F, b1, b3, nullptr, nullptr};
 #ifdef SMTTS_TEST_KERNELS
-    hipError_t e = gemm_swiglu(ops(A, rowmap_plain(K), w, M), sw, split, st);
+    hipError_t e = gemm_swiglu(ops(A, rowmap_plain(K), w, M), sw, split, st, tune_);
 #else
     hipError_t e = hipErrorNotSupported;   // (the v1 SwiGLU instantiations are test kernels: make TEST_KERNELS=1)
 #endif
@@ -2539,7 +2507,6 @@ int Engine::test_swiglu(hipStream_t st, const float* A, const float* W1, const f
 
 // epi: 0 store, 1 store+gelu, 2 swiglu (N = packed 2F), 3 resid tanh-gate
 int Engine::bench_gemm(int M, int N, int K, int epi, int split, int cfg, int iters, int ver, float* avg_us) {
-    DeepScope deep_scope(gemm_deep_);
     HIPC(hipSetDevice(device_));
     float *A = nullptr, *Wf = nullptr, *C = nullptr, *bias = nullptr, *gate = nullptr;
     bf16_t *hi = nullptr, *lo = nullptr, *ahi = nullptr, *alo = nullptr;
@@ -2573,30 +2540,30 @@ int Engine::bench_gemm(int M, int N, int K, int epi, int split, int cfg, int ite
     auto run = [&]() -> hipError_t {
         if (ver == 3) {
             switch (epi) {
-                case 0: return gemm3_store(g3, ACT_NONE, store_to(C, rowmap_plain(N), bias), 1, split, 0, cfg);
-                case 1: return gemm3_store(g3, ACT_GELU, store_to(C, rowmap_plain(N), bias), 1, split, 0, cfg);
-                case 2: { EpiSwiGLU sw{C, N / 2, bias, bias, nullptr, nullptr}; return gemm3_swiglu(g3, sw, split, 0); }
+                case 0: return gemm3_store(g3, ACT_NONE, store_to(C, rowmap_plain(N), bias), 1, split, 0, tune_, cfg);
+                case 1: return gemm3_store(g3, ACT_GELU, store_to(C, rowmap_plain(N), bias), 1, split, 0, tune_, cfg);
+                case 2: { EpiSwiGLU sw{C, N / 2, bias, bias, nullptr, nullptr}; return gemm3_swiglu(g3, sw, split, 0, tune_); }
                 case 4: {   // GELU hidden written as ONE 16-bit operand array (the codec's first FFN product): C is reused as that array
                     EpiStore<ACT_NONE> e{nullptr, rowmap_plain(N), 0, bias, 0, 1.f, nullptr, reinterpret_cast<bf16_t*>(C), sm_lo_for(split == PREC_BF16X3 ? PREC_F16 : split, nullptr)};
-                    return gemm3_store(g3, ACT_GELU, e, 1, split, 0, cfg);
+                    return gemm3_store(g3, ACT_GELU, e, 1, split, 0, tune_, cfg);
                 }
-                case 5: { EpiResid<0> r{C, rowmap_plain(N), bias, gate, 0, 0, 0, M, nullptr}; return gemm3_resid(g3, 2, r, split, 0, cfg); }   // LayerScale residual (codec FF2)
-                case 6: return gemm3_store(g3, ACT_NONE, store_to(C, rowmap_plain(N), nullptr), 1, split, 0, cfg);   // no bias: what a split-K slice stores
+                case 5: { EpiResid<0> r{C, rowmap_plain(N), bias, gate, 0, 0, 0, M, nullptr}; return gemm3_resid(g3, 2, r, split, 0, tune_, cfg); }   // LayerScale residual (codec FF2)
+                case 6: return gemm3_store(g3, ACT_NONE, store_to(C, rowmap_plain(N), nullptr), 1, split, 0, tune_, cfg);   // no bias: what a split-K slice stores
                 case 7: case 9: {   // LN-fold producer (the DiT's out-proj with a row mask / FF2 without): residual + next operand image + row partials
                     EpiResidLN r{C, rowmap_plain(N), bias, gate, epi == 7 ? maskb : nullptr, bias, yimg, sm_lo_for(split == PREC_BF16X3 ? PREC_F16 : split, nullptr), N, partb, N / 32};
-                    return gemm3_resid_ln(g3, r, split, 0, cfg);
+                    return gemm3_resid_ln(g3, r, split, 0, tune_, cfg);
                 }
-                case 8: { EpiResid<0> r{C, rowmap_plain(N), bias, gate, 0, 0, 0, M, maskb}; return gemm3_resid(g3, 1, r, split, 0, cfg); }   // tanh-gated residual with a row mask
-                default: { EpiResid<0> r{C, rowmap_plain(N), bias, gate, 0, 0, 0, M, nullptr}; return gemm3_resid(g3, 1, r, split, 0, cfg); }
+                case 8: { EpiResid<0> r{C, rowmap_plain(N), bias, gate, 0, 0, 0, M, maskb}; return gemm3_resid(g3, 1, r, split, 0, tune_, cfg); }   // tanh-gated residual with a row mask
+                default: { EpiResid<0> r{C, rowmap_plain(N), bias, gate, 0, 0, 0, M, nullptr}; return gemm3_resid(g3, 1, r, split, 0, tune_, cfg); }
             }
         }
         switch (epi) {
-            case 0: return gemm_store(g, ACT_NONE, store_to(C, rowmap_plain(N), bias), 1, split, 0, cfg);
-            case 1: return gemm_store(g, ACT_GELU, store_to(C, rowmap_plain(N), bias), 1, split, 0, cfg);
+            case 0: return gemm_store(g, ACT_NONE, store_to(C, rowmap_plain(N), bias), 1, split, 0, tune_, cfg);
+            case 1: return gemm_store(g, ACT_GELU, store_to(C, rowmap_plain(N), bias), 1, split, 0, tune_, cfg);
 #ifdef SMTTS_TEST_KERNELS
-            case 2: { EpiSwiGLU sw{C, N / 2, bias, bias, nullptr, nullptr}; return gemm_swiglu(g, sw, split, 0); }
+            case 2: { EpiSwiGLU sw{C, N / 2, bias, bias, nullptr, nullptr}; return gemm_swiglu(g, sw, split, 0, tune_); }
 #endif
-            default: { EpiResid<0> r{C, rowmap_plain(N), bias, gate, 0, 0, 0, M, nullptr}; return gemm_resid(g, 1, r, split, 0, cfg); }
+            default: { EpiResid<0> r{C, rowmap_plain(N), bias, gate, 0, 0, 0, M, nullptr}; return gemm_resid(g, 1, r, split, 0, tune_, cfg); }
         }
     };
     for (int i = 0; i < 3; ++i) HIPC(run());

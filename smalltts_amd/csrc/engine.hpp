@@ -342,13 +342,14 @@ class Engine {
     std::vector<void*> pack_allocs_;  // everything finalize() builds: freed and rebuilt by the next finalize()
     bool packing_ = false;
     int tuning_ = TUNE_LATENCY;
-    int gemm_deep_ = 1;   // gemm3 ring depth of this engine's launches (1 deep — both tunings since round 3; 0 shallow: SMTTS_GEMM_DEEP / SMTTS_GEMM_DEEP_TP); installed per operator call (DeepScope)
-    int persist_cus_ = 0;        // grid cap of the persistent codec kernels for this engine's calls (0 = one workgroup per CU): 0 under latency tuning,
+    LaunchTuning tune_;          // what every launcher that reads tuning is handed next to the stream (common.hpp).  set_tuning() moves two fields: the ring
+                                 // depth (1 under both tunings since round 3; SMTTS_GEMM_DEEP) and the persistent codec grids' cap: 0 under latency tuning,
     int persist_cus_tp_ = 192;   // this under throughput tuning (SMTTS_PERSIST_CUS; profiles/r03ac_*, r03ad_*)
     bool dual_stream_latency_ = true;  // the dual-stream setting that TUNE_LATENCY restores
     int preset_ = kDefaultPrecision;   // set_precision(kDefaultPrecision) in the constructor fills prec_
     int prec_[SITE_COUNT] = {3, 3, 3, 3, 3, 3, 3, 3};
     bool fused_ffn_ = true;  // test hook: smtts_test_set_fused_ffn
+    bool small_m_splitk_ = true;   // SMTTS_SMALLM_SPLITK=0: A/B switch for the K-sliced small-M products of the codec
     int chain_min_run_ = 16;   // ... and decodes of at least this many tiles per wave of the chain's grid (codec_stage_chain)
     int chain_min_blocks_ = 2; // ... for stages of at least this many blocks (a single block gains nothing from the chain's contiguous walk; SMTTS_CHAIN_MIN=1: debugging)
     bool stage_chain_ = true; // codec stages with C = 32: all blocks of the stage in ONE launch (SMTTS_STAGE_CHAIN=0: one launch per block)

@@ -24,7 +24,7 @@ struct GemmOperands {
     int M, N, K;
     long a_z, w_z;  // per-blockIdx.z element strides
     int w_zmod;     // weights use (z % w_zmod) * w_z when non-zero (grouped conv: z = batch*G + group)
-    int xcd_order = 1;  // unbatched launches: XCD-aware tile order (set by gemm_launch from g_gemm_xcd; A/B switch)
+    int xcd_order = 1;  // unbatched launches: XCD-aware tile order (set by gemm_launch from LaunchTuning::xcd; A/B switch)
 };
 
 __device__ __forceinline__ void split4(const float4& v, uint2& hi, uint2& lo) {
@@ -1008,11 +1008,10 @@ static inline hipError_t gemm_launch_split(const GemmOperands& g, const Epi& epi
 // variant: PREC_F16 runs as split-bf16 here (its OUTPUT may still be written in any operand format, see store_act1).
 template <class Epi>
 static inline hipError_t gemm_launch(const GemmOperands& g_in, const Epi& epi, int Z, int split, hipStream_t st,
-                                     int cfg = -1) {
+                                     const LaunchTuning& tu, int cfg = -1) {
     if (g_in.M <= 0 || g_in.N <= 0) return hipSuccess;
-    extern int g_gemm_xcd;
     GemmOperands g = g_in;
-    g.xcd_order = g_gemm_xcd;
+    g.xcd_order = tu.xcd;
     if (cfg < 0) cfg = gemm_pick_cfg(g.M, g.N, g.K, Epi::PAIRED);
     if (split != PREC_BF16) return gemm_launch_split<3, Epi>(g, epi, Z, cfg, st);
     return gemm_launch_split<1, Epi>(g, epi, Z, cfg, st);

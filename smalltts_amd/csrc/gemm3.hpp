@@ -24,7 +24,7 @@ struct Gemm3Operands {
     long a_z, w_z;
     int w_zmod;
     int nfast = 0;     // tile order inside an XCD's run: 0 = M fastest, 1 = N fastest, G > 1 = bands of G row tiles (set by gemm3_launch)
-    int stage16 = 1;   // 16-bit outputs through the LDS-staged epilogue (set by gemm3_launch from g_gemm3_stage16; A/B switch)
+    int stage16 = 1;   // 16-bit outputs through the LDS-staged epilogue (set by gemm3_launch from LaunchTuning::stage16; A/B switch)
     int ksplit_tiles;  // > 0: blockIdx.z is a split-K index; this launch slice covers k-tiles [z*ksplit_tiles, +ksplit_tiles)
 };
 
@@ -393,13 +393,13 @@ template <class Epi> struct gemm4_enabled : std::false_type {};
 static inline bool gemm4_ok(const Gemm3Operands&) { return false; }
 #endif
 
-static inline int gemm3_pick_cfg(int M, int N, bool paired, bool single = false /* one array per operand (fp16 / bf16) */) {
-    extern int g_gemm3_w4_minm;   // single-array formats: 128x128 with four 64x64 waves from this M up (0 = never); split-bf16 falls back
+static inline int gemm3_pick_cfg(int M, int N, bool paired, bool single /* one array per operand (fp16 / bf16) */, const LaunchTuning& tu) {
+    // w4_minm: single-array formats run 128x128 with four 64x64 waves from this M up (0 = never); split-bf16 falls back
     // round 2 (profiles/r02k_ab_keepx_w4.txt) took the 4-wave tile for the wide, short-K first FFN product of the codec's GEMM stages
     // (24000 x 2048 x 512: 122 -> 98 us); with the LDS-staged 16-bit epilogue the 8-wave 128x128 tile now beats it on those very
     // shapes (round 3, profiles/r03j_gemm_codec_tile_sweep.txt: 101 vs 90 us, 4800 x 4096 x 1024: 69 vs 62 us) -> off by default
     // (SMTTS_GEMM_W4_MINM=<M> switches it back on); 256x256 and 256x128 tiles were measured there too and bought nothing.
-    if (g_gemm3_w4_minm > 0 && M >= g_gemm3_w4_minm && N >= 2048) return G3_128x128_W4;
+    if (tu.w4_minm > 0 && M >= tu.w4_minm && N >= 2048) return G3_128x128_W4;
     if (single && !paired && M >= 2048 && N >= 2048) return G3_128x128;
     if (paired) {
         // the SwiGLU pair epilogue needs 32x64 wave tiles: 128x128 or 160x128.  Single-array formats run two such workgroups per
@@ -413,10 +413,9 @@ static inline int gemm3_pick_cfg(int M, int N, bool paired, bool single = false 
     // cost model measured on MI355X: time ~ rounds(tiles / 256 CUs) x bytes ingested per workgroup / ~40 GB/s.
     // 128x128 moves the fewest bytes per flop; prefer it whenever it fills at least half the chip in ONE round or
     // many rounds (a 64x128 grid of 257..511 tiles costs two rounds, e.g. DiT QKVG: 300 tiles 36.5 us vs 150 tiles 29.5 us)
-    extern int g_gemm3_t160;
     const long t160 = (long)((M + 159) / 160) * ((N + 127) / 128);
-    if (g_gemm3_t160 && M <= 640 && M > 480 && t160 > 128 && t160 <= 256) return G3_160x128;
-    if (g_gemm3_t160 && M > 640 && N >= 128) {
+    if (tu.t160 && M <= 640 && M > 480 && t160 > 128 && t160 <= 256) return G3_160x128;
+    if (tu.t160 && M > 640 && N >= 128) {
         // rounds x measured time of one k-tile round (us: 64x128 1.03, 128x128 2.0, 160x128 2.37; one workgroup per CU each):
         // the 160-row tile wins where it saves a round, e.g. 4800 x 1024: 600 tiles of 64x128 = 3 rounds vs 240 = 1 round
         auto rounds = [](long t) { return (double)((t + 255) / 256); };
@@ -445,10 +444,9 @@ static inline int gemm3_pick_cfg(int M, int N, bool paired, bool single = false 
 // budget can hold twice the k-tiles in flight.  Measured (profiles/r02b_ab_ring_depth.txt, f16, M = 600): deep rings cut one
 // batch's latency (QKVG 25.4 -> 21.5 us, SwiGLU 22.7 -> 19.4, 64x64 16.0 -> 14.5; 14.8 -> 14.2 ms per batch one at a time)
 // but cost throughput with several batches in flight (10.1 -> 10.4 ms per batch): a workgroup that holds 128 KiB of LDS while
-// it waits on memory keeps the other streams' kernels off its CU.  Hence a run-time choice: g_gemm3_deep (Engine tuning mode).
+// it waits on memory keeps the other streams' kernels off its CU.  Hence a run-time choice: LaunchTuning::deep (Engine tuning mode).
 template <int SPLIT, class Epi>
-static inline hipError_t gemm3_launch_split(const Gemm3Operands& g, const Epi& epi, int Z, int cfg, hipStream_t st) {
-    extern thread_local int g_gemm3_deep;
+static inline hipError_t gemm3_launch_split(const Gemm3Operands& g, const Epi& epi, int Z, int cfg, hipStream_t st, const LaunchTuning& tu) {
     if constexpr (SPLIT == PREC_BF16 || SPLIT == PREC_F16) {
         // deep rings pay when the whole grid is resident at once (one latency-bound round); a grid of several rounds at the deep
         // ring's occupancy runs faster shallow with more workgroups per CU (teacher QKVG, 450 tiles of 128x128: 35.1 us deep — two
@@ -457,7 +455,7 @@ static inline hipError_t gemm3_launch_split(const Gemm3Operands& g, const Epi& e
                    bn = cfg == G4_256x256 ? 256 : cfg == G3_64x64 || cfg == G3_32x64 ? 64 : cfg == G3_64x32 ? 32 : 128;
         const long tiles = ((g.M + bm - 1) / bm) * ((g.N + bn - 1) / bn) * (Z > 0 ? Z : 1);
         const long deep_slots = cfg == G3_64x64 ? 512 : 256;
-        if (g_gemm3_deep && tiles <= deep_slots) {
+        if (tu.deep && tiles <= deep_slots) {
             switch (cfg) {
                 case G3_128x128:
                     return gemm3_launch_cfg<128, 128, 4, 2, SPLIT, 4, Epi>(g, epi, Z, st);
@@ -466,7 +464,7 @@ static inline hipError_t gemm3_launch_split(const Gemm3Operands& g, const Epi& e
                     break;
                 case G3_64x64:
                     if constexpr (epi_small_n<Epi>::value) {   // the DiT's N = 960 residual projections: 150 workgroups, one per CU — the LDS is there for a longer ring
-                        if (g_gemm3_deep >= 2) return gemm3_launch_cfg<64, 64, 2, 2, SPLIT, 8, Epi>(g, epi, Z, st);
+                        if (tu.deep >= 2) return gemm3_launch_cfg<64, 64, 2, 2, SPLIT, 8, Epi>(g, epi, Z, st);
                     }
                     if constexpr (!Epi::PAIRED) return gemm3_launch_cfg<64, 64, 2, 2, SPLIT, 4, Epi>(g, epi, Z, st);
                     break;
@@ -482,7 +480,7 @@ static inline hipError_t gemm3_launch_split(const Gemm3Operands& g, const Epi& e
         // whole memory round trip (the grouped conv pos-embed: 31 k-tiles, 1.26 us each).  A grid that is resident at once (<= 256
         // workgroups, one per CU: 128 KiB of LDS) takes four stages (round 6)
         const long tiles64 = ((g.M + 63) / 64) * ((g.N + 63) / 64) * (Z > 0 ? Z : 1);
-        if (g_gemm3_deep && cfg == G3_64x64 && tiles64 <= 256) return gemm3_launch_cfg<64, 64, 2, 2, 3, 4, Epi>(g, epi, Z, st);
+        if (tu.deep && cfg == G3_64x64 && tiles64 <= 256) return gemm3_launch_cfg<64, 64, 2, 2, 3, 4, Epi>(g, epi, Z, st);
     }
     switch (cfg) {
 #ifdef SMTTS_LAB
@@ -510,51 +508,50 @@ static inline hipError_t gemm3_launch_split(const Gemm3Operands& g, const Epi& e
             if constexpr (SPLIT == PREC_BF16 || SPLIT == PREC_F16) return gemm3_launch_cfg<128, 128, 2, 2, SPLIT, 2, Epi>(g, epi, Z, st);
             break;
         case G3_64x32:
-            if constexpr (epi_small_n<Epi>::value && SPLIT != 3) return g_gemm3_deep >= 2 ? gemm3_launch_cfg<64, 32, 2, 1, SPLIT, 8, Epi>(g, epi, Z, st)
+            if constexpr (epi_small_n<Epi>::value && SPLIT != 3) return tu.deep >= 2 ? gemm3_launch_cfg<64, 32, 2, 1, SPLIT, 8, Epi>(g, epi, Z, st)
                                                                                          : gemm3_launch_cfg<64, 32, 2, 1, SPLIT, 4, Epi>(g, epi, Z, st);
             break;
         case G3_32x64:
-            if constexpr (epi_small_n<Epi>::value && SPLIT != 3) return g_gemm3_deep >= 2 ? gemm3_launch_cfg<32, 64, 1, 2, SPLIT, 8, Epi>(g, epi, Z, st)
+            if constexpr (epi_small_n<Epi>::value && SPLIT != 3) return tu.deep >= 2 ? gemm3_launch_cfg<32, 64, 1, 2, SPLIT, 8, Epi>(g, epi, Z, st)
                                                                                          : gemm3_launch_cfg<32, 64, 1, 2, SPLIT, 4, Epi>(g, epi, Z, st);
             break;
     }
     return hipErrorInvalidValue;
 }
 
+// The host-set switches of the kernel argument: the epilogue path and the tile order (w_elem_bytes: bytes per element of W over all
+// its arrays).  The bigger operand streams, the smaller stays in L2 — unless the smaller one does not fit there either (> 3 MB): bands
+static inline void gemm3_set_order(Gemm3Operands& g, double w_elem_bytes, const LaunchTuning& tu) {
+    g.stage16 = tu.stage16;
+    const double wbytes = (double)g.N * g.K * w_elem_bytes;
+    g.nfast = tu.nfast && (long)g.M > (long)g.N ? (tu.group > 1 && wbytes > 3e6 && g.M >= 1024 ? tu.group : 1) : 0;
+}
+
 template <class Epi>
 static inline hipError_t gemm3_launch(const Gemm3Operands& g_in, const Epi& epi, int Z, int split, hipStream_t st,
-                                      int cfg = -1) {
+                                      const LaunchTuning& tu, int cfg = -1) {
     const Gemm3Operands& g0 = g_in;
     if (g0.M <= 0 || g0.N <= 0) return hipSuccess;
     if (!gemm3_ok(g0)) return hipErrorInvalidValue;
-    if (cfg < 0) cfg = gemm3_pick_cfg(g0.M, g0.N, Epi::PAIRED, split != PREC_BF16X3);
-    extern int g_gemm3_nfast;
+    if (cfg < 0) cfg = gemm3_pick_cfg(g0.M, g0.N, Epi::PAIRED, split != PREC_BF16X3, tu);
     Gemm3Operands g = g_in;
-    extern int g_gemm3_stage16;
-    g.stage16 = g_gemm3_stage16;
-    // the bigger operand streams, the smaller stays in L2 — unless the smaller one does not fit there either (> 3 MB): bands
-    extern int g_gemm3_group;
-    const double wbytes = (double)g.N * g.K * (split == PREC_BF16X3 ? 4.0 : 2.0);
-    g.nfast = g_gemm3_nfast && (long)g.M > (long)g.N ? (g_gemm3_group > 1 && wbytes > 3e6 && g.M >= 1024 ? g_gemm3_group : 1) : 0;
+    gemm3_set_order(g, split == PREC_BF16X3 ? 4.0 : 2.0, tu);
     if ((cfg == G3_64x32 || cfg == G3_32x64) && (split == PREC_BF16X3 || !epi_small_n<Epi>::value)) cfg = G3_64x64;   // (no such instantiation)
     if (cfg == G4_256x256 && (split == PREC_BF16X3 || !gemm4_ok(g) || !gemm4_enabled<Epi>::value)) cfg = G3_128x128;   // (no such instantiation)
-    if (split == PREC_BF16X3) return gemm3_launch_split<3, Epi>(g, epi, Z, cfg == G3_128x128_W4 ? G3_128x128 : cfg, st);
-    if (split == PREC_F16) return gemm3_launch_split<2, Epi>(g, epi, Z, cfg, st);
-    return gemm3_launch_split<1, Epi>(g, epi, Z, cfg, st);
+    if (split == PREC_BF16X3) return gemm3_launch_split<3, Epi>(g, epi, Z, cfg == G3_128x128_W4 ? G3_128x128 : cfg, st, tu);
+    if (split == PREC_F16) return gemm3_launch_split<2, Epi>(g, epi, Z, cfg, st, tu);
+    return gemm3_launch_split<1, Epi>(g, epi, Z, cfg, st, tu);
 }
 
 // PREC_F16X2: one fp16 array of A (g.Ahi) against an fp16 hi + lo pair of W (g.Whi, g.Wlo) — two MFMA passes instead of the
 // three of split-bf16, A rounded to 11 bits, W exact to ~22.  Instantiated only where it is used (the codec's ConvTranspose
 // products, gemm3_store.hip): not part of gemm3_launch's run-time precision switch.
 template <class Epi>
-static inline hipError_t gemm3_launch_x2(const Gemm3Operands& g_in, const Epi& epi, int Z, hipStream_t st, int cfg = -1) {
+static inline hipError_t gemm3_launch_x2(const Gemm3Operands& g_in, const Epi& epi, int Z, hipStream_t st, const LaunchTuning& tu, int cfg = -1) {
     if (g_in.M <= 0 || g_in.N <= 0) return hipSuccess;
     if (!gemm3_ok(g_in) || !g_in.Wlo) return hipErrorInvalidValue;
-    if (cfg < 0) cfg = gemm3_pick_cfg(g_in.M, g_in.N, Epi::PAIRED, false);
-    extern int g_gemm3_nfast, g_gemm3_stage16, g_gemm3_group;
+    if (cfg < 0) cfg = gemm3_pick_cfg(g_in.M, g_in.N, Epi::PAIRED, false, tu);
     Gemm3Operands g = g_in;
-    g.stage16 = g_gemm3_stage16;
-    const double wbytes = (double)g.N * g.K * 4.0;
-    g.nfast = g_gemm3_nfast && (long)g.M > (long)g.N ? (g_gemm3_group > 1 && wbytes > 3e6 && g.M >= 1024 ? g_gemm3_group : 1) : 0;
-    return gemm3_launch_split<PREC_F16X2, Epi>(g, epi, Z, cfg == G3_128x128_W4 ? G3_128x128 : cfg, st);
+    gemm3_set_order(g, 4.0, tu);
+    return gemm3_launch_split<PREC_F16X2, Epi>(g, epi, Z, cfg == G3_128x128_W4 ? G3_128x128 : cfg, st, tu);
 }

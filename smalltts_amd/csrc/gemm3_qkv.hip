@@ -20,20 +20,18 @@ static hipError_t qkv_split(const Gemm3Operands& g, const E& p, int split, bool 
     return qkv_go<1>(g, p, big, deep, st);
 }
 
-hipError_t gemm3_qkv(const Gemm3Operands& g_in, const EpiQKV& p, int split, hipStream_t st) {
+hipError_t gemm3_qkv(const Gemm3Operands& g_in, const EpiQKV& p, int split, hipStream_t st, const LaunchTuning& tu) {
     if (g_in.M <= 0) return hipSuccess;
     if (!gemm3_ok(g_in) || g_in.N != 4 * p.H * p.HW || (p.HW != 64 && p.HW != 128) || (p.dh & 1) || p.dh > p.HW || (p.rot_dim & 1) ||
         p.rot_dim > p.dh || (g_in.N % 128))
         return hipErrorInvalidValue;
-    extern thread_local int g_gemm3_deep;
-    extern int g_gemm3_nfast;
     Gemm3Operands g = g_in;
-    g.nfast = g_gemm3_nfast && (long)g.M > (long)g.N;
+    g.nfast = tu.nfast && (long)g.M > (long)g.N;   // (this launcher's own rule: no bands, stage16 untouched — not gemm3_set_order)
     static const int big_minm = lab_env("SMTTS_QKV_BIG_MINM") ? atoi(lab_env("SMTTS_QKV_BIG_MINM")) : 641;   // A/B: 128x128 tiles from this many rows up
     const bool big = g.M >= big_minm;
     const long tiles = (long)((g.M + (big ? 127 : 63)) / (big ? 128 : 64)) * (g.N / 128);
-    const bool deep = g_gemm3_deep && split != PREC_BF16X3 && tiles <= 256;   // deep rings only while the grid is one resident round (gemm3_launch_split)
-    ProfScope ps(st, gemm3_prof_name(g, false, big ? G3_128x128 : G3_64x128, split, "qkv_img"), 2.0 * g.M * (double)g.N * g.K,
+    const bool deep = tu.deep && split != PREC_BF16X3 && tiles <= 256;   // deep rings only while the grid is one resident round (gemm3_launch_split)
+    ProfScope ps(st, gemm3_prof_name(g, false, big ? G3_128x128 : G3_64x128, split, "qkv_img", tu), 2.0 * g.M * (double)g.N * g.K,
                  (split == 3 ? 4.0 : 2.0) * ((double)g.M * g.K + (double)g.N * g.K) + (p.prec == PREC_BF16X3 ? 4.0 : 2.0) * g.M * (double)g.N,
                  gemm_bytes8d(4 * p.H * p.dh, g.K, 1));
     if (p.fold.part) {   // LN-fold consumer: its own instantiations

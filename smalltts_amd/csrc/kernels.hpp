@@ -187,7 +187,7 @@ hipError_t launch_zero_pad_frames3(float* x0, float* x1, float* x2 /* may be nul
 // C in {32, 64}: weights LDS-resident, wave-autonomous (codec_ffn_wave.hip); w1 [F][ld1], w2 [>= C][F]
 hipError_t launch_codec_ffn_wave(float* x, RowMap img, const float* norm_w, const bf16_t* w1hi, const bf16_t* w1lo, int ld1,
                                  const float* b1, const bf16_t* w2hi, const bf16_t* w2lo, const float* b2, const float* gamma,
-                                 int M, int C, int F, float eps, int split, hipStream_t st);
+                                 int M, int C, int F, float eps, int split, hipStream_t st, const LaunchTuning& tu);
 // C in {32, 64}: mixer + FFN of one codec block in ONE pass over the image (codec_ffn_wave.hip, MIX kernels): xout = block(xin)
 // all blocks of a C = 32 codec stage in one launch (codec_ffn_wave.hip, stage chain): per block the one-pass block's operands
 struct CodecChainBlock {
@@ -197,16 +197,16 @@ struct CodecChainBlock {
 };
 bool codec_chain_wave_ok(int C, int F, int K, int T, int split, int nb);
 hipError_t launch_codec_chain_wave(const float* xin, float* xout, RowMap img, const CodecChainBlock* blocks, int nb, int M, int C, int F, int K,
-                                   float eps, int split, hipStream_t st);
+                                   float eps, int split, hipStream_t st, const LaunchTuning& tu);
 bool codec_block_wave_ok(int C, int F, int K, int T, int split);
 hipError_t launch_codec_block_wave(const float* xin, float* xout, RowMap img, const float* mnorm_w, const float* dw_w, const float* dw_b,
                                    const float* mgamma, const float* norm_w, const bf16_t* w1hi, const bf16_t* w1lo, int ld1,
                                    const float* b1, const bf16_t* w2hi, const bf16_t* w2lo, const float* b2, const float* gamma, int M,
-                                   int C, int F, int K, float eps, int split, hipStream_t st);
+                                   int C, int F, int K, float eps, int split, hipStream_t st, const LaunchTuning& tu);
 // C in {128, 256}: weights streamed through an LDS ring (codec_ffn_stream.hip); w1 [F][C], w2t = launch_w2_tile_pack(W2 [C][F])
 hipError_t launch_codec_ffn_stream(float* x, RowMap img, const float* norm_w, const bf16_t* w1hi, const bf16_t* w1lo,
                                    const float* b1, const bf16_t* w2thi, const bf16_t* w2tlo, const float* b2, const float* gamma,
-                                   int M, int C, int F, float eps, int split, hipStream_t st);
+                                   int M, int C, int F, float eps, int split, hipStream_t st, const LaunchTuning& tu);
 hipError_t launch_w2_tile_pack(const bf16_t* in, bf16_t* out, int C, int F, hipStream_t st);
 
 
@@ -217,7 +217,7 @@ hipError_t launch_w2_tile_pack(const bf16_t* in, bf16_t* out, int C, int F, hipS
 // Streaming ConvTranspose1d-as-GEMM for the two finest codec stages (W resident in LDS, one wave per 32 rows): codec_upsample.hip
 bool codec_upsample_wave_ok(int K, int N);
 hipError_t launch_codec_upsample_wave(const float* x, RowMap amap, const bf16_t* whi, const bf16_t* wlo, int ldw, const float* bias,
-                                      float* out, RowMap omap, int M, int K, int N, int split, hipStream_t st);
+                                      float* out, RowMap omap, int M, int K, int N, int split, hipStream_t st, const LaunchTuning& tu);
 hipError_t launch_splitk_resid_ln(const float* part, int S, float* x, const float* bias, const float* gate, long gld,
                                   int grow0, int grstride, int rows_per_batch, const uint8_t* rowmask, int M, int N, float eps,
                                   const float* shift, const float* scale, bf16_t* yhi, bf16_t* ylo, hipStream_t st,
