@@ -53,7 +53,7 @@ int smtts_create(int device_id, smtts_handle* out);
 int smtts_destroy(smtts_handle h);
 const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation error */
 const char* smtts_version(void);
-/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
+/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, then smtts_take_scores and smtts_take_select, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
 #define SMTTS_ABI_VERSION 11
 int smtts_abi_version(void);
@@ -183,6 +183,47 @@ int smtts_sample_pinned(smtts_handle h, void* stream, int mode, int n_steps, int
  * 1 <= P <= 198 (the API's range), anything else is an error. */
 int smtts_align_path(smtts_handle h, void* stream, const float* mass, int B, int N, int P, const int32_t* n_len, const int32_t* p0,
                      const int32_t* p1, int32_t* spans, float* score);
+
+/* ---- takes (DESIGN.md '8d. Takes'): sample every row K times, keep the best-aligned take on the device ----------------------------
+ * smtts_take_scores, behind smtts_align_path on `stream`, one workgroup per row: mass f32 (B,N,P) (the tap), spans i32 (B,P,2) and
+ * path_score f32 (B) (smtts_align_path's outputs), n_len / p0 / p1 i32 (B), all DEVICE; n, p0, p1 are clamped exactly as
+ * smtts_align_path clamps them (n into [0, N], p0 and p1 into [0, P]), Pw = p1 - p0.  For a row with n > 0 and Pw > 0, with
+ * (first_p, last_p) = spans[b][p]: a span with first_p < 0 or last_p < first_p is EMPTY (length 0, and its token counts as skipped);
+ * of any other span both ends are clamped into [0, n - 1] before anything is indexed, and its length is last_p - first_p + 1 of the
+ * clamped ends.  Four integer features:
+ *     cells   = sum over p in [p0, p1) of the span lengths
+ *     skipped = number of p in [p0, p1) without a frame f in [first_p, last_p] with mass[b][f][p] >= tau_tok   (the span's peak stays
+ *               below the threshold; an empty span is skipped)
+ *     longest = max over p in [p0, p1) of the span lengths
+ *     idle    = number of frames f < n without a token p in [p0, p1) with mass[b][f][p] >= tau_frm
+ * Every comparison is made on one fp32 value: a value equal to the threshold attends, a NaN never does (a span of NaNs is skipped, a
+ * frame of NaNs is idle), and no reduction order can change a feature.  Then, as single correctly rounded fp32 operations in this
+ * order (no fma):
+ *     c0 = path_score[b] / (float)cells      c1 = (float)skipped / (float)Pw      c2 = (float)longest / (float)n
+ *     c3 = (float)idle / (float)n            total = ((w0 * c0 + w1 * c1) + w2 * c2) + w3 * c3
+ * Rows with n == 0 or Pw <= 0: features 0, total = +inf.  -> feat i32 (B,4) = (cells, skipped, longest, idle), total f32 (B); lower is
+ * better.  numpy float32 reproduces both bit for bit (the payload of a NaN total, e.g. from cells == 0, is not specified).  No index
+ * leaves the row whatever the buffers hold.  1 <= N <= 225, 1 <= P <= 198, 1 <= B <= 65536; the weights >= 0 and the thresholds not NaN.
+ *
+ * smtts_take_select: rows are piece-major, row = g * K + k, 1 <= K <= 16, B = G * K, 1 <= G <= 65535.  Key of a take: s' = isnan(total) ?
+ * +inf : total.  The winner of group g is the lowest k with the smallest s' (strict < walking k upward: ties and groups that are +inf
+ * throughout give k = 0).  Row g * K + winner of x f32 (B,N,64), n_len i32 (B) and, where given, spans i32 (B,P,2) and mass f32 (B,N,P)
+ * is copied to row g of x_win (G,N,64), n_win (G), spans_win (G,P,2), mass_win (G,N,P), bit for bit (16-byte lanes where a row's byte
+ * count and both base addresses allow, 4-byte elements otherwise: no alignment is required); winner i32 (G) = the k.  spans / spans_win
+ * and mass / mass_win are each given or NULL together; a NULL pair is skipped.  Inputs and outputs must not overlap.
+ *
+ * Both: an argument error (NULL handle or required pointer, B / G / K / N / P out of range, half an optional pair, a negative or NaN
+ * weight, a NaN threshold) returns 1 with a message naming the entry before anything is enqueued.  One launch each, no atomics, no
+ * synchronisation: two calls return the same bits.
+ * Only this mechanism is verified.  Whether the total ranks takes the way a listener would is UNVALIDATED on trained weights: every
+ * weight this project has run is seeded noise, the weights and thresholds the Python side passes by default (api.Takes) are design
+ * choices and not measurements, and the tap's layer / head selection they rest on is unvalidated in the same way. */
+int smtts_take_scores(smtts_handle h, void* stream, const float* mass, const int32_t* spans, const float* path_score, const int32_t* n_len,
+                      const int32_t* p0, const int32_t* p1, int B, int N, int P, float tau_tok, float tau_frm, float w0, float w1, float w2,
+                      float w3, int32_t* feat, float* total);
+int smtts_take_select(smtts_handle h, void* stream, const float* total, int G, int K, int N, int P, const float* x, const int32_t* n_len,
+                      const int32_t* spans /* or NULL */, const float* mass /* or NULL */, float* x_win, int32_t* n_win,
+                      int32_t* spans_win, float* mass_win, int32_t* winner);
 
 /* ---- codec ------------------------------------------------------------------------------------ */
 int smtts_codec_hop(smtts_handle h);

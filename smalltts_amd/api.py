@@ -290,6 +290,63 @@ def as_alignment(align) -> Optional["Alignment"]:
 ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS = 225, 198   # the range of smtts_align_path: 30 s of frames, the phoneme window
 
 
+class Takes:
+    """Best-of-K sampling (immutable; DESIGN 8d, include/smalltts_hip.h smtts_take_scores / smtts_take_select): every row is sampled
+    `k` times (1..16) from seeds take_seed(seed, 0 .. k-1), each take's text alignment is scored on the device and only the take with
+    the lowest total is decoded.  total = w0 * path cost per cell + w1 * skipped tokens / tokens + w2 * longest span / frames + w3 *
+    idle frames / frames with `weights` = (w0, w1, w2, w3), all >= 0; a token is skipped when no frame of its span gives it
+    `tau_token` of its attention, a frame is idle when it gives no token of the row `tau_frame`.
+
+    The defaults are design choices, not measurements.  What the score is worth is UNVALIDATED on trained weights: every weight this
+    project has run is seeded noise, nobody has measured whether the lowest total is the take a listener would keep, and the score
+    rests on the tap's layer / head selection (Alignment), which is unvalidated in the same way.  The mechanism is verified: the
+    features and the total (bit for bit against a numpy restatement), the selection, and that the winner's latents, audio and words
+    are those of the same row sampled alone."""
+    __slots__ = ("k", "weights", "tau_token", "tau_frame")
+    MAX_K, MAX_ROWS = 16, 64   # smtts_take_select's K; the largest sampler batch the tap is tested at
+
+    def __init__(self, k: int, weights: Sequence[float] = (1.0, 2.0, 1.0, 1.0), tau_token: float = 0.1, tau_frame: float = 0.1) -> None:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+            raise TypeError(f"Takes: k must be an integer, got {type(k).__name__}")
+        if not 1 <= int(k) <= self.MAX_K:
+            raise ValueError(f"Takes: k must lie in [1, {self.MAX_K}], got {int(k)}")
+        w = tuple(float(v) for v in weights)
+        if len(w) != 4 or not all(v >= 0.0 and np.isfinite(v) for v in w):
+            raise ValueError(f"Takes: weights must be four finite numbers >= 0, got {w}")
+        if not (np.isfinite(float(tau_token)) and np.isfinite(float(tau_frame))):
+            raise ValueError("Takes: tau_token and tau_frame must be finite")
+        set_ = object.__setattr__
+        set_(self, "k", int(k))
+        set_(self, "weights", w)
+        set_(self, "tau_token", float(tau_token))
+        set_(self, "tau_frame", float(tau_frame))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Takes is immutable")
+
+    __delattr__ = __setattr__
+
+    def __repr__(self) -> str:
+        return "Takes(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Takes) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self) -> int:
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
+def as_takes(takes) -> Optional["Takes"]:
+    """The `takes=` argument of the synthesis calls: None -> None (off), an int K -> Takes(K), a Takes -> itself."""
+    if takes is None:
+        return None
+    if isinstance(takes, Takes):
+        return takes
+    if isinstance(takes, (int, np.integer)) and not isinstance(takes, bool):
+        return Takes(int(takes))
+    raise TypeError(f"takes must be None, an int or a Takes, got {type(takes).__name__}")
+
+
 def token_groups(ids: Sequence[int]) -> List[Tuple[str, str, int, int]]:
     """The units word timings are reported for: runs of token ids between the space symbol.  -> [(kind, phonemes, t0, t1), ...] in
     order, [t0, t1) the run's token indices, phonemes = decode_token_ids of them.  kind "word": a run of letter / IPA symbols;
@@ -516,6 +573,14 @@ def piece_seed(seed: int, i: int) -> int:
     return int(np.random.SeedSequence([int(seed), int(i)]).generate_state(1, np.uint64)[0] >> 1)
 
 
+def take_seed(seed: int, k: int) -> int:
+    """Seed of take k of a row spoken from `seed`: take 0 is the row itself (take_seed(s, 0) == s), take k >= 1 draws from
+    SeedSequence([seed, k, 0x54414B45]) reduced to 63 bits (three words: never a piece_seed)."""
+    if int(k) == 0:
+        return int(seed)
+    return int(np.random.SeedSequence([int(seed), int(k), 0x54414B45]).generate_state(1, np.uint64)[0] >> 1)
+
+
 def _split_sources(weights) -> List[str]:
     if isinstance(weights, (list, tuple)):
         return [str(w) for w in weights]
@@ -631,7 +696,8 @@ class Voice:
 class _Batch(NamedTuple):
     """One batch on the device, enqueued on the stream that was current when it was made; nothing here has been read back.
     `rerun()` enqueues the same work again on the current stream (the fp16 range guard's second pass), the tap, the path and the
-    endpoints included when the record has them, and returns a new record; its closure keeps the batch's voices alive."""
+    endpoints included when the record has them, and returns a new record; its closure keeps the batch's voices alive.  With takes=
+    the rows are the winners: latents, mass and spans are those of the take kept for each row."""
     audio: torch.Tensor                  # (B, 1, HOP_SIZE * Nmax) fp32; causal decoder => row b is its first HOP_SIZE * ns[b] samples
     latents: torch.Tensor                # (B, Nmax, 64) fp32
     mass: Optional[torch.Tensor]         # align=: the tapped text attention (engine.sample), else None
@@ -640,6 +706,31 @@ class _Batch(NamedTuple):
     gain: Optional[torch.Tensor]         # endpoints: (B,) fp32, else None
     ns: List[int]                        # frames per row
     rerun: Callable[[], "_Batch"]
+    winner: Optional[torch.Tensor] = None  # takes=: (B,) int32, the take kept per row (engine.take_select); None with one take
+    total: Optional[torch.Tensor] = None   # takes=: (B * K,) fp32, every take's total, piece-major (engine.take_scores), else None
+    feat: Optional[torch.Tensor] = None    # takes=: (B * K, 4) int32 (cells, skipped, longest, idle), else None
+
+
+def _read_takes(recs: Sequence[_Batch], K: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
+    """What takes= left in finished batches, in ONE small read-back: -> (winner (n,) int32, totals (n, K) fp32, features (n, K, 4)
+    int32) over the rows of all records in order; a record without a winner table (one take) reports 0."""
+    parts = []
+    for rec in recs:
+        parts += [rec.total.view(torch.int32), rec.feat.reshape(-1)] + ([] if rec.winner is None else [rec.winner])
+    flat = torch.cat(parts).cpu().numpy()
+    wins, tots, feats, pos = [], [], [], 0
+    for rec in recs:
+        R = int(rec.total.shape[0])
+        G = R // K
+        tots.append(flat[pos: pos + R].view(np.float32).reshape(G, K))
+        feats.append(flat[pos + R: pos + 5 * R].reshape(G, K, 4))
+        pos += 5 * R
+        if rec.winner is None:
+            wins.append(np.zeros(G, np.int32))
+        else:
+            wins.append(flat[pos: pos + G])
+            pos += G
+    return np.concatenate(wins), np.concatenate(tots), np.concatenate(feats)
 
 
 def _rows(audio: np.ndarray, ns: Sequence[int]) -> List[np.ndarray]:
@@ -724,7 +815,7 @@ class SmallTTS:
                          frames: Optional[Sequence[int]] = None, _defer: bool = False,
                          voices: Optional[Sequence[Voice]] = None, seeds: Optional[Sequence[int]] = None, trim=None,
                          align=None, prefix_lens: Optional[Sequence[int]] = None, return_alignment: bool = False,
-                         pins: Optional[Sequence[Optional[tuple]]] = None, start_step: int = 0):
+                         pins: Optional[Sequence[Optional[tuple]]] = None, start_step: int = 0, takes=None, return_takes: bool = False):
         """Batched synthesize: per-utterance (R_i,64) refs, token lists and durations -> list of (1, samples).
         `frames` overrides the per-utterance frame counts (default floor(duration * 7.5), infer/onnx.py:84; the HTTP server
         rounds up like the reference's Rust server, pipeline.rs:66).
@@ -745,10 +836,29 @@ class SmallTTS:
         causal, so the audio in front of the first free frame is that of the kept latents.  `start_step` = k > 0 runs only the
         sampler steps from k on, from the given latents (every row needs them then).  Works with every other argument; the fp16
         range guard's re-run uses the same pins.  Only the mechanism is verified: how well the 4-step student inpaints is
-        UNVALIDATED on trained weights (every weight this project has run is seeded noise)."""
+        UNVALIDATED on trained weights (every weight this project has run is seeded noise).
+        `takes` (an int K or a Takes): every row is sampled K times and only the best-aligned take is decoded.  Row g
+        becomes the K sampler rows g * K + k, which share its tokens, frames, voice or reference and pins and draw their noise from
+        take_seed(seed_g, k), seed_g = seeds[g], or piece_seed(a fresh draw, g) without `seeds` (not together with `noise`).  On
+        the batch's stream: the condition encoder and the sampler on G * K rows with the text-attention tap (`align` chooses the
+        Alignment, default Alignment(); its limits of 225 frames and 198 tokens apply, and `prefix_lens` keeps a prepended
+        transcription out of the path and the score also without `align`), engine.align_path, engine.take_scores,
+        engine.take_select, then the codec and the endpoints on the G winners only, so that every other argument works as on a
+        batch of G rows (words, return_alignment and return_latents are the winners').  At most 64 sampler rows (G * K).  K = 1 is
+        the call without `takes`, bit for bit.  `return_takes`: one more element at the very end, per row (winner k, the winner's
+        seed, totals (K,) fp32, features (K, 4) int32 = (cells, skipped, longest, idle)), from one small read-back (K = 1: the
+        tap and the score run for it; without `seeds` the seed reported is the batch's).  What the score is worth is UNVALIDATED on
+        trained weights (Takes)."""
         ep = as_endpointing(trim)
         al = as_alignment(align)
-        if al is None and (prefix_lens is not None or return_alignment):
+        tk = as_takes(takes)
+        if tk is None and return_takes:
+            raise ValueError("synthesize_batch: return_takes= belongs to takes=")
+        if tk is not None and noise is not None:
+            raise ValueError("synthesize_batch: noise= and takes= exclude each other")
+        K = 1 if tk is None else tk.k
+        scored = tk is not None and (K > 1 or return_takes)    # the tap, the path and the score run for the takes
+        if al is None and (return_alignment or (prefix_lens is not None and not scored)):   # (scored takes align too: they take prefix_lens)
             raise ValueError("synthesize_batch: prefix_lens= and return_alignment= belong to align=")
         if voices is not None:
             if ref_latents is not None:
@@ -769,61 +879,82 @@ class SmallTTS:
         ns = [int(f) for f in frames] if frames is not None else [_frames(d) for d in durations]
         rs = [int(np.asarray(r).shape[0]) for r in ref_latents]
         ps = [len(p) for p in phoneme_ids]
+        if tk is not None and B * K > Takes.MAX_ROWS:
+            raise ValueError(f"synthesize_batch: takes= runs at most {Takes.MAX_ROWS} sampler rows, got {B} rows x {K} takes")
+        al_run = al if (al is not None or not scored) else Alignment()
+        rows = [g for g in range(B) for _k in range(K)]        # sampler row g * K + k speaks caller row g (K = 1: the rows themselves)
+        Bs = len(rows)
+        s_ns, s_rs, s_ps = [ns[g] for g in rows], [rs[g] for g in rows], [ps[g] for g in rows]
         Rm, Pm, Nm = (0 if voices is not None else max(max(rs), 1)), max(max(ps), 1), max(ns)
-        ref = np.zeros((B, Rm, 64), np.float32)
-        ids = np.zeros((B, Pm), np.int64)
-        pm = np.zeros((B, Pm), bool)
-        mask = np.zeros((B, Nm), bool)
-        for b in range(B):
-            ref[b, :rs[b]] = np.asarray(ref_latents[b], np.float32)
-            ids[b, :ps[b]] = np.asarray(list(phoneme_ids[b]), np.int64)
-            pm[b, :ps[b]] = True
-            mask[b, :ns[b]] = True
+        ref = np.zeros((Bs, Rm, 64), np.float32)
+        ids = np.zeros((Bs, Pm), np.int64)
+        pm = np.zeros((Bs, Pm), bool)
+        mask = np.zeros((Bs, Nm), bool)
+        for b, g in enumerate(rows):
+            ref[b, :rs[g]] = np.asarray(ref_latents[g], np.float32)
+            ids[b, :ps[g]] = np.asarray(list(phoneme_ids[g]), np.int64)
+            pm[b, :ps[g]] = True
+            mask[b, :ns[g]] = True
         eng = self.engine
         pinned = _check_pins(pins, ns, start_step, self.num_steps)
         pin_kw = {}
         if pinned is not None:
-            x_pin, keep = np.zeros((B, Nm, 64), np.float32), np.zeros((B, Nm), bool)
-            for b, pe in enumerate(pinned):
-                if pe is not None:
-                    x_pin[b, :ns[b]], keep[b, :ns[b]] = pe
+            x_pin, keep = np.zeros((Bs, Nm, 64), np.float32), np.zeros((Bs, Nm), bool)
+            for b, g in enumerate(rows):
+                if pinned[g] is not None:
+                    x_pin[b, :ns[g]], keep[b, :ns[g]] = pinned[g]
             pin_kw = {"x_pin": x_pin, "pin": keep, "start_step": int(start_step)}
-        seed = self._next_seed() if seeds is None else 0
+        if K > 1:                                              # every take draws its own rows of noise
+            fresh = None if seeds is not None else self._next_seed()
+            row_seeds = [int(v) for v in seeds] if seeds is not None else [piece_seed(fresh, g) for g in range(B)]
+            s_seeds, seed = [take_seed(row_seeds[g], k) for g in range(B) for k in range(K)], 0
+        else:
+            seed = self._next_seed() if seeds is None else 0
+            s_seeds, row_seeds = seeds, ([seed] * B if seeds is None else [int(v) for v in seeds])
         voices = None if voices is None else list(voices)      # run() keeps them alive while the batch is in flight
+        s_voices = None if voices is None else [voices[g] for g in rows]
         p0s = [0] * B if prefix_lens is None else [int(v) for v in prefix_lens]
-        if al is not None:
+        if al_run is not None:
             if Nm > ALIGN_MAX_FRAMES or Pm > ALIGN_MAX_TOKENS:
                 raise ValueError(f"synthesize_batch: align= covers rows of at most {ALIGN_MAX_FRAMES} frames and {ALIGN_MAX_TOKENS} tokens "
                                  f"(got {Nm} frames, {Pm} tokens)")
             if len(p0s) != B or any(p < 0 or p > ps[b] for b, p in enumerate(p0s)):
                 raise ValueError("synthesize_batch: prefix_lens needs one length in [0, tokens of the row] per row")
 
+        s_p0s = [p0s[g] for g in rows]
+
         def run() -> _Batch:
-            cache = eng.cond_encode(ref, np.asarray(rs, np.int64), ids, pm)
+            cache = eng.cond_encode(ref, np.asarray(s_rs, np.int64), ids, pm)
             if voices is not None:
-                cache.update(eng.voice_expand(voices))
-            nz = noise if seeds is None else eng.randn_rows(seeds, ns, self.num_steps, n_max=Nm)
-            mass = spans = seg = gain = None
-            if al is None:
+                cache.update(eng.voice_expand(s_voices))
+            nz = noise if s_seeds is None else eng.randn_rows(s_seeds, s_ns, self.num_steps, n_max=Nm)
+            mass = spans = seg = gain = winner = total = feat = None
+            if al_run is None:
                 x = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, **pin_kw)
             else:
                 # the tap and the path ride on this batch's stream behind its sampler; a re-run (fp16 range guard) recomputes them
-                x, mass = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, align=al, **pin_kw)
-                spans = eng.align_path(mass, ns, p0s, ps)[0]
+                x, mass = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, align=al_run, **pin_kw)
+                spans, score = eng.align_path(mass, s_ns, s_p0s, s_ps)[:2]
+                if scored:                                     # takes: score every sampler row, keep one per caller row
+                    feat, total = eng.take_scores(mass, spans, score, s_ns, s_p0s, s_ps, tk)
+                if K > 1:
+                    x, _n, spans, mass, winner = eng.take_select(total, K, x, s_ns, spans, mass)
             audio = eng.codec_decode(x)                        # (B, 1, HOP * Nm); causal => prefixes are exact
             if ep is not None:                                 # behind the decode, on the same stream
                 seg, gain, _e = eng.endpoints(audio, ns, ep)
-            return _Batch(audio, x, mass, spans, seg, gain, ns, run)
+            return _Batch(audio, x, mass, spans, seg, gain, ns, run, winner, total, feat)
 
         rec = run()
         if _defer:                                             # synthesize_batches / synthesize_long / the server: stay on the device / stream
             return rec
-        return self._finish_batch(rec, ep, None if al is None else (phoneme_ids, p0s, ps), return_latents, return_alignment)
+        return self._finish_batch(rec, ep, None if al is None else (phoneme_ids, p0s, ps), return_latents, return_alignment,
+                                  (K, row_seeds) if return_takes else None)
 
     def _finish_batch(self, rec: _Batch, ep: Optional["Endpointing"], tokens: Optional[tuple], return_latents: bool,
-                      return_alignment: bool):
+                      return_alignment: bool, takes: Optional[tuple] = None):
         """synthesize_batch's tail: one batch from the device to what the call returns.  `tokens` = (token lists, prefix lengths, token
-        counts) with align=, else None.  -> rows[, latents][, words[, raw alignment]]; the rows alone are returned bare."""
+        counts) with align=, else None; `takes` = (K, the rows' seeds) with return_takes, else None.
+        -> rows[, latents][, words[, raw alignment]][, takes]; the rows alone are returned bare."""
         eng = self.engine
         B = len(rec.ns)
         head = (rec.audio if ep is None else rec.seg).cpu().numpy()   # synchronises: the saturation counters are final
@@ -854,6 +985,11 @@ class SmallTTS:
             if return_alignment:
                 mh = rec.mass.cpu().numpy()
                 res.append([(mh[b, : rec.ns[b], : ps[b]], spans_h[b, : ps[b]]) for b in range(B)])
+        if takes is not None:
+            K, row_seeds = takes
+            win, tot, ft = _read_takes([rec], K)
+            res.append([(int(win[b]), take_seed(row_seeds[b], int(win[b])) if K > 1 else int(row_seeds[b]), tot[b], ft[b])
+                        for b in range(B)])
         return outs if len(res) == 1 else tuple(res)
 
     def synthesize_batches(self, batches: Sequence[tuple], in_flight: int = 3, release_workspaces: bool = False) -> List[list]:
@@ -907,7 +1043,7 @@ class SmallTTS:
                         durations: Optional[Sequence[float]] = None, seed: Optional[int] = None, gap_ms: float = 120.0,
                         fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3, pcm16: bool = False,
                         prefix_tokens: Optional[Sequence[int]] = None, trim=None, return_segments: bool = False,
-                        return_words: bool = False, align=None, return_pieces: bool = False):
+                        return_words: bool = False, align=None, return_pieces: bool = False, takes=None, return_takes: bool = False):
         """A whole text in one voice -> one waveform (1, S), fp32 or (pcm16=True) int16 PCM, S = sum(3200 * n_i) + (pieces - 1) *
         round(gap_ms * 24).
 
@@ -937,10 +1073,24 @@ class SmallTTS:
 
         `return_pieces=True`: additionally -> [Piece(tokens, prefix_len, latents, seed), ...], what each piece was spoken from and
         its latents (one read-back from the finished batches): render_long(pieces, ...) with the same join parameters reproduces the
-        waveform, and respeak makes the latents of a replacement piece.  Returns (waveform[, segments][, words][, pieces])."""
+        waveform, and respeak makes the latents of a replacement piece.
+
+        `takes` (an int K or a Takes; DESIGN 8d, what the score is worth is UNVALIDATED on trained weights): every piece is sampled K
+        times, from take_seed(piece seed, k), and only the best-aligned take of each is decoded and joined
+        (synthesize_batch(takes=)); `align` then chooses the tapped layers / heads / steps also without return_words.  The groups
+        stay plan_long's, `max_batch` pieces per batch, so the decode batches have render_long's shapes while the sampler batch is K
+        times larger; where K * max_batch would pass 64 sampler rows the group size is lowered to 64 // K, and render_long then
+        reproduces the waveform when it is given that max_batch.  A Piece's `seed` is the winning take's seed.  K = 1 is the call
+        without `takes`.  `return_takes=True`: additionally -> per piece (winner k, the winner's seed, totals (K,), features (K, 4)),
+        from one small read-back.  Returns (waveform[, segments][, words][, pieces][, takes])."""
         ep = as_endpointing(trim)
+        tk = as_takes(takes)
+        if tk is None and return_takes:
+            raise ValueError("synthesize_long: return_takes= belongs to takes=")
+        if tk is not None and tk.k == 1 and not return_takes:
+            tk = None                                          # one take and nothing to report: the call without takes
         al = as_alignment(align if align is not None else (True if return_words else None))
-        if al is not None and not return_words:
+        if al is not None and not return_words and tk is None:
             raise ValueError("synthesize_long: align= belongs to return_words=True")
         if voice.engine is not self.engine:
             raise ValueError("synthesize_long: the Voice belongs to another engine")
@@ -960,26 +1110,37 @@ class SmallTTS:
         toks = [prefix + [int(t) for t in p] for p in token_lists]
         ns = [_frames(d) for d in durations]
         eng = self.engine
+        K = 1 if tk is None else tk.k
+        if tk is not None and K * max_batch > Takes.MAX_ROWS:
+            max_batch = Takes.MAX_ROWS // K                    # the sampler batch is K times the group
         groups, offsets, S = plan_long(ns, max_batch, gap_ms)
 
-        def result(out, segs, words, made):                    # words None: not aligned
+        def result(out, segs, words, made, taken=None):        # words None: not aligned
             res = ((out,) + ((segs,) if return_segments else ()) + ((words,) if words is not None else ())
-                   + ((made,) if return_pieces else ()))
+                   + ((made,) if return_pieces else ()) + ((taken,) if return_takes else ()))
             return res if len(res) > 1 else out
 
         if not toks:
-            return result(np.zeros((1, 0), np.int16 if pcm16 else np.float32), [], [] if return_words else None, [])
+            return result(np.zeros((1, 0), np.int16 if pcm16 else np.float32), [], [] if return_words else None, [], [])
         base = self._next_seed() if seed is None else int(seed)
         seeds = [piece_seed(base, i) for i in range(len(toks))]
+        al_b = al if (al is not None or tk is None) else Alignment()   # takes: the path leaves the prefix out, as the words do
+        # (return_takes with one take: the deferred batch returns its record either way, the flag makes it score its rows)
+        kw = ({} if al_b is None else {"align": al_b}) if tk is None else {"align": al_b, "takes": tk, "return_takes": return_takes}
         # with trim every batch enqueues its endpoints behind its decode, on its own stream: they overlap the other batches in flight
         calls = [lambda g=g: self.synthesize_batch(None, [toks[i] for i in g], None, frames=[ns[i] for i in g], voices=[voice] * len(g),
                                                    seeds=[seeds[i] for i in g], trim=ep, _defer=True,
-                                                   **({} if al is None else {"align": al, "prefix_lens": [len(prefix)] * len(g)}))
+                                                   **kw, **({} if al_b is None else {"prefix_lens": [len(prefix)] * len(g)}))
                  for g in groups]
         out, segs, pending = self._join_long(calls, groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16)
-        words = made = None
+        words = made = taken = None
+        spoken = seeds
+        if tk is not None and (return_takes or return_pieces):
+            win, tot, ft = _read_takes(pending, K)             # one small read-back for the whole text
+            spoken = [take_seed(seeds[i], int(win[i])) for i in range(len(toks))]  # what each piece was spoken from: the winner's seed
+            taken = [(int(win[i]), spoken[i], tot[i], ft[i]) for i in range(len(toks))]
         piece_spans: List[Optional[np.ndarray]] = [None] * len(toks)
-        if al is not None:
+        if return_words:
             # one small read-back for the whole text: every batch's (B, P, 2) span table, flattened
             flat = torch.cat([rec.spans.reshape(-1) for rec in pending]).cpu().numpy()
             words, pos = [], 0
@@ -1000,8 +1161,8 @@ class SmallTTS:
                 Ng = int(rec.latents.shape[1])
                 xg = flat[pos: pos + len(g) * Ng * 64].reshape(len(g), Ng, 64)
                 pos += len(g) * Ng * 64
-                made += [Piece(toks[i], len(prefix), xg[r, : ns[i]], seeds[i], piece_spans[i]) for r, i in enumerate(g)]
-        return result(out, segs, words, made)
+                made += [Piece(toks[i], len(prefix), xg[r, : ns[i]], spoken[i], piece_spans[i]) for r, i in enumerate(g)]
+        return result(out, segs, words, made, taken)
 
     def _join_long(self, calls, groups, ns, offsets, S, ep: Optional["Endpointing"], in_flight: int, gap_ms: float, fade_ms: float,
                    pcm16: bool):
@@ -1065,7 +1226,8 @@ class SmallTTS:
 
     def respeak(self, tokens: Sequence[int], latents, frames: Tuple[int, int], *, voice: Optional[Voice] = None, ref_latents=None,
                 new_tokens: Optional[Sequence[int]] = None, new_frames: Optional[int] = None, seed: Optional[int] = None,
-                start_step: int = 0, trim=None, align=None, prefix_len: int = 0, return_alignment: bool = False):
+                start_step: int = 0, trim=None, align=None, prefix_len: int = 0, return_alignment: bool = False, takes=None,
+                return_takes: bool = False):
         """Speaks frames [f0, f1) = `frames` of one utterance again and keeps the rest: `latents` (n, 64) are the utterance's (from
         return_latents / a Piece), `tokens` its token list; one row through synthesize_batch(pins=splice_pins(latents, f0, f1,
         new_frames)).  -> (audio (1, S'), latents (n', 64)[, words with align=]), n' = n - (f1 - f0) + new_frames: the frames in front
@@ -1080,6 +1242,9 @@ class SmallTTS:
         free region too (same length only); start_step = num_steps - 1 is nearly a no-op by the schedule (alpha(0) = 1,
         sigma(0) = 3.1e-5).  `prefix_len`: leading tokens that are a prepended transcription (align= leaves them out).
         `return_alignment` (with align=): one more element, (mass (n', P) fp32, spans (P, 2) int32) of the new row.
+        `takes` / `return_takes`: as synthesize_batch's; the row is re-spoken K times from take_seed(seed, k), every take with the
+        same pins, and the best-aligned one comes back (with return_takes one more element at the end: (winner k, the winner's
+        seed, totals, features)).
 
         Only the mechanism is verified.  It is UNVALIDATED on trained weights: every weight this project has run is seeded noise,
         and nobody has measured how well a 4-step distilled student inpaints."""
@@ -1100,13 +1265,15 @@ class SmallTTS:
         al = as_alignment(align)
         if return_alignment and al is None:
             raise ValueError("respeak: return_alignment= belongs to align=")
+        tk = as_takes(takes)
+        scored = tk is not None and (tk.k > 1 or return_takes)   # synthesize_batch's rule: these takes are aligned, so the prefix counts
         res = self.synthesize_batch(None if voice is not None else [np.asarray(ref_latents, np.float32)], [toks], None,
                                     frames=[int(x_pin.shape[0])], voices=None if voice is None else [voice],
                                     seeds=[self._next_seed() if seed is None else int(seed)], trim=trim, return_latents=True,
-                                    pins=[(x_pin, keep)], start_step=start_step,
-                                    **({} if al is None else {"align": al, "prefix_lens": [int(prefix_len)],
-                                                              "return_alignment": bool(return_alignment)}))
-        return (res[0][0], res[1][0]) + (tuple(r[0] for r in res[2:]) if al is not None else ())
+                                    pins=[(x_pin, keep)], start_step=start_step, takes=tk, return_takes=bool(return_takes),
+                                    **({} if al is None and not scored else {"prefix_lens": [int(prefix_len)]}),
+                                    **({} if al is None else {"align": al, "return_alignment": bool(return_alignment)}))
+        return (res[0][0], res[1][0]) + tuple(r[0] for r in res[2:])   # (words, raw alignment and takes: only when asked for)
 
     def synthesize_sharded(self, ref_latents: Sequence[np.ndarray], phoneme_ids: Sequence[Sequence[int]],
                            duration_sec: float, *, max_batch: int = 8) -> np.ndarray:

@@ -142,6 +142,30 @@ int smtts_align_path(smtts_handle h, void* stream, const float* mass, int B, int
     return e == hipSuccess ? 0 : E.fail_hip(e, "align_path");
 }
 
+int smtts_take_scores(smtts_handle h, void* stream, const float* mass, const int32_t* spans, const float* path_score, const int32_t* n_len,
+                      const int32_t* p0, const int32_t* p1, int B, int N, int P, float tau_tok, float tau_frm, float w0, float w1, float w2,
+                      float w3, int32_t* feat, float* total) { NULLCHK;
+    if (B < 1 || B > 65536) return E.fail("smtts_take_scores: B must be in [1, 65536]");
+    if (N < 1 || P < 1 || N > 225 || P > 198) return E.fail("smtts_take_scores: N must be in [1, 225] and P in [1, 198] (the range of smtts_align_path)");
+    if (!mass || !spans || !path_score || !n_len || !p0 || !p1 || !feat || !total) return E.fail("smtts_take_scores: a required pointer is NULL");
+    if (!(w0 >= 0.f) || !(w1 >= 0.f) || !(w2 >= 0.f) || !(w3 >= 0.f)) return E.fail("smtts_take_scores: the weights must be >= 0 (and not NaN)");
+    if (tau_tok != tau_tok || tau_frm != tau_frm) return E.fail("smtts_take_scores: the thresholds must not be NaN");
+    hipError_t e = launch_take_scores(mass, spans, path_score, n_len, p0, p1, B, N, P, tau_tok, tau_frm, w0, w1, w2, w3, feat, total, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "take_scores");
+}
+int smtts_take_select(smtts_handle h, void* stream, const float* total, int G, int K, int N, int P, const float* x, const int32_t* n_len,
+                      const int32_t* spans, const float* mass, float* x_win, int32_t* n_win, int32_t* spans_win, float* mass_win,
+                      int32_t* winner) { NULLCHK;
+    if (G < 1 || G > 65535) return E.fail("smtts_take_select: G must be in [1, 65535]");
+    if (K < 1 || K > 16) return E.fail("smtts_take_select: K must be in [1, 16]");
+    if (N < 1 || P < 1 || N > 225 || P > 198) return E.fail("smtts_take_select: N must be in [1, 225] and P in [1, 198] (the range of smtts_align_path)");
+    if (!total || !x || !n_len || !x_win || !n_win || !winner) return E.fail("smtts_take_select: a required pointer is NULL");
+    if ((spans != nullptr) != (spans_win != nullptr) || (mass != nullptr) != (mass_win != nullptr))
+        return E.fail("smtts_take_select: spans / spans_win and mass / mass_win are given or NULL together");
+    hipError_t e = launch_take_select(total, G, K, N, P, x, n_len, spans, mass, x_win, n_win, spans_win, mass_win, winner, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "take_select");
+}
+
 int smtts_codec_hop(smtts_handle h) { NULLCHK0; return E.codec_spec().hop(); }
 size_t smtts_decode_workspace_bytes(smtts_handle h, int B, int T) { NULLCHK0; return E.decode_ws_bytes(B, T); }
 int smtts_codec_decode(smtts_handle h, void* stream, const float* latents, int B, int T, float* audio, void* ws,

@@ -75,6 +75,18 @@ hipError_t launch_attn_text_mass(const AttnImg& a, float* mass, int rows, unsign
 // rows), score f32 (B) = the path cost (0 for empty rows).  N <= 225 and P <= 198 (back-pointers in LDS), else hipErrorInvalidValue.
 hipError_t launch_align_path(const float* mass, int B, int N, int P, const int* n_len, const int* p0, const int* p1, int* spans, float* score,
                              hipStream_t st);
+// ---- takes (takes.hip) ------------------------------------------------------------------------------------------------------------
+// Quality score of every sampler row behind launch_align_path, one workgroup per row: feat int32 (B, 4) = (cells, skipped, longest, idle)
+// and total f32 (B) = ((w0 c0 + w1 c1) + w2 c2) + w3 c3 from single rounded fp32 operations (the definitions: include/smalltts_hip.h
+// smtts_take_scores); +inf and zero features for an empty row.  n_len / p0 / p1 as launch_align_path (DEVICE, clamped).  N <= 225, P <= 198.
+hipError_t launch_take_scores(const float* mass, const int* spans, const float* path_score, const int* n_len, const int* p0, const int* p1,
+                              int B, int N, int P, float tau_tok, float tau_frm, float w0, float w1, float w2, float w3, int* feat,
+                              float* total, hipStream_t st);
+// Rows piece-major (row = g * K + k, 1 <= K <= 16): the winner of group g is the lowest k with the smallest total (NaN counts as +inf);
+// its rows of x (N, 64), n_len and, where given, spans (P, 2) and mass (N, P) are copied to row g of the outputs bit for bit, winner
+// int32 (G) = k.  An optional input and its output are given or NULL together.
+hipError_t launch_take_select(const float* total, int G, int K, int N, int P, const float* x, const int* n_len, const int* spans,
+                              const float* mass, float* x_win, int* n_win, int* spans_win, float* mass_win, int* winner, hipStream_t st);
 // fp32 projection rows [B*N][4*H*dh] = [q | k | v | gate] (bias included) -> the self part of AttnImg (dit.py:95-108; the arithmetic
 // the gemm3 EpiQKV epilogue performs on its accumulators, as a stand-alone kernel: test hook + reference for the epilogue)
 struct QkvPackArgs {

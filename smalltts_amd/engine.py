@@ -505,6 +505,80 @@ class HipEngine:
                                            _p(score)), "align_path")
         return spans, score
 
+    def _upload_i32(self, rows) -> torch.Tensor:
+        """Small per-call host table -> device int32 on the current stream, through pinned staging (no synchronising copy)."""
+        t = torch.from_numpy(np.ascontiguousarray([[int(v) for v in r] for r in rows], dtype=np.int32))
+        return t.pin_memory().to(self.device, non_blocking=True)
+
+    def take_scores(self, mass: torch.Tensor, spans: torch.Tensor, path_score: torch.Tensor, ns, p0, p1, takes):
+        """The quality score of every row behind align_path (smtts_take_scores; the definition: include/smalltts_hip.h).
+        mass fp32 (B,N,P), spans int32 (B,P,2) and path_score fp32 (B) as sample(align=) / align_path return them, contiguous on the
+        device; ns, p0, p1 the host integers align_path was given; takes anything with .weights (four floats >= 0), .tau_token and
+        .tau_frame (e.g. api.Takes).  -> (feat int32 (B,4) = (cells, skipped, longest, idle), total fp32 (B), lower is better, +inf
+        for an empty row), both on the device.  One launch on the current stream, no synchronisation.  What the total is worth on
+        trained weights is unvalidated (api.Takes)."""
+        if mass.dim() != 3 or mass.dtype != torch.float32 or not mass.is_contiguous() or mass.device != self.device:
+            raise ValueError("take_scores: mass must be a contiguous fp32 (B,N,P) tensor on the engine's device")
+        B, N, P = (int(v) for v in mass.shape)
+        if not (1 <= N <= ALIGN_MAX_FRAMES and 1 <= P <= ALIGN_MAX_TOKENS):
+            raise ValueError(f"take_scores: N = {N}, P = {P} outside the supported range N <= {ALIGN_MAX_FRAMES}, P <= {ALIGN_MAX_TOKENS}")
+        if spans.dtype != torch.int32 or tuple(spans.shape) != (B, P, 2) or not spans.is_contiguous() or spans.device != self.device:
+            raise ValueError(f"take_scores: spans must be a contiguous int32 ({B},{P},2) tensor on the engine's device")
+        if (path_score.dtype != torch.float32 or tuple(path_score.shape) != (B,) or not path_score.is_contiguous()
+                or path_score.device != self.device):
+            raise ValueError(f"take_scores: path_score must be a contiguous fp32 ({B},) tensor on the engine's device")
+        if B < 1 or len(ns) != B or len(p0) != B or len(p1) != B:
+            raise ValueError("take_scores: one frame count and one token range per row")
+        w = [float(v) for v in takes.weights]
+        tt, tf = float(takes.tau_token), float(takes.tau_frame)
+        if len(w) != 4 or not all(v >= 0.0 for v in w) or tt != tt or tf != tf:
+            raise ValueError("take_scores: four weights >= 0 and thresholds that are not NaN")
+        tab = self._upload_i32([ns, p0, p1])
+        feat = torch.empty(B, 4, dtype=torch.int32, device=self.device)
+        total = torch.empty(B, device=self.device)
+        self._ck(self.lib.smtts_take_scores(self.h, self._stream(), _p(mass), _p(spans), _p(path_score), _p(tab[0]), _p(tab[1]), _p(tab[2]),
+                                            B, N, P, tt, tf, w[0], w[1], w[2], w[3], _p(feat), _p(total)), "take_scores")
+        return feat, total
+
+    def take_select(self, total: torch.Tensor, K: int, x: torch.Tensor, ns, spans: Optional[torch.Tensor] = None,
+                    mass: Optional[torch.Tensor] = None):
+        """Keeps the best take of every group on the device (smtts_take_select): rows are piece-major, row = g * K + k, B = G * K.
+        total fp32 (B) (take_scores), x fp32 (B,N,64), optionally spans int32 (B,P,2) and mass fp32 (B,N,P), all contiguous on the
+        device; ns the B frame counts (host integers).  The winner of group g is the lowest k with the smallest total (NaN counts
+        as +inf).  -> (x_win (G,N,64), n_win int32 (G), spans_win (G,P,2) or None, mass_win (G,N,P) or None, winner int32 (G)), on the
+        device, the winners' rows bit for bit.  One launch on the current stream, no synchronisation."""
+        K = int(K)
+        if total.dim() != 1 or total.dtype != torch.float32 or not total.is_contiguous() or total.device != self.device:
+            raise ValueError("take_select: total must be a contiguous fp32 (B,) tensor on the engine's device")
+        B = int(total.shape[0])
+        if not 1 <= K <= 16 or B < 1 or B % K:
+            raise ValueError(f"take_select: K must be in [1, 16] and divide the {B} rows")
+        G = B // K
+        if x.dim() != 3 or tuple(x.shape[::2]) != (B, LATENT) or x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device:
+            raise ValueError(f"take_select: x must be a contiguous fp32 ({B},N,{LATENT}) tensor on the engine's device")
+        N = int(x.shape[1])
+        P = int(spans.shape[1]) if spans is not None and spans.dim() == 3 else int(mass.shape[2]) if mass is not None and mass.dim() == 3 else 1
+        if not (1 <= N <= ALIGN_MAX_FRAMES and 1 <= P <= ALIGN_MAX_TOKENS):
+            raise ValueError(f"take_select: N = {N}, P = {P} outside the supported range N <= {ALIGN_MAX_FRAMES}, P <= {ALIGN_MAX_TOKENS}")
+        if spans is not None and (spans.dtype != torch.int32 or tuple(spans.shape) != (B, P, 2) or not spans.is_contiguous()
+                                  or spans.device != self.device):
+            raise ValueError(f"take_select: spans must be a contiguous int32 ({B},{P},2) tensor on the engine's device, or None")
+        if mass is not None and (mass.dtype != torch.float32 or tuple(mass.shape) != (B, N, P) or not mass.is_contiguous()
+                                 or mass.device != self.device):
+            raise ValueError(f"take_select: mass must be a contiguous fp32 ({B},{N},{P}) tensor on the engine's device, or None")
+        if len(ns) != B:
+            raise ValueError("take_select: one frame count per row")
+        tab = self._upload_i32([ns])
+        dev = self.device
+        x_win = torch.empty(G, N, LATENT, device=dev)
+        n_win = torch.empty(G, dtype=torch.int32, device=dev)
+        spans_win = None if spans is None else torch.empty(G, P, 2, dtype=torch.int32, device=dev)
+        mass_win = None if mass is None else torch.empty(G, N, P, device=dev)
+        winner = torch.empty(G, dtype=torch.int32, device=dev)
+        self._ck(self.lib.smtts_take_select(self.h, self._stream(), _p(total), G, K, N, P, _p(x), _p(tab[0]), _p(spans), _p(mass),
+                                            _p(x_win), _p(n_win), _p(spans_win), _p(mass_win), _p(winner)), "take_select")
+        return x_win, n_win, spans_win, mass_win, winner
+
     @property
     def hop(self) -> int:
         return int(self.lib.smtts_codec_hop(self.h))

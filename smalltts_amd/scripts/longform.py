@@ -5,12 +5,14 @@ Without espeak: --tokens-file (one comma-separated token list per line = one pie
 --words out.json: when every word / punctuation mark / [event] is spoken (from the DiT's text attention: api.Alignment, default
 selection unvalidated on trained weights; resolution one codec frame = 133 ms).  --srt out.srt: one subtitle cue per piece, and
 next to it out.words.srt with one cue per word group.  --take OUT.npz: the pieces (tokens, latents, seeds; with --words also each
-piece's token spans) and the join parameters, what scripts/respeak.py re-speaks a span of and renders again."""
+piece's token spans) and the join parameters, what scripts/respeak.py re-speaks a span of and renders again.
+--takes K: every piece is sampled K times and the take whose text alignment scores best is kept (api.Takes; what the score is worth is
+unvalidated on trained weights); with --words the JSON becomes {"words": [...], "takes": [{piece, winner, seed, totals}, ...]}."""
 import argparse
 import json
 from pathlib import Path
 
-from ..api import SAMPLE_RATE, Endpointing, SmallTTS, estimate_duration, format_srt, save_take, split_text, token_groups
+from ..api import SAMPLE_RATE, Endpointing, SmallTTS, Takes, estimate_duration, format_srt, save_take, split_text, token_groups
 from ..audio import read_wav, write_wav_pcm16
 from ..phonemes import decode_token_ids, get_token_ids, parse_tokens_arg
 from ._common import add_engine_args
@@ -21,14 +23,20 @@ def group_texts(token_lists) -> list:
     return [(i, kind, ph) for i, toks in enumerate(token_lists) for kind, ph, _t0, _t1 in token_groups(toks)]
 
 
-def words_json(words, texts) -> str:
+def words_json(words, texts, takes=None) -> str:
     """synthesize_long's words + group_texts -> the --words file: a JSON list of {index, piece, kind, phonemes, start, end (samples),
-    start_s, end_s (seconds)}."""
+    start_s, end_s (seconds)}.  With `takes` (synthesize_long's return_takes) the file is {"words": that list, "takes": [{piece,
+    winner, seed, totals}, ...]}, one entry per piece; a total that is not finite is written as null."""
     if len(words) != len(texts):
         raise ValueError(f"{len(words)} timed groups for {len(texts)} groups of the text")
-    return json.dumps([{"index": int(gi), "piece": int(pi), "kind": kind, "phonemes": ph, "start": int(s), "end": int(e),
-                        "start_s": round(int(s) / SAMPLE_RATE, 4), "end_s": round(int(e) / SAMPLE_RATE, 4)}
-                       for (gi, kind, s, e), (pi, _k, ph) in zip(words, texts)], ensure_ascii=False, indent=1)
+    rows = [{"index": int(gi), "piece": int(pi), "kind": kind, "phonemes": ph, "start": int(s), "end": int(e),
+             "start_s": round(int(s) / SAMPLE_RATE, 4), "end_s": round(int(e) / SAMPLE_RATE, 4)}
+            for (gi, kind, s, e), (pi, _k, ph) in zip(words, texts)]
+    if takes is not None:
+        fin = lambda v: float(v) if float("-inf") < float(v) < float("inf") else None
+        rows = {"words": rows, "takes": [{"piece": i, "winner": int(w), "seed": int(sd), "totals": [fin(v) for v in tot]}
+                                         for i, (w, sd, tot, _feat) in enumerate(takes)]}
+    return json.dumps(rows, ensure_ascii=False, indent=1)
 
 
 def piece_cues(segments, piece_texts) -> list:
@@ -40,7 +48,8 @@ def word_cues(words, texts) -> list:
     return [(s, e, ph) for (_gi, _kind, s, e), (_pi, _k, ph) in zip(words, texts)]
 
 
-def main(argv=None):
+def parse_args(argv=None):
+    """The command line -> its namespace (argument errors exit, as argparse does)."""
     ap = argparse.ArgumentParser()
     ap.add_argument("--wav", required=True, help="reference audio file (the voice)")
     ap.add_argument("--text-file", default=None, help="text to speak (any length)")
@@ -54,6 +63,7 @@ def main(argv=None):
     ap.add_argument("--words", default=None, metavar="OUT.json", help="write the time of every word / punctuation mark / [event] (133 ms resolution)")
     ap.add_argument("--srt", default=None, metavar="OUT.srt", help="write one subtitle cue per piece, and OUT.words.srt with one cue per word group")
     ap.add_argument("--take", default=None, metavar="OUT.npz", help="save the pieces and the join parameters (for scripts/respeak.py)")
+    ap.add_argument("--takes", type=int, default=None, metavar="K", help=f"sample every piece K times (1..{Takes.MAX_K}) and keep the best-aligned take")
     ap.add_argument("--max-batch", type=int, default=8)
     ap.add_argument("--in-flight", type=int, default=3)
     add_engine_args(ap)
@@ -64,6 +74,15 @@ def main(argv=None):
         ap.error("--tokens-file needs --durations")
     if args.level is not None and not args.trim:
         ap.error("--level needs --trim")
+    if args.takes is not None and not 1 <= args.takes <= Takes.MAX_K:
+        ap.error(f"--takes must lie in [1, {Takes.MAX_K}]")
+    if args.takes is not None and args.takes * args.max_batch > Takes.MAX_ROWS:
+        args.max_batch = Takes.MAX_ROWS // args.takes   # synthesize_long's rule, applied here so that --take records the group size used
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     print("loading")
     tts = SmallTTS(weights=args.weights, device=args.device, precision=args.precision, num_steps=args.steps, seed=args.seed)
@@ -79,6 +98,8 @@ def main(argv=None):
         kw.update(return_segments=True, return_words=True)
     if args.take:
         kw.update(return_pieces=True)
+    if args.takes is not None:
+        kw.update(takes=args.takes, return_takes=True)
     if args.tokens_file:
         with open(args.tokens_file) as f:
             token_lists = [parse_tokens_arg(line) for line in f if line.strip()]
@@ -96,6 +117,10 @@ def main(argv=None):
         print(f"generating {len(pieces)} pieces")
         token_lists, piece_texts = [tok(p) for p in pieces], pieces
         audio = tts.synthesize_long(voice, token_lists=token_lists, durations=[estimate_duration(p) for p in pieces], **kw)
+    chosen = None
+    if args.takes is not None:
+        audio, chosen = (audio[:-1] if len(audio) > 2 else audio[0]), audio[-1]
+        print("takes kept: " + " ".join(str(w) for w, _seed, _tot, _feat in chosen))
     if args.take:
         audio, taken = (audio[:-1] if timed else audio[0]), audio[-1]
         Path(args.take).parent.mkdir(parents=True, exist_ok=True)
@@ -107,7 +132,7 @@ def main(argv=None):
         texts = group_texts(token_lists)
         if args.words:
             Path(args.words).parent.mkdir(parents=True, exist_ok=True)
-            Path(args.words).write_text(words_json(words, texts), encoding="utf-8")
+            Path(args.words).write_text(words_json(words, texts, chosen), encoding="utf-8")
             print(f"{args.words} ({len(words)} word groups)")
         if args.srt:
             Path(args.srt).parent.mkdir(parents=True, exist_ok=True)

@@ -1,15 +1,17 @@
 """python -m smalltts_amd.scripts.respeak --take T.npz --wav ref.wav --piece I (--frames A:B | --groups A:B) [--seed S]
-    [--start-step K] --out out.wav [--take-out T2.npz]
+    [--start-step K] [--takes K] --out out.wav [--take-out T2.npz]
 Speaks a span of one piece of a long take again and keeps everything else: the take (scripts/longform.py --take) holds every piece's
 tokens and latents; frames [A, B) of piece I, or the frames its token groups [A, B) touch (the spans longform --words saved), are
 regenerated with the rest of the piece pinned (api.SmallTTS.respeak), the whole take is rendered again with its own join parameters
 (api.SmallTTS.render_long) and written out, with the updated take next to it.  A new take needs a new --seed (none: one is drawn).
 --tokens: the piece's new token list when the text changes (the take's prefix is prepended); --new-frames: the length of the
-regenerated region.  Only the mechanism is verified: how well the 4-step student inpaints is unvalidated on trained weights."""
+regenerated region.  --takes K: the span is re-spoken K times, every take with the same pins, and the best-aligned one is kept
+(api.Takes; the updated take records the winner's seed).  Only the mechanism is verified: how well the 4-step student inpaints, and
+what the takes' score is worth, are unvalidated on trained weights."""
 import argparse
 from pathlib import Path
 
-from ..api import Endpointing, Piece, SmallTTS, frames_of_groups, load_take, save_take, token_groups
+from ..api import Endpointing, Piece, SmallTTS, Takes, frames_of_groups, load_take, save_take, token_groups
 from ..audio import read_wav, write_wav_pcm16
 from ..phonemes import parse_tokens_arg
 from ._common import add_engine_args
@@ -50,6 +52,7 @@ def main(argv=None):
     ap.add_argument("--groups", default=None, metavar="A:B", help="regenerate the frames of the piece's token groups [A, B)")
     ap.add_argument("--new-frames", type=int, default=None, help="length of the regenerated region (default: B - A frames)")
     ap.add_argument("--start-step", type=int, default=0, help="run only the sampler steps from K on, from the take's latents")
+    ap.add_argument("--takes", type=int, default=None, metavar="K", help=f"re-speak the span K times (1..{Takes.MAX_K}) and keep the best-aligned take")
     ap.add_argument("--out", required=True)
     ap.add_argument("--take-out", default=None, metavar="T2.npz", help="where the updated take goes (default: next to --out)")
     add_engine_args(ap)
@@ -57,6 +60,8 @@ def main(argv=None):
     pieces, join = load_take(args.take)
     if not 0 <= args.piece < len(pieces):
         ap.error(f"--piece must lie in [0, {len(pieces)})")
+    if args.takes is not None and not 1 <= args.takes <= Takes.MAX_K:
+        ap.error(f"--takes must lie in [1, {Takes.MAX_K}]")
     old = pieces[args.piece]
     try:
         f0, f1 = span_frames(old, args.frames, args.groups)
@@ -78,7 +83,11 @@ def main(argv=None):
     print(f"re-speaking frames [{f0}, {f1}) of piece {args.piece} (seed {seed})")
     res = tts.respeak(old.tokens, old.latents, (f0, f1), voice=voice, new_tokens=tokens, new_frames=args.new_frames, seed=seed,
                       start_step=args.start_step, prefix_len=old.prefix_len,
-                      **({"align": True, "return_alignment": True} if timed else {}))
+                      **({"align": True, "return_alignment": True} if timed else {}),
+                      **({} if args.takes is None else {"takes": args.takes, "return_takes": True}))
+    if args.takes is not None:
+        winner, seed = res[-1][0], res[-1][1]
+        print(f"take {winner} of {args.takes} kept (seed {seed})")
     pieces[args.piece] = Piece(tokens, old.prefix_len, res[1], seed, res[3][1] if timed else None)
     trim = Endpointing(level_dbfs=join["level_dbfs"]) if join["trim"] else None
     audio = tts.render_long(pieces, gap_ms=join["gap_ms"], fade_ms=join["fade_ms"], max_batch=join["max_batch"],
