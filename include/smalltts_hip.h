@@ -225,6 +225,46 @@ int smtts_take_select(smtts_handle h, void* stream, const float* total, int G, i
                       const int32_t* spans /* or NULL */, const float* mass /* or NULL */, float* x_win, int32_t* n_win,
                       int32_t* spans_win, float* mass_win, int32_t* winner);
 
+/* ---- repair (DESIGN.md '8e. Repair'): re-speak only the badly aligned words of a take, on the device -----------------------------
+ * smtts_repair_plan, behind smtts_align_path (and smtts_take_select) on `stream`, one workgroup per row, writes the pin mask that
+ * smtts_sample_pinned takes: mass f32 (B,N,P) (the tap), spans i32 (B,P,2) (smtts_align_path's output), n_len / p0 / p1 i32 (B), keep u8
+ * (B,N) or NULL, all DEVICE; n, p0, p1 are clamped exactly as smtts_take_scores clamps them (n into [0, N], p0 and p1 into [0, P]).  For
+ * a token p in [p0, p1) with (first, last) = spans[b][p]:
+ *     a span with first < 0 or last < first is EMPTY: the token is bad and frees nothing;
+ *     of any other span both ends are clamped into [0, n - 1] before anything is indexed, len = last - first + 1 of the clamped ends;
+ *     such a token is bad iff len > max_span, or no frame f in [first, last] has mass[b][f][p] >= tau_tok (one fp32 comparison: a value
+ *     equal to the threshold attends, a NaN never does);
+ *     a bad token with a non-empty span frees the frames [max(0, first - margin), min(n - 1, last + margin)].
+ * -> pin u8 (B,N): pin[b][f] = 1 for f < n that no bad token frees, and for f < n with keep[b][f] != 0 whatever the plan says; 0 for
+ * every other f < N (every byte of the row is written).  counts i32 (B,2) = (bad tokens, frames f < n with pin 0).  A row with n == 0
+ * or p1 <= p0 gets pin all 0 and counts (0, 0).  No index leaves the row whatever the buffers hold.  1 <= N <= 225, 1 <= P <= 198,
+ * 1 <= B <= 65536, 1 <= max_span <= 225, 0 <= margin <= 32, tau_tok not NaN.
+ *
+ * smtts_repair_keep, 1 <= G <= 65535: with key(t) = isnan(t) ? +inf : t,
+ *     replace[g] = counts[g][1] > 0 && key(total_new[g]) < key(total_cur[g])        (strict <: a tie keeps the current row, and a row
+ *                                                                                    with nothing freed is never replaced)
+ * Where replace[g] holds, row g of x_new f32 (G,N,64) and, where given, spans_new i32 (G,P,2) and mass_new f32 (G,N,P) is copied over
+ * row g of x_cur, spans_cur, mass_cur IN PLACE, bit for bit (16-byte lanes where a row's byte count and both base addresses allow,
+ * 4-byte elements otherwise: no alignment is required); every other row of the _cur buffers keeps its bits.  total_out f32 (G) and
+ * feat_out i32 (G,4) are total / feat of whichever row stays, kept i32 (G) = replace.  counts i32 (G,2) is smtts_repair_plan's, feat_cur
+ * / feat_new i32 (G,4) smtts_take_scores'.  spans_cur / spans_new and mass_cur / mass_new are each given or NULL together; a NULL pair
+ * is skipped.  Every workgroup re-derives replace[g] from the inputs, so total_out, feat_out and kept must not overlap any input; the
+ * _new buffers must not overlap the _cur ones.
+ *
+ * Both: an argument error (NULL handle or required pointer, half an optional pair, a shape or parameter out of range, a NaN threshold)
+ * returns 1 with a message naming the entry before anything is enqueued.  One launch each, no atomics, no synchronisation: two calls
+ * return the same bits.
+ * Only this mechanism is verified.  It is UNVALIDATED on trained weights: every weight this project has run is seeded noise, nobody has
+ * measured whether a 4-step distilled student inpaints the freed frames audibly well, nobody has measured whether a lower total is the
+ * better take, and the thresholds the Python side passes by default (api.Repair) are design choices and not measurements. */
+int smtts_repair_plan(smtts_handle h, void* stream, const float* mass, const int32_t* spans, const int32_t* n_len, const int32_t* p0,
+                      const int32_t* p1, const uint8_t* keep /* or NULL */, int B, int N, int P, float tau_tok, int max_span, int margin,
+                      uint8_t* pin, int32_t* counts);
+int smtts_repair_keep(smtts_handle h, void* stream, int G, int N, int P, const float* total_cur, const float* total_new,
+                      const int32_t* counts, const int32_t* feat_cur, const int32_t* feat_new, float* x_cur, const float* x_new,
+                      int32_t* spans_cur /* or NULL */, const int32_t* spans_new, float* mass_cur /* or NULL */, const float* mass_new,
+                      float* total_out, int32_t* feat_out, int32_t* kept);
+
 /* ---- codec ------------------------------------------------------------------------------------ */
 int smtts_codec_hop(smtts_handle h);
 size_t smtts_decode_workspace_bytes(smtts_handle h, int B, int T);

@@ -54,6 +54,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_align_path": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "smtts_take_scores": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, f32, vp, vp]),
     "smtts_take_select": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "smtts_repair_plan": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, i32, i32, vp, vp]),
+    "smtts_repair_keep": (i32, [vp, vp, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "smtts_codec_hop": (i32, [vp]),
     "smtts_decode_workspace_bytes": (sz, [vp, i32, i32]),
     "smtts_codec_decode": (i32, [vp, vp, vp, i32, i32, vp, vp, sz]),

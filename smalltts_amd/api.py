@@ -347,6 +347,65 @@ def as_takes(takes) -> Optional["Takes"]:
     raise TypeError(f"takes must be None, an int or a Takes, got {type(takes).__name__}")
 
 
+class Repair:
+    """Repair of a take (immutable; DESIGN 8e, include/smalltts_hip.h smtts_repair_plan / smtts_repair_keep): behind the sampler (and
+    the take selection) the tokens of every row whose alignment is bad are found on the device, only their frames are drawn again by
+    one pinned sampler pass with every other frame held to the row's latents, the row is scored again, and the repaired row is kept
+    only where its total is strictly lower; `rounds` (1..4) such passes.  A token is bad when its span on the monotone path is empty,
+    longer than `max_span` frames (1..225), or holds no frame that gives the token `tau_token` of its attention; a bad token frees its
+    span plus `margin` frames (0..32) on either side.  The total is the call's Takes' (the default weights without `takes`).
+
+    The defaults are design choices, not measurements.  Repair is UNVALIDATED on trained weights: every weight this project has run
+    is seeded noise, nobody has measured whether a 4-step student inpaints the freed frames audibly well, and nobody has measured
+    whether a lower total is the better take.  The mechanism is verified: the plan and the keep rule (bit for bit against a numpy
+    restatement), that a repaired row is the pinned call by hand, and that every frame the plan pinned keeps its bits."""
+    __slots__ = ("rounds", "tau_token", "max_span", "margin")
+    MAX_ROUNDS, MAX_MARGIN = 4, 32
+
+    def __init__(self, rounds: int = 1, tau_token: float = 0.1, max_span: int = 8, margin: int = 2) -> None:
+        for name, v in (("rounds", rounds), ("max_span", max_span), ("margin", margin)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"Repair: {name} must be an integer, got {type(v).__name__}")
+        if not 1 <= int(rounds) <= self.MAX_ROUNDS:
+            raise ValueError(f"Repair: rounds must lie in [1, {self.MAX_ROUNDS}], got {int(rounds)}")
+        if not 1 <= int(max_span) <= ALIGN_MAX_FRAMES:
+            raise ValueError(f"Repair: max_span must lie in [1, {ALIGN_MAX_FRAMES}], got {int(max_span)}")
+        if not 0 <= int(margin) <= self.MAX_MARGIN:
+            raise ValueError(f"Repair: margin must lie in [0, {self.MAX_MARGIN}], got {int(margin)}")
+        if not np.isfinite(float(tau_token)):
+            raise ValueError("Repair: tau_token must be finite")
+        set_ = object.__setattr__
+        set_(self, "rounds", int(rounds))
+        set_(self, "tau_token", float(tau_token))
+        set_(self, "max_span", int(max_span))
+        set_(self, "margin", int(margin))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Repair is immutable")
+
+    __delattr__ = __setattr__
+
+    def __repr__(self) -> str:
+        return "Repair(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Repair) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
+
+    def __hash__(self) -> int:
+        return hash(tuple(getattr(self, k) for k in self.__slots__))
+
+
+def as_repair(repair) -> Optional["Repair"]:
+    """The `repair=` argument of the synthesis calls: None -> None (off), an int -> Repair(rounds), a Repair -> itself."""
+    if repair is None:
+        return None
+    if isinstance(repair, Repair):
+        return repair
+    if isinstance(repair, (int, np.integer)) and not isinstance(repair, bool):
+        return Repair(int(repair))
+    raise TypeError(f"repair must be None, an int or a Repair, got {type(repair).__name__}")
+
+
 def token_groups(ids: Sequence[int]) -> List[Tuple[str, str, int, int]]:
     """The units word timings are reported for: runs of token ids between the space symbol.  -> [(kind, phonemes, t0, t1), ...] in
     order, [t0, t1) the run's token indices, phonemes = decode_token_ids of them.  kind "word": a run of letter / IPA symbols;
@@ -581,6 +640,14 @@ def take_seed(seed: int, k: int) -> int:
     return int(np.random.SeedSequence([int(seed), int(k), 0x54414B45]).generate_state(1, np.uint64)[0] >> 1)
 
 
+def repair_seed(seed: int, r: int) -> int:
+    """Seed of repair round r >= 1 of a row spoken from `seed`: SeedSequence([seed, r, 0x52455052]) reduced to 63 bits (three words
+    with a tag of its own: never a piece_seed or a take_seed)."""
+    if int(r) < 1:
+        raise ValueError(f"repair_seed: rounds count from 1, got {int(r)}")
+    return int(np.random.SeedSequence([int(seed), int(r), 0x52455052]).generate_state(1, np.uint64)[0] >> 1)
+
+
 def _split_sources(weights) -> List[str]:
     if isinstance(weights, (list, tuple)):
         return [str(w) for w in weights]
@@ -709,6 +776,9 @@ class _Batch(NamedTuple):
     winner: Optional[torch.Tensor] = None  # takes=: (B,) int32, the take kept per row (engine.take_select); None with one take
     total: Optional[torch.Tensor] = None   # takes=: (B * K,) fp32, every take's total, piece-major (engine.take_scores), else None
     feat: Optional[torch.Tensor] = None    # takes=: (B * K, 4) int32 (cells, skipped, longest, idle), else None
+    rp_kept: Optional[List[torch.Tensor]] = None     # repair=: per round (B,) int32, 1 where the repaired row was kept (engine.repair_keep)
+    rp_counts: Optional[List[torch.Tensor]] = None   # repair=: per round (B, 2) int32 (bad tokens, freed frames) (engine.repair_plan)
+    rp_totals: Optional[List[torch.Tensor]] = None   # repair=: rounds + 1 (B,) fp32: the rows' totals before round 1 and after every round
 
 
 def _read_takes(recs: Sequence[_Batch], K: int) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
@@ -731,6 +801,25 @@ def _read_takes(recs: Sequence[_Batch], K: int) -> Tuple[np.ndarray, np.ndarray,
             wins.append(flat[pos: pos + G])
             pos += G
     return np.concatenate(wins), np.concatenate(tots), np.concatenate(feats)
+
+
+def _read_repair(recs: Sequence[_Batch]) -> List[tuple]:
+    """What repair= left in finished batches, in ONE small read-back: per row of all records in order -> (kept (rounds,) int32,
+    counts (rounds, 2) int32 = (bad tokens, freed frames) of every round's plan, before (rounds,) fp32 and after (rounds,) fp32, the
+    row's total entering and leaving every round)."""
+    parts = []
+    for rec in recs:
+        parts += [t.reshape(-1) for t in rec.rp_kept] + [t.reshape(-1) for t in rec.rp_counts] + [t.view(torch.int32) for t in rec.rp_totals]
+    flat = torch.cat(parts).cpu().numpy()
+    out, pos = [], 0
+    for rec in recs:
+        R, G = len(rec.rp_kept), int(rec.rp_kept[0].shape[0])
+        kept = flat[pos: pos + R * G].reshape(R, G)
+        counts = flat[pos + R * G: pos + 3 * R * G].reshape(R, G, 2)
+        tot = flat[pos + 3 * R * G: pos + (4 * R + 1) * G].view(np.float32).reshape(R + 1, G)
+        pos += (4 * R + 1) * G
+        out += [(kept[:, g].copy(), counts[:, g].copy(), tot[:-1, g].copy(), tot[1:, g].copy()) for g in range(G)]
+    return out
 
 
 def _rows(audio: np.ndarray, ns: Sequence[int]) -> List[np.ndarray]:
@@ -815,7 +904,8 @@ class SmallTTS:
                          frames: Optional[Sequence[int]] = None, _defer: bool = False,
                          voices: Optional[Sequence[Voice]] = None, seeds: Optional[Sequence[int]] = None, trim=None,
                          align=None, prefix_lens: Optional[Sequence[int]] = None, return_alignment: bool = False,
-                         pins: Optional[Sequence[Optional[tuple]]] = None, start_step: int = 0, takes=None, return_takes: bool = False):
+                         pins: Optional[Sequence[Optional[tuple]]] = None, start_step: int = 0, takes=None, return_takes: bool = False,
+                         repair=None, return_repair: bool = False):
         """Batched synthesize: per-utterance (R_i,64) refs, token lists and durations -> list of (1, samples).
         `frames` overrides the per-utterance frame counts (default floor(duration * 7.5), infer/onnx.py:84; the HTTP server
         rounds up like the reference's Rust server, pipeline.rs:66).
@@ -848,16 +938,33 @@ class SmallTTS:
         the call without `takes`, bit for bit.  `return_takes`: one more element at the very end, per row (winner k, the winner's
         seed, totals (K,) fp32, features (K, 4) int32 = (cells, skipped, longest, idle)), from one small read-back (K = 1: the
         tap and the score run for it; without `seeds` the seed reported is the batch's).  What the score is worth is UNVALIDATED on
-        trained weights (Takes)."""
+        trained weights (Takes).
+        `repair` (an int = rounds, or a Repair): behind the sampler and the take selection, on the batch's stream and
+        without a read-back, `rounds` times: engine.repair_plan pins every frame of the G rows but those of the badly aligned tokens
+        (the caller's `pins` stay pinned whatever the plan says), one pinned sampler pass on G rows draws only the freed frames
+        again, from repair_seed(seed_g, r) with the row's current latents in view, engine.align_path and engine.take_scores score
+        the result, and engine.repair_keep replaces the row only where its total is strictly lower.  A frame the plan pinned keeps
+        its bits; a row with nothing bad comes back as without `repair`, bit for bit.  Repair implies the tap, the path and the
+        score as return_takes does (the total's weights are the Takes', Takes(1)'s without `takes`), and everything else works on
+        the merged rows.  Not together with `noise` or `start_step` > 0.  `return_repair`: one more element at the very end, per
+        row (kept (rounds,), (bad tokens, freed frames) (rounds, 2), total before (rounds,), total after (rounds,)), from one small
+        read-back.  Only the mechanism is verified: whether the 4-step student inpaints audibly well, and whether a lower total
+        is the better take, are UNVALIDATED on trained weights (Repair)."""
         ep = as_endpointing(trim)
         al = as_alignment(align)
         tk = as_takes(takes)
+        rp = as_repair(repair)
         if tk is None and return_takes:
             raise ValueError("synthesize_batch: return_takes= belongs to takes=")
         if tk is not None and noise is not None:
             raise ValueError("synthesize_batch: noise= and takes= exclude each other")
+        if rp is None and return_repair:
+            raise ValueError("synthesize_batch: return_repair= belongs to repair=")
+        if rp is not None and (noise is not None or int(start_step) > 0):
+            raise ValueError("synthesize_batch: repair= excludes noise= and start_step > 0")
         K = 1 if tk is None else tk.k
-        scored = tk is not None and (K > 1 or return_takes)    # the tap, the path and the score run for the takes
+        scored = (tk is not None and (K > 1 or return_takes)) or rp is not None   # the tap, the path and the score run for these
+        tk_run = tk if tk is not None else Takes(1)            # the weights and thresholds of the total
         if al is None and (return_alignment or (prefix_lens is not None and not scored)):   # (scored takes align too: they take prefix_lens)
             raise ValueError("synthesize_batch: prefix_lens= and return_alignment= belong to align=")
         if voices is not None:
@@ -911,6 +1018,12 @@ class SmallTTS:
         else:
             seed = self._next_seed() if seeds is None else 0
             s_seeds, row_seeds = seeds, ([seed] * B if seeds is None else [int(v) for v in seeds])
+        if rp is not None:                                     # every round draws its own rows of noise for the G rows
+            base = row_seeds if (seeds is not None or K > 1) else [piece_seed(seed, g) for g in range(B)]
+            rp_seeds = [[repair_seed(base[g], r) for g in range(B)] for r in range(1, rp.rounds + 1)]
+            g_sel = slice(None, None, K)                       # sampler row g * K speaks caller row g
+            g_ref, g_ids, g_pm, g_mask = (np.ascontiguousarray(a[g_sel]) for a in (ref, ids, pm, mask))
+            g_keep = None if pinned is None else np.ascontiguousarray(pin_kw["pin"][g_sel])
         voices = None if voices is None else list(voices)      # run() keeps them alive while the batch is in flight
         s_voices = None if voices is None else [voices[g] for g in rows]
         p0s = [0] * B if prefix_lens is None else [int(v) for v in prefix_lens]
@@ -936,25 +1049,47 @@ class SmallTTS:
                 x, mass = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, align=al_run, **pin_kw)
                 spans, score = eng.align_path(mass, s_ns, s_p0s, s_ps)[:2]
                 if scored:                                     # takes: score every sampler row, keep one per caller row
-                    feat, total = eng.take_scores(mass, spans, score, s_ns, s_p0s, s_ps, tk)
+                    feat, total = eng.take_scores(mass, spans, score, s_ns, s_p0s, s_ps, tk_run)
                 if K > 1:
                     x, _n, spans, mass, winner = eng.take_select(total, K, x, s_ns, spans, mass)
+            rp_kept = rp_counts = rp_totals = None
+            if rp is not None:                                 # repair: G rows from here on, the winners' latents are the pins
+                if K > 1:                                      # the cache has G * K rows: the conditions again at G rows
+                    cache = eng.cond_encode(g_ref, np.asarray(rs, np.int64), g_ids, g_pm)
+                    if voices is not None:
+                        cache.update(eng.voice_expand(voices))
+                    sel = winner.long() + torch.arange(0, B * K, K, device=eng.device)
+                    t_cur, f_cur = total[sel], feat[sel]       # the winners' totals and features
+                else:
+                    t_cur, f_cur = total, feat
+                keep_d = None if g_keep is None else torch.from_numpy(g_keep).pin_memory().to(eng.device, non_blocking=True)
+                rp_kept, rp_counts, rp_totals = [], [], [t_cur]
+                for r in range(rp.rounds):
+                    plan, counts = eng.repair_plan(mass, spans, ns, p0s, ps, rp, keep_d)
+                    nz_r = eng.randn_rows(rp_seeds[r], ns, self.num_steps, n_max=Nm)
+                    x_new, mass_new = eng.sample(cache, g_mask, num_steps=self.num_steps, noise=nz_r, seed=0, align=al_run, x_pin=x,
+                                                 pin=plan, start_step=0)
+                    spans_new, score_new = eng.align_path(mass_new, ns, p0s, ps)[:2]
+                    f_new, t_new = eng.take_scores(mass_new, spans_new, score_new, ns, p0s, ps, tk_run)
+                    # x, spans and mass are merged in place; every round's small outputs are tensors of their own (the report reads them)
+                    t_cur, f_cur, kept = eng.repair_keep(t_cur, t_new, counts, f_cur, f_new, x, x_new, spans, spans_new, mass, mass_new)
+                    rp_kept.append(kept); rp_counts.append(counts); rp_totals.append(t_cur)
             audio = eng.codec_decode(x)                        # (B, 1, HOP * Nm); causal => prefixes are exact
             if ep is not None:                                 # behind the decode, on the same stream
                 seg, gain, _e = eng.endpoints(audio, ns, ep)
-            return _Batch(audio, x, mass, spans, seg, gain, ns, run, winner, total, feat)
+            return _Batch(audio, x, mass, spans, seg, gain, ns, run, winner, total, feat, rp_kept, rp_counts, rp_totals)
 
         rec = run()
         if _defer:                                             # synthesize_batches / synthesize_long / the server: stay on the device / stream
             return rec
         return self._finish_batch(rec, ep, None if al is None else (phoneme_ids, p0s, ps), return_latents, return_alignment,
-                                  (K, row_seeds) if return_takes else None)
+                                  (K, row_seeds) if return_takes else None, return_repair)
 
     def _finish_batch(self, rec: _Batch, ep: Optional["Endpointing"], tokens: Optional[tuple], return_latents: bool,
-                      return_alignment: bool, takes: Optional[tuple] = None):
+                      return_alignment: bool, takes: Optional[tuple] = None, return_repair: bool = False):
         """synthesize_batch's tail: one batch from the device to what the call returns.  `tokens` = (token lists, prefix lengths, token
         counts) with align=, else None; `takes` = (K, the rows' seeds) with return_takes, else None.
-        -> rows[, latents][, words[, raw alignment]][, takes]; the rows alone are returned bare."""
+        -> rows[, latents][, words[, raw alignment]][, takes][, repair]; the rows alone are returned bare."""
         eng = self.engine
         B = len(rec.ns)
         head = (rec.audio if ep is None else rec.seg).cpu().numpy()   # synchronises: the saturation counters are final
@@ -990,6 +1125,8 @@ class SmallTTS:
             win, tot, ft = _read_takes([rec], K)
             res.append([(int(win[b]), take_seed(row_seeds[b], int(win[b])) if K > 1 else int(row_seeds[b]), tot[b], ft[b])
                         for b in range(B)])
+        if return_repair:
+            res.append(_read_repair([rec]))
         return outs if len(res) == 1 else tuple(res)
 
     def synthesize_batches(self, batches: Sequence[tuple], in_flight: int = 3, release_workspaces: bool = False) -> List[list]:
@@ -1043,7 +1180,8 @@ class SmallTTS:
                         durations: Optional[Sequence[float]] = None, seed: Optional[int] = None, gap_ms: float = 120.0,
                         fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3, pcm16: bool = False,
                         prefix_tokens: Optional[Sequence[int]] = None, trim=None, return_segments: bool = False,
-                        return_words: bool = False, align=None, return_pieces: bool = False, takes=None, return_takes: bool = False):
+                        return_words: bool = False, align=None, return_pieces: bool = False, takes=None, return_takes: bool = False,
+                        repair=None, return_repair: bool = False):
         """A whole text in one voice -> one waveform (1, S), fp32 or (pcm16=True) int16 PCM, S = sum(3200 * n_i) + (pieces - 1) *
         round(gap_ms * 24).
 
@@ -1082,15 +1220,26 @@ class SmallTTS:
         times larger; where K * max_batch would pass 64 sampler rows the group size is lowered to 64 // K, and render_long then
         reproduces the waveform when it is given that max_batch.  A Piece's `seed` is the winning take's seed.  K = 1 is the call
         without `takes`.  `return_takes=True`: additionally -> per piece (winner k, the winner's seed, totals (K,), features (K, 4)),
-        from one small read-back.  Returns (waveform[, segments][, words][, pieces][, takes])."""
+        from one small read-back.
+
+        `repair` (an int = rounds, or a Repair; DESIGN 8e, UNVALIDATED on trained weights like `takes`): every group repairs its
+        rows behind its sampler and take selection (synthesize_batch(repair=)), from repair_seed(piece seed, r); `align` then
+        chooses the tapped layers / heads / steps also without return_words.  A Piece's latents are the repaired latents, so
+        render_long reproduces the waveform as ever, while its `seed` stays what the piece was first spoken from: the repaired
+        frames are not a function of that seed alone.  `return_repair=True`: additionally, as the very last element -> per piece
+        (kept (rounds,), (bad tokens, freed frames) (rounds, 2), total before (rounds,), total after (rounds,)), from one small
+        read-back.  Returns (waveform[, segments][, words][, pieces][, takes][, repair])."""
         ep = as_endpointing(trim)
         tk = as_takes(takes)
+        rp = as_repair(repair)
         if tk is None and return_takes:
             raise ValueError("synthesize_long: return_takes= belongs to takes=")
+        if rp is None and return_repair:
+            raise ValueError("synthesize_long: return_repair= belongs to repair=")
         if tk is not None and tk.k == 1 and not return_takes:
             tk = None                                          # one take and nothing to report: the call without takes
         al = as_alignment(align if align is not None else (True if return_words else None))
-        if al is not None and not return_words and tk is None:
+        if al is not None and not return_words and tk is None and rp is None:
             raise ValueError("synthesize_long: align= belongs to return_words=True")
         if voice.engine is not self.engine:
             raise ValueError("synthesize_long: the Voice belongs to another engine")
@@ -1115,18 +1264,20 @@ class SmallTTS:
             max_batch = Takes.MAX_ROWS // K                    # the sampler batch is K times the group
         groups, offsets, S = plan_long(ns, max_batch, gap_ms)
 
-        def result(out, segs, words, made, taken=None):        # words None: not aligned
+        def result(out, segs, words, made, taken=None, mended=None):   # words None: not aligned
             res = ((out,) + ((segs,) if return_segments else ()) + ((words,) if words is not None else ())
-                   + ((made,) if return_pieces else ()) + ((taken,) if return_takes else ()))
+                   + ((made,) if return_pieces else ()) + ((taken,) if return_takes else ()) + ((mended,) if return_repair else ()))
             return res if len(res) > 1 else out
 
         if not toks:
-            return result(np.zeros((1, 0), np.int16 if pcm16 else np.float32), [], [] if return_words else None, [], [])
+            return result(np.zeros((1, 0), np.int16 if pcm16 else np.float32), [], [] if return_words else None, [], [], [])
         base = self._next_seed() if seed is None else int(seed)
         seeds = [piece_seed(base, i) for i in range(len(toks))]
-        al_b = al if (al is not None or tk is None) else Alignment()   # takes: the path leaves the prefix out, as the words do
+        al_b = al if (al is not None or (tk is None and rp is None)) else Alignment()   # takes, repair: the path leaves the prefix out, as the words do
         # (return_takes with one take: the deferred batch returns its record either way, the flag makes it score its rows)
         kw = ({} if al_b is None else {"align": al_b}) if tk is None else {"align": al_b, "takes": tk, "return_takes": return_takes}
+        if rp is not None:
+            kw["repair"] = rp
         # with trim every batch enqueues its endpoints behind its decode, on its own stream: they overlap the other batches in flight
         calls = [lambda g=g: self.synthesize_batch(None, [toks[i] for i in g], None, frames=[ns[i] for i in g], voices=[voice] * len(g),
                                                    seeds=[seeds[i] for i in g], trim=ep, _defer=True,
@@ -1134,6 +1285,7 @@ class SmallTTS:
                  for g in groups]
         out, segs, pending = self._join_long(calls, groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16)
         words = made = taken = None
+        mended = _read_repair(pending) if return_repair else None   # one small read-back for the whole text
         spoken = seeds
         if tk is not None and (return_takes or return_pieces):
             win, tot, ft = _read_takes(pending, K)             # one small read-back for the whole text
@@ -1162,7 +1314,7 @@ class SmallTTS:
                 xg = flat[pos: pos + len(g) * Ng * 64].reshape(len(g), Ng, 64)
                 pos += len(g) * Ng * 64
                 made += [Piece(toks[i], len(prefix), xg[r, : ns[i]], spoken[i], piece_spans[i]) for r, i in enumerate(g)]
-        return result(out, segs, words, made, taken)
+        return result(out, segs, words, made, taken, mended)
 
     def _join_long(self, calls, groups, ns, offsets, S, ep: Optional["Endpointing"], in_flight: int, gap_ms: float, fade_ms: float,
                    pcm16: bool):

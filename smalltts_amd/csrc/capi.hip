@@ -166,6 +166,33 @@ int smtts_take_select(smtts_handle h, void* stream, const float* total, int G, i
     return e == hipSuccess ? 0 : E.fail_hip(e, "take_select");
 }
 
+int smtts_repair_plan(smtts_handle h, void* stream, const float* mass, const int32_t* spans, const int32_t* n_len, const int32_t* p0,
+                      const int32_t* p1, const uint8_t* keep, int B, int N, int P, float tau_tok, int max_span, int margin, uint8_t* pin,
+                      int32_t* counts) { NULLCHK;
+    if (B < 1 || B > 65536) return E.fail("smtts_repair_plan: B must be in [1, 65536]");
+    if (N < 1 || P < 1 || N > 225 || P > 198) return E.fail("smtts_repair_plan: N must be in [1, 225] and P in [1, 198] (the range of smtts_align_path)");
+    if (!mass || !spans || !n_len || !p0 || !p1 || !pin || !counts) return E.fail("smtts_repair_plan: a required pointer is NULL");
+    if (max_span < 1 || max_span > 225) return E.fail("smtts_repair_plan: max_span must be in [1, 225]");
+    if (margin < 0 || margin > 32) return E.fail("smtts_repair_plan: margin must be in [0, 32]");
+    if (tau_tok != tau_tok) return E.fail("smtts_repair_plan: the threshold must not be NaN");
+    hipError_t e = launch_repair_plan(mass, spans, n_len, p0, p1, keep, B, N, P, tau_tok, max_span, margin, pin, counts, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "repair_plan");
+}
+int smtts_repair_keep(smtts_handle h, void* stream, int G, int N, int P, const float* total_cur, const float* total_new,
+                      const int32_t* counts, const int32_t* feat_cur, const int32_t* feat_new, float* x_cur, const float* x_new,
+                      int32_t* spans_cur, const int32_t* spans_new, float* mass_cur, const float* mass_new, float* total_out,
+                      int32_t* feat_out, int32_t* kept) { NULLCHK;
+    if (G < 1 || G > 65535) return E.fail("smtts_repair_keep: G must be in [1, 65535]");
+    if (N < 1 || P < 1 || N > 225 || P > 198) return E.fail("smtts_repair_keep: N must be in [1, 225] and P in [1, 198] (the range of smtts_align_path)");
+    if (!total_cur || !total_new || !counts || !feat_cur || !feat_new || !x_cur || !x_new || !total_out || !feat_out || !kept)
+        return E.fail("smtts_repair_keep: a required pointer is NULL");
+    if ((spans_cur != nullptr) != (spans_new != nullptr) || (mass_cur != nullptr) != (mass_new != nullptr))
+        return E.fail("smtts_repair_keep: spans_cur / spans_new and mass_cur / mass_new are given or NULL together");
+    hipError_t e = launch_repair_keep(G, N, P, total_cur, total_new, counts, feat_cur, feat_new, x_cur, x_new, spans_cur, spans_new, mass_cur,
+                                      mass_new, total_out, feat_out, kept, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "repair_keep");
+}
+
 int smtts_codec_hop(smtts_handle h) { NULLCHK0; return E.codec_spec().hop(); }
 size_t smtts_decode_workspace_bytes(smtts_handle h, int B, int T) { NULLCHK0; return E.decode_ws_bytes(B, T); }
 int smtts_codec_decode(smtts_handle h, void* stream, const float* latents, int B, int T, float* audio, void* ws,

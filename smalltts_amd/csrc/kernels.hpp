@@ -87,6 +87,19 @@ hipError_t launch_take_scores(const float* mass, const int* spans, const float* 
 // int32 (G) = k.  An optional input and its output are given or NULL together.
 hipError_t launch_take_select(const float* total, int G, int K, int N, int P, const float* x, const int* n_len, const int* spans,
                               const float* mass, float* x_win, int* n_win, int* spans_win, float* mass_win, int* winner, hipStream_t st);
+// ---- repair (repair.hip) ----------------------------------------------------------------------------------------------------------
+// Pin mask of every row behind launch_align_path, one workgroup per row: a token of [p0, p1) is bad when its span is empty, longer than
+// max_span, or holds no frame with mass >= tau_tok; a bad token with a span frees its frames +- margin.  pin u8 (B, N) = 1 for frames
+// below n that are not freed or that keep (u8 (B, N) or NULL) names, 0 elsewhere (every byte written); counts int32 (B, 2) = (bad
+// tokens, frames below n with pin 0).  The definitions: include/smalltts_hip.h smtts_repair_plan.  N <= 225, P <= 198.
+hipError_t launch_repair_plan(const float* mass, const int* spans, const int* n_len, const int* p0, const int* p1, const uint8_t* keep,
+                              int B, int N, int P, float tau_tok, int max_span, int margin, uint8_t* pin, int* counts, hipStream_t st);
+// Row g of x_new (N, 64) and, where given, spans_new (P, 2) and mass_new (N, P) replaces row g of the _cur buffers in place, bit for
+// bit, where counts[g][1] > 0 and total_new[g] < total_cur[g] (NaN counts as +inf, strict <); total_out / feat_out (G) / (G, 4) are
+// those of the row that stays, kept int32 (G) the decision.  The three small outputs must not alias an input.
+hipError_t launch_repair_keep(int G, int N, int P, const float* total_cur, const float* total_new, const int* counts, const int* feat_cur,
+                              const int* feat_new, float* x_cur, const float* x_new, int* spans_cur, const int* spans_new, float* mass_cur,
+                              const float* mass_new, float* total_out, int* feat_out, int* kept, hipStream_t st);
 // fp32 projection rows [B*N][4*H*dh] = [q | k | v | gate] (bias included) -> the self part of AttnImg (dit.py:95-108; the arithmetic
 // the gemm3 EpiQKV epilogue performs on its accumulators, as a stand-alone kernel: test hook + reference for the epilogue)
 struct QkvPackArgs {

@@ -21,6 +21,7 @@
 
 #include "kernels.hpp"
 #include "prof.hpp"
+#include "row_copy.hpp"
 
 namespace {
 
@@ -44,11 +45,6 @@ __device__ __forceinline__ float rn_div(float a, float b) {
     return a / b;
 }
 
-__device__ __forceinline__ int wave_sum(int v) {
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 __device__ __forceinline__ int wave_max(int v) {
 #pragma unroll
     for (int o = 32; o >= 1; o >>= 1) {
@@ -116,28 +112,7 @@ __global__ __launch_bounds__(TK_NT) void take_scores_kernel(const float* __restr
     }
 }
 
-struct TakeCopy {   // one gathered buffer: rows of `n4` 4-byte elements; vec: 16-byte lanes (n4 % 4 == 0, both bases 16-byte aligned)
-    const uint32_t* src;
-    uint32_t* dst;
-    long n4;
-    int vec;
-};
-
-__device__ __forceinline__ void take_copy_row(const TakeCopy& c, long srow, long drow) {
-    if (!c.src) return;   // (uniform)
-    const long i0 = (long)blockIdx.x * TK_NT + threadIdx.x, step = (long)gridDim.x * TK_NT;
-    if (c.vec) {
-        const uint4* const s = reinterpret_cast<const uint4*>(c.src + srow * c.n4);
-        uint4* const d = reinterpret_cast<uint4*>(c.dst + drow * c.n4);
-        for (long i = i0; i < c.n4 / 4; i += step) d[i] = s[i];
-    } else {
-        const uint32_t* const s = c.src + srow * c.n4;
-        uint32_t* const d = c.dst + drow * c.n4;
-        for (long i = i0; i < c.n4; i += step) d[i] = s[i];
-    }
-}
-
-__global__ __launch_bounds__(TK_NT) void take_select_kernel(const float* __restrict__ total, int K, TakeCopy x, TakeCopy sp, TakeCopy ms,
+__global__ __launch_bounds__(TK_NT) void take_select_kernel(const float* __restrict__ total, int K, RowCopy x, RowCopy sp, RowCopy ms,
                                                             const int* __restrict__ n_len, int* __restrict__ n_win, int* __restrict__ winner) {
     const int g = blockIdx.y;
     int win = 0;
@@ -149,22 +124,13 @@ __global__ __launch_bounds__(TK_NT) void take_select_kernel(const float* __restr
         if (s < best) { best = s; win = k; }
     }
     const long srow = (long)g * K + win;
-    take_copy_row(x, srow, g);
-    take_copy_row(sp, srow, g);
-    take_copy_row(ms, srow, g);
+    row_copy(x, srow, g, TK_NT);
+    row_copy(sp, srow, g, TK_NT);
+    row_copy(ms, srow, g, TK_NT);
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         n_win[g] = n_len[srow];
         winner[g] = win;
     }
-}
-
-TakeCopy take_copy(const void* src, void* dst, long n4) {
-    TakeCopy c;
-    c.src = static_cast<const uint32_t*>(src);
-    c.dst = static_cast<uint32_t*>(dst);
-    c.n4 = n4;
-    c.vec = src && (n4 % 4 == 0) && (((uintptr_t)src | (uintptr_t)dst) & 15) == 0;
-    return c;
 }
 
 }  // namespace
@@ -185,8 +151,8 @@ hipError_t launch_take_select(const float* total, int G, int K, int N, int P, co
     if (G <= 0) return hipSuccess;
     if (K < 1 || K > 16 || N < 1 || P < 1 || N > TK_MAXN || P > TK_MAXP || G > 65535) return hipErrorInvalidValue;
     if ((spans != nullptr) != (spans_win != nullptr) || (mass != nullptr) != (mass_win != nullptr)) return hipErrorInvalidValue;
-    const TakeCopy cx = take_copy(x, x_win, (long)N * 64), cs = take_copy(spans, spans_win, (long)P * 2),
-                   cm = take_copy(mass, mass_win, (long)N * P);
+    const RowCopy cx = make_row_copy(x, x_win, (long)N * 64), cs = make_row_copy(spans, spans_win, (long)P * 2),
+                   cm = make_row_copy(mass, mass_win, (long)N * P);
     // lanes of the widest copy, four to a thread
     long units = cx.vec ? cx.n4 / 4 : cx.n4;
     if (cm.src) units = std::max(units, cm.vec ? cm.n4 / 4 : cm.n4);

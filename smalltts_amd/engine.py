@@ -579,6 +579,78 @@ class HipEngine:
                                             _p(x_win), _p(n_win), _p(spans_win), _p(mass_win), _p(winner)), "take_select")
         return x_win, n_win, spans_win, mass_win, winner
 
+    def repair_plan(self, mass: torch.Tensor, spans: torch.Tensor, ns, p0, p1, repair, keep: Optional[torch.Tensor] = None):
+        """The pin mask that re-speaks only the badly aligned tokens of every row (smtts_repair_plan; the definition:
+        include/smalltts_hip.h).  mass fp32 (B,N,P) and spans int32 (B,P,2) as sample(align=) / align_path (or take_select)
+        return them, contiguous on the device; ns, p0, p1 the host integers align_path was given; repair anything with .tau_token,
+        .max_span and .margin (e.g. api.Repair); keep an optional bool / uint8 (B,N) device tensor of frames that stay pinned whatever
+        the plan says.  -> (pin bool (B,N), what sample(pin=) takes: True = keep the frame; counts int32 (B,2) = (bad tokens, freed
+        frames)), on the device.  One launch on the current stream, no synchronisation.  How well the freed frames are re-spoken is
+        unvalidated on trained weights (api.Repair)."""
+        if mass.dim() != 3 or mass.dtype != torch.float32 or not mass.is_contiguous() or mass.device != self.device:
+            raise ValueError("repair_plan: mass must be a contiguous fp32 (B,N,P) tensor on the engine's device")
+        B, N, P = (int(v) for v in mass.shape)
+        if not (1 <= N <= ALIGN_MAX_FRAMES and 1 <= P <= ALIGN_MAX_TOKENS):
+            raise ValueError(f"repair_plan: N = {N}, P = {P} outside the supported range N <= {ALIGN_MAX_FRAMES}, P <= {ALIGN_MAX_TOKENS}")
+        if spans.dtype != torch.int32 or tuple(spans.shape) != (B, P, 2) or not spans.is_contiguous() or spans.device != self.device:
+            raise ValueError(f"repair_plan: spans must be a contiguous int32 ({B},{P},2) tensor on the engine's device")
+        if keep is not None and (keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != (B, N) or not keep.is_contiguous()
+                                 or keep.device != self.device):
+            raise ValueError(f"repair_plan: keep must be a contiguous bool or uint8 ({B},{N}) tensor on the engine's device, or None")
+        if B < 1 or len(ns) != B or len(p0) != B or len(p1) != B:
+            raise ValueError("repair_plan: one frame count and one token range per row")
+        tt, span, margin = float(repair.tau_token), int(repair.max_span), int(repair.margin)
+        if tt != tt or not 1 <= span <= ALIGN_MAX_FRAMES or not 0 <= margin <= 32:
+            raise ValueError(f"repair_plan: a threshold that is not NaN, max_span in [1, {ALIGN_MAX_FRAMES}] and margin in [0, 32]")
+        tab = self._upload_i32([ns, p0, p1])
+        pin = torch.empty(B, N, dtype=torch.bool, device=self.device)       # (one byte per frame, written 0 / 1)
+        counts = torch.empty(B, 2, dtype=torch.int32, device=self.device)
+        self._ck(self.lib.smtts_repair_plan(self.h, self._stream(), _p(mass), _p(spans), _p(tab[0]), _p(tab[1]), _p(tab[2]), _p(keep), B, N, P,
+                                            tt, span, margin, _p(pin), _p(counts)), "repair_plan")
+        return pin, counts
+
+    def repair_keep(self, total_cur: torch.Tensor, total_new: torch.Tensor, counts: torch.Tensor, feat_cur: torch.Tensor,
+                    feat_new: torch.Tensor, x_cur: torch.Tensor, x_new: torch.Tensor, spans_cur: Optional[torch.Tensor] = None,
+                    spans_new: Optional[torch.Tensor] = None, mass_cur: Optional[torch.Tensor] = None,
+                    mass_new: Optional[torch.Tensor] = None):
+        """Keeps the repaired row only where it is strictly better (smtts_repair_keep): where counts[g][1] > 0 and total_new[g] <
+        total_cur[g] (NaN counts as +inf), row g of x_new (G,N,64) and, where given, spans_new (G,P,2) and mass_new (G,N,P) replaces
+        row g of x_cur, spans_cur, mass_cur IN PLACE, bit for bit; every other row keeps its bits.  total_* fp32 (G), feat_* int32
+        (G,4) (take_scores), counts int32 (G,2) (repair_plan), all contiguous on the device.  -> (total_out (G), feat_out (G,4), kept
+        int32 (G)), fresh tensors: those of the row that stays, and the decision.  One launch on the current stream, no
+        synchronisation."""
+        dev = self.device
+
+        def ok(t, dtype, shape):
+            return t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev
+        if total_cur.dim() != 1 or int(total_cur.shape[0]) < 1:
+            raise ValueError("repair_keep: total_cur must be a contiguous fp32 (G,) tensor on the engine's device")
+        G = int(total_cur.shape[0])
+        if not (ok(total_cur, torch.float32, (G,)) and ok(total_new, torch.float32, (G,))):
+            raise ValueError(f"repair_keep: total_cur and total_new must be contiguous fp32 ({G},) tensors on the engine's device")
+        if not (ok(counts, torch.int32, (G, 2)) and ok(feat_cur, torch.int32, (G, 4)) and ok(feat_new, torch.int32, (G, 4))):
+            raise ValueError(f"repair_keep: counts must be int32 ({G},2) and feat_cur / feat_new int32 ({G},4), contiguous on the engine's device")
+        if x_cur.dim() != 3 or not ok(x_cur, torch.float32, (G, int(x_cur.shape[1]), LATENT)) or not ok(x_new, torch.float32, tuple(x_cur.shape)):
+            raise ValueError(f"repair_keep: x_cur and x_new must be contiguous fp32 ({G},N,{LATENT}) tensors on the engine's device")
+        N = int(x_cur.shape[1])
+        if (spans_cur is None) != (spans_new is None) or (mass_cur is None) != (mass_new is None):
+            raise ValueError("repair_keep: spans_cur / spans_new and mass_cur / mass_new are given or None together")
+        P = (int(spans_cur.shape[1]) if spans_cur is not None and spans_cur.dim() == 3
+             else int(mass_cur.shape[2]) if mass_cur is not None and mass_cur.dim() == 3 else 1)
+        if not (1 <= N <= ALIGN_MAX_FRAMES and 1 <= P <= ALIGN_MAX_TOKENS):
+            raise ValueError(f"repair_keep: N = {N}, P = {P} outside the supported range N <= {ALIGN_MAX_FRAMES}, P <= {ALIGN_MAX_TOKENS}")
+        if spans_cur is not None and not (ok(spans_cur, torch.int32, (G, P, 2)) and ok(spans_new, torch.int32, (G, P, 2))):
+            raise ValueError(f"repair_keep: spans_cur and spans_new must be contiguous int32 ({G},{P},2) tensors on the engine's device, or None")
+        if mass_cur is not None and not (ok(mass_cur, torch.float32, (G, N, P)) and ok(mass_new, torch.float32, (G, N, P))):
+            raise ValueError(f"repair_keep: mass_cur and mass_new must be contiguous fp32 ({G},{N},{P}) tensors on the engine's device, or None")
+        total_out = torch.empty(G, device=dev)
+        feat_out = torch.empty(G, 4, dtype=torch.int32, device=dev)
+        kept = torch.empty(G, dtype=torch.int32, device=dev)
+        self._ck(self.lib.smtts_repair_keep(self.h, self._stream(), G, N, P, _p(total_cur), _p(total_new), _p(counts), _p(feat_cur),
+                                            _p(feat_new), _p(x_cur), _p(x_new), _p(spans_cur), _p(spans_new), _p(mass_cur), _p(mass_new),
+                                            _p(total_out), _p(feat_out), _p(kept)), "repair_keep")
+        return total_out, feat_out, kept
+
     @property
     def hop(self) -> int:
         return int(self.lib.smtts_codec_hop(self.h))

@@ -7,12 +7,15 @@ selection unvalidated on trained weights; resolution one codec frame = 133 ms). 
 next to it out.words.srt with one cue per word group.  --take OUT.npz: the pieces (tokens, latents, seeds; with --words also each
 piece's token spans) and the join parameters, what scripts/respeak.py re-speaks a span of and renders again.
 --takes K: every piece is sampled K times and the take whose text alignment scores best is kept (api.Takes; what the score is worth is
-unvalidated on trained weights); with --words the JSON becomes {"words": [...], "takes": [{piece, winner, seed, totals}, ...]}."""
+unvalidated on trained weights); with --words the JSON becomes {"words": [...], "takes": [{piece, winner, seed, totals}, ...]}.
+--repair [ROUNDS]: behind the sampler (and --takes) only the badly aligned words of every piece are spoken again, ROUNDS times
+(default 1), and a repaired piece is kept where it scores strictly better (api.Repair; unvalidated on trained weights like --takes);
+with --words the JSON gains "repair": [{piece, kept, bad, free, before, after}, ...], one list entry per round in each field."""
 import argparse
 import json
 from pathlib import Path
 
-from ..api import SAMPLE_RATE, Endpointing, SmallTTS, Takes, estimate_duration, format_srt, save_take, split_text, token_groups
+from ..api import SAMPLE_RATE, Endpointing, Repair, SmallTTS, Takes, estimate_duration, format_srt, save_take, split_text, token_groups
 from ..audio import read_wav, write_wav_pcm16
 from ..phonemes import decode_token_ids, get_token_ids, parse_tokens_arg
 from ._common import add_engine_args
@@ -23,19 +26,27 @@ def group_texts(token_lists) -> list:
     return [(i, kind, ph) for i, toks in enumerate(token_lists) for kind, ph, _t0, _t1 in token_groups(toks)]
 
 
-def words_json(words, texts, takes=None) -> str:
+def words_json(words, texts, takes=None, repair=None) -> str:
     """synthesize_long's words + group_texts -> the --words file: a JSON list of {index, piece, kind, phonemes, start, end (samples),
     start_s, end_s (seconds)}.  With `takes` (synthesize_long's return_takes) the file is {"words": that list, "takes": [{piece,
-    winner, seed, totals}, ...]}, one entry per piece; a total that is not finite is written as null."""
+    winner, seed, totals}, ...]}, one entry per piece; a total that is not finite is written as null.  With `repair`
+    (synthesize_long's return_repair) the file is such an object with "repair": [{piece, kept, bad, free, before, after}, ...], every
+    field but `piece` a list with one entry per round."""
     if len(words) != len(texts):
         raise ValueError(f"{len(words)} timed groups for {len(texts)} groups of the text")
     rows = [{"index": int(gi), "piece": int(pi), "kind": kind, "phonemes": ph, "start": int(s), "end": int(e),
              "start_s": round(int(s) / SAMPLE_RATE, 4), "end_s": round(int(e) / SAMPLE_RATE, 4)}
             for (gi, kind, s, e), (pi, _k, ph) in zip(words, texts)]
+    fin = lambda v: float(v) if float("-inf") < float(v) < float("inf") else None
+    if takes is not None or repair is not None:
+        rows = {"words": rows}
     if takes is not None:
-        fin = lambda v: float(v) if float("-inf") < float(v) < float("inf") else None
-        rows = {"words": rows, "takes": [{"piece": i, "winner": int(w), "seed": int(sd), "totals": [fin(v) for v in tot]}
-                                         for i, (w, sd, tot, _feat) in enumerate(takes)]}
+        rows["takes"] = [{"piece": i, "winner": int(w), "seed": int(sd), "totals": [fin(v) for v in tot]}
+                         for i, (w, sd, tot, _feat) in enumerate(takes)]
+    if repair is not None:
+        rows["repair"] = [{"piece": i, "kept": [int(v) for v in kept], "bad": [int(c[0]) for c in counts], "free": [int(c[1]) for c in counts],
+                           "before": [fin(v) for v in before], "after": [fin(v) for v in after]}
+                          for i, (kept, counts, before, after) in enumerate(repair)]
     return json.dumps(rows, ensure_ascii=False, indent=1)
 
 
@@ -64,6 +75,8 @@ def parse_args(argv=None):
     ap.add_argument("--srt", default=None, metavar="OUT.srt", help="write one subtitle cue per piece, and OUT.words.srt with one cue per word group")
     ap.add_argument("--take", default=None, metavar="OUT.npz", help="save the pieces and the join parameters (for scripts/respeak.py)")
     ap.add_argument("--takes", type=int, default=None, metavar="K", help=f"sample every piece K times (1..{Takes.MAX_K}) and keep the best-aligned take")
+    ap.add_argument("--repair", type=int, nargs="?", const=1, default=None, metavar="ROUNDS",
+                    help=f"speak only the badly aligned words of every piece again, ROUNDS times (1..{Repair.MAX_ROUNDS}, default 1)")
     ap.add_argument("--max-batch", type=int, default=8)
     ap.add_argument("--in-flight", type=int, default=3)
     add_engine_args(ap)
@@ -76,6 +89,8 @@ def parse_args(argv=None):
         ap.error("--level needs --trim")
     if args.takes is not None and not 1 <= args.takes <= Takes.MAX_K:
         ap.error(f"--takes must lie in [1, {Takes.MAX_K}]")
+    if args.repair is not None and not 1 <= args.repair <= Repair.MAX_ROUNDS:
+        ap.error(f"--repair must lie in [1, {Repair.MAX_ROUNDS}]")
     if args.takes is not None and args.takes * args.max_batch > Takes.MAX_ROWS:
         args.max_batch = Takes.MAX_ROWS // args.takes   # synthesize_long's rule, applied here so that --take records the group size used
     return args
@@ -100,6 +115,8 @@ def main(argv=None):
         kw.update(return_pieces=True)
     if args.takes is not None:
         kw.update(takes=args.takes, return_takes=True)
+    if args.repair is not None:
+        kw.update(repair=args.repair, return_repair=True)
     if args.tokens_file:
         with open(args.tokens_file) as f:
             token_lists = [parse_tokens_arg(line) for line in f if line.strip()]
@@ -117,7 +134,10 @@ def main(argv=None):
         print(f"generating {len(pieces)} pieces")
         token_lists, piece_texts = [tok(p) for p in pieces], pieces
         audio = tts.synthesize_long(voice, token_lists=token_lists, durations=[estimate_duration(p) for p in pieces], **kw)
-    chosen = None
+    chosen = mended = None
+    if args.repair is not None:                            # (the very last element)
+        audio, mended = (audio[:-1] if len(audio) > 2 else audio[0]), audio[-1]
+        print("repaired: " + " ".join(str(int(sum(kept))) for kept, _counts, _before, _after in mended))
     if args.takes is not None:
         audio, chosen = (audio[:-1] if len(audio) > 2 else audio[0]), audio[-1]
         print("takes kept: " + " ".join(str(w) for w, _seed, _tot, _feat in chosen))
@@ -132,7 +152,7 @@ def main(argv=None):
         texts = group_texts(token_lists)
         if args.words:
             Path(args.words).parent.mkdir(parents=True, exist_ok=True)
-            Path(args.words).write_text(words_json(words, texts, chosen), encoding="utf-8")
+            Path(args.words).write_text(words_json(words, texts, chosen, mended), encoding="utf-8")
             print(f"{args.words} ({len(words)} word groups)")
         if args.srt:
             Path(args.srt).parent.mkdir(parents=True, exist_ok=True)
