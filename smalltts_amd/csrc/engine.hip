@@ -24,7 +24,7 @@ struct Bump {  // bump allocator over a caller-owned workspace (also used, with 
     template <class T>
     T* take(size_t n) {
         off = (off + 255) & ~size_t(255);
-        T* r = reinterpret_cast<T*>(p + off);
+        T* r = reinterpret_cast<T*>(reinterpret_cast<uintptr_t>(p) + off);   // (integer arithmetic: the sizing run's base is null)
         off += n * sizeof(T);
         return r;
     }
@@ -143,9 +143,9 @@ Engine::~Engine() {
     if (g_prof == &prof_) g_prof = nullptr;
     (void)hipSetDevice(device_);
     for (auto& kv : aux_sets_) {
-        if (kv.second.stream) (void)hipStreamDestroy(kv.second.stream);
-        if (kv.second.fork) (void)hipEventDestroy(kv.second.fork);
-        if (kv.second.join) (void)hipEventDestroy(kv.second.join);
+        (void)hipStreamDestroy(kv.second.stream);
+        (void)hipEventDestroy(kv.second.fork);
+        (void)hipEventDestroy(kv.second.join);
     }
     for (void* p : allocs_) (void)hipFree(p);
     for (void* p : pack_allocs_) (void)hipFree(p);
@@ -969,18 +969,22 @@ size_t Engine::cond_ws_bytes(int B, int R, int P) const {
 // rows) that each fill a fraction of the chip; run side by side they overlap almost completely.
 // One side stream + event pair PER CALLER STREAM (round 6): a caller that keeps several batches in flight gives each its own stream, and
 // each of those forks onto its own side stream — the text encoders / modulation chains of batches in flight no longer queue behind one
-// another on a single engine-wide stream.  The set of the call being enqueued is installed in aux_ / ev_fork_ / ev_join_ (one host thread
-// enqueues one call at a time).
-int Engine::ensure_aux(hipStream_t st) {
-    AuxSet& a = aux_sets_[st];
-    if (!a.stream) {
-        if (aux_sets_.size() > 64) return fail("side streams: more than 64 caller streams on one engine");
-        HIPC(hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking));
-        HIPC(hipEventCreateWithFlags(&a.fork, hipEventDisableTiming));
-        HIPC(hipEventCreateWithFlags(&a.join, hipEventDisableTiming));
+// another on a single engine-wide stream.  A set enters the map only complete (stream and both events), at most 64 of them.
+const Engine::AuxSet* Engine::side_set(hipStream_t st) {
+    const auto it = aux_sets_.find(st);
+    if (it != aux_sets_.end()) return &it->second;
+    if (aux_sets_.size() >= 64) { fail("side streams: more than 64 caller streams on one engine"); return nullptr; }
+    AuxSet a;
+    hipError_t e = hipStreamCreateWithFlags(&a.stream, hipStreamNonBlocking);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&a.fork, hipEventDisableTiming);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&a.join, hipEventDisableTiming);
+    if (e != hipSuccess) {
+        if (a.fork) (void)hipEventDestroy(a.fork);
+        if (a.stream) (void)hipStreamDestroy(a.stream);
+        fail_hip(e, "side stream / events of a caller stream");
+        return nullptr;
     }
-    aux_ = a.stream; ev_fork_ = a.fork; ev_join_ = a.join;
-    return 0;
+    return &aux_sets_.emplace(st, a).first->second;
 }
 
 int Engine::cond_encode(hipStream_t st, const float* ref, const int64_t* ref_len, const int64_t* ids,
@@ -997,12 +1001,12 @@ int Engine::cond_encode(hipStream_t st, const float* ref, const int64_t* ref_len
     w.plan(bump, B, R);
     wt.plan(bump, B, P);
     const bool fork = dual_stream_ && R > 0 && P > 0;
-    hipStream_t stt = st;  // stream of the text half
+    const AuxSet* const side = fork ? side_set(st) : nullptr;
+    if (fork && !side) return 1;
+    const hipStream_t stt = fork ? side->stream : st;  // stream of the text half
     if (fork) {
-        if (ensure_aux(st)) return 1;
-        HIPC(hipEventRecord(ev_fork_, st));  // inputs produced on the caller's stream are visible to the side stream
-        HIPC(hipStreamWaitEvent(aux_, ev_fork_, 0));
-        stt = aux_;
+        HIPC(hipEventRecord(side->fork, st));  // inputs produced on the caller's stream are visible to the side stream
+        HIPC(hipStreamWaitEvent(stt, side->fork, 0));
     }
 
     // ---- E2 text encoder (phonemes.py:200-207) + phoneme_proj (dit.py:293-298) ---------------
@@ -1014,7 +1018,7 @@ int Engine::cond_encode(hipStream_t st, const float* ref, const int64_t* ref_len
         if (enc_out(stt, true, wt, B * P, ph_mask, mem)) return 1;
         if (enc_kv(stt, true, wt, mem, B, P, k_text, v_text)) return 1;
     }
-    if (fork) HIPC(hipEventRecord(ev_join_, aux_));
+    if (fork) HIPC(hipEventRecord(side->join, stt));
     // ---- E1 style encoder (style.py:144-174) -------------------------------------------------
     if (R > 0) {
         HIPC(launch_len_mask(ref_len, ref_mask, B, R, st));
@@ -1025,7 +1029,7 @@ int Engine::cond_encode(hipStream_t st, const float* ref, const int64_t* ref_len
         // ---- E3 cross KV for the reference tokens (dit.py:80-93) -------------------------------
         if (enc_kv(st, false, w, seq, B, R, k_ref, v_ref)) return 1;
     }
-    if (fork) HIPC(hipStreamWaitEvent(st, ev_join_, 0));  // join: everything after cond_encode sees both halves
+    if (fork) HIPC(hipStreamWaitEvent(st, side->join, 0));  // join: everything after cond_encode sees both halves
     return 0;
 }
 
@@ -1062,24 +1066,35 @@ int Engine::enc_kv(hipStream_t st, bool text, const EncWs& w, const float* seq, 
 // (tiny-M GEMM chain on the fp32-A kernel; the tanh of the gates, dit.py:198,201, is applied once here
 // instead of per output element in the residual epilogues)
 // ---------------------------------------------------------------------------------------------
-int Engine::modulation(hipStream_t st, const float* t_dev, int rows, float* sinb, float* t1, float* temb, float* e1,
-                       float* semb, float* mod, float* ftab) {
+struct Engine::ModWs {
+    float *sinb, *t1, *temb, *e1, *semb, *mod, *ftab = nullptr;
+    void plan(Bump& b, int rows, bool fold = false) {
+        if (fold) ftab = b.take<float>((size_t)rows * 2 * kFoldNF);
+        sinb = b.take<float>((size_t)rows * 256);
+        t1 = b.take<float>((size_t)rows * kHidden);
+        temb = b.take<float>((size_t)rows * kHidden);
+        e1 = b.take<float>((size_t)rows * 2 * kHidden);
+        semb = b.take<float>((size_t)rows * kHidden);
+        mod = b.take<float>((size_t)rows * kModLd);
+    }
+};
+int Engine::modulation(hipStream_t st, const float* t_dev, int rows, const ModWs& m) {
     ProfTag ptag("mod");
     const int pc = prec_[SITE_COND];  // tiny-M chain on the fp32-A kernel: always split-bf16 unless the preset is plain bf16
-    HIPC(launch_time_sinusoid(t_dev, sinb, rows, st));
-    HIPC(gemm_store(ops(sinb, rowmap_plain(256), time0_, rows), ACT_SILU,
-                    store_to(t1, rowmap_plain(kHidden), rawp("time_embedding.mlp.0.bias")), 1, pc, st, tune_));
-    HIPC(gemm_store(ops(t1, rowmap_plain(kHidden), time2_, rows), ACT_NONE,
-                    store_to(temb, rowmap_plain(kHidden), rawp("time_embedding.mlp.2.bias")), 1, pc, st, tune_));
-    HIPC(gemm_store(ops(temb, rowmap_plain(kHidden), emb0_, rows), ACT_SILU,
-                    store_to(e1, rowmap_plain(2 * kHidden), rawp("dit.emb_proj.0.bias")), 1, pc, st, tune_));
+    HIPC(launch_time_sinusoid(t_dev, m.sinb, rows, st));
+    HIPC(gemm_store(ops(m.sinb, rowmap_plain(256), time0_, rows), ACT_SILU,
+                    store_to(m.t1, rowmap_plain(kHidden), rawp("time_embedding.mlp.0.bias")), 1, pc, st, tune_));
+    HIPC(gemm_store(ops(m.t1, rowmap_plain(kHidden), time2_, rows), ACT_NONE,
+                    store_to(m.temb, rowmap_plain(kHidden), rawp("time_embedding.mlp.2.bias")), 1, pc, st, tune_));
+    HIPC(gemm_store(ops(m.temb, rowmap_plain(kHidden), emb0_, rows), ACT_SILU,
+                    store_to(m.e1, rowmap_plain(2 * kHidden), rawp("dit.emb_proj.0.bias")), 1, pc, st, tune_));
     // AdaLN consumes silu(emb) only (dit.py:20,36), so the SiLU is fused into this epilogue
-    HIPC(gemm_store(ops(e1, rowmap_plain(2 * kHidden), emb2_, rows), ACT_SILU,
-                    store_to(semb, rowmap_plain(kHidden), rawp("dit.emb_proj.2.bias")), 1, pc, st, tune_));
-    HIPC(gemm_store(ops(semb, rowmap_plain(kHidden), modall_, rows), ACT_NONE,
-                    store_to(mod, rowmap_plain(kModLd), modall_b_), 1, pc, st, tune_));
-    HIPC(launch_tanh_gates(mod, rows, kModLd, kBlocks, kModPerBlock, kHidden, st));
-    return ftab ? fold_tables(st, mod, rows, ftab) : 0;
+    HIPC(gemm_store(ops(m.e1, rowmap_plain(2 * kHidden), emb2_, rows), ACT_SILU,
+                    store_to(m.semb, rowmap_plain(kHidden), rawp("dit.emb_proj.2.bias")), 1, pc, st, tune_));
+    HIPC(gemm_store(ops(m.semb, rowmap_plain(kHidden), modall_, rows), ACT_NONE,
+                    store_to(m.mod, rowmap_plain(kModLd), modall_b_), 1, pc, st, tune_));
+    HIPC(launch_tanh_gates(m.mod, rows, kModLd, kBlocks, kModPerBlock, kHidden, st));
+    return m.ftab ? fold_tables(st, m.mod, rows, m.ftab) : 0;
 }
 
 // LN-fold tables of every (step, block, site): W shift and W (1 + scale) on the weights the block GEMMs multiply
@@ -1111,20 +1126,6 @@ int Engine::fold_tables(hipStream_t st, const float* mod, int rows, float* ftab)
 
 bool Engine::dit_fold_on(long rows) const { return fold_epi_on() && rows <= kFoldMaxRows; }
 
-namespace {
-struct ModWs {
-    float *sinb, *t1, *temb, *e1, *semb, *mod, *ftab = nullptr;
-    void plan(Bump& b, int rows, bool fold = false) {
-        if (fold) ftab = b.take<float>((size_t)rows * 2 * kFoldNF);
-        sinb = b.take<float>((size_t)rows * 256);
-        t1 = b.take<float>((size_t)rows * kHidden);
-        temb = b.take<float>((size_t)rows * kHidden);
-        e1 = b.take<float>((size_t)rows * 2 * kHidden);
-        semb = b.take<float>((size_t)rows * kHidden);
-        mod = b.take<float>((size_t)rows * kModLd);
-    }
-};
-}  // namespace
 struct Engine::CoreWs {
     float *h, *x, *qkvg, *part, *lnpart, *lnc;   // lnc [M]: the LN-fold producers' row shift (gemm.hpp LnFoldIn::cshift)
     float *rope_c, *rope_s;  // cos / sin of a caller-supplied angle table: per call (several calls may be in flight on different streams)
@@ -1155,60 +1156,92 @@ struct Engine::CoreWs {
     }
 };
 
-size_t Engine::denoise_core_bytes(int B, int N) const {
-    Bump b(nullptr);
-    CoreWs w;
-    w.plan(b, B, N);
-    return b.off + 256;
+namespace {
+struct SampleWs {
+    float *ts, *xt, *v, *x, *nz, *xt3, *v3;
+    void plan(Bump& b, int B, int N, int n_steps, int cfg) {
+        const size_t e = (size_t)B * N * kLatent;
+        ts = b.take<float>(n_steps);
+        xt = b.take<float>(e);
+        v = b.take<float>(e);
+        x = b.take<float>(e);
+        nz = b.take<float>(e);
+        xt3 = b.take<float>(cfg ? 3 * e : 1);
+        v3 = b.take<float>(cfg ? 3 * e : 1);
+    }
+};
+}  // namespace
+// THE workspace of a DiT operator, three parts: sampler buffers (n_steps > 0: sample) + modulation chain, table and LN-fold tables |
+// core | cross-KV images of all 12 layers (Kc, Vc^T, each hi + lo).  B: the caller's rows, the evaluations run on 3B rows with cfg.
+// A part is sized like every workspace of this file, its last offset + 256 bytes of slack (the cross part: + 256 per image as well); the
+// core starts on the first 256-byte boundary behind the tables, the cross images behind the core and its slack.  plan() on a null base
+// sizes (dit_ws_bytes), the same plan() on the workspace carves.
+struct Engine::DitWs {
+    SampleWs s;
+    ModWs m;
+    CoreWs core;
+    CrossImg cross;
+    size_t plan(void* base, int B, int N, int R, int P, int mod_rows, bool fold, int n_steps, int cfg) {
+        auto behind = [](const Bump& b, size_t slack) { return reinterpret_cast<char*>((reinterpret_cast<uintptr_t>(b.p) + b.off + slack + 255) & ~uintptr_t(255)); };
+        Bump tb(base);
+        if (n_steps > 0) s.plan(tb, B, N, n_steps, cfg);
+        m.plan(tb, mod_rows, fold);
+        const int Bd = cfg ? 3 * B : B;
+        Bump cb(behind(tb, 0));
+        core.plan(cb, Bd, N);
+        cross.Rp = pad8(R > 0 ? R : 0);
+        cross.Cp = cross.Rp + pad8(P > 0 ? P : 0);
+        const size_t n = (size_t)kBlocks * Bd * kHeads * cross.Cp * 128;
+        Bump xb(behind(cb, 256));
+        cross.kc = xb.take<bf16_t>(n); cross.kc_lo = xb.take<bf16_t>(n);
+        cross.vtc = xb.take<bf16_t>(n); cross.vtc_lo = xb.take<bf16_t>(n);
+        return (tb.off + 256) + (cb.off + 256) + (4 * (n * sizeof(bf16_t) + 256) + 256);
+    }
+};
+size_t Engine::dit_ws_bytes(int B, int N, int R, int P, int mod_rows, bool fold, int n_steps, int cfg) const {
+    DitWs w;
+    return w.plan(nullptr, B, N, R, P, mod_rows, fold, n_steps, cfg);
+}
+
+// What dit_blocks reads besides the residual stream, for the operators and the test hook alike.  rope: a caller-supplied angle table
+// (reference operator input, infer/onnx.py:42-47,122), its cos / sin go into the workspace.
+int Engine::dit_run(hipStream_t st, const CoreWs& w, const uint8_t* mask, const ModRow& row, const Cond& cond, const float* rope, int B,
+                    int N, bool fold, bool unsplit, DitRun& d) {
+    if (rope) HIPC(launch_rope_cossin(rope, w.rope_c, w.rope_s, N * 64, st));
+    d.mask = mask; d.row = row; d.cond = &cond;
+    d.rc = rope ? w.rope_c : rope_dit_cos_;
+    d.rs = rope ? w.rope_s : rope_dit_sin_;
+    d.frow = fold ? row.ftab + (long)row.row0 * 2 * kFoldNF : nullptr;   // [0]: W shift, [1]: W (1 + scale)
+    d.ks_out = unsplit ? 1 : ksplit_out_;
+    d.ks_ff2 = unsplit ? 1 : ksplit_ff2_;
+    d.B = B; d.N = N;
+    return 0;
 }
 
 // ---------------------------------------------------------------------------------------------
 // D0: one denoiser evaluation given a ready modulation table (model.py:97-100, dit.py:316-327)
 // ---------------------------------------------------------------------------------------------
-int Engine::denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, const float* mod, int mod_row0,
-                         int mod_rstride, const float* k_ref, const float* v_ref, const uint8_t* ref_mask,
-                         const float* k_text, const float* v_text, const uint8_t* ph_mask, const float* rope, int B,
-                         int N, int R, int P, float* velocity, char* wsp, const CrossImg& ci, const float* ftab) {
+int Engine::denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, const ModRow& row, const Cond& cond, const float* rope,
+                         int B, int N, float* velocity, const CoreWs& w, Call& call) {
     ProfTag ptag("dit");
-    Bump bump(wsp);
-    CoreWs w;
-    w.plan(bump, B, N);
     const int M = B * N;
-    // zero regions that no kernel of this call writes (pad frames of the conv image, pad columns of the FF hidden, pad key
-    // columns of V^T): once per workspace use — the sampler's later steps find them as the first step left them
-    const bool init_ws = !ws_ready_;
-    ws_ready_ = ws_keep_;
-    if (dit_embed(st, w, x_t, mask, B, N, init_ws)) return 1;
-    DitRun d;
-    d.rc = rope_dit_cos_;
-    d.rs = rope_dit_sin_;
-    if (rope) {  // caller-supplied angle table (reference operator input, infer/onnx.py:42-47,122)
-        HIPC(launch_rope_cossin(rope, w.rope_c, w.rope_s, N * 64, st));
-        d.rc = w.rope_c;
-        d.rs = w.rope_s;
-    }
-    if (join_pending_) {   // the modulation table is being computed on the side stream (sample)
-        HIPC(hipStreamWaitEvent(st, ev_join_, 0));
-        join_pending_ = false;
-    }
+    if (dit_embed(st, w, x_t, mask, B, N, !call.ws_zeroed)) return 1;
     // LN-fold (gemm.hpp LnFoldIn): inside the fused sampler — one modulation row for the whole batch, tables from modulation() —
     // the AdaLN between two block GEMMs lives in their epilogues (ftab: the tables sample() planned by the same predicate)
-    const bool fold = ftab && mod_rstride == 0 && dit_fold_on(M);
+    const bool fold = row.ftab && row.rstride == 0 && dit_fold_on(M);
     // split-K exists to fill the chip at M = 600 (150 tiles of 64x64 for N = 960); the 3B-row CFG batches of the teacher
     // sampler (M = 1800: 435 tiles) fill it without, and the fused epilogue is cheaper than partials + reduce (495 -> 454 ms)
     // ... and so do several batches in flight (throughput tuning): there the unsplit GEMM + a separate AdaLN costs 2.3x fewer
     // workgroup-microseconds than three K slices + reduce, and that is what counts when other streams want the CUs
     static const bool splitk_tp = lab_env("SMTTS_SPLITK_TP") && atoi(lab_env("SMTTS_SPLITK_TP")) != 0;   // (A/B only)
     const bool unsplit = M > 1024 || (tuning_ == TUNE_THROUGHPUT && !splitk_tp);
-    d.mask = mask; d.mod = mod; d.mod_row0 = mod_row0; d.mod_rstride = mod_rstride;
-    d.k_ref = k_ref; d.v_ref = v_ref; d.ref_mask = ref_mask; d.k_text = k_text; d.v_text = v_text; d.ph_mask = ph_mask;
-    d.ci = &ci;
-    d.frow = fold ? ftab + (long)mod_row0 * 2 * kFoldNF : nullptr;   // [0]: W shift, [1]: W (1 + scale)
-    d.ks_out = unsplit ? 1 : ksplit_out_;
-    d.ks_ff2 = unsplit ? 1 : ksplit_ff2_;
-    d.B = B; d.N = N; d.R = R; d.P = P;
-    d.init_ws = init_ws;
-    if (dit_blocks(st, w, d, 0, kBlocks)) return 1;
+    DitRun d;
+    if (dit_run(st, w, mask, row, cond, rope, B, N, fold, unsplit, d)) return 1;
+    HIPC(call.join());   // the modulation table may be on its way on the side stream (sample)
+    if (dit_blocks(st, w, d, 0, kBlocks, call)) return 1;
+    // the regions no kernel of this call writes (pad frames of the conv image, pad columns of the FF hidden, pad key columns of V^T)
+    // are zeroed now: the sampler's later steps find them as the first step left them
+    call.ws_zeroed = true;
     return dit_head(st, w, M, velocity);
 }
 
@@ -1251,50 +1284,44 @@ int Engine::dit_embed(hipStream_t st, const CoreWs& w, const float* x_t, const u
 }
 
 // D5-D8: DiT blocks [l0, l1) on the residual stream w.x (dit.py:189-212, 95-135)
-int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0, int l1) {
-    const int B = d.B, N = d.N, R = d.R, P = d.P, M = B * N;
-    const uint8_t* const mask = d.mask;
-    const uint8_t *const ref_mask = d.ref_mask, *const ph_mask = d.ph_mask;
-    const float *const k_ref = d.k_ref, *const v_ref = d.v_ref, *const k_text = d.k_text, *const v_text = d.v_text;
-    const float* const mod = d.mod;
-    const int mod_row0 = d.mod_row0, mod_rstride = d.mod_rstride;
-    const CrossImg& ci = *d.ci;
+int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0, int l1, Call& call) {
+    const int B = d.B, N = d.N, M = B * N;
+    const Cond& c = *d.cond;
+    const CrossImg& ci = c.img;
+    const bool init_ws = !call.ws_zeroed;
+    AlignTap& tap = call.tap;
     const RowMap rh = rowmap_plain(kHidden);
     const int pb = prec_[SITE_DIT_BLOCK], pc = prec_[SITE_COND];
     unsigned* const sb = satp(SITE_DIT_BLOCK);
     const SplitBuf yb = w.y.as(pb, sb), ob = w.o.as(pb, sb), ffh = w.ffh.as(pb, sb);
     if (!(attn_img_ && attn_epi_) && ensure_qkvg_unpadded()) return 1;
     // zero the padded tail columns [2400, 2432) of the FF hidden once per workspace use
-    if (d.init_ws) {
+    if (init_ws) {
         HIPC(hipMemsetAsync(w.ffh.hi, 0, (size_t)M * kFFp * 2, st));
         if (pb == PREC_BF16X3) HIPC(hipMemsetAsync(w.ffh.lo, 0, (size_t)M * kFFp * 2, st));
     }
-    const float* const rc = d.rc;
-    const float* const rs = d.rs;
     // The AdaLN in front of each GEMM is fused into the kernel that produced the residual stream it normalises
     // (split-K reduction + gated residual + LayerNorm-modulate in one pass); only the first one of the range runs alone.
     // LN-fold: the first AdaLN (here) and the final one (velocity head, SITE_COND precision) keep their ln_modulate, the first one
     // also writes the row means the producers shift by
     const bool fold = d.frow != nullptr;
     float* const lnc = fold && LN_FOLD_SHIFT ? w.lnc : nullptr;
-    HIPC(launch_ln_modulate(w.x, nullptr, yb.hi, yb.lo, M, kHidden, 1e-6f, mod + (long)l0 * kModPerBlock + 0 * kHidden,
-                            mod + (long)l0 * kModPerBlock + 1 * kHidden, kModLd, mod_row0, mod_rstride, N, st, lnc));
-    const int ks_out = d.ks_out, ks_ff2 = d.ks_ff2;
-    const float* const mrow = mod + (long)mod_row0 * kModLd;            // this step's modulation row (fold path only)
-    const float* const frow = d.frow;
+    HIPC(launch_ln_modulate(w.x, nullptr, yb.hi, yb.lo, M, kHidden, 1e-6f, d.row.mod + (long)l0 * kModPerBlock + 0 * kHidden,
+                            d.row.mod + (long)l0 * kModPerBlock + 1 * kHidden, kModLd, d.row.row0, d.row.rstride, N, st, lnc));
+    const float* const mrow = d.row.mod + (long)d.row.row0 * kModLd;    // this step's modulation row (fold path only)
     auto fold_in = [&](int l, int site) {
         LnFoldIn f;
         f.part = w.lnpart; f.NP = kLnGroups; f.inv_c = 1.0f / kHidden; f.eps = 1e-6f;
         const long off = (long)l * kFoldPerBlock + (site ? 4L * kHeads * 128 : 0);
-        f.wsh = frow + off;
-        f.wc = frow + kFoldNF + off;
+        f.wsh = d.frow + off;
+        f.wc = d.frow + kFoldNF + off;
         f.cshift = lnc;
         f.nh = kFF;
         return f;
     };
     for (int l = l0; l < l1; ++l) {
         const DitBlockW& b = blocks_[l];
-        const float* m = mod + (long)l * kModPerBlock;
+        const float* m = d.row.mod + (long)l * kModPerBlock;
         // D5 AdaLN-Zero (dit.py:19-25) already in w.y; D6 joint attention (dit.py:95-135)
         const bool epi = attn_img_ && attn_epi_;   // the GEMM's own epilogue writes the attention operands
         if (!epi)
@@ -1304,22 +1331,22 @@ int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0,
         a.q = w.qkvg; a.k = w.qkvg + kHidden; a.v = w.qkvg + 2 * kHidden; a.gate = w.qkvg + 3 * kHidden;
         a.bs = (long)N * 4 * kHidden; a.rs = 4 * kHidden;
         a.qw = b.qn; a.kw = b.kn; a.eps = 1e-6f;
-        a.rope_cos = rc; a.rope_sin = rs; a.rot_dim = 64;
-        const long lr = (long)l * B * kHeads * R * kDh, lp = (long)l * B * kHeads * P * kDh;
-        a.k_ref = R > 0 ? k_ref + lr : nullptr; a.v_ref = R > 0 ? v_ref + lr : nullptr; a.R = R;
-        a.k_text = P > 0 ? k_text + lp : nullptr; a.v_text = P > 0 ? v_text + lp : nullptr; a.P = P;
-        a.mask_self = mask; a.mask_ref = ref_mask; a.mask_text = ph_mask;
+        a.rope_cos = d.rc; a.rope_sin = d.rs; a.rot_dim = 64;
+        const long lr = (long)l * B * kHeads * c.R * kDh, lp = (long)l * B * kHeads * c.P * kDh;
+        a.k_ref = c.R > 0 ? c.k_ref + lr : nullptr; a.v_ref = c.R > 0 ? c.v_ref + lr : nullptr; a.R = c.R;
+        a.k_text = c.P > 0 ? c.k_text + lp : nullptr; a.v_text = c.P > 0 ? c.v_text + lp : nullptr; a.P = c.P;
+        a.mask_self = d.mask; a.mask_ref = c.ref_mask; a.mask_text = c.ph_mask;
         a.out = nullptr; a.out_hi = ob.hi; a.out_lo = ob.lo; a.obs = (long)N * kHidden; a.ors = kHidden;
         a.B = B; a.N = N; a.H = kHeads; a.dh = kDh;
         if (attn_img_) {
             const int pa = prec_[SITE_ATTN], Np = pad8(N);
             QkvPackArgs pk{};
             pk.qkvg = w.qkvg; pk.qw = b.qn; pk.kw = b.kn; pk.eps = 1e-6f; pk.q_scale = 1.0f / sqrtf((float)kDh);
-            pk.rope_cos = rc; pk.rope_sin = rs; pk.rot_dim = 64; pk.prec = pa;
+            pk.rope_cos = d.rc; pk.rope_sin = d.rs; pk.rot_dim = 64; pk.prec = pa;
             pk.q = w.qi.hi; pk.q_lo = img_lo(pa, w.qi.lo); pk.k = w.ki.hi; pk.k_lo = img_lo(pa, w.ki.lo); pk.vt = w.vti.hi; pk.vt_lo = img_lo(pa, w.vti.lo);
             pk.g = w.gi.hi; pk.g_lo = img_lo(pa, w.gi.lo);
             pk.B = B; pk.N = N; pk.H = kHeads; pk.dh = kDh; pk.dhp = 128; pk.Np = Np;
-            if (l == l0 && Np != N && d.init_ws) {   // pad key columns of V^T (the producer only writes n < N)
+            if (l == l0 && Np != N && init_ws) {   // pad key columns of V^T (the producer only writes n < N)
                 HIPC(hipMemsetAsync(w.vti.hi, 0, w.vt_elems * 2, st));
                 if (pa == PREC_BF16X3) HIPC(hipMemsetAsync(w.vti.lo, 0, w.vt_elems * 2, st));
             }
@@ -1340,16 +1367,16 @@ int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0,
                 ai.kc = ci.kc + lc; ai.vtc = ci.vtc + lc;
                 if (pa == PREC_BF16X3) { ai.kc_lo = ci.kc_lo + lc; ai.vtc_lo = ci.vtc_lo + lc; }
             }
-            ai.mask_self = mask; ai.mask_ref = ref_mask; ai.mask_text = ph_mask;
+            ai.mask_self = d.mask; ai.mask_ref = c.ref_mask; ai.mask_text = c.ph_mask;
             ai.out_hi = ob.hi; ai.out_lo = ob.lo; ai.ors = kHidden;
-            ai.B = B; ai.N = N; ai.H = kHeads; ai.dh = kDh; ai.Np = Np; ai.R = R; ai.P = P; ai.Rp = ci.Rp; ai.Cp = ci.Cp;
+            ai.B = B; ai.N = N; ai.H = kHeads; ai.dh = kDh; ai.Np = Np; ai.R = c.R; ai.P = c.P; ai.Rp = ci.Rp; ai.Cp = ci.Cp;
             HIPC(launch_attention_img(ai, st));
-            if (tap_.mass && tap_.step_on && ((tap_.layers >> l) & 1u)) {   // word timings: the text probabilities of this (step, layer)
-                HIPC(launch_attn_text_mass(ai, tap_.mass, tap_.rows, tap_.heads, tap_.scale, tap_.first ? 1 : 0, st));
-                tap_.first = false;
+            if (tap.mass && tap.step_on && ((tap.layers >> l) & 1u)) {   // word timings: the text probabilities of this (step, layer)
+                HIPC(launch_attn_text_mass(ai, tap.mass, tap.rows, tap.heads, tap.scale, tap.first ? 1 : 0, st));
+                tap.first = false;
             }
         } else {
-            if (tap_.mass) return fail("the text-attention tap reads the attention operand images: not available with the image path switched off");
+            if (tap.mass) return fail("the text-attention tap reads the attention operand images: not available with the image path switched off");
 #ifdef SMTTS_TEST_KERNELS   // the fp32 VALU reference attention (attention.hip): test builds only
             a.prenormed = 1;
             HIPC(launch_qk_prep(a, st));
@@ -1359,18 +1386,18 @@ int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0,
 #endif
         }
         // to_out + mask + gated residual (dit.py:117-118,198), then the MLP AdaLN (dit.py:199)
-        EpiResid<0> r1{w.x, rh, nullptr, m + 2 * kHidden, kModLd, mod_row0, mod_rstride, N, mask};
+        EpiResid<0> r1{w.x, rh, nullptr, m + 2 * kHidden, kModLd, d.row.row0, d.row.rstride, N, d.mask};
         NextLN ln1{m + 3 * kHidden, m + 4 * kHidden, yb.hi, yb.lo};
         const float* const mr = mrow + (long)l * kModPerBlock;
         if (fold) {
-            EpiResidLN e1{w.x, rh, nullptr, mr + 2 * kHidden, mask, mr + 4 * kHidden, yb.hi, yb.lo, kHidden, w.lnpart, kLnGroups, 0, lnc};
+            EpiResidLN e1{w.x, rh, nullptr, mr + 2 * kHidden, d.mask, mr + 4 * kHidden, yb.hi, yb.lo, kHidden, w.lnpart, kLnGroups, 0, lnc};
             HIPC(gemm3_resid_ln(ops3(w.o, rh, b.out, M, pb), e1, pb, st, tune_));
-        } else if (ks_out > 1) {
-            HIPC(gemm3_resid_splitk(ops3(w.o, rh, b.out, M, pb), r1, w.part, ks_out, pb, st, tune_, ln1));
+        } else if (d.ks_out > 1) {
+            HIPC(gemm3_resid_splitk(ops3(w.o, rh, b.out, M, pb), r1, w.part, d.ks_out, pb, st, tune_, ln1));
         } else {
             HIPC(gemm3_resid(ops3(w.o, rh, b.out, M, pb), 1, r1, pb, st, tune_));
-            HIPC(launch_ln_modulate(w.x, nullptr, ln1.yhi, ln1.ylo, M, kHidden, 1e-6f, ln1.shift, ln1.scale, kModLd, mod_row0,
-                                    mod_rstride, N, st));
+            HIPC(launch_ln_modulate(w.x, nullptr, ln1.yhi, ln1.ylo, M, kHidden, 1e-6f, ln1.shift, ln1.scale, kModLd, d.row.row0,
+                                    d.row.rstride, N, st));
         }
         // D7 feed-forward (dit.py:199-201)
         EpiSwiGLU sw{nullptr, kFFp, b.b1, b.b3, ffh.hi, ffh.lo};
@@ -1378,7 +1405,7 @@ int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0,
         HIPC(gemm3_swiglu(ops3(w.y, rh, b.ff13, M, pb), sw, pb, st, tune_));
         // w2 + gated residual, then the next block's attention AdaLN — or D8's final AdaLN (chunk order scale, shift:
         // dit.py:37) after the last block
-        EpiResid<0> r2{w.x, rh, b.b2, m + 5 * kHidden, kModLd, mod_row0, mod_rstride, N, nullptr};
+        EpiResid<0> r2{w.x, rh, b.b2, m + 5 * kHidden, kModLd, d.row.row0, d.row.rstride, N, nullptr};
         const float* mn = m + kModPerBlock;  // next block's modulation (or the final norm's [scale | shift])
         const SplitBuf yv = w.y.as(pc, satp(SITE_COND));  // the final AdaLN feeds the velocity head (SITE_COND)
         NextLN ln2 = l + 1 < kBlocks ? NextLN{mn + 0 * kHidden, mn + 1 * kHidden, yb.hi, yb.lo}
@@ -1386,12 +1413,12 @@ int Engine::dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0,
         if (fold && l + 1 < kBlocks) {
             EpiResidLN e2{w.x, rh, b.b2, mr + 5 * kHidden, nullptr, mr + kModPerBlock + kHidden, yb.hi, yb.lo, kHidden, w.lnpart, kLnGroups, 0, lnc};
             HIPC(gemm3_resid_ln(ops3(w.ffh, rowmap_plain(kFFp), b.ff2, M, pb), e2, pb, st, tune_));
-        } else if (ks_ff2 > 1) {
-            HIPC(gemm3_resid_splitk(ops3(w.ffh, rowmap_plain(kFFp), b.ff2, M, pb), r2, w.part, ks_ff2, pb, st, tune_, ln2));
+        } else if (d.ks_ff2 > 1) {
+            HIPC(gemm3_resid_splitk(ops3(w.ffh, rowmap_plain(kFFp), b.ff2, M, pb), r2, w.part, d.ks_ff2, pb, st, tune_, ln2));
         } else {
             HIPC(gemm3_resid(ops3(w.ffh, rowmap_plain(kFFp), b.ff2, M, pb), 1, r2, pb, st, tune_));
-            HIPC(launch_ln_modulate(w.x, nullptr, ln2.yhi, ln2.ylo, M, kHidden, 1e-6f, ln2.shift, ln2.scale, kModLd, mod_row0,
-                                    mod_rstride, N, st));
+            HIPC(launch_ln_modulate(w.x, nullptr, ln2.yhi, ln2.ylo, M, kHidden, 1e-6f, ln2.shift, ln2.scale, kModLd, d.row.row0,
+                                    d.row.rstride, N, st));
         }
     }
     return 0;
@@ -1429,37 +1456,22 @@ int Engine::ensure_qkvg_unpadded() {
 
 // Cross-KV cache of all 12 layers in the attention kernel's operand format: built once per sampler call (or per denoise_step
 // call) from the fp32 rank-5 tensors the C ABI hands over — 25 MB of traffic against 4 x 12 attention launches that then DMA it.
-size_t Engine::cross_img_bytes(int B, int R, int P) const {
-    const size_t Cp = (size_t)pad8(R) + pad8(P);
-    return 4 * ((size_t)kBlocks * B * kHeads * Cp * 128 * 2 + 256) + 256;   // Kc, Vc^T, each hi + lo
-}
-int Engine::pack_cross(hipStream_t st, const float* k_ref, const float* v_ref, const float* k_text, const float* v_text, int B,
-                       int R, int P, char* ws, CrossImg& ci) {
-    ci = CrossImg();
-    if (!attn_img_ || (R <= 0 && P <= 0)) return 0;
+int Engine::pack_cross(hipStream_t st, Cond& c, int B, const CrossImg& carved) {
+    c.img = CrossImg();
+    if (!attn_img_ || (c.R <= 0 && c.P <= 0)) return 0;
+    c.img = carved;
     const int pa = prec_[SITE_ATTN];
-    Bump bump(ws);
-    ci.Rp = pad8(R > 0 ? R : 0);
-    ci.Cp = ci.Rp + pad8(P > 0 ? P : 0);
-    const size_t n = (size_t)kBlocks * B * kHeads * ci.Cp * 128;
-    ci.kc = bump.take<bf16_t>(n); ci.kc_lo = bump.take<bf16_t>(n);
-    ci.vtc = bump.take<bf16_t>(n); ci.vtc_lo = bump.take<bf16_t>(n);
     CrossPackArgs p{};
-    p.k_ref = k_ref; p.v_ref = v_ref; p.k_text = k_text; p.v_text = v_text;
-    p.kc = ci.kc; p.kc_lo = img_lo(pa, ci.kc_lo); p.vtc = ci.vtc; p.vtc_lo = img_lo(pa, ci.vtc_lo);
+    p.k_ref = c.k_ref; p.v_ref = c.v_ref; p.k_text = c.k_text; p.v_text = c.v_text;
+    p.kc = carved.kc; p.kc_lo = img_lo(pa, carved.kc_lo); p.vtc = carved.vtc; p.vtc_lo = img_lo(pa, carved.vtc_lo);
     p.prec = pa; p.L = kBlocks; p.B = B; p.H = kHeads; p.dh = kDh; p.dhp = 128;
-    p.R = R > 0 ? R : 0; p.P = P > 0 ? P : 0; p.Rp = ci.Rp; p.Cp = ci.Cp;
+    p.R = c.R > 0 ? c.R : 0; p.P = c.P > 0 ? c.P : 0; p.Rp = carved.Rp; p.Cp = carved.Cp;
     ProfTag ptag("dit");
     HIPC(launch_cross_pack(p, st));
     return 0;
 }
 
-size_t Engine::denoise_ws_bytes(int B, int N, int R, int P, int rows) const {
-    Bump b(nullptr);
-    ModWs m;
-    m.plan(b, rows);
-    return b.off + 256 + denoise_core_bytes(B, N) + cross_img_bytes(B, R, P);
-}
+size_t Engine::denoise_ws_bytes(int B, int N, int R, int P, int rows) const { return dit_ws_bytes(B, N, R, P, rows, false, 0, 0); }
 
 int Engine::denoise_step(hipStream_t st, const float* x_t, const uint8_t* mask, const float* t, const float* k_ref,
                          const float* v_ref, const uint8_t* ref_mask, const float* k_text, const float* v_text,
@@ -1470,15 +1482,13 @@ int Engine::denoise_step(hipStream_t st, const float* x_t, const uint8_t* mask, 
     if (ws_bytes < denoise_ws_bytes(B, N, R, P, B)) return fail("denoise_step: workspace too small");
     if (ws_misaligned(ws)) return fail("denoise_step: workspace must be 256-byte aligned");
     HIPC(hipSetDevice(device_));
-    Bump bump(ws);
-    ModWs m;
-    m.plan(bump, B);
-    if (modulation(st, t, B, m.sinb, m.t1, m.temb, m.e1, m.semb, m.mod)) return 1;
-    char* core = static_cast<char*>(ws) + ((bump.off + 255) & ~size_t(255));
-    CrossImg ci;
-    if (pack_cross(st, k_ref, v_ref, k_text, v_text, B, R, P, core + ((denoise_core_bytes(B, N) + 255) & ~size_t(255)), ci)) return 1;
-    return denoise_core(st, x_t, mask, m.mod, 0, 1, k_ref, v_ref, ref_mask, k_text, v_text, ph_mask, rope, B, N, R, P,
-                        velocity, core, ci);
+    DitWs w;
+    w.plan(ws, B, N, R, P, B, false, 0, 0);
+    if (modulation(st, t, B, w.m)) return 1;
+    Cond cond{k_ref, v_ref, k_text, v_text, ref_mask, ph_mask, R, P, {}};
+    if (pack_cross(st, cond, B, w.cross)) return 1;
+    Call call(st);
+    return denoise_core(st, x_t, mask, ModRow{w.m.mod, 0, 1, nullptr}, cond, rope, B, N, velocity, w.core, call);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1504,36 +1514,15 @@ static float linspace10(int i, int n) {
     return (float)(1.0 + step * (double)i);
 }
 
-namespace {
-struct SampleWs {
-    float *ts, *xt, *v, *x, *nz, *xt3, *v3;
-    void plan(Bump& b, int B, int N, int n_steps, int cfg) {
-        const size_t e = (size_t)B * N * kLatent;
-        ts = b.take<float>(n_steps);
-        xt = b.take<float>(e);
-        v = b.take<float>(e);
-        x = b.take<float>(e);
-        nz = b.take<float>(e);
-        xt3 = b.take<float>(cfg ? 3 * e : 1);
-        v3 = b.take<float>(cfg ? 3 * e : 1);
-    }
-};
-}  // namespace
-
 size_t Engine::sample_ws_bytes(int B, int N, int R, int P, int n_steps, int cfg) const {
-    Bump b(nullptr);
-    SampleWs s;
-    s.plan(b, B, N, n_steps, cfg);
-    ModWs m;
-    m.plan(b, n_steps, dit_fold_on((long)(cfg ? 3 * B : B) * N));
-    return b.off + 256 + denoise_core_bytes(cfg ? 3 * B : B, N) + cross_img_bytes(cfg ? 3 * B : B, R, P);
+    return dit_ws_bytes(B, N, R, P, n_steps, dit_fold_on((long)(cfg ? 3 * B : B) * N), n_steps, cfg);
 }
 
 int Engine::sample_pinned(hipStream_t st, int mode, int n_steps, int cfg, float s_text, float s_spk, const uint8_t* mask,
                           const float* k_ref, const float* v_ref, const uint8_t* ref_mask, const float* k_text,
                           const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P, const float* noise,
-                          uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes, const uint8_t* tap_steps,
-                          unsigned tap_layers, unsigned tap_heads, float* text_mass, const float* x_pin, const uint8_t* pin,
+                          uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes, const uint8_t* sel_steps,
+                          unsigned sel_layers, unsigned sel_heads, float* text_mass, const float* x_pin, const uint8_t* pin,
                           int start_step) {
     if (!dit_ready_) return fail("sample: DiT weights not finalized");
     if (n_steps < 1) return fail("sample: n_steps must be >= 1");
@@ -1552,34 +1541,32 @@ int Engine::sample_pinned(hipStream_t st, int mode, int n_steps, int cfg, float 
             return fail("sample_pinned: x_pin, noise and the workspace must be 16-byte aligned");
     }
     // the text-attention tap (align.hip): validated before anything is enqueued; off (text_mass == null) nothing below differs from sample()
-    struct TapGuard { Engine* e; ~TapGuard() { e->tap_ = AlignTap(); } } tap_guard{this};
-    std::vector<uint8_t> tap_on(n_steps, 0);
+    Call call(st);
+    AlignTap& tap = call.tap;
+    std::vector<uint8_t> step_sel(n_steps, 0);
     if (text_mass) {
         if (!attn_img_) return fail("sample_align: the text-attention tap reads the attention operand images: not available with the image path switched off");
         if (B <= 0 || N <= 0 || P <= 0) return fail("sample_align: the tap needs frames and text keys (B, N, P > 0)");
-        tap_layers &= (1u << kBlocks) - 1u;
-        tap_heads &= (1u << kHeads) - 1u;
+        sel_layers &= (1u << kBlocks) - 1u;
+        sel_heads &= (1u << kHeads) - 1u;
         int ns = 0, nl = 0, nh = 0;
-        for (int i = start_step; i < n_steps; ++i) ns += (tap_on[i] = tap_steps ? (tap_steps[i] != 0) : (i + 1 == n_steps));
-        for (int l = 0; l < kBlocks; ++l) nl += (tap_layers >> l) & 1u;
-        for (int h = 0; h < kHeads; ++h) nh += (tap_heads >> h) & 1u;
+        for (int i = start_step; i < n_steps; ++i) ns += (step_sel[i] = sel_steps ? (sel_steps[i] != 0) : (i + 1 == n_steps));
+        for (int l = 0; l < kBlocks; ++l) nl += (sel_layers >> l) & 1u;
+        for (int h = 0; h < kHeads; ++h) nh += (sel_heads >> h) & 1u;
         if (!ns || !nl || !nh) return fail("sample_align: the tap selects no (step, layer, head): 12 layers (bits 0..11), 8 heads (bits 0..7)");
         if (sizeof(float) * ((size_t)4 * (128 + pad8(N) + pad8(R > 0 ? R : 0) + pad8(P) + P) + 8) > 64 * 1024)
             return fail("sample_align: N + R + 2 P too large for the tap kernel's LDS tile");
-        tap_.mass = text_mass; tap_.layers = tap_layers; tap_.heads = tap_heads; tap_.rows = B;
-        tap_.scale = 1.0f / (float)(ns * nl * nh);
-        tap_.first = true; tap_.step_on = false;
+        tap.mass = text_mass; tap.layers = sel_layers; tap.heads = sel_heads; tap.rows = B;
+        tap.scale = 1.0f / (float)(ns * nl * nh);
     }
     HIPC(hipSetDevice(device_));
-    Bump bump(ws);
-    SampleWs s;
-    s.plan(bump, B, N, n_steps, cfg);
-    ModWs m;
+    const int Bd = cfg ? 3 * B : B;
+    DitWs w;
     // (the fold replaces split-K partials + reduce; the 3B-row CFG batches of the teacher run unsplit + ln_modulate already, and there
     // the table kernel — every block weight once per four steps — and the heavier epilogue cost more than the norm launches: 239.0 vs
     // 240.6 ms per 128-step batch, profiles/r06l_ab_teacher_fold.txt)
-    m.plan(bump, n_steps, dit_fold_on((long)(cfg ? 3 * B : B) * N));
-    char* core = static_cast<char*>(ws) + ((bump.off + 255) & ~size_t(255));
+    w.plan(ws, B, N, R, P, n_steps, dit_fold_on((long)Bd * N), n_steps, cfg);
+    const SampleWs& s = w.s;
     const long e = (long)B * N * kLatent;
 
     std::vector<float> ts(n_steps), al(n_steps), sg(n_steps);
@@ -1594,41 +1581,32 @@ int Engine::sample_pinned(hipStream_t st, int mode, int n_steps, int cfg, float 
     // t is shared by the whole batch -> every AdaLN vector of every step in one pass (SURVEY §7 hard part 3)
     // The table does not depend on the batch's data, only the first AdaLN needs it: in latency tuning it is computed on the
     // engine's side stream while the main stream packs the cross-KV images and embeds the first step's input (0.2 ms of tiny-M
-    // GEMMs that fill a fraction of the chip); the main stream joins right before its first ln_modulate (denoise_core).
-    // (an early return between the fork and the first denoise_core must not leave the flag set for the next call, nor the side
-    // stream's writes into this workspace unordered against whatever the caller does next on `st`: ADVICE r3)
-    struct JoinGuard {
-        Engine* e; hipStream_t st;
-        ~JoinGuard() { if (e->join_pending_) { (void)hipStreamWaitEvent(st, e->ev_join_, 0); e->join_pending_ = false; } }
-    } join_guard{this, st};
+    // GEMMs that fill a fraction of the chip); the main stream joins right before its first ln_modulate (denoise_core) — or, on an
+    // early return between the fork and that point, when the call record goes (Call::~Call: ADVICE r3).
     if (dual_stream_ && !prof_on_) {
-        if (ensure_aux(st)) return 1;
-        HIPC(hipEventRecord(ev_fork_, st));
-        HIPC(hipStreamWaitEvent(aux_, ev_fork_, 0));
-        const int mod_rc = modulation(aux_, s.ts, n_steps, m.sinb, m.t1, m.temb, m.e1, m.semb, m.mod, m.ftab);
-        HIPC(hipEventRecord(ev_join_, aux_));   // recorded even when the chain failed half-way: the guard joins what was enqueued
-        join_pending_ = true;
+        if (!(call.side = side_set(st))) return 1;
+        HIPC(hipEventRecord(call.side->fork, st));
+        HIPC(hipStreamWaitEvent(call.side->stream, call.side->fork, 0));
+        const int mod_rc = modulation(call.side->stream, s.ts, n_steps, w.m);
+        HIPC(hipEventRecord(call.side->join, call.side->stream));   // recorded even when the chain failed half-way: what was enqueued is joined
+        call.join_owed = true;
         if (mod_rc) return 1;
-    } else if (modulation(st, s.ts, n_steps, m.sinb, m.t1, m.temb, m.e1, m.semb, m.mod, m.ftab)) {
+    } else if (modulation(st, s.ts, n_steps, w.m)) {
         return 1;
     }
 
-    const int Bd = cfg ? 3 * B : B;
-    struct KeepWs { Engine* e; explicit KeepWs(Engine* e_) : e(e_) { e->ws_ready_ = false; e->ws_keep_ = true; } ~KeepWs() { e->ws_ready_ = e->ws_keep_ = false; } } keep_ws(this);
-    CrossImg ci;   // the cross-KV cache in the attention kernel's operand format: once per call, read by every step
-    if (pack_cross(st, k_ref, v_ref, k_text, v_text, Bd, R, P, core + ((denoise_core_bytes(Bd, N) + 255) & ~size_t(255)), ci)) return 1;
+    // the cross-KV cache in the attention kernel's operand format: once per call, read by every step
+    Cond cond{k_ref, v_ref, k_text, v_text, ref_mask, ph_mask, R, P, {}};
+    if (pack_cross(st, cond, Bd, w.cross)) return 1;
     // mask for 3B rows when cfg: caller passes mask with B rows; replicate by pointer arithmetic is impossible,
     // so the cfg path expects `mask` to already hold 3B rows (documented in the header).
     auto eval_velocity = [&](int step) -> int {
-        tap_.step_on = tap_.mass && tap_on[step];
-        if (!cfg)
-            return denoise_core(st, s.xt, mask, m.mod, step, 0, k_ref, v_ref, ref_mask, k_text, v_text, ph_mask, nullptr,
-                                B, N, R, P, s.v, core, ci, m.ftab);
+        tap.step_on = tap.mass && step_sel[step];
+        const ModRow row{w.m.mod, step, 0, w.m.ftab};   // one row for the whole batch
+        if (!cfg) return denoise_core(st, s.xt, mask, row, cond, nullptr, B, N, s.v, w.core, call);
         for (int r = 0; r < 3; ++r)
             HIPC(hipMemcpyAsync(s.xt3 + r * e, s.xt, e * sizeof(float), hipMemcpyDeviceToDevice, st));
-        if (denoise_core(st, s.xt3, mask, m.mod, step, 0, k_ref, v_ref, ref_mask, k_text, v_text, ph_mask, nullptr, Bd,
-                         N, R, P, s.v3, core, ci, m.ftab))
-            return 1;
+        if (denoise_core(st, s.xt3, mask, row, cond, nullptr, Bd, N, s.v3, w.core, call)) return 1;
         HIPC(launch_cfg_combine(s.v3, s.v, s_text, s_spk, e, st));
         return 0;
     };
@@ -2151,7 +2129,7 @@ int Engine::test_codec_stage(hipStream_t st, int part, int stage, int what, cons
 }
 
 // DiT / encoder stages through the code of denoise_step / sample / cond_encode (include/smalltts_hip.h smtts_test_dit_stage).  The
-// workspace is planned by the product's own planners (ModWs + CoreWs + the cross images, EncWs) and filled with 0xff first.
+// workspace is planned by the product's own planners (DitWs, EncWs) and filled with 0xff first.
 int Engine::test_dit_stage(hipStream_t st, int net, int what, int l0, int l1, int path, int twice, const void* xin,
                            const uint8_t* mask, int B, int S, const float* t, const float* modin, int mod_rows, int mod_row0,
                            int mod_rstride, const float* k_ref, const float* v_ref, const uint8_t* ref_mask, int R,
@@ -2214,18 +2192,12 @@ int Engine::test_dit_stage(hipStream_t st, int net, int what, int l0, int l1, in
     HIPC(hipSetDevice(device_));
     // workspace: as denoise_step / sample plan it (modulation table + LN-fold tables, core, cross images), or as cond_encode does
     const bool need_mod = dit && (what & (1 | 4));
-    size_t bytes;
-    {
+    size_t bytes = dit ? dit_ws_bytes(B, S, R, P, need_mod ? mod_rows : 1, fold, 0, 0) : 0;
+    if (!dit) {
         Bump b(nullptr);
-        if (dit) {
-            ModWs m;
-            m.plan(b, need_mod ? mod_rows : 1, fold);
-            bytes = ((b.off + 255) & ~size_t(255)) + ((denoise_core_bytes(B, S) + 255) & ~size_t(255)) + cross_img_bytes(B, R, P);
-        } else {
-            EncWs e;
-            e.plan(b, B, S);
-            bytes = b.off + 256;
-        }
+        EncWs e;
+        e.plan(b, B, S);
+        bytes = b.off + 256;
     }
     void* ws = nullptr;
     HIPC(hipMalloc(&ws, bytes));
@@ -2233,18 +2205,17 @@ int Engine::test_dit_stage(hipStream_t st, int net, int what, int l0, int l1, in
     {
         ProfTag ptag(dit ? "dit" : "enc");
         // all-ones bytes: NaN in every operand format; a kernel that read what nobody wrote would turn it into NaN in the output
-        auto run = [&](bool init_ws) -> int {
+        Call call(st);
+        auto run = [&]() -> int {
             Bump bump(ws);
             if (dit) {
-                ModWs m;
-                m.plan(bump, need_mod ? mod_rows : 1, fold);
-                char* core = static_cast<char*>(ws) + ((bump.off + 255) & ~size_t(255));
-                Bump cb(core);
-                CoreWs w;
-                w.plan(cb, B, S);
+                DitWs dw;
+                dw.plan(ws, B, S, R, P, need_mod ? mod_rows : 1, fold, 0, 0);
+                const ModWs& m = dw.m;
+                const CoreWs& w = dw.core;
                 if (need_mod) {
                     if (what & 1) {
-                        if (modulation(st, t, mod_rows, m.sinb, m.t1, m.temb, m.e1, m.semb, m.mod, fold ? m.ftab : nullptr)) return 1;
+                        if (modulation(st, t, mod_rows, m)) return 1;
                     } else {
                         HIPC(hipMemcpyAsync(m.mod, modin, (size_t)mod_rows * kModLd * 4, hipMemcpyDeviceToDevice, st));
                         if (fold && fold_tables(st, m.mod, mod_rows, m.ftab)) return 1;
@@ -2252,31 +2223,16 @@ int Engine::test_dit_stage(hipStream_t st, int net, int what, int l0, int l1, in
                     if (mod_out) HIPC(hipMemcpyAsync(mod_out, m.mod, (size_t)mod_rows * kModLd * 4, hipMemcpyDeviceToDevice, st));
                 }
                 if (what & 2) {
-                    if (dit_embed(st, w, static_cast<const float*>(xin), mask, B, S, init_ws)) return 1;
+                    if (dit_embed(st, w, static_cast<const float*>(xin), mask, B, S, !call.ws_zeroed)) return 1;
                 } else if (what & 4) {
                     HIPC(hipMemcpyAsync(w.x, xin, (size_t)M * kHidden * 4, hipMemcpyDeviceToDevice, st));
                 }
                 if (what & 4) {
-                    CrossImg ci;
-                    if (pack_cross(st, k_ref, v_ref, k_text, v_text, B, R, P, core + ((denoise_core_bytes(B, S) + 255) & ~size_t(255)), ci))
-                        return 1;
+                    Cond cond{k_ref, v_ref, k_text, v_text, ref_mask, ph_mask, R, P, {}};
+                    if (pack_cross(st, cond, B, dw.cross)) return 1;
                     DitRun d;
-                    d.rc = rope_dit_cos_;
-                    d.rs = rope_dit_sin_;
-                    if (rope) {
-                        HIPC(launch_rope_cossin(rope, w.rope_c, w.rope_s, S * 64, st));
-                        d.rc = w.rope_c;
-                        d.rs = w.rope_s;
-                    }
-                    d.mask = mask; d.mod = m.mod; d.mod_row0 = mod_row0; d.mod_rstride = mod_rstride;
-                    d.k_ref = k_ref; d.v_ref = v_ref; d.ref_mask = ref_mask; d.k_text = k_text; d.v_text = v_text; d.ph_mask = ph_mask;
-                    d.ci = &ci;
-                    d.frow = fold ? m.ftab + (long)mod_row0 * 2 * kFoldNF : nullptr;
-                    d.ks_out = ks == 1 ? 1 : ksplit_out_;
-                    d.ks_ff2 = ks == 1 ? 1 : ksplit_ff2_;
-                    d.B = B; d.N = S; d.R = R; d.P = P;
-                    d.init_ws = init_ws;
-                    if (dit_blocks(st, w, d, l0, l1)) return 1;
+                    if (dit_run(st, w, mask, ModRow{m.mod, mod_row0, mod_rstride, m.ftab}, cond, rope, B, S, fold, ks == 1, d)) return 1;
+                    if (dit_blocks(st, w, d, l0, l1, call)) return 1;
                     const int pi = prec_[l1 == kBlocks ? SITE_COND : SITE_DIT_BLOCK];
                     if (img_out) {
                         const SplitBuf y = w.y.as(pi, nullptr);
@@ -2329,9 +2285,10 @@ int Engine::test_dit_stage(hipStream_t st, int net, int what, int l0, int l1, in
             }
             return 0;
         };
-        rc = hipMemsetAsync(ws, 0xff, bytes, st) != hipSuccess ? fail("test_dit_stage: memset") : run(true);
+        rc = hipMemsetAsync(ws, 0xff, bytes, st) != hipSuccess ? fail("test_dit_stage: memset") : run();
         // twice: a second run on the same workspace, as the sampler's later steps find it (its never-written regions are not zeroed again)
-        if (!rc && twice) rc = run(false);
+        call.ws_zeroed = true;
+        if (!rc && twice) rc = run();
     }
     const hipError_t es = hipStreamSynchronize(st);
     const hipError_t ef = hipFree(ws);

@@ -1,11 +1,14 @@
 // smalltts gfx950 engine: owns the weights (fp32 originals + bf16 hi/lo GEMM packs) for one GPU and
 // sequences the kernels of the three boundary operators the reference runs through onnxruntime
 // (condition_encoder / denoiser / codec, reference infer/onnx.py:91-128) plus the fused sampler.
-// Not thread-safe: one Engine per GPU, driven by one host thread (mirrors the reference's one-Session-per-pipeline model,
-// src/server/src/main.rs:24).  That thread may keep several operator calls in flight on DIFFERENT streams as long as each
-// call has its own workspace and outputs: all per-call scratch (incl. the rope cos / sin of a caller-supplied table) lives
-// in the workspace, weights are read-only after finalize().  The dual-stream condition encoder / modulation chain forks onto a side
-// stream that belongs to the CALLER's stream (one per caller stream, round 6).  Exception: per-kernel profiling assumes one call at a time.
+// One Engine per GPU, driven by one host thread (mirrors the reference's one-Session-per-pipeline model, src/server/src/main.rs:24).
+// That thread may keep several operator calls in flight on DIFFERENT streams as long as each call has its own workspace and outputs:
+// what belongs to one call lives in that call — its device scratch (incl. the rope cos / sin of a caller-supplied table) in the
+// workspace, its host state (side set, owed join, zeroed workspace regions, text-attention tap) in the Call record the operator
+// entry creates and hands down.  The engine keeps configuration, the weights (read-only after finalize()), the map of side sets
+// (the dual-stream condition encoder / modulation chain forks onto a side stream that belongs to the CALLER's stream, one per caller
+// stream), the error string and the profiler — and is not thread-safe because of the last three.  Per-kernel profiling assumes one
+// call at a time.
 #pragma once
 #include <initializer_list>
 #include <map>
@@ -171,16 +174,16 @@ class Engine {
                             seed, x_out, steps_out, ws, ws_bytes, nullptr, 0u, 0u, nullptr);
     }
     // sample() plus the text-attention tap (align.hip): text_mass f32 (B, N, P), DEVICE, caller-owned, ends as the mean over the selected
-    // (step, layer, head) triples of each frame's softmax probability on each text key.  tap_steps: HOST array of n_steps flags (null: the
-    // last step only); tap_layers / tap_heads: bit masks (bit l / h).  text_mass == null: the tap is off and this is sample() — not one
+    // (step, layer, head) triples of each frame's softmax probability on each text key.  sel_steps: HOST array of n_steps flags (null: the
+    // last step only); sel_layers / sel_heads: bit masks (bit l / h).  text_mass == null: the tap is off and this is sample() — not one
     // launch more, the latents bit for bit the same either way.
     int sample_align(hipStream_t st, int mode, int n_steps, int cfg, float s_text, float s_spk, const uint8_t* mask,
                      const float* k_ref, const float* v_ref, const uint8_t* ref_mask, const float* k_text,
                      const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P, const float* noise,
-                     uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes, const uint8_t* tap_steps,
-                     unsigned tap_layers, unsigned tap_heads, float* text_mass) {
+                     uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes, const uint8_t* sel_steps,
+                     unsigned sel_layers, unsigned sel_heads, float* text_mass) {
         return sample_pinned(st, mode, n_steps, cfg, s_text, s_spk, mask, k_ref, v_ref, ref_mask, k_text, v_text, ph_mask, B, N, R, P, noise,
-                             seed, x_out, steps_out, ws, ws_bytes, tap_steps, tap_layers, tap_heads, text_mass, nullptr, nullptr, 0);
+                             seed, x_out, steps_out, ws, ws_bytes, sel_steps, sel_layers, sel_heads, text_mass, nullptr, nullptr, 0);
     }
     // sample_align() that keeps pinned frames (mode 0, cfg == 0; the definition: include/smalltts_hip.h).  x_pin f32 (B, N, 64), pin bool
     // (B, N), both DEVICE; K = pin && mask.  The loop runs steps [start_step, n_steps) from x = x_pin (start_step == 0: K ? x_pin : 0) and
@@ -189,8 +192,8 @@ class Engine {
     int sample_pinned(hipStream_t st, int mode, int n_steps, int cfg, float s_text, float s_spk, const uint8_t* mask,
                       const float* k_ref, const float* v_ref, const uint8_t* ref_mask, const float* k_text,
                       const float* v_text, const uint8_t* ph_mask, int B, int N, int R, int P, const float* noise,
-                      uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes, const uint8_t* tap_steps,
-                      unsigned tap_layers, unsigned tap_heads, float* text_mass, const float* x_pin, const uint8_t* pin, int start_step);
+                      uint64_t seed, float* x_out, float* steps_out, void* ws, size_t ws_bytes, const uint8_t* sel_steps,
+                      unsigned sel_layers, unsigned sel_heads, float* text_mass, const float* x_pin, const uint8_t* pin, int start_step);
 
     size_t decode_ws_bytes(int B, int T) const;
     int codec_decode(hipStream_t st, const float* latents, int B, int T, float* audio, void* ws, size_t ws_bytes);
@@ -247,8 +250,8 @@ class Engine {
     int finalize_codec(bool decoder);
     int build_encoder(EncoderW& e, const std::string& prefix, int dim, int heads, int ff, int layers, float eps);
     int make_rope(int dim, float** cos_out, float** sin_out);
-    int modulation(hipStream_t st, const float* t_dev, int rows, float* sinb, float* t1, float* temb, float* e1,
-                   float* semb, float* mod, float* ftab = nullptr);
+    struct ModWs;
+    int modulation(hipStream_t st, const float* t_dev, int rows, const ModWs& m);   // ... and its LN-fold tables where m plans them
     int fold_tables(hipStream_t st, const float* mod, int rows, float* ftab);   // LN-fold tables of `rows` modulation rows (fold_vectors)
     // ---- condition encoders: one call = per encoder in, blocks [0, L), out, kv.  cond_encode and the test hook (test_dit_stage) run
     // the same functions on workspaces planned the same way (EncWs)
@@ -261,33 +264,21 @@ class Engine {
                    int ks);
     int enc_out(hipStream_t st, bool text, const EncWs& w, int M, const uint8_t* key_mask, float* seq);
     int enc_kv(hipStream_t st, bool text, const EncWs& w, const float* seq, int B, int S, float* k, float* v);
-    struct DenoiseWs;
-    // cross-KV cache of all layers in the attention kernel's operand format (attention_img.hip), built once per sampler call
+    // cross-KV cache of all layers in the attention kernel's operand format (attention_img.hip), built once per operator call
     struct CrossImg { bf16_t *kc = nullptr, *kc_lo = nullptr, *vtc = nullptr, *vtc_lo = nullptr; int Rp = 0, Cp = 0; };
-    size_t cross_img_bytes(int B, int R, int P) const;
-    int pack_cross(hipStream_t st, const float* k_ref, const float* v_ref, const float* k_text, const float* v_text, int B, int R,
-                   int P, char* ws, CrossImg& ci);
-    int denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, const float* mod, int mod_row0,
-                     int mod_rstride, const float* k_ref, const float* v_ref, const uint8_t* ref_mask,
-                     const float* k_text, const float* v_text, const uint8_t* ph_mask, const float* rope, int B,
-                     int N, int R, int P, float* velocity, char* ws, const CrossImg& ci, const float* ftab = nullptr);
-    size_t denoise_core_bytes(int B, int N) const;
-    // ---- DiT: one evaluation = embed, blocks [0, 12), head (denoise_core); the modulation table comes from modulation()
-    struct CoreWs;
-    struct DitRun {   // what the block stages read besides the residual stream
-        const uint8_t* mask = nullptr;
-        const float* mod = nullptr;
-        int mod_row0 = 0, mod_rstride = 0;
-        const float *k_ref = nullptr, *v_ref = nullptr, *k_text = nullptr, *v_text = nullptr;
-        const uint8_t *ref_mask = nullptr, *ph_mask = nullptr;
-        const float *rc = nullptr, *rs = nullptr;   // rope cos / sin [N][64]
-        const CrossImg* ci = nullptr;
-        const float* frow = nullptr;   // LN-fold tables of this step's modulation row: non-null = the fold path
-        int ks_out = 1, ks_ff2 = 1;    // K slices of the out-proj / FF2 launches outside the fold (1: unsplit GEMM + ln_modulate)
-        int B = 0, N = 0, R = 0, P = 0;
-        bool init_ws = true;           // zero the regions no kernel writes (the sampler's later steps find them as the first one left them)
+    struct Cond {   // what a DiT evaluation reads of the conditions: filled once per operator call, where pack_cross runs
+        const float *k_ref, *v_ref, *k_text, *v_text;
+        const uint8_t *ref_mask, *ph_mask;
+        int R, P;
+        CrossImg img;
     };
-    struct AlignTap {   // the text-attention tap of the sampler call in progress (sample_align); mass == null: off
+    int pack_cross(hipStream_t st, Cond& c, int B, const CrossImg& carved);   // fills c.img (carved: DitWs) — or leaves it empty
+    struct ModRow {   // the modulation row of utterance b is row0 + b rstride of mod; ftab: the LN-fold tables of those rows, or null
+        const float* mod = nullptr;
+        int row0 = 0, rstride = 0;
+        const float* ftab = nullptr;
+    };
+    struct AlignTap {   // the text-attention tap (sample_align); mass == null: off
         float* mass = nullptr;
         unsigned layers = 0, heads = 0;
         int rows = 0;          // batch rows tapped (the conditional rows of a CFG batch)
@@ -295,13 +286,47 @@ class Engine {
         bool first = true;     // the next tap stores, later ones add
         bool step_on = false;  // the step being evaluated is selected
     };
-    AlignTap tap_;
+    struct AuxSet { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
+    // The host state of ONE operator call (sample_pinned, denoise_step, test_dit_stage), handed down by reference
+    struct Call {
+        hipStream_t st;
+        const AuxSet* side = nullptr;   // the side set of this caller stream; null: the call does not fork
+        bool join_owed = false;         // the side stream's modulation table must be joined before the first AdaLN reads it
+        bool ws_zeroed = false;         // the regions of the workspace no kernel writes were zeroed by an earlier evaluation of this call
+        AlignTap tap;                   // dit_blocks moves first / step_on
+        explicit Call(hipStream_t s) : st(s) {}
+        Call(const Call&) = delete;
+        hipError_t join() {
+            const hipError_t e = join_owed ? hipStreamWaitEvent(st, side->join, 0) : hipSuccess;
+            if (e == hipSuccess) join_owed = false;
+            return e;
+        }
+        // an early return between the fork and the first AdaLN must not leave the side stream's writes into this workspace unordered
+        // against whatever the caller does next on `st`
+        ~Call() { (void)join(); }
+    };
+    // ---- DiT: one evaluation = embed, blocks [0, 12), head (denoise_core); the modulation table comes from modulation()
+    struct CoreWs;
+    struct DitWs;
+    size_t dit_ws_bytes(int B, int N, int R, int P, int mod_rows, bool fold, int n_steps, int cfg) const;
+    struct DitRun {   // what the block stages read besides the residual stream (dit_run)
+        const uint8_t* mask = nullptr;
+        ModRow row;
+        const Cond* cond = nullptr;
+        const float *rc = nullptr, *rs = nullptr;   // rope cos / sin [N][64]
+        const float* frow = nullptr;   // LN-fold tables of this step's modulation row: non-null = the fold path
+        int ks_out = 1, ks_ff2 = 1;    // K slices of the out-proj / FF2 launches outside the fold (1: unsplit GEMM + ln_modulate)
+        int B = 0, N = 0;
+    };
+    int dit_run(hipStream_t st, const CoreWs& w, const uint8_t* mask, const ModRow& row, const Cond& cond, const float* rope, int B, int N,
+                bool fold, bool unsplit, DitRun& d);
+    int denoise_core(hipStream_t st, const float* x_t, const uint8_t* mask, const ModRow& row, const Cond& cond, const float* rope, int B,
+                     int N, float* velocity, const CoreWs& w, Call& call);
     int dit_embed(hipStream_t st, const CoreWs& w, const float* x_t, const uint8_t* mask, int B, int N, bool init_ws);
     // blocks [l0, l1): the AdaLN of block l0 runs as the ln_modulate launch (and seeds the fold's row shift); each block ends in the
     // next block's AdaLN image in w.y — after block 11 the final AdaLN (SITE_COND format)
-    int dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0, int l1);
+    int dit_blocks(hipStream_t st, const CoreWs& w, const DitRun& d, int l0, int l1, Call& call);
     int dit_head(hipStream_t st, const CoreWs& w, int M, float* velocity);
-    // runs one block; the result lives in *x on return (the fused mixer ping-pongs *x <-> *xalt)
     int ensure_qkvg_unpadded();   // packs DitBlockW::qkvg of every block on first use of an A/B attention path
     bool qkvg_unpadded_ready_ = false;   // ... set only after EVERY block packed (a failure half-way unlinks what was built)
     // ---- codec: one call = stem, then per stage the resampling into it (stage > 0) and its blocks, then final norm + head.  The
@@ -364,13 +389,8 @@ class Engine {
                                            // a launch of these 600-row products is ~8 us of fixed cost whatever its k-loop (5 k-tiles at 3 slices), so the third
                                            // slice only adds a partial slab (a third of the fp32 slab traffic of the reduce kernel)
     bool dual_stream_ = true;  // cond_encode: text encoder on a side stream (SMTTS_SINGLE_STREAM=1 turns it off)
-    struct AuxSet { hipStream_t stream = nullptr; hipEvent_t fork = nullptr, join = nullptr; };
-    std::map<hipStream_t, AuxSet> aux_sets_;   // side stream + fork / join events per caller stream (ensure_aux)
-    hipStream_t aux_ = nullptr;                // ... of the call being enqueued
-    hipEvent_t ev_fork_ = nullptr, ev_join_ = nullptr;
-    int ensure_aux(hipStream_t st);
-    bool ws_ready_ = false, ws_keep_ = false;   // sample(): the denoiser workspace's never-written regions were zeroed by an earlier step of this call
-    bool join_pending_ = false;   // sample(): the side stream's modulation table must be joined before the first AdaLN
+    std::map<hipStream_t, AuxSet> aux_sets_;      // side stream + fork / join events per caller stream: complete entries only
+    const AuxSet* side_set(hipStream_t st);       // ... looked up, created on a stream's first fork; null with err_ set on failure
     int num_cus_ = 256;
     bool convpos_by_group_ = true;  // grouped conv pos-embed as one product per group over the batch's rows (false: per (utterance, group))
     bool attn_img_ = true;   // attention on producer-written operand images (attention_img.hip: DMA + MFMA only); false (SMTTS_ATTN_IMG=0, test hook) = fp32 projection + qk_prep + the fp32 VALU reference kernel (attention.hip)

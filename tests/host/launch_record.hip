@@ -1,16 +1,9 @@
-// Launch recorder (tests/test_launch_table_cpu.py): the library's launcher objects linked against recording stand-ins for the few HIP
-// runtime entry points they call.  No GPU is opened.  Every launcher call of the sweep below prints one line: the call, then the
+// Launch recorder (tests/test_launch_table_cpu.py): the library's launcher objects linked against recording stand-ins for the HIP
+// runtime entry points they call (hip_record.hpp).  No GPU is opened.  Every launcher call of the sweep below prints one line: the call, then the
 // kernel instantiation, grid, workgroup and dynamic LDS it launched (or the error it returned), and for gemm3_kernel / gemm_kernel the
 // host-set switches of the operand struct.  tests/golden/launch_table.txt.gz holds the lines recorded at the last commit that passed
 // tuning through globals (its id is the table's first line): which kernel runs for which shape and tuning is pinned line by line.
-#include <cxxabi.h>
-
-#include <cstdio>
-#include <cstring>
-#include <map>
-#include <string>
-
-#include "gemm_ops.hpp"
+#include "hip_record.hpp"
 #include "kernels.hpp"
 #include "prof.hpp"
 
@@ -18,55 +11,11 @@ thread_local Profiler* g_prof = nullptr;   // (engine.hip's, which is not linked
 thread_local const char* g_prof_tag = nullptr;
 thread_local int g_prof_shapes = 0;
 
-// ---- the recording runtime ---------------------------------------------------------------------------------------------------------
-static std::map<const void*, std::string>& kernel_names() { static std::map<const void*, std::string> m; return m; }
-static struct { dim3 grid, block; size_t lds; hipStream_t st; } g_cfg;
 static int g_launches = 0;   // of the current call
-
-extern "C" {
-void** __hipRegisterFatBinary(const void*) { static void* h; return &h; }
-void __hipUnregisterFatBinary(void**) {}
-void __hipRegisterVar(void**, void*, char*, char*, int, size_t, int, int) {}
-void __hipRegisterFunction(void**, const void* host, char*, const char* device_name, unsigned, uint3*, uint3*, dim3*, dim3*, int*) {
-    int status = 0;
-    char* d = abi::__cxa_demangle(device_name, nullptr, nullptr, &status);
-    std::string n = status == 0 && d ? d : device_name;
-    free(d);
-    if (n.compare(0, 5, "void ") == 0) n.erase(0, 5);
-    for (size_t at; (at = n.find("(anonymous namespace)::")) != std::string::npos;) n.erase(at, 23);
-    int depth = 0;   // cut the parameter list: the first '(' outside the template arguments
-    for (size_t i = 0; i < n.size(); ++i) {
-        if (n[i] == '<') ++depth;
-        else if (n[i] == '>') --depth;
-        else if (n[i] == '(' && depth == 0) { n.erase(i); break; }
-    }
-    std::string packed;
-    for (char c : n)
-        if (c != ' ') packed += c;
-    kernel_names()[host] = packed;
-}
-hipError_t __hipPushCallConfiguration(dim3 grid, dim3 block, size_t lds, hipStream_t st) { g_cfg = {grid, block, lds, st}; return hipSuccess; }
-hipError_t __hipPopCallConfiguration(dim3* grid, dim3* block, size_t* lds, hipStream_t* st) {
-    *grid = g_cfg.grid; *block = g_cfg.block; *lds = g_cfg.lds; *st = g_cfg.st;
-    return hipSuccess;
-}
-hipError_t hipLaunchKernel(const void* f, dim3 grid, dim3 block, void** args, size_t lds, hipStream_t) {
-    auto it = kernel_names().find(f);
-    const std::string name = it == kernel_names().end() ? "?" : it->second;
-    printf(" -> %s grid=%u,%u,%u wg=%u lds=%zu", name.c_str(), grid.x, grid.y, grid.z, block.x, lds);
-    if (name.compare(0, 13, "gemm3_kernel<") == 0) {
-        const Gemm3Operands* g = static_cast<const Gemm3Operands*>(args[0]);
-        printf(" nfast=%d stage16=%d", g->nfast, g->stage16);
-    } else if (name.compare(0, 12, "gemm_kernel<") == 0) {
-        printf(" xcd_order=%d", static_cast<const GemmOperands*>(args[0])->xcd_order);
-    }
+static void on_launch(const std::string& name, dim3 grid, dim3 block, size_t lds, hipStream_t, void** args) {
+    printf(" -> ");
+    print_launch(name, grid, block, lds, args);
     ++g_launches;
-    return hipSuccess;
-}
-hipError_t hipFuncSetAttribute(const void*, hipFuncAttribute, int) { return hipSuccess; }
-hipError_t hipGetDevice(int* dev) { *dev = 0; return hipSuccess; }
-hipError_t hipDeviceGetAttribute(int* v, hipDeviceAttribute_t, int) { *v = 256; return hipSuccess; }
-hipError_t hipGetLastError() { return hipSuccess; }
 }
 
 // one line per call: "<call> -> <launch>" or "<call> -> err=<hipError_t>" (a call that does neither printed nothing after "->")
