@@ -53,7 +53,7 @@ int smtts_create(int device_id, smtts_handle* out);
 int smtts_destroy(smtts_handle h);
 const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation error */
 const char* smtts_version(void);
-/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, then smtts_take_scores and smtts_take_select, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
+/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, then smtts_take_scores and smtts_take_select, then the streamed decode entries, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
 #define SMTTS_ABI_VERSION 11
 int smtts_abi_version(void);
@@ -271,6 +271,34 @@ size_t smtts_decode_workspace_bytes(smtts_handle h, int B, int T);
 /* latents f32 (B,T,64) -> audio f32 (B,1,hop*T) */
 int smtts_codec_decode(smtts_handle h, void* stream, const float* latents, int B, int T, float* audio, void* ws,
                        size_t ws_bytes);
+/* ---- streamed decode: chunks of audio with carried causal state (DESIGN.md '8f. Streamed decode') ------------------------------
+ * smtts_codec_decode_stream decodes the next T latent frames of B independent streams and returns their hop * T samples each; the
+ * concatenation of a stream's chunks is the decode of the concatenated latents (the same kernels as smtts_codec_decode, chosen by the
+ * same gates at the chunk's B and T; fp32 summation order is the only admissible difference where a gate picks another kernel at
+ * another size).  Nothing in the codec depends on absolute position and no kernel looks back further than 6 frames, so a stream's
+ * whole memory is, for every image a look-back kernel reads, the last 8 frames that image had: its STATE.
+ *
+ * State pool: caller-owned DEVICE memory, n_slots slots of smtts_decode_state_bytes(h) bytes each (the slot stride; a multiple of 256),
+ * 16-byte aligned.  A slot holds one [8][C] fp32 block per boundary, densely in this order (the size is their sum, rounded up to 256):
+ *     the latent image (C = latent_dim); the input of every block of every stage, stages and blocks in decoder order (C of the stage);
+ *     the output of every stage that feeds a ConvTranspose, in stage order; the head's input (C of the last stage).
+ * Default spec: 34 boundaries, 849 920 bytes.  Frame j of a block is the frame 8 - j steps before the next frame of that image.
+ * A ZERO slot is the start of an utterance (the causal zero padding): smtts_codec_decode_stream on a zeroed slot returns what
+ * smtts_codec_decode returns, bit for bit.  After a chunk of T >= 8 frames a block holds the image's last 8 frames; after T < 8 the old
+ * block moved up by T frames with the chunk's T frames behind it.  The state belongs to the caller between calls: copying a slot
+ * (device to device, ordered against the calls on their stream) takes a snapshot a stream can be rewound to, zeroing it resets the
+ * stream.  It depends on the weights and the codec spec, not on precision or tuning.
+ * slots: DEVICE int64 (B), the slot of every row (smtts_voice_expand's table convention); a slot may appear at most ONCE per call (two
+ * rows on one slot race).  The table is not visible to the host side of this call: the kernel clamps every index into [0, n_slots),
+ * it never follows one outside the pool.  ws: smtts_decode_stream_workspace_bytes(h, B, T) bytes, 256-byte aligned: the plan of
+ * smtts_codec_decode at the CHUNK's size, whatever the utterance's length.
+ * Refused with an error, nothing enqueued: no finalized decoder, B < 1, T < 1, n_slots < 1, a NULL pointer, a pool that is not 16-byte
+ * aligned, a workspace that is too small or not 256-byte aligned.  One launch (carry_frames) per boundary and chunk more than
+ * smtts_codec_decode, none of its pad-zeroing launches. */
+size_t smtts_decode_state_bytes(smtts_handle h);                       /* per slot, multiple of 256; 0 on error */
+size_t smtts_decode_stream_workspace_bytes(smtts_handle h, int B, int T);
+int smtts_codec_decode_stream(smtts_handle h, void* stream, const float* latents, int B, int T, void* state_pool, int64_t n_slots,
+                              const int64_t* slots /* DEVICE (B) */, float* audio /* (B,1,hop*T) */, void* ws, size_t ws_bytes);
 size_t smtts_encode_workspace_bytes(smtts_handle h, int B, int S);
 /* audio f32 (B,1,S) -> latents f32 (B, S/hop, 64) */
 int smtts_codec_encode(smtts_handle h, void* stream, const float* audio, int B, int S, float* latents, void* ws,
@@ -386,6 +414,12 @@ int smtts_test_ln_fold(smtts_handle h, void* stream, const float* A, const float
  * with an error and no launch. */
 int smtts_test_codec_stage(smtts_handle h, void* stream, int part, int stage, int what, const float* x, int B, int T_in, int C_in,
                            float* out, int* T_out, int* C_out);
+/* one carry_frames launch (codec_stream.hip) on an image of the caller's: img f32 [B][8 + T][C], C a multiple of 4; the boundary's
+ * [8][C] block lies `offset` bytes into slot slots[b] (DEVICE int64 (B), each slot once) of a pool with `slot_stride` bytes per slot; img,
+ * state_pool, slot_stride and offset 16-byte aligned.  pad frame j <- block[j]; block[j] <- frame T - 8 + j of the row where that is
+ * >= 0, block[j + T] otherwise.  This hook knows no pool size: negative indices are clamped to 0, others are the caller's to keep in range. */
+int smtts_test_carry_frames(smtts_handle h, void* stream, float* img, int B, int T, int C, void* state_pool, int64_t slot_stride,
+                            int64_t offset, const int64_t* slots);
 /* DiT / condition-encoder stages through the code of smtts_denoise_step / smtts_sample / smtts_cond_encode.  net: 0 DiT, 1 style
  * encoder, 2 text encoder.  what (a run of the chain bits, in pipeline order):
  *   DiT:      1 modulation table from t[mod_rows] (otherwise `mod` [mod_rows][71040] is the table; either feeds the blocks), 2 embed

@@ -59,6 +59,10 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_codec_hop": (i32, [vp]),
     "smtts_decode_workspace_bytes": (sz, [vp, i32, i32]),
     "smtts_codec_decode": (i32, [vp, vp, vp, i32, i32, vp, vp, sz]),
+    "smtts_decode_state_bytes": (sz, [vp]),
+    "smtts_decode_stream_workspace_bytes": (sz, [vp, i32, i32]),
+    "smtts_codec_decode_stream": (i32, [vp, vp, vp, i32, i32, vp, i64, vp, vp, vp, sz]),
+    "smtts_test_carry_frames": (i32, [vp, vp, vp, i32, i32, i32, vp, i64, i64, vp]),
     "smtts_encode_workspace_bytes": (sz, [vp, i32, i32]),
     "smtts_codec_encode": (i32, [vp, vp, vp, i32, i32, vp, vp, sz]),
     "smtts_set_dual_stream": (i32, [vp, i32]),

@@ -20,7 +20,7 @@ from typing import Callable, Dict, Iterable, List, NamedTuple, Optional, Sequenc
 import numpy as np
 import torch
 
-from .engine import DEFAULT_PRECISION, HipEngine
+from .engine import DEFAULT_PRECISION, SITES, HipEngine
 from .weights import DEFAULT_CODEC, CodecSpec, all_param_specs, load_weight_file
 
 SAMPLE_RATE = 24_000
@@ -737,6 +737,19 @@ def get_engine(weights: Optional[str] = None, device: int = 0, precision: str = 
     return eng
 
 
+def stream_chunks(n: int, chunk_frames: Sequence[int] = (2, 4, 8, 16, 32)) -> List[int]:
+    """The chunk sizes synthesize_stream decodes n frames in: chunk_frames in order, the last size repeated, the final chunk whatever
+    is left (small chunks first: the first sample leaves early; larger ones later: fewer launches per second of audio)."""
+    sizes: List[int] = []
+    n, k = int(n), 0
+    while n > 0:
+        c = min(int(chunk_frames[min(k, len(chunk_frames) - 1)]), n)
+        sizes.append(c)
+        n -= c
+        k += 1
+    return sizes
+
+
 def _frames(duration_sec: float) -> int:
     return max(1, int(duration_sec * SAMPLE_RATE / HOP_SIZE))  # floor, infer/onnx.py:84
 
@@ -905,7 +918,7 @@ class SmallTTS:
                          voices: Optional[Sequence[Voice]] = None, seeds: Optional[Sequence[int]] = None, trim=None,
                          align=None, prefix_lens: Optional[Sequence[int]] = None, return_alignment: bool = False,
                          pins: Optional[Sequence[Optional[tuple]]] = None, start_step: int = 0, takes=None, return_takes: bool = False,
-                         repair=None, return_repair: bool = False):
+                         repair=None, return_repair: bool = False, _decode: bool = True):
         """Batched synthesize: per-utterance (R_i,64) refs, token lists and durations -> list of (1, samples).
         `frames` overrides the per-utterance frame counts (default floor(duration * 7.5), infer/onnx.py:84; the HTTP server
         rounds up like the reference's Rust server, pipeline.rs:66).
@@ -1074,7 +1087,7 @@ class SmallTTS:
                     # x, spans and mass are merged in place; every round's small outputs are tensors of their own (the report reads them)
                     t_cur, f_cur, kept = eng.repair_keep(t_cur, t_new, counts, f_cur, f_new, x, x_new, spans, spans_new, mass, mass_new)
                     rp_kept.append(kept); rp_counts.append(counts); rp_totals.append(t_cur)
-            audio = eng.codec_decode(x)                        # (B, 1, HOP * Nm); causal => prefixes are exact
+            audio = eng.codec_decode(x) if _decode else None   # (B, 1, HOP * Nm); causal => prefixes are exact (None: synthesize_stream decodes)
             if ep is not None:                                 # behind the decode, on the same stream
                 seg, gain, _e = eng.endpoints(audio, ns, ep)
             return _Batch(audio, x, mass, spans, seg, gain, ns, run, winner, total, feat, rp_kept, rp_counts, rp_totals)
@@ -1463,6 +1476,72 @@ class SmallTTS:
         """ref_latents (T,64) f32, phoneme ids, duration -> audio (1, samples) f32 @ 24 kHz."""
         return self.synthesize_batch([ref_latents], [phoneme_ids], [duration_sec])[0]
 
+    def synthesize_stream(self, ref_latents: Optional[np.ndarray], phoneme_ids: Sequence[int], duration_sec: float, *,
+                          chunk_frames: Sequence[int] = (2, 4, 8, 16, 32), pcm16: bool = False, seed: Optional[int] = None,
+                          voice: Optional[Voice] = None, frames: Optional[int] = None, return_latents: bool = False):
+        """synthesize() that hands the audio out while it is still being decoded: -> an iterator of numpy chunks
+        (1, samples) fp32, or int16 with pcm16=True (engine.pcm16 on the device), whose concatenation is the utterance.
+        The sampler runs ONCE, exactly as synthesize_batch runs it for this row (same seeds: `seed` is its seeds=[seed]; same
+        latents bit for bit; same fp16 range guard on the DiT sites), on the call; the latents are then decoded in chunks of
+        chunk_frames[0], chunk_frames[1], ... frames (stream_chunks: the last size repeats, the final chunk is what is left)
+        through engine.codec_decode_stream, whose carried state makes the chunks continue each other.  Per chunk: one D2D copy of
+        the state slot (the snapshot a re-decode starts from), the decode, the copy into one of two alternating pinned host
+        buffers and an event.  The event is waited for and the fp16 range counters are read before the chunk is yielded; a codec
+        site that clamped is demoted (engine.check_fp16_range) and that chunk alone is decoded again from its snapshot; a DiT site
+        that clamped (seen at the first chunk) runs the sampler again.  Reading the counters synchronises the device, so chunk
+        k + 1 is enqueued right behind that read and in front of the yield of chunk k: the device decodes chunk k + 1 while the
+        caller consumes chunk k, and no chunk waits for the decode of its successor.  `voice` (encode_voice) instead of
+        ref_latents (pass None); `frames` overrides floor(duration * 7.5); return_latents: yields (chunk, latents (n, 64)).
+        Not for trim=, align=, takes=, repair= (they need the whole utterance) or synthesize_long."""
+        sizes_in = [int(c) for c in chunk_frames]
+        if not sizes_in or min(sizes_in) < 1:
+            raise ValueError("synthesize_stream: chunk_frames needs at least one size, all >= 1")
+        if (voice is None) == (ref_latents is None):
+            raise ValueError("synthesize_stream: pass either ref_latents or voice (with ref_latents=None)")
+        rec = self.synthesize_batch(None if voice is not None else [ref_latents], [phoneme_ids], [duration_sec],
+                                    frames=None if frames is None else [int(frames)], seeds=None if seed is None else [int(seed)],
+                                    voices=None if voice is None else [voice], _defer=True, _decode=False)
+        return self._stream_chunks(rec, stream_chunks(rec.ns[0], sizes_in), bool(pcm16), bool(return_latents))
+
+    def _stream_chunks(self, rec: _Batch, sizes: Sequence[int], pcm16: bool, return_latents: bool):
+        eng = self.engine
+        if not sizes:
+            return
+        state = eng.decode_state(1)
+        snap = torch.empty_like(state)
+        dt = torch.int16 if pcm16 else torch.float32
+        hop = eng.hop                                          # (the loaded codec's, not the reference constant: test specs differ)
+        host = [torch.empty(1, hop * max(sizes), dtype=dt).pin_memory() for _ in range(2)]
+
+        def enqueue(k: int, t0: int):
+            snap.copy_(state)                                  # what a re-decode of chunk k starts from
+            a = eng.codec_decode_stream(rec.latents[:, t0:t0 + sizes[k]], state, [0])
+            a = eng.pcm16(a) if pcm16 else a
+            host[k % 2][:, :hop * sizes[k]].copy_(a[0], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            return ev
+        ev, t0, lat = enqueue(0, 0), 0, None
+        for k, c in enumerate(sizes):
+            ev.synchronize()
+            for _ in range(len(SITES) + 1):                    # every pass demotes a site: it ends
+                hit = eng.check_fp16_range("synthesize_stream")
+                if not hit:
+                    break
+                if any(not str(site).startswith("codec") for site in hit):   # the latents were clipped: sample again, start over
+                    assert k == 0, "a DiT site clamped behind the sampler"
+                    rec = rec.rerun()
+                state.copy_(snap)
+                ev = enqueue(k, t0)
+                ev.synchronize()
+            out = host[k % 2][:, :hop * c].numpy().copy()
+            if return_latents and lat is None:
+                lat = rec.latents[0].cpu().numpy()
+            if k + 1 < len(sizes):
+                ev = enqueue(k + 1, t0 + c)
+            yield (out, lat[t0:t0 + c]) if return_latents else out
+            t0 += c
+
     def forward(self, conditionings: List[torch.Tensor], transcriptions: list, texts: list,
                 duration_sec: float = 3.0) -> List[torch.Tensor]:
         from .phonemes import get_token_ids
@@ -1498,6 +1577,35 @@ class Decoder(_CodecRunner):
     def decode(self, latents: torch.Tensor) -> torch.Tensor:
         """latents f32 (batch, T, 64) -> audio f32 (batch, 1, 3200*T), returned on the CPU like the reference."""
         return self.engine.codec_decode(latents.detach()).cpu()
+
+    def open_stream(self, rows: int = 1) -> "DecodeStream":
+        """`rows` utterances decoded chunk by chunk: DecodeStream.decode(latents_chunk) continues where the last call ended."""
+        return DecodeStream(self.engine, rows)
+
+
+class DecodeStream:
+    """The causal state of `rows` utterances being decoded in chunks (engine.codec_decode_stream).  decode(chunk (rows, T, 64)) ->
+    audio (rows, 1, 3200 * T) on the CPU; the concatenated chunks are Decoder.decode of the concatenated latents.  reset(): all rows
+    start a new utterance.  snapshot() / restore(s): rewind to a point between two chunks."""
+
+    def __init__(self, engine: HipEngine, rows: int = 1) -> None:
+        self.engine, self.rows = engine, int(rows)
+        self.state = engine.decode_state(self.rows)
+        self._slots = list(range(self.rows))
+
+    def decode(self, latents: torch.Tensor) -> torch.Tensor:
+        if latents.dim() != 3 or int(latents.shape[0]) != self.rows:
+            raise ValueError(f"DecodeStream.decode: a ({self.rows}, T, 64) chunk wanted, got {tuple(latents.shape)}")
+        return self.engine.codec_decode_stream(latents.detach(), self.state, self._slots).cpu()
+
+    def reset(self) -> None:
+        self.state.zero_()
+
+    def snapshot(self) -> torch.Tensor:
+        return self.state.clone()
+
+    def restore(self, snap: torch.Tensor) -> None:
+        self.state.copy_(snap)
 
 
 class Encoder(_CodecRunner):

@@ -1,6 +1,7 @@
 // extern "C" surface of libsmalltts_hip.so — see include/smalltts_hip.h for the contract.
 #include "../../include/smalltts_hip.h"
 
+#include <cstdint>
 #include <cstring>
 #include <string>
 
@@ -198,6 +199,28 @@ size_t smtts_decode_workspace_bytes(smtts_handle h, int B, int T) { NULLCHK0; re
 int smtts_codec_decode(smtts_handle h, void* stream, const float* latents, int B, int T, float* audio, void* ws,
                        size_t ws_bytes) { NULLCHK;
     return E.codec_decode(ST(stream), latents, B, T, audio, ws, ws_bytes);
+}
+size_t smtts_decode_state_bytes(smtts_handle h) { NULLCHK0;
+    if (!E.has_decoder()) { E.fail("smtts_decode_state_bytes: decoder weights not finalized"); return 0; }
+    return E.decode_state_layout().bytes;
+}
+size_t smtts_decode_stream_workspace_bytes(smtts_handle h, int B, int T) { NULLCHK0;
+    if (B < 1 || T < 1) { E.fail("smtts_decode_stream_workspace_bytes: B and T must be positive"); return 0; }
+    return E.decode_ws_bytes(B, T);
+}
+int smtts_codec_decode_stream(smtts_handle h, void* stream, const float* latents, int B, int T, void* state_pool, int64_t n_slots,
+                              const int64_t* slots, float* audio, void* ws, size_t ws_bytes) { NULLCHK;
+    return E.codec_decode_stream(ST(stream), latents, B, T, state_pool, n_slots, slots, audio, ws, ws_bytes);
+}
+int smtts_test_carry_frames(smtts_handle h, void* stream, float* img, int B, int T, int C, void* state_pool, int64_t slot_stride,
+                            int64_t offset, const int64_t* slots) { NULLCHK;
+    if (B < 1 || T < 1 || C < 4 || C % 4) return E.fail("smtts_test_carry_frames: B, T >= 1 and C a positive multiple of 4");
+    if (!img || !state_pool || !slots) return E.fail("smtts_test_carry_frames: a required pointer is NULL");
+    if (offset < 0 || slot_stride < offset + 32 * (int64_t)C) return E.fail("smtts_test_carry_frames: the [8][C] block does not fit the slot");
+    if (((uintptr_t)img | (uintptr_t)state_pool | (uintptr_t)slot_stride | (uintptr_t)offset) & 15)
+        return E.fail("smtts_test_carry_frames: img, state_pool, slot_stride and offset must be 16-byte aligned");
+    hipError_t e = launch_carry_frames(img, B, T, C, state_pool, (long)slot_stride, (long)offset, INT64_MAX, slots, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "carry_frames");
 }
 size_t smtts_encode_workspace_bytes(smtts_handle h, int B, int S) { NULLCHK0; return E.encode_ws_bytes(B, S); }
 int smtts_codec_encode(smtts_handle h, void* stream, const float* audio, int B, int S, float* latents, void* ws,

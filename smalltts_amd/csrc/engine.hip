@@ -1686,7 +1686,7 @@ int Engine::codec_stage_chain(hipStream_t st, const CodecStageW& sg, float** xp,
 }
 
 int Engine::codec_block(hipStream_t st, const CodecBlockW& w, float** xp, float** xaltp, float* nbuf, bf16_t* n2hi,
-                        bf16_t* n2lo, bf16_t* hhi, bf16_t* hlo, int B, int T, int C, size_t n2_elems) {
+                        bf16_t* n2lo, bf16_t* hhi, bf16_t* hlo, int B, int T, int C, size_t n2_elems, bool carried) {
     const int M = B * T, pad = kCodecPad;
     float* x = *xp;
     const RowMap img = rowmap_batched(C, T, (long)(pad + T) * C, (long)pad * C);
@@ -1722,6 +1722,10 @@ int Engine::codec_block(hipStream_t st, const CodecBlockW& w, float** xp, float*
         n2_done = true;
     } else {
         HIPC(launch_rmsnorm(x, img, nbuf, nullptr, nullptr, img, M, C, cspec_.eps, w.norm_w, st));
+        if (carried) {   // the conv reads K - 1 pad frames of the NORMALISED image: RMSNorm is per frame, so the carried frames' rows are exact
+            const RowMap pm = rowmap_batched(C, pad, (long)(pad + T) * C, 0);
+            HIPC(launch_rmsnorm(x, pm, nbuf, nullptr, nullptr, pm, B * pad, C, cspec_.eps, w.norm_w, st));
+        }
         if (fused_ffn_ && C % 64 == 0 && F % 64 == 0 && C <= 2048) {  // + the FFN's RMSNorm of the updated rows (split pair n2)
             HIPC(launch_dwconv_resid_rms(x, nbuf, w.dw_w, w.dw_b, w.gamma, B, T, C, cspec_.kernel, pad, cspec_.eps, w.ffn_norm_w,
                                          n2hi, n2lo_f, rowmap_plain(C), st));
@@ -1841,14 +1845,15 @@ size_t Engine::decode_ws_bytes(int B, int T) const { return codec_ws_bytes(codec
 
 // latent image with causal zero pad, then stem conv k (as GEMM over K*latent contiguous floats) into w.xa; pads of the three
 // images at the stage-0 geometry
-int Engine::decode_stem(hipStream_t st, const CodecWs& w, const float* latents, int B, int T) {
+int Engine::decode_stem(hipStream_t st, const CodecWs& w, const float* latents, int B, int T, const CodecCarry* cy) {
     const int pad = kCodecPad, Kc = cspec_.kernel, L = cspec_.latent_dim, C = dec_.stages[0].C;
     const int pcv = prec_[SITE_CODEC_CONV];
     const int pcv3 = pcv == PREC_F16 || pcv == PREC_F16X2 ? PREC_BF16X3 : pcv;  // the fp32-A kernel has no fp16 variant
-    HIPC(launch_zero_pad_frames(w.lat, B, T, L, pad, st));
+    if (!cy) HIPC(launch_zero_pad_frames(w.lat, B, T, L, pad, st));
     HIPC(hipMemcpy2DAsync(w.lat + (long)pad * L, (size_t)(pad + T) * L * 4, latents, (size_t)T * L * 4, (size_t)T * L * 4, B,
                           hipMemcpyDeviceToDevice, st));
-    HIPC(launch_zero_pad_frames3(w.xa, w.xb, w.nb, B, T, C, pad, st));
+    if (cy) HIPC(cy->run(w.lat, B, T, L, cy->lay->lat, st));   // (behind the copy: the new state is the chunk's last frames)
+    else HIPC(launch_zero_pad_frames3(w.xa, w.xb, w.nb, B, T, C, pad, st));
     RowMap am = rowmap_batched(L, T, (long)(pad + T) * L, (long)(pad - (Kc - 1)) * L);
     RowMap om = rowmap_batched(C, T, (long)(pad + T) * C, (long)pad * C);
     HIPC(gemm_store(ops(w.lat, am, dec_.stem, B * T), ACT_NONE, store_to(w.xa, om, dec_.stem_b), 1, pcv3, st, tune_));
@@ -1857,7 +1862,8 @@ int Engine::decode_stem(hipStream_t st, const CodecWs& w, const float* latents, 
 
 // decoder stage i: the ConvTranspose into it (i > 0, what & 2), then its blocks (what & 4).  *x holds the image of (*Ti, *C) frames on
 // entry and on return; *xn is the ping-pong partner
-int Engine::decode_stage(hipStream_t st, const CodecWs& w, int i, int what, float** xp, float** xnp, int B, int* Tip, int* Cp) {
+int Engine::decode_stage(hipStream_t st, const CodecWs& w, int i, int what, float** xp, float** xnp, int B, int* Tip, int* Cp,
+                         const CodecCarry* cy) {
     static const char* kDecTags[] = {"dec.s0", "dec.s1", "dec.s2", "dec.s3", "dec.s4", "dec.s5", "dec.s6", "dec.s7"};
     ProfTag ptag(kDecTags[i < 8 ? i : 7]);
     const int pad = kCodecPad, pcv = prec_[SITE_CODEC_CONV];
@@ -1871,6 +1877,7 @@ int Engine::decode_stage(hipStream_t st, const CodecWs& w, int i, int what, floa
         const int r = sg.r, Cn = sg.C, Tn = Ti * r;
         RowMap am = rowmap_batched(C, Ti, (long)(pad + Ti) * C, (long)(pad - 1) * C);
         RowMap om = rowmap_batched((long)r * Cn, Ti, (long)(pad + Tn) * Cn, (long)pad * Cn);
+        if (cy) HIPC(cy->run(x, B, Ti, C, cy->lay->out[i - 1], st));   // frame t - 1 of the first output frames: the previous chunk's last
         if (fused_ffn_ && codec_upsample_wave_ok(sg.resample.K, sg.resample.N) && sg.resample.K == 2 * C && sg.resample.N == r * Cn)
             HIPC(launch_codec_upsample_wave(x, am, sg.resample.hi, sg.resample.lo, sg.resample.K, sg.resample_bias, xn, om,
                                             B * Ti, sg.resample.K, sg.resample.N, pcv3, st, tune_));
@@ -1896,11 +1903,17 @@ int Engine::decode_stage(hipStream_t st, const CodecWs& w, int i, int what, floa
         C = Cn;
         // zero pads of the three images at the new geometry, in one launch BEHIND the product: it writes data rows only, and its
         // input (now the ping-pong partner) is free to be overwritten from here on
-        HIPC(launch_zero_pad_frames3(x, xn, w.nb, B, Ti, C, pad, st));
+        if (!cy) HIPC(launch_zero_pad_frames3(x, xn, w.nb, B, Ti, C, pad, st));
     }
     *Tip = Ti;
     *Cp = C;
-    if (what & 4) {
+    if ((what & 4) && cy) {
+        // the images ping-pong and out-of-place kernels write no pad frames: the carry goes on the current input in front of EVERY block
+        for (size_t j = 0; j < sg.blocks.size(); ++j) {
+            HIPC(cy->run(x, B, Ti, C, cy->lay->block[i][j], st));
+            if (codec_block(st, sg.blocks[j], &x, &xn, w.nb, w.n2hi, w.n2lo, w.hhi, w.hlo, B, Ti, C, w.max_img, true)) return 1;
+        }
+    } else if (what & 4) {
         if (const int ch = codec_stage_chain(st, sg, &x, &xn, B, Ti, C)) {   // > 0: the whole stage went out as one launch
             if (ch < 0) return 1;
         } else {
@@ -1914,11 +1927,16 @@ int Engine::decode_stage(hipStream_t st, const CodecWs& w, int i, int what, floa
 }
 
 // final RMSNorm (if loaded) + head conv: the image of the last stage -> (B, Ti) audio
-int Engine::decode_head(hipStream_t st, const CodecWs& w, const float* x, int B, int Ti, int C, float* audio) {
+int Engine::decode_head(hipStream_t st, const CodecWs& w, float* x, int B, int Ti, int C, float* audio, const CodecCarry* cy) {
     const int pad = kCodecPad;
+    if (cy) HIPC(cy->run(x, B, Ti, C, cy->lay->head, st));
     if (dec_.final_norm_w) {   // out of place into the (zero-padded) scratch image: the head conv reads K - 1 pad frames
         const RowMap img = rowmap_batched(C, Ti, (long)(pad + Ti) * C, (long)pad * C);
         HIPC(launch_rmsnorm(x, img, w.nb, nullptr, nullptr, img, B * Ti, C, cspec_.eps, dec_.final_norm_w, st));
+        if (cy) {   // ... which here hold the carried frames, normalised like every other frame
+            const RowMap pm = rowmap_batched(C, pad, (long)(pad + Ti) * C, 0);
+            HIPC(launch_rmsnorm(x, pm, w.nb, nullptr, nullptr, pm, B * pad, C, cspec_.eps, dec_.final_norm_w, st));
+        }
         x = w.nb;
     }
     HIPC(launch_head_conv(x, dec_.head_w, dec_.head_b_host, audio, B, Ti, C, cspec_.kernel, pad, st));
@@ -1941,6 +1959,52 @@ int Engine::codec_decode(hipStream_t st, const float* latents, int B, int T, flo
     for (int i = 0; i < cspec_.n_ratios + 1; ++i)
         if (decode_stage(st, w, i, 2 | 4, &x, &xn, B, &Ti, &C)) return 1;
     return decode_head(st, w, x, B, Ti, C, audio);
+}
+
+// ---- streamed decode --------------------------------------------------------------------------------------------------------------
+Engine::DecodeStateLayout Engine::decode_state_layout() const {
+    const CodecSpecC& s = cspec_;
+    const int S = s.n_ratios + 1;
+    DecodeStateLayout l;
+    size_t off = 0;
+    auto take = [&](size_t C) { const size_t o = off; off += (size_t)kCodecPad * C * sizeof(float); ++l.count; return o; };
+    auto width = [&](int i) { return (size_t)s.n_filters << (S - 1 - i); };
+    l.lat = take((size_t)s.latent_dim);
+    l.block.resize(S);
+    for (int i = 0; i < S; ++i)
+        for (int j = 0; j < s.depths[i]; ++j) l.block[i].push_back(take(width(i)));
+    for (int i = 0; i + 1 < S; ++i) l.out.push_back(take(width(i)));
+    l.head = take(width(S - 1));
+    l.bytes = (off + 255) & ~size_t(255);
+    return l;
+}
+
+int Engine::codec_decode_stream(hipStream_t st, const float* latents, int B, int T, void* pool, int64_t n_slots, const int64_t* slots,
+                                float* audio, void* ws, size_t ws_bytes) {
+    if (!dec_.ready) return fail("codec_decode_stream: decoder weights not finalized");
+    if (B < 1 || T < 1) return fail("codec_decode_stream: B and T must be positive");
+    if (!latents || !pool || !slots || !audio) return fail("codec_decode_stream: a required pointer is NULL");
+    if (n_slots < 1) return fail("codec_decode_stream: the state pool has no slots");
+    if (reinterpret_cast<uintptr_t>(pool) & 15) return fail("codec_decode_stream: the state pool must be 16-byte aligned");
+    if ((cspec_.latent_dim | cspec_.n_filters) % 4) return fail("codec_decode_stream: channel counts must be multiples of 4");
+    const CodecPlan plan = codec_plan(true, B, T);
+    if (ws_bytes < codec_ws_bytes(plan)) return fail("codec_decode_stream: workspace too small");
+    if (ws_misaligned(ws)) return fail("codec_decode_stream: workspace must be 256-byte aligned");
+    const DecodeStateLayout lay = decode_state_layout();
+    for (size_t i = 0; i < lay.block.size(); ++i)
+        if (lay.block[i].size() != dec_.stages[i].blocks.size()) return fail("codec_decode_stream: the codec spec changed after finalize");
+    HIPC(hipSetDevice(device_));
+    const CodecCarry cy{pool, (long)lay.bytes, (long)n_slots, slots, &lay};
+    Bump bump(ws);
+    CodecWs w;
+    w.plan(bump, plan);
+    if (decode_stem(st, w, latents, B, T, &cy)) return 1;
+    float* x = w.xa;
+    float* xn = w.xb;
+    int Ti = T, C = dec_.stages[0].C;
+    for (int i = 0; i < cspec_.n_ratios + 1; ++i)
+        if (decode_stage(st, w, i, 2 | 4, &x, &xn, B, &Ti, &C, &cy)) return 1;
+    return decode_head(st, w, x, B, Ti, C, audio, &cy);
 }
 
 size_t Engine::encode_ws_bytes(int B, int S_) const { return codec_ws_bytes(codec_plan(false, B, S_)); }

@@ -197,6 +197,21 @@ class Engine {
 
     size_t decode_ws_bytes(int B, int T) const;
     int codec_decode(hipStream_t st, const float* latents, int B, int T, float* audio, void* ws, size_t ws_bytes);
+    // Streamed decode (include/smalltts_hip.h smtts_codec_decode_stream): T latent frames of B streams whose causal state
+    // (the last 8 frames of every image a look-back kernel reads: DecodeStateLayout) lives in slot slots[b] of the caller's pool.  The
+    // kernels are codec_decode's at the chunk's (B, T); in front of every consumer carry_frames (codec_stream.hip) puts the carried
+    // frames where codec_decode has zeros.  The stage chain is never taken (its warm-up tile special-cases the utterance start).
+    struct DecodeStateLayout {   // byte offsets of the boundaries' [8][C] fp32 blocks inside a slot, in slot order
+        size_t lat = 0;                           // the latent image (C = latent_dim)
+        std::vector<std::vector<size_t>> block;   // [stage][block]: the input of every block
+        std::vector<size_t> out;                  // [stage < n_ratios]: the output of a stage that feeds a ConvTranspose
+        size_t head = 0;                          // the head's input
+        size_t bytes = 0;                         // one slot = the slot stride of a pool: the sum, rounded up to 256
+        int count = 0;                            // boundaries
+    };
+    DecodeStateLayout decode_state_layout() const;   // from the codec spec alone: THE layout, for the size query and the driver
+    int codec_decode_stream(hipStream_t st, const float* latents, int B, int T, void* pool, int64_t n_slots, const int64_t* slots,
+                            float* audio, void* ws, size_t ws_bytes);
     size_t encode_ws_bytes(int B, int S) const;
     int codec_encode(hipStream_t st, const float* audio, int B, int S, float* latents, void* ws, size_t ws_bytes);
 
@@ -335,9 +350,17 @@ class Engine {
     struct CodecWs;
     CodecPlan codec_plan(bool decoder, int B, long T) const;   // T: decoder latent frames / encoder audio samples of the whole call
     size_t codec_ws_bytes(const CodecPlan& p) const;
-    int decode_stem(hipStream_t st, const CodecWs& w, const float* latents, int B, int T);
-    int decode_stage(hipStream_t st, const CodecWs& w, int i, int what, float** x, float** xn, int B, int* Ti, int* C);
-    int decode_head(hipStream_t st, const CodecWs& w, const float* x, int B, int Ti, int C, float* audio);
+    // cy (streamed decode): where these zero pad frames, they carry them instead, on the image the next consumer reads, in front of it
+    struct CodecCarry {
+        void* pool; long stride, n_slots; const int64_t* slots; const DecodeStateLayout* lay;
+        hipError_t run(float* img, int B, int T, int C, size_t off, hipStream_t st) const {
+            return launch_carry_frames(img, B, T, C, pool, stride, (long)off, n_slots, slots, st);
+        }
+    };
+    int decode_stem(hipStream_t st, const CodecWs& w, const float* latents, int B, int T, const CodecCarry* cy = nullptr);
+    int decode_stage(hipStream_t st, const CodecWs& w, int i, int what, float** x, float** xn, int B, int* Ti, int* C,
+                     const CodecCarry* cy = nullptr);
+    int decode_head(hipStream_t st, const CodecWs& w, float* x, int B, int Ti, int C, float* audio, const CodecCarry* cy = nullptr);
     int encode_stem(hipStream_t st, const CodecWs& w, const float* audio, int B, int S);
     int encode_stage(hipStream_t st, const CodecWs& w, int i, int what, float** x, float** xn, int B, int* Ti, int* C);
     int encode_head(hipStream_t st, const CodecWs& w, const float* x, int B, int Ti, int C, float* latents);
@@ -345,7 +368,8 @@ class Engine {
                      const float* bias, float* out, const RowMap& om, int M);
     int codec_stage_chain(hipStream_t st, const CodecStageW& sg, float** x, float** xalt, int B, int T, int C);
     int codec_block(hipStream_t st, const CodecBlockW& w, float** x, float** xalt, float* nbuf, bf16_t* n2hi, bf16_t* n2lo,
-                    bf16_t* hhi, bf16_t* hlo, int B, int T, int C, size_t n2_elems /* capacity of n2hi (bf16 elements) */);
+                    bf16_t* hhi, bf16_t* hlo, int B, int T, int C, size_t n2_elems /* capacity of n2hi (bf16 elements) */,
+                    bool carried = false /* the pad frames of *x hold carried frames: a path that reads pads of nbuf normalises them too */);
     int check_shape(const std::string& name, std::initializer_list<long> want);
     void invalidate() { finalized_ = false; dit_ready_ = false; dec_.ready = false; enc_.ready = false; }
     void free_packs();

@@ -206,6 +206,11 @@ hipError_t launch_stem_conv1(const float* audio, const float* w, const float* bi
                              int K, int pad, hipStream_t st);
 hipError_t launch_zero_pad_frames(float* x, int B, int T, int C, int pad, hipStream_t st);
 hipError_t launch_zero_pad_frames3(float* x0, float* x1, float* x2 /* may be null */, int B, int T, int C, int pad, hipStream_t st);
+// streamed decode (codec_stream.hip): the 8 pad frames of img [B][8 + T][C] <- the boundary's [8][C] block (at byte `offset`) of slot
+// slots[b] of the state pool, the block <- the last 8 frames the image now has behind it (T < 8: the old block moved up by T, then the
+// chunk).  slots: DEVICE int64 (B), each slot at most once, clamped into [0, n_slots).  img, pool, slot_stride, offset: 16-byte aligned
+hipError_t launch_carry_frames(float* img, int B, int T, int C, void* pool, long slot_stride, long offset, long n_slots,
+                               const int64_t* slots, hipStream_t st);
 
 // Fused codec FFN block for C in {32, 64, 128}: x += gamma * (W2 gelu(W1 rmsnorm(x) + b1) + b2), hidden kept in LDS.
 // w1 packed [F][CP], w2 packed [CP][F] with CP = max(C, 64) (zero padded).  (codec_ffn.hip)

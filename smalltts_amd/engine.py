@@ -665,6 +665,49 @@ class HipEngine:
                  "codec_decode")
         return audio
 
+    # ---- streamed decode: chunks of audio with carried causal state (include/smalltts_hip.h) ------------------------
+    @property
+    def decode_state_bytes(self) -> int:
+        """Bytes of one state slot of a streamed decode (a multiple of 256: the slot stride of a pool)."""
+        n = int(self.lib.smtts_decode_state_bytes(self.h))
+        if n <= 0:
+            raise RuntimeError(f"decode_state_bytes: {self.lib.smtts_last_error(self.h).decode()}")
+        return n
+
+    def decode_state(self, n_slots: int) -> torch.Tensor:
+        """A zeroed state pool of n_slots streams: uint8 (n_slots, state_bytes) on the device.  A zero slot is the start of an
+        utterance; the pool is the caller's: state[k].zero_() resets stream k, state[k].clone() / .copy_() snapshot and rewind it
+        (on the stream the decodes run on)."""
+        n_slots = int(n_slots)
+        if n_slots < 1:
+            raise ValueError("decode_state: at least one slot")
+        return torch.zeros(n_slots, self.decode_state_bytes, dtype=torch.uint8, device=self.device)
+
+    def codec_decode_stream(self, latents, state: torch.Tensor, slots) -> torch.Tensor:
+        """The next chunk of B streams: latents (B,T,64), row b continuing the stream whose state is slot slots[b] of `state`
+        (decode_state()) -> audio (B,1,hop*T); the state moves on in place.  The concatenated chunks of a stream are the decode of
+        its concatenated latents (smtts_codec_decode_stream).  slots: B distinct host integers in [0, n_slots); the table goes up
+        pinned and non-blocking.  On the current stream, no synchronisation."""
+        lat = self._dev(latents, torch.float32)
+        if lat.dim() != 3 or int(lat.shape[2]) != LATENT or int(lat.shape[0]) < 1 or int(lat.shape[1]) < 1:
+            raise ValueError(f"codec_decode_stream: latents must be (B,T,{LATENT}) with B, T >= 1, got {tuple(lat.shape)}")
+        B, T, _ = (int(v) for v in lat.shape)
+        sb = self.decode_state_bytes
+        if (not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 2 or int(state.shape[1]) != sb
+                or int(state.shape[0]) < 1 or not state.is_contiguous() or state.device != self.device or state.data_ptr() % 16):
+            raise ValueError(f"codec_decode_stream: state must be a contiguous, 16-byte aligned uint8 (n_slots,{sb}) tensor on the "
+                             "engine's device (decode_state())")
+        n_slots = int(state.shape[0])
+        sl = [int(v) for v in slots]
+        if len(sl) != B or len(set(sl)) != B or min(sl) < 0 or max(sl) >= n_slots:
+            raise ValueError(f"codec_decode_stream: {B} distinct slots in [0, {n_slots}) wanted, got {sl}")
+        tab = self._upload_i64(sl)
+        audio = torch.empty(B, 1, self.hop * T, device=self.device)
+        ws = self._workspace(self.lib.smtts_decode_stream_workspace_bytes(self.h, B, T))
+        self._ck(self.lib.smtts_codec_decode_stream(self.h, self._stream(), _p(lat), B, T, _p(state), n_slots, _p(tab), _p(audio),
+                                                    _p(ws), ws.numel()), "codec_decode_stream")
+        return audio
+
     def codec_encode(self, audio) -> torch.Tensor:
         """(B,1,S) -> (B,S//hop,64) (reference operator: codec/encoder.onnx, codec/onnx.py:64-75)."""
         a = self._dev(audio, torch.float32)

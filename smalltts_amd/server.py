@@ -23,6 +23,12 @@ An optional `align=1` query parameter (requests of at most 225 frames = 30 s and
 `x-smtts-words`, a JSON list of `[start sample, end sample]` per token group of the text (api.token_groups: words, punctuation marks,
 [event] runs, in order) in samples of the returned audio, from the DiT's text attention (api.Alignment defaults, unvalidated on trained
 weights; resolution one codec frame = 3200 samples).  A list over 6 KB is answered with 400.  Without the parameter nothing changes.
+An optional `stream=1` query parameter: the answer starts while the utterance is still being decoded.  It comes with
+`Transfer-Encoding: chunked` as `audio/L16; rate=24000; channels=1`: raw mono PCM16 without a container, little-endian like the WAV
+answers (`x-smtts-pcm: s16le`), rounded to nearest on the device (engine.pcm16), one HTTP chunk per decoded chunk of 2, 4, 8, 16,
+32, 32, ... frames (api.stream_chunks).  Such requests ride in batches of their own, as align=1 requests do; the dispatcher drives a
+streamed batch's chunk loop itself, so other batches are enqueued behind it.  stream=1 with trim=1 or align=1 is a 400: both need the
+whole utterance.  Without the parameter (or with stream=0) the answer is byte for byte what it was.
 
     python -m smalltts_amd.server --port 3000 --weights assets/smalltts.smtts
 """
@@ -206,14 +212,40 @@ def words_header(words) -> str:
     return v
 
 
-class Request:
-    __slots__ = ("wav", "sr", "tokens", "duration", "seed", "trim", "align", "future", "t_in")
+def parse_stream_query(q: dict, trim=None, align: bool = False) -> bool:
+    """The optional `stream` query parameter -> False (off: the answer is today's) or True.  1 / true or 0 / false; stream=1 excludes
+    trim=1 and align=1, which need the whole utterance.  Anything else is a 400 for the offender alone."""
+    raw = q.get("stream", ["0"])[0].strip().lower()
+    if raw not in ("0", "1", "true", "false"):
+        raise HttpError(400, "invalid `stream`: 0 or 1")
+    on = raw in ("1", "true")
+    if on and (trim is not None or align):
+        raise HttpError(400, "invalid `stream`: not together with trim=1 or align=1 (both need the whole utterance)")
+    return on
 
-    def __init__(self, wav, sr, tokens, duration, seed, trim=None, align=False):
+
+def http_chunk(data: bytes) -> bytes:
+    """One chunk of a Transfer-Encoding: chunked body; b"" is the terminating chunk."""
+    return f"{len(data):x}\r\n".encode() + data + b"\r\n"
+
+
+class Request:
+    __slots__ = ("wav", "sr", "tokens", "duration", "seed", "trim", "align", "stream", "chunks", "future", "t_in")
+
+    def __init__(self, wav, sr, tokens, duration, seed, trim=None, align=False, stream=False):
         self.wav, self.sr, self.tokens, self.duration, self.seed, self.trim = wav, sr, tokens, duration, seed, trim
         self.align = bool(align)
+        self.stream = bool(stream)
+        # a streamed request is answered through this queue: bytes (PCM16 of one chunk), then None; or an HttpError
+        self.chunks: Optional["queue.Queue"] = queue.Queue() if self.stream else None
         self.future: Future = Future()
         self.t_in = time.perf_counter()
+
+    def fail(self, e: Exception):
+        if not self.future.done():
+            self.future.set_exception(e)
+        if self.chunks is not None:
+            self.chunks.put(e)
 
 
 # ----------------------------------------------------------------------------------------------------------------------
@@ -308,13 +340,15 @@ class Batcher:
                         n = validate_request(r.duration, r.tokens)   # (the handler checked already; a direct submit() may not have)
                         if r.align:
                             parse_align_query({"align": ["1"]}, r.duration, r.tokens)
+                        if r.stream:
+                            parse_stream_query({"stream": ["1"]}, r.trim, r.align)
                         refs.append(self._ref_latents(r))
                         ns.append(n)
                         ok.append(r)
                     except HttpError as e:
-                        r.future.set_exception(e)
+                        r.fail(e)
                     except Exception as e:   # engine errors while encoding this voice
-                        r.future.set_exception(HttpError(500, f"inference failed: {e}"))
+                        r.fail(HttpError(500, f"inference failed: {e}"))
                 if not ok:
                     continue
                 # padded-work budgets, not a request count: one long request neither blows the workspace up for 23 batch-mates
@@ -322,7 +356,9 @@ class Batcher:
                 # requests that ask for word timings ride in batches of their own: the tap covers padded shapes up to 225 x 198, which
                 # each of them fits, and the others' batches run exactly as without the feature
                 plan = []
-                for sel in ([j for j, r in enumerate(ok) if not r.align], [j for j, r in enumerate(ok) if r.align]):
+                # ... and so do streamed requests: their batch is sampled once and then decoded chunk by chunk (_stream_batch)
+                for sel in ([j for j, r in enumerate(ok) if not r.align and not r.stream], [j for j, r in enumerate(ok) if r.align],
+                            [j for j, r in enumerate(ok) if r.stream]):
                     if sel:
                         plan += [[sel[k] for k in g] for g in plan_batches([ns[j] for j in sel], [len(ok[j].tokens) for j in sel],
                                                                             [int(refs[j].shape[0]) for j in sel], self.max_pack)]
@@ -340,6 +376,14 @@ class Batcher:
                             for b, r in enumerate(g_ok):
                                 for s_ in range(self.steps):
                                     noise[s_, b, :g_ns[b]] = self.eng.randn(g_ns[b] * LATENT, r.seed, s_).view(g_ns[b], LATENT)
+                            if g_ok[0].stream:
+                                self._stream_batch(g_ok, g_refs, g_ns, noise)
+                                self.eng.use_workspace(None)
+                                self._slots.release()
+                                self.stats["requests"] += len(g_ok)
+                                self.stats["batches"] += 1
+                                self.stats["streamed"] = self.stats.get("streamed", 0) + len(g_ok)
+                                continue
                             rec = self.tts.synthesize_batch(g_refs, [r.tokens for r in g_ok], [r.duration for r in g_ok],
                                                             noise=noise, frames=g_ns, _defer=True,
                                                             **({"align": True} if g_align else {}))
@@ -358,7 +402,7 @@ class Batcher:
                         self.eng.use_workspace(None)
                         self._slots.release()
                         for r in g_ok:
-                            r.future.set_exception(HttpError(500, f"inference failed: {e}"))
+                            r.fail(HttpError(500, f"inference failed: {e}"))
                 # fp16 range guard (engine.check_fp16_range): the counters are read when the queue has run dry — a device
                 # synchronisation the busy path should not pay per batch.  A site that clamped runs split-bf16 from then on; the
                 # requests that hit it were answered with saturated (finite) operands, which is what the warning is for.
@@ -380,6 +424,38 @@ class Batcher:
         finally:
             self.eng.set_tuning(prev)
             self.done_q.put(None)
+
+    def _stream_batch(self, reqs: List[Request], refs, ns: List[int], noise):
+        """A batch of streamed requests on the current stream: the sampler once (synthesize_batch without its decode), then the
+        latents in chunks through engine.codec_decode_stream, one state slot per row.  Chunk k + 1 is enqueued before chunk k's
+        event is waited for; every row gets the PCM16 of its own frames of each chunk, then None."""
+        from .api import stream_chunks
+        torch, eng = self.torch, self.eng
+        rec = self.tts.synthesize_batch(refs, [r.tokens for r in reqs], [r.duration for r in reqs], noise=noise, frames=ns,
+                                        _defer=True, _decode=False)
+        B, hop = len(reqs), eng.hop
+        state = eng.decode_state(B)
+        sizes = stream_chunks(max(ns))
+        host = [torch.empty(B, hop * max(sizes), dtype=torch.int16).pin_memory() for _ in range(2)]
+
+        def enqueue(k, t0):
+            a = eng.pcm16(eng.codec_decode_stream(rec.latents[:, t0:t0 + sizes[k]], state, list(range(B))))
+            host[k % 2][:, :hop * sizes[k]].copy_(a[:, 0], non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            return ev
+        ev, t0 = enqueue(0, 0), 0
+        for k, c in enumerate(sizes):
+            nxt = enqueue(k + 1, t0 + c) if k + 1 < len(sizes) else None
+            ev.synchronize()
+            for b, r in enumerate(reqs):
+                n = min(t0 + c, ns[b]) - t0                    # frames of this chunk that belong to row b
+                if n > 0:
+                    r.chunks.put(host[k % 2][b, :hop * n].numpy().astype("<i2").tobytes())
+            ev, t0 = nxt, t0 + c
+        for r in reqs:
+            r.chunks.put(None)
+            r.future.set_result(None)
 
     # -- completer thread: waits for a batch, copies out, wakes the handlers ---------------------------------------------
     def _complete(self):
@@ -439,6 +515,28 @@ def make_handler(batcher: Batcher, tokenizer: str = "espeak"):
             self.end_headers()
             self.wfile.write(body)
 
+        def _send_stream(self, req: Request):
+            """stream=1: the status line waits for the first chunk (an error before it is an ordinary error answer); from then on one
+            HTTP chunk per decoded chunk.  An error behind the first chunk closes the connection without the terminating chunk."""
+            batcher.submit(req)
+            item = req.chunks.get(timeout=120)
+            if isinstance(item, Exception):
+                raise item if isinstance(item, HttpError) else HttpError(500, f"inference failed: {item}")
+            self.send_response(200)
+            self.send_header("content-type", f"audio/L16; rate={SAMPLE_RATE}; channels=1")
+            self.send_header("x-smtts-pcm", "s16le")
+            self.send_header("transfer-encoding", "chunked")
+            self.send_header("access-control-allow-origin", "*")
+            self.end_headers()
+            while item is not None:
+                if isinstance(item, Exception):
+                    self.close_connection = True
+                    return
+                self.wfile.write(http_chunk(item))
+                self.wfile.flush()
+                item = req.chunks.get(timeout=120)
+            self.wfile.write(http_chunk(b""))
+
         def do_GET(self):
             path = urllib.parse.urlsplit(self.path).path
             if path == "/health":
@@ -490,7 +588,10 @@ def make_handler(batcher: Batcher, tokenizer: str = "espeak"):
                 validate_request(duration, tokens)   # 400 for the offender alone, before it can join a batch
                 trim = parse_trim_query(q)
                 align = parse_align_query(q, duration, tokens)
+                stream = parse_stream_query(q, trim, align)
                 seed = int(q["seed"][0]) if "seed" in q else int.from_bytes(np.random.bytes(7), "little")
+                if stream:
+                    return self._send_stream(Request(wav, sr, tokens, duration, seed, stream=True))
                 fut = batcher.submit(Request(wav, sr, tokens, duration, seed, trim, align))
                 audio = fut.result(timeout=120)
                 extra = {}

@@ -197,6 +197,25 @@ class CodecSpec:
 
 DEFAULT_CODEC = CodecSpec()
 
+DECODE_STATE_FRAMES = 8   # frames every boundary of a streamed decode carries (csrc/engine.hpp kCodecPad)
+
+
+def decode_state_layout(spec: CodecSpec = DEFAULT_CODEC):
+    """The state slot of a streamed decode (include/smalltts_hip.h smtts_codec_decode_stream; the engine's own statement:
+    csrc/engine.hip Engine::decode_state_layout).  -> (boundaries, slot_bytes): boundaries a list of (name, channels, byte offset)
+    in slot order, each an [8][channels] fp32 block: the latent image; the input of every block of every stage; the output of
+    every stage that feeds a ConvTranspose; the head's input.  slot_bytes = their sum rounded up to 256, the slot stride of a pool."""
+    n = spec.n_stages
+    names = ([("latent", spec.latent_dim)]
+             + [(f"stage{i}.block{j}", spec.dec_channels(i)) for i in range(n) for j in range(spec.dec_depths[i])]
+             + [(f"stage{i}.out", spec.dec_channels(i)) for i in range(n - 1)]
+             + [("head", spec.dec_channels(n - 1))])
+    out, off = [], 0
+    for name, c in names:
+        out.append((name, int(c), off))
+        off += DECODE_STATE_FRAMES * int(c) * 4
+    return out, (off + 255) // 256 * 256
+
 
 def _optional(spec: CodecSpec, name: str) -> bool:
     """Is this tensor of the full inventory present under the spec's flags?"""
