@@ -53,7 +53,7 @@ int smtts_create(int device_id, smtts_handle* out);
 int smtts_destroy(smtts_handle h);
 const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation error */
 const char* smtts_version(void);
-/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, then smtts_take_scores and smtts_take_select, then the streamed decode entries, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
+/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, then smtts_take_scores and smtts_take_select, then the streamed decode entries, then smtts_deliver, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
 #define SMTTS_ABI_VERSION 11
 int smtts_abi_version(void);
@@ -318,6 +318,62 @@ int smtts_resample_poly(smtts_handle h, void* stream, const float* x, int channe
                         int down, int klen, int width, float* y, int64_t n_out);
 /* float [-1, 1] -> int16 PCM: clamp, x 32767, round to nearest (reference server audio.rs:22-37; CLIs write PCM_16, tryme.py:29) */
 int smtts_pcm16(smtts_handle h, void* stream, const float* x, int64_t n, int16_t* y);
+
+/* ---- delivery: audio at the caller's rate and encoding, whole or streamed (DESIGN.md '8g. Delivery') ------------------------------
+ * smtts_deliver resamples the next chunk of B independent streams with a polyphase bank and encodes the result; the concatenation
+ * of a stream's chunks is, BIT FOR BIT, the delivery of the whole signal in one call, whatever the chunking.  Additive entries.
+ *
+ * Signal: audio f32 (B,1,row_stride), DEVICE.  table: DEVICE int64 (B,4) = (slot, n_before, len, last) per row: row b of this call is
+ * the next len[b] samples (clamped to [0, row_stride]; nothing behind them is read) of a stream that has already seen n_before[b]
+ * samples (clamped to [0, 2^50]); last != 0: the stream ends with this chunk.  x = the stream's whole signal, n = n_before + len.
+ * Bank: f32 [up][klen], klen = 2 * width + down, the layout of smtts_resample_poly (smalltts_amd/audio.py:_sinc_kernel).
+ * Sum:  y[f * up + p] = sum_{k = 0 .. klen - 1} x[f * down - width + k] * bank[p][k], where x[i] enters as +0.0f for i < 0 and,
+ *       once the stream has ended, for i >= n.  Every sample is ONE chain acc = fmaf(x_k, bank[p][k], acc) from acc = +0.0f over ALL
+ *       klen taps in the order k = 0 .. klen - 1 (no sum is shortened at an edge), in whichever call it is emitted.
+ *       n_before = 0, len = n, last = 1 is smtts_resample_poly's definition cut to ceil(up * n / down) samples (audio.resample_hq's
+ *       length).
+ * Emission: F(m) = max(0, (m - width) / down) (integer division) = the frames all of whose inputs lie in x[0 .. m).
+ *       last == 0: row b writes the frames [F(n_before), F(n)), up * (F(n) - F(n_before)) samples;
+ *       last != 0: the samples [up * F(n_before), ceil(up * n / down)).
+ *       They go to out[b][0 .. cnt_b), nothing is written behind them.  len = 0 with last != 0 is a pure flush.  The host knows
+ *       cnt_b from integers alone (smalltts_amd/audio.py:deliver_counts).
+ * State: caller-owned DEVICE pool of n_slots slots of smtts_deliver_state_bytes(h, klen) bytes each (the slot stride, a multiple of
+ *       256), 16-byte aligned.  A slot holds the stream's last H = klen - 1 input samples as f32, oldest first; a ZERO slot is the
+ *       start of a stream.  After the call the slot holds the last H samples of x[0 .. n) (with len < H the old content moves up by
+ *       len), also after last != 0.  slot indices are clamped into [0, n_slots) by the kernel, never followed outside the pool; a
+ *       slot may appear at most ONCE per call (smtts_codec_decode_stream's rules; the Python wrapper refuses duplicates and indices
+ *       out of range).  The slot belongs to the caller between calls: copy it for a snapshot, zero it to reset the stream.
+ *       The history is updated by a second launch (one workgroup per row: loads, a barrier, stores) behind the main one.
+ *       state_pool == NULL with a bank: every row starts and ends here: history reads as zeros, nothing is carried, slot is ignored,
+ *       and every row must have n_before = 0 and last = 1 (the kernel reads them as such).
+ * Pass-through: up == down == 1 with bank == NULL, klen == width == 0 and state_pool == NULL is the native rate: a pure encode with
+ *       no state, F(m) = m, cnt_b = len[b] whatever `last` says.
+ * enc:  0 = f32;  1 = int16, exactly smtts_pcm16's arithmetic on the f32 value (clamp to [-1, 1], x 32767, round to nearest even);
+ *       2 = G.711 mu-law (uint8) of that int16 s;  3 = G.711 A-law (uint8) of that int16 s.  The codes are byte for byte those of
+ *       CPython's audioop.lin2ulaw(s, 2) / audioop.lin2alaw(s, 2), i.e. the CCITT / Sun g711.c encoders on s >> 2 and s >> 3
+ *       (arithmetic shifts).  With seg(v, e) = the number of i in 0 .. 7 with v > (e + 1) * 2^i - 1:
+ *         mu-law: v = s >> 2; mask = 0xFF; if v < 0: v = -v, mask = 0x7F; v = min(v, 8159) + 33; g = seg(v, 0x3F);
+ *                 code = g >= 8 ? 0x7F ^ mask : ((g << 4) | ((v >> (g + 1)) & 15)) ^ mask
+ *         A-law:  v = s >> 3; mask = 0xD5; if v < 0: v = -v - 1, mask = 0x55; g = seg(v, 0x1F);
+ *                 code = g >= 8 ? 0x7F ^ mask : ((g << 4) | ((v >> (g < 2 ? 1 : g)) & 15)) ^ mask
+ *       Known answers (s: mu-law, A-law): 0: ff d5; 1: ff d5; -1: 7e 55; 4: fe d5; -4: 7e 55; 100: f2 d3; -100: 72 53;
+ *       1000: ce fa; -1000: 4e 7a; 32635: 80 aa; 32767: 80 aa; -32768: 00 2a.
+ *       out_stride (the row pitch of out) counts elements of the output type.
+ * Refused with 1 and a message naming the entry, nothing enqueued: a NULL handle (the size query returns 0); B outside [1, 65535];
+ *       row_stride outside [1, 2^40]; a NULL audio, table or out; up or down outside [1, 4096]; with a bank: klen != 2 * width + down,
+ *       klen > 8192, a tile window of (256 / up + 1) * down + klen floats plus a bank of up to 48 KiB above 64 KiB of LDS; without a
+ *       bank anything but the pass-through form; a pool with klen <= 1, with n_slots < 1 or not 16-byte aligned; enc outside 0 .. 3;
+ *       out_stride smaller than the largest count row_stride can produce: ceil(up * (row_stride + width + down - 1) / down) with a
+ *       pool, ceil(up * row_stride / down) without, row_stride at the pass-through rate.
+ * One launch whatever B is, plus the history launch when a pool is given.  No atomics, nothing depends on scheduling: two calls return
+ * the same bits.
+ * Only this mechanism is verified.  The banks the Python side builds (audio._sinc_kernel: a Kaiser-windowed sinc restated from
+ * torchaudio's published algorithm) are unpinned against torchaudio, as on the input side, and their 64 zero crossings
+ * (audio.DELIVER_ZEROS) are a design choice, not a measurement. */
+size_t smtts_deliver_state_bytes(smtts_handle h, int klen);   /* per slot, multiple of 256; 0 for klen <= 1 or on error */
+int smtts_deliver(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride,
+                  const int64_t* table /* DEVICE (B,4): slot, n_before, len, last */, const float* bank, int up, int down, int klen,
+                  int width, void* state_pool, int64_t n_slots, int enc, void* out, int64_t out_stride);
 
 /* ---- long-form synthesis: one voice, many rows (DESIGN.md 'Long-form synthesis') ----------------------------------
  * The two halves of smtts_cond_encode are independent (k_ref / v_ref depend on the reference only, k_text / v_text on the phonemes

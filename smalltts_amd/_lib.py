@@ -70,6 +70,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_randn": (i32, [vp, vp, vp, i64, u64, u64]),
     "smtts_resample_poly": (i32, [vp, vp, vp, i32, i64, vp, i32, i32, i32, i32, vp, i64]),
     "smtts_pcm16": (i32, [vp, vp, vp, i64, vp]),
+    "smtts_deliver_state_bytes": (sz, [vp, i32]),
+    "smtts_deliver": (i32, [vp, vp, vp, i32, i64, vp, vp, i32, i32, i32, i32, vp, i64, i32, vp, i64]),
     "smtts_voice_expand": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
     "smtts_randn_rows": (i32, [vp, vp, vp, vp, vp, i32, i32, i32]),
     "smtts_stitch": (i32, [vp, vp, vp, i32, i64, vp, vp, vp, i32, vp, i64, i32]),

@@ -406,6 +406,69 @@ def as_repair(repair) -> Optional["Repair"]:
     raise TypeError(f"repair must be None, an int or a Repair, got {type(repair).__name__}")
 
 
+class Delivery:
+    """The rate and encoding audio leaves the engine in (immutable; DESIGN 8g, include/smalltts_hip.h smtts_deliver): `rate` one of
+    8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000 Hz, `encoding` "f32" | "pcm16" | "mulaw" | "alaw" (G.711, audioop's codes).
+    Resampled and encoded on the device behind the decode, whole or in chunks that continue each other bit for bit.  The banks are
+    the project's Kaiser-sinc restatement with audio.DELIVER_ZEROS zero crossings: unpinned against torchaudio, a design choice."""
+    __slots__ = ("rate", "encoding")
+
+    def __init__(self, rate: int = 24_000, encoding: str = "f32") -> None:
+        from .audio import DELIVER_ENCODINGS, DELIVER_RATES
+        if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)):
+            raise TypeError(f"Delivery: rate must be an integer, got {type(rate).__name__}")
+        if int(rate) not in DELIVER_RATES:
+            raise ValueError(f"Delivery: rate must be one of {DELIVER_RATES}, got {int(rate)}")
+        if encoding not in DELIVER_ENCODINGS:
+            raise ValueError(f"Delivery: encoding must be one of {DELIVER_ENCODINGS}, got {encoding!r}")
+        object.__setattr__(self, "rate", int(rate))
+        object.__setattr__(self, "encoding", str(encoding))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Delivery is immutable")
+
+    __delattr__ = __setattr__
+
+    def __repr__(self) -> str:
+        return f"Delivery(rate={self.rate!r}, encoding={self.encoding!r})"
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Delivery) and (self.rate, self.encoding) == (other.rate, other.encoding)
+
+    def __hash__(self) -> int:
+        return hash((self.rate, self.encoding))
+
+    @property
+    def ratio(self) -> Tuple[int, int]:
+        """(up, down) of 24 kHz -> rate in lowest terms."""
+        from .audio import deliver_ratio
+        return deliver_ratio(self.rate)
+
+    @property
+    def dtype(self):
+        from .audio import DELIVER_DTYPES
+        return DELIVER_DTYPES[self.encoding]
+
+    def samples(self, s: int) -> int:
+        """A position or length of `s` samples at 24 kHz in output samples: ceil(up * s / down)."""
+        up, down = self.ratio
+        return -(-up * int(s) // down)
+
+
+def as_delivery(deliver) -> Optional["Delivery"]:
+    """The `deliver=` argument of the synthesis calls: None -> None (today's path: 24 kHz fp32, not one launch more), a Delivery ->
+    itself, an int -> Delivery(rate), a (rate, encoding) pair -> Delivery(rate, encoding)."""
+    if deliver is None:
+        return None
+    if isinstance(deliver, Delivery):
+        return deliver
+    if isinstance(deliver, (int, np.integer)) and not isinstance(deliver, bool):
+        return Delivery(int(deliver))
+    if isinstance(deliver, (tuple, list)) and len(deliver) == 2:
+        return Delivery(deliver[0], deliver[1])
+    raise TypeError(f"deliver must be None, a Delivery, a rate or a (rate, encoding) pair, got {type(deliver).__name__}")
+
+
 def token_groups(ids: Sequence[int]) -> List[Tuple[str, str, int, int]]:
     """The units word timings are reported for: runs of token ids between the space symbol.  -> [(kind, phonemes, t0, t1), ...] in
     order, [t0, t1) the run's token indices, phonemes = decode_token_ids of them.  kind "word": a run of letter / IPA symbols;
@@ -918,7 +981,7 @@ class SmallTTS:
                          voices: Optional[Sequence[Voice]] = None, seeds: Optional[Sequence[int]] = None, trim=None,
                          align=None, prefix_lens: Optional[Sequence[int]] = None, return_alignment: bool = False,
                          pins: Optional[Sequence[Optional[tuple]]] = None, start_step: int = 0, takes=None, return_takes: bool = False,
-                         repair=None, return_repair: bool = False, _decode: bool = True):
+                         repair=None, return_repair: bool = False, _decode: bool = True, deliver=None):
         """Batched synthesize: per-utterance (R_i,64) refs, token lists and durations -> list of (1, samples).
         `frames` overrides the per-utterance frame counts (default floor(duration * 7.5), infer/onnx.py:84; the HTTP server
         rounds up like the reference's Rust server, pipeline.rs:66).
@@ -962,11 +1025,21 @@ class SmallTTS:
         the merged rows.  Not together with `noise` or `start_step` > 0.  `return_repair`: one more element at the very end, per
         row (kept (rounds,), (bad tokens, freed frames) (rounds, 2), total before (rounds,), total after (rounds,)), from one small
         read-back.  Only the mechanism is verified: whether the 4-step student inpaints audibly well, and whether a lower total
-        is the better take, are UNVALIDATED on trained weights (Repair)."""
+        is the better take, are UNVALIDATED on trained weights (Repair).
+        `deliver` (a Delivery, a rate or a (rate, encoding) pair): behind the decode, on the batch's stream, every row is
+        resampled to the Delivery's rate and encoded on the device (engine.deliver, one launch whatever B is) and only that is copied
+        out: row b comes back as (1, rate * ns[b] / 7.5) samples in the encoding's dtype (float32, int16, or uint8 G.711 codes), and
+        the words of `align` are given in output samples.  Not together with `trim`.  None is the call as it always was: 24 kHz
+        fp32, not one launch more."""
         ep = as_endpointing(trim)
         al = as_alignment(align)
         tk = as_takes(takes)
         rp = as_repair(repair)
+        dv = as_delivery(deliver)
+        if dv is not None and ep is not None:
+            raise ValueError("synthesize_batch: deliver= and trim= exclude each other")
+        if dv is not None and _defer:
+            raise ValueError("synthesize_batch: a deferred batch is delivered by its caller (engine.deliver)")
         if tk is None and return_takes:
             raise ValueError("synthesize_batch: return_takes= belongs to takes=")
         if tk is not None and noise is not None:
@@ -1096,20 +1169,29 @@ class SmallTTS:
         if _defer:                                             # synthesize_batches / synthesize_long / the server: stay on the device / stream
             return rec
         return self._finish_batch(rec, ep, None if al is None else (phoneme_ids, p0s, ps), return_latents, return_alignment,
-                                  (K, row_seeds) if return_takes else None, return_repair)
+                                  (K, row_seeds) if return_takes else None, return_repair, dv)
 
     def _finish_batch(self, rec: _Batch, ep: Optional["Endpointing"], tokens: Optional[tuple], return_latents: bool,
-                      return_alignment: bool, takes: Optional[tuple] = None, return_repair: bool = False):
+                      return_alignment: bool, takes: Optional[tuple] = None, return_repair: bool = False,
+                      dv: Optional["Delivery"] = None):
         """synthesize_batch's tail: one batch from the device to what the call returns.  `tokens` = (token lists, prefix lengths, token
         counts) with align=, else None; `takes` = (K, the rows' seeds) with return_takes, else None.
         -> rows[, latents][, words[, raw alignment]][, takes][, repair]; the rows alone are returned bare."""
         eng = self.engine
         B = len(rec.ns)
-        head = (rec.audio if ep is None else rec.seg).cpu().numpy()   # synchronises: the saturation counters are final
+
+        def read_head(rec):
+            if dv is None:
+                return (rec.audio if ep is None else rec.seg).cpu().numpy(), None
+            out, counts = eng.deliver(rec.audio, [eng.hop * n for n in rec.ns], dv.rate, dv.encoding)   # behind the decode, same stream
+            return out.cpu().numpy(), counts
+        head, counts = read_head(rec)                          # synchronises: the saturation counters are final
         if eng.check_fp16_range("synthesize"):                 # an fp16 operand clipped: the site is split-bf16 now, run again
             rec = rec.rerun()
-            head = (rec.audio if ep is None else rec.seg).cpu().numpy()
-        if ep is None:
+            head, counts = read_head(rec)
+        if dv is not None:
+            outs = [head[b: b + 1, : counts[b]] for b in range(B)]
+        elif ep is None:
             outs = _rows(head, rec.ns)
         else:                                                  # cut and levelled on the device: only the windows are copied out
             offs, S = plan_packed(head[:, 1], 0.0)
@@ -1129,6 +1211,8 @@ class SmallTTS:
                 groups = token_groups(list(phoneme_ids[b])[p0s[b]:ps[b]])
                 win = None if ep is None else (int(head[b, 0]), int(head[b, 1]))
                 words.append(word_times(groups, spans_h[b], rec.ns[b], token0=p0s[b], window=win))
+            if dv is not None:                                 # positions in output samples
+                words = [[(i, kind, dv.samples(s), dv.samples(e)) for i, kind, s, e in row] for row in words]
             res.append(words)
             if return_alignment:
                 mh = rec.mass.cpu().numpy()
@@ -1194,7 +1278,7 @@ class SmallTTS:
                         fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3, pcm16: bool = False,
                         prefix_tokens: Optional[Sequence[int]] = None, trim=None, return_segments: bool = False,
                         return_words: bool = False, align=None, return_pieces: bool = False, takes=None, return_takes: bool = False,
-                        repair=None, return_repair: bool = False):
+                        repair=None, return_repair: bool = False, deliver=None):
         """A whole text in one voice -> one waveform (1, S), fp32 or (pcm16=True) int16 PCM, S = sum(3200 * n_i) + (pieces - 1) *
         round(gap_ms * 24).
 
@@ -1241,7 +1325,17 @@ class SmallTTS:
         render_long reproduces the waveform as ever, while its `seed` stays what the piece was first spoken from: the repaired
         frames are not a function of that seed alone.  `return_repair=True`: additionally, as the very last element -> per piece
         (kept (rounds,), (bad tokens, freed frames) (rounds, 2), total before (rounds,), total after (rounds,)), from one small
-        read-back.  Returns (waveform[, segments][, words][, pieces][, takes][, repair])."""
+        read-back.
+
+        `deliver` (a Delivery, a rate or a (rate, encoding) pair): the JOINED waveform, one row, is resampled and encoded
+        on the device behind the join (engine.deliver) and comes back as (1, ceil(up * S / down)) in the encoding's dtype; segment
+        offsets, lengths and starts and the word times are then given in output samples, ceil(up * s / down) of the 24 kHz position
+        (a length as the difference of its two ends).  The pieces' batches are not resampled one by one.  Not together with
+        pcm16=True (ask for Delivery(rate, "pcm16")).  None is the call as it always was.
+        Returns (waveform[, segments][, words][, pieces][, takes][, repair])."""
+        dv = as_delivery(deliver)
+        if dv is not None and pcm16:
+            raise ValueError("synthesize_long: deliver= and pcm16=True exclude each other: ask for Delivery(rate, 'pcm16')")
         ep = as_endpointing(trim)
         tk = as_takes(takes)
         rp = as_repair(repair)
@@ -1278,12 +1372,16 @@ class SmallTTS:
         groups, offsets, S = plan_long(ns, max_batch, gap_ms)
 
         def result(out, segs, words, made, taken=None, mended=None):   # words None: not aligned
+            if dv is not None:                                 # positions in output samples
+                segs = [(dv.samples(o), dv.samples(o + n) - dv.samples(o), dv.samples(st), g) for o, n, st, g in segs]
+                words = None if words is None else [(i, kind, dv.samples(a), dv.samples(b)) for i, kind, a, b in words]
             res = ((out,) + ((segs,) if return_segments else ()) + ((words,) if words is not None else ())
                    + ((made,) if return_pieces else ()) + ((taken,) if return_takes else ()) + ((mended,) if return_repair else ()))
             return res if len(res) > 1 else out
 
         if not toks:
-            return result(np.zeros((1, 0), np.int16 if pcm16 else np.float32), [], [] if return_words else None, [], [], [])
+            return result(np.zeros((1, 0), dv.dtype if dv is not None else np.int16 if pcm16 else np.float32), [],
+                          [] if return_words else None, [], [], [])
         base = self._next_seed() if seed is None else int(seed)
         seeds = [piece_seed(base, i) for i in range(len(toks))]
         al_b = al if (al is not None or (tk is None and rp is None)) else Alignment()   # takes, repair: the path leaves the prefix out, as the words do
@@ -1296,7 +1394,7 @@ class SmallTTS:
                                                    seeds=[seeds[i] for i in g], trim=ep, _defer=True,
                                                    **kw, **({} if al_b is None else {"prefix_lens": [len(prefix)] * len(g)}))
                  for g in groups]
-        out, segs, pending = self._join_long(calls, groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16)
+        out, segs, pending = self._join_long(calls, groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16, dv)
         words = made = taken = None
         mended = _read_repair(pending) if return_repair else None   # one small read-back for the whole text
         spoken = seeds
@@ -1330,7 +1428,7 @@ class SmallTTS:
         return result(out, segs, words, made, taken, mended)
 
     def _join_long(self, calls, groups, ns, offsets, S, ep: Optional["Endpointing"], in_flight: int, gap_ms: float, fade_ms: float,
-                   pcm16: bool):
+                   pcm16: bool, dv: Optional["Delivery"] = None):
         """The tail synthesize_long and render_long share: the deferred batches `calls` (one per group) run through _run_in_flight,
         their rows are joined on the device and copied out once.  With `ep` the records carry their endpoints (every batch enqueued
         them behind its decode, and so does its re-run): the tables are read back once and the join puts the speech windows `gap_ms`
@@ -1353,6 +1451,11 @@ class SmallTTS:
                 eng.stitch(rec.audio, rec.ns, offs, fade, out)
             else:
                 eng.stitch_seg(rec.audio, rec.seg, rec.gain if ep.level_dbfs is not None else None, offs, fade, out)
+        if dv is not None:                                     # the joined waveform, one row, at the caller's rate and encoding
+            if S == 0:
+                return np.zeros((1, 0), dv.dtype), segs, pending
+            d, cnt = eng.deliver(out.view(1, 1, S), [S], dv.rate, dv.encoding)
+            return d[:, :cnt[0]].cpu().numpy(), segs, pending
         return out.cpu().numpy()[None], segs, pending
 
     def render_long(self, pieces, *, gap_ms: float = 120.0, fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3,
@@ -1478,7 +1581,7 @@ class SmallTTS:
 
     def synthesize_stream(self, ref_latents: Optional[np.ndarray], phoneme_ids: Sequence[int], duration_sec: float, *,
                           chunk_frames: Sequence[int] = (2, 4, 8, 16, 32), pcm16: bool = False, seed: Optional[int] = None,
-                          voice: Optional[Voice] = None, frames: Optional[int] = None, return_latents: bool = False):
+                          voice: Optional[Voice] = None, frames: Optional[int] = None, return_latents: bool = False, deliver=None):
         """synthesize() that hands the audio out while it is still being decoded: -> an iterator of numpy chunks
         (1, samples) fp32, or int16 with pcm16=True (engine.pcm16 on the device), whose concatenation is the utterance.
         The sampler runs ONCE, exactly as synthesize_batch runs it for this row (same seeds: `seed` is its seeds=[seed]; same
@@ -1492,7 +1595,15 @@ class SmallTTS:
         k + 1 is enqueued right behind that read and in front of the yield of chunk k: the device decodes chunk k + 1 while the
         caller consumes chunk k, and no chunk waits for the decode of its successor.  `voice` (encode_voice) instead of
         ref_latents (pass None); `frames` overrides floor(duration * 7.5); return_latents: yields (chunk, latents (n, 64)).
+        `deliver` (a Delivery, a rate or a (rate, encoding) pair): every decoded chunk is resampled and encoded on the
+        device behind its decode (engine.deliver with one delivery slot next to the decode slot, last=True on the final chunk);
+        the chunks are (1, count) arrays in the encoding's dtype whose sizes follow audio.deliver_counts (a chunk waits for the
+        resampler's look-ahead, the final chunk flushes it) and whose concatenation is the delivery of the whole utterance, bit for
+        bit.  The delivery slot is snapshotted and restored with the decode slot for a re-decode.  Not together with pcm16=True.
         Not for trim=, align=, takes=, repair= (they need the whole utterance) or synthesize_long."""
+        dv = as_delivery(deliver)
+        if dv is not None and pcm16:
+            raise ValueError("synthesize_stream: deliver= and pcm16=True exclude each other: ask for Delivery(rate, 'pcm16')")
         sizes_in = [int(c) for c in chunk_frames]
         if not sizes_in or min(sizes_in) < 1:
             raise ValueError("synthesize_stream: chunk_frames needs at least one size, all >= 1")
@@ -1501,9 +1612,9 @@ class SmallTTS:
         rec = self.synthesize_batch(None if voice is not None else [ref_latents], [phoneme_ids], [duration_sec],
                                     frames=None if frames is None else [int(frames)], seeds=None if seed is None else [int(seed)],
                                     voices=None if voice is None else [voice], _defer=True, _decode=False)
-        return self._stream_chunks(rec, stream_chunks(rec.ns[0], sizes_in), bool(pcm16), bool(return_latents))
+        return self._stream_chunks(rec, stream_chunks(rec.ns[0], sizes_in), bool(pcm16), bool(return_latents), dv)
 
-    def _stream_chunks(self, rec: _Batch, sizes: Sequence[int], pcm16: bool, return_latents: bool):
+    def _stream_chunks(self, rec: _Batch, sizes: Sequence[int], pcm16: bool, return_latents: bool, dv: Optional["Delivery"] = None):
         eng = self.engine
         if not sizes:
             return
@@ -1511,13 +1622,31 @@ class SmallTTS:
         snap = torch.empty_like(state)
         dt = torch.int16 if pcm16 else torch.float32
         hop = eng.hop                                          # (the loaded codec's, not the reference constant: test specs differ)
-        host = [torch.empty(1, hop * max(sizes), dtype=dt).pin_memory() for _ in range(2)]
+        cnt = [hop * c for c in sizes]                         # samples chunk k hands out
+        dstate = dsnap = None
+        if dv is not None:                                     # one delivery slot next to the decode slot; sizes from integers alone
+            from .audio import deliver_counts
+            _bank, up, down, width, _klen = eng.deliver_bank(dv.rate)
+            dt = torch.from_numpy(np.zeros(0, dv.dtype)).dtype
+            dstate = eng.deliver_state(1, dv.rate)             # None at 24 kHz: a pure encode carries nothing
+            dsnap = None if dstate is None else torch.empty_like(dstate)
+            if dstate is not None:
+                t0s = np.concatenate([[0], np.cumsum(sizes)[:-1]])
+                cnt = [deliver_counts(hop * int(t), hop * c, k == len(sizes) - 1, up, down, width) for k, (t, c) in enumerate(zip(t0s, sizes))]
+        host = [torch.empty(1, max(max(cnt), 1), dtype=dt).pin_memory() for _ in range(2)]
 
         def enqueue(k: int, t0: int):
             snap.copy_(state)                                  # what a re-decode of chunk k starts from
             a = eng.codec_decode_stream(rec.latents[:, t0:t0 + sizes[k]], state, [0])
+            if dv is not None:
+                if dstate is not None:
+                    dsnap.copy_(dstate)
+                    a = eng.deliver(a, [hop * sizes[k]], dv.rate, dv.encoding, state=dstate, slots=[0], n_before=[hop * t0],
+                                    last=k == len(sizes) - 1)[0][None]
+                else:
+                    a = eng.deliver(a, [hop * sizes[k]], dv.rate, dv.encoding)[0][None]
             a = eng.pcm16(a) if pcm16 else a
-            host[k % 2][:, :hop * sizes[k]].copy_(a[0], non_blocking=True)
+            host[k % 2][:, :cnt[k]].copy_(a[0][:, :cnt[k]], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record()
             return ev
@@ -1532,9 +1661,11 @@ class SmallTTS:
                     assert k == 0, "a DiT site clamped behind the sampler"
                     rec = rec.rerun()
                 state.copy_(snap)
+                if dstate is not None:
+                    dstate.copy_(dsnap)
                 ev = enqueue(k, t0)
                 ev.synchronize()
-            out = host[k % 2][:, :hop * c].numpy().copy()
+            out = host[k % 2][:, :cnt[k]].numpy().copy()
             if return_latents and lat is None:
                 lat = rec.latents[0].cpu().numpy()
             if k + 1 < len(sizes):
@@ -1578,34 +1709,61 @@ class Decoder(_CodecRunner):
         """latents f32 (batch, T, 64) -> audio f32 (batch, 1, 3200*T), returned on the CPU like the reference."""
         return self.engine.codec_decode(latents.detach()).cpu()
 
-    def open_stream(self, rows: int = 1) -> "DecodeStream":
-        """`rows` utterances decoded chunk by chunk: DecodeStream.decode(latents_chunk) continues where the last call ended."""
-        return DecodeStream(self.engine, rows)
+    def open_stream(self, rows: int = 1, deliver=None) -> "DecodeStream":
+        """`rows` utterances decoded chunk by chunk: DecodeStream.decode(latents_chunk) continues where the last call ended.
+        `deliver` (a Delivery, a rate or a (rate, encoding) pair): the chunks leave at that rate and encoding."""
+        return DecodeStream(self.engine, rows, deliver)
 
 
 class DecodeStream:
     """The causal state of `rows` utterances being decoded in chunks (engine.codec_decode_stream).  decode(chunk (rows, T, 64)) ->
     audio (rows, 1, 3200 * T) on the CPU; the concatenated chunks are Decoder.decode of the concatenated latents.  reset(): all rows
-    start a new utterance.  snapshot() / restore(s): rewind to a point between two chunks."""
+    start a new utterance.  snapshot() / restore(s): rewind to a point between two chunks.
+    With `deliver` decode(chunk, last=False) -> (rows, count) on the CPU in the Delivery's dtype: the chunk at its rate and
+    encoding, count = audio.deliver_counts of the samples seen so far (the resampler's look-ahead is held back until last=True
+    flushes it); the concatenated chunks are engine.deliver of the whole decode, bit for bit.  The delivery slots are reset,
+    snapshotted and restored together with the decode slots."""
 
-    def __init__(self, engine: HipEngine, rows: int = 1) -> None:
+    def __init__(self, engine: HipEngine, rows: int = 1, deliver=None) -> None:
         self.engine, self.rows = engine, int(rows)
         self.state = engine.decode_state(self.rows)
         self._slots = list(range(self.rows))
+        self.deliver = as_delivery(deliver)
+        self._dstate = None if self.deliver is None else engine.deliver_state(self.rows, self.deliver.rate)
+        self._seen = 0                                         # samples every row's delivery stream has taken in
 
-    def decode(self, latents: torch.Tensor) -> torch.Tensor:
+    def decode(self, latents: torch.Tensor, last: bool = False) -> torch.Tensor:
         if latents.dim() != 3 or int(latents.shape[0]) != self.rows:
             raise ValueError(f"DecodeStream.decode: a ({self.rows}, T, 64) chunk wanted, got {tuple(latents.shape)}")
-        return self.engine.codec_decode_stream(latents.detach(), self.state, self._slots).cpu()
+        audio = self.engine.codec_decode_stream(latents.detach(), self.state, self._slots)
+        if self.deliver is None:
+            return audio.cpu()
+        n = int(audio.shape[-1])
+        kw = {} if self._dstate is None else {"state": self._dstate, "slots": self._slots, "n_before": [self._seen] * self.rows,
+                                              "last": bool(last)}
+        out, counts = self.engine.deliver(audio, [n] * self.rows, self.deliver.rate, self.deliver.encoding, **kw)
+        self._seen += n
+        return out[:, :counts[0]].cpu()
 
     def reset(self) -> None:
         self.state.zero_()
+        if self._dstate is not None:
+            self._dstate.zero_()
+        self._seen = 0
 
-    def snapshot(self) -> torch.Tensor:
-        return self.state.clone()
+    def snapshot(self):
+        if self.deliver is None:
+            return self.state.clone()
+        return (self.state.clone(), None if self._dstate is None else self._dstate.clone(), self._seen)
 
-    def restore(self, snap: torch.Tensor) -> None:
-        self.state.copy_(snap)
+    def restore(self, snap) -> None:
+        if self.deliver is None:
+            self.state.copy_(snap)
+            return
+        self.state.copy_(snap[0])
+        if self._dstate is not None:
+            self._dstate.copy_(snap[1])
+        self._seen = int(snap[2])
 
 
 class Encoder(_CodecRunner):

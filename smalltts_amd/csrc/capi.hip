@@ -5,19 +5,9 @@
 #include <cstring>
 #include <string>
 
-#include "engine.hpp"
+#include "capi_handle.hpp"
 
-struct smtts_engine {
-    Engine e;
-    explicit smtts_engine(int dev) : e(dev) {}
-};
-static thread_local std::string g_create_err;
-
-#define E (h->e)
-// every entry point that takes a handle rejects NULL with an error code (message via smtts_last_error(NULL))
-#define NULLCHK if (!h) { g_create_err = std::string(__func__) + ": null handle"; return 1; }
-#define NULLCHK0 if (!h) { g_create_err = std::string(__func__) + ": null handle"; return 0; }
-#define ST(s) static_cast<hipStream_t>(s)
+thread_local std::string g_create_err;
 
 extern "C" {
 

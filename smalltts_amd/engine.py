@@ -890,6 +890,90 @@ class HipEngine:
         self._ck(self.lib.smtts_pcm16(self.h, self._stream(), _p(x), x.numel(), _p(y)), "pcm16")
         return y
 
+    # ---- delivery: audio at the caller's rate and encoding, whole or streamed (include/smalltts_hip.h smtts_deliver) ----
+    def deliver_bank(self, rate: int, zeros: Optional[int] = None):
+        """-> (bank (up, klen) fp32 on the device or None at 24 kHz, up, down, width, klen), cached per (rate, zeros)."""
+        from .audio import DELIVER_ZEROS, _sinc_kernel, deliver_ratio
+        up, down = deliver_ratio(rate)
+        if (up, down) == (1, 1):
+            return None, 1, 1, 0, 0
+        zeros = DELIVER_ZEROS if zeros is None else int(zeros)
+        key = ("deliver", int(rate), zeros)
+        bank = self._banks.get(key)
+        if bank is None:
+            k, width = _sinc_kernel(down, up, zeros)
+            bank = (torch.from_numpy(k).to(self.device).contiguous(), width)
+            self._banks[key] = bank
+        return bank[0], up, down, bank[1], int(bank[0].shape[1])
+
+    def deliver_state(self, n_slots: int, rate: int, zeros: Optional[int] = None) -> Optional[torch.Tensor]:
+        """A zeroed state pool of n_slots delivery streams at `rate`: uint8 (n_slots, smtts_deliver_state_bytes) on the device, the
+        last klen - 1 input samples of each stream.  None at 24 kHz (the pass-through carries nothing).  A zero slot is the start of
+        a stream; state[k].clone() / .copy_() snapshot and rewind it, like decode_state()."""
+        if int(n_slots) < 1:
+            raise ValueError("deliver_state: at least one slot")
+        klen = self.deliver_bank(rate, zeros)[4]
+        if klen == 0:
+            return None
+        sb = int(self.lib.smtts_deliver_state_bytes(self.h, klen))
+        if sb <= 0:
+            raise RuntimeError(f"deliver_state: {self.lib.smtts_last_error(self.h).decode()}")
+        return torch.zeros(int(n_slots), sb, dtype=torch.uint8, device=self.device)
+
+    def deliver(self, audio, lens, rate: int, encoding: str = "f32", *, state: Optional[torch.Tensor] = None, slots=None,
+                n_before=None, last=True, zeros: Optional[int] = None):
+        """audio (B,1,S) fp32 on the device, row b = the next lens[b] samples of its stream -> (out (B, max count) in the encoding's
+        dtype on the device, counts): row b of `out` holds counts[b] samples at `rate`, nothing is written behind them
+        (smtts_deliver).  encoding "f32" | "pcm16" | "mulaw" | "alaw".  Whole signals: state=None (then n_before must be 0 and last
+        True).  Streams: state=deliver_state(...), slots = B distinct slot indices, n_before = samples each stream has seen, last =
+        True (or a flag per row) on a stream's final chunk; the chunks' concatenation is the whole call's result, bit for bit.
+        counts come from audio.deliver_counts: integers alone.  The table goes up pinned and non-blocking; on the current stream, no
+        synchronisation."""
+        from .audio import DELIVER_ENCODINGS, deliver_counts, deliver_max_count
+        if encoding not in DELIVER_ENCODINGS:
+            raise ValueError(f"deliver: encoding must be one of {DELIVER_ENCODINGS}, got {encoding!r}")
+        enc = DELIVER_ENCODINGS.index(encoding)
+        bank, up, down, width, klen = self.deliver_bank(rate, zeros)
+        if (not isinstance(audio, torch.Tensor) or audio.dtype != torch.float32 or audio.dim() != 3 or int(audio.shape[1]) != 1
+                or not audio.is_contiguous() or audio.device != self.device or int(audio.shape[0]) < 1 or int(audio.shape[2]) < 1):
+            raise ValueError("deliver: audio must be a contiguous fp32 (B,1,S) tensor on the engine's device with B, S >= 1")
+        B, row = int(audio.shape[0]), int(audio.shape[2])
+        ln = [int(v) for v in lens]
+        if len(ln) != B or min(ln) < 0 or max(ln) > row:
+            raise ValueError(f"deliver: {B} lengths in [0, {row}] wanted, got {ln}")
+        lasts = [bool(v) for v in last] if isinstance(last, (list, tuple)) else [bool(last)] * B
+        nb = [0] * B if n_before is None else [int(v) for v in n_before]
+        if len(lasts) != B or len(nb) != B or min(nb) < 0:
+            raise ValueError(f"deliver: one non-negative n_before and one last flag per row wanted, got {nb}, {lasts}")
+        pooled = state is not None
+        if pooled and bank is None:
+            raise ValueError("deliver: 24 kHz is a pure encode and carries no state: pass state=None")
+        if pooled:
+            sb = int(self.lib.smtts_deliver_state_bytes(self.h, klen))
+            if (not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 2 or int(state.shape[1]) != sb
+                    or int(state.shape[0]) < 1 or not state.is_contiguous() or state.device != self.device or state.data_ptr() % 16):
+                raise ValueError(f"deliver: state must be a contiguous, 16-byte aligned uint8 (n_slots,{sb}) tensor on the engine's "
+                                 "device (deliver_state())")
+            n_slots = int(state.shape[0])
+            sl = [int(v) for v in (slots if slots is not None else [])]
+            if len(sl) != B or len(set(sl)) != B or min(sl) < 0 or max(sl) >= n_slots:
+                raise ValueError(f"deliver: {B} distinct slots in [0, {n_slots}) wanted, got {sl}")
+        else:
+            if slots is not None or (bank is not None and (any(nb) or not all(lasts))):
+                raise ValueError("deliver: without state every row starts and ends here: no slots, n_before = 0, last = True "
+                                 "(24 kHz, a pure encode, takes any n_before and last and ignores them)")
+            n_slots, sl = 0, [0] * B
+        if bank is None:
+            counts, stride = list(ln), row
+        else:
+            counts = deliver_counts(nb, ln, lasts, up, down, width)
+            stride = max(1, deliver_max_count(row, up, down, width, pooled))
+        out = torch.empty(B, stride, dtype=(torch.float32, torch.int16, torch.uint8, torch.uint8)[enc], device=self.device)
+        tab = self._upload_i64([[s, a, n, int(f)] for s, a, n, f in zip(sl, nb, ln, lasts)])
+        self._ck(self.lib.smtts_deliver(self.h, self._stream(), _p(audio), B, row, _p(tab), _p(bank), up, down, klen, width,
+                                        _p(state) if pooled else None, n_slots, enc, _p(out), stride), "deliver")
+        return out, counts
+
     def profile(self, on, tagged: bool = False, shapes: bool = False):
         """on: False/True; tagged=True prefixes kernel names with the pipeline phase (enc, mod, dit, dec.s<i> ...); shapes=True
         (implies tagged) also appends each GEMM product's shape to its class name ("gemm3<...> 600x3840x960").

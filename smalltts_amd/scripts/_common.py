@@ -4,7 +4,7 @@ import json
 
 import numpy as np
 
-from ..audio import read_wav, resample_hq
+from ..audio import DELIVER_RATES, read_wav, resample_hq, write_wav, write_wav_pcm16
 from ..phonemes import get_token_ids, parse_tokens_arg
 
 
@@ -16,6 +16,30 @@ def add_engine_args(ap: argparse.ArgumentParser) -> None:
     ap.add_argument("--seed", type=int, default=None)
     ap.add_argument("--tokens", default=None, help="pre-tokenised phoneme ids (comma/space separated or JSON)")
     ap.add_argument("--tokenizer", default="espeak", choices=["espeak", "chars"])
+
+
+def add_delivery_args(ap: argparse.ArgumentParser) -> None:
+    """--rate / --encoding: the output leaves the engine resampled and encoded on the device (api.Delivery)."""
+    ap.add_argument("--rate", type=int, default=None, choices=DELIVER_RATES, help="output sample rate (default 24000)")
+    ap.add_argument("--encoding", default=None, choices=["pcm16", "mulaw", "alaw"],
+                    help="output WAV encoding: pcm16 (default), or G.711 mu-law / A-law (8 bits)")
+
+
+def delivery_for(args):
+    """-> None (neither flag: the output is written as it always was) or the api.Delivery the flags ask for."""
+    from ..api import Delivery
+    if args.rate is None and args.encoding is None:
+        return None
+    return Delivery(args.rate or 24_000, args.encoding or "pcm16")
+
+
+def write_output(path: str, audio, delivery=None) -> None:
+    """A synthesis result to a WAV: float samples at 24 kHz as PCM_16 (the host writer), or what a Delivery returned, as it is."""
+    a = np.asarray(audio).reshape(-1)
+    if delivery is None:
+        write_wav_pcm16(path, a, 24_000)
+    else:
+        write_wav(path, a, delivery.rate, delivery.encoding)
 
 
 def tokens_for(args, text: str):

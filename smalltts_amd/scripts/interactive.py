@@ -4,7 +4,8 @@ Type a line, get speech: every line is tokenised, given estimate_duration(line) 
 reference voice; prints generation time and the real-time factor like the reference (`gen 0.02s, 480.0x rt`).  The reference
 plays through `sounddevice` and draws with `rich`; both are optional here — without sounddevice every utterance is written to
 out/interactive_NNN.wav instead.  --stream decodes in chunks (SmallTTS.synthesize_stream) and prints the time to the first chunk next
-to the total (`gen 0.02s, first chunk 0.01s, 480.0x rt`)."""
+to the total (`gen 0.02s, first chunk 0.01s, 480.0x rt`); with it --rate / --encoding make the chunks leave the device at that rate
+and encoding (api.Delivery), and the file written is a WAV of that format."""
 import argparse
 import sys
 import time
@@ -14,8 +15,7 @@ import numpy as np
 import torch
 
 from ..api import Encoder, SmallTTS, estimate_duration
-from ..audio import write_wav_pcm16
-from ._common import add_engine_args, load_reference_wav, tokens_for
+from ._common import add_delivery_args, add_engine_args, delivery_for, load_reference_wav, tokens_for, write_output
 
 
 def main(argv=None, lines=None):
@@ -25,7 +25,11 @@ def main(argv=None, lines=None):
     ap.add_argument("--outdir", default="out")
     ap.add_argument("--stream", action="store_true", help="decode in chunks; also print the time to the first chunk")
     add_engine_args(ap)
+    add_delivery_args(ap)
     args = ap.parse_args(argv)
+    dv = delivery_for(args)
+    if dv is not None and not args.stream:
+        ap.error("--rate / --encoding belong to --stream")
     try:
         import sounddevice as sd
     except Exception:
@@ -58,14 +62,14 @@ def main(argv=None, lines=None):
         t_first = None
         if args.stream:
             chunks = []
-            for c in model.synthesize_stream(ref_latents, tokens, estimate_duration(s)):
+            for c in model.synthesize_stream(ref_latents, tokens, estimate_duration(s), **({} if dv is None else {"deliver": dv})):
                 t_first = time.perf_counter() - st if t_first is None else t_first
                 chunks.append(c)
             audio = np.concatenate(chunks, axis=1)
         else:
             audio = model.synthesize(ref_latents, tokens, estimate_duration(s))
         dt = time.perf_counter() - st
-        dur = audio.shape[-1] / 24_000.0
+        dur = audio.shape[-1] / float(24_000 if dv is None else dv.rate)
         rtf = dur / dt if dt > 0 else 0.0
         if first:
             print(f"gen {dt:.2f}s (+{time.perf_counter() - t0 - dt:.2f}s warmup), " + (f"first chunk {t_first:.2f}s, " if t_first is not None else "")
@@ -74,12 +78,12 @@ def main(argv=None, lines=None):
         else:
             print(f"gen {dt:.2f}s, " + (f"first chunk {t_first:.2f}s, " if t_first is not None else "") + f"{rtf:.1f}x rt")
         a = audio.squeeze()
-        if sd is not None:
+        if sd is not None and dv is None:
             sd.play(a, 24_000)
             sd.wait()
         else:
             path = str(Path(args.outdir) / f"interactive_{n:03d}.wav")
-            write_wav_pcm16(path, a, 24_000)
+            write_output(path, a, dv)
             print(path)
         n += 1
     return n

@@ -10,15 +10,17 @@ piece's token spans) and the join parameters, what scripts/respeak.py re-speaks 
 unvalidated on trained weights); with --words the JSON becomes {"words": [...], "takes": [{piece, winner, seed, totals}, ...]}.
 --repair [ROUNDS]: behind the sampler (and --takes) only the badly aligned words of every piece are spoken again, ROUNDS times
 (default 1), and a repaired piece is kept where it scores strictly better (api.Repair; unvalidated on trained weights like --takes);
-with --words the JSON gains "repair": [{piece, kept, bad, free, before, after}, ...], one list entry per round in each field."""
+with --words the JSON gains "repair": [{piece, kept, bad, free, before, after}, ...], one list entry per round in each field.
+--rate R / --encoding pcm16|mulaw|alaw: the joined waveform is resampled and encoded on the device (api.Delivery) and written as a WAV
+of that format; not together with --words / --srt."""
 import argparse
 import json
 from pathlib import Path
 
 from ..api import SAMPLE_RATE, Endpointing, Repair, SmallTTS, Takes, estimate_duration, format_srt, save_take, split_text, token_groups
-from ..audio import read_wav, write_wav_pcm16
+from ..audio import read_wav
 from ..phonemes import decode_token_ids, get_token_ids, parse_tokens_arg
-from ._common import add_engine_args
+from ._common import add_delivery_args, add_engine_args, delivery_for, write_output
 
 
 def group_texts(token_lists) -> list:
@@ -80,7 +82,10 @@ def parse_args(argv=None):
     ap.add_argument("--max-batch", type=int, default=8)
     ap.add_argument("--in-flight", type=int, default=3)
     add_engine_args(ap)
+    add_delivery_args(ap)
     args = ap.parse_args(argv)
+    if (args.rate is not None or args.encoding is not None) and (args.words or args.srt):
+        ap.error("--rate / --encoding do not go with --words / --srt (their files count 24 kHz samples)")
     if (args.text_file is None) == (args.tokens_file is None):
         ap.error("pass either --text-file or --tokens-file")
     if args.tokens_file and not args.durations:
@@ -108,6 +113,9 @@ def main(argv=None):
     voice = tts.encode_voice_wav(y, sr)
     kw = dict(seed=args.seed, gap_ms=args.gap_ms, fade_ms=args.fade_ms, max_batch=args.max_batch, in_flight=args.in_flight,
               trim=Endpointing(level_dbfs=args.level) if args.trim else None)
+    dv = delivery_for(args)
+    if dv is not None:
+        kw.update(deliver=dv)                              # the joined waveform leaves the device at that rate and encoding
     timed = bool(args.words or args.srt)
     if timed:
         kw.update(return_segments=True, return_words=True)
@@ -160,8 +168,8 @@ def main(argv=None):
             wpath = str(Path(args.srt).with_suffix("")) + ".words.srt"
             Path(wpath).write_text(format_srt(word_cues(words, texts)), encoding="utf-8")
             print(f"{args.srt}, {wpath}")
-    write_wav_pcm16(args.out, audio.squeeze(0), 24_000)
-    print(f"{args.out} ({audio.shape[1] / 24_000:.1f}s)")
+    write_output(args.out, audio.squeeze(0), dv)
+    print(f"{args.out} ({audio.shape[1] / (24_000 if dv is None else dv.rate):.1f}s)")
 
 
 if __name__ == "__main__":

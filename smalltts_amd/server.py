@@ -29,6 +29,13 @@ answers (`x-smtts-pcm: s16le`), rounded to nearest on the device (engine.pcm16),
 32, 32, ... frames (api.stream_chunks).  Such requests ride in batches of their own, as align=1 requests do; the dispatcher drives a
 streamed batch's chunk loop itself, so other batches are enqueued behind it.  stream=1 with trim=1 or align=1 is a 400: both need the
 whole utterance.  Without the parameter (or with stream=0) the answer is byte for byte what it was.
+Optional `rate=8000|11025|16000|22050|24000|32000|44100|48000` and `encoding=pcm16|mulaw|alaw` query parameters: the audio
+is resampled and encoded on the device (engine.deliver) behind the decode.  Whole answers are a WAV of that format (PCM16: tag 1,
+rounded to nearest on the device; G.711: tags 7 / 6, 8 bits, with a fact chunk); stream=1 answers `audio/L16; rate=R; channels=1`,
+`audio/PCMU; rate=R` or `audio/PCMA; rate=R` with `x-smtts-pcm: s16le|mulaw|alaw`, and its chunks are as long as the resampler's
+look-ahead allows (audio.deliver_counts), the last one flushing it.  One parameter alone defaults the other to 24000 / pcm16.
+`x-smtts-start`, `x-smtts-samples` and `x-smtts-words` are then given in output samples; `level=` is refused next to them (a gain
+cannot be applied to encoded samples), invalid values are a 400.  Without either parameter the answer is byte for byte what it was.
 
     python -m smalltts_amd.server --port 3000 --weights assets/smalltts.smtts
 """
@@ -224,16 +231,43 @@ def parse_stream_query(q: dict, trim=None, align: bool = False) -> bool:
     return on
 
 
+def parse_deliver_query(q: dict, trim=None):
+    """The optional `rate` / `encoding` query parameters -> None (neither given: the answer is today's) or an api.Delivery; one alone
+    defaults the other to 24000 / "pcm16".  Anything else is a 400 for the offender alone."""
+    from .api import Delivery
+    from .audio import DELIVER_RATES
+    if "rate" not in q and "encoding" not in q:
+        return None
+    rate, encoding = 24_000, "pcm16"
+    if "rate" in q:
+        raw = q["rate"][0].strip()
+        if not raw.isdigit() or int(raw) not in DELIVER_RATES:
+            raise HttpError(400, "invalid `rate`: one of " + ", ".join(str(r) for r in DELIVER_RATES))
+        rate = int(raw)
+    if "encoding" in q:
+        encoding = q["encoding"][0].strip().lower()
+        if encoding not in ("pcm16", "mulaw", "alaw"):
+            raise HttpError(400, "invalid `encoding`: pcm16, mulaw or alaw")
+    if trim is not None and trim.level_dbfs is not None:
+        raise HttpError(400, "invalid `level`: not together with rate / encoding (a gain cannot be applied to encoded samples)")
+    return Delivery(rate, encoding)
+
+
+STREAM_TYPES = {"pcm16": ("audio/L16; rate={rate}; channels=1", "s16le"), "mulaw": ("audio/PCMU; rate={rate}", "mulaw"),
+                "alaw": ("audio/PCMA; rate={rate}", "alaw")}
+
+
 def http_chunk(data: bytes) -> bytes:
     """One chunk of a Transfer-Encoding: chunked body; b"" is the terminating chunk."""
     return f"{len(data):x}\r\n".encode() + data + b"\r\n"
 
 
 class Request:
-    __slots__ = ("wav", "sr", "tokens", "duration", "seed", "trim", "align", "stream", "chunks", "future", "t_in")
+    __slots__ = ("wav", "sr", "tokens", "duration", "seed", "trim", "align", "stream", "chunks", "future", "t_in", "deliver")
 
-    def __init__(self, wav, sr, tokens, duration, seed, trim=None, align=False, stream=False):
+    def __init__(self, wav, sr, tokens, duration, seed, trim=None, align=False, stream=False, deliver=None):
         self.wav, self.sr, self.tokens, self.duration, self.seed, self.trim = wav, sr, tokens, duration, seed, trim
+        self.deliver = deliver                                 # None or an api.Delivery: the rate and encoding of the answer
         self.align = bool(align)
         self.stream = bool(stream)
         # a streamed request is answered through this queue: bytes (PCM16 of one chunk), then None; or an HttpError
@@ -357,8 +391,10 @@ class Batcher:
                 # each of them fits, and the others' batches run exactly as without the feature
                 plan = []
                 # ... and so do streamed requests: their batch is sampled once and then decoded chunk by chunk (_stream_batch)
+                # ... one batch per Delivery among them: a streamed batch delivers all its rows in one launch per chunk
                 for sel in ([j for j, r in enumerate(ok) if not r.align and not r.stream], [j for j, r in enumerate(ok) if r.align],
-                            [j for j, r in enumerate(ok) if r.stream]):
+                            *[[j for j, r in enumerate(ok) if r.stream and r.deliver == dv]
+                              for dv in dict.fromkeys(r.deliver for r in ok if r.stream)]):
                     if sel:
                         plan += [[sel[k] for k in g] for g in plan_batches([ns[j] for j in sel], [len(ok[j].tokens) for j in sel],
                                                                             [int(refs[j].shape[0]) for j in sel], self.max_pack)]
@@ -390,6 +426,9 @@ class Batcher:
                             audio, spans = rec.audio, rec.spans   # spans: (B, P, 2) per token, found on this stream behind the sampler
                             # endpoints behind the decode, on the batch's stream: one pair of launches per distinct setting
                             ends = {ep: self.eng.endpoints(audio, g_ns, ep)[:2] for ep in {r.trim for r in g_ok if r.trim is not None}}
+                            # delivery behind the decode, on the batch's stream: one launch per distinct Delivery, all rows
+                            outs = {dv: self.eng.deliver(audio, [self.eng.hop * n for n in g_ns], dv.rate, dv.encoding)
+                                    for dv in {r.deliver for r in g_ok if r.deliver is not None}}
                             ev = torch.cuda.Event()
                             ev.record()
                         self.eng.use_workspace(None)
@@ -397,7 +436,7 @@ class Batcher:
                         self.stats["batches"] += 1
                         self.stats["max_batch_seen"] = max(self.stats["max_batch_seen"], len(g_ok))
                         self.stats["max_padded_frames"] = max(self.stats.get("max_padded_frames", 0), len(g_ok) * max(g_ns))
-                        self.done_q.put((ev, audio, g_ns, g_ok, ends, spans))
+                        self.done_q.put((ev, audio, g_ns, g_ok, ends, spans, outs))
                     except Exception as e:
                         self.eng.use_workspace(None)
                         self._slots.release()
@@ -428,7 +467,11 @@ class Batcher:
     def _stream_batch(self, reqs: List[Request], refs, ns: List[int], noise):
         """A batch of streamed requests on the current stream: the sampler once (synthesize_batch without its decode), then the
         latents in chunks through engine.codec_decode_stream, one state slot per row.  Chunk k + 1 is enqueued before chunk k's
-        event is waited for; every row gets the PCM16 of its own frames of each chunk, then None."""
+        event is waited for; every row gets the PCM16 of its own frames of each chunk, then None.  With a Delivery (the same for every
+        row of the batch) each chunk goes through engine.deliver instead of engine.pcm16, one delivery slot per row: a row's chunk is
+        its frames of the decoded chunk, flagged last where the row ends in it, and its bytes are the audio.deliver_counts samples that
+        call emits for it; the concatenation is the delivery of the row's whole decode.  A row that ended earlier rides along with
+        length 0 and its output is dropped."""
         from .api import stream_chunks
         torch, eng = self.torch, self.eng
         rec = self.tts.synthesize_batch(refs, [r.tokens for r in reqs], [r.duration for r in reqs], noise=noise, frames=ns,
@@ -436,6 +479,9 @@ class Batcher:
         B, hop = len(reqs), eng.hop
         state = eng.decode_state(B)
         sizes = stream_chunks(max(ns))
+        dv = reqs[0].deliver
+        if dv is not None:
+            return self._stream_batch_delivered(reqs, rec, ns, state, sizes, dv)
         host = [torch.empty(B, hop * max(sizes), dtype=torch.int16).pin_memory() for _ in range(2)]
 
         def enqueue(k, t0):
@@ -457,16 +503,53 @@ class Batcher:
             r.chunks.put(None)
             r.future.set_result(None)
 
+    def _stream_batch_delivered(self, reqs: List[Request], rec, ns: List[int], state, sizes: List[int], dv):
+        """_stream_batch's chunk loop at a Delivery's rate and encoding (see there)."""
+        from .audio import deliver_max_count
+        torch, eng = self.torch, self.eng
+        B, hop = len(reqs), eng.hop
+        _bank, up, down, width, _klen = eng.deliver_bank(dv.rate)
+        dstate = eng.deliver_state(B, dv.rate)                 # None at 24 kHz
+        dt = torch.from_numpy(np.zeros(0, dv.dtype)).dtype
+        host = [torch.empty(B, max(1, deliver_max_count(hop * max(sizes), up, down, width, dstate is not None)), dtype=dt).pin_memory()
+                for _ in range(2)]
+
+        def enqueue(k, t0):
+            a = eng.codec_decode_stream(rec.latents[:, t0:t0 + sizes[k]], state, list(range(B)))
+            nb = [hop * min(t0, n) for n in ns]                                  # what each row's delivery stream has seen
+            ln = [hop * max(0, min(t0 + sizes[k], n) - t0) for n in ns]         # the row's frames of this chunk
+            last = [t0 + sizes[k] >= n for n in ns]
+            kw = {} if dstate is None else {"state": dstate, "slots": list(range(B)), "n_before": nb, "last": last}
+            out, counts = eng.deliver(a, ln, dv.rate, dv.encoding, **kw)
+            host[k % 2][:, :out.shape[1]].copy_(out, non_blocking=True)
+            ev = torch.cuda.Event()
+            ev.record()
+            return ev, [c if l > 0 else 0 for c, l in zip(counts, ln)]           # a row that ended earlier hands out nothing more
+        (ev, counts), t0 = enqueue(0, 0), 0
+        for k, c in enumerate(sizes):
+            nxt = enqueue(k + 1, t0 + c) if k + 1 < len(sizes) else (None, None)
+            ev.synchronize()
+            for b, r in enumerate(reqs):
+                if counts[b] > 0:
+                    a = host[k % 2][b, :counts[b]].numpy()
+                    r.chunks.put(a.astype(a.dtype.newbyteorder("<")).tobytes())
+            (ev, counts), t0 = nxt, t0 + c
+        for r in reqs:
+            r.chunks.put(None)
+            r.future.set_result(None)
+
     # -- completer thread: waits for a batch, copies out, wakes the handlers ---------------------------------------------
     def _complete(self):
         while True:
             item = self.done_q.get()
             if item is None:
                 break
-            ev, audio, ns, reqs, ends, spans = item
+            ev, audio, ns, reqs, ends, spans, outs = item
             try:
                 ev.synchronize()
-                host = audio.cpu().numpy()
+                # rows that are delivered leave in their own format; the 24 kHz fp32 batch is copied out only if a row wants it
+                host = audio.cpu().numpy() if any(r.deliver is None for r in reqs) else None
+                outs = {dv: (o.cpu().numpy(), cnt) for dv, (o, cnt) in outs.items()}
                 ends = {ep: (seg.cpu().numpy(), gain.cpu().numpy()) for ep, (seg, gain) in ends.items()}
                 spans = None if spans is None else spans.cpu().numpy()
 
@@ -475,6 +558,19 @@ class Batcher:
                     return word_times(token_groups(r.tokens), spans[b], ns[b], window=window)
 
                 for b, r in enumerate(reqs):
+                    if r.deliver is not None:                  # (samples in the Delivery's dtype, ...) in output samples
+                        dv = r.deliver
+                        o, cnt = outs[dv]
+                        words = words_of(b, r, None if r.trim is None else tuple(int(v) for v in ends[r.trim][0][b])) if r.align else None
+                        if words is not None:
+                            words = [(i, kind, dv.samples(s), dv.samples(e)) for i, kind, s, e in words]
+                        if r.trim is None:
+                            y = o[b, : cnt[b]].copy()
+                        else:                                  # the speech window, cut at its ends in output samples
+                            start, n = (int(v) for v in ends[r.trim][0][b])
+                            y = (o[b, dv.samples(start): dv.samples(start + n)].copy(), dv.samples(start))
+                        r.future.set_result((y, words) if r.align else y)
+                        continue
                     if r.trim is None:
                         y = host[b, 0, : HOP * ns[b]].copy()
                         r.future.set_result((y, words_of(b, r, None)) if r.align else y)
@@ -523,8 +619,10 @@ def make_handler(batcher: Batcher, tokenizer: str = "espeak"):
             if isinstance(item, Exception):
                 raise item if isinstance(item, HttpError) else HttpError(500, f"inference failed: {item}")
             self.send_response(200)
-            self.send_header("content-type", f"audio/L16; rate={SAMPLE_RATE}; channels=1")
-            self.send_header("x-smtts-pcm", "s16le")
+            ctype, pcm = ((f"audio/L16; rate={SAMPLE_RATE}; channels=1", "s16le") if req.deliver is None
+                          else (STREAM_TYPES[req.deliver.encoding][0].format(rate=req.deliver.rate), STREAM_TYPES[req.deliver.encoding][1]))
+            self.send_header("content-type", ctype)
+            self.send_header("x-smtts-pcm", pcm)
             self.send_header("transfer-encoding", "chunked")
             self.send_header("access-control-allow-origin", "*")
             self.end_headers()
@@ -589,19 +687,25 @@ def make_handler(batcher: Batcher, tokenizer: str = "espeak"):
                 trim = parse_trim_query(q)
                 align = parse_align_query(q, duration, tokens)
                 stream = parse_stream_query(q, trim, align)
+                deliver = parse_deliver_query(q, trim)
                 seed = int(q["seed"][0]) if "seed" in q else int.from_bytes(np.random.bytes(7), "little")
                 if stream:
-                    return self._send_stream(Request(wav, sr, tokens, duration, seed, stream=True))
-                fut = batcher.submit(Request(wav, sr, tokens, duration, seed, trim, align))
+                    return self._send_stream(Request(wav, sr, tokens, duration, seed, stream=True, deliver=deliver))
+                fut = batcher.submit(Request(wav, sr, tokens, duration, seed, trim, align, deliver=deliver))
                 audio = fut.result(timeout=120)
                 extra = {}
                 if align:
                     audio, words = audio
                     extra["x-smtts-words"] = words_header(words)
-                if trim is None:
-                    self._send(200, encode_wav(audio), "audio/wav", extra or None)
+                if deliver is not None:                        # already encoded on the device: a WAV of that format
+                    from .audio import wav_bytes
+                    enc_wav = lambda a: wav_bytes(a, deliver.rate, deliver.encoding)
                 else:
-                    self._send(200, encode_wav(audio[0]), "audio/wav",
+                    enc_wav = encode_wav
+                if trim is None:
+                    self._send(200, enc_wav(audio), "audio/wav", extra or None)
+                else:
+                    self._send(200, enc_wav(audio[0]), "audio/wav",
                                {"x-smtts-start": str(audio[1]), "x-smtts-samples": str(len(audio[0])), **extra})
             except HttpError as e:
                 self._send(e.code, e.msg.encode())
