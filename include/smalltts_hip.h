@@ -53,7 +53,7 @@ int smtts_create(int device_id, smtts_handle* out);
 int smtts_destroy(smtts_handle h);
 const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation error */
 const char* smtts_version(void);
-/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, then smtts_take_scores and smtts_take_select, then the streamed decode entries, then smtts_deliver, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
+/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, then smtts_take_scores and smtts_take_select, then the streamed decode entries, then smtts_deliver, then smtts_join_stream and smtts_peek_saturations, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
 #define SMTTS_ABI_VERSION 11
 int smtts_abi_version(void);
@@ -93,6 +93,10 @@ int smtts_set_site_precision(smtts_handle h, int site, int prec);
  * smalltts_amd/api.py does that automatically.  Synchronises the device.  Real checkpoints enter through
  * src/scripts/train/dmd2/distill.py:468-479; the SwiGLU hidden (models/backbone/dit.py:176-186) is the likeliest site. */
 int smtts_get_saturations(smtts_handle h, uint32_t* counts, int n_sites, int reset);
+/* the same counts as they stand, for callers that keep batches in flight: no device-wide wait and no reset (a reset would
+ * race the counting of the work in flight).  Whatever had COMPLETED before the call is counted in full; work still running may be
+ * counted in part.  A site that clamped keeps its count until the next smtts_get_saturations(reset = 1). */
+int smtts_peek_saturations(smtts_handle h, uint32_t* counts, int n_sites);
 const char* smtts_range_report(smtts_handle h);      /* "" when every fused FFN block was certified */
 float smtts_range_worst_bound(smtts_handle h);       /* largest certified bound of the last finalize (fp16 max: 65504) */
 int smtts_has_part(smtts_handle h, int part); /* 0 dit, 1 codec decoder, 2 codec encoder */
@@ -422,6 +426,38 @@ int smtts_endpoints(smtts_handle h, void* stream, const float* audio, int B, int
  * (it does not even round); then smtts_stitch's PCM16 arithmetic when pcm16 != 0.  seg = (0, len) with gain NULL is smtts_stitch. */
 int smtts_stitch_seg(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* seg,
                      const float* gain, const int64_t* off, const float* fade, int F, void* out, int64_t out_n, int pcm16);
+/* the running join: the joined stream of a long text as an APPEND, batch by batch, with the plan made on the device.
+ * Stream: the pieces come in order, over any number of calls on one state; piece b of a call is the window (start, n) = seg[b] of its
+ *       row, clamped into the row as smtts_stitch_seg clamps it (a negative n is 0).  A piece with n = 0 takes neither room nor a gap.
+ *       A non-empty piece is preceded by `gap` samples of +0.0 if and only if a non-empty piece came before it, in this call or in any
+ *       earlier call on the same state.  A sample of a window is ((audio[b][start + i] * gain[b]) * g), g the fade weight of
+ *       smtts_stitch over the window's own ends (F_b = min(F, n / 2)); each step is one fp32 multiply, gain == NULL skips the first (it
+ *       does not even round); then smtts_stitch's PCM16 arithmetic when pcm16 != 0 (a gap sample is then the int16 0).  This is what
+ *       api.plan_packed and smtts_stitch_seg write into one zero-filled buffer; seg = (0, len) with every n > 0 is plan_long's layout.
+ * State: caller-owned DEVICE slot of two int64, 16-byte aligned: pos = samples of the joined stream emitted so far, k = non-empty
+ *       pieces so far.  A ZERO slot starts a stream.  It belongs to the caller between calls: copy it for a snapshot.
+ * In:   audio f32 (B,1,row_stride); seg i64 (B,2) DEVICE (what smtts_endpoints left there: no host round trip); gain f32 (B) DEVICE or
+ *       NULL; fade f32 (F) DEVICE (F = 0: none, fade may be NULL); gap >= 0 samples; last (copied into dtable only).
+ * Out:  chunk[0 .. pos_after - pos_before), f32 or (pcm16 != 0) int16, chunk_cap elements: the next samples of the joined stream, the
+ *       gaps included as zeros the kernel writes (no memset of the chunk); nothing behind the chunk's length is touched.  Samples that
+ *       would land at or beyond chunk_cap are dropped; rec still carries the untruncated pos_after (sum of min(n_b, row_stride) + B *
+ *       gap elements always suffice).
+ *       off i64 (B) DEVICE: the ABSOLUTE position of piece b in the joined stream (an empty piece: where the last non-empty one ended,
+ *       as plan_packed has it).
+ *       rec i64 (4) DEVICE = (pos_before, pos_after, k_before, k_after).
+ *       dtable i64 (4) DEVICE or NULL = (slot, n_before = pos_before, len = pos_after - pos_before, last != 0): exactly the row
+ *       smtts_deliver reads, so a delivery of the chunk (B = 1, row_stride = chunk_cap) can be enqueued right behind without the host
+ *       knowing the length; `slot` is copied through.
+ * One main launch whatever B is: every workgroup derives its row's offset from the seg table and the slot itself (no prefix-sum
+ *       launch, no atomics; integer sums, so their order cannot matter).  The state is advanced, and rec / dtable are written, by a
+ *       second small launch behind the main one, so that no workgroup of the first sees a slot half written (smtts_deliver's history
+ *       launch is the precedent).  Nothing depends on scheduling: two calls on equal inputs return equal bits.
+ * Refused with 1 and a message naming the entry, nothing enqueued: a NULL handle, audio, seg, off, rec, chunk or state; a state that
+ *       is not 16-byte aligned; B outside [1, 1024]; row_stride outside [1, 2^40]; gap < 0 or gap > 2^31; F < 0, or F > 0 with fade
+ *       NULL; chunk_cap < 1. */
+int smtts_join_stream(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* seg,
+                      const float* gain, const float* fade, int F, int64_t gap, int last, int64_t* state /* DEVICE (2): pos, k */,
+                      void* chunk, int64_t chunk_cap, int pcm16, int64_t* off, int64_t* rec, int64_t* dtable, int64_t slot);
 
 /* cond_encode runs the text encoder on a side stream owned by the engine, one per caller stream (fork / join with events; default
  * on: shortest latency for one batch at a time).  Callers that keep several batches in flight on their own streams should turn it

@@ -28,6 +28,7 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_version": (cstr, []),
     "smtts_abi_version": (i32, []),
     "smtts_get_saturations": (i32, [vp, C.POINTER(C.c_uint32), i32, i32]),
+    "smtts_peek_saturations": (i32, [vp, C.POINTER(C.c_uint32), i32]),
     "smtts_range_report": (cstr, [vp]),
     "smtts_range_worst_bound": (f32, [vp]),
     "smtts_set_tensor": (i32, [vp, cstr, vp, C.POINTER(i64), i32, i32]),
@@ -77,6 +78,7 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_stitch": (i32, [vp, vp, vp, i32, i64, vp, vp, vp, i32, vp, i64, i32]),
     "smtts_endpoints": (i32, [vp, vp, vp, i32, i64, vp, i32, f32, f32, i32, i32, i32, f32, f32, f32, vp, vp, vp, vp]),
     "smtts_stitch_seg": (i32, [vp, vp, vp, i32, i64, vp, vp, vp, vp, i32, vp, i64, i32]),
+    "smtts_join_stream": (i32, [vp, vp, vp, i32, i64, vp, vp, vp, i32, i64, i32, vp, vp, i64, i32, vp, vp, vp, i64]),
     "smtts_alpha_sigma": (None, [f32, C.POINTER(f32), C.POINTER(f32)]),
     "smtts_profile_enable": (i32, [vp, i32]),
     "smtts_profile_report": (i32, [vp, C.c_char_p, sz]),

@@ -813,6 +813,38 @@ def stream_chunks(n: int, chunk_frames: Sequence[int] = (2, 4, 8, 16, 32)) -> Li
     return sizes
 
 
+def stream_groups(n: int, batch_sizes: Optional[Sequence[int]] = (1, 2, 4, 8), max_batch: int = 8) -> List[List[int]]:
+    """The groups synthesize_long_stream speaks n pieces in: consecutive pieces, the first groups of `batch_sizes` pieces each (every
+    size capped by `max_batch`), the last size repeated, the final group whatever is left (a small batch first: the first chunk
+    leaves after one piece's work; full batches later: the throughput of synthesize_long).  batch_sizes=None: plan_long's groups,
+    `max_batch` pieces each."""
+    if max_batch < 1:
+        raise ValueError("max_batch must be at least 1")
+    sizes = [int(max_batch)] if batch_sizes is None else [int(s) for s in batch_sizes]
+    if not sizes or min(sizes) < 1:
+        raise ValueError("batch_sizes must be None or a non-empty sequence of positive sizes")
+    groups: List[List[int]] = []
+    i, n = 0, int(n)
+    while i < n:
+        c = min(sizes[min(len(groups), len(sizes) - 1)], int(max_batch), n - i)
+        groups.append(list(range(i, i + c)))
+        i += c
+    return groups
+
+
+_NP_OF = {torch.float32: np.float32, torch.int64: np.int64, torch.int32: np.int32, torch.int16: np.int16, torch.uint8: np.uint8}
+
+
+class LongChunk(NamedTuple):
+    """One chunk of synthesize_long_stream: the next `audio.shape[1]` samples of the joined waveform, what one group of pieces added."""
+    audio: np.ndarray                    # (1, s_g), in the dtype synthesize_long would return
+    index: int                           # the group's number, from 0
+    offset: int                          # the chunk's first sample in the joined stream (in output samples with deliver=)
+    segments: List[tuple]                # this chunk's pieces: (offset in the stream, n, start inside the piece, gain), as synthesize_long's
+    words: Optional[List[tuple]]         # return_words: (group index, kind, start sample, end sample) of this chunk's pieces, else None
+    pieces: Optional[List["Piece"]]      # return_pieces: this chunk's Pieces, else None
+
+
 def _frames(duration_sec: float) -> int:
     return max(1, int(duration_sec * SAMPLE_RATE / HOP_SIZE))  # floor, infer/onnx.py:84
 
@@ -1273,6 +1305,42 @@ class SmallTTS:
             pending = [rec.rerun() for rec in pending]
         return pending
 
+    def _long_inputs(self, what: str, voice: Voice, text, token_lists, durations, prefix_tokens):
+        """What synthesize_long and synthesize_long_stream speak: -> (prefix tokens, every piece's tokens with the prefix in front,
+        frames per piece), from `text` (split_text, phonemised, estimate_duration) or from pre-split `token_lists` with `durations`."""
+        if voice.engine is not self.engine:
+            raise ValueError(f"{what}: the Voice belongs to another engine")
+        prefix = [int(t) for t in (prefix_tokens or [])]
+        if (text is None) == (token_lists is None):
+            raise ValueError(f"{what}: pass either text or token_lists (with durations)")
+        if text is not None:
+            from .phonemes import get_token_ids
+            pieces = split_text(text, max_tokens=198 - len(prefix))
+            token_lists = [get_token_ids(p) for p in pieces]
+            durations = [estimate_duration(p) for p in pieces]
+        else:
+            if durations is None or (not np.isscalar(durations) and len(durations) != len(token_lists)):
+                raise ValueError(f"{what}: token_lists needs one duration per piece")
+            if np.isscalar(durations):
+                durations = [float(durations)] * len(token_lists)
+        toks = [prefix + [int(t) for t in p] for p in token_lists]
+        return prefix, toks, [_frames(d) for d in durations]
+
+    def _long_calls(self, voice: Voice, toks, ns, seeds, groups, n_prefix: int, ep, al, tk, rp, return_takes: bool):
+        """One deferred synthesize_batch per group of a long text, as synthesize_long and synthesize_long_stream enqueue them:
+        -> (calls, the Alignment the batches run with or None)."""
+        al_b = al if (al is not None or (tk is None and rp is None)) else Alignment()   # takes, repair: the path leaves the prefix out, as the words do
+        # (return_takes with one take: the deferred batch returns its record either way, the flag makes it score its rows)
+        kw = ({} if al_b is None else {"align": al_b}) if tk is None else {"align": al_b, "takes": tk, "return_takes": return_takes}
+        if rp is not None:
+            kw["repair"] = rp
+        # with trim every batch enqueues its endpoints behind its decode, on its own stream: they overlap the other batches in flight
+        calls = [lambda g=g: self.synthesize_batch(None, [toks[i] for i in g], None, frames=[ns[i] for i in g], voices=[voice] * len(g),
+                                                   seeds=[seeds[i] for i in g], trim=ep, _defer=True,
+                                                   **kw, **({} if al_b is None else {"prefix_lens": [n_prefix] * len(g)}))
+                 for g in groups]
+        return calls, al_b
+
     def synthesize_long(self, voice: Voice, text: Optional[str] = None, *, token_lists: Optional[Sequence[Sequence[int]]] = None,
                         durations: Optional[Sequence[float]] = None, seed: Optional[int] = None, gap_ms: float = 120.0,
                         fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3, pcm16: bool = False,
@@ -1348,23 +1416,7 @@ class SmallTTS:
         al = as_alignment(align if align is not None else (True if return_words else None))
         if al is not None and not return_words and tk is None and rp is None:
             raise ValueError("synthesize_long: align= belongs to return_words=True")
-        if voice.engine is not self.engine:
-            raise ValueError("synthesize_long: the Voice belongs to another engine")
-        prefix = [int(t) for t in (prefix_tokens or [])]
-        if (text is None) == (token_lists is None):
-            raise ValueError("synthesize_long: pass either text or token_lists (with durations)")
-        if text is not None:
-            from .phonemes import get_token_ids
-            pieces = split_text(text, max_tokens=198 - len(prefix))
-            token_lists = [get_token_ids(p) for p in pieces]
-            durations = [estimate_duration(p) for p in pieces]
-        else:
-            if durations is None or (not np.isscalar(durations) and len(durations) != len(token_lists)):
-                raise ValueError("synthesize_long: token_lists needs one duration per piece")
-            if np.isscalar(durations):
-                durations = [float(durations)] * len(token_lists)
-        toks = [prefix + [int(t) for t in p] for p in token_lists]
-        ns = [_frames(d) for d in durations]
+        prefix, toks, ns = self._long_inputs("synthesize_long", voice, text, token_lists, durations, prefix_tokens)
         eng = self.engine
         K = 1 if tk is None else tk.k
         if tk is not None and K * max_batch > Takes.MAX_ROWS:
@@ -1384,16 +1436,7 @@ class SmallTTS:
                           [] if return_words else None, [], [], [])
         base = self._next_seed() if seed is None else int(seed)
         seeds = [piece_seed(base, i) for i in range(len(toks))]
-        al_b = al if (al is not None or (tk is None and rp is None)) else Alignment()   # takes, repair: the path leaves the prefix out, as the words do
-        # (return_takes with one take: the deferred batch returns its record either way, the flag makes it score its rows)
-        kw = ({} if al_b is None else {"align": al_b}) if tk is None else {"align": al_b, "takes": tk, "return_takes": return_takes}
-        if rp is not None:
-            kw["repair"] = rp
-        # with trim every batch enqueues its endpoints behind its decode, on its own stream: they overlap the other batches in flight
-        calls = [lambda g=g: self.synthesize_batch(None, [toks[i] for i in g], None, frames=[ns[i] for i in g], voices=[voice] * len(g),
-                                                   seeds=[seeds[i] for i in g], trim=ep, _defer=True,
-                                                   **kw, **({} if al_b is None else {"prefix_lens": [len(prefix)] * len(g)}))
-                 for g in groups]
+        calls, al_b = self._long_calls(voice, toks, ns, seeds, groups, len(prefix), ep, al, tk, rp, return_takes)
         out, segs, pending = self._join_long(calls, groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16, dv)
         words = made = taken = None
         mended = _read_repair(pending) if return_repair else None   # one small read-back for the whole text
@@ -1457,6 +1500,193 @@ class SmallTTS:
             d, cnt = eng.deliver(out.view(1, 1, S), [S], dv.rate, dv.encoding)
             return d[:, :cnt[0]].cpu().numpy(), segs, pending
         return out.cpu().numpy()[None], segs, pending
+
+    def synthesize_long_stream(self, voice: Voice, text: Optional[str] = None, *, token_lists: Optional[Sequence[Sequence[int]]] = None,
+                               durations: Optional[Sequence[float]] = None, seed: Optional[int] = None, gap_ms: float = 120.0,
+                               fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3, pcm16: bool = False,
+                               prefix_tokens: Optional[Sequence[int]] = None, trim=None, align=None, return_words: bool = False,
+                               return_pieces: bool = False, takes=None, repair=None, deliver=None,
+                               batch_sizes: Optional[Sequence[int]] = (1, 2, 4, 8)):
+        """synthesize_long handed out batch by batch: a generator of LongChunk(audio, index, offset, segments, words,
+        pieces), one per group of pieces, whose audio concatenated along axis 1 is the joined waveform.  The arguments are
+        synthesize_long's (without the return_takes / return_repair reports; the segments always come, in the chunks).
+
+        `batch_sizes`: the pieces ride in stream_groups(pieces, batch_sizes, max_batch): by default one piece first, then 2, 4, 8,
+        8, ..., so that the first chunk leaves after one small batch; None: plan_long's groups, and then the chunks' concatenation
+        IS synthesize_long(...)'s waveform for the same arguments, bit for bit, and the concatenated segments, words and pieces
+        equal its lists (another grouping changes batch shapes: equal within the engine's batch-shape tolerance).
+
+        Up to `in_flight` groups are enqueued ahead, each on its own stream and workspace under throughput tuning, as synthesize_long
+        enqueues them; the tuning and the workspace are the caller's again before every yield.  When a group's batch has completed
+        and the fp16 range guard has been read (engine.check_fp16_range(in_flight=True): no device-wide wait), its tail goes onto
+        the caller's stream: engine.join_stream appends its pieces to the joined stream, planned on the device from the table
+        engine.endpoints left there, then engine.deliver_from_table when `deliver` is given (one delivery stream for the whole text:
+        the chunks continue each other as DecodeStream's do), then ONE pinned copy of the audio with the positions and whatever the
+        flags asked for.  The host waits once, enqueues the next group and yields.  If the guard demotes a site, chunks already
+        handed out stay; the groups in flight are waited for and run again one at a time, in order, and the rest of the text runs at
+        the demoted precision.  With `deliver`, offsets, segments and words are in output samples by synthesize_long's rule; a
+        chunk's `offset` is the count of samples handed out before it (the resampler's look-ahead moves a little audio from one
+        chunk into the next; the last chunk flushes).
+
+        Closing the generator early waits for what is in flight and leaves the engine as a finished call does.  Empty text yields
+        nothing.  Arguments are checked here, before the first next()."""
+        dv = as_delivery(deliver)
+        if dv is not None and pcm16:
+            raise ValueError("synthesize_long_stream: deliver= and pcm16=True exclude each other: ask for Delivery(rate, 'pcm16')")
+        ep = as_endpointing(trim)
+        tk = as_takes(takes)
+        rp = as_repair(repair)
+        if tk is not None and tk.k == 1:
+            tk = None                                          # one take and nothing to report: the call without takes
+        al = as_alignment(align if align is not None else (True if return_words else None))
+        if al is not None and not return_words and tk is None and rp is None:
+            raise ValueError("synthesize_long_stream: align= belongs to return_words=True")
+        prefix, toks, ns = self._long_inputs("synthesize_long_stream", voice, text, token_lists, durations, prefix_tokens)
+        K = 1 if tk is None else tk.k
+        if tk is not None and K * max_batch > Takes.MAX_ROWS:
+            max_batch = Takes.MAX_ROWS // K                    # the sampler batch is K times the group
+        groups = stream_groups(len(toks), batch_sizes, max_batch)
+        if int(in_flight) < 1:
+            raise ValueError("synthesize_long_stream: in_flight must be at least 1")
+        base = (self._next_seed() if seed is None else int(seed)) if toks else 0
+        seeds = [piece_seed(base, i) for i in range(len(toks))]
+        calls, _al_b = self._long_calls(voice, toks, ns, seeds, groups, len(prefix), ep, al, tk, rp, False)
+        return self._long_chunks(calls, groups, toks, ns, seeds, len(prefix), ep, K, int(in_flight), gap_ms, fade_ms, pcm16, dv,
+                                 return_words, return_pieces)
+
+    def _long_chunks(self, calls, groups, toks, ns, seeds, n_prefix: int, ep: Optional["Endpointing"], K: int, in_flight: int,
+                     gap_ms: float, fade_ms: float, pcm16: bool, dv: Optional["Delivery"], return_words: bool, return_pieces: bool):
+        """synthesize_long_stream's generator: the groups' deferred batches `calls`, enqueued ahead, verified, joined and handed out."""
+        if not calls:
+            return
+        from .audio import deliver_counts
+        eng = self.engine
+        dev = eng.device
+        cur = torch.cuda.current_stream(dev)
+        L = max(1, min(in_flight, len(calls)))
+        streams = [torch.cuda.Stream(dev) for _ in range(L)]
+        for st in streams:
+            st.wait_stream(cur)
+        gap = max(0, int(round(gap_ms * SAMPLE_RATE / 1000.0)))
+        w = fade_table(fade_ms)
+        fade = torch.from_numpy(w).to(dev) if w.size else None
+        jstate = eng.join_state()
+        bank_rate = dv is not None and dv.ratio != (1, 1)
+        dstate = eng.deliver_state(1, dv.rate) if bank_rate else None
+        if bank_rate:
+            _bank, up, down, width, _klen = eng.deliver_bank(dv.rate)
+        queue: Dict[int, list] = {}                            # group -> [record, its event (None: run again on the caller's stream)]
+
+        def enqueue(i: int) -> None:
+            # throughput tuning and the named workspace around this one enqueue, as _run_in_flight sets them: never held across a yield
+            prev_tuning = eng.set_tuning("throughput")
+            try:
+                with torch.cuda.stream(streams[i % L]):
+                    eng.use_workspace(f"batch{i % L}")
+                    rec = calls[i]()
+                    ev = torch.cuda.Event()
+                    ev.record()
+            finally:
+                eng.use_workspace(None)
+                eng.set_tuning(prev_tuning)
+            queue[i] = [rec, ev]
+
+        def tail(gi: int, rec: _Batch):
+            """Group gi's join, delivery and ONE copy out, on the caller's stream -> (host bytes, the layout to read them by)."""
+            g = groups[gi]
+            if ep is None:
+                seg, gain = eng._upload_i64([[0, HOP_SIZE * n] for n in rec.ns]), None
+            else:
+                seg, gain = rec.seg, (rec.gain if ep.level_dbfs is not None else None)
+            cap = sum(HOP_SIZE * n for n in rec.ns) + len(g) * gap       # no window is longer than its row's hop * n samples
+            last = gi == len(groups) - 1
+            chunk, off, pos, dtable = eng.join_stream(rec.audio, seg, gain, fade, gap, jstate, last=last, pcm16=pcm16, cap=cap,
+                                                      deliver_slot=0)
+            audio = chunk if dv is None else eng.deliver_from_table(chunk, dtable, dv.rate, dv.encoding, state=dstate)
+            parts = [("off", off), ("pos", pos)]
+            if ep is not None:
+                parts += [("seg", rec.seg), ("gain", rec.gain)]
+            if return_words:
+                parts.append(("spans", rec.spans))
+            if return_pieces:
+                parts.append(("latents", rec.latents))
+                if rec.winner is not None:
+                    parts.append(("winner", rec.winner))
+            parts.append(("audio", audio))                     # 8-byte items first, the audio last: every part starts aligned
+            packed = torch.cat([t.reshape(-1).view(torch.uint8) for _name, t in parts])
+            host = torch.empty(packed.numel(), dtype=torch.uint8, pin_memory=True)
+            host.copy_(packed, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            done.synchronize()                                 # the one wait of the tail
+            flat, res, at = host.numpy().copy(), {}, 0
+            for name, t in parts:
+                nb = t.numel() * t.element_size()
+                res[name] = flat[at: at + nb].view(_NP_OF[t.dtype]).reshape(tuple(t.shape))
+                at += nb
+            return res, last
+
+        n_words, sent, nxt = 0, 0, 0
+        try:
+            while nxt < L:
+                enqueue(nxt)
+                nxt += 1
+            for gi, g in enumerate(groups):
+                rec, ev = queue[gi]
+                with torch.cuda.stream(cur):                   # (the consumer may have changed streams between two chunks)
+                    if ev is not None:
+                        ev.synchronize()
+                        if eng.check_fp16_range("synthesize_long_stream", in_flight=True):
+                            # clipped somewhere: what was handed out stays; everything enqueued and not handed out again, one at a time,
+                            # in order, on the caller's stream at the demoted precision (the joined stream only ever advances by
+                            # verified batches)
+                            for st in streams:
+                                st.synchronize()
+                            eng.check_fp16_range("synthesize_long_stream")   # all of it has finished: the counters start from zero again
+                            for j in sorted(queue):
+                                queue[j] = [queue[j][0].rerun(), None]
+                            rec = queue[gi][0]
+                        else:
+                            cur.wait_event(ev)
+                    res, last = tail(gi, rec)
+                del queue[gi]
+                if nxt < len(calls):
+                    enqueue(nxt)
+                    nxt += 1
+                pos0, pos1 = int(res["pos"][0]), int(res["pos"][1])
+                count = pos1 - pos0 if not bank_rate else deliver_counts(pos0, pos1 - pos0, last, up, down, width)
+                audio = res["audio"].reshape(1, -1)[:, :count]
+                segs, words, made = [], ([] if return_words else None), ([] if return_pieces else None)
+                for r, i in enumerate(g):
+                    off_i = int(res["off"][r])
+                    if ep is None:
+                        segs.append((off_i, HOP_SIZE * ns[i], 0, 1.0))
+                    else:
+                        segs.append((off_i, int(res["seg"][r, 1]), int(res["seg"][r, 0]), float(res["gain"][r])))
+                    if return_words:
+                        words += word_times(token_groups(toks[i][n_prefix:]), res["spans"][r], ns[i], token0=n_prefix,
+                                            window=(segs[-1][2], segs[-1][1]) if ep is not None else None, offset=off_i,
+                                            index0=n_words + len(words))
+                    if return_pieces:
+                        spoken = take_seed(seeds[i], int(res["winner"][r])) if "winner" in res else seeds[i]
+                        made.append(Piece(toks[i], n_prefix, res["latents"][r, : ns[i]], spoken,
+                                          res["spans"][r, : len(toks[i])] if return_words else None))
+                if return_words:
+                    n_words += len(words)
+                if dv is not None:                             # positions in output samples, synthesize_long's rule
+                    segs = [(dv.samples(o), dv.samples(o + n) - dv.samples(o), dv.samples(st), gn) for o, n, st, gn in segs]
+                    words = None if words is None else [(i, kind, dv.samples(a), dv.samples(b)) for i, kind, a, b in words]
+                chunk = LongChunk(audio, gi, pos0 if dv is None else sent, segs, words, made)
+                sent += count
+                yield chunk
+        finally:
+            # a consumer that stopped listening, an error, or the end: wait for what is in flight and leave the engine as a finished
+            # call does (the tuning and the workspace are the caller's already: they are never held across a yield)
+            queue.clear()
+            for st in streams:
+                st.synchronize()
+                cur.wait_stream(st)
+            eng.check_fp16_range("synthesize_long_stream")
 
     def render_long(self, pieces, *, gap_ms: float = 120.0, fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3,
                     pcm16: bool = False, trim=None, return_segments: bool = False):

@@ -88,6 +88,47 @@ def write_wav(path: str, samples: np.ndarray, sample_rate: int, encoding: str = 
         f.write(wav_bytes(samples, sample_rate, encoding))
 
 
+class WavStreamWriter:
+    """write_wav for samples that arrive in chunks (api.SmallTTS.synthesize_long_stream): the header goes out first with zero
+    sizes, every write() appends ALREADY ENCODED samples, and close() pads to an even length and patches the RIFF and data sizes
+    and, for G.711 and f32, the fact chunk's sample count.  The closed file equals wav_bytes of the concatenation byte for byte.
+    The file must be seekable.  Also a context manager."""
+
+    def __init__(self, path: str, sample_rate: int, encoding: str = "pcm16") -> None:
+        if encoding not in WAV_TAGS:
+            raise ValueError(f"encoding must be one of {DELIVER_ENCODINGS}, got {encoding!r}")
+        self.sample_rate, self.encoding = int(sample_rate), encoding
+        self.n_samples = self.n_bytes = 0
+        self._f = open(path, "wb")
+        self._f.write(_wav_header(0, 0, self.sample_rate, encoding))
+
+    def write(self, samples: np.ndarray) -> None:
+        a = np.asarray(samples).reshape(-1)
+        want = DELIVER_DTYPES[self.encoding]
+        if a.dtype != want:
+            raise ValueError(f"WavStreamWriter: {self.encoding} samples must be {np.dtype(want).name}, got {a.dtype}")
+        data = a.astype(a.dtype.newbyteorder("<")).tobytes()
+        self._f.write(data)
+        self.n_samples += a.size
+        self.n_bytes += len(data)
+
+    def close(self) -> None:
+        if self._f is None:
+            return
+        if self.n_bytes & 1:
+            self._f.write(b"\0")
+        self._f.seek(0)
+        self._f.write(_wav_header(self.n_bytes, self.n_samples, self.sample_rate, self.encoding))
+        self._f.close()
+        self._f = None
+
+    def __enter__(self) -> "WavStreamWriter":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+
 def g711_decode(codes: np.ndarray, law: str) -> np.ndarray:
     """G.711 codes (uint8) -> int16 PCM, the CCITT / Sun g711.c decoders (audioop.ulaw2lin / alaw2lin at width 2)."""
     c = np.asarray(codes, np.uint8).astype(np.int32)

@@ -70,6 +70,10 @@ int smtts_get_saturations(smtts_handle h, uint32_t* counts, int n_sites, int res
     if (!counts || n_sites < 0) return E.fail("get_saturations: bad arguments");
     return E.get_saturations(counts, n_sites, reset != 0);
 }
+int smtts_peek_saturations(smtts_handle h, uint32_t* counts, int n_sites) { NULLCHK;
+    if (!counts || n_sites < 0) return E.fail("peek_saturations: bad arguments");
+    return E.peek_saturations(counts, n_sites);
+}
 const char* smtts_range_report(smtts_handle h) {
     if (!h) { g_create_err = std::string(__func__) + ": null handle"; return ""; }
     return E.range_report().c_str();

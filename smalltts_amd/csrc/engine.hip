@@ -92,6 +92,14 @@ int Engine::get_saturations(unsigned* out, int n, bool reset) {
     return 0;
 }
 
+int Engine::peek_saturations(unsigned* out, int n) {
+    HIPC(hipSetDevice(device_));
+    unsigned dev[SITE_COUNT] = {};
+    if (sat_) HIPC(hipMemcpy(dev, sat_, sizeof dev, hipMemcpyDeviceToHost));   // no device-wide wait, no reset: work in flight goes on counting
+    for (int i = 0; i < n; ++i) out[i] = i < SITE_COUNT ? dev[i] + sat_static_[i] : 0u;
+    return 0;
+}
+
 void Engine::set_tuning(int mode) {
     if (mode == TUNE_THROUGHPUT) {
         if (tuning_ != TUNE_THROUGHPUT) dual_stream_latency_ = dual_stream_;

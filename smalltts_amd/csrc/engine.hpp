@@ -248,6 +248,9 @@ class Engine {
     // below the fp16 range at finalize() (those kernels do not count at run time: they are VALU-bound, see finalize_codec).
     // Synchronises the device.
     int get_saturations(unsigned* out, int n, bool reset);
+    // the same counts as they stand, while other streams go on working: no device-wide wait and no reset (a reset would race the
+    // counting of the batches in flight).  What has COMPLETED before the call is counted in full; work in flight may be counted in part.
+    int peek_saturations(unsigned* out, int n);
     const std::string& range_report() const { return range_report_; }
     float range_worst() const { return range_worst_; }
 

@@ -182,12 +182,22 @@ class HipEngine:
         self._ck(self.lib.smtts_get_saturations(self.h, buf, n, int(bool(reset))), "get_saturations")
         return {name: int(buf[i]) for name, i in SITES.items()}
 
-    def check_fp16_range(self, what: str = "") -> list:
+    def saturations_now(self) -> Dict[str, int]:
+        """saturations() as the counters stand, next to batches in flight on other streams: no device-wide wait and no reset
+        (smtts_peek_saturations).  Work that had completed before the call is counted in full."""
+        n = len(SITES)
+        buf = (C.c_uint32 * n)()
+        self._ck(self.lib.smtts_peek_saturations(self.h, buf, n), "peek_saturations")
+        return {name: int(buf[i]) for name, i in SITES.items()}
+
+    def check_fp16_range(self, what: str = "", *, in_flight: bool = False) -> list:
         """Reads the saturation counters; every site that clamped is switched to split-bf16 (fp32 range) for the rest of this
         engine's life and a RuntimeWarning says so.  Returns the sites demoted by THIS call: the caller should run the
-        operation again — its results were clipped."""
+        operation again — its results were clipped.  in_flight=True reads with saturations_now(): the caller has waited for the work
+        it verifies and keeps other batches running (a clamp of theirs, seen early, demotes as well)."""
         import warnings
-        hit = {k: v for k, v in self.saturations(reset=True).items() if v and k not in self._demoted}
+        counts = self.saturations_now() if in_flight else self.saturations(reset=True)
+        hit = {k: v for k, v in counts.items() if v and k not in self._demoted}
         for site, count in hit.items():
             rep = self.lib.smtts_range_report(self.h).decode() if site == "codec_ffn" else ""
             self._demoted[site] = f"{count} clamp(s)" + (f"; {rep}" if rep else "")
@@ -855,6 +865,51 @@ class HipEngine:
                                            _p(fade) if F else None, F, _p(out), out.numel(), int(out.dtype == torch.int16)), "stitch_seg")
         return out
 
+    # ---- the running join: the joined stream handed out batch by batch (include/smalltts_hip.h smtts_join_stream) ----
+    def join_state(self) -> torch.Tensor:
+        """A zeroed join slot: int64 (2,) = (pos, k) on the device, the start of a joined stream.  state.clone() / .copy_() snapshot
+        and rewind it."""
+        return torch.zeros(2, dtype=torch.int64, device=self.device)
+
+    def join_stream(self, audio: torch.Tensor, seg: torch.Tensor, gain: Optional[torch.Tensor], fade: Optional[torch.Tensor], gap: int,
+                    state: torch.Tensor, *, last: bool, pcm16: bool, cap: Optional[int] = None, deliver_slot: Optional[int] = None):
+        """The next pieces of a joined stream (smtts_join_stream): audio (B,1,S) fp32, seg int64 (B,2) = (start, n) and gain fp32 (B)
+        or None on the device as endpoints() returns them, fade the (F,) fp32 table on the device or None, gap samples between
+        non-empty pieces, state = join_state() carried from call to call.  -> (chunk, off, rec, dtable), all on the device: chunk
+        (cap,) fp32 or int16 holds the stream's next rec[1] - rec[0] samples, off (B,) the pieces' absolute positions, rec (4,) =
+        (pos before, pos after, k before, k after), dtable (4,) = (deliver_slot or 0, pos before, length, last), the row
+        deliver_from_table reads.  cap defaults to B * (S + gap), which no table can overrun.  off, rec and dtable are views of ONE
+        int64 tensor (chunk-independent), so a caller copies them out together.  On the current stream, no synchronisation."""
+        if audio.dim() != 3 or audio.shape[1] != 1:
+            raise ValueError("join_stream: audio must be (B,1,S)")
+        B, row = int(audio.shape[0]), int(audio.shape[-1])
+        if audio.dtype != torch.float32 or not audio.is_contiguous() or audio.device != self.device or B < 1 or row < 1:
+            raise ValueError("join_stream: audio must be contiguous fp32 (B,1,S) on the engine's device")
+        if seg.dtype != torch.int64 or tuple(seg.shape) != (B, 2) or not seg.is_contiguous() or seg.device != self.device:
+            raise ValueError("join_stream: seg must be a contiguous int64 (B,2) tensor on the engine's device")
+        if gain is not None and (gain.dtype != torch.float32 or tuple(gain.shape) != (B,) or not gain.is_contiguous()
+                                 or gain.device != self.device):
+            raise ValueError("join_stream: gain must be a contiguous fp32 (B,) tensor on the engine's device, or None")
+        F = 0 if fade is None else int(fade.numel())
+        if F and (fade.dtype != torch.float32 or fade.device != self.device or not fade.is_contiguous()):
+            raise ValueError("join_stream: fade must be a contiguous fp32 tensor on the engine's device")
+        if (not isinstance(state, torch.Tensor) or state.dtype != torch.int64 or tuple(state.shape) != (2,) or not state.is_contiguous()
+                or state.device != self.device or state.data_ptr() % 16):
+            raise ValueError("join_stream: state must be a contiguous, 16-byte aligned int64 (2,) tensor on the engine's device (join_state())")
+        gap = int(gap)
+        if gap < 0:
+            raise ValueError("join_stream: gap must not be negative")
+        cap = B * (row + gap) if cap is None else int(cap)
+        if cap < 1:
+            raise ValueError("join_stream: cap must be at least 1")
+        chunk = torch.empty(cap, dtype=torch.int16 if pcm16 else torch.float32, device=self.device)
+        small = torch.empty(B + 8, dtype=torch.int64, device=self.device)
+        off, rec, dtable = small[:B], small[B: B + 4], small[B + 4:]
+        self._ck(self.lib.smtts_join_stream(self.h, self._stream(), _p(audio), B, row, _p(seg), _p(gain), _p(fade) if F else None, F, gap,
+                                            int(bool(last)), _p(state), _p(chunk), cap, int(bool(pcm16)), _p(off), _p(rec), _p(dtable),
+                                            int(deliver_slot or 0)), "join_stream")
+        return chunk, off, rec, dtable
+
     # ---- device-side audio front / back end ---------------------------------------------------------
     def resample(self, audio, sr: int, target: int = 24_000) -> torch.Tensor:
         """(samples,) or (channels, samples) float -> resampled on the device (same bank as audio.resample_hq)."""
@@ -973,6 +1028,44 @@ class HipEngine:
         self._ck(self.lib.smtts_deliver(self.h, self._stream(), _p(audio), B, row, _p(tab), _p(bank), up, down, klen, width,
                                         _p(state) if pooled else None, n_slots, enc, _p(out), stride), "deliver")
         return out, counts
+
+    def deliver_from_table(self, chunk: torch.Tensor, dtable: torch.Tensor, rate: int, encoding: str = "f32", *,
+                           state: Optional[torch.Tensor] = None, zeros: Optional[int] = None) -> torch.Tensor:
+        """deliver() for ONE row whose table row already lies on the device: chunk (cap,) fp32 and dtable int64 (4,) = (slot, n_before,
+        len, last) as join_stream() wrote them, so the delivery is enqueued right behind the join without the host knowing the
+        length.  -> out (1, audio.deliver_max_count(cap, ...)) in the encoding's dtype on the device; the row's count follows
+        afterwards from join_stream's rec with audio.deliver_counts(rec[0], rec[1] - rec[0], last, up, down, width): integers alone
+        (at 24 kHz: rec[1] - rec[0]).  state = deliver_state(...) carries the stream from chunk to chunk through the slot dtable names
+        (clamped into the pool by the kernel); state=None: the chunk starts and ends a stream of its own (at 24 kHz, a pure encode,
+        there is nothing to carry and state must be None).  On the current stream, no synchronisation."""
+        from .audio import DELIVER_ENCODINGS, deliver_max_count
+        if encoding not in DELIVER_ENCODINGS:
+            raise ValueError(f"deliver_from_table: encoding must be one of {DELIVER_ENCODINGS}, got {encoding!r}")
+        enc = DELIVER_ENCODINGS.index(encoding)
+        bank, up, down, width, klen = self.deliver_bank(rate, zeros)
+        if (not isinstance(chunk, torch.Tensor) or chunk.dtype != torch.float32 or chunk.dim() != 1 or not chunk.is_contiguous()
+                or chunk.device != self.device or int(chunk.numel()) < 1):
+            raise ValueError("deliver_from_table: chunk must be a contiguous 1-D fp32 tensor on the engine's device")
+        if (not isinstance(dtable, torch.Tensor) or dtable.dtype != torch.int64 or tuple(dtable.shape) != (4,) or not dtable.is_contiguous()
+                or dtable.device != self.device):
+            raise ValueError("deliver_from_table: dtable must be a contiguous int64 (4,) tensor on the engine's device")
+        row = int(chunk.numel())
+        pooled = state is not None
+        if pooled and bank is None:
+            raise ValueError("deliver_from_table: 24 kHz is a pure encode and carries no state: pass state=None")
+        n_slots = 0
+        if pooled:
+            sb = int(self.lib.smtts_deliver_state_bytes(self.h, klen))
+            if (not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 2 or int(state.shape[1]) != sb
+                    or int(state.shape[0]) < 1 or not state.is_contiguous() or state.device != self.device or state.data_ptr() % 16):
+                raise ValueError(f"deliver_from_table: state must be a contiguous, 16-byte aligned uint8 (n_slots,{sb}) tensor on the "
+                                 "engine's device (deliver_state())")
+            n_slots = int(state.shape[0])
+        stride = row if bank is None else max(1, deliver_max_count(row, up, down, width, pooled))
+        out = torch.empty(1, stride, dtype=(torch.float32, torch.int16, torch.uint8, torch.uint8)[enc], device=self.device)
+        self._ck(self.lib.smtts_deliver(self.h, self._stream(), _p(chunk), 1, row, _p(dtable), _p(bank), up, down, klen, width,
+                                        _p(state) if pooled else None, n_slots, enc, _p(out), stride), "deliver")
+        return out
 
     def profile(self, on, tagged: bool = False, shapes: bool = False):
         """on: False/True; tagged=True prefixes kernel names with the pipeline phase (enc, mod, dit, dec.s<i> ...); shapes=True

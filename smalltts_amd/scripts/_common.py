@@ -33,6 +33,12 @@ def delivery_for(args):
     return Delivery(args.rate or 24_000, args.encoding or "pcm16")
 
 
+def pcm16_host(audio) -> np.ndarray:
+    """float [-1, 1] -> int16 by write_wav_pcm16's arithmetic (clamp, x 32767, round to nearest even)."""
+    a = np.asarray(audio, dtype=np.float32).reshape(-1)
+    return np.round(np.clip(a, -1.0, 1.0) * 32767.0).astype(np.int16)
+
+
 def write_output(path: str, audio, delivery=None) -> None:
     """A synthesis result to a WAV: float samples at 24 kHz as PCM_16 (the host writer), or what a Delivery returned, as it is."""
     a = np.asarray(audio).reshape(-1)

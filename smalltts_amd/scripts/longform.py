@@ -12,15 +12,22 @@ unvalidated on trained weights); with --words the JSON becomes {"words": [...], 
 (default 1), and a repaired piece is kept where it scores strictly better (api.Repair; unvalidated on trained weights like --takes);
 with --words the JSON gains "repair": [{piece, kept, bad, free, before, after}, ...], one list entry per round in each field.
 --rate R / --encoding pcm16|mulaw|alaw: the joined waveform is resampled and encoded on the device (api.Delivery) and written as a WAV
-of that format; not together with --words / --srt."""
+of that format; not together with --words / --srt.
+--stream: the WAV is written while the text is still being spoken (api.SmallTTS.synthesize_long_stream, audio.WavStreamWriter): one
+chunk per group of pieces, the first after one piece's work; the time to the first chunk and the total are printed.  --batch-sizes
+1,2,4,8 (the default ramp) or `none` (groups of --max-batch, the file --stream-less runs write, byte for byte).  --words / --srt /
+--take are written at the end from what the chunks carried; the per-piece reports of --takes / --repair are not streamed."""
 import argparse
 import json
+import time
 from pathlib import Path
 
+import numpy as np
+
 from ..api import SAMPLE_RATE, Endpointing, Repair, SmallTTS, Takes, estimate_duration, format_srt, save_take, split_text, token_groups
-from ..audio import read_wav
+from ..audio import WavStreamWriter, read_wav
 from ..phonemes import decode_token_ids, get_token_ids, parse_tokens_arg
-from ._common import add_delivery_args, add_engine_args, delivery_for, write_output
+from ._common import add_delivery_args, add_engine_args, delivery_for, pcm16_host, write_output
 
 
 def group_texts(token_lists) -> list:
@@ -61,6 +68,30 @@ def word_cues(words, texts) -> list:
     return [(s, e, ph) for (_gi, _kind, s, e), (_pi, _k, ph) in zip(words, texts)]
 
 
+def stream_to_wav(tts, args, dv, voice, **kw):
+    """--stream: synthesize_long_stream into args.out as the chunks arrive -> what synthesize_long would have returned for `kw`
+    (the waveform is NOT kept: a (1, total samples) view of one zero stands in for its shape)."""
+    timed, want_pieces = kw.pop("return_segments", False), kw.get("return_pieces", False)
+    for k in ("return_takes", "return_repair"):
+        kw.pop(k, None)
+    segments, words, made, total = [], [], [], 0
+    t0 = time.perf_counter()
+    first = None
+    with WavStreamWriter(args.out, 24_000 if dv is None else dv.rate, "pcm16" if dv is None else dv.encoding) as wav:
+        for chunk in tts.synthesize_long_stream(voice, batch_sizes=args.batch_sizes, **kw):
+            if first is None:
+                first = time.perf_counter() - t0
+            wav.write(pcm16_host(chunk.audio) if dv is None else chunk.audio)
+            total += chunk.audio.shape[1]
+            segments += chunk.segments
+            words += chunk.words or []
+            made += chunk.pieces or []
+    print(f"first chunk after {0.0 if first is None else first:.3f}s, all of it after {time.perf_counter() - t0:.3f}s")
+    audio = np.broadcast_to(np.zeros((), np.float32), (1, total))
+    res = (audio,) + ((segments, words) if timed else ()) + ((made,) if want_pieces else ())
+    return res if len(res) > 1 else audio
+
+
 def parse_args(argv=None):
     """The command line -> its namespace (argument errors exit, as argparse does)."""
     ap = argparse.ArgumentParser()
@@ -81,9 +112,23 @@ def parse_args(argv=None):
                     help=f"speak only the badly aligned words of every piece again, ROUNDS times (1..{Repair.MAX_ROUNDS}, default 1)")
     ap.add_argument("--max-batch", type=int, default=8)
     ap.add_argument("--in-flight", type=int, default=3)
+    ap.add_argument("--stream", action="store_true", help="write the WAV chunk by chunk while the text is being spoken")
+    ap.add_argument("--batch-sizes", default=None, metavar="N,N,...|none",
+                    help="with --stream: pieces per group, the last value repeated (default 1,2,4,8); none = groups of --max-batch")
     add_engine_args(ap)
     add_delivery_args(ap)
     args = ap.parse_args(argv)
+    if args.batch_sizes is not None and not args.stream:
+        ap.error("--batch-sizes needs --stream")
+    if args.batch_sizes is not None and args.batch_sizes.strip().lower() != "none":
+        try:
+            args.batch_sizes = tuple(int(v) for v in args.batch_sizes.replace(",", " ").split())
+        except ValueError:
+            ap.error("--batch-sizes takes positive integers, comma-separated, or none")
+        if not args.batch_sizes or min(args.batch_sizes) < 1:
+            ap.error("--batch-sizes takes positive integers, comma-separated, or none")
+    elif args.stream:
+        args.batch_sizes = (1, 2, 4, 8) if args.batch_sizes is None else None
     if (args.rate is not None or args.encoding is not None) and (args.words or args.srt):
         ap.error("--rate / --encoding do not go with --words / --srt (their files count 24 kHz samples)")
     if (args.text_file is None) == (args.tokens_file is None):
@@ -125,6 +170,7 @@ def main(argv=None):
         kw.update(takes=args.takes, return_takes=True)
     if args.repair is not None:
         kw.update(repair=args.repair, return_repair=True)
+    speak = tts.synthesize_long if not args.stream else (lambda *a, **k: stream_to_wav(tts, args, dv, *a, **k))
     if args.tokens_file:
         with open(args.tokens_file) as f:
             token_lists = [parse_tokens_arg(line) for line in f if line.strip()]
@@ -133,7 +179,7 @@ def main(argv=None):
             durs = durs * len(token_lists)
         print(f"generating {len(token_lists)} pieces")
         piece_texts = [decode_token_ids(t) for t in token_lists]
-        audio = tts.synthesize_long(voice, token_lists=token_lists, durations=durs, **kw)
+        audio = speak(voice, token_lists=token_lists, durations=durs, **kw)
     else:
         with open(args.text_file) as f:
             text = f.read()
@@ -141,8 +187,10 @@ def main(argv=None):
         pieces = split_text(text, count_tokens=lambda t: len(tok(t)))
         print(f"generating {len(pieces)} pieces")
         token_lists, piece_texts = [tok(p) for p in pieces], pieces
-        audio = tts.synthesize_long(voice, token_lists=token_lists, durations=[estimate_duration(p) for p in pieces], **kw)
+        audio = speak(voice, token_lists=token_lists, durations=[estimate_duration(p) for p in pieces], **kw)
     chosen = mended = None
+    if args.stream:
+        args.takes = args.repair = None                    # (their reports are not streamed)
     if args.repair is not None:                            # (the very last element)
         audio, mended = (audio[:-1] if len(audio) > 2 else audio[0]), audio[-1]
         print("repaired: " + " ".join(str(int(sum(kept))) for kept, _counts, _before, _after in mended))
@@ -168,7 +216,8 @@ def main(argv=None):
             wpath = str(Path(args.srt).with_suffix("")) + ".words.srt"
             Path(wpath).write_text(format_srt(word_cues(words, texts)), encoding="utf-8")
             print(f"{args.srt}, {wpath}")
-    write_output(args.out, audio.squeeze(0), dv)
+    if not args.stream:                                    # (streamed: the file is complete already)
+        write_output(args.out, audio.squeeze(0), dv)
     print(f"{args.out} ({audio.shape[1] / (24_000 if dv is None else dv.rate):.1f}s)")
 
 
