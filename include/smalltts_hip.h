@@ -99,7 +99,7 @@ int smtts_get_saturations(smtts_handle h, uint32_t* counts, int n_sites, int res
 int smtts_peek_saturations(smtts_handle h, uint32_t* counts, int n_sites);
 const char* smtts_range_report(smtts_handle h);      /* "" when every fused FFN block was certified */
 float smtts_range_worst_bound(smtts_handle h);       /* largest certified bound of the last finalize (fp16 max: 65504) */
-int smtts_has_part(smtts_handle h, int part); /* 0 dit, 1 codec decoder, 2 codec encoder */
+int smtts_has_part(smtts_handle h, int part); /* 0 dit, 1 codec decoder, 2 codec encoder, 3 latent phoneme recogniser (asr.* tensors) */
 
 /* ---- condition encoder ---------------------------------------------------------------------- */
 size_t smtts_cond_workspace_bytes(smtts_handle h, int B, int R, int P);
@@ -268,6 +268,35 @@ int smtts_repair_keep(smtts_handle h, void* stream, int G, int N, int P, const f
                       const int32_t* counts, const int32_t* feat_cur, const int32_t* feat_new, float* x_cur, const float* x_new,
                       int32_t* spans_cur /* or NULL */, const int32_t* spans_new, float* mass_cur /* or NULL */, const float* mass_new,
                       float* total_out, int32_t* feat_out, int32_t* kept);
+
+/* ---- CTC score (DESIGN.md '8i. CTC score'): the latent phoneme recogniser and its CTC on the device -------------------------------
+ * smtts_asr_logprobs replaces the reference's ASR(64).forward (src/smalltts/models/asr.py:41-52: upsample x4, a 7-layer Conformer at
+ * width 64 with 16 heads, FFN 1024 and depthwise kernel 9, Linear 64 -> 198, log-softmax) for an engine that was given the asr.* tensors
+ * (smtts_has_part(h, 3)).  x f32 (B,N,64) latents, n_len i32 (B) frames per row (clamped into [0, N]), both DEVICE -> logp f32
+ * (B, 4 N, 198).  Row b has t_b = 4 n_b frames; every row is computed as if it were alone in its batch (attention keys and depthwise-conv
+ * taps outside [0, t_b) do not exist), so nothing behind n_len[b] of x reaches a result, and logp at and behind frame t_b is written as
+ * 0.0.  fp32 operands and accumulation; no atomics: two runs, alone or inside any batch, return the same bits.  ws: at least
+ * smtts_asr_workspace_bytes(h, B, N) bytes, 256-byte aligned, contents irrelevant; x, n_len, logp 4-byte aligned.  1 <= B <= 64 and
+ * 1 <= N <= 225, anything else (and an engine without the part) is an error; the size query returns 0 outside the range.
+ *
+ * smtts_ctc_score replaces CTCLoss(blank = 0) of the reference's distillation loss (src/scripts/train/dmd2/distill.py:344-348) as a
+ * score: logp f32 (B,T,C), t_len i32 (B) (clamped into [0, T]), tokens i32 (B,P), p0 / p1 i32 (B) (clamped into [0, P] exactly as
+ * smtts_align_path clamps them), all DEVICE.  The target of row b is tokens[b][p0 : p1), L = p1 - p0, every token clamped into [1, C) so
+ * that no index leaves the row.  -> nll f32 (B) = F.ctc_loss(reduction = 'none', zero_infinity = False) of the row: the forward
+ * recursion over the 2 L + 1 extended states in fp32, logaddexp with the maximum taken first (-inf, never NaN, when all operands are
+ * -inf).  +inf for t_len == 0, for L <= 0 and for an infeasible row (t_len < L + repeats); a NaN that the recursion reads gives NaN.
+ * 1 <= B <= 65536, 1 <= T <= 65536, 1 <= P <= 198, 2 <= C <= 256.  Needs no weights: works on any handle.
+ *
+ * smtts_ctc_greedy: per frame t < t_len[b] the class with the largest logp (the lowest class on ties; NaN is never the largest), equal
+ * neighbours collapsed, class 0 dropped -> ids i32 (B,T) with zeros behind the count, n_ids i32 (B).  1 <= T <= 4096.  Any handle.
+ * All three: one stream, no synchronisation, an argument error enqueues nothing. */
+size_t smtts_asr_workspace_bytes(smtts_handle h, int B, int N);
+int smtts_asr_logprobs(smtts_handle h, void* stream, const float* x, const int32_t* n_len, int B, int N, void* ws, size_t ws_bytes,
+                       float* logp);
+int smtts_ctc_score(smtts_handle h, void* stream, const float* logp, const int32_t* t_len, const int32_t* tokens, const int32_t* p0,
+                    const int32_t* p1, int B, int T, int P, int C, float* nll);
+int smtts_ctc_greedy(smtts_handle h, void* stream, const float* logp, const int32_t* t_len, int B, int T, int C, int32_t* ids,
+                     int32_t* n_ids);
 
 /* ---- codec ------------------------------------------------------------------------------------ */
 int smtts_codec_hop(smtts_handle h);

@@ -52,6 +52,10 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
                                  vp, vp, vp, sz, vp, u32, u32, vp]),
     "smtts_sample_pinned": (i32, [vp, vp, i32, i32, i32, f32, f32, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, u64,
                                   vp, vp, vp, sz, vp, u32, u32, vp, vp, vp, i32]),
+    "smtts_asr_workspace_bytes": (sz, [vp, i32, i32]),
+    "smtts_asr_logprobs": (i32, [vp, vp, vp, vp, i32, i32, vp, sz, vp]),
+    "smtts_ctc_score": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
+    "smtts_ctc_greedy": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "smtts_align_path": (i32, [vp, vp, vp, i32, i32, i32, vp, vp, vp, vp, vp]),
     "smtts_take_scores": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, f32, f32, f32, f32, f32, f32, vp, vp]),
     "smtts_take_select": (i32, [vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp]),

@@ -20,8 +20,8 @@ from typing import Callable, Dict, Iterable, List, NamedTuple, Optional, Sequenc
 import numpy as np
 import torch
 
-from .engine import DEFAULT_PRECISION, SITES, HipEngine
-from .weights import DEFAULT_CODEC, CodecSpec, all_param_specs, load_weight_file
+from .engine import ASR_MAX_ROWS, ASR_UPSAMPLE, DEFAULT_PRECISION, SITES, HipEngine
+from .weights import DEFAULT_CODEC, CodecSpec, all_param_specs, asr_param_specs, load_weight_file
 
 SAMPLE_RATE = 24_000
 HOP_SIZE = 3_200
@@ -290,6 +290,20 @@ def as_alignment(align) -> Optional["Alignment"]:
 ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS = 225, 198   # the range of smtts_align_path: 30 s of frames, the phoneme window
 
 
+def phoneme_error_rate(ids: Sequence[int], ref: Sequence[int]) -> float:
+    """Edit distance (substitutions, insertions, deletions, each 1) between two phoneme id sequences over the length of `ref`; host
+    only.  An empty `ref` gives 0.0 for an empty `ids`, +inf otherwise."""
+    a, b = [int(v) for v in ids], [int(v) for v in ref]
+    if not b:
+        return 0.0 if not a else float("inf")
+    row = list(range(len(b) + 1))
+    for i, x in enumerate(a, 1):
+        prev, row[0] = row[0], i
+        for j, y in enumerate(b, 1):
+            prev, row[j] = row[j], min(row[j] + 1, row[j - 1] + 1, prev + (x != y))
+    return row[-1] / len(b)
+
+
 class Takes:
     """Best-of-K sampling (immutable; DESIGN 8d, include/smalltts_hip.h smtts_take_scores / smtts_take_select): every row is sampled
     `k` times (1..16) from seeds take_seed(seed, 0 .. k-1), each take's text alignment is scored on the device and only the take with
@@ -301,11 +315,18 @@ class Takes:
     project has run is seeded noise, nobody has measured whether the lowest total is the take a listener would keep, and the score
     rests on the tap's layer / head selection (Alignment), which is unvalidated in the same way.  The mechanism is verified: the
     features and the total (bit for bit against a numpy restatement), the selection, and that the winner's latents, audio and words
-    are those of the same row sampled alone."""
-    __slots__ = ("k", "weights", "tau_token", "tau_frame")
+    are those of the same row sampled alone.
+
+    `ctc` (>= 0, default 0 = off: the launches and bits of the score above): a CTC term.  The latent phoneme recogniser
+    (engine part "asr", SmallTTS(recogniser=True)) reads every take's latents, nll = the CTC negative log-likelihood of the row's
+    spoken tokens (smtts_ctc_score), and total' = total + (ctc * nll) / tokens, three single fp32 operations in that order.  It asks
+    "were these phonemes spoken?" and is the quantity the 4-step student was distilled to make small; UNVALIDATED in the same way:
+    no recogniser checkpoint has ever been loaded, and its Conformer composition is restated from recollection.  Not with repair=."""
+    __slots__ = ("k", "weights", "tau_token", "tau_frame", "ctc")
     MAX_K, MAX_ROWS = 16, 64   # smtts_take_select's K; the largest sampler batch the tap is tested at
 
-    def __init__(self, k: int, weights: Sequence[float] = (1.0, 2.0, 1.0, 1.0), tau_token: float = 0.1, tau_frame: float = 0.1) -> None:
+    def __init__(self, k: int, weights: Sequence[float] = (1.0, 2.0, 1.0, 1.0), tau_token: float = 0.1, tau_frame: float = 0.1,
+                 ctc: float = 0.0) -> None:
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
             raise TypeError(f"Takes: k must be an integer, got {type(k).__name__}")
         if not 1 <= int(k) <= self.MAX_K:
@@ -315,7 +336,10 @@ class Takes:
             raise ValueError(f"Takes: weights must be four finite numbers >= 0, got {w}")
         if not (np.isfinite(float(tau_token)) and np.isfinite(float(tau_frame))):
             raise ValueError("Takes: tau_token and tau_frame must be finite")
+        if isinstance(ctc, bool) or not (np.isfinite(float(ctc)) and float(ctc) >= 0.0):
+            raise ValueError(f"Takes: ctc must be a finite number >= 0, got {ctc!r}")
         set_ = object.__setattr__
+        set_(self, "ctc", float(ctc))
         set_(self, "k", int(k))
         set_(self, "weights", w)
         set_(self, "tau_token", float(tau_token))
@@ -720,7 +744,7 @@ def _split_sources(weights) -> List[str]:
 def _validated(tensors: Dict[str, object], source: str, codec: CodecSpec) -> Dict[str, object]:
     """Reject a tensor whose shape is not the inventory's BEFORE it reaches the packers: the kernels assume the model's
     strides (960 / 2400 / 512 ...), so a checkpoint of another model size must be a clean error naming the tensor."""
-    want = dict(all_param_specs(codec))
+    want = dict(all_param_specs(codec) + asr_param_specs())
     bad = [(k, tuple(v.shape), want[k]) for k, v in tensors.items() if k in want and tuple(v.shape) != tuple(want[k])]
     if bad:
         k, got, exp = bad[0]
@@ -748,7 +772,7 @@ def _load_weights_into(eng: HipEngine, weights, parts: Sequence[str]) -> None:
       * ``synthetic[:seed]``       seeded random weights for every requested part NOT provided by an earlier source.
     e.g. ``"dmd.pt+codec.smtts"`` (DiT checkpoint + separately converted codec) or ``"dmd.pt+synthetic:7"``."""
     have: set = set()
-    prefixes = {"dit": ("velocity.",), "decoder": ("codec.decoder.",), "encoder": ("codec.encoder.",)}
+    prefixes = {"dit": ("velocity.",), "decoder": ("codec.decoder.",), "encoder": ("codec.encoder.",), "asr": ("asr.",)}
     codec = eng.codec_spec
 
     def note(names):
@@ -787,7 +811,11 @@ def _load_weights_into(eng: HipEngine, weights, parts: Sequence[str]) -> None:
 
 def get_engine(weights: Optional[str] = None, device: int = 0, precision: str = DEFAULT_PRECISION,
                parts: Sequence[str] = ("dit", "decoder", "encoder")) -> HipEngine:
-    """One engine (one weight copy) per (weights, device, parts); shared by SmallTTS/Encoder/Decoder."""
+    """One engine (one weight copy) per (weights, device, parts); shared by SmallTTS/Encoder/Decoder.  parts: of "dit", "decoder",
+    "encoder" and "asr" (the latent phoneme recogniser, DESIGN 8i: optional, not among the defaults)."""
+    unknown = [p for p in parts if p not in ("dit", "decoder", "encoder", "asr")]
+    if unknown:
+        raise ValueError(f"get_engine: unknown part {unknown[0]!r} (dit, decoder, encoder, asr)")
     weights = weights or DEFAULT_WEIGHTS
     key = ("+".join(_split_sources(weights)), int(device), tuple(sorted(parts)))
     eng = _ENGINES.get(key)
@@ -884,6 +912,7 @@ class _Batch(NamedTuple):
     winner: Optional[torch.Tensor] = None  # takes=: (B,) int32, the take kept per row (engine.take_select); None with one take
     total: Optional[torch.Tensor] = None   # takes=: (B * K,) fp32, every take's total, piece-major (engine.take_scores), else None
     feat: Optional[torch.Tensor] = None    # takes=: (B * K, 4) int32 (cells, skipped, longest, idle), else None
+    nll: Optional[torch.Tensor] = None     # Takes(ctc > 0): (B * K,) fp32, every take's CTC nll, piece-major (engine.ctc_score), else None
     rp_kept: Optional[List[torch.Tensor]] = None     # repair=: per round (B,) int32, 1 where the repaired row was kept (engine.repair_keep)
     rp_counts: Optional[List[torch.Tensor]] = None   # repair=: per round (B, 2) int32 (bad tokens, freed frames) (engine.repair_plan)
     rp_totals: Optional[List[torch.Tensor]] = None   # repair=: rounds + 1 (B,) fp32: the rows' totals before round 1 and after every round
@@ -909,6 +938,23 @@ def _read_takes(recs: Sequence[_Batch], K: int) -> Tuple[np.ndarray, np.ndarray,
             wins.append(flat[pos: pos + G])
             pos += G
     return np.concatenate(wins), np.concatenate(tots), np.concatenate(feats)
+
+
+def _read_nll(recs: Sequence[_Batch], K: int) -> np.ndarray:
+    """The CTC term of Takes(ctc > 0) of finished batches, in one small read-back: -> nll (n, K) fp32 over the rows of all records."""
+    return torch.cat([rec.nll for rec in recs]).cpu().numpy().reshape(-1, K)
+
+
+def check_takes_ctc(what: str, tk: Optional["Takes"], rp: Optional["Repair"], eng: HipEngine) -> bool:
+    """Takes(ctc > 0) asks for the recogniser part and excludes repair= (its keep rule re-scores with take_scores alone).  -> whether the
+    CTC term is on."""
+    if tk is None or tk.ctc == 0.0:
+        return False
+    if rp is not None:
+        raise ValueError(f"{what}: Takes(ctc > 0) and repair= exclude each other (repair's keep rule scores without the CTC term)")
+    if not eng.has("asr"):
+        raise ValueError(f"{what}: Takes(ctc > 0) needs the recogniser part (SmallTTS(recogniser=True) or get_engine(parts=(..., 'asr')))")
+    return True
 
 
 def _read_repair(recs: Sequence[_Batch]) -> List[tuple]:
@@ -943,15 +989,20 @@ class SmallTTS:
                  codec_decoder_path: str = "assets/codec/decoder.onnx",
                  providers: Optional[Iterable[str]] = None, *, weights: Optional[str] = None, device: int = 0,
                  precision: str = DEFAULT_PRECISION, num_steps: int = NUM_STEPS, seed: Optional[int] = None,
-                 engine: Optional[HipEngine] = None, device_ids: Optional[Sequence[int]] = None) -> None:
+                 engine: Optional[HipEngine] = None, device_ids: Optional[Sequence[int]] = None, recogniser: bool = False) -> None:
         """Keyword-only additions to the reference signature (infer/onnx.py:53-59): `weights`, `device`, `precision`,
         `num_steps`, `seed`, and `device_ids` — the GPUs `synthesize_sharded` spreads a request list over from THIS process
-        (one weight replica, engine and host thread per GPU; under torch.distributed the process group is used instead)."""
+        (one weight replica, engine and host thread per GPU; under torch.distributed the process group is used instead).
+        `recogniser=True` adds the latent phoneme recogniser (engine part "asr") to this instance's engine: transcribe(),
+        ctc_score() and Takes(ctc=) need it."""
         if device_ids:
             device = int(device_ids[0])
-        self.engine = engine or get_engine(weights, device, precision, parts=("dit", "decoder", "encoder"))
+        parts = ("dit", "decoder", "encoder") + (("asr",) if recogniser else ())
+        self.engine = engine or get_engine(weights, device, precision, parts=parts)
         if not (self.engine.has("dit") and self.engine.has("decoder")):
             raise RuntimeError("SmallTTS needs DiT and codec-decoder weights")
+        if recogniser and not self.engine.has("asr"):
+            raise RuntimeError("SmallTTS(recogniser=True): the engine holds no recogniser part (asr.* tensors)")
         self.num_steps = int(num_steps)
         self._seed = seed
         self._rng = np.random.default_rng(seed) if seed is not None else None
@@ -1006,6 +1057,69 @@ class SmallTTS:
             y = y[start:start + n]
         lat = Encoder(engine=self.engine).encode_reference(y.reshape(1, 1, -1))
         return self.encode_voice(lat[0].numpy())
+
+    def _asr_rows(self, what: str, latents, lengths):
+        """-> (x (B, N, 64) fp32 on the device, frames per row): `latents` a (B, N, 64) array / tensor with `lengths` (None: N for every
+        row), or a sequence of (n_b, 64) arrays (their own lengths)."""
+        eng = self.engine
+        if not eng.has("asr"):
+            raise ValueError(f"{what}: needs the recogniser part (SmallTTS(recogniser=True))")
+        if isinstance(latents, (np.ndarray, torch.Tensor)) and latents.ndim == 3:
+            ns = [int(latents.shape[1])] * int(latents.shape[0]) if lengths is None else [int(v) for v in lengths]
+            x = eng._dev(latents, torch.float32)
+        else:
+            rows = [np.asarray(r, np.float32) for r in latents]
+            if lengths is not None:
+                raise ValueError(f"{what}: lengths= belongs to a (B, N, 64) array; a list of rows carries its own lengths")
+            ns = [int(r.shape[0]) for r in rows]
+            x = np.zeros((len(rows), max(ns + [1]), 64), np.float32)
+            for b, r in enumerate(rows):
+                if r.ndim != 2 or r.shape[1] != 64:
+                    raise ValueError(f"{what}: row {b} must be (frames, 64), got {r.shape}")
+                x[b, :ns[b]] = r
+            x = eng._dev(x, torch.float32)
+        B, N = int(x.shape[0]), int(x.shape[1])
+        if x.shape[2] != 64 or len(ns) != B or any(n < 0 or n > N for n in ns):
+            raise ValueError(f"{what}: latents (B, N, 64) and one length in [0, N] per row")
+        if not (1 <= B <= ASR_MAX_ROWS and 1 <= N <= ALIGN_MAX_FRAMES):
+            raise ValueError(f"{what}: at most {ASR_MAX_ROWS} rows of at most {ALIGN_MAX_FRAMES} frames (got {B} x {N})")
+        return x, ns
+
+    def transcribe(self, latents, lengths=None) -> List[List[int]]:
+        """Greedy phoneme ids of every row of latents: the recogniser's per-frame argmax (4 frames per latent frame), runs collapsed,
+        blanks dropped (engine.asr_logprobs, engine.ctc_greedy).  latents: (B, N, 64) with `lengths` frames per row (None:
+        all N), or a list of (n_b, 64) rows.  Needs SmallTTS(recogniser=True).  What the recogniser hears is unvalidated: no trained
+        recogniser checkpoint has ever been loaded."""
+        x, ns = self._asr_rows("transcribe", latents, lengths)
+        eng = self.engine
+        ids, n = eng.ctc_greedy(eng.asr_logprobs(x, ns), [ASR_UPSAMPLE * v for v in ns])
+        flat = torch.cat([n, ids.reshape(-1)]).cpu().numpy()   # one read-back
+        B = len(ns)
+        T = int(ids.shape[1])
+        return [flat[B + b * T: B + b * T + int(flat[b])].tolist() for b in range(B)]
+
+    def ctc_score(self, latents, phoneme_ids: Sequence[Sequence[int]], lengths=None, prefix_lens=None) -> List[Tuple[float, float]]:
+        """Per row (nll, nll / L): the CTC negative log-likelihood of the row's tokens phoneme_ids[b][prefix_lens[b]:] (L of them)
+        under the recogniser's reading of its latents (engine.asr_logprobs, engine.ctc_score); +inf for a row without
+        frames or tokens and for one with too few frames for its tokens.  latents / lengths as transcribe().  Lower = the phonemes
+        were more probably spoken; what that is worth is unvalidated on trained weights."""
+        x, ns = self._asr_rows("ctc_score", latents, lengths)
+        B = len(ns)
+        toks = [[int(t) for t in row] for row in phoneme_ids]
+        p0 = [0] * B if prefix_lens is None else [int(v) for v in prefix_lens]
+        if len(toks) != B or len(p0) != B or any(p < 0 or p > len(t) for p, t in zip(p0, toks)):
+            raise ValueError("ctc_score: one token list and one prefix length in [0, tokens of the row] per row")
+        P = max([len(t) for t in toks] + [1])
+        if P > ALIGN_MAX_TOKENS:
+            raise ValueError(f"ctc_score: at most {ALIGN_MAX_TOKENS} tokens per row, got {P}")
+        tab = np.zeros((B, P), np.int32)
+        for b, t in enumerate(toks):
+            tab[b, :len(t)] = t
+        eng = self.engine
+        nll = eng.ctc_score(eng.asr_logprobs(x, ns), [ASR_UPSAMPLE * v for v in ns], eng._dev(tab, torch.int32), p0, [len(t) for t in toks])
+        nll = nll.cpu().numpy()
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return [(float(v), float(np.float32(v) / np.float32(max(len(t) - p, 0)))) for v, t, p in zip(nll, toks, p0)]
 
     def synthesize_batch(self, ref_latents: Optional[Sequence[np.ndarray]], phoneme_ids: Sequence[Sequence[int]],
                          durations, *, noise: Optional[np.ndarray] = None, return_latents: bool = False,
@@ -1083,6 +1197,7 @@ class SmallTTS:
         K = 1 if tk is None else tk.k
         scored = (tk is not None and (K > 1 or return_takes)) or rp is not None   # the tap, the path and the score run for these
         tk_run = tk if tk is not None else Takes(1)            # the weights and thresholds of the total
+        ctc_w = tk.ctc if check_takes_ctc("synthesize_batch", tk, rp, self.engine) and scored else 0.0
         if al is None and (return_alignment or (prefix_lens is not None and not scored)):   # (scored takes align too: they take prefix_lens)
             raise ValueError("synthesize_batch: prefix_lens= and return_alignment= belong to align=")
         if voices is not None:
@@ -1159,7 +1274,7 @@ class SmallTTS:
             if voices is not None:
                 cache.update(eng.voice_expand(s_voices))
             nz = noise if s_seeds is None else eng.randn_rows(s_seeds, s_ns, self.num_steps, n_max=Nm)
-            mass = spans = seg = gain = winner = total = feat = None
+            mass = spans = seg = gain = winner = total = feat = nll = None
             if al_run is None:
                 x = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, **pin_kw)
             else:
@@ -1168,6 +1283,11 @@ class SmallTTS:
                 spans, score = eng.align_path(mass, s_ns, s_p0s, s_ps)[:2]
                 if scored:                                     # takes: score every sampler row, keep one per caller row
                     feat, total = eng.take_scores(mass, spans, score, s_ns, s_p0s, s_ps, tk_run)
+                if ctc_w > 0.0:                                # the CTC term: total' = total + (ctc * nll) / tokens, single fp32 operations
+                    tok = torch.from_numpy(ids.astype(np.int32)).pin_memory().to(eng.device, non_blocking=True)
+                    pw = torch.tensor([float(max(0, p1 - p0)) for p0, p1 in zip(s_p0s, s_ps)], dtype=torch.float32).pin_memory()
+                    nll = eng.ctc_score(eng.asr_logprobs(x, s_ns), [ASR_UPSAMPLE * n for n in s_ns], tok, s_p0s, s_ps)
+                    total = total + (nll * ctc_w) / pw.to(eng.device, non_blocking=True)
                 if K > 1:
                     x, _n, spans, mass, winner = eng.take_select(total, K, x, s_ns, spans, mass)
             rp_kept = rp_counts = rp_totals = None
@@ -1195,7 +1315,7 @@ class SmallTTS:
             audio = eng.codec_decode(x) if _decode else None   # (B, 1, HOP * Nm); causal => prefixes are exact (None: synthesize_stream decodes)
             if ep is not None:                                 # behind the decode, on the same stream
                 seg, gain, _e = eng.endpoints(audio, ns, ep)
-            return _Batch(audio, x, mass, spans, seg, gain, ns, run, winner, total, feat, rp_kept, rp_counts, rp_totals)
+            return _Batch(audio, x, mass, spans, seg, gain, ns, run, winner, total, feat, nll, rp_kept, rp_counts, rp_totals)
 
         rec = run()
         if _defer:                                             # synthesize_batches / synthesize_long / the server: stay on the device / stream
@@ -1252,7 +1372,8 @@ class SmallTTS:
         if takes is not None:
             K, row_seeds = takes
             win, tot, ft = _read_takes([rec], K)
-            res.append([(int(win[b]), take_seed(row_seeds[b], int(win[b])) if K > 1 else int(row_seeds[b]), tot[b], ft[b])
+            extra = [()] * B if rec.nll is None else [(v,) for v in _read_nll([rec], K)]   # Takes(ctc > 0): the K values of nll too
+            res.append([(int(win[b]), take_seed(row_seeds[b], int(win[b])) if K > 1 else int(row_seeds[b]), tot[b], ft[b]) + extra[b]
                         for b in range(B)])
         if return_repair:
             res.append(_read_repair([rec]))
@@ -1413,6 +1534,7 @@ class SmallTTS:
             raise ValueError("synthesize_long: return_repair= belongs to repair=")
         if tk is not None and tk.k == 1 and not return_takes:
             tk = None                                          # one take and nothing to report: the call without takes
+        check_takes_ctc("synthesize_long", tk, rp, self.engine)
         al = as_alignment(align if align is not None else (True if return_words else None))
         if al is not None and not return_words and tk is None and rp is None:
             raise ValueError("synthesize_long: align= belongs to return_words=True")
@@ -1444,7 +1566,8 @@ class SmallTTS:
         if tk is not None and (return_takes or return_pieces):
             win, tot, ft = _read_takes(pending, K)             # one small read-back for the whole text
             spoken = [take_seed(seeds[i], int(win[i])) for i in range(len(toks))]  # what each piece was spoken from: the winner's seed
-            taken = [(int(win[i]), spoken[i], tot[i], ft[i]) for i in range(len(toks))]
+            extra = [()] * len(toks) if pending[0].nll is None else [(v,) for v in _read_nll(pending, K)]   # Takes(ctc > 0): nll (K,) too
+            taken = [(int(win[i]), spoken[i], tot[i], ft[i]) + extra[i] for i in range(len(toks))]
         piece_spans: List[Optional[np.ndarray]] = [None] * len(toks)
         if return_words:
             # one small read-back for the whole text: every batch's (B, P, 2) span table, flattened

@@ -13,7 +13,13 @@ Two sources, both optional at run time because neither exists offline:
   by name is listed in the report instead of being guessed — codec parity stays "unpinned" until a name map for
   the exported codec graph has been checked against real files.
 
+* optionally the recogniser the student was distilled against: a ``torch.save`` of ``ASR(64).state_dict()`` (reference
+  ``models/asr.py``; keys ``encoder.…``, ``proj.…``, ``upsample.deconv.…``, bare or under ``"model"`` / ``"state_dict"``, wrapper
+  prefixes stripped as for the DiT) becomes the ``asr.`` tensors, checked against :func:`smalltts_amd.weights.asr_param_specs`.
+  No such checkpoint has ever been loaded by this project: the path is checked on synthetic state dicts only.
+
 CLI:  python -m smalltts_amd.convert --checkpoint ckpt.pt --out weights.smtts
+      python -m smalltts_amd.convert [--checkpoint ckpt.pt] --asr-checkpoint asr.pt --out weights.smtts
       python -m smalltts_amd.convert --onnx condition_encoder.onnx denoiser.onnx --out weights.smtts [--allow-partial]
       python -m smalltts_amd.convert --onnx decoder.onnx encoder.onnx --codec [--codec-spec spec.json] [--map-by-position]
                                      --out codec.smtts --report codec_report.json
@@ -30,8 +36,8 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 
 import numpy as np
 
-from .weights import (CodecSpec, clean_state_dict_keys, codec_decoder_param_specs, codec_encoder_param_specs, dit_param_specs,
-                      save_weight_file)
+from .weights import (CodecSpec, asr_param_specs, clean_state_dict_keys, codec_decoder_param_specs, codec_encoder_param_specs,
+                      dit_param_specs, save_weight_file)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -84,15 +90,47 @@ def state_dict_from_checkpoint(obj, key: Optional[str] = None) -> Dict[str, np.n
     return out
 
 
-def convert_checkpoint(path: str, out: str, key: Optional[str] = None, allow_partial: bool = False) -> ConversionReport:
+def asr_tensors_from_checkpoint(path: str, key: Optional[str] = None, allow_partial: bool = False):
+    """The recogniser's state dict (ASR(64): encoder.*, proj.*, upsample.deconv.*) -> ({"asr." + name: array}, report).  BatchNorm's
+    num_batches_tracked counters are not parameters of the forward pass and are dropped without a word."""
     import torch
-    ck = torch.load(path, map_location="cpu", weights_only=True)
-    tensors = state_dict_from_checkpoint(ck, key)
-    rep = check_against_specs(tensors, dit_param_specs())
+    tensors = state_dict_from_checkpoint(torch.load(path, map_location="cpu", weights_only=True), key)
+    tensors = {"asr." + k: v for k, v in tensors.items() if not k.endswith("num_batches_tracked")}
+    rep = check_against_specs(tensors, asr_param_specs())
     if not rep.ok and not allow_partial:
-        raise ValueError(f"{path}: not a DiTModel(64) state_dict — {rep.summary()}; first problems: "
-                         f"{(rep['missing'] + [m[0] for m in rep['shape_mismatch']])[:5]}")
-    keep = {n: tensors[n] for n, _ in dit_param_specs() if n in tensors}
+        raise ValueError(f"{path}: not an ASR(64) state_dict — {rep.summary()}; first problems: "
+                         f"{(rep['missing'] + [f'{m[0]} has shape {m[1]}, expected {m[2]}' for m in rep['shape_mismatch']])[:5]}")
+    bad = {m[0] for m in rep["shape_mismatch"]}
+    return {n: tensors[n] for n, _ in asr_param_specs() if n in tensors and n not in bad}, rep
+
+
+def convert_checkpoint(path: Optional[str], out: str, key: Optional[str] = None, allow_partial: bool = False,
+                       asr_checkpoint: Optional[str] = None) -> ConversionReport:
+    """DiT checkpoint and / or recogniser checkpoint -> one weight file.  The report is the DiT's; with asr_checkpoint its "asr" entry
+    is the recogniser's (alone: the recogniser's report itself)."""
+    import torch
+    keep: Dict[str, np.ndarray] = {}
+    rep = None
+    if path is not None:
+        ck = torch.load(path, map_location="cpu", weights_only=True)
+        tensors = state_dict_from_checkpoint(ck, key)
+        rep = check_against_specs(tensors, dit_param_specs())
+        if not rep.ok and not allow_partial:
+            raise ValueError(f"{path}: not a DiTModel(64) state_dict — {rep.summary()}; first problems: "
+                             f"{(rep['missing'] + [m[0] for m in rep['shape_mismatch']])[:5]}")
+        keep = {n: tensors[n] for n, _ in dit_param_specs() if n in tensors}
+    if asr_checkpoint is not None:
+        asr, arep = asr_tensors_from_checkpoint(asr_checkpoint, None, allow_partial)
+        keep.update(asr)
+        if rep is None:
+            rep = arep
+        else:
+            rep["asr"] = dict(arep)
+            for k in ("missing", "shape_mismatch", "unexpected"):   # one verdict for the file
+                rep[k] = rep[k] + arep[k]
+            rep["matched"] += arep["matched"]
+    if rep is None:
+        raise ValueError("convert_checkpoint: neither a DiT nor a recogniser checkpoint was given")
     save_weight_file(out, keep)
     return rep
 
@@ -314,9 +352,11 @@ def convert_onnx(paths: Sequence[str], out: str, codec: Optional[CodecSpec] = No
 
 def main(argv: Optional[Sequence[str]] = None) -> int:
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    src = ap.add_mutually_exclusive_group(required=True)
+    src = ap.add_mutually_exclusive_group(required=False)
     src.add_argument("--checkpoint", help="training checkpoint (.pt) holding the DiTModel state_dict")
     src.add_argument("--onnx", nargs="+", help=".onnx files whose initialisers hold the weights")
+    ap.add_argument("--asr-checkpoint", default=None, help="torch.save of the recogniser's state dict (ASR(64)): written as the asr.* "
+                                                           "tensors, alone or next to --checkpoint")
     ap.add_argument("--key", default=None, help="checkpoint entry to use (default: student_model / model)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--allow-partial", action="store_true", help="write what matched instead of failing")
@@ -328,10 +368,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--map-by-position", action="store_true",
                     help="--onnx: also take initialisers matched by position inside their shape signature (unverified; see the report)")
     a = ap.parse_args(argv)
+    if not (a.checkpoint or a.onnx or a.asr_checkpoint):
+        ap.error("one of --checkpoint, --onnx, --asr-checkpoint is required")
+    if a.onnx and a.asr_checkpoint:
+        ap.error("--asr-checkpoint goes with --checkpoint or alone, not with --onnx")
     codec = None
     if a.codec or a.codec_spec:
         codec = CodecSpec(**json.load(open(a.codec_spec))) if a.codec_spec else CodecSpec()
-    rep = (convert_checkpoint(a.checkpoint, a.out, a.key, a.allow_partial) if a.checkpoint
+    rep = (convert_checkpoint(a.checkpoint, a.out, a.key, a.allow_partial, a.asr_checkpoint) if not a.onnx
            else convert_onnx(a.onnx, a.out, codec, a.allow_partial, a.map_by_position, a.parts.split(",") if a.parts else None))
     print(rep.summary())
     if "signature" in rep:

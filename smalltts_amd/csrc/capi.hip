@@ -80,7 +80,7 @@ const char* smtts_range_report(smtts_handle h) {
 }
 float smtts_range_worst_bound(smtts_handle h) { NULLCHK0; return E.range_worst(); }
 int smtts_has_part(smtts_handle h, int part) { NULLCHK0;
-    return part == 0 ? E.has_dit() : part == 1 ? E.has_decoder() : part == 2 ? E.has_encoder() : 0;
+    return part == 0 ? E.has_dit() : part == 1 ? E.has_decoder() : part == 2 ? E.has_encoder() : part == 3 ? E.has_asr() : 0;
 }
 
 size_t smtts_cond_workspace_bytes(smtts_handle h, int B, int R, int P) { NULLCHK0; return E.cond_ws_bytes(B, R, P); }
@@ -186,6 +186,29 @@ int smtts_repair_keep(smtts_handle h, void* stream, int G, int N, int P, const f
     hipError_t e = launch_repair_keep(G, N, P, total_cur, total_new, counts, feat_cur, feat_new, x_cur, x_new, spans_cur, spans_new, mass_cur,
                                       mass_new, total_out, feat_out, kept, ST(stream));
     return e == hipSuccess ? 0 : E.fail_hip(e, "repair_keep");
+}
+
+size_t smtts_asr_workspace_bytes(smtts_handle h, int B, int N) { NULLCHK0; return E.asr_workspace_bytes(B, N); }
+int smtts_asr_logprobs(smtts_handle h, void* stream, const float* x, const int32_t* n_len, int B, int N, void* ws, size_t ws_bytes,
+                       float* logp) { NULLCHK;
+    return E.asr_logprobs(ST(stream), x, n_len, B, N, ws, ws_bytes, logp);
+}
+int smtts_ctc_score(smtts_handle h, void* stream, const float* logp, const int32_t* t_len, const int32_t* tokens, const int32_t* p0,
+                    const int32_t* p1, int B, int T, int P, int C, float* nll) { NULLCHK;
+    if (B < 1 || B > 65536) return E.fail("smtts_ctc_score: B must be in [1, 65536]");
+    if (T < 1 || T > 65536 || P < 1 || P > 198 || C < 2 || C > 256)
+        return E.fail("smtts_ctc_score: T must be in [1, 65536], P in [1, 198] and C in [2, 256] (a row's states and emission ring live in LDS)");
+    if (!logp || !t_len || !tokens || !p0 || !p1 || !nll) return E.fail("smtts_ctc_score: a required pointer is NULL");
+    hipError_t e = launch_ctc_score(logp, t_len, tokens, p0, p1, B, T, P, C, nll, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "ctc_score");
+}
+int smtts_ctc_greedy(smtts_handle h, void* stream, const float* logp, const int32_t* t_len, int B, int T, int C, int32_t* ids,
+                     int32_t* n_ids) { NULLCHK;
+    if (B < 1 || B > 65536) return E.fail("smtts_ctc_greedy: B must be in [1, 65536]");
+    if (T < 1 || T > 4096 || C < 1 || C > 65536) return E.fail("smtts_ctc_greedy: T must be in [1, 4096] (a row's classes live in LDS) and C in [1, 65536]");
+    if (!logp || !t_len || !ids || !n_ids) return E.fail("smtts_ctc_greedy: a required pointer is NULL");
+    hipError_t e = launch_ctc_greedy(logp, t_len, B, T, C, ids, n_ids, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "ctc_greedy");
 }
 
 int smtts_codec_hop(smtts_handle h) { NULLCHK0; return E.codec_spec().hop(); }

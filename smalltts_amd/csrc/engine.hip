@@ -705,6 +705,117 @@ int Engine::certify_codec_ffn(const std::string& name, CodecBlockW& b, int C, in
     return 0;
 }
 
+// ---------------------------------------------------------------------------------------------
+// recogniser (asr.hip): shapes by name, then the packs its kernels read
+// ---------------------------------------------------------------------------------------------
+int Engine::finalize_asr() {
+    constexpr long D = 64, FF = 1024, C = 198, L = 7, KC = 9;
+    const std::string EL = "asr.encoder.conformer_layers.";
+    if (check_shape("asr.upsample.deconv.weight", {D, 1, 4}) || check_shape("asr.upsample.deconv.bias", {D}) ||
+        check_shape("asr.proj.weight", {C, D}) || check_shape("asr.proj.bias", {C}))
+        return 1;
+    for (int l = 0; l < L; ++l) {
+        const std::string p = EL + std::to_string(l) + ".";
+        for (const char* f : {"ffn1", "ffn2"}) {
+            const std::string q = p + f + ".sequential.";
+            if (check_shape(q + "0.weight", {D}) || check_shape(q + "0.bias", {D}) || check_shape(q + "1.weight", {FF, D}) ||
+                check_shape(q + "1.bias", {FF}) || check_shape(q + "4.weight", {D, FF}) || check_shape(q + "4.bias", {D}))
+                return 1;
+        }
+        for (const char* n : {"self_attn_layer_norm", "conv_module.layer_norm", "final_layer_norm", "conv_module.sequential.3"})
+            if (check_shape(p + n + ".weight", {D}) || check_shape(p + n + ".bias", {D})) return 1;
+        const std::string c = p + "conv_module.sequential.";
+        if (check_shape(p + "self_attn.in_proj_weight", {3 * D, D}) || check_shape(p + "self_attn.in_proj_bias", {3 * D}) ||
+            check_shape(p + "self_attn.out_proj.weight", {D, D}) || check_shape(p + "self_attn.out_proj.bias", {D}) ||
+            check_shape(c + "0.weight", {2 * D, D, 1}) || check_shape(c + "0.bias", {2 * D}) || check_shape(c + "2.weight", {D, 1, KC}) ||
+            check_shape(c + "2.bias", {D}) || check_shape(c + "3.running_mean", {D}) || check_shape(c + "3.running_var", {D}) ||
+            check_shape(c + "5.weight", {D, D, 1}) || check_shape(c + "5.bias", {D}))
+            return 1;
+    }
+    bool bad = false;
+    auto host = [&](const std::string& n) {
+        const RawTensor* t = raw(n);
+        std::vector<float> v((size_t)t->numel);
+        if (hipMemcpy(v.data(), t->d, v.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) bad = true;
+        return v;
+    };
+    auto up = [&](const std::vector<float>& v) -> const float* {
+        float* d = static_cast<float*>(dalloc(v.size() * 4));
+        if (!d || hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { bad = true; return nullptr; }
+        return d;
+    };
+    // W (n_out, k_in) row-major -> blocks of 64 outputs x 64 inputs, each [k][n]; block order: outputs outer, inputs inner
+    // (n_pad: outputs rounded up with zero columns)
+    auto blocks_t = [&](const std::string& n, long n_out, long k_in, long n_pad) {
+        const std::vector<float> w = host(n);
+        std::vector<float> o((size_t)(n_pad * k_in), 0.f);
+        const long kb = k_in / 64;
+        for (long r = 0; r < n_out; ++r)
+            for (long k = 0; k < k_in; ++k) o[(size_t)((((r / 64) * kb + k / 64) * 64 + k % 64) * 64 + r % 64)] = w[(size_t)(r * k_in + k)];
+        return up(o);
+    };
+    asr_.up_w = rawp("asr.upsample.deconv.weight");
+    asr_.up_b = rawp("asr.upsample.deconv.bias");
+    for (int l = 0; l < L; ++l) {
+        const std::string p = EL + std::to_string(l) + ".";
+        AsrLayerW& w = asr_.layer[l];
+        for (int f = 0; f < 2; ++f) {
+            const std::string q = p + (f ? "ffn2" : "ffn1") + ".sequential.";
+            AsrFfnW& g = f ? w.ffn2 : w.ffn1;
+            g.ln_w = rawp(q + "0.weight"); g.ln_b = rawp(q + "0.bias");
+            g.w1t = blocks_t(q + "1.weight", FF, D, FF); g.b1 = rawp(q + "1.bias");
+            g.w2t = blocks_t(q + "4.weight", D, FF, D); g.b2 = rawp(q + "4.bias");
+        }
+        w.aln_w = rawp(p + "self_attn_layer_norm.weight"); w.aln_b = rawp(p + "self_attn_layer_norm.bias");
+        w.wqkv_t = blocks_t(p + "self_attn.in_proj_weight", 3 * D, D, 3 * D); w.bqkv = rawp(p + "self_attn.in_proj_bias");
+        w.wo_t = blocks_t(p + "self_attn.out_proj.weight", D, D, D); w.bo = rawp(p + "self_attn.out_proj.bias");
+        const std::string c = p + "conv_module.sequential.";
+        w.conv.ln_w = rawp(p + "conv_module.layer_norm.weight"); w.conv.ln_b = rawp(p + "conv_module.layer_norm.bias");
+        w.conv.pw1t = blocks_t(c + "0.weight", 2 * D, D, 2 * D); w.conv.pw1b = rawp(c + "0.bias");
+        w.conv.dw_w = rawp(c + "2.weight"); w.conv.dw_b = rawp(c + "2.bias");
+        {   // BatchNorm1d in eval: y = (x - mean) / sqrt(var + 1e-5) * weight + bias = x * scale + shift
+            const std::vector<float> g = host(c + "3.weight"), be = host(c + "3.bias"), mu = host(c + "3.running_mean"), var = host(c + "3.running_var");
+            std::vector<float> sc(D), sh(D);
+            for (long i = 0; i < D; ++i) {
+                if (!(var[i] >= 0.f)) return fail("tensor " + c + "3.running_var has a negative (or NaN) entry");
+                const double s = (double)g[i] / std::sqrt((double)var[i] + 1e-5);
+                sc[i] = (float)s;
+                sh[i] = (float)((double)be[i] - (double)mu[i] * s);
+            }
+            w.conv.bn_scale = up(sc); w.conv.bn_shift = up(sh);
+        }
+        w.conv.pw2t = blocks_t(c + "5.weight", D, D, D); w.conv.pw2b = rawp(c + "5.bias");
+        w.fln_w = rawp(p + "final_layer_norm.weight"); w.fln_b = rawp(p + "final_layer_norm.bias");
+    }
+    asr_.proj_t = blocks_t("asr.proj.weight", C, D, 256);
+    {
+        std::vector<float> pb = host("asr.proj.bias");
+        pb.resize(256, 0.f);
+        asr_.proj_b = up(pb);
+    }
+    if (bad) return fail("finalize: packing the recogniser weights failed (device memory)");
+    asr_ready_ = true;
+    return 0;
+}
+
+size_t Engine::asr_workspace_bytes(int B, int N) {
+    if (B < 1 || B > 64 || N < 1 || N > 225) { fail("smtts_asr_workspace_bytes: B must be in [1, 64] and N in [1, 225]"); return 0; }
+    return asr_ws_bytes(B, N);
+}
+
+int Engine::asr_logprobs(hipStream_t st, const float* x, const int32_t* n_len, int B, int N, void* ws, size_t ws_bytes, float* logp) {
+    if (!asr_ready_) return fail("smtts_asr_logprobs: this engine holds no recogniser (load the asr.* tensors and finalize)");
+    if (B < 1 || B > 64 || N < 1 || N > 225) return fail("smtts_asr_logprobs: B must be in [1, 64] and N in [1, 225]");
+    if (!x || !n_len || !ws || !logp) return fail("smtts_asr_logprobs: a required pointer is NULL");
+    if ((uintptr_t)ws & 255) return fail("smtts_asr_logprobs: the workspace must be 256-byte aligned");
+    if (ws_bytes < asr_ws_bytes(B, N)) return fail("smtts_asr_logprobs: workspace too small (smtts_asr_workspace_bytes)");
+    if (((uintptr_t)x | (uintptr_t)n_len | (uintptr_t)logp) & 3) return fail("smtts_asr_logprobs: x, n_len and logp must be 4-byte aligned");
+    HIPC(hipSetDevice(device_));
+    ProfTag tag("asr");
+    const hipError_t e = launch_asr_logprobs(asr_, x, n_len, B, N, ws, logp, st);
+    return e == hipSuccess ? 0 : fail_hip(e, "asr_logprobs");
+}
+
 int Engine::finalize() {
     HIPC(hipSetDevice(device_));
     HIPC(hipDeviceSynchronize());  // nothing in flight may still read the packs of an earlier finalize()
@@ -722,6 +833,9 @@ int Engine::finalize() {
     }
     if (raw("codec.encoder.stem.weight")) {
         if (finalize_codec(false)) return 1;
+    }
+    if (raw("asr.proj.weight")) {
+        if (finalize_asr()) return 1;
     }
     HIPC(hipDeviceSynchronize());
     finalized_ = true;

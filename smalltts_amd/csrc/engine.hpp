@@ -108,6 +108,7 @@ class Engine {
     bool has_dit() const { return dit_ready_; }
     bool has_decoder() const { return dec_.ready; }
     bool has_encoder() const { return enc_.ready; }
+    bool has_asr() const { return asr_ready_; }
     // Per-site operand precision (PREC_* of common.hpp).  Sites: the GEMMs grouped by how much latent / audio error their
     // rounding causes (tests/studies/precision_ladder_cpu.py) and by what they cost.
     enum Site { SITE_DIT_BLOCK = 0,   // QKVG, out-proj, FF1 (SwiGLU), FF2 of the 12 DiT blocks: 95 % of the DiT's flops and bytes
@@ -215,6 +216,10 @@ class Engine {
     size_t encode_ws_bytes(int B, int S) const;
     int codec_encode(hipStream_t st, const float* audio, int B, int S, float* latents, void* ws, size_t ws_bytes);
 
+    // The latent phoneme recogniser (asr.hip; include/smalltts_hip.h smtts_asr_logprobs): present when the asr.* tensors were loaded
+    size_t asr_workspace_bytes(int B, int N);
+    int asr_logprobs(hipStream_t st, const float* x, const int32_t* n_len, int B, int N, void* ws, size_t ws_bytes, float* logp);
+
     const CodecSpecC& codec_spec() const { return cspec_; }
     // per-kernel HIP-event timing (bench.py); report = JSON array, valid after the stream is synchronised
     void profile_enable(int mode);  // 0 off, 1 per-kernel, 2 per-kernel prefixed with the pipeline phase
@@ -266,6 +271,7 @@ class Engine {
     float* concat_vec(const std::vector<std::string>& names, const std::vector<int>& zero_len = {});
     int finalize_dit();
     int finalize_codec(bool decoder);
+    int finalize_asr();
     int build_encoder(EncoderW& e, const std::string& prefix, int dim, int heads, int ff, int layers, float eps);
     int make_rope(int dim, float** cos_out, float** sin_out);
     struct ModWs;
@@ -374,7 +380,7 @@ class Engine {
                     bf16_t* hhi, bf16_t* hlo, int B, int T, int C, size_t n2_elems /* capacity of n2hi (bf16 elements) */,
                     bool carried = false /* the pad frames of *x hold carried frames: a path that reads pads of nbuf normalises them too */);
     int check_shape(const std::string& name, std::initializer_list<long> want);
-    void invalidate() { finalized_ = false; dit_ready_ = false; dec_.ready = false; enc_.ready = false; }
+    void invalidate() { finalized_ = false; dit_ready_ = false; dec_.ready = false; enc_.ready = false; asr_ready_ = false; }
     void free_packs();
 
     // the tag a producer of attention operand images is handed in place of the (unused) lo array when the images are fp16
@@ -453,6 +459,9 @@ class Engine {
 
     CodecSpecC cspec_;
     CodecHalfW dec_, enc_;
+
+    bool asr_ready_ = false;
+    AsrW asr_{};
 };
 
 void alpha_sigma_host(float t, float& a, float& s);

@@ -910,8 +910,11 @@ __device__ __forceinline__ void gemm_epilogue_staged16(const Epi& epi, floatx16 
         RowCtx rc;
         epi.rows(z, mt + rm, M, rc);
         if (Epi::PAIRED) {
-            unsigned short o[16];
-            epi.colpair16(z, ncol0 + cn, rc, acc[i][0], acc[i][TN - 1], o);
+            // A column past the output width (the SwiGLU hidden of the DiT: 2400 units in 64-unit wave tiles, so units 2400 .. 2431 of
+            // the last tile) is not stored below.  It may not be evaluated either: its bias index lies behind the bias vectors, in
+            // whatever the allocation's slack holds, and a non-finite or huge value there was counted as fp16 clamps of the site.
+            unsigned short o[16] = {};
+            if (ncol0 + cn < Nout) epi.colpair16(z, ncol0 + cn, rc, acc[i][0], acc[i][TN - 1], o);
 #pragma unroll
             for (int r = 0; r < 16; ++r)
                 *reinterpret_cast<unsigned short*>(stage + (rm + (r & 3) + 8 * (r >> 2)) * RS + 2 * cn) = o[r];

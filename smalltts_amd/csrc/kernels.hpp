@@ -87,6 +87,37 @@ hipError_t launch_take_scores(const float* mass, const int* spans, const float* 
 // int32 (G) = k.  An optional input and its output are given or NULL together.
 hipError_t launch_take_select(const float* total, int G, int K, int N, int P, const float* x, const int* n_len, const int* spans,
                               const float* mass, float* x_win, int* n_win, int* spans_win, float* mass_win, int* winner, hipStream_t st);
+// ---- CTC (ctc.hip) ------------------------------------------------------------------------------------------------------------------
+// nll f32 (B) = F.ctc_loss(blank 0, reduction 'none', zero_infinity False) of logp f32 (B, T, C) over the first t_len[b] frames against
+// tokens[b][p0 : p1) (i32 (B, P); t_len into [0, T], p0 / p1 into [0, P], tokens into [1, C), all DEVICE, clamped); +inf for an empty or
+// infeasible row.  One workgroup per row, thread = extended state.  T >= 1, 1 <= P <= 198, 2 <= C <= 256, else hipErrorInvalidValue.
+hipError_t launch_ctc_score(const float* logp, const int* t_len, const int* tokens, const int* p0, const int* p1, int B, int T, int P, int C,
+                            float* nll, hipStream_t st);
+// per-frame argmax (lowest class on ties), runs collapsed, class 0 dropped -> ids i32 (B, T), zeros behind n_ids i32 (B).  1 <= T <= 4096.
+hipError_t launch_ctc_greedy(const float* logp, const int* t_len, int B, int T, int C, int* ids, int* n_ids, hipStream_t st);
+// ---- recogniser (asr.hip) -----------------------------------------------------------------------------------------------------------
+// Device pointers of the packed recogniser weights (Engine::finalize_asr): every 64 x 64 block of a product's weight transposed to
+// [k][n], 16-byte aligned; vectors as loaded.
+struct AsrFfnW { const float *ln_w, *ln_b, *w1t /* [16][64 k][64 hidden] */, *b1, *w2t /* [16][64 hidden][64 n] */, *b2; };
+struct AsrConvW {
+    const float *ln_w, *ln_b, *pw1t /* [2][64][64]: value half, gate half */, *pw1b, *dw_w /* [64][9] */, *dw_b;
+    const float *bn_scale, *bn_shift /* BatchNorm (eval) folded */, *pw2t, *pw2b;
+};
+struct AsrLayerW {
+    AsrFfnW ffn1, ffn2;
+    const float *aln_w, *aln_b, *wqkv_t /* [3][64][64] */, *bqkv, *wo_t, *bo;
+    AsrConvW conv;
+    const float *fln_w, *fln_b;
+};
+struct AsrW {
+    const float *up_w /* [64][4] */, *up_b;
+    AsrLayerW layer[7];
+    const float *proj_t /* [4][64][64], classes >= 198 zero */, *proj_b /* [256] */;
+};
+size_t asr_ws_bytes(int B, int N);
+// x f32 (B, N, 64), n_len i32 (B) (clamped into [0, N]) -> logp f32 (B, 4 N, 198), 0.0 at and behind frame 4 n_b; ws: asr_ws_bytes, 256-byte
+// aligned, may hold anything.  1 <= N <= 225.
+hipError_t launch_asr_logprobs(const AsrW& w, const float* x, const int* n_len, int B, int N, void* ws, float* logp, hipStream_t st);
 // ---- repair (repair.hip) ----------------------------------------------------------------------------------------------------------
 // Pin mask of every row behind launch_align_path, one workgroup per row: a token of [p0, p1) is bad when its span is empty, longer than
 // max_span, or holds no frame with mass >= tau_tok; a bad token with a span frees its frames +- margin.  pin u8 (B, N) = 1 for frames

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .weights import (DEFAULT_CODEC, CodecSpec, codec_decoder_param_specs, codec_encoder_param_specs,
+from .weights import (DEFAULT_CODEC, CodecSpec, asr_param_specs, codec_decoder_param_specs, codec_encoder_param_specs,
                       dit_param_specs, init_rule, tensor_key)
 
 N_LAYERS, N_HEADS, HEAD_DIM, LATENT = 12, 8, 120, 64
@@ -25,6 +25,7 @@ DEFAULT_PRECISION = "f16"
 
 
 ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS = 225, 198   # smtts_align_path: 30 s of codec frames, the phoneme window
+ASR_MAX_ROWS, ASR_UPSAMPLE, ASR_CLASSES = 64, 4, 198   # smtts_asr_logprobs: rows per call, frames per latent frame, phoneme classes
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -340,6 +341,8 @@ class HipEngine:
             specs += codec_decoder_param_specs(spec)
         if "encoder" in parts:
             specs += codec_encoder_param_specs(spec)
+        if "asr" in parts:
+            specs += asr_param_specs()
         for name, shape in specs:
             mean, hr = init_rule(name, shape)
             sh = (C.c_int64 * max(1, len(shape)))(*shape)
@@ -362,7 +365,7 @@ class HipEngine:
         self.check_fp16_range("finalize")   # static part: fused codec FFN blocks whose range the weights do not certify
 
     def has(self, part: str) -> bool:
-        return bool(self.lib.smtts_has_part(self.h, {"dit": 0, "decoder": 1, "encoder": 2}[part]))
+        return bool(self.lib.smtts_has_part(self.h, {"dit": 0, "decoder": 1, "encoder": 2, "asr": 3}[part]))
 
     # ---- operators -----------------------------------------------------------------------------
     def cond_encode(self, ref, ref_len, ids, ph_mask, debug: bool = False) -> Dict[str, torch.Tensor]:
@@ -514,6 +517,69 @@ class HipEngine:
         self._ck(self.lib.smtts_align_path(self.h, self._stream(), _p(mass), B, N, P, _p(tab[0]), _p(tab[1]), _p(tab[2]), _p(spans),
                                            _p(score)), "align_path")
         return spans, score
+
+    def asr_logprobs(self, x: torch.Tensor, ns, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Per-frame phoneme log-probabilities of latents (smtts_asr_logprobs; the definition: include/smalltts_hip.h).
+        x fp32 (B,N,64) contiguous on the device, B <= 64, N <= 225; ns the frames per row (host integers).  -> logp fp32 (B,4N,198)
+        on the device (out: a contiguous fp32 tensor of that shape to write into), 0.0 at and behind frame 4 ns[b]; every row is
+        computed as if it were alone.  Needs the recogniser part (load_synthetic(parts=(..., "asr")) or the asr.* tensors).  Launches
+        on the current stream, no synchronisation."""
+        if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device or x.shape[2] != LATENT:
+            raise ValueError("asr_logprobs: x must be a contiguous fp32 (B,N,64) tensor on the engine's device")
+        B, N = int(x.shape[0]), int(x.shape[1])
+        if not (1 <= B <= ASR_MAX_ROWS and 1 <= N <= ALIGN_MAX_FRAMES):
+            raise ValueError(f"asr_logprobs: B = {B}, N = {N} outside the supported range B <= {ASR_MAX_ROWS}, N <= {ALIGN_MAX_FRAMES}")
+        if len(ns) != B:
+            raise ValueError("asr_logprobs: one frame count per row")
+        if not self.has("asr"):
+            raise ValueError("asr_logprobs: this engine holds no recogniser part")
+        want = (B, ASR_UPSAMPLE * N, ASR_CLASSES)
+        if out is None:
+            out = torch.empty(want, device=self.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != want or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"asr_logprobs: out must be a contiguous fp32 {want} tensor on the engine's device")
+        tab = self._upload_i32([ns])
+        ws = self._workspace(self.lib.smtts_asr_workspace_bytes(self.h, B, N))
+        self._ck(self.lib.smtts_asr_logprobs(self.h, self._stream(), _p(x), _p(tab[0]), B, N, _p(ws), ws.numel(), _p(out)), "asr_logprobs")
+        return out
+
+    def ctc_score(self, logp: torch.Tensor, ts, tokens: torch.Tensor, p0, p1) -> torch.Tensor:
+        """CTC negative log-likelihood of every row (smtts_ctc_score; the definition: include/smalltts_hip.h).  logp fp32
+        (B,T,C) and tokens int32 (B,P), contiguous on the device, P <= 198, C <= 256; ts the frames per row, [p0[b], p1[b]) the
+        target tokens of row b (host integers).  -> nll fp32 (B) on the device: F.ctc_loss(blank=0, reduction='none'), +inf for an
+        empty or infeasible row.  Needs no weights.  One launch on the current stream, no synchronisation."""
+        if logp.dim() != 3 or logp.dtype != torch.float32 or not logp.is_contiguous() or logp.device != self.device:
+            raise ValueError("ctc_score: logp must be a contiguous fp32 (B,T,C) tensor on the engine's device")
+        B, T, Cn = (int(v) for v in logp.shape)
+        if tokens.dim() != 2 or tokens.dtype != torch.int32 or not tokens.is_contiguous() or tokens.device != self.device or tokens.shape[0] != B:
+            raise ValueError(f"ctc_score: tokens must be a contiguous int32 ({B},P) tensor on the engine's device")
+        P = int(tokens.shape[1])
+        if not (T >= 1 and 1 <= P <= ALIGN_MAX_TOKENS and 2 <= Cn <= 256):
+            raise ValueError(f"ctc_score: T = {T}, P = {P}, C = {Cn} outside the supported range T >= 1, P <= {ALIGN_MAX_TOKENS}, 2 <= C <= 256")
+        if B < 1 or len(ts) != B or len(p0) != B or len(p1) != B:
+            raise ValueError("ctc_score: one frame count and one token range per row")
+        tab = self._upload_i32([ts, p0, p1])
+        nll = torch.empty(B, device=self.device)
+        self._ck(self.lib.smtts_ctc_score(self.h, self._stream(), _p(logp), _p(tab[0]), _p(tokens), _p(tab[1]), _p(tab[2]), B, T, P, Cn,
+                                          _p(nll)), "ctc_score")
+        return nll
+
+    def ctc_greedy(self, logp: torch.Tensor, ts):
+        """Greedy CTC transcript of every row (smtts_ctc_greedy): per-frame argmax (lowest class on ties), runs collapsed, class 0
+        dropped.  logp fp32 (B,T,C) contiguous on the device, T <= 4096; ts the frames per row (host integers).  -> (ids int32 (B,T),
+        zeros behind the count; n_ids int32 (B)), on the device.  Needs no weights.  One launch, no synchronisation."""
+        if logp.dim() != 3 or logp.dtype != torch.float32 or not logp.is_contiguous() or logp.device != self.device:
+            raise ValueError("ctc_greedy: logp must be a contiguous fp32 (B,T,C) tensor on the engine's device")
+        B, T, Cn = (int(v) for v in logp.shape)
+        if not (1 <= T <= 4096 and Cn >= 1):
+            raise ValueError(f"ctc_greedy: T = {T}, C = {Cn} outside the supported range 1 <= T <= 4096, C >= 1")
+        if B < 1 or len(ts) != B:
+            raise ValueError("ctc_greedy: one frame count per row")
+        tab = self._upload_i32([ts])
+        ids = torch.empty(B, T, dtype=torch.int32, device=self.device)
+        n_ids = torch.empty(B, dtype=torch.int32, device=self.device)
+        self._ck(self.lib.smtts_ctc_greedy(self.h, self._stream(), _p(logp), _p(tab[0]), B, T, Cn, _p(ids), _p(n_ids)), "ctc_greedy")
+        return ids, n_ids
 
     def _upload_i32(self, rows) -> torch.Tensor:
         """Small per-call host table -> device int32 on the current stream, through pinned staging (no synchronising copy)."""

@@ -8,6 +8,9 @@ next to it out.words.srt with one cue per word group.  --take OUT.npz: the piece
 piece's token spans) and the join parameters, what scripts/respeak.py re-speaks a span of and renders again.
 --takes K: every piece is sampled K times and the take whose text alignment scores best is kept (api.Takes; what the score is worth is
 unvalidated on trained weights); with --words the JSON becomes {"words": [...], "takes": [{piece, winner, seed, totals}, ...]}.
+--ctc W (with --takes; loads the latent phoneme recogniser, api.SmallTTS(recogniser=True)): the score gains W * CTC nll / tokens of the
+recogniser's reading of every take (api.Takes(ctc=); unvalidated like the rest of the score, not with --repair), and every
+entry of "takes" in the --words JSON gains "nll", the K values.
 --repair [ROUNDS]: behind the sampler (and --takes) only the badly aligned words of every piece are spoken again, ROUNDS times
 (default 1), and a repaired piece is kept where it scores strictly better (api.Repair; unvalidated on trained weights like --takes);
 with --words the JSON gains "repair": [{piece, kept, bad, free, before, after}, ...], one list entry per round in each field.
@@ -50,8 +53,9 @@ def words_json(words, texts, takes=None, repair=None) -> str:
     if takes is not None or repair is not None:
         rows = {"words": rows}
     if takes is not None:
-        rows["takes"] = [{"piece": i, "winner": int(w), "seed": int(sd), "totals": [fin(v) for v in tot]}
-                         for i, (w, sd, tot, _feat) in enumerate(takes)]
+        rows["takes"] = [{"piece": i, "winner": int(t[0]), "seed": int(t[1]), "totals": [fin(v) for v in t[2]],
+                          **({"nll": [fin(v) for v in t[4]]} if len(t) > 4 else {})}      # (Takes(ctc > 0) reports the K values of nll too)
+                         for i, t in enumerate(takes)]
     if repair is not None:
         rows["repair"] = [{"piece": i, "kept": [int(v) for v in kept], "bad": [int(c[0]) for c in counts], "free": [int(c[1]) for c in counts],
                            "before": [fin(v) for v in before], "after": [fin(v) for v in after]}
@@ -108,6 +112,8 @@ def parse_args(argv=None):
     ap.add_argument("--srt", default=None, metavar="OUT.srt", help="write one subtitle cue per piece, and OUT.words.srt with one cue per word group")
     ap.add_argument("--take", default=None, metavar="OUT.npz", help="save the pieces and the join parameters (for scripts/respeak.py)")
     ap.add_argument("--takes", type=int, default=None, metavar="K", help=f"sample every piece K times (1..{Takes.MAX_K}) and keep the best-aligned take")
+    ap.add_argument("--ctc", type=float, default=None, metavar="W",
+                    help="with --takes: add W * CTC nll / tokens of the latent phoneme recogniser to every take's score (loads the recogniser)")
     ap.add_argument("--repair", type=int, nargs="?", const=1, default=None, metavar="ROUNDS",
                     help=f"speak only the badly aligned words of every piece again, ROUNDS times (1..{Repair.MAX_ROUNDS}, default 1)")
     ap.add_argument("--max-batch", type=int, default=8)
@@ -141,6 +147,10 @@ def parse_args(argv=None):
         ap.error(f"--takes must lie in [1, {Takes.MAX_K}]")
     if args.repair is not None and not 1 <= args.repair <= Repair.MAX_ROUNDS:
         ap.error(f"--repair must lie in [1, {Repair.MAX_ROUNDS}]")
+    if args.ctc is not None and (args.takes is None or not args.ctc >= 0.0 or args.ctc == float("inf")):
+        ap.error("--ctc takes a finite weight >= 0 and needs --takes")
+    if args.ctc and args.repair is not None:
+        ap.error("--ctc and --repair exclude each other (repair's keep rule scores without the CTC term)")
     if args.takes is not None and args.takes * args.max_batch > Takes.MAX_ROWS:
         args.max_batch = Takes.MAX_ROWS // args.takes   # synthesize_long's rule, applied here so that --take records the group size used
     return args
@@ -150,7 +160,8 @@ def main(argv=None):
     args = parse_args(argv)
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     print("loading")
-    tts = SmallTTS(weights=args.weights, device=args.device, precision=args.precision, num_steps=args.steps, seed=args.seed)
+    tts = SmallTTS(weights=args.weights, device=args.device, precision=args.precision, num_steps=args.steps, seed=args.seed,
+                   recogniser=bool(args.ctc))
     print("encoding reference audio")
     y, sr = read_wav(args.wav)
     if y.ndim == 2:
@@ -167,7 +178,7 @@ def main(argv=None):
     if args.take:
         kw.update(return_pieces=True)
     if args.takes is not None:
-        kw.update(takes=args.takes, return_takes=True)
+        kw.update(takes=Takes(args.takes, ctc=args.ctc) if args.ctc else args.takes, return_takes=True)
     if args.repair is not None:
         kw.update(repair=args.repair, return_repair=True)
     speak = tts.synthesize_long if not args.stream else (lambda *a, **k: stream_to_wav(tts, args, dv, *a, **k))
@@ -196,7 +207,7 @@ def main(argv=None):
         print("repaired: " + " ".join(str(int(sum(kept))) for kept, _counts, _before, _after in mended))
     if args.takes is not None:
         audio, chosen = (audio[:-1] if len(audio) > 2 else audio[0]), audio[-1]
-        print("takes kept: " + " ".join(str(w) for w, _seed, _tot, _feat in chosen))
+        print("takes kept: " + " ".join(str(t[0]) for t in chosen))
     if args.take:
         audio, taken = (audio[:-1] if timed else audio[0]), audio[-1]
         Path(args.take).parent.mkdir(parents=True, exist_ok=True)

@@ -1,5 +1,5 @@
 """python -m smalltts_amd.scripts.respeak --take T.npz --wav ref.wav --piece I (--frames A:B | --groups A:B) [--seed S]
-    [--start-step K] [--takes K] --out out.wav [--take-out T2.npz]
+    [--start-step K] [--takes K [--ctc W]] --out out.wav [--take-out T2.npz]
 Speaks a span of one piece of a long take again and keeps everything else: the take (scripts/longform.py --take) holds every piece's
 tokens and latents; frames [A, B) of piece I, or the frames its token groups [A, B) touch (the spans longform --words saved), are
 regenerated with the rest of the piece pinned (api.SmallTTS.respeak), the whole take is rendered again with its own join parameters
@@ -7,7 +7,8 @@ regenerated with the rest of the piece pinned (api.SmallTTS.respeak), the whole 
 --tokens: the piece's new token list when the text changes (the take's prefix is prepended); --new-frames: the length of the
 regenerated region.  --takes K: the span is re-spoken K times, every take with the same pins, and the best-aligned one is kept
 (api.Takes; the updated take records the winner's seed).  Only the mechanism is verified: how well the 4-step student inpaints, and
-what the takes' score is worth, are unvalidated on trained weights."""
+what the takes' score is worth, are unvalidated on trained weights.  --ctc W: the takes' score gains W * CTC nll / tokens of the latent
+phoneme recogniser (api.Takes(ctc=); loads the recogniser; unvalidated in the same way)."""
 import argparse
 from pathlib import Path
 
@@ -53,6 +54,8 @@ def main(argv=None):
     ap.add_argument("--new-frames", type=int, default=None, help="length of the regenerated region (default: B - A frames)")
     ap.add_argument("--start-step", type=int, default=0, help="run only the sampler steps from K on, from the take's latents")
     ap.add_argument("--takes", type=int, default=None, metavar="K", help=f"re-speak the span K times (1..{Takes.MAX_K}) and keep the best-aligned take")
+    ap.add_argument("--ctc", type=float, default=None, metavar="W",
+                    help="with --takes: add W * CTC nll / tokens of the latent phoneme recogniser to every take's score (loads the recogniser)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--take-out", default=None, metavar="T2.npz", help="where the updated take goes (default: next to --out)")
     add_engine_args(ap)
@@ -62,6 +65,8 @@ def main(argv=None):
         ap.error(f"--piece must lie in [0, {len(pieces)})")
     if args.takes is not None and not 1 <= args.takes <= Takes.MAX_K:
         ap.error(f"--takes must lie in [1, {Takes.MAX_K}]")
+    if args.ctc is not None and (args.takes is None or not args.ctc >= 0.0 or args.ctc == float("inf")):
+        ap.error("--ctc takes a finite weight >= 0 and needs --takes")
     old = pieces[args.piece]
     try:
         f0, f1 = span_frames(old, args.frames, args.groups)
@@ -69,7 +74,8 @@ def main(argv=None):
         ap.error(str(e))
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     print("loading")
-    tts = SmallTTS(weights=args.weights, device=args.device, precision=args.precision, num_steps=args.steps, seed=args.seed)
+    tts = SmallTTS(weights=args.weights, device=args.device, precision=args.precision, num_steps=args.steps, seed=args.seed,
+                   recogniser=bool(args.ctc))
     print("encoding reference audio")
     y, sr = read_wav(args.wav)
     if y.ndim == 2:
@@ -84,7 +90,7 @@ def main(argv=None):
     res = tts.respeak(old.tokens, old.latents, (f0, f1), voice=voice, new_tokens=tokens, new_frames=args.new_frames, seed=seed,
                       start_step=args.start_step, prefix_len=old.prefix_len,
                       **({"align": True, "return_alignment": True} if timed else {}),
-                      **({} if args.takes is None else {"takes": args.takes, "return_takes": True}))
+                      **({} if args.takes is None else {"takes": Takes(args.takes, ctc=args.ctc) if args.ctc else args.takes, "return_takes": True}))
     if args.takes is not None:
         winner, seed = res[-1][0], res[-1][1]
         print(f"take {winner} of {args.takes} kept (seed {seed})")

@@ -283,6 +283,41 @@ def codec_encoder_param_specs(spec: CodecSpec = DEFAULT_CODEC):
     return [t for t in s if _optional(spec, t[0])]
 
 
+# the latent phoneme recogniser (reference models/asr.py: ASR(64) = upsample x4, torchaudio Conformer, Linear to PHONEME_VOCAB)
+ASR_DIM = 64
+ASR_HEADS = 16
+ASR_FF = 1024
+ASR_LAYERS = 7
+ASR_CONV_K = 9
+ASR_UPSAMPLE = 4
+
+
+def asr_param_specs() -> List[Tuple[str, Tuple[int, ...]]]:
+    """State dict of ASR(64) under the prefix "asr." (num_batches_tracked of the BatchNorm left out: it is not a parameter of the
+    forward pass).  Not part of all_param_specs(): the recogniser is an optional part (engine part 3)."""
+    d, ff, k = ASR_DIM, ASR_FF, ASR_CONV_K
+    specs: List[Tuple[str, Tuple[int, ...]]] = [("asr.upsample.deconv.weight", (d, 1, ASR_UPSAMPLE)), ("asr.upsample.deconv.bias", (d,))]
+    for i in range(ASR_LAYERS):
+        p = f"asr.encoder.conformer_layers.{i}."
+        for f in ("ffn1", "ffn2"):
+            q = p + f + ".sequential."
+            specs += [(q + "0.weight", (d,)), (q + "0.bias", (d,)), (q + "1.weight", (ff, d)), (q + "1.bias", (ff,)),
+                      (q + "4.weight", (d, ff)), (q + "4.bias", (d,))]
+        specs += [(p + "self_attn_layer_norm.weight", (d,)), (p + "self_attn_layer_norm.bias", (d,)),
+                  (p + "self_attn.in_proj_weight", (3 * d, d)), (p + "self_attn.in_proj_bias", (3 * d,)),
+                  (p + "self_attn.out_proj.weight", (d, d)), (p + "self_attn.out_proj.bias", (d,))]
+        c = p + "conv_module."
+        specs += [(c + "layer_norm.weight", (d,)), (c + "layer_norm.bias", (d,)),
+                  (c + "sequential.0.weight", (2 * d, d, 1)), (c + "sequential.0.bias", (2 * d,)),
+                  (c + "sequential.2.weight", (d, 1, k)), (c + "sequential.2.bias", (d,)),
+                  (c + "sequential.3.weight", (d,)), (c + "sequential.3.bias", (d,)),
+                  (c + "sequential.3.running_mean", (d,)), (c + "sequential.3.running_var", (d,)),
+                  (c + "sequential.5.weight", (d, d, 1)), (c + "sequential.5.bias", (d,))]
+        specs += [(p + "final_layer_norm.weight", (d,)), (p + "final_layer_norm.bias", (d,))]
+    specs += [("asr.proj.weight", (PHONEME_VOCAB, d)), ("asr.proj.bias", (PHONEME_VOCAB,))]
+    return specs
+
+
 def all_param_specs(spec: CodecSpec = DEFAULT_CODEC):
     return dit_param_specs() + codec_decoder_param_specs(spec) + codec_encoder_param_specs(spec)
 
@@ -307,6 +342,15 @@ def init_rule(name: str, shape: Tuple[int, ...]) -> Tuple[float, float]:
     leaf = name.rsplit(".", 1)[-1]
     if len(shape) == 0:                                   # style_encoder.log_scale (style.py:134)
         return -1.8, 0.1
+    if name.startswith("asr."):                           # the recogniser's own leaves; everything else of it falls through
+        if leaf == "running_var":
+            return 1.0, 0.5                               # (> 0: BatchNorm divides by its root)
+        if leaf == "running_mean":
+            return 0.0, 0.1
+        if name.endswith("conv_module.sequential.3.weight"):   # the BatchNorm scale
+            return 1.0, 0.2
+        if leaf == "in_proj_bias":
+            return 0.0, 0.1
     if leaf in ("gamma", "ffn_gamma"):                    # codec layer scales
         return 0.5, 0.2
     is_norm = (name.endswith("norm.weight") or name.endswith("norm_cross.weight"))
