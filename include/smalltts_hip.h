@@ -99,7 +99,7 @@ int smtts_get_saturations(smtts_handle h, uint32_t* counts, int n_sites, int res
 int smtts_peek_saturations(smtts_handle h, uint32_t* counts, int n_sites);
 const char* smtts_range_report(smtts_handle h);      /* "" when every fused FFN block was certified */
 float smtts_range_worst_bound(smtts_handle h);       /* largest certified bound of the last finalize (fp16 max: 65504) */
-int smtts_has_part(smtts_handle h, int part); /* 0 dit, 1 codec decoder, 2 codec encoder, 3 latent phoneme recogniser (asr.* tensors) */
+int smtts_has_part(smtts_handle h, int part); /* 0 dit, 1 codec decoder, 2 codec encoder, 3 latent phoneme recogniser (asr.* tensors), 4 latent speaker verifier (sv.* tensors) */
 
 /* ---- condition encoder ---------------------------------------------------------------------- */
 size_t smtts_cond_workspace_bytes(smtts_handle h, int B, int R, int P);
@@ -297,6 +297,29 @@ int smtts_ctc_score(smtts_handle h, void* stream, const float* logp, const int32
                     const int32_t* p1, int B, int T, int P, int C, float* nll);
 int smtts_ctc_greedy(smtts_handle h, void* stream, const float* logp, const int32_t* t_len, int B, int T, int C, int32_t* ids,
                      int32_t* n_ids);
+
+/* ---- Speaker score (DESIGN.md '8j. Speaker score'): the latent speaker verifier on the device ---------------------------------------
+ * smtts_sv_embed replaces the reference's SV(192).forward (src/smalltts/models/sv/model.py:26-35: speechbrain's ECAPA_TDNN on the 64-dim
+ * latents, lengths / max as its relative lengths) for an engine that was given the sv.* tensors (smtts_has_part(h, 4)).  x f32 (B,N,64)
+ * latents, n_len i32 (B) frames per row (clamped into [0, N]), both DEVICE -> emb f32 (B, 192), not normalised.  Every row is computed
+ * as if it were alone in its batch at its own length: reflect padding reflects about the row's own first and last frame and every mean,
+ * softmax and statistic runs over [0, n_b), so nothing at or behind n_len[b] of x reaches a result (what the reference computes for a
+ * batch of one).  A row with n_b < 6 has no embedding (the dilation-5 reflect padding needs more frames than it pads): its emb row is
+ * written as 0.0.  fp32 operands and accumulation; no atomics: two runs, alone or inside any batch, return the same bits.  ws: at least
+ * smtts_sv_workspace_bytes(h, B, N) bytes, 256-byte aligned, contents irrelevant; x, n_len, emb 4-byte aligned.  1 <= B <= 64 and
+ * 6 <= N <= 225, anything else (and an engine without the part) is an error; the size query returns 0 outside the range.
+ *
+ * smtts_sv_cosine replaces cosine_loss's similarity of the reference's distillation loss (src/scripts/train/dmd2/distill.py:30-31,
+ * 351-353) as a score: row b of emb f32 (B,D) against row b / K of ref f32 (B/K,D), both DEVICE -> cos f32 (B) =
+ * (a . r) / (max(||a||, 1e-8) max(||r||, 1e-8)), F.cosine_similarity's rule: a zero row gives 0.  1 <= B <= 65536, 1 <= K <= 16,
+ * B % K == 0, 1 <= D <= 1024.  Needs no weights: works on any handle.
+ * Both: one stream, no synchronisation, an argument error enqueues nothing.
+ * Limits: the score is unvalidated on trained weights (every weight this project has run is seeded noise); the ECAPA composition and
+ * its state-dict names are restated from recollection, unpinned; no verifier checkpoint has ever been loaded. */
+size_t smtts_sv_workspace_bytes(smtts_handle h, int B, int N);
+int smtts_sv_embed(smtts_handle h, void* stream, const float* x, const int32_t* n_len, int B, int N, void* ws, size_t ws_bytes,
+                   float* emb);
+int smtts_sv_cosine(smtts_handle h, void* stream, const float* emb, const float* ref, int B, int K, int D, float* cos);
 
 /* ---- codec ------------------------------------------------------------------------------------ */
 int smtts_codec_hop(smtts_handle h);

@@ -20,8 +20,8 @@ from typing import Callable, Dict, Iterable, List, NamedTuple, Optional, Sequenc
 import numpy as np
 import torch
 
-from .engine import ASR_MAX_ROWS, ASR_UPSAMPLE, DEFAULT_PRECISION, SITES, HipEngine
-from .weights import DEFAULT_CODEC, CodecSpec, all_param_specs, asr_param_specs, load_weight_file
+from .engine import ASR_MAX_ROWS, ASR_UPSAMPLE, DEFAULT_PRECISION, SITES, SV_DIM, SV_MAX_ROWS, SV_MIN_FRAMES, HipEngine
+from .weights import DEFAULT_CODEC, CodecSpec, all_param_specs, asr_param_specs, load_weight_file, sv_param_specs
 
 SAMPLE_RATE = 24_000
 HOP_SIZE = 3_200
@@ -321,12 +321,20 @@ class Takes:
     (engine part "asr", SmallTTS(recogniser=True)) reads every take's latents, nll = the CTC negative log-likelihood of the row's
     spoken tokens (smtts_ctc_score), and total' = total + (ctc * nll) / tokens, three single fp32 operations in that order.  It asks
     "were these phonemes spoken?" and is the quantity the 4-step student was distilled to make small; UNVALIDATED in the same way:
-    no recogniser checkpoint has ever been loaded, and its Conformer composition is restated from recollection.  Not with repair=."""
-    __slots__ = ("k", "weights", "tau_token", "tau_frame", "ctc")
+    no recogniser checkpoint has ever been loaded, and its Conformer composition is restated from recollection.  Not with repair=.
+
+    `sv` (>= 0, default 0 = off: not one launch more, not one bit changed): a speaker term.  The latent speaker verifier
+    (engine part "sv", SmallTTS(verifier=True)) embeds every take's latents (smtts_sv_embed), cos = the cosine of that embedding with
+    the reference voice's (smtts_sv_cosine; the Voice's `speaker`, or the embedding of the row's ref_latents), and
+    total' = total + sv * (1 - cos), three single fp32 operations in that order, behind the CTC term where that is on.  It asks "does
+    this take sound like the reference voice?" and is the third quantity the 4-step student was distilled to make small; UNVALIDATED
+    in the same way: no verifier checkpoint has ever been loaded, its ECAPA composition is restated from recollection, and the weight
+    is a design choice.  Every row and every reference needs 6 to 225 frames.  Not with repair=."""
+    __slots__ = ("k", "weights", "tau_token", "tau_frame", "ctc", "sv")
     MAX_K, MAX_ROWS = 16, 64   # smtts_take_select's K; the largest sampler batch the tap is tested at
 
     def __init__(self, k: int, weights: Sequence[float] = (1.0, 2.0, 1.0, 1.0), tau_token: float = 0.1, tau_frame: float = 0.1,
-                 ctc: float = 0.0) -> None:
+                 ctc: float = 0.0, sv: float = 0.0) -> None:
         if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
             raise TypeError(f"Takes: k must be an integer, got {type(k).__name__}")
         if not 1 <= int(k) <= self.MAX_K:
@@ -338,8 +346,11 @@ class Takes:
             raise ValueError("Takes: tau_token and tau_frame must be finite")
         if isinstance(ctc, bool) or not (np.isfinite(float(ctc)) and float(ctc) >= 0.0):
             raise ValueError(f"Takes: ctc must be a finite number >= 0, got {ctc!r}")
+        if isinstance(sv, bool) or not (np.isfinite(float(sv)) and float(sv) >= 0.0):
+            raise ValueError(f"Takes: sv must be a finite number >= 0, got {sv!r}")
         set_ = object.__setattr__
         set_(self, "ctc", float(ctc))
+        set_(self, "sv", float(sv))
         set_(self, "k", int(k))
         set_(self, "weights", w)
         set_(self, "tau_token", float(tau_token))
@@ -744,7 +755,7 @@ def _split_sources(weights) -> List[str]:
 def _validated(tensors: Dict[str, object], source: str, codec: CodecSpec) -> Dict[str, object]:
     """Reject a tensor whose shape is not the inventory's BEFORE it reaches the packers: the kernels assume the model's
     strides (960 / 2400 / 512 ...), so a checkpoint of another model size must be a clean error naming the tensor."""
-    want = dict(all_param_specs(codec) + asr_param_specs())
+    want = dict(all_param_specs(codec) + asr_param_specs() + sv_param_specs())
     bad = [(k, tuple(v.shape), want[k]) for k, v in tensors.items() if k in want and tuple(v.shape) != tuple(want[k])]
     if bad:
         k, got, exp = bad[0]
@@ -772,7 +783,7 @@ def _load_weights_into(eng: HipEngine, weights, parts: Sequence[str]) -> None:
       * ``synthetic[:seed]``       seeded random weights for every requested part NOT provided by an earlier source.
     e.g. ``"dmd.pt+codec.smtts"`` (DiT checkpoint + separately converted codec) or ``"dmd.pt+synthetic:7"``."""
     have: set = set()
-    prefixes = {"dit": ("velocity.",), "decoder": ("codec.decoder.",), "encoder": ("codec.encoder.",), "asr": ("asr.",)}
+    prefixes = {"dit": ("velocity.",), "decoder": ("codec.decoder.",), "encoder": ("codec.encoder.",), "asr": ("asr.",), "sv": ("sv.",)}
     codec = eng.codec_spec
 
     def note(names):
@@ -812,10 +823,11 @@ def _load_weights_into(eng: HipEngine, weights, parts: Sequence[str]) -> None:
 def get_engine(weights: Optional[str] = None, device: int = 0, precision: str = DEFAULT_PRECISION,
                parts: Sequence[str] = ("dit", "decoder", "encoder")) -> HipEngine:
     """One engine (one weight copy) per (weights, device, parts); shared by SmallTTS/Encoder/Decoder.  parts: of "dit", "decoder",
-    "encoder" and "asr" (the latent phoneme recogniser, DESIGN 8i: optional, not among the defaults)."""
-    unknown = [p for p in parts if p not in ("dit", "decoder", "encoder", "asr")]
+    "encoder", "asr" (the latent phoneme recogniser) and "sv" (the latent speaker verifier); the last two are
+    optional and not among the defaults."""
+    unknown = [p for p in parts if p not in ("dit", "decoder", "encoder", "asr", "sv")]
     if unknown:
-        raise ValueError(f"get_engine: unknown part {unknown[0]!r} (dit, decoder, encoder, asr)")
+        raise ValueError(f"get_engine: unknown part {unknown[0]!r} (dit, decoder, encoder, asr, sv)")
     weights = weights or DEFAULT_WEIGHTS
     key = ("+".join(_split_sources(weights)), int(device), tuple(sorted(parts)))
     eng = _ENGINES.get(key)
@@ -880,11 +892,14 @@ def _frames(duration_sec: float) -> int:
 class Voice:
     """A reference voice encoded once: the reference half of the cross-KV cache, `k_ref` / `v_ref` (12, 1, 8, R, 120) fp32 on the
     engine's device (what cond_encode returns for this reference at B = 1), its length `R` and the `engine` it belongs to.
+    `speaker`: the reference's speaker embedding, a (192,) fp32 tensor on the device (engine.sv_embed of the reference latents;
+    DESIGN 8j), or None: the engine held no verifier part when the voice was encoded, or the reference is under 6 or over 225 frames.
     Immutable; any number of calls (and batches in flight) of that engine may read it."""
-    __slots__ = ("engine", "k_ref", "v_ref", "R")
+    __slots__ = ("engine", "k_ref", "v_ref", "R", "speaker")
 
-    def __init__(self, engine: HipEngine, k_ref: torch.Tensor, v_ref: torch.Tensor) -> None:
+    def __init__(self, engine: HipEngine, k_ref: torch.Tensor, v_ref: torch.Tensor, speaker: Optional[torch.Tensor] = None) -> None:
         set_ = object.__setattr__
+        set_(self, "speaker", speaker)
         set_(self, "engine", engine)
         set_(self, "k_ref", k_ref)
         set_(self, "v_ref", v_ref)
@@ -913,6 +928,7 @@ class _Batch(NamedTuple):
     total: Optional[torch.Tensor] = None   # takes=: (B * K,) fp32, every take's total, piece-major (engine.take_scores), else None
     feat: Optional[torch.Tensor] = None    # takes=: (B * K, 4) int32 (cells, skipped, longest, idle), else None
     nll: Optional[torch.Tensor] = None     # Takes(ctc > 0): (B * K,) fp32, every take's CTC nll, piece-major (engine.ctc_score), else None
+    cos: Optional[torch.Tensor] = None     # Takes(sv > 0): (B * K,) fp32, every take's cosine with its reference voice (engine.sv_cosine), else None
     rp_kept: Optional[List[torch.Tensor]] = None     # repair=: per round (B,) int32, 1 where the repaired row was kept (engine.repair_keep)
     rp_counts: Optional[List[torch.Tensor]] = None   # repair=: per round (B, 2) int32 (bad tokens, freed frames) (engine.repair_plan)
     rp_totals: Optional[List[torch.Tensor]] = None   # repair=: rounds + 1 (B,) fp32: the rows' totals before round 1 and after every round
@@ -957,6 +973,44 @@ def check_takes_ctc(what: str, tk: Optional["Takes"], rp: Optional["Repair"], en
     return True
 
 
+def _read_cos(recs: Sequence[_Batch], K: int) -> np.ndarray:
+    """The speaker term of Takes(sv > 0) of finished batches, in one small read-back: -> cos (n, K) fp32 over the rows of all records."""
+    return torch.cat([rec.cos for rec in recs]).cpu().numpy().reshape(-1, K)
+
+
+def _takes_extra(recs: Sequence[_Batch], K: int, n: int) -> List[tuple]:
+    """What return_takes appends to every row's tuple: nll (K,) with Takes(ctc > 0), then cos (K,) with Takes(sv > 0)."""
+    extra = [()] * n
+    if recs[0].nll is not None:
+        extra = [e + (v,) for e, v in zip(extra, _read_nll(recs, K))]
+    if recs[0].cos is not None:
+        extra = [e + (v,) for e, v in zip(extra, _read_cos(recs, K))]
+    return extra
+
+
+def check_takes_sv(what: str, tk: Optional["Takes"], rp: Optional["Repair"], eng: HipEngine, ns: Optional[Sequence[int]] = None,
+                   voices: Optional[Sequence["Voice"]] = None, rs: Optional[Sequence[int]] = None) -> bool:
+    """Takes(sv > 0) asks for the verifier part, excludes repair= (its keep rule re-scores with take_scores alone), and needs 6 to 225
+    frames in every row (`ns`) and an embedding for every reference: the `speaker` of every Voice, or 6 to 225 reference frames
+    (`rs`).  Everything is checked in front of any launch.  -> whether the speaker term is on."""
+    if tk is None or tk.sv == 0.0:
+        return False
+    if rp is not None:
+        raise ValueError(f"{what}: Takes(sv > 0) and repair= exclude each other (repair's keep rule scores without the speaker term)")
+    if not eng.has("sv"):
+        raise ValueError(f"{what}: Takes(sv > 0) needs the verifier part (SmallTTS(verifier=True) or get_engine(parts=(..., 'sv')))")
+    if ns is not None and any(n < SV_MIN_FRAMES or n > ALIGN_MAX_FRAMES for n in ns):
+        raise ValueError(f"{what}: Takes(sv > 0) needs {SV_MIN_FRAMES} to {ALIGN_MAX_FRAMES} frames in every row (a shorter row has no "
+                         f"speaker embedding), got {min(ns)} .. {max(ns)}")
+    if voices is not None and any(v.speaker is None for v in voices):
+        raise ValueError(f"{what}: Takes(sv > 0) needs a Voice with a speaker embedding (encode it on an engine with the verifier part, "
+                         f"from {SV_MIN_FRAMES} to {ALIGN_MAX_FRAMES} reference frames)")
+    if voices is None and rs is not None and any(r < SV_MIN_FRAMES or r > ALIGN_MAX_FRAMES for r in rs):
+        raise ValueError(f"{what}: Takes(sv > 0) needs {SV_MIN_FRAMES} to {ALIGN_MAX_FRAMES} reference frames in every row "
+                         f"(a shorter reference has no speaker embedding)")
+    return True
+
+
 def _read_repair(recs: Sequence[_Batch]) -> List[tuple]:
     """What repair= left in finished batches, in ONE small read-back: per row of all records in order -> (kept (rounds,) int32,
     counts (rounds, 2) int32 = (bad tokens, freed frames) of every round's plan, before (rounds,) fp32 and after (rounds,) fp32, the
@@ -989,20 +1043,24 @@ class SmallTTS:
                  codec_decoder_path: str = "assets/codec/decoder.onnx",
                  providers: Optional[Iterable[str]] = None, *, weights: Optional[str] = None, device: int = 0,
                  precision: str = DEFAULT_PRECISION, num_steps: int = NUM_STEPS, seed: Optional[int] = None,
-                 engine: Optional[HipEngine] = None, device_ids: Optional[Sequence[int]] = None, recogniser: bool = False) -> None:
+                 engine: Optional[HipEngine] = None, device_ids: Optional[Sequence[int]] = None, recogniser: bool = False,
+                 verifier: bool = False) -> None:
         """Keyword-only additions to the reference signature (infer/onnx.py:53-59): `weights`, `device`, `precision`,
         `num_steps`, `seed`, and `device_ids` — the GPUs `synthesize_sharded` spreads a request list over from THIS process
         (one weight replica, engine and host thread per GPU; under torch.distributed the process group is used instead).
         `recogniser=True` adds the latent phoneme recogniser (engine part "asr") to this instance's engine: transcribe(),
-        ctc_score() and Takes(ctc=) need it."""
+        ctc_score() and Takes(ctc=) need it.  `verifier=True` adds the latent speaker verifier (engine part "sv"):
+        speaker_embedding(), speaker_similarity(), a Voice's `speaker` and Takes(sv=) need it."""
         if device_ids:
             device = int(device_ids[0])
-        parts = ("dit", "decoder", "encoder") + (("asr",) if recogniser else ())
+        parts = ("dit", "decoder", "encoder") + (("asr",) if recogniser else ()) + (("sv",) if verifier else ())
         self.engine = engine or get_engine(weights, device, precision, parts=parts)
         if not (self.engine.has("dit") and self.engine.has("decoder")):
             raise RuntimeError("SmallTTS needs DiT and codec-decoder weights")
         if recogniser and not self.engine.has("asr"):
             raise RuntimeError("SmallTTS(recogniser=True): the engine holds no recogniser part (asr.* tensors)")
+        if verifier and not self.engine.has("sv"):
+            raise RuntimeError("SmallTTS(verifier=True): the engine holds no verifier part (sv.* tensors)")
         self.num_steps = int(num_steps)
         self._seed = seed
         self._rng = np.random.default_rng(seed) if seed is not None else None
@@ -1033,7 +1091,10 @@ class SmallTTS:
             raise ValueError(f"encode_voice: reference latents must be (R, 64) with R >= 1, got {ref.shape}")
         cache = self.engine.cond_encode(ref[None], np.asarray([ref.shape[0]], np.int64), np.zeros((1, 0), np.int64),
                                         np.zeros((1, 0), bool))
-        return Voice(self.engine, cache["k_ref"], cache["v_ref"])
+        speaker = None
+        if self.engine.has("sv") and SV_MIN_FRAMES <= ref.shape[0] <= ALIGN_MAX_FRAMES:   # (a reference outside has no embedding)
+            speaker = self.engine.sv_embed(self.engine._dev(ref[None], torch.float32), [int(ref.shape[0])])[0]
+        return Voice(self.engine, cache["k_ref"], cache["v_ref"], speaker)
 
     def encode_voice_wav(self, audio, sr: int, trim=None) -> Voice:
         """Mono samples at `sr` Hz -> Voice: device resampler to 24 kHz, codec encoder (through Encoder.encode_reference and its
@@ -1059,11 +1120,33 @@ class SmallTTS:
         return self.encode_voice(lat[0].numpy())
 
     def _asr_rows(self, what: str, latents, lengths):
+        """_latent_rows for the recogniser's calls: the part, at most 64 rows of at most 225 frames."""
+        if not self.engine.has("asr"):
+            raise ValueError(f"{what}: needs the recogniser part (SmallTTS(recogniser=True))")
+        x, ns = self._latent_rows(what, latents, lengths)
+        B, N = int(x.shape[0]), int(x.shape[1])
+        if not (1 <= B <= ASR_MAX_ROWS and 1 <= N <= ALIGN_MAX_FRAMES):
+            raise ValueError(f"{what}: at most {ASR_MAX_ROWS} rows of at most {ALIGN_MAX_FRAMES} frames (got {B} x {N})")
+        return x, ns
+
+    def _sv_rows(self, what: str, latents, lengths):
+        """_latent_rows for the verifier's calls: the part, at most 64 rows, every row of 6 to 225 frames."""
+        if not self.engine.has("sv"):
+            raise ValueError(f"{what}: needs the verifier part (SmallTTS(verifier=True))")
+        x, ns = self._latent_rows(what, latents, lengths)
+        if not 1 <= len(ns) <= SV_MAX_ROWS:
+            raise ValueError(f"{what}: at most {SV_MAX_ROWS} rows, got {len(ns)}")
+        if any(n < SV_MIN_FRAMES or n > ALIGN_MAX_FRAMES for n in ns):
+            raise ValueError(f"{what}: every row needs {SV_MIN_FRAMES} to {ALIGN_MAX_FRAMES} frames (a shorter row has no speaker "
+                             f"embedding), got {min(ns)} .. {max(ns)}")
+        if int(x.shape[1]) > ALIGN_MAX_FRAMES:                  # padding behind the longest row
+            x = x[:, :max(ns)].contiguous()
+        return x, ns
+
+    def _latent_rows(self, what: str, latents, lengths):
         """-> (x (B, N, 64) fp32 on the device, frames per row): `latents` a (B, N, 64) array / tensor with `lengths` (None: N for every
         row), or a sequence of (n_b, 64) arrays (their own lengths)."""
         eng = self.engine
-        if not eng.has("asr"):
-            raise ValueError(f"{what}: needs the recogniser part (SmallTTS(recogniser=True))")
         if isinstance(latents, (np.ndarray, torch.Tensor)) and latents.ndim == 3:
             ns = [int(latents.shape[1])] * int(latents.shape[0]) if lengths is None else [int(v) for v in lengths]
             x = eng._dev(latents, torch.float32)
@@ -1081,9 +1164,40 @@ class SmallTTS:
         B, N = int(x.shape[0]), int(x.shape[1])
         if x.shape[2] != 64 or len(ns) != B or any(n < 0 or n > N for n in ns):
             raise ValueError(f"{what}: latents (B, N, 64) and one length in [0, N] per row")
-        if not (1 <= B <= ASR_MAX_ROWS and 1 <= N <= ALIGN_MAX_FRAMES):
-            raise ValueError(f"{what}: at most {ASR_MAX_ROWS} rows of at most {ALIGN_MAX_FRAMES} frames (got {B} x {N})")
         return x, ns
+
+    def speaker_embedding(self, latents, lengths=None) -> np.ndarray:
+        """(B, 192) float32: the latent speaker verifier's embedding of every row of latents (engine.sv_embed), not
+        normalised; every row is computed as if it were alone.  latents / lengths as transcribe().  Needs SmallTTS(verifier=True);
+        ValueError for a row under 6 or over 225 frames.  What the embedding is worth is unvalidated: no trained verifier checkpoint
+        has ever been loaded."""
+        x, ns = self._sv_rows("speaker_embedding", latents, lengths)
+        return self.engine.sv_embed(x, ns).cpu().numpy()
+
+    def speaker_similarity(self, latents, reference, lengths=None) -> List[float]:
+        """Per row the cosine of its speaker embedding with the reference's (engine.sv_embed, engine.sv_cosine), in
+        [-1, 1], higher = closer.  `reference`: a Voice (its `speaker`), one (R, 64) array of reference latents for every row, or a
+        sequence of such arrays, one per row.  ValueError for a row or a reference under 6 or over 225 frames, a Voice without an
+        embedding, and without the verifier part.  Unvalidated on trained weights like speaker_embedding()."""
+        what = "speaker_similarity"
+        x, ns = self._sv_rows(what, latents, lengths)
+        eng, B = self.engine, len(ns)
+        if isinstance(reference, Voice):
+            if reference.engine is not eng:
+                raise ValueError(f"{what}: the Voice belongs to another engine")
+            if reference.speaker is None:
+                raise ValueError(f"{what}: the Voice has no speaker embedding (encode it on an engine with the verifier part, from "
+                                 f"{SV_MIN_FRAMES} to {ALIGN_MAX_FRAMES} reference frames)")
+            ref = reference.speaker[None].expand(B, -1).contiguous()
+        else:
+            one = isinstance(reference, (np.ndarray, torch.Tensor)) and reference.ndim == 2
+            rx, rn = self._sv_rows(what + " (reference)", [reference] if one else list(reference), None)
+            if not one and len(rn) != B:
+                raise ValueError(f"{what}: one reference, or one per row ({B}), got {len(rn)}")
+            ref = eng.sv_embed(rx, rn)
+            if one:
+                ref = ref.expand(B, -1).contiguous()
+        return [float(v) for v in eng.sv_cosine(eng.sv_embed(x, ns), ref, 1).cpu().numpy()]
 
     def transcribe(self, latents, lengths=None) -> List[List[int]]:
         """Greedy phoneme ids of every row of latents: the recogniser's per-frame argmax (4 frames per latent frame), runs collapsed,
@@ -1200,6 +1314,7 @@ class SmallTTS:
         ctc_w = tk.ctc if check_takes_ctc("synthesize_batch", tk, rp, self.engine) and scored else 0.0
         if al is None and (return_alignment or (prefix_lens is not None and not scored)):   # (scored takes align too: they take prefix_lens)
             raise ValueError("synthesize_batch: prefix_lens= and return_alignment= belong to align=")
+        sv_on = check_takes_sv("synthesize_batch", tk, rp, self.engine) and scored   # (rows and references: below, once they are known)
         if voices is not None:
             if ref_latents is not None:
                 raise ValueError("synthesize_batch: pass either ref_latents or voices (with ref_latents=None), not both")
@@ -1219,6 +1334,9 @@ class SmallTTS:
         ns = [int(f) for f in frames] if frames is not None else [_frames(d) for d in durations]
         rs = [int(np.asarray(r).shape[0]) for r in ref_latents]
         ps = [len(p) for p in phoneme_ids]
+        if sv_on:
+            check_takes_sv("synthesize_batch", tk, rp, self.engine, ns, voices, rs)
+        sv_w = tk.sv if sv_on else 0.0
         if tk is not None and B * K > Takes.MAX_ROWS:
             raise ValueError(f"synthesize_batch: takes= runs at most {Takes.MAX_ROWS} sampler rows, got {B} rows x {K} takes")
         al_run = al if (al is not None or not scored) else Alignment()
@@ -1274,7 +1392,7 @@ class SmallTTS:
             if voices is not None:
                 cache.update(eng.voice_expand(s_voices))
             nz = noise if s_seeds is None else eng.randn_rows(s_seeds, s_ns, self.num_steps, n_max=Nm)
-            mass = spans = seg = gain = winner = total = feat = nll = None
+            mass = spans = seg = gain = winner = total = feat = nll = cos = None
             if al_run is None:
                 x = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, **pin_kw)
             else:
@@ -1288,6 +1406,11 @@ class SmallTTS:
                     pw = torch.tensor([float(max(0, p1 - p0)) for p0, p1 in zip(s_p0s, s_ps)], dtype=torch.float32).pin_memory()
                     nll = eng.ctc_score(eng.asr_logprobs(x, s_ns), [ASR_UPSAMPLE * n for n in s_ns], tok, s_p0s, s_ps)
                     total = total + (nll * ctc_w) / pw.to(eng.device, non_blocking=True)
+                if sv_w > 0.0:                                 # the speaker term: total' = total + sv * (1 - cos), single fp32 operations
+                    spk = (torch.stack([v.speaker for v in voices]) if voices is not None
+                           else eng.sv_embed(eng._dev(np.ascontiguousarray(ref[::K]), torch.float32), rs))
+                    cos = eng.sv_cosine(eng.sv_embed(x, s_ns), spk, K)
+                    total = total + (1.0 - cos) * sv_w
                 if K > 1:
                     x, _n, spans, mass, winner = eng.take_select(total, K, x, s_ns, spans, mass)
             rp_kept = rp_counts = rp_totals = None
@@ -1315,7 +1438,7 @@ class SmallTTS:
             audio = eng.codec_decode(x) if _decode else None   # (B, 1, HOP * Nm); causal => prefixes are exact (None: synthesize_stream decodes)
             if ep is not None:                                 # behind the decode, on the same stream
                 seg, gain, _e = eng.endpoints(audio, ns, ep)
-            return _Batch(audio, x, mass, spans, seg, gain, ns, run, winner, total, feat, nll, rp_kept, rp_counts, rp_totals)
+            return _Batch(audio, x, mass, spans, seg, gain, ns, run, winner, total, feat, nll, cos, rp_kept, rp_counts, rp_totals)
 
         rec = run()
         if _defer:                                             # synthesize_batches / synthesize_long / the server: stay on the device / stream
@@ -1372,7 +1495,7 @@ class SmallTTS:
         if takes is not None:
             K, row_seeds = takes
             win, tot, ft = _read_takes([rec], K)
-            extra = [()] * B if rec.nll is None else [(v,) for v in _read_nll([rec], K)]   # Takes(ctc > 0): the K values of nll too
+            extra = _takes_extra([rec], K, B)                  # Takes(ctc > 0): the K values of nll too; Takes(sv > 0): then the K cosines
             res.append([(int(win[b]), take_seed(row_seeds[b], int(win[b])) if K > 1 else int(row_seeds[b]), tot[b], ft[b]) + extra[b]
                         for b in range(B)])
         if return_repair:
@@ -1539,6 +1662,7 @@ class SmallTTS:
         if al is not None and not return_words and tk is None and rp is None:
             raise ValueError("synthesize_long: align= belongs to return_words=True")
         prefix, toks, ns = self._long_inputs("synthesize_long", voice, text, token_lists, durations, prefix_tokens)
+        check_takes_sv("synthesize_long", tk, rp, self.engine, ns or None, [voice])   # every piece, in front of the first batch
         eng = self.engine
         K = 1 if tk is None else tk.k
         if tk is not None and K * max_batch > Takes.MAX_ROWS:
@@ -1566,7 +1690,7 @@ class SmallTTS:
         if tk is not None and (return_takes or return_pieces):
             win, tot, ft = _read_takes(pending, K)             # one small read-back for the whole text
             spoken = [take_seed(seeds[i], int(win[i])) for i in range(len(toks))]  # what each piece was spoken from: the winner's seed
-            extra = [()] * len(toks) if pending[0].nll is None else [(v,) for v in _read_nll(pending, K)]   # Takes(ctc > 0): nll (K,) too
+            extra = _takes_extra(pending, K, len(toks))        # Takes(ctc > 0): nll (K,) too; Takes(sv > 0): then cos (K,)
             taken = [(int(win[i]), spoken[i], tot[i], ft[i]) + extra[i] for i in range(len(toks))]
         piece_spans: List[Optional[np.ndarray]] = [None] * len(toks)
         if return_words:
@@ -1665,6 +1789,7 @@ class SmallTTS:
         if al is not None and not return_words and tk is None and rp is None:
             raise ValueError("synthesize_long_stream: align= belongs to return_words=True")
         prefix, toks, ns = self._long_inputs("synthesize_long_stream", voice, text, token_lists, durations, prefix_tokens)
+        check_takes_sv("synthesize_long_stream", tk, rp, self.engine, ns or None, [voice])   # every piece, in front of the first batch
         K = 1 if tk is None else tk.k
         if tk is not None and K * max_batch > Takes.MAX_ROWS:
             max_batch = Takes.MAX_ROWS // K                    # the sampler batch is K times the group

@@ -18,7 +18,13 @@ Two sources, both optional at run time because neither exists offline:
   prefixes stripped as for the DiT) becomes the ``asr.`` tensors, checked against :func:`smalltts_amd.weights.asr_param_specs`.
   No such checkpoint has ever been loaded by this project: the path is checked on synthetic state dicts only.
 
+* optionally the speaker verifier the student was distilled against: the ``{"model": state_dict}`` file the reference's
+  ``train/dmd2/sv.py`` writes for ``SV(192)`` (keys ``ecapa.…``; bare dicts and wrapper prefixes are taken as for the recogniser)
+  becomes the ``sv.`` tensors, checked against :func:`smalltts_amd.weights.sv_param_specs`.  No such checkpoint has ever been loaded
+  by this project, and the key names are restated from recollection: the path is checked on synthetic state dicts only.
+
 CLI:  python -m smalltts_amd.convert --checkpoint ckpt.pt --out weights.smtts
+      python -m smalltts_amd.convert [--checkpoint ckpt.pt] [--asr-checkpoint asr.pt] --sv-checkpoint sv.pt --out weights.smtts
       python -m smalltts_amd.convert [--checkpoint ckpt.pt] --asr-checkpoint asr.pt --out weights.smtts
       python -m smalltts_amd.convert --onnx condition_encoder.onnx denoiser.onnx --out weights.smtts [--allow-partial]
       python -m smalltts_amd.convert --onnx decoder.onnx encoder.onnx --codec [--codec-spec spec.json] [--map-by-position]
@@ -37,7 +43,7 @@ from typing import Dict, Iterable, List, Optional, Sequence, Tuple
 import numpy as np
 
 from .weights import (CodecSpec, asr_param_specs, clean_state_dict_keys, codec_decoder_param_specs, codec_encoder_param_specs,
-                      dit_param_specs, save_weight_file)
+                      dit_param_specs, save_weight_file, sv_param_specs)
 
 
 # ----------------------------------------------------------------------------------------------
@@ -104,10 +110,24 @@ def asr_tensors_from_checkpoint(path: str, key: Optional[str] = None, allow_part
     return {n: tensors[n] for n, _ in asr_param_specs() if n in tensors and n not in bad}, rep
 
 
+def sv_tensors_from_checkpoint(path: str, key: Optional[str] = None, allow_partial: bool = False):
+    """The verifier's state dict (SV(192): ecapa.*) -> ({"sv." + name: array}, report).  BatchNorm's num_batches_tracked counters are
+    not parameters of the forward pass and are dropped without a word."""
+    import torch
+    tensors = state_dict_from_checkpoint(torch.load(path, map_location="cpu", weights_only=True), key)
+    tensors = {"sv." + k: v for k, v in tensors.items() if not k.endswith("num_batches_tracked")}
+    rep = check_against_specs(tensors, sv_param_specs())
+    if not rep.ok and not allow_partial:
+        raise ValueError(f"{path}: not an SV(192) state_dict — {rep.summary()}; first problems: "
+                         f"{(rep['missing'] + [f'{m[0]} has shape {m[1]}, expected {m[2]}' for m in rep['shape_mismatch']])[:5]}")
+    bad = {m[0] for m in rep["shape_mismatch"]}
+    return {n: tensors[n] for n, _ in sv_param_specs() if n in tensors and n not in bad}, rep
+
+
 def convert_checkpoint(path: Optional[str], out: str, key: Optional[str] = None, allow_partial: bool = False,
-                       asr_checkpoint: Optional[str] = None) -> ConversionReport:
-    """DiT checkpoint and / or recogniser checkpoint -> one weight file.  The report is the DiT's; with asr_checkpoint its "asr" entry
-    is the recogniser's (alone: the recogniser's report itself)."""
+                       asr_checkpoint: Optional[str] = None, sv_checkpoint: Optional[str] = None) -> ConversionReport:
+    """DiT checkpoint and / or recogniser and verifier checkpoints -> one weight file.  The report is the DiT's; with asr_checkpoint /
+    sv_checkpoint its "asr" / "sv" entry is that part's (a part alone: its report itself)."""
     import torch
     keep: Dict[str, np.ndarray] = {}
     rep = None
@@ -119,18 +139,20 @@ def convert_checkpoint(path: Optional[str], out: str, key: Optional[str] = None,
             raise ValueError(f"{path}: not a DiTModel(64) state_dict — {rep.summary()}; first problems: "
                              f"{(rep['missing'] + [m[0] for m in rep['shape_mismatch']])[:5]}")
         keep = {n: tensors[n] for n, _ in dit_param_specs() if n in tensors}
-    if asr_checkpoint is not None:
-        asr, arep = asr_tensors_from_checkpoint(asr_checkpoint, None, allow_partial)
-        keep.update(asr)
+    for part, ck, load in (("asr", asr_checkpoint, asr_tensors_from_checkpoint), ("sv", sv_checkpoint, sv_tensors_from_checkpoint)):
+        if ck is None:
+            continue
+        got, arep = load(ck, None, allow_partial)
+        keep.update(got)
         if rep is None:
             rep = arep
         else:
-            rep["asr"] = dict(arep)
+            rep[part] = dict(arep)
             for k in ("missing", "shape_mismatch", "unexpected"):   # one verdict for the file
                 rep[k] = rep[k] + arep[k]
             rep["matched"] += arep["matched"]
     if rep is None:
-        raise ValueError("convert_checkpoint: neither a DiT nor a recogniser checkpoint was given")
+        raise ValueError("convert_checkpoint: neither a DiT nor a recogniser nor a verifier checkpoint was given")
     save_weight_file(out, keep)
     return rep
 
@@ -357,6 +379,8 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     src.add_argument("--onnx", nargs="+", help=".onnx files whose initialisers hold the weights")
     ap.add_argument("--asr-checkpoint", default=None, help="torch.save of the recogniser's state dict (ASR(64)): written as the asr.* "
                                                            "tensors, alone or next to --checkpoint")
+    ap.add_argument("--sv-checkpoint", default=None, help="torch.save of the speaker verifier's {'model': state dict} (SV(192)): written "
+                                                          "as the sv.* tensors, alone or next to --checkpoint / --asr-checkpoint")
     ap.add_argument("--key", default=None, help="checkpoint entry to use (default: student_model / model)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--allow-partial", action="store_true", help="write what matched instead of failing")
@@ -368,14 +392,14 @@ def main(argv: Optional[Sequence[str]] = None) -> int:
     ap.add_argument("--map-by-position", action="store_true",
                     help="--onnx: also take initialisers matched by position inside their shape signature (unverified; see the report)")
     a = ap.parse_args(argv)
-    if not (a.checkpoint or a.onnx or a.asr_checkpoint):
-        ap.error("one of --checkpoint, --onnx, --asr-checkpoint is required")
-    if a.onnx and a.asr_checkpoint:
-        ap.error("--asr-checkpoint goes with --checkpoint or alone, not with --onnx")
+    if not (a.checkpoint or a.onnx or a.asr_checkpoint or a.sv_checkpoint):
+        ap.error("one of --checkpoint, --onnx, --asr-checkpoint, --sv-checkpoint is required")
+    if a.onnx and (a.asr_checkpoint or a.sv_checkpoint):
+        ap.error("--asr-checkpoint and --sv-checkpoint go with --checkpoint or alone, not with --onnx")
     codec = None
     if a.codec or a.codec_spec:
         codec = CodecSpec(**json.load(open(a.codec_spec))) if a.codec_spec else CodecSpec()
-    rep = (convert_checkpoint(a.checkpoint, a.out, a.key, a.allow_partial, a.asr_checkpoint) if not a.onnx
+    rep = (convert_checkpoint(a.checkpoint, a.out, a.key, a.allow_partial, a.asr_checkpoint, a.sv_checkpoint) if not a.onnx
            else convert_onnx(a.onnx, a.out, codec, a.allow_partial, a.map_by_position, a.parts.split(",") if a.parts else None))
     print(rep.summary())
     if "signature" in rep:

@@ -80,7 +80,7 @@ const char* smtts_range_report(smtts_handle h) {
 }
 float smtts_range_worst_bound(smtts_handle h) { NULLCHK0; return E.range_worst(); }
 int smtts_has_part(smtts_handle h, int part) { NULLCHK0;
-    return part == 0 ? E.has_dit() : part == 1 ? E.has_decoder() : part == 2 ? E.has_encoder() : part == 3 ? E.has_asr() : 0;
+    return part == 0 ? E.has_dit() : part == 1 ? E.has_decoder() : part == 2 ? E.has_encoder() : part == 3 ? E.has_asr() : part == 4 ? E.has_sv() : 0;
 }
 
 size_t smtts_cond_workspace_bytes(smtts_handle h, int B, int R, int P) { NULLCHK0; return E.cond_ws_bytes(B, R, P); }
@@ -209,6 +209,21 @@ int smtts_ctc_greedy(smtts_handle h, void* stream, const float* logp, const int3
     if (!logp || !t_len || !ids || !n_ids) return E.fail("smtts_ctc_greedy: a required pointer is NULL");
     hipError_t e = launch_ctc_greedy(logp, t_len, B, T, C, ids, n_ids, ST(stream));
     return e == hipSuccess ? 0 : E.fail_hip(e, "ctc_greedy");
+}
+
+size_t smtts_sv_workspace_bytes(smtts_handle h, int B, int N) { NULLCHK0; return E.sv_workspace_bytes(B, N); }
+int smtts_sv_embed(smtts_handle h, void* stream, const float* x, const int32_t* n_len, int B, int N, void* ws, size_t ws_bytes,
+                   float* emb) { NULLCHK;
+    return E.sv_embed(ST(stream), x, n_len, B, N, ws, ws_bytes, emb);
+}
+int smtts_sv_cosine(smtts_handle h, void* stream, const float* emb, const float* ref, int B, int K, int D, float* cos) { NULLCHK;
+    if (B < 1 || B > 65536) return E.fail("smtts_sv_cosine: B must be in [1, 65536]");
+    if (K < 1 || K > 16 || B % K || D < 1 || D > 1024)
+        return E.fail("smtts_sv_cosine: K must be in [1, 16] and divide B, D must be in [1, 1024]");
+    if (!emb || !ref || !cos) return E.fail("smtts_sv_cosine: a required pointer is NULL");
+    if (((uintptr_t)emb | (uintptr_t)ref | (uintptr_t)cos) & 3) return E.fail("smtts_sv_cosine: emb, ref and cos must be 4-byte aligned");
+    hipError_t e = launch_sv_cosine(emb, ref, B, K, D, cos, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "sv_cosine");
 }
 
 int smtts_codec_hop(smtts_handle h) { NULLCHK0; return E.codec_spec().hop(); }

@@ -816,6 +816,130 @@ int Engine::asr_logprobs(hipStream_t st, const float* x, const int32_t* n_len, i
     return e == hipSuccess ? 0 : fail_hip(e, "asr_logprobs");
 }
 
+// ---------------------------------------------------------------------------------------------
+// speaker verifier (sv.hip): shapes by name, then the packs its kernels read
+// ---------------------------------------------------------------------------------------------
+int Engine::finalize_sv() {
+    constexpr long C = 768, BAND = 64, SE = 192, ATT = 192, MFA = 2304, POOL = 4608, EMB = 192, IN = 64;
+    static const int DIL[3] = {2, 3, 5};
+    const std::string EC = "sv.ecapa.";
+    auto chk_conv = [&](const std::string& p, long o, long i, long k) {
+        return check_shape(p + ".conv.weight", {o, i, k}) || check_shape(p + ".conv.bias", {o});
+    };
+    auto chk_norm = [&](const std::string& p, long n) {
+        for (const char* leaf : {"weight", "bias", "running_mean", "running_var"})
+            if (check_shape(p + ".norm." + leaf, {n})) return 1;
+        return 0;
+    };
+    auto chk_tdnn = [&](const std::string& p, long i, long o, long k) { return chk_conv(p + ".conv", o, i, k) || chk_norm(p + ".norm", o); };
+    if (chk_tdnn(EC + "blocks.0", IN, C, 3) || chk_tdnn(EC + "mfa", MFA, MFA, 1) || chk_tdnn(EC + "asp.tdnn", 3 * MFA, ATT, 1) ||
+        chk_conv(EC + "asp.conv", MFA, ATT, 1) || chk_norm(EC + "asp_bn", POOL) || chk_conv(EC + "fc", EMB, POOL, 1))
+        return 1;
+    for (int i = 1; i <= 3; ++i) {
+        const std::string p = EC + "blocks." + std::to_string(i) + ".";
+        if (chk_tdnn(p + "tdnn1", C, C, 1) || chk_tdnn(p + "tdnn2", C, C, 1) || chk_conv(p + "se_block.conv1", SE, C, 1) ||
+            chk_conv(p + "se_block.conv2", C, SE, 1))
+            return 1;
+        for (int j = 0; j < 11; ++j)
+            if (chk_tdnn(p + "res2net_block.blocks." + std::to_string(j), BAND, BAND, 3)) return 1;
+    }
+    bool bad = false;
+    auto host = [&](const std::string& n) {
+        const RawTensor* t = raw(n);
+        std::vector<float> v((size_t)t->numel);
+        if (hipMemcpy(v.data(), t->d, v.size() * 4, hipMemcpyDeviceToHost) != hipSuccess) bad = true;
+        return v;
+    };
+    auto up = [&](const std::vector<float>& v) -> const float* {
+        float* d = static_cast<float*>(dalloc(v.size() * 4));
+        if (!d || hipMemcpy(d, v.data(), v.size() * 4, hipMemcpyHostToDevice) != hipSuccess) { bad = true; return nullptr; }
+        return d;
+    };
+    // conv weight (n_out, i_all, taps) row-major, input channels [0, i_use) -> 64 x 64 blocks [k][n] with k = tap * i_use + channel;
+    // block order: outputs outer, k inner
+    auto blocks_t = [&](const std::string& n, long n_out, long i_all, long i_use, long taps) {
+        const std::vector<float> w = host(n);
+        std::vector<float> o((size_t)(n_out * i_use * taps));
+        const long kb = taps * i_use / 64;
+        for (long r = 0; r < n_out; ++r)
+            for (long i = 0; i < i_use; ++i)
+                for (long t = 0; t < taps; ++t) {
+                    const long k = t * i_use + i;
+                    o[(size_t)((((r / 64) * kb + k / 64) * 64 + k % 64) * 64 + r % 64)] = w[(size_t)((r * i_all + i) * taps + t)];
+                }
+        return up(o);
+    };
+    // columns [i0, i0 + i_use) of a k = 1 weight (n_out, i_all) -> [k][n_out]
+    auto cols_t = [&](const std::string& n, long n_out, long i_all, long i0, long i_use) {
+        const std::vector<float> w = host(n);
+        std::vector<float> o((size_t)(n_out * i_use));
+        for (long r = 0; r < n_out; ++r)
+            for (long k = 0; k < i_use; ++k) o[(size_t)(k * n_out + r)] = w[(size_t)(r * i_all + i0 + k)];
+        return up(o);
+    };
+    // BatchNorm1d in eval: y = (x - mean) / sqrt(var + 1e-5) * weight + bias = x * scale + shift
+    int bn_bad = 0;
+    auto fold = [&](const std::string& p, const float*& scale, const float*& shift) {
+        const std::vector<float> g = host(p + ".norm.weight"), be = host(p + ".norm.bias"), mu = host(p + ".norm.running_mean"),
+                                 var = host(p + ".norm.running_var");
+        std::vector<float> sc(g.size()), sh(g.size());
+        for (size_t i = 0; i < g.size(); ++i) {
+            if (!(var[i] >= 0.f)) { if (!bn_bad) fail("tensor " + p + ".norm.running_var has a negative (or NaN) entry"); bn_bad = 1; return; }
+            const double s = (double)g[i] / std::sqrt((double)var[i] + 1e-5);
+            sc[i] = (float)s;
+            sh[i] = (float)((double)be[i] - (double)mu[i] * s);
+        }
+        scale = up(sc); shift = up(sh);
+    };
+    auto tdnn = [&](const std::string& p, long i, long i_use, long o, long k) {
+        SvTdnnW t{};
+        t.wt = blocks_t(p + ".conv.conv.weight", o, i, i_use, k);
+        t.b = rawp(p + ".conv.conv.bias");
+        fold(p + ".norm", t.scale, t.shift);
+        return t;
+    };
+    sv_.in = tdnn(EC + "blocks.0", IN, IN, C, 3);
+    for (int i = 0; i < 3; ++i) {
+        const std::string p = EC + "blocks." + std::to_string(i + 1) + ".";
+        SvBlockW& b = sv_.block[i];
+        b.tdnn1 = tdnn(p + "tdnn1", C, C, C, 1);
+        for (int j = 0; j < 11; ++j) b.band[j] = tdnn(p + "res2net_block.blocks." + std::to_string(j), BAND, BAND, BAND, 3);
+        b.tdnn2 = tdnn(p + "tdnn2", C, C, C, 1);
+        b.se_w1t = cols_t(p + "se_block.conv1.conv.weight", SE, C, 0, C); b.se_b1 = rawp(p + "se_block.conv1.conv.bias");
+        b.se_w2t = cols_t(p + "se_block.conv2.conv.weight", C, SE, 0, SE); b.se_b2 = rawp(p + "se_block.conv2.conv.bias");
+        b.dil = DIL[i];
+    }
+    sv_.mfa = tdnn(EC + "mfa", MFA, MFA, MFA, 1);
+    sv_.att = tdnn(EC + "asp.tdnn", 3 * MFA, MFA, ATT, 1);
+    sv_.att_ct = cols_t(EC + "asp.tdnn.conv.conv.weight", ATT, 3 * MFA, MFA, POOL);
+    sv_.logit = SvTdnnW{blocks_t(EC + "asp.conv.conv.weight", MFA, ATT, ATT, 1), rawp(EC + "asp.conv.conv.bias"), nullptr, nullptr};
+    fold(EC + "asp_bn", sv_.pool_scale, sv_.pool_shift);
+    sv_.fc_t = cols_t(EC + "fc.conv.weight", EMB, POOL, 0, POOL);
+    sv_.fc_b = rawp(EC + "fc.conv.bias");
+    if (bn_bad) return 1;
+    if (bad) return fail("finalize: packing the verifier weights failed (device memory)");
+    sv_ready_ = true;
+    return 0;
+}
+
+size_t Engine::sv_workspace_bytes(int B, int N) {
+    if (B < 1 || B > 64 || N < 6 || N > 225) { fail("smtts_sv_workspace_bytes: B must be in [1, 64] and N in [6, 225]"); return 0; }
+    return sv_ws_bytes(B, N);
+}
+
+int Engine::sv_embed(hipStream_t st, const float* x, const int32_t* n_len, int B, int N, void* ws, size_t ws_bytes, float* emb) {
+    if (!sv_ready_) return fail("smtts_sv_embed: this engine holds no speaker verifier (load the sv.* tensors and finalize)");
+    if (B < 1 || B > 64 || N < 6 || N > 225) return fail("smtts_sv_embed: B must be in [1, 64] and N in [6, 225]");
+    if (!x || !n_len || !ws || !emb) return fail("smtts_sv_embed: a required pointer is NULL");
+    if ((uintptr_t)ws & 255) return fail("smtts_sv_embed: the workspace must be 256-byte aligned");
+    if (ws_bytes < sv_ws_bytes(B, N)) return fail("smtts_sv_embed: workspace too small (smtts_sv_workspace_bytes)");
+    if (((uintptr_t)x | (uintptr_t)n_len | (uintptr_t)emb) & 3) return fail("smtts_sv_embed: x, n_len and emb must be 4-byte aligned");
+    HIPC(hipSetDevice(device_));
+    ProfTag tag("sv");
+    const hipError_t e = launch_sv_embed(sv_, x, n_len, B, N, ws, emb, st);
+    return e == hipSuccess ? 0 : fail_hip(e, "sv_embed");
+}
+
 int Engine::finalize() {
     HIPC(hipSetDevice(device_));
     HIPC(hipDeviceSynchronize());  // nothing in flight may still read the packs of an earlier finalize()
@@ -836,6 +960,9 @@ int Engine::finalize() {
     }
     if (raw("asr.proj.weight")) {
         if (finalize_asr()) return 1;
+    }
+    if (raw("sv.ecapa.fc.conv.weight")) {
+        if (finalize_sv()) return 1;
     }
     HIPC(hipDeviceSynchronize());
     finalized_ = true;

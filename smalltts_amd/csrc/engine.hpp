@@ -109,6 +109,7 @@ class Engine {
     bool has_decoder() const { return dec_.ready; }
     bool has_encoder() const { return enc_.ready; }
     bool has_asr() const { return asr_ready_; }
+    bool has_sv() const { return sv_ready_; }
     // Per-site operand precision (PREC_* of common.hpp).  Sites: the GEMMs grouped by how much latent / audio error their
     // rounding causes (tests/studies/precision_ladder_cpu.py) and by what they cost.
     enum Site { SITE_DIT_BLOCK = 0,   // QKVG, out-proj, FF1 (SwiGLU), FF2 of the 12 DiT blocks: 95 % of the DiT's flops and bytes
@@ -220,6 +221,10 @@ class Engine {
     size_t asr_workspace_bytes(int B, int N);
     int asr_logprobs(hipStream_t st, const float* x, const int32_t* n_len, int B, int N, void* ws, size_t ws_bytes, float* logp);
 
+    // The latent speaker verifier (sv.hip; include/smalltts_hip.h smtts_sv_embed): present when the sv.* tensors were loaded
+    size_t sv_workspace_bytes(int B, int N);
+    int sv_embed(hipStream_t st, const float* x, const int32_t* n_len, int B, int N, void* ws, size_t ws_bytes, float* emb);
+
     const CodecSpecC& codec_spec() const { return cspec_; }
     // per-kernel HIP-event timing (bench.py); report = JSON array, valid after the stream is synchronised
     void profile_enable(int mode);  // 0 off, 1 per-kernel, 2 per-kernel prefixed with the pipeline phase
@@ -272,6 +277,7 @@ class Engine {
     int finalize_dit();
     int finalize_codec(bool decoder);
     int finalize_asr();
+    int finalize_sv();
     int build_encoder(EncoderW& e, const std::string& prefix, int dim, int heads, int ff, int layers, float eps);
     int make_rope(int dim, float** cos_out, float** sin_out);
     struct ModWs;
@@ -380,7 +386,7 @@ class Engine {
                     bf16_t* hhi, bf16_t* hlo, int B, int T, int C, size_t n2_elems /* capacity of n2hi (bf16 elements) */,
                     bool carried = false /* the pad frames of *x hold carried frames: a path that reads pads of nbuf normalises them too */);
     int check_shape(const std::string& name, std::initializer_list<long> want);
-    void invalidate() { finalized_ = false; dit_ready_ = false; dec_.ready = false; enc_.ready = false; asr_ready_ = false; }
+    void invalidate() { finalized_ = false; dit_ready_ = false; dec_.ready = false; enc_.ready = false; asr_ready_ = false; sv_ready_ = false; }
     void free_packs();
 
     // the tag a producer of attention operand images is handed in place of the (unused) lo array when the images are fp16
@@ -462,6 +468,9 @@ class Engine {
 
     bool asr_ready_ = false;
     AsrW asr_{};
+
+    bool sv_ready_ = false;
+    SvW sv_{};
 };
 
 void alpha_sigma_host(float t, float& a, float& s);

@@ -118,6 +118,31 @@ size_t asr_ws_bytes(int B, int N);
 // x f32 (B, N, 64), n_len i32 (B) (clamped into [0, N]) -> logp f32 (B, 4 N, 198), 0.0 at and behind frame 4 n_b; ws: asr_ws_bytes, 256-byte
 // aligned, may hold anything.  1 <= N <= 225.
 hipError_t launch_asr_logprobs(const AsrW& w, const float* x, const int* n_len, int B, int N, void* ws, float* logp, hipStream_t st);
+// ---- speaker verifier (sv.hip) ---------------------------------------------------------------------------------------------------------
+// Device pointers of the packed verifier weights (Engine::finalize_sv).  A product's weight (n_out, k_in): 64 x 64 blocks, each transposed
+// to [k][n], outputs outer, inputs inner; a k = 3 convolution has k_in = tap * channels + channel.  scale / shift: the BatchNorm (eval)
+// behind the ReLU, folded; NULL where the product has none.
+struct SvTdnnW { const float *wt, *b, *scale, *shift; };
+struct SvBlockW {
+    SvTdnnW tdnn1, band[11] /* each [3 taps * 64][64] */, tdnn2;
+    const float *se_w1t /* [768][192] */, *se_b1, *se_w2t /* [192][768] */, *se_b2;
+    int dil;
+};
+struct SvW {
+    SvTdnnW in;      // blocks.0: 3 taps x 64 -> 768
+    SvBlockW block[3];
+    SvTdnnW mfa;     // 2304 -> 2304
+    SvTdnnW att;     // the pooling's TDNN, columns [0, 2304) of its 6912: 2304 -> 192
+    const float* att_ct /* its columns [2304, 6912) transposed: [4608][192] */;
+    SvTdnnW logit;   // 192 -> 2304, bias only
+    const float *pool_scale, *pool_shift /* asp_bn folded, 4608 */, *fc_t /* [4608][192] */, *fc_b;
+};
+size_t sv_ws_bytes(int B, int N);
+// x f32 (B, N, 64), n_len i32 (B) (clamped into [0, N]) -> emb f32 (B, 192), every row as if alone in its batch; 0.0 for a row under 6
+// frames.  ws: sv_ws_bytes, 256-byte aligned, may hold anything.  6 <= N <= 225, else hipErrorInvalidValue.
+hipError_t launch_sv_embed(const SvW& w, const float* x, const int* n_len, int B, int N, void* ws, float* emb, hipStream_t st);
+// cos f32 (B): row b of emb (B, D) against row b / K of ref (B / K, D), each norm clamped at 1e-8 (a zero row gives 0).  One wave per row.
+hipError_t launch_sv_cosine(const float* emb, const float* ref, int B, int K, int D, float* cos, hipStream_t st);
 // ---- repair (repair.hip) ----------------------------------------------------------------------------------------------------------
 // Pin mask of every row behind launch_align_path, one workgroup per row: a token of [p0, p1) is bad when its span is empty, longer than
 // max_span, or holds no frame with mass >= tau_tok; a bad token with a span frees its frames +- margin.  pin u8 (B, N) = 1 for frames

@@ -13,7 +13,7 @@ import torch
 
 from . import _lib
 from .weights import (DEFAULT_CODEC, CodecSpec, asr_param_specs, codec_decoder_param_specs, codec_encoder_param_specs,
-                      dit_param_specs, init_rule, tensor_key)
+                      dit_param_specs, init_rule, sv_param_specs, tensor_key)
 
 N_LAYERS, N_HEADS, HEAD_DIM, LATENT = 12, 8, 120, 64
 ACT = {"none": 0, "silu": 1, "gelu": 2, "mish": 3}
@@ -26,6 +26,7 @@ DEFAULT_PRECISION = "f16"
 
 ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS = 225, 198   # smtts_align_path: 30 s of codec frames, the phoneme window
 ASR_MAX_ROWS, ASR_UPSAMPLE, ASR_CLASSES = 64, 4, 198   # smtts_asr_logprobs: rows per call, frames per latent frame, phoneme classes
+SV_MAX_ROWS, SV_MIN_FRAMES, SV_DIM = 64, 6, 192        # smtts_sv_embed: rows per call, the shortest row with an embedding, its width
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -343,6 +344,8 @@ class HipEngine:
             specs += codec_encoder_param_specs(spec)
         if "asr" in parts:
             specs += asr_param_specs()
+        if "sv" in parts:
+            specs += sv_param_specs()
         for name, shape in specs:
             mean, hr = init_rule(name, shape)
             sh = (C.c_int64 * max(1, len(shape)))(*shape)
@@ -365,7 +368,7 @@ class HipEngine:
         self.check_fp16_range("finalize")   # static part: fused codec FFN blocks whose range the weights do not certify
 
     def has(self, part: str) -> bool:
-        return bool(self.lib.smtts_has_part(self.h, {"dit": 0, "decoder": 1, "encoder": 2, "asr": 3}[part]))
+        return bool(self.lib.smtts_has_part(self.h, {"dit": 0, "decoder": 1, "encoder": 2, "asr": 3, "sv": 4}[part]))
 
     # ---- operators -----------------------------------------------------------------------------
     def cond_encode(self, ref, ref_len, ids, ph_mask, debug: bool = False) -> Dict[str, torch.Tensor]:
@@ -542,6 +545,49 @@ class HipEngine:
         ws = self._workspace(self.lib.smtts_asr_workspace_bytes(self.h, B, N))
         self._ck(self.lib.smtts_asr_logprobs(self.h, self._stream(), _p(x), _p(tab[0]), B, N, _p(ws), ws.numel(), _p(out)), "asr_logprobs")
         return out
+
+    def sv_embed(self, x: torch.Tensor, ns, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """Speaker embedding of every row of latents (smtts_sv_embed; the definition: include/smalltts_hip.h).  x fp32
+        (B,N,64) contiguous on the device, B <= 64, 6 <= N <= 225; ns the frames per row (host integers).  -> emb fp32 (B,192) on the
+        device (out: a contiguous fp32 tensor of that shape to write into), not normalised; every row is computed as if it were alone,
+        and a row under 6 frames has no embedding: its row is 0.0.  Needs the verifier part (load_synthetic(parts=(..., "sv")) or the
+        sv.* tensors).  Launches on the current stream, no synchronisation."""
+        if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device or x.shape[2] != LATENT:
+            raise ValueError("sv_embed: x must be a contiguous fp32 (B,N,64) tensor on the engine's device")
+        B, N = int(x.shape[0]), int(x.shape[1])
+        if not (1 <= B <= SV_MAX_ROWS and SV_MIN_FRAMES <= N <= ALIGN_MAX_FRAMES):
+            raise ValueError(f"sv_embed: B = {B}, N = {N} outside the supported range B <= {SV_MAX_ROWS}, "
+                             f"{SV_MIN_FRAMES} <= N <= {ALIGN_MAX_FRAMES}")
+        if len(ns) != B:
+            raise ValueError("sv_embed: one frame count per row")
+        if not self.has("sv"):
+            raise ValueError("sv_embed: this engine holds no verifier part")
+        want = (B, SV_DIM)
+        if out is None:
+            out = torch.empty(want, device=self.device)
+        elif out.dtype != torch.float32 or tuple(out.shape) != want or not out.is_contiguous() or out.device != self.device:
+            raise ValueError(f"sv_embed: out must be a contiguous fp32 {want} tensor on the engine's device")
+        tab = self._upload_i32([ns])
+        ws = self._workspace(self.lib.smtts_sv_workspace_bytes(self.h, B, N))
+        self._ck(self.lib.smtts_sv_embed(self.h, self._stream(), _p(x), _p(tab[0]), B, N, _p(ws), ws.numel(), _p(out)), "sv_embed")
+        return out
+
+    def sv_cosine(self, emb: torch.Tensor, ref: torch.Tensor, K: int = 1) -> torch.Tensor:
+        """Cosine of row b of emb against row b // K of ref (smtts_sv_cosine; DESIGN 8j): emb fp32 (B,D) and ref fp32 (B/K,D),
+        contiguous on the device, 1 <= K <= 16, D <= 1024.  -> cos fp32 (B) on the device, F.cosine_similarity's rule (each norm clamped
+        at 1e-8: a zero row gives 0).  Needs no weights.  One launch on the current stream, no synchronisation."""
+        for name, t in (("emb", emb), ("ref", ref)):
+            if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+                raise ValueError(f"sv_cosine: {name} must be a contiguous fp32 2-d tensor on the engine's device")
+        B, D = int(emb.shape[0]), int(emb.shape[1])
+        K = int(K)
+        if not (1 <= K <= 16 and B >= 1 and B % K == 0 and 1 <= D <= 1024):
+            raise ValueError(f"sv_cosine: B = {B}, K = {K}, D = {D} outside the supported range 1 <= K <= 16, B % K == 0, 1 <= D <= 1024")
+        if tuple(ref.shape) != (B // K, D):
+            raise ValueError(f"sv_cosine: ref must have shape ({B // K}, {D})")
+        cos = torch.empty(B, device=self.device)
+        self._ck(self.lib.smtts_sv_cosine(self.h, self._stream(), _p(emb), _p(ref), B, K, D, _p(cos)), "sv_cosine")
+        return cos
 
     def ctc_score(self, logp: torch.Tensor, ts, tokens: torch.Tensor, p0, p1) -> torch.Tensor:
         """CTC negative log-likelihood of every row (smtts_ctc_score; the definition: include/smalltts_hip.h).  logp fp32

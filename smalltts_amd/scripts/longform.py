@@ -11,6 +11,9 @@ unvalidated on trained weights); with --words the JSON becomes {"words": [...], 
 --ctc W (with --takes; loads the latent phoneme recogniser, api.SmallTTS(recogniser=True)): the score gains W * CTC nll / tokens of the
 recogniser's reading of every take (api.Takes(ctc=); unvalidated like the rest of the score, not with --repair), and every
 entry of "takes" in the --words JSON gains "nll", the K values.
+--sv W (with --takes; loads the latent speaker verifier, api.SmallTTS(verifier=True)): the score gains W * (1 - cosine) of every take's
+speaker embedding with the reference voice's (api.Takes(sv=); unvalidated in the same way, not with --repair; every piece
+and the reference need 6 to 225 frames), and every entry of "takes" gains "cos", the K cosines of the piece.
 --repair [ROUNDS]: behind the sampler (and --takes) only the badly aligned words of every piece are spoken again, ROUNDS times
 (default 1), and a repaired piece is kept where it scores strictly better (api.Repair; unvalidated on trained weights like --takes);
 with --words the JSON gains "repair": [{piece, kept, bad, free, before, after}, ...], one list entry per round in each field.
@@ -38,7 +41,7 @@ def group_texts(token_lists) -> list:
     return [(i, kind, ph) for i, toks in enumerate(token_lists) for kind, ph, _t0, _t1 in token_groups(toks)]
 
 
-def words_json(words, texts, takes=None, repair=None) -> str:
+def words_json(words, texts, takes=None, repair=None, extra=None) -> str:
     """synthesize_long's words + group_texts -> the --words file: a JSON list of {index, piece, kind, phonemes, start, end (samples),
     start_s, end_s (seconds)}.  With `takes` (synthesize_long's return_takes) the file is {"words": that list, "takes": [{piece,
     winner, seed, totals}, ...]}, one entry per piece; a total that is not finite is written as null.  With `repair`
@@ -53,8 +56,10 @@ def words_json(words, texts, takes=None, repair=None) -> str:
     if takes is not None or repair is not None:
         rows = {"words": rows}
     if takes is not None:
+        # (Takes(ctc > 0) reports the K values of nll too, Takes(sv > 0) the K cosines behind them: `extra` names what the tuples carry)
+        names = list(extra) if extra is not None else (["nll"] if takes and len(takes[0]) > 4 else [])
         rows["takes"] = [{"piece": i, "winner": int(t[0]), "seed": int(t[1]), "totals": [fin(v) for v in t[2]],
-                          **({"nll": [fin(v) for v in t[4]]} if len(t) > 4 else {})}      # (Takes(ctc > 0) reports the K values of nll too)
+                          **{n: [fin(v) for v in t[4 + j]] for j, n in enumerate(names)}}
                          for i, t in enumerate(takes)]
     if repair is not None:
         rows["repair"] = [{"piece": i, "kept": [int(v) for v in kept], "bad": [int(c[0]) for c in counts], "free": [int(c[1]) for c in counts],
@@ -114,6 +119,9 @@ def parse_args(argv=None):
     ap.add_argument("--takes", type=int, default=None, metavar="K", help=f"sample every piece K times (1..{Takes.MAX_K}) and keep the best-aligned take")
     ap.add_argument("--ctc", type=float, default=None, metavar="W",
                     help="with --takes: add W * CTC nll / tokens of the latent phoneme recogniser to every take's score (loads the recogniser)")
+    ap.add_argument("--sv", type=float, default=None, metavar="W",
+                    help="with --takes: add W * (1 - cosine with the reference voice) of the latent speaker verifier to every take's score "
+                         "(loads the verifier)")
     ap.add_argument("--repair", type=int, nargs="?", const=1, default=None, metavar="ROUNDS",
                     help=f"speak only the badly aligned words of every piece again, ROUNDS times (1..{Repair.MAX_ROUNDS}, default 1)")
     ap.add_argument("--max-batch", type=int, default=8)
@@ -151,6 +159,10 @@ def parse_args(argv=None):
         ap.error("--ctc takes a finite weight >= 0 and needs --takes")
     if args.ctc and args.repair is not None:
         ap.error("--ctc and --repair exclude each other (repair's keep rule scores without the CTC term)")
+    if args.sv is not None and (args.takes is None or not args.sv >= 0.0 or args.sv == float("inf")):
+        ap.error("--sv takes a finite weight >= 0 and needs --takes")
+    if args.sv and args.repair is not None:
+        ap.error("--sv and --repair exclude each other (repair's keep rule scores without the speaker term)")
     if args.takes is not None and args.takes * args.max_batch > Takes.MAX_ROWS:
         args.max_batch = Takes.MAX_ROWS // args.takes   # synthesize_long's rule, applied here so that --take records the group size used
     return args
@@ -161,7 +173,7 @@ def main(argv=None):
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     print("loading")
     tts = SmallTTS(weights=args.weights, device=args.device, precision=args.precision, num_steps=args.steps, seed=args.seed,
-                   recogniser=bool(args.ctc))
+                   recogniser=bool(args.ctc), verifier=bool(args.sv))
     print("encoding reference audio")
     y, sr = read_wav(args.wav)
     if y.ndim == 2:
@@ -178,7 +190,7 @@ def main(argv=None):
     if args.take:
         kw.update(return_pieces=True)
     if args.takes is not None:
-        kw.update(takes=Takes(args.takes, ctc=args.ctc) if args.ctc else args.takes, return_takes=True)
+        kw.update(takes=Takes(args.takes, ctc=args.ctc or 0.0, sv=args.sv or 0.0) if (args.ctc or args.sv) else args.takes, return_takes=True)
     if args.repair is not None:
         kw.update(repair=args.repair, return_repair=True)
     speak = tts.synthesize_long if not args.stream else (lambda *a, **k: stream_to_wav(tts, args, dv, *a, **k))
@@ -219,7 +231,7 @@ def main(argv=None):
         texts = group_texts(token_lists)
         if args.words:
             Path(args.words).parent.mkdir(parents=True, exist_ok=True)
-            Path(args.words).write_text(words_json(words, texts, chosen, mended), encoding="utf-8")
+            Path(args.words).write_text(words_json(words, texts, chosen, mended, (["nll"] if args.ctc else []) + (["cos"] if args.sv else [])), encoding="utf-8")
             print(f"{args.words} ({len(words)} word groups)")
         if args.srt:
             Path(args.srt).parent.mkdir(parents=True, exist_ok=True)

@@ -1,5 +1,5 @@
 """python -m smalltts_amd.scripts.respeak --take T.npz --wav ref.wav --piece I (--frames A:B | --groups A:B) [--seed S]
-    [--start-step K] [--takes K [--ctc W]] --out out.wav [--take-out T2.npz]
+    [--start-step K] [--takes K [--ctc W] [--sv W]] --out out.wav [--take-out T2.npz]
 Speaks a span of one piece of a long take again and keeps everything else: the take (scripts/longform.py --take) holds every piece's
 tokens and latents; frames [A, B) of piece I, or the frames its token groups [A, B) touch (the spans longform --words saved), are
 regenerated with the rest of the piece pinned (api.SmallTTS.respeak), the whole take is rendered again with its own join parameters
@@ -8,7 +8,9 @@ regenerated with the rest of the piece pinned (api.SmallTTS.respeak), the whole 
 regenerated region.  --takes K: the span is re-spoken K times, every take with the same pins, and the best-aligned one is kept
 (api.Takes; the updated take records the winner's seed).  Only the mechanism is verified: how well the 4-step student inpaints, and
 what the takes' score is worth, are unvalidated on trained weights.  --ctc W: the takes' score gains W * CTC nll / tokens of the latent
-phoneme recogniser (api.Takes(ctc=); loads the recogniser; unvalidated in the same way)."""
+phoneme recogniser (api.Takes(ctc=); loads the recogniser; unvalidated in the same way).  --sv W: it gains W * (1 - cosine)
+of every take's speaker embedding with the reference voice's (api.Takes(sv=); loads the latent speaker verifier; unvalidated
+in the same way; the piece and the reference need 6 to 225 frames)."""
 import argparse
 from pathlib import Path
 
@@ -56,6 +58,9 @@ def main(argv=None):
     ap.add_argument("--takes", type=int, default=None, metavar="K", help=f"re-speak the span K times (1..{Takes.MAX_K}) and keep the best-aligned take")
     ap.add_argument("--ctc", type=float, default=None, metavar="W",
                     help="with --takes: add W * CTC nll / tokens of the latent phoneme recogniser to every take's score (loads the recogniser)")
+    ap.add_argument("--sv", type=float, default=None, metavar="W",
+                    help="with --takes: add W * (1 - cosine with the reference voice) of the latent speaker verifier to every take's score "
+                         "(loads the verifier)")
     ap.add_argument("--out", required=True)
     ap.add_argument("--take-out", default=None, metavar="T2.npz", help="where the updated take goes (default: next to --out)")
     add_engine_args(ap)
@@ -67,6 +72,8 @@ def main(argv=None):
         ap.error(f"--takes must lie in [1, {Takes.MAX_K}]")
     if args.ctc is not None and (args.takes is None or not args.ctc >= 0.0 or args.ctc == float("inf")):
         ap.error("--ctc takes a finite weight >= 0 and needs --takes")
+    if args.sv is not None and (args.takes is None or not args.sv >= 0.0 or args.sv == float("inf")):
+        ap.error("--sv takes a finite weight >= 0 and needs --takes")
     old = pieces[args.piece]
     try:
         f0, f1 = span_frames(old, args.frames, args.groups)
@@ -75,7 +82,7 @@ def main(argv=None):
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     print("loading")
     tts = SmallTTS(weights=args.weights, device=args.device, precision=args.precision, num_steps=args.steps, seed=args.seed,
-                   recogniser=bool(args.ctc))
+                   recogniser=bool(args.ctc), verifier=bool(args.sv))
     print("encoding reference audio")
     y, sr = read_wav(args.wav)
     if y.ndim == 2:
@@ -90,7 +97,8 @@ def main(argv=None):
     res = tts.respeak(old.tokens, old.latents, (f0, f1), voice=voice, new_tokens=tokens, new_frames=args.new_frames, seed=seed,
                       start_step=args.start_step, prefix_len=old.prefix_len,
                       **({"align": True, "return_alignment": True} if timed else {}),
-                      **({} if args.takes is None else {"takes": Takes(args.takes, ctc=args.ctc) if args.ctc else args.takes, "return_takes": True}))
+                      **({} if args.takes is None else {"takes": Takes(args.takes, ctc=args.ctc or 0.0, sv=args.sv or 0.0) if (args.ctc or args.sv) else args.takes,
+                                                       "return_takes": True}))
     if args.takes is not None:
         winner, seed = res[-1][0], res[-1][1]
         print(f"take {winner} of {args.takes} kept (seed {seed})")

@@ -318,6 +318,48 @@ def asr_param_specs() -> List[Tuple[str, Tuple[int, ...]]]:
     return specs
 
 
+# the latent speaker verifier (reference models/sv/model.py: SV(192) = speechbrain's ECAPA_TDNN on the 64-dim latents)
+SV_IN = 64
+SV_DIM = 192
+SV_CHANNELS = 768
+SV_SCALE = 12                 # Res2Net bands of SV_CHANNELS / SV_SCALE = 64 channels
+SV_DILATIONS = (2, 3, 5)      # of the three SERes2Net blocks
+SV_SE = 192
+SV_ATT = 192
+SV_MFA = 3 * SV_CHANNELS      # 2304
+SV_MIN_FRAMES = 6             # reflect padding needs pad < n; the widest pad is the dilation 5
+
+
+def sv_param_specs() -> List[Tuple[str, Tuple[int, ...]]]:
+    """State dict of SV(192) under the prefix "sv." (speechbrain's wrappers nest .conv.conv and .norm.norm; num_batches_tracked left
+    out).  Not part of all_param_specs(): the verifier is an optional part (engine part 4).  The names are recollection."""
+    c, band = SV_CHANNELS, SV_CHANNELS // SV_SCALE
+
+    def conv(p, o, i, k):
+        return [(p + ".conv.weight", (o, i, k)), (p + ".conv.bias", (o,))]
+
+    def norm(p, n):
+        return [(p + ".norm." + leaf, (n,)) for leaf in ("weight", "bias", "running_mean", "running_var")]
+
+    def tdnn(p, i, o, k):
+        return conv(p + ".conv", o, i, k) + norm(p + ".norm", o)
+
+    e = "sv.ecapa."
+    specs = tdnn(e + "blocks.0", SV_IN, c, 3)
+    for i in range(1, 4):
+        p = e + f"blocks.{i}."
+        specs += tdnn(p + "tdnn1", c, c, 1)
+        for j in range(SV_SCALE - 1):
+            specs += tdnn(p + f"res2net_block.blocks.{j}", band, band, 3)
+        specs += tdnn(p + "tdnn2", c, c, 1)
+        specs += conv(p + "se_block.conv1", SV_SE, c, 1) + conv(p + "se_block.conv2", c, SV_SE, 1)
+    specs += tdnn(e + "mfa", SV_MFA, SV_MFA, 1)
+    specs += tdnn(e + "asp.tdnn", 3 * SV_MFA, SV_ATT, 1) + conv(e + "asp.conv", SV_MFA, SV_ATT, 1)
+    specs += norm(e + "asp_bn", 2 * SV_MFA)
+    specs += conv(e + "fc", SV_DIM, 2 * SV_MFA, 1)
+    return specs
+
+
 def all_param_specs(spec: CodecSpec = DEFAULT_CODEC):
     return dit_param_specs() + codec_decoder_param_specs(spec) + codec_encoder_param_specs(spec)
 
@@ -351,6 +393,15 @@ def init_rule(name: str, shape: Tuple[int, ...]) -> Tuple[float, float]:
             return 1.0, 0.2
         if leaf == "in_proj_bias":
             return 0.0, 0.1
+    if name.startswith("sv."):                            # the verifier: conv, ReLU, BatchNorm; norms and biases fall through
+        if leaf == "running_var":
+            return 1.0, 0.5
+        if leaf == "running_mean":
+            return 0.0, 0.1
+        if leaf == "weight" and len(shape) == 3:
+            # He-style where a ReLU follows (every TDNN conv and the gate's first product): the ReLU halves the second moment
+            relu = ".se_block.conv2." not in name and ".asp.conv." not in name and ".fc." not in name
+            return 0.0, math.sqrt((6.0 if relu else 3.0) / int(np.prod(shape[1:])))
     if leaf in ("gamma", "ffn_gamma"):                    # codec layer scales
         return 0.5, 0.2
     is_norm = (name.endswith("norm.weight") or name.endswith("norm_cross.weight"))
