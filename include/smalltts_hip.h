@@ -53,7 +53,7 @@ int smtts_create(int device_id, smtts_handle* out);
 int smtts_destroy(smtts_handle h);
 const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation error */
 const char* smtts_version(void);
-/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, then smtts_take_scores and smtts_take_select, then the streamed decode entries, then smtts_deliver, then smtts_join_stream and smtts_peek_saturations, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
+/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, then smtts_take_scores and smtts_take_select, then the streamed decode entries, then smtts_deliver, then smtts_join_stream and smtts_peek_saturations, then the smtts_watermark entries, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
 #define SMTTS_ABI_VERSION 11
 int smtts_abi_version(void);
@@ -430,6 +430,72 @@ size_t smtts_deliver_state_bytes(smtts_handle h, int klen);   /* per slot, multi
 int smtts_deliver(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride,
                   const int64_t* table /* DEVICE (B,4): slot, n_before, len, last */, const float* bank, int up, int down, int klen,
                   int width, void* state_pool, int64_t n_slots, int enc, void* out, int64_t out_stride);
+
+/* ---- watermark: key the 24 kHz stream on the device, detect it (DESIGN.md '8k. Watermark') ----------------------------------------
+ * A zero-bit, keyed, additive spread-spectrum mark.  The mark is a function of the ABSOLUTE stream position, so the concatenation of a
+ * stream's marked chunks is, BIT FOR BIT, the mark of the whole signal in one call, whatever the chunking.  Additive entries.
+ *
+ * Chips: for stream sample i >= 0, w = the four words of Philox4x32-10 with counter (lo32(i >> 7), hi32(i >> 7), 0x574D4B31, 0) and
+ *       key (lo32(key), hi32(key)) (smtts_randn's counter layout with stream id 'WMK1'; oracle/philox.py restates it).
+ *       c[i] = +1 if bit (i & 31) of w[(i >> 5) & 3] is set, else -1.
+ *
+ * smtts_watermark
+ * Signal: audio, out f32 (B,1,row_stride), DEVICE, not overlapping.  table: DEVICE int64 (B,4) = (slot, n_before, len, last) with
+ *       smtts_deliver's clamps (len to [0, row_stride], n_before to [0, 2^50], slot into the pool); `last` is ignored: there is no
+ *       look-ahead.  x = the stream's whole signal so far, row b of this call = x[n_before .. n_before + len).
+ * Mark: block k = the samples [64 k, 64 k + 64).  E[k] = ONE sequential fp32 chain over j = 0 .. 63 from acc = +0.0f:
+ *       sq = x_j * x_j (rounded), acc = acc + sq (rounded); no fma.  R[k] = sqrt(E[k] * 0.015625f) (correctly rounded).
+ *       A[k] = strength * R[k - 1] (one rounded multiply), A[0] = 0.
+ *       y[i] = c[i] > 0 ? x[i] + A[i / 64] : x[i] - A[i / 64]: one rounded fp32 add; no clamp (the encoders clamp).
+ *       So silence stays silence, the first block is never marked, strength = 0 changes no value (-0.0f + 0.0f is +0.0f: a zero's
+ *       sign may change, nothing else), and a numpy float32 loop reproduces y exactly.
+ *       Row b writes out[b][0 .. len_b) and nothing behind that.
+ * State: caller-owned DEVICE pool of n_slots slots of smtts_watermark_state_bytes(h) = 512 bytes each, 16-byte aligned.  A slot holds
+ *       the stream's last 127 INPUT (unmarked) samples as f32, oldest first (127 f32, rounded up to 512 bytes); a ZERO slot is the
+ *       start of a stream.  After the call the slot holds the last 127 samples of x[0 .. n_before + len) (with len < 127 the old
+ *       content moves up by len).  It is updated by a second launch (one workgroup per row: loads, a barrier, stores) behind the
+ *       main one.  Slot indices are clamped, never followed outside the pool; a slot may appear at most ONCE per call (the Python
+ *       wrapper refuses duplicates).  state_pool == NULL: every row starts here: n_before reads as 0, slot is ignored, nothing is
+ *       carried.
+ * Refused with 1 and a message naming the entry, nothing enqueued: a NULL handle (the size query returns 0), audio, table or out;
+ *       B outside [1, 65535]; row_stride outside [1, 2^40]; strength negative, not finite or above 1; audio and out overlapping (in
+ *       place is a race on the block in front); a pool with n_slots < 1 or not 16-byte aligned.
+ * One launch whatever B is, plus the history launch when a pool is given.  No atomics: two calls return the same bits.
+ *
+ * smtts_watermark_detect
+ * Signal: audio f32 (B,row_stride), DEVICE; len DEVICE int64 (B), clamped to [0, row_stride]; nothing behind len is read.  y = the
+ *       row's len samples, zeros outside [0, len).  The device works in fp32.
+ *       d2[j] = y[j-1] - 2 y[j] + y[j+1] for 0 <= j < len, 0 outside;   d4[j] = y[j-2] - 4 y[j-1] + 6 y[j] - 4 y[j+1] + y[j+2];
+ *       r[j] = sqrt((1/64) sum_{m = j-96 .. j-33} y[m]^2);   v[j] = (1/64) sum_{m = j-32 .. j+31} d2[m]^2;
+ *       u[j] = d4[j] * r[j] / (v[j] + 1e-8f);   den = sum_{j < len} u[j]^2.
+ *       For offset o (audio[j] is stream sample j + o): T(o) = sum_{j < len} u[j] * c[j + o], z(o) = T(o) / sqrt(den).
+ *       u does not depend on o.  Under "not marked with this key" z(o) is about N(0, 1).
+ * Order: u[j]: d2 = (y[m-1] + y[m+1]) - 2 y[m]; both 64-term sums are chains in ascending m from +0.0f; the square root and the
+ *       division are correctly rounded; d4 = ((y[j-2] + y[j+2]) - 4 (y[j-1] + y[j+1])) + 6 y[j]; u = (d4 * r) / (v + 1e-8f).  No
+ *       product is contracted into the sum behind it (a contraction would only remove roundings).
+ *       T(o): tiles of 1024 samples in ascending order; inside a tile a chain acc = acc + (+-u[j]) in ascending j from +0.0f (the
+ *       sign flipped exactly, no product), then ONE add total = total + acc, total from +0.0f.
+ *       den: per tile of 1024 samples thread t (of 256) chains u[t]^2, u[t + 256]^2, u[t + 512]^2, u[t + 768]^2 (0 at or behind len)
+ *       from +0.0f, then a halving tree (stride 128, 64 .. 1: s[t] += s[t + stride]); over the ceil(len / 1024) tile sums the same
+ *       again: thread t chains the tiles t, t + 256, ..., then the same tree.
+ *       So two calls return the same bits and a row does not depend on its batch-mates.
+ * Out, all DEVICE: u f32 (B,row_stride), written below len only; may be NULL, it then lives in ws.  den f32 (B).  T f32 (B,n_off),
+ *       T[b][k] = T(o_lo + k).  best_off int64 (B) = o_lo + argmax_k T[b][k], the lowest k on ties.  best_z f32 (B) =
+ *       T[b][best] / sqrtf(den[b]) (both correctly rounded), 0 where den[b] == 0.
+ * Workspace: smtts_watermark_detect_workspace_bytes(h, B, row_stride) bytes, 256-byte aligned: u's place and the tile sums.
+ * Refused with 1 and a message naming the entry, nothing enqueued: a NULL handle (the size query returns 0); B outside [1, 1024];
+ *       row_stride outside [1, 2^40]; a NULL audio, len, ws, den, T, best_off or best_z; o_lo outside [0, 2^40]; n_off outside
+ *       [1, 65536]; a workspace not 256-byte aligned or smaller than the query's answer.
+ * Three launches whatever B, len and n_off are.  Needs no weights: works on any handle, like smtts_sv_cosine.
+ * Unvalidated: detection on real speech and on trained weights; the default strength has never been listened to. */
+size_t smtts_watermark_state_bytes(smtts_handle h);   /* per slot: 512 */
+int smtts_watermark(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride,
+                    const int64_t* table /* DEVICE (B,4): slot, n_before, len, last */, uint64_t key, float strength,
+                    void* state_pool, int64_t n_slots, float* out);
+size_t smtts_watermark_detect_workspace_bytes(smtts_handle h, int B, int64_t row_stride);
+int smtts_watermark_detect(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* len /* DEVICE (B) */,
+                           uint64_t key, int64_t o_lo, int n_off, void* ws, size_t ws_bytes, float* u, float* den, float* T,
+                           int64_t* best_off, float* best_z);
 
 /* ---- long-form synthesis: one voice, many rows (DESIGN.md 'Long-form synthesis') ----------------------------------
  * The two halves of smtts_cond_encode are independent (k_ref / v_ref depend on the reference only, k_text / v_text on the phonemes

@@ -80,6 +80,10 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_pcm16": (i32, [vp, vp, vp, i64, vp]),
     "smtts_deliver_state_bytes": (sz, [vp, i32]),
     "smtts_deliver": (i32, [vp, vp, vp, i32, i64, vp, vp, i32, i32, i32, i32, vp, i64, i32, vp, i64]),
+    "smtts_watermark_state_bytes": (sz, [vp]),
+    "smtts_watermark": (i32, [vp, vp, vp, i32, i64, vp, u64, f32, vp, i64, vp]),
+    "smtts_watermark_detect_workspace_bytes": (sz, [vp, i32, i64]),
+    "smtts_watermark_detect": (i32, [vp, vp, vp, i32, i64, vp, u64, i64, i32, vp, sz, vp, vp, vp, vp, vp]),
     "smtts_voice_expand": (i32, [vp, vp, vp, i32, i32, vp, vp, vp]),
     "smtts_randn_rows": (i32, [vp, vp, vp, vp, vp, i32, i32, i32]),
     "smtts_stitch": (i32, [vp, vp, vp, i32, i64, vp, vp, vp, i32, vp, i64, i32]),

@@ -504,6 +504,71 @@ def as_delivery(deliver) -> Optional["Delivery"]:
     raise TypeError(f"deliver must be None, a Delivery, a rate or a (rate, encoding) pair, got {type(deliver).__name__}")
 
 
+class Watermark:
+    """A keyed watermark on the audio the engine hands out (immutable; DESIGN 8k, include/smalltts_hip.h smtts_watermark): `key` an
+    integer in [0, 2^64), the shared secret the detector needs (whoever holds it can also strip the mark); `strength` in [0, 1], the
+    mark's amplitude relative to the RMS of the 64 samples in front (0.02: 34 dB below the signal; a design choice that has never
+    been listened to).  Embedded on the device at 24 kHz in front of the delivery, whole or in chunks that continue each other bit
+    for bit; SmallTTS.detect_watermark finds it again in f32 or PCM16 audio, also cropped from the front.  Detection is unvalidated
+    on real speech and on trained weights."""
+    __slots__ = ("key", "strength")
+
+    def __init__(self, key: int, strength: float = 0.02) -> None:
+        if isinstance(key, bool) or not isinstance(key, (int, np.integer)):
+            raise TypeError(f"Watermark: key must be an integer, got {type(key).__name__}")
+        if not 0 <= int(key) < 2 ** 64:
+            raise ValueError(f"Watermark: key must be in [0, 2^64), got {int(key)}")
+        if isinstance(strength, bool) or not isinstance(strength, (int, float, np.integer, np.floating)):
+            raise TypeError(f"Watermark: strength must be a number, got {type(strength).__name__}")
+        if not (0.0 <= float(strength) <= 1.0):                # (also refuses NaN)
+            raise ValueError(f"Watermark: strength must be in [0, 1], got {float(strength)}")
+        object.__setattr__(self, "key", int(key))
+        object.__setattr__(self, "strength", float(strength))
+
+    def __setattr__(self, name, value):
+        raise AttributeError("Watermark is immutable")
+
+    __delattr__ = __setattr__
+
+    def __repr__(self) -> str:
+        return f"Watermark(key={self.key!r}, strength={self.strength!r})"
+
+    def __eq__(self, other) -> bool:
+        return isinstance(other, Watermark) and (self.key, self.strength) == (other.key, other.strength)
+
+    def __hash__(self) -> int:
+        return hash((self.key, self.strength))
+
+
+def as_watermark(watermark) -> Optional["Watermark"]:
+    """The `watermark=` argument of the synthesis calls: None -> None (no mark, not one launch more), a Watermark -> itself, an
+    int -> Watermark(key), a (key, strength) pair -> Watermark(key, strength)."""
+    if watermark is None:
+        return None
+    if isinstance(watermark, Watermark):
+        return watermark
+    if isinstance(watermark, (int, np.integer)) and not isinstance(watermark, bool):
+        return Watermark(int(watermark))
+    if isinstance(watermark, (tuple, list)) and len(watermark) == 2:
+        return Watermark(watermark[0], watermark[1])
+    raise TypeError(f"watermark must be None, a Watermark, a key or a (key, strength) pair, got {type(watermark).__name__}")
+
+
+def marked_delivery(what: str, watermark, dv: Optional["Delivery"]):
+    """watermark= next to deliver= -> (Watermark or None, Delivery or None).  A mark without deliver= leaves as Delivery(24000, "f32");
+    any other rate, and G.711, are refused: the mark lives mostly above 4 kHz and is about as large as G.711's own noise, it would
+    not survive, and a silent no-op is worse than a refusal."""
+    wm = as_watermark(watermark)
+    if wm is None:
+        return None, dv
+    if dv is None:
+        dv = Delivery(24_000, "f32")
+    if dv.rate != 24_000 or dv.encoding not in ("f32", "pcm16"):
+        raise ValueError(f"{what}: watermark= needs 24000 Hz and f32 or pcm16 (the mark would not survive resampling or G.711), "
+                         f"got {dv!r}")
+    return wm, dv
+
+
 def token_groups(ids: Sequence[int]) -> List[Tuple[str, str, int, int]]:
     """The units word timings are reported for: runs of token ids between the space symbol.  -> [(kind, phonemes, t0, t1), ...] in
     order, [t0, t1) the run's token indices, phonemes = decode_token_ids of them.  kind "word": a run of letter / IPA symbols;
@@ -1035,6 +1100,47 @@ def _rows(audio: np.ndarray, ns: Sequence[int]) -> List[np.ndarray]:
     return [audio[b, :, : HOP_SIZE * n] for b, n in enumerate(ns)]
 
 
+def detect_watermark(engine: HipEngine, audio, key: int, *, max_offset: int = 0, threshold: float = 6.0) -> List[Tuple[float, int, bool]]:
+    """Looks for Watermark(key)'s mark in 24 kHz audio (include/smalltts_hip.h smtts_watermark_detect): `audio` one array
+    or a list of rows, float32 or int16 (PCM16: divided by 32767).  -> per row (z, offset, present): the best score over the
+    hypotheses "the row's first sample is stream sample o", o = 0 .. max_offset (audio cropped from the front), the lowest such o,
+    and z >= threshold.  Where the key's mark is absent z is about N(0, 1) per offset: the default threshold of 6 lets through
+    roughly (max_offset + 1) * 1e-9 false alarms.  The offsets are searched 65 536 per device call; needs no weights."""
+    rows = [audio] if isinstance(audio, np.ndarray) else list(audio)
+    key, max_offset = int(key), int(max_offset)
+    if not 0 <= key < 2 ** 64:
+        raise ValueError(f"detect_watermark: key must be in [0, 2^64), got {key}")
+    if not 0 <= max_offset <= 2 ** 40:
+        raise ValueError(f"detect_watermark: max_offset must be in [0, 2^40], got {max_offset}")
+    if not rows:
+        return []
+    flat = []
+    for r in rows:
+        r = np.asarray(r)
+        if r.dtype == np.int16:
+            r = r.astype(np.float32) / np.float32(32767.0)
+        elif r.dtype != np.float32:
+            raise TypeError(f"detect_watermark: float32 or int16 audio wanted, got {r.dtype}")
+        flat.append(np.ascontiguousarray(r.reshape(-1)))
+    res: List[Tuple[float, int, bool]] = []
+    for g0 in range(0, len(flat), 1024):                       # smtts_watermark_detect takes at most 1024 rows
+        grp = flat[g0: g0 + 1024]
+        lens = [len(r) for r in grp]
+        x = np.zeros((len(grp), max(max(lens), 1)), np.float32)
+        for b, r in enumerate(grp):
+            x[b, : len(r)] = r
+        xd = torch.from_numpy(x).to(engine.device)
+        best_z = np.full(len(grp), -np.inf, np.float32)
+        best_o = np.zeros(len(grp), np.int64)
+        for o_lo in range(0, max_offset + 1, 65536):
+            _T, _den, off, z = engine.watermark_detect(xd, lens, key, o_lo=o_lo, n_off=min(65536, max_offset + 1 - o_lo))
+            z, off = z.cpu().numpy(), off.cpu().numpy()
+            better = z > best_z                                # strictly: the lowest offset wins a tie
+            best_z, best_o = np.where(better, z, best_z), np.where(better, off, best_o)
+        res += [(float(best_z[b]), int(best_o[b]), bool(best_z[b] >= threshold)) for b in range(len(grp))]
+    return res
+
+
 class SmallTTS:
     """DMD few-step synthesis: condition-encode -> n-step sampler -> codec decode, all on one MI355X."""
 
@@ -1082,6 +1188,11 @@ class SmallTTS:
         if self._rng is not None:
             return int(self._rng.integers(0, 2 ** 63 - 1))
         return int(np.random.randint(0, 2 ** 31 - 1)) * 2654435761 % (2 ** 63)
+
+    def detect_watermark(self, audio, key: int, *, max_offset: int = 0, threshold: float = 6.0) -> List[Tuple[float, int, bool]]:
+        """detect_watermark on this instance's engine: one array or a list of rows, float32 or int16 at 24 kHz -> per row
+        (z, offset, present).  `max_offset`: how many samples the audio may have lost at its front."""
+        return detect_watermark(self.engine, audio, key, max_offset=max_offset, threshold=threshold)
 
     def encode_voice(self, ref_latents) -> Voice:
         """(R, 64) reference latents -> Voice: the style encoder and the 12 reference K / V projections run once, at B = 1, without
@@ -1241,7 +1352,8 @@ class SmallTTS:
                          voices: Optional[Sequence[Voice]] = None, seeds: Optional[Sequence[int]] = None, trim=None,
                          align=None, prefix_lens: Optional[Sequence[int]] = None, return_alignment: bool = False,
                          pins: Optional[Sequence[Optional[tuple]]] = None, start_step: int = 0, takes=None, return_takes: bool = False,
-                         repair=None, return_repair: bool = False, _decode: bool = True, deliver=None):
+                         repair=None, return_repair: bool = False, _decode: bool = True, deliver=None,
+                         watermark=None):
         """Batched synthesize: per-utterance (R_i,64) refs, token lists and durations -> list of (1, samples).
         `frames` overrides the per-utterance frame counts (default floor(duration * 7.5), infer/onnx.py:84; the HTTP server
         rounds up like the reference's Rust server, pipeline.rs:66).
@@ -1290,14 +1402,16 @@ class SmallTTS:
         resampled to the Delivery's rate and encoded on the device (engine.deliver, one launch whatever B is) and only that is copied
         out: row b comes back as (1, rate * ns[b] / 7.5) samples in the encoding's dtype (float32, int16, or uint8 G.711 codes), and
         the words of `align` are given in output samples.  Not together with `trim`.  None is the call as it always was: 24 kHz
-        fp32, not one launch more."""
+        fp32, not one launch more.
+        `watermark` (a Watermark, a key or a (key, strength) pair): every row is marked on the device in front of the
+        delivery (each row a stream of its own); without `deliver` it means Delivery(24000, "f32").  24 kHz, f32 or pcm16 only."""
         ep = as_endpointing(trim)
         al = as_alignment(align)
         tk = as_takes(takes)
         rp = as_repair(repair)
-        dv = as_delivery(deliver)
+        wm, dv = marked_delivery("synthesize_batch", watermark, as_delivery(deliver))
         if dv is not None and ep is not None:
-            raise ValueError("synthesize_batch: deliver= and trim= exclude each other")
+            raise ValueError("synthesize_batch: deliver= (and with it watermark=) and trim= exclude each other")
         if dv is not None and _defer:
             raise ValueError("synthesize_batch: a deferred batch is delivered by its caller (engine.deliver)")
         if tk is None and return_takes:
@@ -1444,11 +1558,11 @@ class SmallTTS:
         if _defer:                                             # synthesize_batches / synthesize_long / the server: stay on the device / stream
             return rec
         return self._finish_batch(rec, ep, None if al is None else (phoneme_ids, p0s, ps), return_latents, return_alignment,
-                                  (K, row_seeds) if return_takes else None, return_repair, dv)
+                                  (K, row_seeds) if return_takes else None, return_repair, dv, wm)
 
     def _finish_batch(self, rec: _Batch, ep: Optional["Endpointing"], tokens: Optional[tuple], return_latents: bool,
                       return_alignment: bool, takes: Optional[tuple] = None, return_repair: bool = False,
-                      dv: Optional["Delivery"] = None):
+                      dv: Optional["Delivery"] = None, wm: Optional["Watermark"] = None):
         """synthesize_batch's tail: one batch from the device to what the call returns.  `tokens` = (token lists, prefix lengths, token
         counts) with align=, else None; `takes` = (K, the rows' seeds) with return_takes, else None.
         -> rows[, latents][, words[, raw alignment]][, takes][, repair]; the rows alone are returned bare."""
@@ -1458,7 +1572,7 @@ class SmallTTS:
         def read_head(rec):
             if dv is None:
                 return (rec.audio if ep is None else rec.seg).cpu().numpy(), None
-            out, counts = eng.deliver(rec.audio, [eng.hop * n for n in rec.ns], dv.rate, dv.encoding)   # behind the decode, same stream
+            out, counts = eng.deliver(rec.audio, [eng.hop * n for n in rec.ns], dv.rate, dv.encoding, mark=wm)   # behind the decode, same stream
             return out.cpu().numpy(), counts
         head, counts = read_head(rec)                          # synchronises: the saturation counters are final
         if eng.check_fp16_range("synthesize"):                 # an fp16 operand clipped: the site is split-bf16 now, run again
@@ -1590,7 +1704,7 @@ class SmallTTS:
                         fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3, pcm16: bool = False,
                         prefix_tokens: Optional[Sequence[int]] = None, trim=None, return_segments: bool = False,
                         return_words: bool = False, align=None, return_pieces: bool = False, takes=None, return_takes: bool = False,
-                        repair=None, return_repair: bool = False, deliver=None):
+                        repair=None, return_repair: bool = False, deliver=None, watermark=None):
         """A whole text in one voice -> one waveform (1, S), fp32 or (pcm16=True) int16 PCM, S = sum(3200 * n_i) + (pieces - 1) *
         round(gap_ms * 24).
 
@@ -1644,10 +1758,13 @@ class SmallTTS:
         offsets, lengths and starts and the word times are then given in output samples, ceil(up * s / down) of the 24 kHz position
         (a length as the difference of its two ends).  The pieces' batches are not resampled one by one.  Not together with
         pcm16=True (ask for Delivery(rate, "pcm16")).  None is the call as it always was.
+        `watermark` (a Watermark, a key or a (key, strength) pair): the JOINED waveform is marked on the device in front of
+        the delivery, as one stream from sample 0; without `deliver` it means Delivery(24000, "f32").  24 kHz, f32 or pcm16 only.
         Returns (waveform[, segments][, words][, pieces][, takes][, repair])."""
-        dv = as_delivery(deliver)
+        wm, dv = marked_delivery("synthesize_long", watermark, as_delivery(deliver))
         if dv is not None and pcm16:
-            raise ValueError("synthesize_long: deliver= and pcm16=True exclude each other: ask for Delivery(rate, 'pcm16')")
+            raise ValueError("synthesize_long: deliver= (and with it watermark=) and pcm16=True exclude each other: ask for "
+                             "Delivery(rate, 'pcm16')")
         ep = as_endpointing(trim)
         tk = as_takes(takes)
         rp = as_repair(repair)
@@ -1683,7 +1800,7 @@ class SmallTTS:
         base = self._next_seed() if seed is None else int(seed)
         seeds = [piece_seed(base, i) for i in range(len(toks))]
         calls, al_b = self._long_calls(voice, toks, ns, seeds, groups, len(prefix), ep, al, tk, rp, return_takes)
-        out, segs, pending = self._join_long(calls, groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16, dv)
+        out, segs, pending = self._join_long(calls, groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16, dv, wm)
         words = made = taken = None
         mended = _read_repair(pending) if return_repair else None   # one small read-back for the whole text
         spoken = seeds
@@ -1718,7 +1835,7 @@ class SmallTTS:
         return result(out, segs, words, made, taken, mended)
 
     def _join_long(self, calls, groups, ns, offsets, S, ep: Optional["Endpointing"], in_flight: int, gap_ms: float, fade_ms: float,
-                   pcm16: bool, dv: Optional["Delivery"] = None):
+                   pcm16: bool, dv: Optional["Delivery"] = None, wm: Optional["Watermark"] = None):
         """The tail synthesize_long and render_long share: the deferred batches `calls` (one per group) run through _run_in_flight,
         their rows are joined on the device and copied out once.  With `ep` the records carry their endpoints (every batch enqueued
         them behind its decode, and so does its re-run): the tables are read back once and the join puts the speech windows `gap_ms`
@@ -1744,7 +1861,7 @@ class SmallTTS:
         if dv is not None:                                     # the joined waveform, one row, at the caller's rate and encoding
             if S == 0:
                 return np.zeros((1, 0), dv.dtype), segs, pending
-            d, cnt = eng.deliver(out.view(1, 1, S), [S], dv.rate, dv.encoding)
+            d, cnt = eng.deliver(out.view(1, 1, S), [S], dv.rate, dv.encoding, mark=wm)
             return d[:, :cnt[0]].cpu().numpy(), segs, pending
         return out.cpu().numpy()[None], segs, pending
 
@@ -1753,7 +1870,7 @@ class SmallTTS:
                                fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3, pcm16: bool = False,
                                prefix_tokens: Optional[Sequence[int]] = None, trim=None, align=None, return_words: bool = False,
                                return_pieces: bool = False, takes=None, repair=None, deliver=None,
-                               batch_sizes: Optional[Sequence[int]] = (1, 2, 4, 8)):
+                               batch_sizes: Optional[Sequence[int]] = (1, 2, 4, 8), watermark=None):
         """synthesize_long handed out batch by batch: a generator of LongChunk(audio, index, offset, segments, words,
         pieces), one per group of pieces, whose audio concatenated along axis 1 is the joined waveform.  The arguments are
         synthesize_long's (without the return_takes / return_repair reports; the segments always come, in the chunks).
@@ -1777,9 +1894,10 @@ class SmallTTS:
 
         Closing the generator early waits for what is in flight and leaves the engine as a finished call does.  Empty text yields
         nothing.  Arguments are checked here, before the first next()."""
-        dv = as_delivery(deliver)
+        wm, dv = marked_delivery("synthesize_long_stream", watermark, as_delivery(deliver))   # (DESIGN 8k: one mark stream for the text)
         if dv is not None and pcm16:
-            raise ValueError("synthesize_long_stream: deliver= and pcm16=True exclude each other: ask for Delivery(rate, 'pcm16')")
+            raise ValueError("synthesize_long_stream: deliver= (and with it watermark=) and pcm16=True exclude each other: ask for "
+                             "Delivery(rate, 'pcm16')")
         ep = as_endpointing(trim)
         tk = as_takes(takes)
         rp = as_repair(repair)
@@ -1800,10 +1918,11 @@ class SmallTTS:
         seeds = [piece_seed(base, i) for i in range(len(toks))]
         calls, _al_b = self._long_calls(voice, toks, ns, seeds, groups, len(prefix), ep, al, tk, rp, False)
         return self._long_chunks(calls, groups, toks, ns, seeds, len(prefix), ep, K, int(in_flight), gap_ms, fade_ms, pcm16, dv,
-                                 return_words, return_pieces)
+                                 return_words, return_pieces, wm)
 
     def _long_chunks(self, calls, groups, toks, ns, seeds, n_prefix: int, ep: Optional["Endpointing"], K: int, in_flight: int,
-                     gap_ms: float, fade_ms: float, pcm16: bool, dv: Optional["Delivery"], return_words: bool, return_pieces: bool):
+                     gap_ms: float, fade_ms: float, pcm16: bool, dv: Optional["Delivery"], return_words: bool, return_pieces: bool,
+                     wm: Optional["Watermark"] = None):
         """synthesize_long_stream's generator: the groups' deferred batches `calls`, enqueued ahead, verified, joined and handed out."""
         if not calls:
             return
@@ -1821,6 +1940,7 @@ class SmallTTS:
         jstate = eng.join_state()
         bank_rate = dv is not None and dv.ratio != (1, 1)
         dstate = eng.deliver_state(1, dv.rate) if bank_rate else None
+        mstate = eng.watermark_state(1) if wm is not None else None   # the mark's slot: only verified batches ever advance it
         if bank_rate:
             _bank, up, down, width, _klen = eng.deliver_bank(dv.rate)
         queue: Dict[int, list] = {}                            # group -> [record, its event (None: run again on the caller's stream)]
@@ -1850,7 +1970,8 @@ class SmallTTS:
             last = gi == len(groups) - 1
             chunk, off, pos, dtable = eng.join_stream(rec.audio, seg, gain, fade, gap, jstate, last=last, pcm16=pcm16, cap=cap,
                                                       deliver_slot=0)
-            audio = chunk if dv is None else eng.deliver_from_table(chunk, dtable, dv.rate, dv.encoding, state=dstate)
+            audio = chunk if dv is None else eng.deliver_from_table(chunk, dtable, dv.rate, dv.encoding, state=dstate, mark=wm,
+                                                                    mark_state=mstate)
             parts = [("off", off), ("pos", pos)]
             if ep is not None:
                 parts += [("seg", rec.seg), ("gain", rec.gain)]
@@ -2059,7 +2180,8 @@ class SmallTTS:
 
     def synthesize_stream(self, ref_latents: Optional[np.ndarray], phoneme_ids: Sequence[int], duration_sec: float, *,
                           chunk_frames: Sequence[int] = (2, 4, 8, 16, 32), pcm16: bool = False, seed: Optional[int] = None,
-                          voice: Optional[Voice] = None, frames: Optional[int] = None, return_latents: bool = False, deliver=None):
+                          voice: Optional[Voice] = None, frames: Optional[int] = None, return_latents: bool = False, deliver=None,
+                          watermark=None):
         """synthesize() that hands the audio out while it is still being decoded: -> an iterator of numpy chunks
         (1, samples) fp32, or int16 with pcm16=True (engine.pcm16 on the device), whose concatenation is the utterance.
         The sampler runs ONCE, exactly as synthesize_batch runs it for this row (same seeds: `seed` is its seeds=[seed]; same
@@ -2078,10 +2200,14 @@ class SmallTTS:
         the chunks are (1, count) arrays in the encoding's dtype whose sizes follow audio.deliver_counts (a chunk waits for the
         resampler's look-ahead, the final chunk flushes it) and whose concatenation is the delivery of the whole utterance, bit for
         bit.  The delivery slot is snapshotted and restored with the decode slot for a re-decode.  Not together with pcm16=True.
+        `watermark` (a Watermark, a key or a (key, strength) pair): every chunk is marked in front of its delivery through
+        one mark slot, snapshotted and restored with the others; the chunks concatenate to the marked utterance, bit for bit.
+        Without `deliver` it means Delivery(24000, "f32").  24 kHz, f32 or pcm16 only.
         Not for trim=, align=, takes=, repair= (they need the whole utterance) or synthesize_long."""
-        dv = as_delivery(deliver)
+        wm, dv = marked_delivery("synthesize_stream", watermark, as_delivery(deliver))
         if dv is not None and pcm16:
-            raise ValueError("synthesize_stream: deliver= and pcm16=True exclude each other: ask for Delivery(rate, 'pcm16')")
+            raise ValueError("synthesize_stream: deliver= (and with it watermark=) and pcm16=True exclude each other: ask for "
+                             "Delivery(rate, 'pcm16')")
         sizes_in = [int(c) for c in chunk_frames]
         if not sizes_in or min(sizes_in) < 1:
             raise ValueError("synthesize_stream: chunk_frames needs at least one size, all >= 1")
@@ -2090,9 +2216,10 @@ class SmallTTS:
         rec = self.synthesize_batch(None if voice is not None else [ref_latents], [phoneme_ids], [duration_sec],
                                     frames=None if frames is None else [int(frames)], seeds=None if seed is None else [int(seed)],
                                     voices=None if voice is None else [voice], _defer=True, _decode=False)
-        return self._stream_chunks(rec, stream_chunks(rec.ns[0], sizes_in), bool(pcm16), bool(return_latents), dv)
+        return self._stream_chunks(rec, stream_chunks(rec.ns[0], sizes_in), bool(pcm16), bool(return_latents), dv, wm)
 
-    def _stream_chunks(self, rec: _Batch, sizes: Sequence[int], pcm16: bool, return_latents: bool, dv: Optional["Delivery"] = None):
+    def _stream_chunks(self, rec: _Batch, sizes: Sequence[int], pcm16: bool, return_latents: bool, dv: Optional["Delivery"] = None,
+                       wm: Optional["Watermark"] = None):
         eng = self.engine
         if not sizes:
             return
@@ -2102,6 +2229,8 @@ class SmallTTS:
         hop = eng.hop                                          # (the loaded codec's, not the reference constant: test specs differ)
         cnt = [hop * c for c in sizes]                         # samples chunk k hands out
         dstate = dsnap = None
+        mstate = None if wm is None else eng.watermark_state(1)   # the mark's slot, next to the decode slot (24 kHz: dstate is None)
+        msnap = None if wm is None else torch.empty_like(mstate)
         if dv is not None:                                     # one delivery slot next to the decode slot; sizes from integers alone
             from .audio import deliver_counts
             _bank, up, down, width, _klen = eng.deliver_bank(dv.rate)
@@ -2121,6 +2250,10 @@ class SmallTTS:
                     dsnap.copy_(dstate)
                     a = eng.deliver(a, [hop * sizes[k]], dv.rate, dv.encoding, state=dstate, slots=[0], n_before=[hop * t0],
                                     last=k == len(sizes) - 1)[0][None]
+                elif wm is not None:
+                    msnap.copy_(mstate)
+                    a = eng.deliver(a, [hop * sizes[k]], dv.rate, dv.encoding, slots=[0], n_before=[hop * t0], mark=wm,
+                                    mark_state=mstate)[0][None]
                 else:
                     a = eng.deliver(a, [hop * sizes[k]], dv.rate, dv.encoding)[0][None]
             a = eng.pcm16(a) if pcm16 else a
@@ -2141,6 +2274,8 @@ class SmallTTS:
                 state.copy_(snap)
                 if dstate is not None:
                     dstate.copy_(dsnap)
+                if mstate is not None:
+                    mstate.copy_(msnap)
                 ev = enqueue(k, t0)
                 ev.synchronize()
             out = host[k % 2][:, :cnt[k]].numpy().copy()
@@ -2187,10 +2322,11 @@ class Decoder(_CodecRunner):
         """latents f32 (batch, T, 64) -> audio f32 (batch, 1, 3200*T), returned on the CPU like the reference."""
         return self.engine.codec_decode(latents.detach()).cpu()
 
-    def open_stream(self, rows: int = 1, deliver=None) -> "DecodeStream":
+    def open_stream(self, rows: int = 1, deliver=None, watermark=None) -> "DecodeStream":
         """`rows` utterances decoded chunk by chunk: DecodeStream.decode(latents_chunk) continues where the last call ended.
-        `deliver` (a Delivery, a rate or a (rate, encoding) pair): the chunks leave at that rate and encoding."""
-        return DecodeStream(self.engine, rows, deliver)
+        `deliver` (a Delivery, a rate or a (rate, encoding) pair): the chunks leave at that rate and encoding.
+        `watermark` (a Watermark, a key or a (key, strength) pair): every row's stream is marked in front of the delivery."""
+        return DecodeStream(self.engine, rows, deliver, watermark)
 
 
 class DecodeStream:
@@ -2200,14 +2336,17 @@ class DecodeStream:
     With `deliver` decode(chunk, last=False) -> (rows, count) on the CPU in the Delivery's dtype: the chunk at its rate and
     encoding, count = audio.deliver_counts of the samples seen so far (the resampler's look-ahead is held back until last=True
     flushes it); the concatenated chunks are engine.deliver of the whole decode, bit for bit.  The delivery slots are reset,
-    snapshotted and restored together with the decode slots."""
+    snapshotted and restored together with the decode slots.
+    With `watermark` (24 kHz, f32 or pcm16, Delivery(24000, "f32") without `deliver`) every row is marked as one stream in
+    front of the delivery; the mark slots are reset, snapshotted and restored with the others."""
 
-    def __init__(self, engine: HipEngine, rows: int = 1, deliver=None) -> None:
+    def __init__(self, engine: HipEngine, rows: int = 1, deliver=None, watermark=None) -> None:
+        self.watermark, self.deliver = marked_delivery("DecodeStream", watermark, as_delivery(deliver))
         self.engine, self.rows = engine, int(rows)
         self.state = engine.decode_state(self.rows)
         self._slots = list(range(self.rows))
-        self.deliver = as_delivery(deliver)
         self._dstate = None if self.deliver is None else engine.deliver_state(self.rows, self.deliver.rate)
+        self._mstate = None if self.watermark is None else engine.watermark_state(self.rows)
         self._seen = 0                                         # samples every row's delivery stream has taken in
 
     def decode(self, latents: torch.Tensor, last: bool = False) -> torch.Tensor:
@@ -2219,6 +2358,8 @@ class DecodeStream:
         n = int(audio.shape[-1])
         kw = {} if self._dstate is None else {"state": self._dstate, "slots": self._slots, "n_before": [self._seen] * self.rows,
                                               "last": bool(last)}
+        if self._mstate is not None:                           # (24 kHz: no delivery state, the mark's slots alone)
+            kw = {"slots": self._slots, "n_before": [self._seen] * self.rows, "mark": self.watermark, "mark_state": self._mstate}
         out, counts = self.engine.deliver(audio, [n] * self.rows, self.deliver.rate, self.deliver.encoding, **kw)
         self._seen += n
         return out[:, :counts[0]].cpu()
@@ -2227,12 +2368,15 @@ class DecodeStream:
         self.state.zero_()
         if self._dstate is not None:
             self._dstate.zero_()
+        if self._mstate is not None:
+            self._mstate.zero_()
         self._seen = 0
 
     def snapshot(self):
         if self.deliver is None:
             return self.state.clone()
-        return (self.state.clone(), None if self._dstate is None else self._dstate.clone(), self._seen)
+        return (self.state.clone(), None if self._dstate is None else self._dstate.clone(), self._seen,
+                None if self._mstate is None else self._mstate.clone())
 
     def restore(self, snap) -> None:
         if self.deliver is None:
@@ -2241,6 +2385,8 @@ class DecodeStream:
         self.state.copy_(snap[0])
         if self._dstate is not None:
             self._dstate.copy_(snap[1])
+        if self._mstate is not None:
+            self._mstate.copy_(snap[3])
         self._seen = int(snap[2])
 
 

@@ -3,6 +3,7 @@
 // layout permits, grid sized to cover the chip (>= 256 CUs x several waves).
 #include <cstdlib>
 #include "kernels.hpp"
+#include "philox.hpp"
 #include "prof.hpp"
 
 #define LAUNCH_CHECK() return hipGetLastError()
@@ -376,19 +377,8 @@ hipError_t launch_cfg_combine(const float* v3, float* v, float s_text, float s_s
 }
 
 // ------------------------------------------------------------------------------------------
-// Philox4x32-10 + Box-Muller
+// Philox4x32-10 (philox.hpp) + Box-Muller
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        uint32_t hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
-        uint32_t hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
-        uint32_t n0 = hi1 ^ c[1] ^ k0, n1 = lo1, n2 = hi0 ^ c[3] ^ k1, n3 = lo0;
-        c[0] = n0; c[1] = n1; c[2] = n2; c[3] = n3;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-}
 // the four normals of quad q of a (seed, stream) sequence: counter = (q, stream), key = seed, two Box-Muller pairs
 __device__ __forceinline__ void randn_quad(long q, uint64_t seed, uint64_t stream, float z[4]) {
     uint32_t c[4] = {(uint32_t)q, (uint32_t)((uint64_t)q >> 32), (uint32_t)stream, (uint32_t)(stream >> 32)};

@@ -1088,15 +1088,21 @@ class HipEngine:
         return torch.zeros(int(n_slots), sb, dtype=torch.uint8, device=self.device)
 
     def deliver(self, audio, lens, rate: int, encoding: str = "f32", *, state: Optional[torch.Tensor] = None, slots=None,
-                n_before=None, last=True, zeros: Optional[int] = None):
+                n_before=None, last=True, zeros: Optional[int] = None, mark=None, mark_state: Optional[torch.Tensor] = None):
         """audio (B,1,S) fp32 on the device, row b = the next lens[b] samples of its stream -> (out (B, max count) in the encoding's
         dtype on the device, counts): row b of `out` holds counts[b] samples at `rate`, nothing is written behind them
         (smtts_deliver).  encoding "f32" | "pcm16" | "mulaw" | "alaw".  Whole signals: state=None (then n_before must be 0 and last
         True).  Streams: state=deliver_state(...), slots = B distinct slot indices, n_before = samples each stream has seen, last =
         True (or a flag per row) on a stream's final chunk; the chunks' concatenation is the whole call's result, bit for bit.
         counts come from audio.deliver_counts: integers alone.  The table goes up pinned and non-blocking; on the current stream, no
-        synchronisation."""
+        synchronisation.
+        mark = (key, strength) (or an object with .key and .strength): the 24 kHz rows are watermarked on the SAME table
+        into a scratch buffer in front of smtts_deliver (engine.watermark's launches, nothing else changes).  mark_state =
+        watermark_state(...) carries the mark from chunk to chunk through the same `slots` and `n_before`, also at 24 kHz, where the
+        delivery itself has no state; without it every row starts a stream of its own."""
         from .audio import DELIVER_ENCODINGS, deliver_counts, deliver_max_count
+        if mark is None and mark_state is not None:
+            raise ValueError("deliver: mark_state= belongs to mark=")
         if encoding not in DELIVER_ENCODINGS:
             raise ValueError(f"deliver: encoding must be one of {DELIVER_ENCODINGS}, got {encoding!r}")
         enc = DELIVER_ENCODINGS.index(encoding)
@@ -1126,10 +1132,15 @@ class HipEngine:
             if len(sl) != B or len(set(sl)) != B or min(sl) < 0 or max(sl) >= n_slots:
                 raise ValueError(f"deliver: {B} distinct slots in [0, {n_slots}) wanted, got {sl}")
         else:
-            if slots is not None or (bank is not None and (any(nb) or not all(lasts))):
+            if (slots is not None and mark_state is None) or (bank is not None and (any(nb) or not all(lasts))):
                 raise ValueError("deliver: without state every row starts and ends here: no slots, n_before = 0, last = True "
                                  "(24 kHz, a pure encode, takes any n_before and last and ignores them)")
             n_slots, sl = 0, [0] * B
+        if mark_state is not None:
+            m_slots = self._watermark_pool(mark_state, "deliver")
+            sl = [int(v) for v in (slots if slots is not None else [])]
+            if len(sl) != B or len(set(sl)) != B or min(sl) < 0 or max(sl) >= m_slots:
+                raise ValueError(f"deliver: {B} distinct slots in [0, {m_slots}) wanted, got {sl}")
         if bank is None:
             counts, stride = list(ln), row
         else:
@@ -1137,20 +1148,27 @@ class HipEngine:
             stride = max(1, deliver_max_count(row, up, down, width, pooled))
         out = torch.empty(B, stride, dtype=(torch.float32, torch.int16, torch.uint8, torch.uint8)[enc], device=self.device)
         tab = self._upload_i64([[s, a, n, int(f)] for s, a, n, f in zip(sl, nb, ln, lasts)])
+        if mark is not None:
+            audio = self._watermark_table(audio, B, row, tab, mark, mark_state, "deliver")
         self._ck(self.lib.smtts_deliver(self.h, self._stream(), _p(audio), B, row, _p(tab), _p(bank), up, down, klen, width,
                                         _p(state) if pooled else None, n_slots, enc, _p(out), stride), "deliver")
         return out, counts
 
     def deliver_from_table(self, chunk: torch.Tensor, dtable: torch.Tensor, rate: int, encoding: str = "f32", *,
-                           state: Optional[torch.Tensor] = None, zeros: Optional[int] = None) -> torch.Tensor:
+                           state: Optional[torch.Tensor] = None, zeros: Optional[int] = None, mark=None,
+                           mark_state: Optional[torch.Tensor] = None) -> torch.Tensor:
         """deliver() for ONE row whose table row already lies on the device: chunk (cap,) fp32 and dtable int64 (4,) = (slot, n_before,
         len, last) as join_stream() wrote them, so the delivery is enqueued right behind the join without the host knowing the
         length.  -> out (1, audio.deliver_max_count(cap, ...)) in the encoding's dtype on the device; the row's count follows
         afterwards from join_stream's rec with audio.deliver_counts(rec[0], rec[1] - rec[0], last, up, down, width): integers alone
         (at 24 kHz: rec[1] - rec[0]).  state = deliver_state(...) carries the stream from chunk to chunk through the slot dtable names
         (clamped into the pool by the kernel); state=None: the chunk starts and ends a stream of its own (at 24 kHz, a pure encode,
-        there is nothing to carry and state must be None).  On the current stream, no synchronisation."""
+        there is nothing to carry and state must be None).  On the current stream, no synchronisation.
+        mark / mark_state: as in deliver(): the chunk is watermarked on the device-written dtable in front of smtts_deliver, so the
+        mark follows the stream's absolute position without the host knowing the length."""
         from .audio import DELIVER_ENCODINGS, deliver_max_count
+        if mark is None and mark_state is not None:
+            raise ValueError("deliver_from_table: mark_state= belongs to mark=")
         if encoding not in DELIVER_ENCODINGS:
             raise ValueError(f"deliver_from_table: encoding must be one of {DELIVER_ENCODINGS}, got {encoding!r}")
         enc = DELIVER_ENCODINGS.index(encoding)
@@ -1175,9 +1193,107 @@ class HipEngine:
             n_slots = int(state.shape[0])
         stride = row if bank is None else max(1, deliver_max_count(row, up, down, width, pooled))
         out = torch.empty(1, stride, dtype=(torch.float32, torch.int16, torch.uint8, torch.uint8)[enc], device=self.device)
+        if mark is not None:
+            if mark_state is not None:
+                self._watermark_pool(mark_state, "deliver_from_table")
+            chunk = self._watermark_table(chunk, 1, row, dtable, mark, mark_state, "deliver_from_table")
         self._ck(self.lib.smtts_deliver(self.h, self._stream(), _p(chunk), 1, row, _p(dtable), _p(bank), up, down, klen, width,
                                         _p(state) if pooled else None, n_slots, enc, _p(out), stride), "deliver")
         return out
+
+    # ---- watermark: key the 24 kHz stream, detect it (include/smalltts_hip.h smtts_watermark) ----
+    @staticmethod
+    def _mark_pair(mark, what: str):
+        """mark= -> (key as uint64, strength)."""
+        key, strength = (mark.key, mark.strength) if hasattr(mark, "key") else tuple(mark)
+        key, strength = int(key), float(strength)
+        if not 0 <= key < 2 ** 64:
+            raise ValueError(f"{what}: the key must be in [0, 2^64), got {key}")
+        if not (0.0 <= strength <= 1.0):
+            raise ValueError(f"{what}: strength must be in [0, 1], got {strength}")
+        return key, strength
+
+    def watermark_state(self, n_slots: int) -> torch.Tensor:
+        """A zeroed state pool of n_slots watermark streams: uint8 (n_slots, smtts_watermark_state_bytes) on the device, the last 127
+        unmarked samples of each stream.  A zero slot is the start of a stream; state[k].clone() / .copy_() snapshot and rewind it."""
+        if int(n_slots) < 1:
+            raise ValueError("watermark_state: at least one slot")
+        return torch.zeros(int(n_slots), int(self.lib.smtts_watermark_state_bytes(self.h)), dtype=torch.uint8, device=self.device)
+
+    def _watermark_pool(self, state, what: str) -> int:
+        sb = int(self.lib.smtts_watermark_state_bytes(self.h))
+        if (not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 2 or int(state.shape[1]) != sb
+                or int(state.shape[0]) < 1 or not state.is_contiguous() or state.device != self.device or state.data_ptr() % 16):
+            raise ValueError(f"{what}: the mark state must be a contiguous, 16-byte aligned uint8 (n_slots,{sb}) tensor on the engine's "
+                             "device (watermark_state())")
+        return int(state.shape[0])
+
+    def _watermark_table(self, audio: torch.Tensor, B: int, row: int, tab: torch.Tensor, mark, state, what: str) -> torch.Tensor:
+        """smtts_watermark on a table that already lies on the device -> the marked copy, shaped like audio."""
+        key, strength = self._mark_pair(mark, what)
+        out = torch.empty_like(audio)
+        self._ck(self.lib.smtts_watermark(self.h, self._stream(), _p(audio), B, row, _p(tab), key, strength, _p(state),
+                                          0 if state is None else int(state.shape[0]), _p(out)), "watermark")
+        return out
+
+    def watermark(self, audio, lens, key: int, strength: float = 0.02, *, state: Optional[torch.Tensor] = None, slots=None,
+                  n_before=None) -> torch.Tensor:
+        """audio (B,1,S) fp32 on the device, row b = the next lens[b] samples of its 24 kHz stream -> the marked copy (B,1,S): row b
+        holds lens[b] marked samples, nothing is written behind them (smtts_watermark).  Whole signals: state=None (every row starts
+        a stream).  Streams: state=watermark_state(...), slots = B distinct slot indices, n_before = samples each stream has seen;
+        the chunks' concatenation is the whole call's result, bit for bit.  On the current stream, no synchronisation."""
+        if (not isinstance(audio, torch.Tensor) or audio.dtype != torch.float32 or audio.dim() != 3 or int(audio.shape[1]) != 1
+                or not audio.is_contiguous() or audio.device != self.device or int(audio.shape[0]) < 1 or int(audio.shape[2]) < 1):
+            raise ValueError("watermark: audio must be a contiguous fp32 (B,1,S) tensor on the engine's device with B, S >= 1")
+        B, row = int(audio.shape[0]), int(audio.shape[2])
+        ln = [int(v) for v in lens]
+        if len(ln) != B or min(ln) < 0 or max(ln) > row:
+            raise ValueError(f"watermark: {B} lengths in [0, {row}] wanted, got {ln}")
+        nb = [0] * B if n_before is None else [int(v) for v in n_before]
+        if len(nb) != B or min(nb) < 0:
+            raise ValueError(f"watermark: one non-negative n_before per row wanted, got {nb}")
+        if state is not None:
+            n_slots = self._watermark_pool(state, "watermark")
+            sl = [int(v) for v in (slots if slots is not None else [])]
+            if len(sl) != B or len(set(sl)) != B or min(sl) < 0 or max(sl) >= n_slots:
+                raise ValueError(f"watermark: {B} distinct slots in [0, {n_slots}) wanted, got {sl}")
+        else:
+            if slots is not None or any(nb):
+                raise ValueError("watermark: without state every row starts here: no slots, n_before = 0")
+            sl = [0] * B
+        tab = self._upload_i64([[s, a, n, 0] for s, a, n in zip(sl, nb, ln)])
+        return self._watermark_table(audio, B, row, tab, (key, strength), state, "watermark")
+
+    def watermark_detect(self, audio: torch.Tensor, lens, key: int, *, o_lo: int = 0, n_off: int = 1, return_u: bool = False):
+        """audio fp32 (B,S) on the device, row b = lens[b] samples at 24 kHz -> (T (B,n_off), den (B), best_off (B) int64, best_z (B)[,
+        u (B,S)]) on the device (smtts_watermark_detect): T[b][k] is the sign correlation at offset o_lo + k ("audio[j] is stream
+        sample j + o"), best_off = o_lo + argmax, best_z = T / sqrt(den), about N(0, 1) where the key's mark is absent.  u is written
+        below lens[b] only (zeros behind).  Needs no weights.  Three launches on the current stream, no synchronisation."""
+        if (not isinstance(audio, torch.Tensor) or audio.dtype != torch.float32 or audio.dim() != 2 or not audio.is_contiguous()
+                or audio.device != self.device or not 1 <= int(audio.shape[0]) <= 1024 or int(audio.shape[1]) < 1):
+            raise ValueError("watermark_detect: audio must be a contiguous fp32 (B,S) tensor on the engine's device, 1 <= B <= 1024, S >= 1")
+        B, row = int(audio.shape[0]), int(audio.shape[1])
+        ln = [int(v) for v in lens]
+        if len(ln) != B or min(ln) < 0 or max(ln) > row:
+            raise ValueError(f"watermark_detect: {B} lengths in [0, {row}] wanted, got {ln}")
+        key, o_lo, n_off = int(key), int(o_lo), int(n_off)
+        if not 0 <= key < 2 ** 64:
+            raise ValueError(f"watermark_detect: the key must be in [0, 2^64), got {key}")
+        if not (0 <= o_lo <= 2 ** 40 and 1 <= n_off <= 65536):
+            raise ValueError(f"watermark_detect: o_lo in [0, 2^40] and n_off in [1, 65536] wanted, got {o_lo}, {n_off}")
+        need = int(self.lib.smtts_watermark_detect_workspace_bytes(self.h, B, row))
+        if need <= 0:
+            raise RuntimeError(f"watermark_detect: {self.lib.smtts_last_error(self.h).decode()}")
+        ws = self._workspace(need)
+        u = torch.zeros(B, row, device=self.device) if return_u else None
+        T = torch.empty(B, n_off, device=self.device)
+        den = torch.empty(B, device=self.device)
+        best_z = torch.empty(B, device=self.device)
+        best_off = torch.empty(B, dtype=torch.int64, device=self.device)
+        lens_d = self._upload_i64(ln)
+        self._ck(self.lib.smtts_watermark_detect(self.h, self._stream(), _p(audio), B, row, _p(lens_d), key, o_lo, n_off, _p(ws), need,
+                                                 _p(u), _p(den), _p(T), _p(best_off), _p(best_z)), "watermark_detect")
+        return (T, den, best_off, best_z, u) if return_u else (T, den, best_off, best_z)
 
     def profile(self, on, tagged: bool = False, shapes: bool = False):
         """on: False/True; tagged=True prefixes kernel names with the pipeline phase (enc, mod, dit, dec.s<i> ...); shapes=True

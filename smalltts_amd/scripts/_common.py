@@ -33,6 +33,35 @@ def delivery_for(args):
     return Delivery(args.rate or 24_000, args.encoding or "pcm16")
 
 
+def key_arg(text: str) -> int:
+    """A watermark key on the command line: decimal, or 0x... hexadecimal."""
+    return int(text, 0)
+
+
+def add_watermark_args(ap: argparse.ArgumentParser) -> None:
+    """--watermark KEY [--watermark-strength S]: the output is marked on the device (api.Watermark)."""
+    ap.add_argument("--watermark", type=key_arg, default=None, metavar="KEY",
+                    help="mark the output with this integer key (24000 Hz PCM16 only); scripts.detect finds it again")
+    ap.add_argument("--watermark-strength", type=float, default=None, metavar="S", help="mark amplitude relative to the signal (default 0.02)")
+
+
+def watermark_for(ap: argparse.ArgumentParser, args, dv):
+    """-> (None or the api.Watermark the flags ask for, the Delivery to use: Delivery(24000, "pcm16") where a mark has none)."""
+    from ..api import Delivery, Watermark
+    if args.watermark is None:
+        if args.watermark_strength is not None:
+            ap.error("--watermark-strength belongs to --watermark")
+        return None, dv
+    if dv is None:
+        dv = Delivery(24_000, "pcm16")
+    if dv.rate != 24_000 or dv.encoding != "pcm16":
+        ap.error("--watermark needs 24000 Hz PCM16 output: the mark would not survive resampling or G.711")
+    try:
+        return Watermark(args.watermark, 0.02 if args.watermark_strength is None else args.watermark_strength), dv
+    except ValueError as e:
+        ap.error(str(e))
+
+
 def pcm16_host(audio) -> np.ndarray:
     """float [-1, 1] -> int16 by write_wav_pcm16's arithmetic (clamp, x 32767, round to nearest even)."""
     a = np.asarray(audio, dtype=np.float32).reshape(-1)

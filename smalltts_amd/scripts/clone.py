@@ -1,5 +1,5 @@
 """python -m smalltts_amd.scripts.clone --wav ref.wav --text "..." [--duration S] [--out out/clone.wav] [--trim] [--trim-ref]
-[--rate 8000 --encoding mulaw]
+[--rate 8000 --encoding mulaw] [--watermark KEY [--watermark-strength S]]
 (reference src/scripts/infer/clone.py: read wav -> mono -> 24 kHz -> codec encode -> synthesize)"""
 import argparse
 from pathlib import Path
@@ -7,7 +7,8 @@ from pathlib import Path
 import torch
 
 from ..api import HOP_SIZE, Encoder, Endpointing, SmallTTS, estimate_duration
-from ._common import add_delivery_args, add_engine_args, delivery_for, load_reference_wav, tokens_for, write_output
+from ._common import (add_delivery_args, add_engine_args, add_watermark_args, delivery_for, load_reference_wav, tokens_for, watermark_for,
+                      write_output)
 
 
 def main(argv=None):
@@ -20,10 +21,11 @@ def main(argv=None):
     ap.add_argument("--trim-ref", action="store_true", help="cut the reference clip to its speech (whole codec hops) before encoding it")
     add_engine_args(ap)
     add_delivery_args(ap)
+    add_watermark_args(ap)
     args = ap.parse_args(argv)
-    dv = delivery_for(args)
+    wm, dv = watermark_for(ap, args, delivery_for(args))
     if dv is not None and args.trim:
-        ap.error("--rate / --encoding do not go with --trim")
+        ap.error("--rate / --encoding / --watermark do not go with --trim")
     Path(args.out).parent.mkdir(parents=True, exist_ok=True)
     print("loading")
     kw = dict(weights=args.weights, device=args.device, precision=args.precision)
@@ -45,7 +47,7 @@ def main(argv=None):
     print(f"generating ({duration:.1f}s)")
     audio = (tts.synthesize_batch([ref_latents], [tokens], [duration], trim=True)[0] if args.trim
              else tts.synthesize(ref_latents, tokens, duration) if dv is None
-             else tts.synthesize_batch([ref_latents], [tokens], [duration], deliver=dv)[0])
+             else tts.synthesize_batch([ref_latents], [tokens], [duration], deliver=dv, watermark=wm)[0])
     write_output(args.out, audio, dv)
     print(args.out)
 

@@ -5,7 +5,8 @@ reference voice; prints generation time and the real-time factor like the refere
 plays through `sounddevice` and draws with `rich`; both are optional here — without sounddevice every utterance is written to
 out/interactive_NNN.wav instead.  --stream decodes in chunks (SmallTTS.synthesize_stream) and prints the time to the first chunk next
 to the total (`gen 0.02s, first chunk 0.01s, 480.0x rt`); with it --rate / --encoding make the chunks leave the device at that rate
-and encoding (api.Delivery), and the file written is a WAV of that format."""
+and encoding (api.Delivery), and the file written is a WAV of that format; --watermark KEY [--watermark-strength S] marks the chunks
+on the device (api.Watermark; 24000 Hz PCM16 only)."""
 import argparse
 import sys
 import time
@@ -15,7 +16,8 @@ import numpy as np
 import torch
 
 from ..api import Encoder, SmallTTS, estimate_duration
-from ._common import add_delivery_args, add_engine_args, delivery_for, load_reference_wav, tokens_for, write_output
+from ._common import (add_delivery_args, add_engine_args, add_watermark_args, delivery_for, load_reference_wav, tokens_for, watermark_for,
+                      write_output)
 
 
 def main(argv=None, lines=None):
@@ -26,10 +28,11 @@ def main(argv=None, lines=None):
     ap.add_argument("--stream", action="store_true", help="decode in chunks; also print the time to the first chunk")
     add_engine_args(ap)
     add_delivery_args(ap)
+    add_watermark_args(ap)
     args = ap.parse_args(argv)
-    dv = delivery_for(args)
+    wm, dv = watermark_for(ap, args, delivery_for(args))
     if dv is not None and not args.stream:
-        ap.error("--rate / --encoding belong to --stream")
+        ap.error("--rate / --encoding / --watermark belong to --stream")
     try:
         import sounddevice as sd
     except Exception:
@@ -62,7 +65,7 @@ def main(argv=None, lines=None):
         t_first = None
         if args.stream:
             chunks = []
-            for c in model.synthesize_stream(ref_latents, tokens, estimate_duration(s), **({} if dv is None else {"deliver": dv})):
+            for c in model.synthesize_stream(ref_latents, tokens, estimate_duration(s), **({} if dv is None else {"deliver": dv, "watermark": wm})):
                 t_first = time.perf_counter() - st if t_first is None else t_first
                 chunks.append(c)
             audio = np.concatenate(chunks, axis=1)

@@ -19,6 +19,8 @@ and the reference need 6 to 225 frames), and every entry of "takes" gains "cos",
 with --words the JSON gains "repair": [{piece, kept, bad, free, before, after}, ...], one list entry per round in each field.
 --rate R / --encoding pcm16|mulaw|alaw: the joined waveform is resampled and encoded on the device (api.Delivery) and written as a WAV
 of that format; not together with --words / --srt.
+--watermark KEY [--watermark-strength S]: the joined waveform is marked with the key on the device (api.Watermark; 24000 Hz
+PCM16 only, with and without --stream); python -m smalltts_amd.scripts.detect --wav out.wav --key KEY finds the mark again.
 --stream: the WAV is written while the text is still being spoken (api.SmallTTS.synthesize_long_stream, audio.WavStreamWriter): one
 chunk per group of pieces, the first after one piece's work; the time to the first chunk and the total are printed.  --batch-sizes
 1,2,4,8 (the default ramp) or `none` (groups of --max-batch, the file --stream-less runs write, byte for byte).  --words / --srt /
@@ -33,7 +35,7 @@ import numpy as np
 from ..api import SAMPLE_RATE, Endpointing, Repair, SmallTTS, Takes, estimate_duration, format_srt, save_take, split_text, token_groups
 from ..audio import WavStreamWriter, read_wav
 from ..phonemes import decode_token_ids, get_token_ids, parse_tokens_arg
-from ._common import add_delivery_args, add_engine_args, delivery_for, pcm16_host, write_output
+from ._common import add_delivery_args, add_engine_args, add_watermark_args, delivery_for, pcm16_host, watermark_for, write_output
 
 
 def group_texts(token_lists) -> list:
@@ -131,7 +133,9 @@ def parse_args(argv=None):
                     help="with --stream: pieces per group, the last value repeated (default 1,2,4,8); none = groups of --max-batch")
     add_engine_args(ap)
     add_delivery_args(ap)
+    add_watermark_args(ap)
     args = ap.parse_args(argv)
+    args.mark, args.delivery = watermark_for(ap, args, delivery_for(args))   # --watermark: the joined waveform is marked on the device
     if args.batch_sizes is not None and not args.stream:
         ap.error("--batch-sizes needs --stream")
     if args.batch_sizes is not None and args.batch_sizes.strip().lower() != "none":
@@ -181,9 +185,11 @@ def main(argv=None):
     voice = tts.encode_voice_wav(y, sr)
     kw = dict(seed=args.seed, gap_ms=args.gap_ms, fade_ms=args.fade_ms, max_batch=args.max_batch, in_flight=args.in_flight,
               trim=Endpointing(level_dbfs=args.level) if args.trim else None)
-    dv = delivery_for(args)
+    dv = args.delivery
     if dv is not None:
         kw.update(deliver=dv)                              # the joined waveform leaves the device at that rate and encoding
+    if args.mark is not None:
+        kw.update(watermark=args.mark)
     timed = bool(args.words or args.srt)
     if timed:
         kw.update(return_segments=True, return_words=True)
