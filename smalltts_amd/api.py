@@ -13,6 +13,7 @@ offline).  Unlike the reference, `forward` runs all utterances as ONE padded bat
 from __future__ import annotations
 
 import collections
+import contextlib
 import hashlib
 import os
 from typing import Callable, Dict, Iterable, List, NamedTuple, Optional, Sequence, Tuple
@@ -22,761 +23,18 @@ import torch
 
 from .engine import ASR_MAX_ROWS, ASR_UPSAMPLE, DEFAULT_PRECISION, SITES, SV_DIM, SV_MAX_ROWS, SV_MIN_FRAMES, HipEngine
 from .weights import DEFAULT_CODEC, CodecSpec, all_param_specs, asr_param_specs, load_weight_file, sv_param_specs
+# the option records (options.py) and the host arithmetic (plans.py) live in modules of their own; every name stays importable from here
+from .options import (ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS, TAKE_JOIN_KEYS, Alignment, Delivery, Endpointing, Piece, Repair, Takes,
+                      Watermark, _Frozen, as_alignment, as_delivery, as_endpointing, as_repair, as_takes, as_watermark, load_take,
+                      marked_delivery, save_take)
+from .plans import (CHARS_PER_SECOND, HOP_SIZE, NUM_STEPS, SAMPLE_RATE, _CLAUSE_END, _SENTENCE_END, _check_pins,
+                    _default_count_tokens, _frames, _hard_cut, _srt_time, _units, estimate_duration, fade_table, format_srt,
+                    frames_of_groups, phoneme_error_rate, piece_seed, plan_long, plan_packed, repair_seed, splice_pins, split_text,
+                    stream_chunks, stream_groups, take_seed, token_groups, word_times)
 
-SAMPLE_RATE = 24_000
-HOP_SIZE = 3_200
-NUM_STEPS = 4
-CHARS_PER_SECOND = 11.5
 DEFAULT_WEIGHTS = os.environ.get("SMALLTTS_WEIGHTS", "assets/smalltts.smtts")
 
 _ENGINES: Dict[tuple, HipEngine] = {}
-
-
-def estimate_duration(text: str, min_sec: float = 0.5, max_sec: float = 30.0) -> float:
-    return max(min_sec, min(len(text) / CHARS_PER_SECOND, max_sec))
-
-
-# ---- long-form text: pieces the model was trained for (5 - 198 phonemes, at most ~30 s per utterance) --------------------------
-_SENTENCE_END = ".!?…"
-_CLAUSE_END = ";:,—"
-
-
-def _default_count_tokens(s: str) -> int:
-    from .phonemes import get_token_ids
-    return len(get_token_ids(s))
-
-
-def _hard_cut(word: str, fits: Callable[[str], bool]) -> List[str]:
-    """A single whitespace-free run that is over budget: longest fitting prefixes, never ending inside an `[event]` tag."""
-    from .phonemes import _EVENT_RE
-    out = []
-    while word and not fits(word):
-        tags = [m.span() for m in _EVENT_RE.finditer(word)]
-        cut = 0
-        for n in range(len(word) - 1, 0, -1):
-            if any(a < n < b for a, b in tags):
-                continue
-            if fits(word[:n]):
-                cut = n
-                break
-        if cut == 0:
-            raise ValueError(f"split_text: the budgets do not admit even one character or [event] tag of {word[:24]!r}")
-        out.append(word[:cut])
-        word = word[cut:]
-    if word:
-        out.append(word)
-    return out
-
-
-def split_text(text: str, max_tokens: int = 198, max_seconds: float = 30.0,
-               count_tokens: Optional[Callable[[str], int]] = None) -> List[str]:
-    """Cuts a text into pieces that each fit one utterance: `count_tokens(piece) <= max_tokens` and
-    `len(piece) / CHARS_PER_SECOND <= max_seconds` (estimate_duration without its clamp).  Cuts prefer sentence ends (`.!?…` in
-    front of whitespace or the end), then clause punctuation (`;:,—`), then whitespace; only a whitespace-free run that is over
-    budget on its own is cut inside, and never inside an `[event]` tag.  Greedy: a piece is extended while the next unit still
-    fits, so short sentences share a piece.  " ".join(pieces) is the text with runs of whitespace collapsed (up to hard cuts).
-    `count_tokens` defaults to len(phonemes.get_token_ids(s)), which needs espeak."""
-    count = count_tokens or _default_count_tokens
-
-    def fits(s: str) -> bool:
-        return len(s) / CHARS_PER_SECOND <= max_seconds and count(s) <= max_tokens
-
-    def pack(units: List[List[str]], level: int) -> List[List[str]]:
-        """units: runs of words that end at a boundary of `level` (0 sentence, 1 clause, 2 word).  Greedy in-order packing; a unit
-        that does not fit on its own is split at the next weaker boundary."""
-        pieces: List[List[str]] = []
-        cur: List[str] = []
-        for u in units:
-            if cur and fits(" ".join(cur + u)):
-                cur = cur + u
-                continue
-            if cur:
-                pieces.append(cur)
-                cur = []
-            if fits(" ".join(u)):
-                cur = u
-            elif level < 2:
-                sub = pack(_units(u, level + 1), level + 1)
-                pieces.extend(sub[:-1])
-                cur = sub[-1]        # the tail may still take what follows
-            else:                    # one word over budget
-                sub = [[w] for w in _hard_cut(u[0], fits)]
-                pieces.extend(sub[:-1])
-                cur = sub[-1]
-        if cur:
-            pieces.append(cur)
-        return pieces
-
-    words = text.split()   # an `[event]` tag holds no whitespace: it stays inside its word
-    if not words:
-        return []
-    return [" ".join(p) for p in pack(_units(words, 0), 0)]
-
-
-def _units(words: List[str], level: int) -> List[List[str]]:
-    """Groups words into runs that end behind a word closing with sentence (level 0) / clause (level 1) punctuation, optionally
-    followed by closing quotes or brackets; level 2: one word per unit."""
-    if level >= 2:
-        return [[w] for w in words]
-    marks = _SENTENCE_END if level == 0 else _SENTENCE_END + _CLAUSE_END
-    units, cur = [], []
-    for w in words:
-        cur.append(w)
-        if w.rstrip("\"'”’»)")[-1:] in marks:
-            units.append(cur)
-            cur = []
-    if cur:
-        units.append(cur)
-    return units
-
-
-def fade_table(fade_ms: float) -> np.ndarray:
-    """Raised-cosine fade-in weights w[i] = 0.5 - 0.5 cos(pi (i + 0.5) / F), F = round(fade_ms * 24): float64 math, rounded to fp32 once."""
-    F = int(round(fade_ms * SAMPLE_RATE / 1000.0))
-    if F <= 0:
-        return np.zeros((0,), np.float32)
-    return (0.5 - 0.5 * np.cos(np.pi * (np.arange(F, dtype=np.float64) + 0.5) / F)).astype(np.float32)
-
-
-def plan_long(ns: Sequence[int], max_batch: int = 8, gap_ms: float = 120.0, hop: int = HOP_SIZE) -> Tuple[List[List[int]], List[int], int]:
-    """The host-side plan of synthesize_long for pieces of `ns` frames: consecutive groups of at most `max_batch` pieces (the
-    splitter bounds every piece by the model's utterance limits, so a count is the only budget needed), every piece's sample
-    offset in the joined waveform, and its length S = sum(hop * n_i) + (len - 1) * round(gap_ms * 24)."""
-    if max_batch < 1:
-        raise ValueError("max_batch must be at least 1")
-    gap = max(0, int(round(gap_ms * SAMPLE_RATE / 1000.0)))
-    groups = [list(range(i, min(i + max_batch, len(ns)))) for i in range(0, len(ns), max_batch)]
-    offsets, pos = [], 0
-    for n in ns:
-        offsets.append(pos)
-        pos += hop * int(n) + gap
-    return groups, offsets, (pos - gap if len(ns) else 0)
-
-
-def plan_packed(ns_trimmed: Sequence[int], gap_ms: float = 120.0) -> Tuple[List[int], int]:
-    """The plan of a trimmed join: pieces of `ns_trimmed` SAMPLES (what the endpoint kernels returned), in order.  A piece with n = 0
-    takes neither room nor a gap; the others lie round(gap_ms * 24) samples apart.  -> (every piece's offset in the joined waveform
-    (an empty piece: where the last non-empty one ended), S = sum(n_i) + (k - 1) gap over the k non-empty pieces; 0 when all are empty)."""
-    gap = max(0, int(round(gap_ms * SAMPLE_RATE / 1000.0)))
-    offsets, pos, k = [], 0, 0
-    for n in ns_trimmed:
-        n = int(n)
-        if n < 0:
-            raise ValueError("plan_packed: negative length")
-        if n and k:
-            pos += gap
-        offsets.append(pos)
-        if n:
-            pos += n
-            k += 1
-    return offsets, pos
-
-
-class Endpointing:
-    """How the ends of the speech in a row are found, and how the row is levelled (immutable; DESIGN 8a, include/smalltts_hip.h
-    smtts_endpoints).  frame_ms: analysis frame; a frame is active when its mean power is above both `rel_db` below the row's
-    loudest frame and `floor_dbfs`; speech = runs of at least `min_run` active frames; `lead_ms` / `tail_ms` are kept in front of the
-    first / behind the last speech frame.  level_dbfs None: no gain; else the speech frames' RMS is brought to it, by at most
-    `max_gain_db`, and never so far that the row's peak passes `peak_dbfs`."""
-    __slots__ = ("frame_ms", "rel_db", "floor_dbfs", "min_run", "lead_ms", "tail_ms", "level_dbfs", "peak_dbfs", "max_gain_db")
-
-    def __init__(self, frame_ms: float = 10.0, rel_db: float = 40.0, floor_dbfs: float = -80.0, min_run: int = 3, lead_ms: float = 30.0,
-                 tail_ms: float = 60.0, level_dbfs: Optional[float] = None, peak_dbfs: float = -1.0, max_gain_db: float = 20.0) -> None:
-        set_ = object.__setattr__
-        for k, v in (("frame_ms", float(frame_ms)), ("rel_db", float(rel_db)), ("floor_dbfs", float(floor_dbfs)), ("min_run", int(min_run)),
-                     ("lead_ms", float(lead_ms)), ("tail_ms", float(tail_ms)),
-                     ("level_dbfs", None if level_dbfs is None else float(level_dbfs)), ("peak_dbfs", float(peak_dbfs)),
-                     ("max_gain_db", float(max_gain_db))):
-            set_(self, k, v)
-        W = 4 * int(round(self.frame_ms * SAMPLE_RATE / 1000.0 / 4))
-        if not 16 <= W <= 4096:
-            raise ValueError(f"Endpointing: frame_ms = {frame_ms} gives a frame of {W} samples, outside [16, 4096]")
-        if not 1 <= self.min_run <= 16:
-            raise ValueError("Endpointing: min_run must be in [1, 16]")
-        if self.lead_ms < 0 or self.tail_ms < 0 or self.rel_db < 0:
-            raise ValueError("Endpointing: lead_ms, tail_ms and rel_db must not be negative")
-        if not all(np.isfinite(v) for v in (self.frame_ms, self.rel_db, self.floor_dbfs, self.lead_ms, self.tail_ms, self.peak_dbfs,
-                                            self.max_gain_db, 0.0 if self.level_dbfs is None else self.level_dbfs)):
-            raise ValueError("Endpointing: every parameter must be finite")
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Endpointing is immutable")
-
-    __delattr__ = __setattr__
-
-    def __repr__(self) -> str:
-        return "Endpointing(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
-
-    def __eq__(self, other) -> bool:
-        return isinstance(other, Endpointing) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self) -> int:
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
-
-    def kernel_params(self) -> Dict[str, object]:
-        """The kernel's parameters: float64 arithmetic, rounded to fp32 once.  W = 4 round(frame_ms * 24 / 4) samples, rel_pow =
-        10^(-rel_db / 10), floor_pow = 10^(floor_dbfs / 10), lead / tail = round(ms * 24) samples, target_rms = 10^(level_dbfs / 20)
-        (0 = no gain), peak_limit = 10^(peak_dbfs / 20), max_gain = 10^(max_gain_db / 20)."""
-        f32 = lambda v: np.float32(np.float64(v))
-        per_ms = SAMPLE_RATE / 1000.0
-        return {"W": 4 * int(round(self.frame_ms * per_ms / 4)), "rel_pow": f32(10.0 ** (-self.rel_db / 10.0)),
-                "floor_pow": f32(10.0 ** (self.floor_dbfs / 10.0)), "min_run": self.min_run,
-                "lead": int(round(self.lead_ms * per_ms)), "tail": int(round(self.tail_ms * per_ms)),
-                "target_rms": np.float32(0.0) if self.level_dbfs is None else f32(10.0 ** (self.level_dbfs / 20.0)),
-                "peak_limit": f32(10.0 ** (self.peak_dbfs / 20.0)), "max_gain": f32(10.0 ** (self.max_gain_db / 20.0))}
-
-
-def as_endpointing(trim) -> Optional["Endpointing"]:
-    """The `trim=` argument of the synthesis calls: None / False -> None (off), True -> Endpointing(), an Endpointing -> itself."""
-    if trim is None or trim is False:
-        return None
-    if trim is True:
-        return Endpointing()
-    if isinstance(trim, Endpointing):
-        return trim
-    raise TypeError(f"trim must be None, a bool or an Endpointing, got {type(trim).__name__}")
-
-
-class Alignment:
-    """Which text-attention probabilities the word timings are read from (immutable; DESIGN 'Word timings', include/smalltts_hip.h
-    smtts_sample_align).  layers: DiT blocks in [0, 12); heads: attention heads in [0, 8); steps: sampler steps, indices into
-    range(num_steps), negative from the end.  None = the default of each: ALL layers, ALL heads, the LAST step (t = 0, where x_t is
-    the current estimate itself).  The result is the mean over the selected (step, layer, head) triples.
-
-    The default is UNVALIDATED on trained weights: every weight this project has run is seeded noise, and nobody has measured in
-    which layers and heads this model's text attention is monotone and peaky.  The mechanism is verified (the probabilities, the
-    optimal monotone path, the mapping to samples); the selection is a parameter for whoever holds a trained checkpoint.
-    Resolution: one codec frame, 3200 samples = 133 ms — word highlighting and subtitles, not lip-sync."""
-    __slots__ = ("layers", "heads", "steps")
-
-    def __init__(self, layers: Optional[Sequence[int]] = None, heads: Optional[Sequence[int]] = None,
-                 steps: Optional[Sequence[int]] = None) -> None:
-        set_ = object.__setattr__
-        for k, v, n in (("layers", layers, 12), ("heads", heads, 8), ("steps", steps, None)):
-            if v is not None:
-                v = tuple(sorted(set(int(i) for i in v)))
-                if not v:
-                    raise ValueError(f"Alignment: {k} must not be empty (None = the default)")
-                if n is not None and (v[0] < 0 or v[-1] >= n):
-                    raise ValueError(f"Alignment: {k} must lie in [0, {n}), got {v}")
-            set_(self, k, v)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Alignment is immutable")
-
-    __delattr__ = __setattr__
-
-    def __repr__(self) -> str:
-        return "Alignment(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
-
-    def __eq__(self, other) -> bool:
-        return isinstance(other, Alignment) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self) -> int:
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
-
-
-def as_alignment(align) -> Optional["Alignment"]:
-    """The `align=` argument of the synthesis calls: None / False -> None (off), True -> Alignment(), an Alignment -> itself."""
-    if align is None or align is False:
-        return None
-    if align is True:
-        return Alignment()
-    if isinstance(align, Alignment):
-        return align
-    raise TypeError(f"align must be None, a bool or an Alignment, got {type(align).__name__}")
-
-
-ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS = 225, 198   # the range of smtts_align_path: 30 s of frames, the phoneme window
-
-
-def phoneme_error_rate(ids: Sequence[int], ref: Sequence[int]) -> float:
-    """Edit distance (substitutions, insertions, deletions, each 1) between two phoneme id sequences over the length of `ref`; host
-    only.  An empty `ref` gives 0.0 for an empty `ids`, +inf otherwise."""
-    a, b = [int(v) for v in ids], [int(v) for v in ref]
-    if not b:
-        return 0.0 if not a else float("inf")
-    row = list(range(len(b) + 1))
-    for i, x in enumerate(a, 1):
-        prev, row[0] = row[0], i
-        for j, y in enumerate(b, 1):
-            prev, row[j] = row[j], min(row[j] + 1, row[j - 1] + 1, prev + (x != y))
-    return row[-1] / len(b)
-
-
-class Takes:
-    """Best-of-K sampling (immutable; DESIGN 8d, include/smalltts_hip.h smtts_take_scores / smtts_take_select): every row is sampled
-    `k` times (1..16) from seeds take_seed(seed, 0 .. k-1), each take's text alignment is scored on the device and only the take with
-    the lowest total is decoded.  total = w0 * path cost per cell + w1 * skipped tokens / tokens + w2 * longest span / frames + w3 *
-    idle frames / frames with `weights` = (w0, w1, w2, w3), all >= 0; a token is skipped when no frame of its span gives it
-    `tau_token` of its attention, a frame is idle when it gives no token of the row `tau_frame`.
-
-    The defaults are design choices, not measurements.  What the score is worth is UNVALIDATED on trained weights: every weight this
-    project has run is seeded noise, nobody has measured whether the lowest total is the take a listener would keep, and the score
-    rests on the tap's layer / head selection (Alignment), which is unvalidated in the same way.  The mechanism is verified: the
-    features and the total (bit for bit against a numpy restatement), the selection, and that the winner's latents, audio and words
-    are those of the same row sampled alone.
-
-    `ctc` (>= 0, default 0 = off: the launches and bits of the score above): a CTC term.  The latent phoneme recogniser
-    (engine part "asr", SmallTTS(recogniser=True)) reads every take's latents, nll = the CTC negative log-likelihood of the row's
-    spoken tokens (smtts_ctc_score), and total' = total + (ctc * nll) / tokens, three single fp32 operations in that order.  It asks
-    "were these phonemes spoken?" and is the quantity the 4-step student was distilled to make small; UNVALIDATED in the same way:
-    no recogniser checkpoint has ever been loaded, and its Conformer composition is restated from recollection.  Not with repair=.
-
-    `sv` (>= 0, default 0 = off: not one launch more, not one bit changed): a speaker term.  The latent speaker verifier
-    (engine part "sv", SmallTTS(verifier=True)) embeds every take's latents (smtts_sv_embed), cos = the cosine of that embedding with
-    the reference voice's (smtts_sv_cosine; the Voice's `speaker`, or the embedding of the row's ref_latents), and
-    total' = total + sv * (1 - cos), three single fp32 operations in that order, behind the CTC term where that is on.  It asks "does
-    this take sound like the reference voice?" and is the third quantity the 4-step student was distilled to make small; UNVALIDATED
-    in the same way: no verifier checkpoint has ever been loaded, its ECAPA composition is restated from recollection, and the weight
-    is a design choice.  Every row and every reference needs 6 to 225 frames.  Not with repair=."""
-    __slots__ = ("k", "weights", "tau_token", "tau_frame", "ctc", "sv")
-    MAX_K, MAX_ROWS = 16, 64   # smtts_take_select's K; the largest sampler batch the tap is tested at
-
-    def __init__(self, k: int, weights: Sequence[float] = (1.0, 2.0, 1.0, 1.0), tau_token: float = 0.1, tau_frame: float = 0.1,
-                 ctc: float = 0.0, sv: float = 0.0) -> None:
-        if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
-            raise TypeError(f"Takes: k must be an integer, got {type(k).__name__}")
-        if not 1 <= int(k) <= self.MAX_K:
-            raise ValueError(f"Takes: k must lie in [1, {self.MAX_K}], got {int(k)}")
-        w = tuple(float(v) for v in weights)
-        if len(w) != 4 or not all(v >= 0.0 and np.isfinite(v) for v in w):
-            raise ValueError(f"Takes: weights must be four finite numbers >= 0, got {w}")
-        if not (np.isfinite(float(tau_token)) and np.isfinite(float(tau_frame))):
-            raise ValueError("Takes: tau_token and tau_frame must be finite")
-        if isinstance(ctc, bool) or not (np.isfinite(float(ctc)) and float(ctc) >= 0.0):
-            raise ValueError(f"Takes: ctc must be a finite number >= 0, got {ctc!r}")
-        if isinstance(sv, bool) or not (np.isfinite(float(sv)) and float(sv) >= 0.0):
-            raise ValueError(f"Takes: sv must be a finite number >= 0, got {sv!r}")
-        set_ = object.__setattr__
-        set_(self, "ctc", float(ctc))
-        set_(self, "sv", float(sv))
-        set_(self, "k", int(k))
-        set_(self, "weights", w)
-        set_(self, "tau_token", float(tau_token))
-        set_(self, "tau_frame", float(tau_frame))
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Takes is immutable")
-
-    __delattr__ = __setattr__
-
-    def __repr__(self) -> str:
-        return "Takes(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
-
-    def __eq__(self, other) -> bool:
-        return isinstance(other, Takes) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self) -> int:
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
-
-
-def as_takes(takes) -> Optional["Takes"]:
-    """The `takes=` argument of the synthesis calls: None -> None (off), an int K -> Takes(K), a Takes -> itself."""
-    if takes is None:
-        return None
-    if isinstance(takes, Takes):
-        return takes
-    if isinstance(takes, (int, np.integer)) and not isinstance(takes, bool):
-        return Takes(int(takes))
-    raise TypeError(f"takes must be None, an int or a Takes, got {type(takes).__name__}")
-
-
-class Repair:
-    """Repair of a take (immutable; DESIGN 8e, include/smalltts_hip.h smtts_repair_plan / smtts_repair_keep): behind the sampler (and
-    the take selection) the tokens of every row whose alignment is bad are found on the device, only their frames are drawn again by
-    one pinned sampler pass with every other frame held to the row's latents, the row is scored again, and the repaired row is kept
-    only where its total is strictly lower; `rounds` (1..4) such passes.  A token is bad when its span on the monotone path is empty,
-    longer than `max_span` frames (1..225), or holds no frame that gives the token `tau_token` of its attention; a bad token frees its
-    span plus `margin` frames (0..32) on either side.  The total is the call's Takes' (the default weights without `takes`).
-
-    The defaults are design choices, not measurements.  Repair is UNVALIDATED on trained weights: every weight this project has run
-    is seeded noise, nobody has measured whether a 4-step student inpaints the freed frames audibly well, and nobody has measured
-    whether a lower total is the better take.  The mechanism is verified: the plan and the keep rule (bit for bit against a numpy
-    restatement), that a repaired row is the pinned call by hand, and that every frame the plan pinned keeps its bits."""
-    __slots__ = ("rounds", "tau_token", "max_span", "margin")
-    MAX_ROUNDS, MAX_MARGIN = 4, 32
-
-    def __init__(self, rounds: int = 1, tau_token: float = 0.1, max_span: int = 8, margin: int = 2) -> None:
-        for name, v in (("rounds", rounds), ("max_span", max_span), ("margin", margin)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
-                raise TypeError(f"Repair: {name} must be an integer, got {type(v).__name__}")
-        if not 1 <= int(rounds) <= self.MAX_ROUNDS:
-            raise ValueError(f"Repair: rounds must lie in [1, {self.MAX_ROUNDS}], got {int(rounds)}")
-        if not 1 <= int(max_span) <= ALIGN_MAX_FRAMES:
-            raise ValueError(f"Repair: max_span must lie in [1, {ALIGN_MAX_FRAMES}], got {int(max_span)}")
-        if not 0 <= int(margin) <= self.MAX_MARGIN:
-            raise ValueError(f"Repair: margin must lie in [0, {self.MAX_MARGIN}], got {int(margin)}")
-        if not np.isfinite(float(tau_token)):
-            raise ValueError("Repair: tau_token must be finite")
-        set_ = object.__setattr__
-        set_(self, "rounds", int(rounds))
-        set_(self, "tau_token", float(tau_token))
-        set_(self, "max_span", int(max_span))
-        set_(self, "margin", int(margin))
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Repair is immutable")
-
-    __delattr__ = __setattr__
-
-    def __repr__(self) -> str:
-        return "Repair(" + ", ".join(f"{k}={getattr(self, k)!r}" for k in self.__slots__) + ")"
-
-    def __eq__(self, other) -> bool:
-        return isinstance(other, Repair) and all(getattr(self, k) == getattr(other, k) for k in self.__slots__)
-
-    def __hash__(self) -> int:
-        return hash(tuple(getattr(self, k) for k in self.__slots__))
-
-
-def as_repair(repair) -> Optional["Repair"]:
-    """The `repair=` argument of the synthesis calls: None -> None (off), an int -> Repair(rounds), a Repair -> itself."""
-    if repair is None:
-        return None
-    if isinstance(repair, Repair):
-        return repair
-    if isinstance(repair, (int, np.integer)) and not isinstance(repair, bool):
-        return Repair(int(repair))
-    raise TypeError(f"repair must be None, an int or a Repair, got {type(repair).__name__}")
-
-
-class Delivery:
-    """The rate and encoding audio leaves the engine in (immutable; DESIGN 8g, include/smalltts_hip.h smtts_deliver): `rate` one of
-    8000, 11025, 16000, 22050, 24000, 32000, 44100, 48000 Hz, `encoding` "f32" | "pcm16" | "mulaw" | "alaw" (G.711, audioop's codes).
-    Resampled and encoded on the device behind the decode, whole or in chunks that continue each other bit for bit.  The banks are
-    the project's Kaiser-sinc restatement with audio.DELIVER_ZEROS zero crossings: unpinned against torchaudio, a design choice."""
-    __slots__ = ("rate", "encoding")
-
-    def __init__(self, rate: int = 24_000, encoding: str = "f32") -> None:
-        from .audio import DELIVER_ENCODINGS, DELIVER_RATES
-        if isinstance(rate, bool) or not isinstance(rate, (int, np.integer)):
-            raise TypeError(f"Delivery: rate must be an integer, got {type(rate).__name__}")
-        if int(rate) not in DELIVER_RATES:
-            raise ValueError(f"Delivery: rate must be one of {DELIVER_RATES}, got {int(rate)}")
-        if encoding not in DELIVER_ENCODINGS:
-            raise ValueError(f"Delivery: encoding must be one of {DELIVER_ENCODINGS}, got {encoding!r}")
-        object.__setattr__(self, "rate", int(rate))
-        object.__setattr__(self, "encoding", str(encoding))
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Delivery is immutable")
-
-    __delattr__ = __setattr__
-
-    def __repr__(self) -> str:
-        return f"Delivery(rate={self.rate!r}, encoding={self.encoding!r})"
-
-    def __eq__(self, other) -> bool:
-        return isinstance(other, Delivery) and (self.rate, self.encoding) == (other.rate, other.encoding)
-
-    def __hash__(self) -> int:
-        return hash((self.rate, self.encoding))
-
-    @property
-    def ratio(self) -> Tuple[int, int]:
-        """(up, down) of 24 kHz -> rate in lowest terms."""
-        from .audio import deliver_ratio
-        return deliver_ratio(self.rate)
-
-    @property
-    def dtype(self):
-        from .audio import DELIVER_DTYPES
-        return DELIVER_DTYPES[self.encoding]
-
-    def samples(self, s: int) -> int:
-        """A position or length of `s` samples at 24 kHz in output samples: ceil(up * s / down)."""
-        up, down = self.ratio
-        return -(-up * int(s) // down)
-
-
-def as_delivery(deliver) -> Optional["Delivery"]:
-    """The `deliver=` argument of the synthesis calls: None -> None (today's path: 24 kHz fp32, not one launch more), a Delivery ->
-    itself, an int -> Delivery(rate), a (rate, encoding) pair -> Delivery(rate, encoding)."""
-    if deliver is None:
-        return None
-    if isinstance(deliver, Delivery):
-        return deliver
-    if isinstance(deliver, (int, np.integer)) and not isinstance(deliver, bool):
-        return Delivery(int(deliver))
-    if isinstance(deliver, (tuple, list)) and len(deliver) == 2:
-        return Delivery(deliver[0], deliver[1])
-    raise TypeError(f"deliver must be None, a Delivery, a rate or a (rate, encoding) pair, got {type(deliver).__name__}")
-
-
-class Watermark:
-    """A keyed watermark on the audio the engine hands out (immutable; DESIGN 8k, include/smalltts_hip.h smtts_watermark): `key` an
-    integer in [0, 2^64), the shared secret the detector needs (whoever holds it can also strip the mark); `strength` in [0, 1], the
-    mark's amplitude relative to the RMS of the 64 samples in front (0.02: 34 dB below the signal; a design choice that has never
-    been listened to).  Embedded on the device at 24 kHz in front of the delivery, whole or in chunks that continue each other bit
-    for bit; SmallTTS.detect_watermark finds it again in f32 or PCM16 audio, also cropped from the front.  Detection is unvalidated
-    on real speech and on trained weights."""
-    __slots__ = ("key", "strength")
-
-    def __init__(self, key: int, strength: float = 0.02) -> None:
-        if isinstance(key, bool) or not isinstance(key, (int, np.integer)):
-            raise TypeError(f"Watermark: key must be an integer, got {type(key).__name__}")
-        if not 0 <= int(key) < 2 ** 64:
-            raise ValueError(f"Watermark: key must be in [0, 2^64), got {int(key)}")
-        if isinstance(strength, bool) or not isinstance(strength, (int, float, np.integer, np.floating)):
-            raise TypeError(f"Watermark: strength must be a number, got {type(strength).__name__}")
-        if not (0.0 <= float(strength) <= 1.0):                # (also refuses NaN)
-            raise ValueError(f"Watermark: strength must be in [0, 1], got {float(strength)}")
-        object.__setattr__(self, "key", int(key))
-        object.__setattr__(self, "strength", float(strength))
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Watermark is immutable")
-
-    __delattr__ = __setattr__
-
-    def __repr__(self) -> str:
-        return f"Watermark(key={self.key!r}, strength={self.strength!r})"
-
-    def __eq__(self, other) -> bool:
-        return isinstance(other, Watermark) and (self.key, self.strength) == (other.key, other.strength)
-
-    def __hash__(self) -> int:
-        return hash((self.key, self.strength))
-
-
-def as_watermark(watermark) -> Optional["Watermark"]:
-    """The `watermark=` argument of the synthesis calls: None -> None (no mark, not one launch more), a Watermark -> itself, an
-    int -> Watermark(key), a (key, strength) pair -> Watermark(key, strength)."""
-    if watermark is None:
-        return None
-    if isinstance(watermark, Watermark):
-        return watermark
-    if isinstance(watermark, (int, np.integer)) and not isinstance(watermark, bool):
-        return Watermark(int(watermark))
-    if isinstance(watermark, (tuple, list)) and len(watermark) == 2:
-        return Watermark(watermark[0], watermark[1])
-    raise TypeError(f"watermark must be None, a Watermark, a key or a (key, strength) pair, got {type(watermark).__name__}")
-
-
-def marked_delivery(what: str, watermark, dv: Optional["Delivery"]):
-    """watermark= next to deliver= -> (Watermark or None, Delivery or None).  A mark without deliver= leaves as Delivery(24000, "f32");
-    any other rate, and G.711, are refused: the mark lives mostly above 4 kHz and is about as large as G.711's own noise, it would
-    not survive, and a silent no-op is worse than a refusal."""
-    wm = as_watermark(watermark)
-    if wm is None:
-        return None, dv
-    if dv is None:
-        dv = Delivery(24_000, "f32")
-    if dv.rate != 24_000 or dv.encoding not in ("f32", "pcm16"):
-        raise ValueError(f"{what}: watermark= needs 24000 Hz and f32 or pcm16 (the mark would not survive resampling or G.711), "
-                         f"got {dv!r}")
-    return wm, dv
-
-
-def token_groups(ids: Sequence[int]) -> List[Tuple[str, str, int, int]]:
-    """The units word timings are reported for: runs of token ids between the space symbol.  -> [(kind, phonemes, t0, t1), ...] in
-    order, [t0, t1) the run's token indices, phonemes = decode_token_ids of them.  kind "word": a run of letter / IPA symbols;
-    "punct": ONE punctuation mark (a mark glued to a word is cut off it); "event": a run of up to NV_REPEAT copies of one [event]
-    id (get_token_ids writes exactly NV_REPEAT).  Spaces, padding (0) and unknown ids separate runs and belong to none."""
-    from .phonemes import EVENTS, NV_REPEAT, PUNCTUATION, decode_token_ids, idx2p, p2idx
-    punct = {p2idx[c] for c in PUNCTUATION if c != " "}
-    events = {p2idx[f"[{e}]"] for e in EVENTS}
-    ids = [int(t) for t in ids]
-    out: List[Tuple[str, str, int, int]] = []
-    i, n = 0, len(ids)
-    while i < n:
-        t = ids[i]
-        if t == p2idx[" "] or t not in idx2p:
-            i += 1
-        elif t in punct:
-            out.append(("punct", decode_token_ids(ids[i:i + 1]), i, i + 1))
-            i += 1
-        elif t in events:
-            j = i
-            while j < n and ids[j] == t and j - i < NV_REPEAT:
-                j += 1
-            out.append(("event", decode_token_ids(ids[i:i + 1]), i, j))
-            i = j
-        else:
-            j = i
-            while j < n and ids[j] in idx2p and ids[j] != p2idx[" "] and ids[j] not in punct and ids[j] not in events:
-                j += 1
-            out.append(("word", decode_token_ids(ids[i:j]), i, j))
-            i = j
-    return out
-
-
-def word_times(groups: Sequence[Tuple[str, str, int, int]], spans, n_frames: int, *, token0: int = 0,
-               window: Optional[Tuple[int, int]] = None, offset: int = 0, index0: int = 0, hop: int = HOP_SIZE) -> List[Tuple[int, str, int, int]]:
-    """Token spans of one row -> [(group index, kind, start sample, end sample), ...].  spans[t] = (first, last) frame of token t
-    (smtts_align_path); group g covers tokens [token0 + t0, token0 + t1): start = hop * first(t0), end = hop * (last(t1 - 1) + 1),
-    both clipped to the row's hop * n_frames samples.  window = (start, n), the row's speech window (trim): the span is intersected
-    with it and counted from its start.  offset: where the row (or its window) starts on the caller's timeline; index0: the first
-    group's index.  A group whose tokens are not on the path (an empty row) collapses to (offset, offset)."""
-    total = hop * max(0, int(n_frames))
-    out = []
-    for gi, (kind, _ph, t0, t1) in enumerate(groups):
-        first, last = int(spans[token0 + t0][0]), int(spans[token0 + t1 - 1][1])
-        if first < 0 or last < 0:
-            s = e = 0
-        else:
-            s, e = min(hop * first, total), min(hop * (last + 1), total)
-        if window is not None:
-            ws, wn = int(window[0]), int(window[1])
-            s, e = min(max(s - ws, 0), wn), min(max(e - ws, 0), wn)
-        out.append((index0 + gi, kind, int(offset) + s, int(offset) + e))
-    return out
-
-
-def _srt_time(samples: int) -> str:
-    ms = (int(samples) * 1000 + SAMPLE_RATE // 2) // SAMPLE_RATE
-    return f"{ms // 3600000:02d}:{ms // 60000 % 60:02d}:{ms // 1000 % 60:02d},{ms % 1000:03d}"
-
-
-def format_srt(cues: Sequence[Tuple[int, int, str]]) -> str:
-    """[(start sample, end sample, text), ...] at 24 kHz -> the text of a SubRip file: numbered cues, times rounded to the nearest
-    millisecond, an end never before its start; cues with empty text are dropped."""
-    out, k = [], 0
-    for s, e, text in cues:
-        text = str(text).strip()
-        if not text:
-            continue
-        k += 1
-        out.append(f"{k}\n{_srt_time(s)} --> {_srt_time(max(int(s), int(e)))}\n{text}\n")
-    return "\n".join(out)
-
-
-def frames_of_groups(groups: Sequence[Tuple[str, str, int, int]], spans, g0: int, g1: int, token0: int = 0) -> Tuple[int, int]:
-    """The frames token groups [g0, g1) of one row touch, by word_times' mapping: (first frame of the first token, last frame of the
-    last token + 1).  groups: token_groups of the row's own tokens; spans[t] = (first, last) frame of token t (smtts_align_path);
-    token0: the prepended tokens in front of them.  A group off the path (an empty row) raises ValueError."""
-    g0, g1 = int(g0), int(g1)
-    if not 0 <= g0 < g1 <= len(groups):
-        raise ValueError(f"frames_of_groups: groups [{g0}, {g1}) outside [0, {len(groups)}) or empty")
-    t0, t1 = int(groups[g0][2]), int(groups[g1 - 1][3])
-    if token0 + t0 < 0 or token0 + t1 > len(spans):
-        raise ValueError(f"frames_of_groups: tokens [{token0 + t0}, {token0 + t1}) outside the span table of {len(spans)} tokens")
-    first, last = int(spans[token0 + t0][0]), int(spans[token0 + t1 - 1][1])
-    if first < 0 or last < first:
-        raise ValueError(f"frames_of_groups: groups [{g0}, {g1}) are not on the alignment path")
-    return first, last + 1
-
-
-def splice_pins(latents, f0: int, f1: int, m: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
-    """The pins of a re-spoken row: frames [f0, f1) of `latents` (n, 64) are replaced by m free frames (default f1 - f0, at least
-    1).  -> (x_pin (n', 64) fp32, keep (n',) bool), n' = n - (f1 - f0) + m: the head [0, f0) and the tail [f1, n) are copied and
-    kept (the tail at its shifted place), the m rows between them are zeros and free."""
-    lat = np.asarray(latents, np.float32)
-    if lat.ndim != 2 or lat.shape[1] != 64:
-        raise ValueError(f"splice_pins: latents must be (n, 64), got {lat.shape}")
-    n, f0, f1 = int(lat.shape[0]), int(f0), int(f1)
-    if not 0 <= f0 < f1 <= n:
-        raise ValueError(f"splice_pins: frames [{f0}, {f1}) must be a non-empty range inside [0, {n})")
-    m = f1 - f0 if m is None else int(m)
-    if m < 1:
-        raise ValueError("splice_pins: at least one frame is regenerated (m >= 1)")
-    x_pin = np.zeros((n - (f1 - f0) + m, 64), np.float32)
-    keep = np.ones((x_pin.shape[0],), bool)
-    x_pin[:f0] = lat[:f0]
-    x_pin[f0 + m:] = lat[f1:]
-    keep[f0:f0 + m] = False
-    return x_pin, keep
-
-
-def _check_pins(pins, ns: Sequence[int], start_step: int, num_steps: int):
-    """synthesize_batch's pins= / start_step= -> [None | (latents (n_b, 64) fp32, keep (n_b,) bool)] per row, or None (off)."""
-    start_step = int(start_step)
-    if pins is None and start_step == 0:
-        return None
-    if not 0 <= start_step < int(num_steps):
-        raise ValueError(f"synthesize_batch: start_step must lie in [0, {int(num_steps)}), got {start_step}")
-    if pins is None or len(pins) != len(ns):
-        raise ValueError(f"synthesize_batch: pins needs one entry per row ({len(ns)}): None or (latents, keep)"
-                         + (" — start_step > 0 starts from them" if pins is None else ""))
-    out = []
-    for b, pe in enumerate(pins):
-        if pe is None:
-            if start_step > 0:
-                raise ValueError(f"synthesize_batch: start_step > 0 needs latents in every row (row {b} has none)")
-            out.append(None)
-            continue
-        if not isinstance(pe, (tuple, list)) or len(pe) != 2:
-            raise ValueError(f"synthesize_batch: pins[{b}] must be None or (latents, keep)")
-        lat, keep = np.asarray(pe[0]), np.asarray(pe[1])
-        if lat.shape != (ns[b], 64) or lat.dtype != np.float32:
-            raise ValueError(f"synthesize_batch: pins[{b}] latents must be fp32 ({ns[b]}, 64), got {lat.dtype} {lat.shape}")
-        if keep.shape != (ns[b],) or keep.dtype != np.bool_:
-            raise ValueError(f"synthesize_batch: pins[{b}] keep must be bool ({ns[b]},), got {keep.dtype} {keep.shape}")
-        out.append((lat, keep))
-    return out
-
-
-class Piece:
-    """One piece of a long take, as synthesize_long(return_pieces=True) spoke it: `tokens` (the prefix included), `prefix_len` (how
-    many of them are the prepended transcription), `latents` (n, 64) fp32 on the host, and the `seed` of its noise; `spans`
-    (len(tokens), 2) int32, the (first, last) frame of every token, when the take was aligned (return_words), else None.  Immutable;
-    render_long joins pieces again, respeak makes the latents of a replacement."""
-    __slots__ = ("tokens", "prefix_len", "latents", "seed", "spans")
-
-    def __init__(self, tokens: Sequence[int], prefix_len: int, latents, seed: int, spans=None) -> None:
-        lat = np.array(latents, np.float32)
-        if lat.ndim != 2 or lat.shape[1] != 64 or lat.shape[0] < 1:
-            raise ValueError(f"Piece: latents must be (n, 64) with n >= 1, got {lat.shape}")
-        if not 0 <= int(prefix_len) <= len(tokens):
-            raise ValueError("Piece: prefix_len must lie in [0, len(tokens)]")
-        lat.setflags(write=False)
-        set_ = object.__setattr__
-        set_(self, "tokens", tuple(int(t) for t in tokens))
-        set_(self, "prefix_len", int(prefix_len))
-        set_(self, "latents", lat)
-        set_(self, "seed", int(seed))
-        if spans is not None:
-            spans = np.array(spans, np.int32)
-            if spans.shape != (len(self.tokens), 2):
-                raise ValueError(f"Piece: spans must be ({len(self.tokens)}, 2), one (first, last) frame per token, got {spans.shape}")
-            spans.setflags(write=False)
-        set_(self, "spans", spans)
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Piece is immutable")
-
-    __delattr__ = __setattr__
-
-    def __repr__(self) -> str:
-        return f"Piece(tokens={len(self.tokens)}, prefix_len={self.prefix_len}, frames={self.latents.shape[0]}, seed={self.seed})"
-
-
-TAKE_JOIN_KEYS = ("gap_ms", "fade_ms", "max_batch", "in_flight", "trim", "level_dbfs")
-
-
-def save_take(path, pieces: Sequence["Piece"], **join) -> None:
-    """A long take -> one .npz: every Piece (tokens, prefix_len, latents, seed, spans when it has them) and the join parameters
-    (TAKE_JOIN_KEYS: gap_ms, fade_ms, max_batch, in_flight, trim as a bool, level_dbfs or None), enough for render_long to give the
-    waveform again.  Plain arrays only (no pickle)."""
-    unknown = sorted(set(join) - set(TAKE_JOIN_KEYS))
-    if unknown:
-        raise ValueError(f"save_take: unknown join parameters {unknown}")
-    level = join.get("level_dbfs")
-    arrs = {"n_pieces": np.int64(len(pieces)), "prefix_len": np.asarray([p.prefix_len for p in pieces], np.int64),
-            "seed": np.asarray([p.seed for p in pieces], np.uint64), "gap_ms": np.float64(join.get("gap_ms", 120.0)),
-            "fade_ms": np.float64(join.get("fade_ms", 5.0)), "max_batch": np.int64(join.get("max_batch", 8)),
-            "in_flight": np.int64(join.get("in_flight", 3)), "trim": np.bool_(join.get("trim", False)),
-            "level_dbfs": np.float64(np.nan if level is None else level)}
-    for i, p in enumerate(pieces):
-        arrs[f"tokens_{i}"] = np.asarray(p.tokens, np.int64)
-        arrs[f"latents_{i}"] = np.asarray(p.latents, np.float32)
-        if p.spans is not None:
-            arrs[f"spans_{i}"] = np.asarray(p.spans, np.int32)
-    with open(path, "wb") as f:
-        np.savez(f, **arrs)
-
-
-def load_take(path) -> Tuple[List["Piece"], Dict[str, object]]:
-    """save_take's file -> (pieces, join parameters as keyword arguments of save_take)."""
-    with np.load(path, allow_pickle=False) as z:
-        n = int(z["n_pieces"])
-        pieces = [Piece(z[f"tokens_{i}"].tolist(), int(z["prefix_len"][i]), z[f"latents_{i}"], int(z["seed"][i]),
-                        z[f"spans_{i}"] if f"spans_{i}" in z.files else None) for i in range(n)]
-        level = float(z["level_dbfs"])
-        join = {"gap_ms": float(z["gap_ms"]), "fade_ms": float(z["fade_ms"]), "max_batch": int(z["max_batch"]),
-                "in_flight": int(z["in_flight"]), "trim": bool(z["trim"]), "level_dbfs": None if np.isnan(level) else level}
-    return pieces, join
 
 
 def _piece_latents(pieces) -> List[np.ndarray]:
@@ -788,27 +46,6 @@ def _piece_latents(pieces) -> List[np.ndarray]:
             raise ValueError(f"render_long: piece {i} must hold (n, 64) latents with n >= 1, got {lat.shape}")
         out.append(lat)
     return out
-
-
-def piece_seed(seed: int, i: int) -> int:
-    """Seed of piece i of a long text: SeedSequence([seed, i]) reduced to 63 bits (like the replica seeds of SmallTTS)."""
-    return int(np.random.SeedSequence([int(seed), int(i)]).generate_state(1, np.uint64)[0] >> 1)
-
-
-def take_seed(seed: int, k: int) -> int:
-    """Seed of take k of a row spoken from `seed`: take 0 is the row itself (take_seed(s, 0) == s), take k >= 1 draws from
-    SeedSequence([seed, k, 0x54414B45]) reduced to 63 bits (three words: never a piece_seed)."""
-    if int(k) == 0:
-        return int(seed)
-    return int(np.random.SeedSequence([int(seed), int(k), 0x54414B45]).generate_state(1, np.uint64)[0] >> 1)
-
-
-def repair_seed(seed: int, r: int) -> int:
-    """Seed of repair round r >= 1 of a row spoken from `seed`: SeedSequence([seed, r, 0x52455052]) reduced to 63 bits (three words
-    with a tag of its own: never a piece_seed or a take_seed)."""
-    if int(r) < 1:
-        raise ValueError(f"repair_seed: rounds count from 1, got {int(r)}")
-    return int(np.random.SeedSequence([int(seed), int(r), 0x52455052]).generate_state(1, np.uint64)[0] >> 1)
 
 
 def _split_sources(weights) -> List[str]:
@@ -905,38 +142,6 @@ def get_engine(weights: Optional[str] = None, device: int = 0, precision: str = 
     return eng
 
 
-def stream_chunks(n: int, chunk_frames: Sequence[int] = (2, 4, 8, 16, 32)) -> List[int]:
-    """The chunk sizes synthesize_stream decodes n frames in: chunk_frames in order, the last size repeated, the final chunk whatever
-    is left (small chunks first: the first sample leaves early; larger ones later: fewer launches per second of audio)."""
-    sizes: List[int] = []
-    n, k = int(n), 0
-    while n > 0:
-        c = min(int(chunk_frames[min(k, len(chunk_frames) - 1)]), n)
-        sizes.append(c)
-        n -= c
-        k += 1
-    return sizes
-
-
-def stream_groups(n: int, batch_sizes: Optional[Sequence[int]] = (1, 2, 4, 8), max_batch: int = 8) -> List[List[int]]:
-    """The groups synthesize_long_stream speaks n pieces in: consecutive pieces, the first groups of `batch_sizes` pieces each (every
-    size capped by `max_batch`), the last size repeated, the final group whatever is left (a small batch first: the first chunk
-    leaves after one piece's work; full batches later: the throughput of synthesize_long).  batch_sizes=None: plan_long's groups,
-    `max_batch` pieces each."""
-    if max_batch < 1:
-        raise ValueError("max_batch must be at least 1")
-    sizes = [int(max_batch)] if batch_sizes is None else [int(s) for s in batch_sizes]
-    if not sizes or min(sizes) < 1:
-        raise ValueError("batch_sizes must be None or a non-empty sequence of positive sizes")
-    groups: List[List[int]] = []
-    i, n = 0, int(n)
-    while i < n:
-        c = min(sizes[min(len(groups), len(sizes) - 1)], int(max_batch), n - i)
-        groups.append(list(range(i, i + c)))
-        i += c
-    return groups
-
-
 _NP_OF = {torch.float32: np.float32, torch.int64: np.int64, torch.int32: np.int32, torch.int16: np.int16, torch.uint8: np.uint8}
 
 
@@ -950,11 +155,22 @@ class LongChunk(NamedTuple):
     pieces: Optional[List["Piece"]]      # return_pieces: this chunk's Pieces, else None
 
 
-def _frames(duration_sec: float) -> int:
-    return max(1, int(duration_sec * SAMPLE_RATE / HOP_SIZE))  # floor, infer/onnx.py:84
+class _LongRequest(NamedTuple):
+    """What SmallTTS._long_request makes of the arguments synthesize_long and synthesize_long_stream share."""
+    wm: Optional["Watermark"]
+    dv: Optional["Delivery"]
+    ep: Optional["Endpointing"]
+    al: Optional["Alignment"]
+    tk: Optional["Takes"]                # None also for one take with nothing to report
+    rp: Optional["Repair"]
+    K: int
+    prefix: List[int]                    # the prepended transcription's tokens
+    toks: List[List[int]]                # every piece's tokens, the prefix in front
+    ns: List[int]                        # frames per piece
+    max_batch: int                       # lowered to 64 // K where K * max_batch would pass the sampler's rows
 
 
-class Voice:
+class Voice(_Frozen):
     """A reference voice encoded once: the reference half of the cross-KV cache, `k_ref` / `v_ref` (12, 1, 8, R, 120) fp32 on the
     engine's device (what cond_encode returns for this reference at B = 1), its length `R` and the `engine` it belongs to.
     `speaker`: the reference's speaker embedding, a (192,) fp32 tensor on the device (engine.sv_embed of the reference latents;
@@ -963,17 +179,7 @@ class Voice:
     __slots__ = ("engine", "k_ref", "v_ref", "R", "speaker")
 
     def __init__(self, engine: HipEngine, k_ref: torch.Tensor, v_ref: torch.Tensor, speaker: Optional[torch.Tensor] = None) -> None:
-        set_ = object.__setattr__
-        set_(self, "speaker", speaker)
-        set_(self, "engine", engine)
-        set_(self, "k_ref", k_ref)
-        set_(self, "v_ref", v_ref)
-        set_(self, "R", int(k_ref.shape[3]))
-
-    def __setattr__(self, name, value):
-        raise AttributeError("Voice is immutable")
-
-    __delattr__ = __setattr__
+        self._set(engine=engine, k_ref=k_ref, v_ref=v_ref, R=int(k_ref.shape[3]), speaker=speaker)
 
 
 class _Batch(NamedTuple):
@@ -1098,6 +304,114 @@ def _read_repair(recs: Sequence[_Batch]) -> List[tuple]:
 def _rows(audio: np.ndarray, ns: Sequence[int]) -> List[np.ndarray]:
     """A decoded batch on the host -> its rows (1, HOP_SIZE * n_b): the decoder is causal, so the prefixes are exact."""
     return [audio[b, :, : HOP_SIZE * n] for b, n in enumerate(ns)]
+
+
+def _to_output_samples(dv: Optional["Delivery"], segs: List[tuple], words: Optional[List[tuple]]):
+    """Segments (offset, n, start, gain) and words (index, kind, start, end) in 24 kHz samples -> the same in the Delivery's output
+    samples, ceil(up * s / down) of every position, a length as the difference of its two ends.  dv None: as they are."""
+    if dv is None:
+        return segs, words
+    segs = [(dv.samples(o), dv.samples(o + n) - dv.samples(o), dv.samples(st), g) for o, n, st, g in segs]
+    words = None if words is None else [(i, kind, dv.samples(a), dv.samples(b)) for i, kind, a, b in words]
+    return segs, words
+
+
+def _piece_rows(off, seg, gain, spans, latents, winner, toks, ns, seeds, n_prefix: int, ep: Optional["Endpointing"],
+                return_words: bool, return_pieces: bool, index0: int):
+    """The pieces of one group of a long text from what was read back for its rows, host arrays only; row r speaks the piece of
+    tokens toks[r] (the n_prefix prepended ones included), ns[r] frames and seed seeds[r].  off[r]: the row's offset in the joined
+    waveform; with `ep` seg[r] = (start, n), its speech window, and gain[r]; with return_words (and for the Pieces' spans) spans[r]
+    (P, 2); with return_pieces latents[r] (N, 64) and winner[r], the take that was kept (None: the piece's own seed).  index0: the
+    words counted in front of this group.  -> (segments, words or None, Pieces or None), positions in 24 kHz samples."""
+    segs, words, made = [], ([] if return_words else None), ([] if return_pieces else None)
+    for r, (tok, n) in enumerate(zip(toks, ns)):
+        segs.append((int(off[r]), HOP_SIZE * n, 0, 1.0) if ep is None else (int(off[r]), int(seg[r][1]), int(seg[r][0]), float(gain[r])))
+        if return_words:
+            words += word_times(token_groups(tok[n_prefix:]), spans[r], n, token0=n_prefix,
+                                window=(segs[-1][2], segs[-1][1]) if ep is not None else None, offset=segs[-1][0],
+                                index0=index0 + len(words))
+        if return_pieces:
+            made.append(Piece(tok, n_prefix, latents[r][:n], seeds[r] if winner is None else take_seed(seeds[r], int(winner[r])),
+                              spans[r][: len(tok)] if return_words else None))
+    return segs, words, made
+
+
+class _Scoring(NamedTuple):
+    """What the take scoring and the repair rounds of one synthesize_batch call read besides the device tensors: host values that
+    no pass of the call changes, so that the first pass and the guard's rerun() enqueue the same work.  G caller rows, each spoken by
+    the K sampler rows g * K .. g * K + K - 1."""
+    K: int
+    tk_run: "Takes"                      # the weights and thresholds of the total
+    ctc_w: float                         # Takes.ctc where the CTC term is on, else 0
+    sv_w: float                          # Takes.sv where the speaker term is on, else 0
+    s_ns: List[int]                      # per sampler row: frames, prefix lengths, token counts
+    s_p0s: List[int]
+    s_ps: List[int]
+    ns: List[int]                        # per caller row: frames, prefix lengths, token counts, reference frames
+    p0s: List[int]
+    ps: List[int]
+    rs: List[int]
+    ref: np.ndarray                      # (G * K, Rm, 64), (G * K, Pm): the sampler rows' references and tokens
+    ids: np.ndarray
+    voices: Optional[List["Voice"]]      # per caller row, or None (ref_latents)
+    al_run: Optional["Alignment"]
+    num_steps: int
+    Nm: int
+    rp: Optional["Repair"] = None
+    rp_seeds: Optional[List[List[int]]] = None   # repair: per round, per caller row
+    g_ref: Optional[np.ndarray] = None   # repair: the conditions' inputs, the frame mask and the caller's pins at G rows
+    g_ids: Optional[np.ndarray] = None
+    g_pm: Optional[np.ndarray] = None
+    g_mask: Optional[np.ndarray] = None
+    g_keep: Optional[np.ndarray] = None
+
+
+def _score_takes(eng: HipEngine, c: _Scoring, x, mass, spans, score):
+    """Scores every sampler row and keeps one per caller row, on the current stream: engine.take_scores, the CTC and speaker terms
+    where they are on, engine.take_select with K > 1.  -> (x, mass, spans, winner, total, feat, nll, cos); x, mass and spans are the
+    winners' with K > 1."""
+    winner = nll = cos = None
+    feat, total = eng.take_scores(mass, spans, score, c.s_ns, c.s_p0s, c.s_ps, c.tk_run)
+    if c.ctc_w > 0.0:                                          # the CTC term: total' = total + (ctc * nll) / tokens, single fp32 operations
+        tok = torch.from_numpy(c.ids.astype(np.int32)).pin_memory().to(eng.device, non_blocking=True)
+        pw = torch.tensor([float(max(0, p1 - p0)) for p0, p1 in zip(c.s_p0s, c.s_ps)], dtype=torch.float32).pin_memory()
+        nll = eng.ctc_score(eng.asr_logprobs(x, c.s_ns), [ASR_UPSAMPLE * n for n in c.s_ns], tok, c.s_p0s, c.s_ps)
+        total = total + (nll * c.ctc_w) / pw.to(eng.device, non_blocking=True)
+    if c.sv_w > 0.0:                                           # the speaker term: total' = total + sv * (1 - cos), single fp32 operations
+        spk = (torch.stack([v.speaker for v in c.voices]) if c.voices is not None
+               else eng.sv_embed(eng._dev(np.ascontiguousarray(c.ref[::c.K]), torch.float32), c.rs))
+        cos = eng.sv_cosine(eng.sv_embed(x, c.s_ns), spk, c.K)
+        total = total + (1.0 - cos) * c.sv_w
+    if c.K > 1:
+        x, _n, spans, mass, winner = eng.take_select(total, c.K, x, c.s_ns, spans, mass)
+    return x, mass, spans, winner, total, feat, nll, cos
+
+
+def _repair_rounds(eng: HipEngine, c: _Scoring, cache, x, mass, spans, winner, total, feat):
+    """The repair rounds of the G caller rows, on the current stream: the winners' latents are the pins, x, spans and mass are merged
+    in place.  -> (kept, counts per round, the rows' totals before round 1 and after every round)."""
+    G = len(c.ns)
+    if c.K > 1:                                                # the cache has G * K rows: the conditions again at G rows
+        cache = eng.cond_encode(c.g_ref, np.asarray(c.rs, np.int64), c.g_ids, c.g_pm)
+        if c.voices is not None:
+            cache.update(eng.voice_expand(c.voices))
+        sel = winner.long() + torch.arange(0, G * c.K, c.K, device=eng.device)
+        t_cur, f_cur = total[sel], feat[sel]                   # the winners' totals and features
+    else:
+        t_cur, f_cur = total, feat
+    keep_d = None if c.g_keep is None else torch.from_numpy(c.g_keep).pin_memory().to(eng.device, non_blocking=True)
+    rp_kept, rp_counts, rp_totals = [], [], [t_cur]
+    for r in range(c.rp.rounds):
+        plan, counts = eng.repair_plan(mass, spans, c.ns, c.p0s, c.ps, c.rp, keep_d)
+        nz_r = eng.randn_rows(c.rp_seeds[r], c.ns, c.num_steps, n_max=c.Nm)
+        x_new, mass_new = eng.sample(cache, c.g_mask, num_steps=c.num_steps, noise=nz_r, seed=0, align=c.al_run, x_pin=x,
+                                     pin=plan, start_step=0)
+        spans_new, score_new = eng.align_path(mass_new, c.ns, c.p0s, c.ps)[:2]
+        f_new, t_new = eng.take_scores(mass_new, spans_new, score_new, c.ns, c.p0s, c.ps, c.tk_run)
+        # x, spans and mass are merged in place; every round's small outputs are tensors of their own (the report reads them)
+        t_cur, f_cur, kept = eng.repair_keep(t_cur, t_new, counts, f_cur, f_new, x, x_new, spans, spans_new, mass, mass_new)
+        rp_kept.append(kept); rp_counts.append(counts); rp_totals.append(t_cur)
+    return rp_kept, rp_counts, rp_totals
 
 
 def detect_watermark(engine: HipEngine, audio, key: int, *, max_offset: int = 0, threshold: float = 6.0) -> List[Tuple[float, int, bool]]:
@@ -1483,12 +797,14 @@ class SmallTTS:
         else:
             seed = self._next_seed() if seeds is None else 0
             s_seeds, row_seeds = seeds, ([seed] * B if seeds is None else [int(v) for v in seeds])
+        rp_kw = {}
         if rp is not None:                                     # every round draws its own rows of noise for the G rows
             base = row_seeds if (seeds is not None or K > 1) else [piece_seed(seed, g) for g in range(B)]
-            rp_seeds = [[repair_seed(base[g], r) for g in range(B)] for r in range(1, rp.rounds + 1)]
             g_sel = slice(None, None, K)                       # sampler row g * K speaks caller row g
             g_ref, g_ids, g_pm, g_mask = (np.ascontiguousarray(a[g_sel]) for a in (ref, ids, pm, mask))
-            g_keep = None if pinned is None else np.ascontiguousarray(pin_kw["pin"][g_sel])
+            rp_kw = {"rp": rp, "rp_seeds": [[repair_seed(base[g], r) for g in range(B)] for r in range(1, rp.rounds + 1)],
+                     "g_ref": g_ref, "g_ids": g_ids, "g_pm": g_pm, "g_mask": g_mask,
+                     "g_keep": None if pinned is None else np.ascontiguousarray(pin_kw["pin"][g_sel])}
         voices = None if voices is None else list(voices)      # run() keeps them alive while the batch is in flight
         s_voices = None if voices is None else [voices[g] for g in rows]
         p0s = [0] * B if prefix_lens is None else [int(v) for v in prefix_lens]
@@ -1500,6 +816,7 @@ class SmallTTS:
                 raise ValueError("synthesize_batch: prefix_lens needs one length in [0, tokens of the row] per row")
 
         s_p0s = [p0s[g] for g in rows]
+        c = _Scoring(K, tk_run, ctc_w, sv_w, s_ns, s_p0s, s_ps, ns, p0s, ps, rs, ref, ids, voices, al_run, self.num_steps, Nm, **rp_kw)
 
         def run() -> _Batch:
             cache = eng.cond_encode(ref, np.asarray(s_rs, np.int64), ids, pm)
@@ -1507,48 +824,17 @@ class SmallTTS:
                 cache.update(eng.voice_expand(s_voices))
             nz = noise if s_seeds is None else eng.randn_rows(s_seeds, s_ns, self.num_steps, n_max=Nm)
             mass = spans = seg = gain = winner = total = feat = nll = cos = None
+            rp_kept = rp_counts = rp_totals = None
             if al_run is None:
                 x = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, **pin_kw)
             else:
                 # the tap and the path ride on this batch's stream behind its sampler; a re-run (fp16 range guard) recomputes them
                 x, mass = eng.sample(cache, mask, num_steps=self.num_steps, noise=nz, seed=seed, align=al_run, **pin_kw)
                 spans, score = eng.align_path(mass, s_ns, s_p0s, s_ps)[:2]
-                if scored:                                     # takes: score every sampler row, keep one per caller row
-                    feat, total = eng.take_scores(mass, spans, score, s_ns, s_p0s, s_ps, tk_run)
-                if ctc_w > 0.0:                                # the CTC term: total' = total + (ctc * nll) / tokens, single fp32 operations
-                    tok = torch.from_numpy(ids.astype(np.int32)).pin_memory().to(eng.device, non_blocking=True)
-                    pw = torch.tensor([float(max(0, p1 - p0)) for p0, p1 in zip(s_p0s, s_ps)], dtype=torch.float32).pin_memory()
-                    nll = eng.ctc_score(eng.asr_logprobs(x, s_ns), [ASR_UPSAMPLE * n for n in s_ns], tok, s_p0s, s_ps)
-                    total = total + (nll * ctc_w) / pw.to(eng.device, non_blocking=True)
-                if sv_w > 0.0:                                 # the speaker term: total' = total + sv * (1 - cos), single fp32 operations
-                    spk = (torch.stack([v.speaker for v in voices]) if voices is not None
-                           else eng.sv_embed(eng._dev(np.ascontiguousarray(ref[::K]), torch.float32), rs))
-                    cos = eng.sv_cosine(eng.sv_embed(x, s_ns), spk, K)
-                    total = total + (1.0 - cos) * sv_w
-                if K > 1:
-                    x, _n, spans, mass, winner = eng.take_select(total, K, x, s_ns, spans, mass)
-            rp_kept = rp_counts = rp_totals = None
+            if scored:                                         # takes: score every sampler row, keep one per caller row
+                x, mass, spans, winner, total, feat, nll, cos = _score_takes(eng, c, x, mass, spans, score)
             if rp is not None:                                 # repair: G rows from here on, the winners' latents are the pins
-                if K > 1:                                      # the cache has G * K rows: the conditions again at G rows
-                    cache = eng.cond_encode(g_ref, np.asarray(rs, np.int64), g_ids, g_pm)
-                    if voices is not None:
-                        cache.update(eng.voice_expand(voices))
-                    sel = winner.long() + torch.arange(0, B * K, K, device=eng.device)
-                    t_cur, f_cur = total[sel], feat[sel]       # the winners' totals and features
-                else:
-                    t_cur, f_cur = total, feat
-                keep_d = None if g_keep is None else torch.from_numpy(g_keep).pin_memory().to(eng.device, non_blocking=True)
-                rp_kept, rp_counts, rp_totals = [], [], [t_cur]
-                for r in range(rp.rounds):
-                    plan, counts = eng.repair_plan(mass, spans, ns, p0s, ps, rp, keep_d)
-                    nz_r = eng.randn_rows(rp_seeds[r], ns, self.num_steps, n_max=Nm)
-                    x_new, mass_new = eng.sample(cache, g_mask, num_steps=self.num_steps, noise=nz_r, seed=0, align=al_run, x_pin=x,
-                                                 pin=plan, start_step=0)
-                    spans_new, score_new = eng.align_path(mass_new, ns, p0s, ps)[:2]
-                    f_new, t_new = eng.take_scores(mass_new, spans_new, score_new, ns, p0s, ps, tk_run)
-                    # x, spans and mass are merged in place; every round's small outputs are tensors of their own (the report reads them)
-                    t_cur, f_cur, kept = eng.repair_keep(t_cur, t_new, counts, f_cur, f_new, x, x_new, spans, spans_new, mass, mass_new)
-                    rp_kept.append(kept); rp_counts.append(counts); rp_totals.append(t_cur)
+                rp_kept, rp_counts, rp_totals = _repair_rounds(eng, c, cache, x, mass, spans, winner, total, feat)
             audio = eng.codec_decode(x) if _decode else None   # (B, 1, HOP * Nm); causal => prefixes are exact (None: synthesize_stream decodes)
             if ep is not None:                                 # behind the decode, on the same stream
                 seg, gain, _e = eng.endpoints(audio, ns, ep)
@@ -1600,9 +886,7 @@ class SmallTTS:
                 groups = token_groups(list(phoneme_ids[b])[p0s[b]:ps[b]])
                 win = None if ep is None else (int(head[b, 0]), int(head[b, 1]))
                 words.append(word_times(groups, spans_h[b], rec.ns[b], token0=p0s[b], window=win))
-            if dv is not None:                                 # positions in output samples
-                words = [[(i, kind, dv.samples(s), dv.samples(e)) for i, kind, s, e in row] for row in words]
-            res.append(words)
+            res.append([_to_output_samples(dv, [], row)[1] for row in words])
             if return_alignment:
                 mh = rec.mass.cpu().numpy()
                 res.append([(mh[b, : rec.ns[b], : ps[b]], spans_h[b, : ps[b]]) for b in range(B)])
@@ -1633,6 +917,27 @@ class SmallTTS:
             eng.release_workspaces()
         return outs
 
+    @contextlib.contextmanager
+    def _throughput(self):
+        """Throughput tuning around what is enqueued inside: unsplit GEMMs, capped persistent codec grids, no engine side stream (it
+        would serialise the text encoders of all batches in flight); the caller's mode is restored afterwards."""
+        prev_tuning = self.engine.set_tuning("throughput")
+        try:
+            yield
+        finally:
+            self.engine.set_tuning(prev_tuning)
+
+    @contextlib.contextmanager
+    def _in_flight_slot(self, stream, i: int):
+        """One batch in flight: what is enqueued inside goes onto `stream` with the workspace `batch{i}`; the default workspace is
+        selected again afterwards."""
+        try:
+            with torch.cuda.stream(stream):
+                self.engine.use_workspace(f"batch{i}")
+                yield
+        finally:
+            self.engine.use_workspace(None)
+
     def _run_in_flight(self, calls: Sequence[Callable[[], _Batch]], in_flight: int) -> List[_Batch]:
         """The machinery of synthesize_batches: calls[i]() enqueues one deferred batch and returns its record; call i runs whole on
         HIP stream i % in_flight with its own workspace under throughput tuning.  Returns the finished records, on the device, after
@@ -1645,17 +950,10 @@ class SmallTTS:
         for st in streams:
             st.wait_stream(cur)
         pending = []
-        # throughput tuning: unsplit GEMMs, capped persistent codec grids, no engine side stream (it would serialise the text encoders of all
-        # batches in flight); the caller's mode is restored afterwards
-        prev_tuning = eng.set_tuning("throughput")
-        try:
+        with self._throughput():                               # held across the whole loop: the engine sees one change and one restore
             for i, call in enumerate(calls):
-                with torch.cuda.stream(streams[i % len(streams)]):
-                    eng.use_workspace(f"batch{i % len(streams)}")
+                with self._in_flight_slot(streams[i % len(streams)], i % len(streams)):
                     pending.append(call())
-        finally:
-            eng.use_workspace(None)
-            eng.set_tuning(prev_tuning)
         for st in streams:
             cur.wait_stream(st)
         torch.cuda.synchronize(dev)
@@ -1683,6 +981,39 @@ class SmallTTS:
                 durations = [float(durations)] * len(token_lists)
         toks = [prefix + [int(t) for t in p] for p in token_lists]
         return prefix, toks, [_frames(d) for d in durations]
+
+    def _long_request(self, what: str, voice: Voice, text, token_lists, durations, prefix_tokens, max_batch: int, pcm16: bool, trim,
+                      align, return_words: bool, takes, repair, deliver, watermark,
+                      reports: Optional[Tuple[bool, bool]] = None) -> "_LongRequest":
+        """The argument front synthesize_long and synthesize_long_stream share, errors in one order for both: the options as their
+        records, one take dropped, the align= rule, the pieces (_long_inputs), the speaker term's limits and the group size takes=
+        allow.  `reports` = synthesize_long's (return_takes, return_repair), which also checks the CTC term here; None: the stream,
+        which has no reports and whose batches check that term."""
+        return_takes, return_repair = reports or (False, False)
+        wm, dv = marked_delivery(what, watermark, as_delivery(deliver))   # (DESIGN 8k: one mark stream for the text)
+        if dv is not None and pcm16:
+            raise ValueError(f"{what}: deliver= (and with it watermark=) and pcm16=True exclude each other: ask for "
+                             "Delivery(rate, 'pcm16')")
+        ep = as_endpointing(trim)
+        tk = as_takes(takes)
+        rp = as_repair(repair)
+        if tk is None and return_takes:
+            raise ValueError(f"{what}: return_takes= belongs to takes=")
+        if rp is None and return_repair:
+            raise ValueError(f"{what}: return_repair= belongs to repair=")
+        if tk is not None and tk.k == 1 and not return_takes:
+            tk = None                                          # one take and nothing to report: the call without takes
+        if reports is not None:
+            check_takes_ctc(what, tk, rp, self.engine)
+        al = as_alignment(align if align is not None else (True if return_words else None))
+        if al is not None and not return_words and tk is None and rp is None:
+            raise ValueError(f"{what}: align= belongs to return_words=True")
+        prefix, toks, ns = self._long_inputs(what, voice, text, token_lists, durations, prefix_tokens)
+        check_takes_sv(what, tk, rp, self.engine, ns or None, [voice])   # every piece, in front of the first batch
+        K = 1 if tk is None else tk.k
+        if tk is not None and K * max_batch > Takes.MAX_ROWS:
+            max_batch = Takes.MAX_ROWS // K                    # the sampler batch is K times the group
+        return _LongRequest(wm, dv, ep, al, tk, rp, K, prefix, toks, ns, max_batch)
 
     def _long_calls(self, voice: Voice, toks, ns, seeds, groups, n_prefix: int, ep, al, tk, rp, return_takes: bool):
         """One deferred synthesize_batch per group of a long text, as synthesize_long and synthesize_long_stream enqueue them:
@@ -1761,35 +1092,13 @@ class SmallTTS:
         `watermark` (a Watermark, a key or a (key, strength) pair): the JOINED waveform is marked on the device in front of
         the delivery, as one stream from sample 0; without `deliver` it means Delivery(24000, "f32").  24 kHz, f32 or pcm16 only.
         Returns (waveform[, segments][, words][, pieces][, takes][, repair])."""
-        wm, dv = marked_delivery("synthesize_long", watermark, as_delivery(deliver))
-        if dv is not None and pcm16:
-            raise ValueError("synthesize_long: deliver= (and with it watermark=) and pcm16=True exclude each other: ask for "
-                             "Delivery(rate, 'pcm16')")
-        ep = as_endpointing(trim)
-        tk = as_takes(takes)
-        rp = as_repair(repair)
-        if tk is None and return_takes:
-            raise ValueError("synthesize_long: return_takes= belongs to takes=")
-        if rp is None and return_repair:
-            raise ValueError("synthesize_long: return_repair= belongs to repair=")
-        if tk is not None and tk.k == 1 and not return_takes:
-            tk = None                                          # one take and nothing to report: the call without takes
-        check_takes_ctc("synthesize_long", tk, rp, self.engine)
-        al = as_alignment(align if align is not None else (True if return_words else None))
-        if al is not None and not return_words and tk is None and rp is None:
-            raise ValueError("synthesize_long: align= belongs to return_words=True")
-        prefix, toks, ns = self._long_inputs("synthesize_long", voice, text, token_lists, durations, prefix_tokens)
-        check_takes_sv("synthesize_long", tk, rp, self.engine, ns or None, [voice])   # every piece, in front of the first batch
-        eng = self.engine
-        K = 1 if tk is None else tk.k
-        if tk is not None and K * max_batch > Takes.MAX_ROWS:
-            max_batch = Takes.MAX_ROWS // K                    # the sampler batch is K times the group
-        groups, offsets, S = plan_long(ns, max_batch, gap_ms)
+        q = self._long_request("synthesize_long", voice, text, token_lists, durations, prefix_tokens, max_batch, pcm16, trim, align,
+                               return_words, takes, repair, deliver, watermark, reports=(return_takes, return_repair))
+        dv, ep, tk, K, toks, ns = q.dv, q.ep, q.tk, q.K, q.toks, q.ns
+        groups, offsets, S = plan_long(ns, q.max_batch, gap_ms)
 
         def result(out, segs, words, made, taken=None, mended=None):   # words None: not aligned
-            if dv is not None:                                 # positions in output samples
-                segs = [(dv.samples(o), dv.samples(o + n) - dv.samples(o), dv.samples(st), g) for o, n, st, g in segs]
-                words = None if words is None else [(i, kind, dv.samples(a), dv.samples(b)) for i, kind, a, b in words]
+            segs, words = _to_output_samples(dv, segs, words)
             res = ((out,) + ((segs,) if return_segments else ()) + ((words,) if words is not None else ())
                    + ((made,) if return_pieces else ()) + ((taken,) if return_takes else ()) + ((mended,) if return_repair else ()))
             return res if len(res) > 1 else out
@@ -1799,39 +1108,30 @@ class SmallTTS:
                           [] if return_words else None, [], [], [])
         base = self._next_seed() if seed is None else int(seed)
         seeds = [piece_seed(base, i) for i in range(len(toks))]
-        calls, al_b = self._long_calls(voice, toks, ns, seeds, groups, len(prefix), ep, al, tk, rp, return_takes)
-        out, segs, pending = self._join_long(calls, groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16, dv, wm)
-        words = made = taken = None
+        calls, _al_b = self._long_calls(voice, toks, ns, seeds, groups, len(q.prefix), ep, q.al, tk, q.rp, return_takes)
+        out, segs, pending = self._join_long(calls, groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16, dv, q.wm)
+        win = taken = None
         mended = _read_repair(pending) if return_repair else None   # one small read-back for the whole text
-        spoken = seeds
         if tk is not None and (return_takes or return_pieces):
             win, tot, ft = _read_takes(pending, K)             # one small read-back for the whole text
-            spoken = [take_seed(seeds[i], int(win[i])) for i in range(len(toks))]  # what each piece was spoken from: the winner's seed
             extra = _takes_extra(pending, K, len(toks))        # Takes(ctc > 0): nll (K,) too; Takes(sv > 0): then cos (K,)
-            taken = [(int(win[i]), spoken[i], tot[i], ft[i]) + extra[i] for i in range(len(toks))]
-        piece_spans: List[Optional[np.ndarray]] = [None] * len(toks)
-        if return_words:
-            # one small read-back for the whole text: every batch's (B, P, 2) span table, flattened
-            flat = torch.cat([rec.spans.reshape(-1) for rec in pending]).cpu().numpy()
-            words, pos = [], 0
-            for g, rec in zip(groups, pending):
-                Pg = int(rec.spans.shape[1])
-                sp = flat[pos: pos + len(g) * Pg * 2].reshape(len(g), Pg, 2)
-                pos += len(g) * Pg * 2
-                for r, i in enumerate(g):
-                    off, n_i, start_i, _gain = segs[i]
-                    piece_spans[i] = sp[r, : len(toks[i])]
-                    words += word_times(token_groups(toks[i][len(prefix):]), sp[r], ns[i], token0=len(prefix),
-                                        window=(start_i, n_i) if ep is not None else None, offset=off, index0=len(words))
-        if return_pieces:
-            # one read-back for the whole text: every batch's latents, flattened
-            flat = torch.cat([rec.latents.reshape(-1) for rec in pending]).cpu().numpy()
-            made, pos = [], 0
-            for g, rec in zip(groups, pending):
-                Ng = int(rec.latents.shape[1])
-                xg = flat[pos: pos + len(g) * Ng * 64].reshape(len(g), Ng, 64)
-                pos += len(g) * Ng * 64
-                made += [Piece(toks[i], len(prefix), xg[r, : ns[i]], spoken[i], piece_spans[i]) for r, i in enumerate(g)]
+            # (what each piece was spoken from: the winner's seed)
+            taken = [(int(win[i]), take_seed(seeds[i], int(win[i])), tot[i], ft[i]) + extra[i] for i in range(len(toks))]
+
+        def read_rows(tensors, width):                         # one read-back for the whole text: every batch's table, flattened
+            flat, pos, out = torch.cat([t.reshape(-1) for t in tensors]).cpu().numpy(), 0, []
+            for g, t in zip(groups, tensors):
+                out.append(flat[pos: pos + len(g) * int(t.shape[1]) * width].reshape(len(g), int(t.shape[1]), width))
+                pos += out[-1].size
+            return out
+        spans = read_rows([rec.spans for rec in pending], 2) if return_words else [None] * len(groups)
+        lats = read_rows([rec.latents for rec in pending], 64) if return_pieces else [None] * len(groups)
+        words, made = ([] if return_words else None), ([] if return_pieces else None)
+        for g, sp, xg in zip(groups, spans, lats):
+            _segs, w, m = _piece_rows([segs[i][0] for i in g], [(segs[i][2], segs[i][1]) for i in g], [segs[i][3] for i in g], sp, xg,
+                                      None if win is None else [win[i] for i in g], [toks[i] for i in g], [ns[i] for i in g],
+                                      [seeds[i] for i in g], len(q.prefix), ep, return_words, return_pieces, len(words or ()))
+            words, made = (words + w if return_words else None), (made + m if return_pieces else None)
         return result(out, segs, words, made, taken, mended)
 
     def _join_long(self, calls, groups, ns, offsets, S, ep: Optional["Endpointing"], in_flight: int, gap_ms: float, fade_ms: float,
@@ -1894,33 +1194,19 @@ class SmallTTS:
 
         Closing the generator early waits for what is in flight and leaves the engine as a finished call does.  Empty text yields
         nothing.  Arguments are checked here, before the first next()."""
-        wm, dv = marked_delivery("synthesize_long_stream", watermark, as_delivery(deliver))   # (DESIGN 8k: one mark stream for the text)
-        if dv is not None and pcm16:
-            raise ValueError("synthesize_long_stream: deliver= (and with it watermark=) and pcm16=True exclude each other: ask for "
-                             "Delivery(rate, 'pcm16')")
-        ep = as_endpointing(trim)
-        tk = as_takes(takes)
-        rp = as_repair(repair)
-        if tk is not None and tk.k == 1:
-            tk = None                                          # one take and nothing to report: the call without takes
-        al = as_alignment(align if align is not None else (True if return_words else None))
-        if al is not None and not return_words and tk is None and rp is None:
-            raise ValueError("synthesize_long_stream: align= belongs to return_words=True")
-        prefix, toks, ns = self._long_inputs("synthesize_long_stream", voice, text, token_lists, durations, prefix_tokens)
-        check_takes_sv("synthesize_long_stream", tk, rp, self.engine, ns or None, [voice])   # every piece, in front of the first batch
-        K = 1 if tk is None else tk.k
-        if tk is not None and K * max_batch > Takes.MAX_ROWS:
-            max_batch = Takes.MAX_ROWS // K                    # the sampler batch is K times the group
-        groups = stream_groups(len(toks), batch_sizes, max_batch)
+        q = self._long_request("synthesize_long_stream", voice, text, token_lists, durations, prefix_tokens, max_batch, pcm16, trim,
+                               align, return_words, takes, repair, deliver, watermark)
+        toks, ns = q.toks, q.ns
+        groups = stream_groups(len(toks), batch_sizes, q.max_batch)
         if int(in_flight) < 1:
             raise ValueError("synthesize_long_stream: in_flight must be at least 1")
         base = (self._next_seed() if seed is None else int(seed)) if toks else 0
         seeds = [piece_seed(base, i) for i in range(len(toks))]
-        calls, _al_b = self._long_calls(voice, toks, ns, seeds, groups, len(prefix), ep, al, tk, rp, False)
-        return self._long_chunks(calls, groups, toks, ns, seeds, len(prefix), ep, K, int(in_flight), gap_ms, fade_ms, pcm16, dv,
-                                 return_words, return_pieces, wm)
+        calls, _al_b = self._long_calls(voice, toks, ns, seeds, groups, len(q.prefix), q.ep, q.al, q.tk, q.rp, False)
+        return self._long_chunks(calls, groups, toks, ns, seeds, len(q.prefix), q.ep, int(in_flight), gap_ms, fade_ms, pcm16, q.dv,
+                                 return_words, return_pieces, q.wm)
 
-    def _long_chunks(self, calls, groups, toks, ns, seeds, n_prefix: int, ep: Optional["Endpointing"], K: int, in_flight: int,
+    def _long_chunks(self, calls, groups, toks, ns, seeds, n_prefix: int, ep: Optional["Endpointing"], in_flight: int,
                      gap_ms: float, fade_ms: float, pcm16: bool, dv: Optional["Delivery"], return_words: bool, return_pieces: bool,
                      wm: Optional["Watermark"] = None):
         """synthesize_long_stream's generator: the groups' deferred batches `calls`, enqueued ahead, verified, joined and handed out."""
@@ -1946,17 +1232,11 @@ class SmallTTS:
         queue: Dict[int, list] = {}                            # group -> [record, its event (None: run again on the caller's stream)]
 
         def enqueue(i: int) -> None:
-            # throughput tuning and the named workspace around this one enqueue, as _run_in_flight sets them: never held across a yield
-            prev_tuning = eng.set_tuning("throughput")
-            try:
-                with torch.cuda.stream(streams[i % L]):
-                    eng.use_workspace(f"batch{i % L}")
-                    rec = calls[i]()
-                    ev = torch.cuda.Event()
-                    ev.record()
-            finally:
-                eng.use_workspace(None)
-                eng.set_tuning(prev_tuning)
+            # throughput tuning and the named workspace around this one enqueue, _run_in_flight's: never held across a yield
+            with self._throughput(), self._in_flight_slot(streams[i % L], i % L):
+                rec = calls[i]()
+                ev = torch.cuda.Event()
+                ev.record()
             queue[i] = [rec, ev]
 
         def tail(gi: int, rec: _Batch):
@@ -2025,26 +1305,11 @@ class SmallTTS:
                 pos0, pos1 = int(res["pos"][0]), int(res["pos"][1])
                 count = pos1 - pos0 if not bank_rate else deliver_counts(pos0, pos1 - pos0, last, up, down, width)
                 audio = res["audio"].reshape(1, -1)[:, :count]
-                segs, words, made = [], ([] if return_words else None), ([] if return_pieces else None)
-                for r, i in enumerate(g):
-                    off_i = int(res["off"][r])
-                    if ep is None:
-                        segs.append((off_i, HOP_SIZE * ns[i], 0, 1.0))
-                    else:
-                        segs.append((off_i, int(res["seg"][r, 1]), int(res["seg"][r, 0]), float(res["gain"][r])))
-                    if return_words:
-                        words += word_times(token_groups(toks[i][n_prefix:]), res["spans"][r], ns[i], token0=n_prefix,
-                                            window=(segs[-1][2], segs[-1][1]) if ep is not None else None, offset=off_i,
-                                            index0=n_words + len(words))
-                    if return_pieces:
-                        spoken = take_seed(seeds[i], int(res["winner"][r])) if "winner" in res else seeds[i]
-                        made.append(Piece(toks[i], n_prefix, res["latents"][r, : ns[i]], spoken,
-                                          res["spans"][r, : len(toks[i])] if return_words else None))
-                if return_words:
-                    n_words += len(words)
-                if dv is not None:                             # positions in output samples, synthesize_long's rule
-                    segs = [(dv.samples(o), dv.samples(o + n) - dv.samples(o), dv.samples(st), gn) for o, n, st, gn in segs]
-                    words = None if words is None else [(i, kind, dv.samples(a), dv.samples(b)) for i, kind, a, b in words]
+                segs, words, made = _piece_rows(res["off"], res.get("seg"), res.get("gain"), res.get("spans"), res.get("latents"),
+                                                res.get("winner"), [toks[i] for i in g], [ns[i] for i in g], [seeds[i] for i in g],
+                                                n_prefix, ep, return_words, return_pieces, n_words)
+                n_words += len(words or ())
+                segs, words = _to_output_samples(dv, segs, words)   # synthesize_long's rule
                 chunk = LongChunk(audio, gi, pos0 if dv is None else sent, segs, words, made)
                 sent += count
                 yield chunk
@@ -2242,20 +1507,23 @@ class SmallTTS:
                 cnt = [deliver_counts(hop * int(t), hop * c, k == len(sizes) - 1, up, down, width) for k, (t, c) in enumerate(zip(t0s, sizes))]
         host = [torch.empty(1, max(max(cnt), 1), dtype=dt).pin_memory() for _ in range(2)]
 
+        def deliver_kw(k: int, t0: int) -> dict:
+            """How chunk k is delivered: through the resampler's slot, or (24 kHz, a pure encode without state) the mark's, or neither."""
+            if dstate is not None:
+                return {"state": dstate, "slots": [0], "n_before": [hop * t0], "last": k == len(sizes) - 1}
+            if wm is not None:
+                return {"slots": [0], "n_before": [hop * t0], "mark": wm, "mark_state": mstate}
+            return {}
+
         def enqueue(k: int, t0: int):
             snap.copy_(state)                                  # what a re-decode of chunk k starts from
             a = eng.codec_decode_stream(rec.latents[:, t0:t0 + sizes[k]], state, [0])
             if dv is not None:
                 if dstate is not None:
                     dsnap.copy_(dstate)
-                    a = eng.deliver(a, [hop * sizes[k]], dv.rate, dv.encoding, state=dstate, slots=[0], n_before=[hop * t0],
-                                    last=k == len(sizes) - 1)[0][None]
                 elif wm is not None:
                     msnap.copy_(mstate)
-                    a = eng.deliver(a, [hop * sizes[k]], dv.rate, dv.encoding, slots=[0], n_before=[hop * t0], mark=wm,
-                                    mark_state=mstate)[0][None]
-                else:
-                    a = eng.deliver(a, [hop * sizes[k]], dv.rate, dv.encoding)[0][None]
+                a = eng.deliver(a, [hop * sizes[k]], dv.rate, dv.encoding, **deliver_kw(k, t0))[0][None]
             a = eng.pcm16(a) if pcm16 else a
             host[k % 2][:, :cnt[k]].copy_(a[0][:, :cnt[k]], non_blocking=True)
             ev = torch.cuda.Event()

@@ -174,7 +174,7 @@ def parse_trim_query(q: dict):
     """The optional `trim` / `level` query parameters -> None (off: the answer is today's) or an api.Endpointing.  `trim` is 1 / true
     or 0 / false; `level` (dBFS of the speech after levelling, -60 .. 0) is only accepted together with trim=1.  Anything else is a
     400 for the offender alone, like validate_request."""
-    from .api import Endpointing
+    from .options import Endpointing
     raw = q.get("trim", ["0"])[0].strip().lower()
     if raw not in ("0", "1", "true", "false"):
         raise HttpError(400, "invalid `trim`: 0 or 1")
@@ -234,7 +234,7 @@ def parse_stream_query(q: dict, trim=None, align: bool = False) -> bool:
 def parse_deliver_query(q: dict, trim=None):
     """The optional `rate` / `encoding` query parameters -> None (neither given: the answer is today's) or an api.Delivery; one alone
     defaults the other to 24000 / "pcm16".  Anything else is a 400 for the offender alone."""
-    from .api import Delivery
+    from .options import Delivery
     from .audio import DELIVER_RATES
     if "rate" not in q and "encoding" not in q:
         return None
@@ -472,7 +472,7 @@ class Batcher:
         its frames of the decoded chunk, flagged last where the row ends in it, and its bytes are the audio.deliver_counts samples that
         call emits for it; the concatenation is the delivery of the row's whole decode.  A row that ended earlier rides along with
         length 0 and its output is dropped."""
-        from .api import stream_chunks
+        from .plans import stream_chunks
         torch, eng = self.torch, self.eng
         rec = self.tts.synthesize_batch(refs, [r.tokens for r in reqs], [r.duration for r in reqs], noise=noise, frames=ns,
                                         _defer=True, _decode=False)
@@ -554,7 +554,7 @@ class Batcher:
                 spans = None if spans is None else spans.cpu().numpy()
 
                 def words_of(b, r, window):   # an aligned request answers (what it would have answered, words)
-                    from .api import token_groups, word_times
+                    from .plans import token_groups, word_times
                     return word_times(token_groups(r.tokens), spans[b], ns[b], window=window)
 
                 for b, r in enumerate(reqs):
