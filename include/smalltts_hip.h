@@ -298,6 +298,39 @@ int smtts_ctc_score(smtts_handle h, void* stream, const float* logp, const int32
 int smtts_ctc_greedy(smtts_handle h, void* stream, const float* logp, const int32_t* t_len, int B, int T, int C, int32_t* ids,
                      int32_t* n_ids);
 
+/* ---- Forced alignment (DESIGN.md '8l. Forced alignment'): the best path of smtts_ctc_score's lattice ------------------------------
+ * smtts_ctc_align: logp, t_len, tokens, p0, p1 exactly as smtts_ctc_score takes and clamps them (t_len into [0, T], p0 / p1 into [0, P],
+ * every token into [1, C)), all DEVICE.  Row b: target l = tokens[b][p0 : p1), L = p1 - p0, extended states [blank, l_0, blank, l_1, ...,
+ * blank], S = 2 L + 1, label(s) = blank for even s and l_(s / 2) for odd s, T_b = t_len[b], lp_t = logp[b][t].  The definition, every step
+ * a single fp32 operation:
+ *     delta_0[0] = lp_0[0];  delta_0[1] = lp_0[l_0];  -inf elsewhere
+ *     v = delta_{t-1}[s], m = 0
+ *     if s >= 1  and delta_{t-1}[s-1] > v:  v = delta_{t-1}[s-1], m = 1
+ *     if skip(s) and delta_{t-1}[s-2] > v:  v = delta_{t-1}[s-2], m = 2      (skip(s) = s odd, s >= 3 and label(s) != label(s - 2))
+ *     delta_t[s] = v + lp_t[label(s)];  move_t[s] = m
+ *     e = (delta_{T_b-1}[S-2] > delta_{T_b-1}[S-1]) ? S-2 : S-1
+ *     score = delta_{T_b-1}[e]
+ * The comparisons are strict: ties prefer staying, then one step; a NaN is never greater.  A row is ALIGNED iff score > -inf.  It is not
+ * for t_len == 0 and L <= 0 (score = -inf), for an infeasible row (t_len < L + repeats: -inf) and for a NaN score; then every span is
+ * (-1, -1), tok_logp is 0 and frame_tok is -1, and score is as computed.  An aligned row is traced back:
+ *     s = e;  for t = T_b - 1 ... 1:  state[t] = s;  s = max(s - move_t[s], 0);   state[0] = s
+ * (a bounded loop whose index stays in [0, S) whatever the data hold).  ->
+ *   spans    i32 (B,P,2)  (first, last) frame t with state[t] == 2 (p - p0) + 1 for token p of [p0, p1), (-1, -1) for every other token;
+ *   tok_logp f32 (B,P)    the sum of lp_t[label] over those frames, t ascending, single fp32 adds; 0 outside the window;
+ *   frame_tok i32 (B,T)   optional (NULL: skipped): the token index p on a label frame, -1 on a blank frame and at or behind t_len[b];
+ *   score    f32 (B).
+ * Frames are frames of logp: behind smtts_asr_logprobs that is a quarter of a codec frame, 800 samples at 24 kHz.  One workgroup per
+ * row and one launch; the 2-bit moves live in LDS (one 32-bit word per state and 16 steps, about 100 KB at the limits), so the trace
+ * never leaves the CU and the entry takes no workspace.  Every sum has a fixed order and there are no atomics: two runs, alone or inside
+ * any batch, return the same bits; nothing at or behind t_len[b] of a row, and nothing outside the row, is read.
+ * 1 <= B <= 65536, 1 <= T <= 1024, 1 <= P <= 198, 2 <= C <= 256.  Needs no weights: works on any handle.  One stream, no
+ * synchronisation; an argument error returns 1 with a message naming the entry before anything is enqueued.
+ * Only this mechanism is verified.  As for the whole of 8i: no recogniser checkpoint has ever been loaded and the Conformer composition
+ * is restated from recollection, so what an alignment of real speech is worth is UNVALIDATED. */
+int smtts_ctc_align(smtts_handle h, void* stream, const float* logp, const int32_t* t_len, const int32_t* tokens, const int32_t* p0,
+                    const int32_t* p1, int B, int T, int P, int C, int32_t* spans, float* tok_logp, int32_t* frame_tok /* or NULL */,
+                    float* score);
+
 /* ---- Speaker score (DESIGN.md '8j. Speaker score'): the latent speaker verifier on the device ---------------------------------------
  * smtts_sv_embed replaces the reference's SV(192).forward (src/smalltts/models/sv/model.py:26-35: speechbrain's ECAPA_TDNN on the 64-dim
  * latents, lengths / max as its relative lengths) for an engine that was given the sv.* tensors (smtts_has_part(h, 4)).  x f32 (B,N,64)

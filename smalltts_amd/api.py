@@ -27,10 +27,10 @@ from .weights import DEFAULT_CODEC, CodecSpec, all_param_specs, asr_param_specs,
 from .options import (ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS, TAKE_JOIN_KEYS, Alignment, Delivery, Endpointing, Piece, Repair, Takes,
                       Watermark, _Frozen, as_alignment, as_delivery, as_endpointing, as_repair, as_takes, as_watermark, load_take,
                       marked_delivery, save_take)
-from .plans import (CHARS_PER_SECOND, HOP_SIZE, NUM_STEPS, SAMPLE_RATE, _CLAUSE_END, _SENTENCE_END, _check_pins,
-                    _default_count_tokens, _frames, _hard_cut, _srt_time, _units, estimate_duration, fade_table, format_srt,
-                    frames_of_groups, phoneme_error_rate, piece_seed, plan_long, plan_packed, repair_seed, splice_pins, split_text,
-                    stream_chunks, stream_groups, take_seed, token_groups, word_times)
+from .plans import (CHARS_PER_SECOND, CTC_HOP, HOP_SIZE, NUM_STEPS, SAMPLE_RATE, _CLAUSE_END, _SENTENCE_END, _check_pins,
+                    _default_count_tokens, _frames, _hard_cut, _srt_time, _units, codec_spans, estimate_duration, fade_table,
+                    format_srt, frames_of_groups, group_confidence, phoneme_error_rate, piece_seed, plan_long, plan_packed,
+                    repair_seed, splice_pins, split_text, stream_chunks, stream_groups, take_seed, token_groups, word_times)
 
 DEFAULT_WEIGHTS = os.environ.get("SMALLTTS_WEIGHTS", "assets/smalltts.smtts")
 
@@ -469,7 +469,7 @@ class SmallTTS:
         `num_steps`, `seed`, and `device_ids` — the GPUs `synthesize_sharded` spreads a request list over from THIS process
         (one weight replica, engine and host thread per GPU; under torch.distributed the process group is used instead).
         `recogniser=True` adds the latent phoneme recogniser (engine part "asr") to this instance's engine: transcribe(),
-        ctc_score() and Takes(ctc=) need it.  `verifier=True` adds the latent speaker verifier (engine part "sv"):
+        ctc_score(), Takes(ctc=) and the alignment calls (align_phonemes(), align_words(), align_wav(), realign()) need it.  `verifier=True` adds the latent speaker verifier (engine part "sv"):
         speaker_embedding(), speaker_similarity(), a Voice's `speaker` and Takes(sv=) need it."""
         if device_ids:
             device = int(device_ids[0])
@@ -643,22 +643,101 @@ class SmallTTS:
         frames or tokens and for one with too few frames for its tokens.  latents / lengths as transcribe().  Lower = the phonemes
         were more probably spoken; what that is worth is unvalidated on trained weights."""
         x, ns = self._asr_rows("ctc_score", latents, lengths)
-        B = len(ns)
-        toks = [[int(t) for t in row] for row in phoneme_ids]
-        p0 = [0] * B if prefix_lens is None else [int(v) for v in prefix_lens]
-        if len(toks) != B or len(p0) != B or any(p < 0 or p > len(t) for p, t in zip(p0, toks)):
-            raise ValueError("ctc_score: one token list and one prefix length in [0, tokens of the row] per row")
-        P = max([len(t) for t in toks] + [1])
-        if P > ALIGN_MAX_TOKENS:
-            raise ValueError(f"ctc_score: at most {ALIGN_MAX_TOKENS} tokens per row, got {P}")
-        tab = np.zeros((B, P), np.int32)
-        for b, t in enumerate(toks):
-            tab[b, :len(t)] = t
+        toks, p0, tab = self._ctc_targets("ctc_score", len(ns), phoneme_ids, prefix_lens)
         eng = self.engine
         nll = eng.ctc_score(eng.asr_logprobs(x, ns), [ASR_UPSAMPLE * v for v in ns], eng._dev(tab, torch.int32), p0, [len(t) for t in toks])
         nll = nll.cpu().numpy()
         with np.errstate(invalid="ignore", divide="ignore"):
             return [(float(v), float(np.float32(v) / np.float32(max(len(t) - p, 0)))) for v, t, p in zip(nll, toks, p0)]
+
+    @staticmethod
+    def _ctc_targets(what: str, B: int, phoneme_ids, prefix_lens):
+        """The targets of a CTC call -> (token lists, prefix lengths, the zero-padded (B, P) int32 table)."""
+        toks = [[int(t) for t in row] for row in phoneme_ids]
+        p0 = [0] * B if prefix_lens is None else [int(v) for v in prefix_lens]
+        if len(toks) != B or len(p0) != B or any(p < 0 or p > len(t) for p, t in zip(p0, toks)):
+            raise ValueError(f"{what}: one token list and one prefix length in [0, tokens of the row] per row")
+        P = max([len(t) for t in toks] + [1])
+        if P > ALIGN_MAX_TOKENS:
+            raise ValueError(f"{what}: at most {ALIGN_MAX_TOKENS} tokens per row, got {P}")
+        tab = np.zeros((B, P), np.int32)
+        for b, t in enumerate(toks):
+            tab[b, :len(t)] = t
+        return toks, p0, tab
+
+    def align_phonemes(self, latents, phoneme_ids: Sequence[Sequence[int]], lengths=None, prefix_lens=None) -> List[tuple]:
+        """Forced alignment: per row (spans, tok_logp, score) of the best CTC path of the row's tokens
+        phoneme_ids[b][prefix_lens[b]:] through the recogniser's reading of its latents (engine.asr_logprobs, engine.ctc_align;
+        DESIGN 8l).  spans (len(ids), 2) int32: the (first, last) RECOGNISER frame of every token, 4 per latent frame, 800 samples
+        each; (-1, -1) for the prefix.  tok_logp (len(ids),) float32: the path's log-probability per token; score: its total.  A
+        row that is not aligned (no frames, no tokens, fewer frames than its tokens and repeats need) has every span (-1, -1), tok_logp
+        0 and score -inf.  latents / lengths as transcribe().  Works on any latents: a saved take, respeak's, an encoded recording.
+        Needs SmallTTS(recogniser=True).  Only the mechanism is verified: no trained recogniser checkpoint has ever been loaded, so
+        what these times are worth on speech is UNVALIDATED."""
+        return self._align_rows("align_phonemes", latents, phoneme_ids, lengths, prefix_lens)[0]
+
+    def _align_rows(self, what: str, latents, phoneme_ids, lengths, prefix_lens):
+        x, ns = self._asr_rows(what, latents, lengths)
+        toks, p0, tab = self._ctc_targets(what, len(ns), phoneme_ids, prefix_lens)
+        eng = self.engine
+        spans, tok_logp, score = eng.ctc_align(eng.asr_logprobs(x, ns), [ASR_UPSAMPLE * v for v in ns], eng._dev(tab, torch.int32), p0,
+                                               [len(t) for t in toks])
+        spans, tok_logp, score = spans.cpu().numpy(), tok_logp.cpu().numpy(), score.cpu().numpy()
+        rows = [(spans[b, :len(t)].copy(), tok_logp[b, :len(t)].copy(), float(score[b])) for b, t in enumerate(toks)]
+        return rows, toks, p0, ns
+
+    def align_words(self, latents, phoneme_ids: Sequence[Sequence[int]], lengths=None, prefix_lens=None) -> List[List[tuple]]:
+        """Word timings from align_phonemes: per row [(index, kind, phonemes, start sample, end sample, confidence), ...] for the
+        token_groups of the row's own tokens (behind its prefix), by word_times at hop 800: samples at 24 kHz from the row's start,
+        resolution 33.3 ms.  confidence: the mean over the group's tokens of tok_logp / span length (plans.group_confidence), the
+        path's mean log-probability per frame, <= 0.  On a row that is not aligned every group collapses to (0, 0) with confidence
+        -inf.  Arguments and limits as align_phonemes; UNVALIDATED on trained weights like it."""
+        rows, toks, p0, ns = self._align_rows("align_words", latents, phoneme_ids, lengths, prefix_lens)
+        out = []
+        for (spans, tok_logp, _score), t, p, n in zip(rows, toks, p0, ns):
+            groups = token_groups(t[p:])
+            times = word_times(groups, spans, ASR_UPSAMPLE * n, token0=p, hop=CTC_HOP)
+            conf = group_confidence(groups, spans, tok_logp, token0=p)
+            out.append([(i, kind, g[1], s, e, c) for (i, kind, s, e), g, c in zip(times, groups, conf)])
+        return out
+
+    def align_wav(self, audio, sr: int, phoneme_ids: Sequence[int]) -> List[tuple]:
+        """Word timings of a recording: mono samples at `sr` Hz, at most 30 s, and the phoneme ids of what it says -> align_words' row,
+        times in samples at 24 kHz.  The clip goes through the device resampler and the codec encoder (Encoder.encode_reference and
+        its cache, as encode_voice_wav), its latents through align_words.  Samples behind the last whole codec hop are not aligned."""
+        a = np.asarray(audio, np.float32)
+        if a.ndim != 1 and not (a.ndim == 2 and 1 in a.shape):
+            raise ValueError(f"align_wav: a mono recording, got an array of shape {a.shape}")
+        sr = int(sr)
+        if sr < 1 or a.size < 1 or a.size > 30 * sr:
+            raise ValueError(f"align_wav: between one sample and 30 s of audio at a positive rate, got {a.size} samples at {sr} Hz")
+        if not self.engine.has("asr"):
+            raise ValueError("align_wav: needs the recogniser part (SmallTTS(recogniser=True))")
+        y = self.engine.resample(a.reshape(-1), sr, SAMPLE_RATE)
+        if int(y.numel()) < HOP_SIZE:
+            raise ValueError("align_wav: the clip is shorter than one codec hop")
+        lat = Encoder(engine=self.engine).encode_reference(y.reshape(1, 1, -1))
+        return self.align_words([lat[0].numpy()], [phoneme_ids])[0]
+
+    def realign(self, pieces: Sequence[Piece]) -> List[Piece]:
+        """The Pieces of a take with `spans` replaced by the recogniser's: align_phonemes on every piece's latents and tokens (its
+        prefix left out), mapped to codec frames by plans.codec_spans, (first // 4, last // 4), (-1, -1) kept.  frames_of_groups,
+        respeak and render_long then work from the CTC alignment instead of the text-attention tap's; tokens, latents and seeds are
+        untouched, so the audio of the take does not change.  A piece that is not aligned keeps its old spans.  At most 64 pieces per
+        call go through the recogniser at once; more are taken in turns."""
+        pieces = list(pieces)
+        if any(not isinstance(p, Piece) for p in pieces):
+            raise ValueError("realign: a sequence of Pieces (synthesize_long(return_pieces=True), load_take)")
+        if not self.engine.has("asr"):
+            raise ValueError("realign: needs the recogniser part (SmallTTS(recogniser=True))")
+        out = []
+        for i in range(0, len(pieces), ASR_MAX_ROWS):
+            grp = pieces[i: i + ASR_MAX_ROWS]
+            rows = self.align_phonemes([p.latents for p in grp], [p.tokens for p in grp], prefix_lens=[p.prefix_len for p in grp])
+            for p, (spans, _tok_logp, score) in zip(grp, rows):
+                aligned = score > float("-inf")                # (False for NaN)
+                out.append(Piece(p.tokens, p.prefix_len, p.latents, p.seed, codec_spans(spans) if aligned else p.spans))
+        return out
 
     def synthesize_batch(self, ref_latents: Optional[Sequence[np.ndarray]], phoneme_ids: Sequence[Sequence[int]],
                          durations, *, noise: Optional[np.ndarray] = None, return_latents: bool = False,

@@ -210,6 +210,15 @@ int smtts_ctc_greedy(smtts_handle h, void* stream, const float* logp, const int3
     hipError_t e = launch_ctc_greedy(logp, t_len, B, T, C, ids, n_ids, ST(stream));
     return e == hipSuccess ? 0 : E.fail_hip(e, "ctc_greedy");
 }
+int smtts_ctc_align(smtts_handle h, void* stream, const float* logp, const int32_t* t_len, const int32_t* tokens, const int32_t* p0,
+                    const int32_t* p1, int B, int T, int P, int C, int32_t* spans, float* tok_logp, int32_t* frame_tok, float* score) { NULLCHK;
+    if (B < 1 || B > 65536) return E.fail("smtts_ctc_align: B must be in [1, 65536]");
+    if (T < 1 || T > 1024 || P < 1 || P > 198 || C < 2 || C > 256)
+        return E.fail("smtts_ctc_align: T must be in [1, 1024], P in [1, 198] and C in [2, 256] (a row's states, moves and emission ring live in LDS)");
+    if (!logp || !t_len || !tokens || !p0 || !p1 || !spans || !tok_logp || !score) return E.fail("smtts_ctc_align: a required pointer is NULL");
+    hipError_t e = launch_ctc_align(logp, t_len, tokens, p0, p1, B, T, P, C, spans, tok_logp, frame_tok, score, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "ctc_align");
+}
 
 size_t smtts_sv_workspace_bytes(smtts_handle h, int B, int N) { NULLCHK0; return E.sv_workspace_bytes(B, N); }
 int smtts_sv_embed(smtts_handle h, void* stream, const float* x, const int32_t* n_len, int B, int N, void* ws, size_t ws_bytes,

@@ -95,6 +95,12 @@ hipError_t launch_ctc_score(const float* logp, const int* t_len, const int* toke
                             float* nll, hipStream_t st);
 // per-frame argmax (lowest class on ties), runs collapsed, class 0 dropped -> ids i32 (B, T), zeros behind n_ids i32 (B).  1 <= T <= 4096.
 hipError_t launch_ctc_greedy(const float* logp, const int* t_len, int B, int T, int C, int* ids, int* n_ids, hipStream_t st);
+// the best path of ctc_score's lattice (same clamping): spans i32 (B, P, 2) = (first, last) frame of every token of the window, (-1, -1)
+// outside it and on a row that is not aligned; tok_logp f32 (B, P) the path's log-probability per token; frame_tok i32 (B, T) or NULL the
+// token of every label frame, -1 elsewhere; score f32 (B) the path's log-probability, -inf for an empty or infeasible row.  One workgroup
+// per row, the 2-bit moves in dynamic LDS sized by T and P.  1 <= T <= 1024, 1 <= P <= 198, 2 <= C <= 256, else hipErrorInvalidValue.
+hipError_t launch_ctc_align(const float* logp, const int* t_len, const int* tokens, const int* p0, const int* p1, int B, int T, int P, int C,
+                            int* spans, float* tok_logp, int* frame_tok, float* score, hipStream_t st);
 // ---- recogniser (asr.hip) -----------------------------------------------------------------------------------------------------------
 // Device pointers of the packed recogniser weights (Engine::finalize_asr): every 64 x 64 block of a product's weight transposed to
 // [k][n], 16-byte aligned; vectors as loaded.

@@ -26,7 +26,8 @@ DEFAULT_PRECISION = "f16"
 
 ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS = 225, 198   # smtts_align_path: 30 s of codec frames, the phoneme window
 ASR_MAX_ROWS, ASR_UPSAMPLE, ASR_CLASSES = 64, 4, 198   # smtts_asr_logprobs: rows per call, frames per latent frame, phoneme classes
-SV_MAX_ROWS, SV_MIN_FRAMES, SV_DIM = 64, 6, 192        # smtts_sv_embed: rows per call, the shortest row with an embedding, its width
+CTC_ALIGN_MAX_FRAMES = 1024                            # smtts_ctc_align: frames of logp per row (its move table lives in LDS)
+SV_MAX_ROWS, SV_MIN_FRAMES, SV_DIM = 64, 6, 192       # smtts_sv_embed: rows per call, the shortest row with an embedding, its width
 
 
 def _p(t: Optional[torch.Tensor]):
@@ -609,6 +610,34 @@ class HipEngine:
         self._ck(self.lib.smtts_ctc_score(self.h, self._stream(), _p(logp), _p(tab[0]), _p(tokens), _p(tab[1]), _p(tab[2]), B, T, P, Cn,
                                           _p(nll)), "ctc_score")
         return nll
+
+    def ctc_align(self, logp: torch.Tensor, ts, tokens: torch.Tensor, p0, p1, frames: bool = False):
+        """The best CTC path of every row (smtts_ctc_align; the definition: include/smalltts_hip.h).  Arguments as
+        ctc_score, T <= 1024.  -> (spans int32 (B,P,2), the (first, last) frame of logp of every token of [p0[b], p1[b]) and (-1, -1)
+        for every other token; tok_logp fp32 (B,P), the path's log-probability per token; score fp32 (B), the path's
+        log-probability), and with frames=True a fourth element frame_tok int32 (B,T): the token of every label frame, -1 on blank
+        frames and behind ts[b].  A row without frames or tokens, an infeasible row and a NaN score are not aligned: every span
+        (-1, -1), tok_logp 0, frame_tok -1, score -inf (or the NaN).  All on the device.  Needs no weights.  One launch on the current
+        stream, no synchronisation."""
+        if logp.dim() != 3 or logp.dtype != torch.float32 or not logp.is_contiguous() or logp.device != self.device:
+            raise ValueError("ctc_align: logp must be a contiguous fp32 (B,T,C) tensor on the engine's device")
+        B, T, Cn = (int(v) for v in logp.shape)
+        if tokens.dim() != 2 or tokens.dtype != torch.int32 or not tokens.is_contiguous() or tokens.device != self.device or tokens.shape[0] != B:
+            raise ValueError(f"ctc_align: tokens must be a contiguous int32 ({B},P) tensor on the engine's device")
+        P = int(tokens.shape[1])
+        if not (1 <= T <= CTC_ALIGN_MAX_FRAMES and 1 <= P <= ALIGN_MAX_TOKENS and 2 <= Cn <= 256):
+            raise ValueError(f"ctc_align: T = {T}, P = {P}, C = {Cn} outside the supported range 1 <= T <= {CTC_ALIGN_MAX_FRAMES}, "
+                             f"P <= {ALIGN_MAX_TOKENS}, 2 <= C <= 256")
+        if B < 1 or len(ts) != B or len(p0) != B or len(p1) != B:
+            raise ValueError("ctc_align: one frame count and one token range per row")
+        tab = self._upload_i32([ts, p0, p1])
+        spans = torch.empty(B, P, 2, dtype=torch.int32, device=self.device)
+        tok_logp = torch.empty(B, P, device=self.device)
+        score = torch.empty(B, device=self.device)
+        frame_tok = torch.empty(B, T, dtype=torch.int32, device=self.device) if frames else None
+        self._ck(self.lib.smtts_ctc_align(self.h, self._stream(), _p(logp), _p(tab[0]), _p(tokens), _p(tab[1]), _p(tab[2]), B, T, P, Cn,
+                                          _p(spans), _p(tok_logp), _p(frame_tok), _p(score)), "ctc_align")
+        return (spans, tok_logp, score, frame_tok) if frames else (spans, tok_logp, score)
 
     def ctc_greedy(self, logp: torch.Tensor, ts):
         """Greedy CTC transcript of every row (smtts_ctc_greedy): per-frame argmax (lowest class on ties), runs collapsed, class 0

@@ -300,8 +300,8 @@ def marked_delivery(what: str, watermark, dv: Optional["Delivery"]):
 class Piece(_Frozen):
     """One piece of a long take, as synthesize_long(return_pieces=True) spoke it: `tokens` (the prefix included), `prefix_len` (how
     many of them are the prepended transcription), `latents` (n, 64) fp32 on the host, and the `seed` of its noise; `spans`
-    (len(tokens), 2) int32, the (first, last) frame of every token, when the take was aligned (return_words), else None.  Immutable;
-    render_long joins pieces again, respeak makes the latents of a replacement."""
+    (len(tokens), 2) int32, the (first, last) frame of every token, when the take was aligned (return_words, or SmallTTS.realign),
+    else None.  Immutable; render_long joins pieces again, respeak makes the latents of a replacement."""
     __slots__ = ("tokens", "prefix_len", "latents", "seed", "spans")
 
     def __init__(self, tokens: Sequence[int], prefix_len: int, latents, seed: int, spans=None) -> None:

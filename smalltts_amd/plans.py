@@ -291,6 +291,36 @@ def frames_of_groups(groups: Sequence[Tuple[str, str, int, int]], spans, g0: int
     return first, last + 1
 
 
+CTC_FRAMES_PER_CODEC_FRAME = 4                    # the recogniser runs at 4 frames per latent frame (engine.ASR_UPSAMPLE)
+CTC_HOP = HOP_SIZE // CTC_FRAMES_PER_CODEC_FRAME  # 800 samples, 33.3 ms: the resolution of a CTC alignment
+
+
+def codec_spans(spans) -> np.ndarray:
+    """Token spans in recogniser frames (smtts_ctc_align) -> the codec frames they touch: (first // 4, last // 4) per token, (-1, -1)
+    kept.  The result is what frames_of_groups, respeak and a Piece's `spans` count in."""
+    sp = np.asarray(spans, np.int32)
+    if sp.ndim != 2 or sp.shape[1] != 2:
+        raise ValueError(f"codec_spans: spans must be (tokens, 2), got {sp.shape}")
+    return np.where(sp < 0, np.int32(-1), sp // np.int32(CTC_FRAMES_PER_CODEC_FRAME)).astype(np.int32)
+
+
+def group_confidence(groups: Sequence[Tuple[str, str, int, int]], spans, tok_logp, token0: int = 0) -> List[float]:
+    """Per token group the mean over its tokens of tok_logp / span length (smtts_ctc_align's outputs of the row; span length = last -
+    first + 1 frames), float32 arithmetic in token order: the mean log-probability per frame the best path gives the group, <= 0 for
+    log-probabilities.  A group with a token off the path (a row that is not aligned) gets -inf."""
+    out = []
+    for _kind, _ph, t0, t1 in groups:
+        acc, ok = np.float32(0.0), t1 > t0
+        for t in range(token0 + t0, token0 + t1):
+            first, last = int(spans[t][0]), int(spans[t][1])
+            if first < 0 or last < first:
+                ok = False
+                break
+            acc = np.float32(acc + np.float32(tok_logp[t]) / np.float32(last - first + 1))
+        out.append(float(np.float32(acc / np.float32(t1 - t0))) if ok else float("-inf"))
+    return out
+
+
 def splice_pins(latents, f0: int, f1: int, m: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray]:
     """The pins of a re-spoken row: frames [f0, f1) of `latents` (n, 64) are replaced by m free frames (default f1 - f0, at least
     1).  -> (x_pin (n', 64) fp32, keep (n',) bool), n' = n - (f1 - f0) + m: the head [0, f0) and the tail [f1, n) are copied and

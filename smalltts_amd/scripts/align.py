@@ -1,0 +1,73 @@
+"""python -m smalltts_amd.scripts.align --wav rec.wav --text "..." --words out.json [--srt out.srt]
+python -m smalltts_amd.scripts.align --take in.npz --out-take out.npz
+Forced alignment by the latent phoneme recogniser (api.SmallTTS.align_wav / realign): the best CTC path of the phonemes
+through the recogniser's reading of the audio's latents, 33.3 ms resolution (800 samples at 24 kHz).
+--wav: a mono recording of at most 30 s and what it says (--text through the tokeniser, or --tokens) -> --words, a JSON list of
+{index, kind, phonemes, start, end (samples at 24 kHz), start_s, end_s, confidence}; confidence is the path's mean log-probability per
+frame over the group's tokens, null where the recording could not be aligned.  --srt: one subtitle cue per word group.
+--take: the pieces of a long take (scripts/longform.py --take) get the recogniser's token spans in place of the text-attention tap's,
+in codec frames, and are written to --out-take with the take's join parameters unchanged: scripts/respeak.py --groups then cuts
+where the recogniser heard the words.  A piece that could not be aligned keeps its spans.
+Only the mechanism is verified: no trained recogniser checkpoint has ever been loaded, so what these times are worth is unvalidated."""
+import argparse
+import json
+from pathlib import Path
+
+from ..api import SAMPLE_RATE, SmallTTS, format_srt, load_take, save_take
+from ..audio import read_wav
+from ._common import add_engine_args, tokens_for
+
+
+def words_json(words) -> str:
+    """align_words' row -> the --words file."""
+    fin = lambda v: float(v) if float("-inf") < float(v) < float("inf") else None
+    return json.dumps([{"index": int(i), "kind": kind, "phonemes": ph, "start": int(s), "end": int(e),
+                        "start_s": round(int(s) / SAMPLE_RATE, 4), "end_s": round(int(e) / SAMPLE_RATE, 4), "confidence": fin(c)}
+                       for i, kind, ph, s, e, c in words], ensure_ascii=False, indent=1)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--wav", default=None, help="a mono recording of at most 30 s")
+    ap.add_argument("--text", default=None, help="what the recording says (or --tokens)")
+    ap.add_argument("--words", default=None, metavar="OUT.json", help="write the time of every word / punctuation mark / [event] (33 ms resolution)")
+    ap.add_argument("--srt", default=None, metavar="OUT.srt", help="write one subtitle cue per word group")
+    ap.add_argument("--take", default=None, metavar="IN.npz", help="a long take (longform --take) to align again")
+    ap.add_argument("--out-take", default=None, metavar="OUT.npz", help="where the take with the recogniser's spans goes")
+    add_engine_args(ap)
+    args = ap.parse_args(argv)
+    if (args.wav is None) == (args.take is None):
+        ap.error("pass either --wav or --take")
+    if args.wav is not None and (not (args.text or args.tokens) or not (args.words or args.srt) or args.out_take):
+        ap.error("--wav needs --text or --tokens, and --words or --srt; --out-take belongs to --take")
+    if args.take is not None and (not args.out_take or args.text or args.words or args.srt):
+        ap.error("--take needs --out-take; --text, --words and --srt belong to --wav")
+    print("loading")
+    tts = SmallTTS(weights=args.weights, device=args.device, precision=args.precision, num_steps=args.steps, seed=args.seed,
+                   recogniser=True)
+    if args.wav is not None:
+        y, sr = read_wav(args.wav)
+        if y.ndim == 2:
+            y = y.mean(axis=1)
+        try:
+            words = tts.align_wav(y, sr, tokens_for(args, args.text or ""))
+        except ValueError as e:
+            ap.error(str(e))
+        if args.words:
+            Path(args.words).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.words).write_text(words_json(words), encoding="utf-8")
+            print(f"{args.words} ({len(words)} word groups)")
+        if args.srt:
+            Path(args.srt).parent.mkdir(parents=True, exist_ok=True)
+            Path(args.srt).write_text(format_srt([(s, e, ph) for _i, _kind, ph, s, e, _c in words]), encoding="utf-8")
+            print(args.srt)
+        return
+    pieces, join = load_take(args.take)
+    out = tts.realign(pieces)
+    Path(args.out_take).parent.mkdir(parents=True, exist_ok=True)
+    save_take(args.out_take, out, **join)
+    print(f"{args.out_take} ({len(out)} pieces)")
+
+
+if __name__ == "__main__":
+    main()
