@@ -6,9 +6,9 @@
 // outside [0, 4 n_b) of the row do not exist, nothing behind 4 n_b is read, frames there are written as 0.0 in the output only.
 //
 // All products share one tile: a workgroup of 256 threads owns 64 frames; the (normalised) activations sit in LDS transposed
-// [k][frame] (a_at), a 64 x 64 block of the weight, transposed to [k][n] at finalize, sits next to them.  The D = 64 products
+// [k][frame] (f32_tile.hpp tile_at), a 64 x 64 block of the weight, transposed to [k][n] at finalize, sits next to them.  The D = 64 products
 // (tile_mm): thread (rg, cg) accumulates frames 4 rg .. 4 rg + 3 x columns 4 cg .. 4 cg + 3 from two 16-byte LDS reads per k (the
-// activation read is a broadcast).  The FFN products, 93 % of the flops (mfma_block): wave w owns one 32 x 32 block.
+// activation read is a broadcast).  The FFN products, 93 % of the flops (f32_tile.hpp mfma_k64): wave w owns one 32 x 32 block.
 //   asr_ffn      LN, then 16 slices of 64 hidden units: W1 slice, SiLU into LDS, W2 slice into the running output; the hidden
 //                activations never leave the CU.  Epilogue: x + 0.5 (. + b2), and for ffn2 the layer's final LayerNorm.
 //                138 us against 186 us on the FMA tile at 32 rows x 300 frames, the same bits.
@@ -19,23 +19,15 @@
 //                pointwise 64 -> 64, residual.  Reads halo frames other workgroups own: input and output are different buffers.
 //   asr_head     projection to 198 classes (4 blocks of 64, zero padded) + log-softmax on the register tile
 // No atomics, every sum in a fixed order that does not depend on the batch: results repeat bit for bit, alone or in a batch.
+#include "f32_tile.hpp"
 #include "kernels.hpp"
 #include "prof.hpp"
 
 namespace {
 
 constexpr int A_NT = 256, A_TM = 64, A_LD = 64;
-// element (k, frame r) of a transposed activation tile: the 4-frame groups of row k are permuted by k, so that the 64 lanes of a
-// transposed store (lane = k) spread over 16 banks instead of one; a thread's 4 frames stay one aligned 16-byte read
-__device__ __forceinline__ int a_at(int k, int r) { return k * A_LD + 4 * ((r >> 2) ^ (k & 15)) + (r & 3); }
 constexpr int A_D = 64, A_FF = 1024, A_C = 198, A_HEADS = 16, A_CONV_OUT = 56, A_HALO = 4;
 constexpr float A_EPS = 1e-5f;
-
-__device__ __forceinline__ int frames_of(const int* n_len, int b, int N) {
-    int n = n_len[b];
-    n = n < 0 ? 0 : n > N ? N : n;
-    return 4 * n;
-}
 
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll
@@ -64,7 +56,7 @@ __device__ __forceinline__ void stage_rows(float* aT, const float* xrow, int t0,
             v = xrow[(long)t * A_D + lane];
             if (LN) v = ln_lane(v, gg, bb);
         }
-        aT[a_at(lane, r)] = v;
+        aT[tile_at<A_LD>(lane, r)] = v;
     }
 }
 
@@ -76,7 +68,7 @@ __device__ __forceinline__ void load_w(float* wS, const float* __restrict__ src)
 __device__ __forceinline__ void tile_mm(const float* aT, const float* wS, int rg, int cg, float (&acc)[4][4]) {
 #pragma unroll 8
     for (int k = 0; k < A_D; ++k) {
-        const float4 a = *reinterpret_cast<const float4*>(aT + a_at(k, 4 * rg));
+        const float4 a = *reinterpret_cast<const float4*>(aT + tile_at<A_LD>(k, 4 * rg));
         const float4 w = *reinterpret_cast<const float4*>(wS + k * A_D + 4 * cg);
         const float av[4] = {a.x, a.y, a.z, a.w}, wv[4] = {w.x, w.y, w.z, w.w};
 #pragma unroll
@@ -96,23 +88,10 @@ __device__ __forceinline__ void zero_acc(float (&acc)[4][4]) {
 __global__ __launch_bounds__(A_NT) void asr_upsample_kernel(const float* __restrict__ x, const int* __restrict__ n_len, int N,
                                                             const float* __restrict__ w, const float* __restrict__ bias,
                                                             float* __restrict__ y) {
-    const int b = blockIdx.y, T = 4 * N, tb = frames_of(n_len, b, N);
+    const int b = blockIdx.y, T = 4 * N, tb = 4 * row_len(n_len, b, N);
     const int i = blockIdx.x * A_NT + threadIdx.x, t = i >> 6, c = i & 63;
     if (t >= tb) return;
     y[((long)b * T + t) * A_D + c] = x[((long)b * N + (t >> 2)) * A_D + c] * w[c * 4 + (t & 3)] + bias[c];
-}
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-// One 32 x 32 block of (64 frames x 64 k) . (64 k x 64 n) on the exact f32-input MFMA (v_mfma_f32_32x32x2_f32: a k-ordered fmaf chain, one
-// rounding per product): lane l feeds A[frame f0 + (l & 31)][k + (l >> 5)] and B[k + (l >> 5)][n0 + (l & 31)], one float each, both
-// conflict-free LDS reads of the images tile_mm reads; the result has its column on the lane and its rows in the 16 registers,
-// row = (reg & 3) + 8 (reg >> 2) + 4 (l >> 5).
-__device__ __forceinline__ void mfma_block(const float* aT, const float* wS, int f0, int n0, int lane, f32x16& acc) {
-    const int r = lane & 31, h = lane >> 5;
-#pragma unroll 8
-    for (int k = 0; k < A_D; k += 2)
-        acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aT[a_at(k + h, f0 + r)], wS[(k + h) * A_D + n0 + r], acc, 0, 0, 0);
 }
 
 // wave w owns the 32 x 32 block (frames 32 (w >> 1) .., columns 32 (w & 1) ..) of both products
@@ -121,7 +100,7 @@ __global__ __launch_bounds__(A_NT) void asr_ffn_kernel(const float* xin, float* 
                                                        const int* __restrict__ n_len, int N, AsrFfnW w, const float* __restrict__ fg,
                                                        const float* __restrict__ fb) {
     __shared__ __attribute__((aligned(16))) float aT[A_D * A_LD], hT[A_D * A_LD], w1s[A_D * A_D], w2s[A_D * A_D];
-    const int b = blockIdx.y, T = 4 * N, tb = frames_of(n_len, b, N), t0 = blockIdx.x * A_TM;
+    const int b = blockIdx.y, T = 4 * N, tb = 4 * row_len(n_len, b, N), t0 = blockIdx.x * A_TM;
     if (t0 >= tb) return;   // (uniform)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int f0 = 32 * (wv >> 1), n0 = 32 * (wv & 1), col = n0 + (lane & 31), rbase = f0 + 4 * (lane >> 5);
@@ -137,20 +116,20 @@ __global__ __launch_bounds__(A_NT) void asr_ffn_kernel(const float* xin, float* 
         f32x16 h;
 #pragma unroll
         for (int i = 0; i < 16; ++i) h[i] = 0.f;
-        mfma_block(aT, w1s, f0, n0, lane, h);
+        mfma_k64<A_LD>(aT, f0 + (lane & 31), w1s, 0, n0, lane, h);
         const float b1 = w.b1[s * A_D + col];
 #pragma unroll
         for (int g = 0; g < 4; ++g)   // registers 4 g .. 4 g + 3: frames rbase + 8 g .. + 3 of hidden unit col
-            *reinterpret_cast<float4*>(hT + a_at(col, rbase + 8 * g)) =
+            *reinterpret_cast<float4*>(hT + tile_at<A_LD>(col, rbase + 8 * g)) =
                 make_float4(silu(h[4 * g] + b1), silu(h[4 * g + 1] + b1), silu(h[4 * g + 2] + b1), silu(h[4 * g + 3] + b1));
         __syncthreads();
-        mfma_block(hT, w2s, f0, n0, lane, out);
+        mfma_k64<A_LD>(hT, f0 + (lane & 31), w2s, 0, n0, lane, out);
         __syncthreads();   // the next slice overwrites w1s / w2s / hT
     }
     const float b2 = w.b2[col];
 #pragma unroll
     for (int i = 0; i < 16; ++i) {
-        const int r = rbase + (i & 3) + 8 * (i >> 2), t = t0 + r;
+        const int r = f0 + tile_row(i, lane), t = t0 + r;
         const float res = t < tb ? xrow[(long)t * A_D + col] : 0.f;
         const float y = fmaf(0.5f, out[i] + b2, res);
         if (FINAL_LN) hT[r * A_LD + col] = y;   // row-major now
@@ -172,7 +151,7 @@ __global__ __launch_bounds__(A_NT) void asr_qkv_kernel(const float* __restrict__
                                                        const float* __restrict__ wt, const float* __restrict__ bias,
                                                        float* __restrict__ qkv) {
     __shared__ __attribute__((aligned(16))) float aT[A_D * A_LD], wS[A_D * A_D];
-    const int b = blockIdx.y, T = 4 * N, tb = frames_of(n_len, b, N), t0 = blockIdx.x * A_TM;
+    const int b = blockIdx.y, T = 4 * N, tb = 4 * row_len(n_len, b, N), t0 = blockIdx.x * A_TM;
     if (t0 >= tb) return;
     const int tid = threadIdx.x, cg = tid & 15, rg = tid >> 4;
     stage_rows<true>(aT, xin + (long)b * T * A_D, t0, tb, g, be);
@@ -200,7 +179,7 @@ constexpr int AT_MAXT = 900;
 __global__ __launch_bounds__(A_NT) void asr_attn_kernel(const float* __restrict__ qkv, const int* __restrict__ n_len, int N,
                                                         float* __restrict__ o) {
     __shared__ float4 ks[AT_MAXT], vs[AT_MAXT];
-    const int b = blockIdx.z, h = blockIdx.y, T = 4 * N, tb = frames_of(n_len, b, N), q0 = blockIdx.x * A_NT;
+    const int b = blockIdx.z, h = blockIdx.y, T = 4 * N, tb = 4 * row_len(n_len, b, N), q0 = blockIdx.x * A_NT;
     if (q0 >= tb) return;   // (uniform)
     const float* const base = qkv + (long)b * T * (3 * A_D) + 4 * h;
     for (int t = threadIdx.x; t < tb; t += A_NT) {
@@ -232,7 +211,7 @@ __global__ __launch_bounds__(A_NT) void asr_proj_kernel(const float* __restrict_
                                                         const float* __restrict__ wt, const float* __restrict__ bias,
                                                         float* __restrict__ x) {
     __shared__ __attribute__((aligned(16))) float aT[A_D * A_LD], wS[A_D * A_D];
-    const int b = blockIdx.y, T = 4 * N, tb = frames_of(n_len, b, N), t0 = blockIdx.x * A_TM;
+    const int b = blockIdx.y, T = 4 * N, tb = 4 * row_len(n_len, b, N), t0 = blockIdx.x * A_TM;
     if (t0 >= tb) return;
     const int tid = threadIdx.x, cg = tid & 15, rg = tid >> 4;
     stage_rows<false>(aT, o + (long)b * T * A_D, t0, tb, nullptr, nullptr);
@@ -255,7 +234,7 @@ __global__ __launch_bounds__(A_NT) void asr_proj_kernel(const float* __restrict_
 __global__ __launch_bounds__(A_NT) void asr_conv_kernel(const float* __restrict__ xin, float* __restrict__ xout,
                                                         const int* __restrict__ n_len, int N, AsrConvW w) {
     __shared__ __attribute__((aligned(16))) float aT[A_D * A_LD], gb[A_TM * A_LD], wS[A_D * A_D];
-    const int b = blockIdx.y, T = 4 * N, tb = frames_of(n_len, b, N), c0 = blockIdx.x * A_CONV_OUT;
+    const int b = blockIdx.y, T = 4 * N, tb = 4 * row_len(n_len, b, N), c0 = blockIdx.x * A_CONV_OUT;
     if (c0 >= tb) return;
     const int t0 = c0 - A_HALO;   // tile row r <-> frame t0 + r; rows [4, 60) are this workgroup's outputs
     const int tid = threadIdx.x, cg = tid & 15, rg = tid >> 4, lane = tid & 63, wv = tid >> 6;
@@ -299,7 +278,7 @@ __global__ __launch_bounds__(A_NT) void asr_conv_kernel(const float* __restrict_
                 for (int j = 0; j < 9; ++j) d = fmaf(gb[(r - A_HALO + j) * A_LD + lane], dw[j], d);
                 y = silu(fmaf(d, sc, sh));
             }
-            aT[a_at(lane, r)] = y;
+            aT[tile_at<A_LD>(lane, r)] = y;
         }
     }
     __syncthreads();
@@ -323,7 +302,7 @@ __global__ __launch_bounds__(A_NT) void asr_head_kernel(const float* __restrict_
                                                         const float* __restrict__ wt, const float* __restrict__ bias,
                                                         float* __restrict__ logp) {
     __shared__ __attribute__((aligned(16))) float aT[A_D * A_LD], wS[A_D * A_D];
-    const int b = blockIdx.y, T = 4 * N, tb = frames_of(n_len, b, N), t0 = blockIdx.x * A_TM;
+    const int b = blockIdx.y, T = 4 * N, tb = 4 * row_len(n_len, b, N), t0 = blockIdx.x * A_TM;
     const int tid = threadIdx.x, cg = tid & 15, rg = tid >> 4;
     float acc[4][4][4];
 #pragma unroll
@@ -372,8 +351,6 @@ __global__ __launch_bounds__(A_NT) void asr_head_kernel(const float* __restrict_
             }
     }
 }
-
-inline size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
 
 }  // namespace
 

@@ -278,6 +278,12 @@ class Engine {
     int finalize_codec(bool decoder);
     int finalize_asr();
     int finalize_sv();
+    struct ScorerPack;   // engine_scorers.hip: a tensor to the host, a packed vector to the device, for both finalizers
+    // the six refusals the two scorer entries share.  entry: the C name without "smtts_"; net: "asr" / "sv"; part: what the engine
+    // lacks; out: the result's name
+    int scorer_entry(const char* entry, const char* net, const char* part, const char* out, bool ready, int n_min,
+                     size_t (*ws_need)(int, int), const float* x, const int32_t* n_len, int B, int N, const void* ws, size_t ws_bytes,
+                     const float* result);
     int build_encoder(EncoderW& e, const std::string& prefix, int dim, int heads, int ff, int layers, float eps);
     int make_rope(int dim, float** cos_out, float** sin_out);
     struct ModWs;

@@ -8,7 +8,7 @@
 // behind n_b is read, and every tile starts at the row's frame 0, so that a row's sums have one order whatever the batch.  A row with
 // n_b < 6 (the d = 5 reflect needs pad < n) has no embedding: its emb row is 0.0 and no other kernel touches it.
 //   sv_tdnn       64 frames x 64 outputs per workgroup, wave w owns one 32 x 32 block; the K dimension streams through LDS in blocks
-//                 of 64 (activations transposed [k][frame] with asr.hip's bank permutation, the weight block [k][n] as packed at
+//                 of 64 (activations transposed [k][frame] with the bank permutation of f32_tile.hpp, the weight block [k][n] as packed at
 //                 finalize), the next block's global loads in flight under the current block's products.  K blocks come from up to
 //                 three source tensors (mfa: the concatenation is never materialised) or from three taps of one (blocks.0: reflect
 //                 indexing on load).  Epilogues: bias; ReLU + affine; row constant + ReLU + affine + tanh (the pooling's attention).
@@ -23,6 +23,7 @@
 //   sv_asp_pool   per row and channel: softmax over the row's frames (maximum first, expf), weighted mean, two-pass std, asp_bn affine
 //   sv_cosine     one wave per row, a fixed butterfly
 // No atomics.  Workspace contents are irrelevant: every buffer element that is read was written by an earlier kernel of the same call.
+#include "f32_tile.hpp"
 #include "kernels.hpp"
 #include "prof.hpp"
 
@@ -33,16 +34,7 @@ constexpr int S_C = 768, S_BAND = 64, S_NBAND = 12, S_SE = 192, S_ATT = 192, S_M
 constexpr int S_MIN = 6, S_MAXN = 225;
 constexpr float S_ASP_EPS = 1e-12f;
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-// (asr.hip a_at) element (k, frame r) of a transposed activation tile: the 4-frame groups of row k are permuted by k
-__device__ __forceinline__ int s_at(int k, int r) { return k * S_LD + 4 * ((r >> 2) ^ (k & 15)) + (r & 3); }
-
-__device__ __forceinline__ int sv_frames(const int* n_len, int b, int N) {
-    const int n = n_len[b];
-    return n < 0 ? 0 : n > N ? N : n;
-}
 
 // index t (|t - [0, n)| < n) reflected about the row's first and last frame
 __device__ __forceinline__ int reflect(int t, int n) { return t < 0 ? -t : t >= n ? 2 * (n - 1) - t : t; }
@@ -55,7 +47,7 @@ __global__ __launch_bounds__(S_NT) void sv_tdnn_kernel(const float* __restrict__
                                                        const int* __restrict__ n_len, int N, SvTdnnW w,
                                                        const float* __restrict__ crow, float* __restrict__ y, int cout) {
     __shared__ __attribute__((aligned(16))) float aT[S_TM * S_LD], wS[S_LD * S_LD];
-    const int b = blockIdx.z, ob = blockIdx.y, t0 = blockIdx.x * S_TM, n = sv_frames(n_len, b, N);
+    const int b = blockIdx.z, ob = blockIdx.y, t0 = blockIdx.x * S_TM, n = row_len(n_len, b, N);
     if (n < S_MIN || t0 >= n) return;   // (uniform)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int f0 = 32 * (wv >> 1), n0 = 32 * (wv & 1), col = n0 + (lane & 31), rbase = f0 + 4 * (lane >> 5);
@@ -75,7 +67,7 @@ __global__ __launch_bounds__(S_NT) void sv_tdnn_kernel(const float* __restrict__
     }
 #define SV_PUT()                                                                                                             \
     {                                                                                                                        \
-        _Pragma("unroll") for (int i = 0; i < 16; ++i) aT[s_at(lane, wv + 4 * i)] = av[i];                                   \
+        _Pragma("unroll") for (int i = 0; i < 16; ++i) aT[tile_at<S_LD>(lane, wv + 4 * i)] = av[i];                                   \
         _Pragma("unroll") for (int i = 0; i < 4; ++i) reinterpret_cast<f32x4*>(wS)[tid + S_NT * i] = wr[i];                  \
     }
     f32x16 acc;
@@ -89,7 +81,7 @@ __global__ __launch_bounds__(S_NT) void sv_tdnn_kernel(const float* __restrict__
         if (kb + 1 < nkb) SV_FETCH(kb + 1)
 #pragma unroll 8
         for (int k = 0; k < S_LD; k += 2)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aT[s_at(k + h, f0 + r)], wS[(k + h) * S_LD + n0 + r], acc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(aT[tile_at<S_LD>(k + h, f0 + r)], wS[(k + h) * S_LD + n0 + r], acc, 0, 0, 0);
         __syncthreads();
         if (kb + 1 < nkb) SV_PUT()
         __syncthreads();
@@ -120,7 +112,7 @@ __global__ __launch_bounds__(R_NT) void sv_res2net_kernel(const float* __restric
     extern __shared__ __attribute__((aligned(16))) float sv_lds[];
     float* const uT = sv_lds;                    // [64 channels][R_LD frames] (r_at)
     float* const wS = sv_lds + S_BAND * R_LD;    // [192 k = tap * 64 + channel][64 outputs]
-    const int b = blockIdx.x, n = sv_frames(n_len, b, N);
+    const int b = blockIdx.x, n = row_len(n_len, b, N);
     if (n < S_MIN) return;   // (uniform)
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, d = w.dil;
     const float* const xr = x + (long)b * N * S_C;
@@ -177,7 +169,7 @@ __global__ __launch_bounds__(R_NT) void sv_res2net_kernel(const float* __restric
 __global__ __launch_bounds__(S_C) void sv_se_squeeze_kernel(const float* __restrict__ x, const int* __restrict__ n_len, int N,
                                                             SvBlockW w, float* __restrict__ gate) {
     __shared__ float sm[S_C], hs[S_SE];
-    const int b = blockIdx.x, n = sv_frames(n_len, b, N), c = threadIdx.x;
+    const int b = blockIdx.x, n = row_len(n_len, b, N), c = threadIdx.x;
     if (n < S_MIN) return;
     const float* const xr = x + (long)b * N * S_C + c;
     float s = 0.f;
@@ -201,7 +193,7 @@ __global__ __launch_bounds__(S_C) void sv_se_squeeze_kernel(const float* __restr
 __global__ __launch_bounds__(S_NT) void sv_se_apply_kernel(const float* __restrict__ x, const float* __restrict__ res,
                                                            const float* __restrict__ gate, const int* __restrict__ n_len, int N,
                                                            float* __restrict__ y) {
-    const int b = blockIdx.y, n = sv_frames(n_len, b, N);
+    const int b = blockIdx.y, n = row_len(n_len, b, N);
     const int i = blockIdx.x * S_NT + threadIdx.x, f = i / (S_C / 4), c4 = i - f * (S_C / 4);
     if (n < S_MIN || f >= n) return;
     const long at = ((long)b * N + f) * (S_C / 4) + c4;
@@ -213,7 +205,7 @@ __global__ __launch_bounds__(S_NT) void sv_se_apply_kernel(const float* __restri
 // ---- attentive statistics pooling -----------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(S_NT) void sv_asp_stats_kernel(const float* __restrict__ x, const int* __restrict__ n_len, int N,
                                                             float* __restrict__ ms) {
-    const int b = blockIdx.y, n = sv_frames(n_len, b, N), c = blockIdx.x * S_NT + threadIdx.x;
+    const int b = blockIdx.y, n = row_len(n_len, b, N), c = blockIdx.x * S_NT + threadIdx.x;
     if (n < S_MIN) return;
     const float* const xr = x + (long)b * N * S_MFA + c;
     const float wgt = 1.0f / (float)n;
@@ -237,7 +229,7 @@ __global__ __launch_bounds__(V_NT) void sv_rowvec_kernel(const float* __restrict
                                                          const float* __restrict__ bias /* or NULL */, const int* __restrict__ n_len,
                                                          int N, int zero_short, float* __restrict__ out) {
     __shared__ float vs[S_POOL], part[V_SEG][S_EMB];
-    const int b = blockIdx.x, n = sv_frames(n_len, b, N), tid = threadIdx.x, seg = tid / S_EMB, o = tid - seg * S_EMB;
+    const int b = blockIdx.x, n = row_len(n_len, b, N), tid = threadIdx.x, seg = tid / S_EMB, o = tid - seg * S_EMB;
     if (n < S_MIN) {   // (uniform)
         if (zero_short && tid < S_EMB) out[(long)b * S_EMB + tid] = 0.f;
         return;
@@ -256,7 +248,7 @@ __global__ __launch_bounds__(V_NT) void sv_rowvec_kernel(const float* __restrict
 __global__ __launch_bounds__(S_NT) void sv_asp_pool_kernel(const float* __restrict__ lg, const float* __restrict__ x,
                                                            const int* __restrict__ n_len, int N, const float* __restrict__ scale,
                                                            const float* __restrict__ shift, float* __restrict__ pooled) {
-    const int b = blockIdx.y, n = sv_frames(n_len, b, N), c = blockIdx.x * S_NT + threadIdx.x;
+    const int b = blockIdx.y, n = row_len(n_len, b, N), c = blockIdx.x * S_NT + threadIdx.x;
     if (n < S_MIN) return;
     const float* const lr = lg + (long)b * N * S_MFA + c;
     const float* const xr = x + (long)b * N * S_MFA + c;
@@ -298,8 +290,6 @@ __global__ __launch_bounds__(S_NT) void sv_cosine_kernel(const float* __restrict
     }
     if (lane == 0) out[b] = ar / (fmaxf(sqrtf(aa), 1e-8f) * fmaxf(sqrtf(rr), 1e-8f));
 }
-
-inline size_t up256(size_t v) { return (v + 255) & ~size_t(255); }
 
 DevOnce g_sv_once;
 

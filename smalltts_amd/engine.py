@@ -528,24 +528,8 @@ class HipEngine:
         on the device (out: a contiguous fp32 tensor of that shape to write into), 0.0 at and behind frame 4 ns[b]; every row is
         computed as if it were alone.  Needs the recogniser part (load_synthetic(parts=(..., "asr")) or the asr.* tensors).  Launches
         on the current stream, no synchronisation."""
-        if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device or x.shape[2] != LATENT:
-            raise ValueError("asr_logprobs: x must be a contiguous fp32 (B,N,64) tensor on the engine's device")
-        B, N = int(x.shape[0]), int(x.shape[1])
-        if not (1 <= B <= ASR_MAX_ROWS and 1 <= N <= ALIGN_MAX_FRAMES):
-            raise ValueError(f"asr_logprobs: B = {B}, N = {N} outside the supported range B <= {ASR_MAX_ROWS}, N <= {ALIGN_MAX_FRAMES}")
-        if len(ns) != B:
-            raise ValueError("asr_logprobs: one frame count per row")
-        if not self.has("asr"):
-            raise ValueError("asr_logprobs: this engine holds no recogniser part")
-        want = (B, ASR_UPSAMPLE * N, ASR_CLASSES)
-        if out is None:
-            out = torch.empty(want, device=self.device)
-        elif out.dtype != torch.float32 or tuple(out.shape) != want or not out.is_contiguous() or out.device != self.device:
-            raise ValueError(f"asr_logprobs: out must be a contiguous fp32 {want} tensor on the engine's device")
-        tab = self._upload_i32([ns])
-        ws = self._workspace(self.lib.smtts_asr_workspace_bytes(self.h, B, N))
-        self._ck(self.lib.smtts_asr_logprobs(self.h, self._stream(), _p(x), _p(tab[0]), B, N, _p(ws), ws.numel(), _p(out)), "asr_logprobs")
-        return out
+        return self._score_latents("asr_logprobs", "asr", "recogniser", x, ns, out, ASR_MAX_ROWS, 1, f"N <= {ALIGN_MAX_FRAMES}",
+                                   lambda B, N: (B, ASR_UPSAMPLE * N, ASR_CLASSES))
 
     def sv_embed(self, x: torch.Tensor, ns, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Speaker embedding of every row of latents (smtts_sv_embed; the definition: include/smalltts_hip.h).  x fp32
@@ -553,24 +537,28 @@ class HipEngine:
         device (out: a contiguous fp32 tensor of that shape to write into), not normalised; every row is computed as if it were alone,
         and a row under 6 frames has no embedding: its row is 0.0.  Needs the verifier part (load_synthetic(parts=(..., "sv")) or the
         sv.* tensors).  Launches on the current stream, no synchronisation."""
+        return self._score_latents("sv_embed", "sv", "verifier", x, ns, out, SV_MAX_ROWS, SV_MIN_FRAMES,
+                                   f"{SV_MIN_FRAMES} <= N <= {ALIGN_MAX_FRAMES}", lambda B, N: (B, SV_DIM))
+
+    def _score_latents(self, entry, part, part_name, x, ns, out, max_rows, min_frames, n_range, shape_of):
+        """asr_logprobs / sv_embed: the operand checks, the result, the frame table and the workspace of smtts_<entry>."""
         if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device or x.shape[2] != LATENT:
-            raise ValueError("sv_embed: x must be a contiguous fp32 (B,N,64) tensor on the engine's device")
+            raise ValueError(f"{entry}: x must be a contiguous fp32 (B,N,64) tensor on the engine's device")
         B, N = int(x.shape[0]), int(x.shape[1])
-        if not (1 <= B <= SV_MAX_ROWS and SV_MIN_FRAMES <= N <= ALIGN_MAX_FRAMES):
-            raise ValueError(f"sv_embed: B = {B}, N = {N} outside the supported range B <= {SV_MAX_ROWS}, "
-                             f"{SV_MIN_FRAMES} <= N <= {ALIGN_MAX_FRAMES}")
+        if not (1 <= B <= max_rows and min_frames <= N <= ALIGN_MAX_FRAMES):
+            raise ValueError(f"{entry}: B = {B}, N = {N} outside the supported range B <= {max_rows}, {n_range}")
         if len(ns) != B:
-            raise ValueError("sv_embed: one frame count per row")
-        if not self.has("sv"):
-            raise ValueError("sv_embed: this engine holds no verifier part")
-        want = (B, SV_DIM)
+            raise ValueError(f"{entry}: one frame count per row")
+        if not self.has(part):
+            raise ValueError(f"{entry}: this engine holds no {part_name} part")
+        want = shape_of(B, N)
         if out is None:
             out = torch.empty(want, device=self.device)
         elif out.dtype != torch.float32 or tuple(out.shape) != want or not out.is_contiguous() or out.device != self.device:
-            raise ValueError(f"sv_embed: out must be a contiguous fp32 {want} tensor on the engine's device")
+            raise ValueError(f"{entry}: out must be a contiguous fp32 {want} tensor on the engine's device")
         tab = self._upload_i32([ns])
-        ws = self._workspace(self.lib.smtts_sv_workspace_bytes(self.h, B, N))
-        self._ck(self.lib.smtts_sv_embed(self.h, self._stream(), _p(x), _p(tab[0]), B, N, _p(ws), ws.numel(), _p(out)), "sv_embed")
+        ws = self._workspace(getattr(self.lib, f"smtts_{part}_workspace_bytes")(self.h, B, N))
+        self._ck(getattr(self.lib, f"smtts_{entry}")(self.h, self._stream(), _p(x), _p(tab[0]), B, N, _p(ws), ws.numel(), _p(out)), entry)
         return out
 
     def sv_cosine(self, emb: torch.Tensor, ref: torch.Tensor, K: int = 1) -> torch.Tensor:

@@ -1,7 +1,7 @@
 // Enqueue recorder (tests/test_enqueue_table_cpu.py): the WHOLE library — engine and C ABI included — linked against the recording
-// stand-ins of hip_record.hpp.  No GPU is opened.  The program drives the C ABI of include/smalltts_hip.h only: it registers the DiT
-// weight inventory it is handed (argv[1]: one "name dim dim ..." line per tensor) with smtts_synth_tensor, finalizes, and makes the
-// operator calls below under both tunings and the f16 / bf16x3 presets.  Each call prints a header line "== <call>", then one line per
+// stand-ins of hip_record.hpp.  No GPU is opened.  The program drives the C ABI of include/smalltts_hip.h only: it registers the weight
+// inventories it is handed (argv[1]: the DiT, argv[2]: a small codec, the recogniser and the verifier; one "name dim dim ..." line per
+// tensor) with smtts_synth_tensor, finalizes, and makes the operator calls below under both tunings and the f16 / bf16x3 presets.  Each call prints a header line "== <call>", then one line per
 // runtime call the operator made while it was being enqueued — the stream (main, main2: the caller's; side<k>: the engine's, in order of
 // creation), then a kernel launch as launch_record prints it, "memset <bytes>", "memcpy <bytes> <kind>", "record ev<k>", "wait ev<k>";
 // "create side<k>" / "create ev<k>" stand alone — then "rc=<code>" and, if non-zero, the error string.  No pointers, no workspace
@@ -64,11 +64,13 @@ struct Bufs {   // sized for 3B rows (cfg) and N = NMAX
     }
 };
 
-static int load_weights(const char* path) {
+// the codec of the second inventory: n_filters = 8, depth 1 everywhere (decoder channels 512 .. 8: every codec path)
+static const int kRatios[6] = {8, 5, 5, 4, 2, 2}, kDepths[7] = {1, 1, 1, 1, 1, 1, 1}, kHop = 3200;
+
+static int load_weights(const char* path, uint64_t key) {
     std::ifstream in(path);
     if (!in) { fprintf(stderr, "enqueue_record: cannot read %s\n", path); return 1; }
     std::string line;
-    uint64_t key = 0;
     while (std::getline(in, line)) {
         std::istringstream ls(line);
         std::string name;
@@ -77,7 +79,7 @@ static int load_weights(const char* path) {
         for (int64_t d; ls >> d;) shape.push_back(d);
         if (smtts_synth_tensor(H, name.c_str(), shape.data(), (int)shape.size(), ++key, 0.f, 0.05f)) return 1;
     }
-    return smtts_finalize(H);
+    return 0;
 }
 
 static void operators(const Bufs& b, const std::string& cfgname) {
@@ -162,14 +164,58 @@ static void operators(const Bufs& b, const std::string& cfgname) {
                                             d.rope ? b.rope : nullptr, b.big[0], b.big[1], b.v, b.big[2], b.big[3], b.big[4], b.mod_out);
             });
         }
+
+    // ---- 11. the codec: decode, encode, two consecutive streamed chunks on two slots, one stage of each half through the hook
+    {
+        float* const lat = dev<float>((size_t)B * 3 * 64);
+        float* const audio = dev<float>((size_t)B * 3 * kHop);
+        size_t n = smtts_decode_workspace_bytes(H, B, 3);
+        ws = dev<char>(n);
+        call(tag("codec_decode B2 T3"), [&] { return smtts_codec_decode(H, nullptr, lat, B, 3, audio, ws, n); });
+        n = smtts_encode_workspace_bytes(H, B, kHop);
+        ws = dev<char>(n);
+        call(tag("codec_encode B2 one hop"), [&] { return smtts_codec_encode(H, nullptr, audio, B, kHop, lat, ws, n); });
+        n = smtts_decode_stream_workspace_bytes(H, B, 2);
+        ws = dev<char>(n);
+        void* const pool = dev<char>(2 * smtts_decode_state_bytes(H));
+        int64_t* const slots = dev<int64_t>(B);
+        for (int chunk = 0; chunk < 2; ++chunk)
+            call(tag(std::string("codec_decode_stream B2 T2 chunk") + char('0' + chunk)),
+                 [&] { return smtts_codec_decode_stream(H, nullptr, lat, B, 2, pool, 2, slots, audio, ws, n); });
+        // decoder stage 1 (C 512 -> 256, ratio 8) on 3 frames; encoder stage 6 (C 256 -> 512, stride 8) on 8: each one frame of the latent
+        float* const sin_ = dev<float>((size_t)B * 8 * 512);
+        float* const sout = dev<float>((size_t)B * 24 * 512);
+        call(tag("test_codec_stage decoder stage1 what6 T3"), [&] { return smtts_test_codec_stage(H, nullptr, 1, 1, 2 | 4, sin_, B, 3, 512, sout, nullptr, nullptr); });
+        call(tag("test_codec_stage encoder stage6 what6 T8"), [&] { return smtts_test_codec_stage(H, nullptr, 2, 6, 2 | 4, sin_, B, 8, 256, sout, nullptr, nullptr); });
+    }
+
+    // ---- 12. the scorers: the recogniser, the verifier at its smallest N and at two frame tiles, one call of each a byte short
+    {
+        float* const x = dev<float>((size_t)B * 70 * 64);
+        int32_t* const n_len = dev<int32_t>(B);
+        float* const logp = dev<float>((size_t)B * 4 * 5 * 198);
+        float* const emb = dev<float>((size_t)B * 192);
+        size_t n = smtts_asr_workspace_bytes(H, B, 5);
+        ws = dev<char>(n);
+        call(tag("asr_logprobs B2 N5"), [&] { return smtts_asr_logprobs(H, nullptr, x, n_len, B, 5, ws, n, logp); });
+        call(tag("asr_logprobs B2 N5 workspace one byte short"), [&] { return smtts_asr_logprobs(H, nullptr, x, n_len, B, 5, ws, n - 1, logp); });
+        for (int N : {6, 70}) {
+            n = smtts_sv_workspace_bytes(H, B, N);
+            ws = dev<char>(n);
+            call(tag("sv_embed B2 N" + std::to_string(N)), [&] { return smtts_sv_embed(H, nullptr, x, n_len, B, N, ws, n, emb); });
+        }
+        call(tag("sv_embed B2 N70 workspace one byte short"), [&] { return smtts_sv_embed(H, nullptr, x, n_len, B, 70, ws, n - 1, emb); });
+    }
 }
 
 int main(int argc, char** argv) {
-    if (argc < 2) { fprintf(stderr, "usage: enqueue_record <weight inventory>\n"); return 2; }
+    if (argc < 3) { fprintf(stderr, "usage: enqueue_record <DiT inventory> <codec, asr and sv inventory>\n"); return 2; }
     const Bufs b;
     for (int tuning = 0; tuning < 2; ++tuning)
         for (int preset : {2, 3}) {
-            if (smtts_create(0, &H) || smtts_set_precision(H, preset) || smtts_set_tuning(H, tuning) || load_weights(argv[1])) {
+            if (smtts_create(0, &H) || smtts_set_precision(H, preset) || smtts_set_tuning(H, tuning) ||
+                smtts_set_codec_spec(H, 64, 8, 7, 4, 1e-5f, kRatios, 6, kDepths) || load_weights(argv[1], 0) || load_weights(argv[2], 1u << 20) ||
+                smtts_finalize(H)) {
                 fprintf(stderr, "enqueue_record: setup failed: %s\n", smtts_last_error(H));
                 return 1;
             }

@@ -119,6 +119,12 @@ hipError_t hipMemset(void* dst, int, size_t bytes) { rec_memset(dst, bytes, null
 hipError_t hipMemsetAsync(void* dst, int, size_t bytes, hipStream_t st) { rec_memset(dst, bytes, st); return hipSuccess; }
 hipError_t hipMemcpy(void* dst, const void*, size_t bytes, hipMemcpyKind kind) { rec_memcpy(dst, bytes, kind, nullptr); return hipSuccess; }
 hipError_t hipMemcpyAsync(void* dst, const void*, size_t bytes, hipMemcpyKind kind, hipStream_t st) { rec_memcpy(dst, bytes, kind, st); return hipSuccess; }
+// (the codec's image copies, device to device only: rows of `width` bytes, `height` of them; the pitches belong to the layout)
+hipError_t hipMemcpy2DAsync(void*, size_t, const void*, size_t, size_t width, size_t height, hipMemcpyKind kind, hipStream_t st) {
+    if (kind != hipMemcpyDeviceToDevice) return hipErrorInvalidValue;
+    if (g_rec_on) printf("%s memcpy2d %zux%zu d2d\n", rec_name(st), width, height);
+    return hipSuccess;
+}
 
 // streams and events
 hipError_t hipStreamCreateWithFlags(hipStream_t* st, unsigned) {

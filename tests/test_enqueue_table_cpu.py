@@ -1,14 +1,16 @@
 """What an engine call enqueues, held on the CPU: tests/host/enqueue_record.hip links the whole library (engine and C ABI included)
-against recording stand-ins for the HIP runtime (tests/host/hip_record.hpp), registers the DiT inventory written here, and makes the
-operator calls of its list under both tunings and two presets: the condition encoder with and without its fork, denoise_step with and
-without a caller rope table, the samplers (plain, on a second caller stream, N = 8, CFG, tap, pins, refused calls followed by a plain
-one) and the DiT / encoder stage hook.  Every kernel launch, memset, copy, event record / wait and stream / event creation is one line,
+against recording stand-ins for the HIP runtime (tests/host/hip_record.hpp), registers the inventories written here (the DiT; a small
+codec, the recogniser and the verifier), and makes the operator calls of its list under both tunings and two presets: the condition
+encoder with and without its fork, denoise_step with and without a caller rope table, the samplers (plain, on a second caller stream,
+N = 8, CFG, tap, pins, refused calls followed by a plain one), the DiT / encoder stage hook, the codec (decode, encode, two streamed
+chunks, one stage of each half through its hook) and the two scorers (with one refused call each).  Every kernel launch, memset, copy, event record / wait and stream / event creation is one line,
 with the stream it went to.  The lines must equal tests/golden/enqueue_table.txt.gz, recorded at the commit its first line names."""
 import gzip
 import os
 import subprocess
 
-from smalltts_amd.weights import dit_param_specs
+from smalltts_amd.weights import (CodecSpec, asr_param_specs, codec_decoder_param_specs, codec_encoder_param_specs, dit_param_specs,
+                                  sv_param_specs)
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 CSRC = os.path.join(ROOT, "smalltts_amd", "csrc")
@@ -25,12 +27,26 @@ def _sections(lines):
     return out
 
 
+def _inventory(specs):
+    return "".join(name + "".join(f" {d}" for d in shape) + "\n" for name, shape in specs)
+
+
+# the codec, recogniser and verifier sections of every configuration; the refused ones enqueue nothing
+PARTS_OK = ("codec_decode B2 T3", "codec_encode B2 one hop", "codec_decode_stream B2 T2 chunk0", "codec_decode_stream B2 T2 chunk1",
+            "test_codec_stage decoder stage1 what6 T3", "test_codec_stage encoder stage6 what6 T8", "asr_logprobs B2 N5", "sv_embed B2 N6",
+            "sv_embed B2 N70")
+PARTS_REFUSED = ("asr_logprobs B2 N5 workspace one byte short", "sv_embed B2 N70 workspace one byte short")
+
+
 def test_every_engine_call_enqueues_the_recorded_sequence(tmp_path):
     jobs = str(min(8, os.cpu_count() or 1))
     subprocess.run(["make", "-C", CSRC, "-j", jobs, "enqueue_record"], check=True, stdout=subprocess.DEVNULL)
     inventory = tmp_path / "dit_inventory.txt"
-    inventory.write_text("".join(name + "".join(f" {d}" for d in shape) + "\n" for name, shape in dit_param_specs()))
-    got = subprocess.run([os.path.join(CSRC, "build", "enqueue_record"), str(inventory)], check=True, capture_output=True,
+    inventory.write_text(_inventory(dit_param_specs()))
+    spec = CodecSpec(n_filters=8, ratios=(8, 5, 5, 4, 2, 2), dec_depths=(1, 1, 1, 1, 1, 1, 1))   # (the recorder hands the engine the same)
+    parts = tmp_path / "parts_inventory.txt"
+    parts.write_text(_inventory(codec_decoder_param_specs(spec) + codec_encoder_param_specs(spec) + asr_param_specs() + sv_param_specs()))
+    got = subprocess.run([os.path.join(CSRC, "build", "enqueue_record"), str(inventory), str(parts)], check=True, capture_output=True,
                          text=True).stdout.splitlines()
     with gzip.open(os.path.join(ROOT, "tests", "golden", "enqueue_table.txt.gz"), "rt") as f:
         head, *want = f.read().splitlines()
@@ -49,6 +65,8 @@ def test_every_engine_call_enqueues_the_recorded_sequence(tmp_path):
         assert len(n9) - len(n8) == (2 if cfg.endswith("bf16x3") else 1)   # pad8(N) != N: the V^T memset(s), once per call
         assert sum(" attn_text_mass" in l for l in body[f"== sample_align steps 10 layers a02 heads 24 [{cfg}]"]) == 3
         assert sum(" cfg_combine" in l for l in body[f"== sample mode1 cfg1 N9 [{cfg}]"]) == 2
+        assert all(len(body[f"== {p} [{cfg}]"]) > 1 and body[f"== {p} [{cfg}]"][-1] == "rc=0" for p in PARTS_OK)
+        assert all(len(body[f"== {p} [{cfg}]"]) == 1 and body[f"== {p} [{cfg}]"][0].startswith("rc=1 ") for p in PARTS_REFUSED)
     lat = {h: b for h, b in _sections(want) if h.endswith("[latency f16]")}
     assert lat["== cond_encode B2 R3 P5 [latency f16]"][:5] == ["create side0", "create ev0", "create ev1", "main record ev0", "side0 wait ev0"]
     assert not any(l.startswith(("side", "create")) for l in lat["== cond_encode B2 R3 P0 [latency f16]"])
