@@ -20,6 +20,18 @@ vp, i32, i64, u64, f32, sz = C.c_void_p, C.c_int, C.c_int64, C.c_uint64, C.c_flo
 u32 = C.c_uint32
 cstr = C.c_char_p
 
+# the codes of include/smalltts_hip.h that the host side passes by name (engine.py, engine_hooks.py)
+ACT = {"none": 0, "silu": 1, "gelu": 2, "mish": 3}
+PRECISION = {"bf16x3": 3, "f16": 2, "bf16": 1,   # presets of smtts_set_precision
+             "f16x2": 4}                          # site value only (codec_conv): fp16 activations x fp16 hi + lo weights, two MFMA passes
+PRESETS = ("bf16x3", "f16", "bf16")              # what set_precision accepts in front of the site overrides
+SITES = {"dit_block": 0, "encoder": 1, "cross_kv": 2, "cond": 3, "codec_ffn": 4, "codec_conv": 5, "convpos": 6, "attn": 7}
+
+
+def ptr(t):
+    """A tensor (or None) as the void * the C ABI takes."""
+    return None if t is None else C.c_void_p(t.data_ptr())
+
 # name -> (restype, argtypes); kept in sync with include/smalltts_hip.h (tests/test_cabi.py checks it)
 SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_create": (i32, [i32, C.POINTER(vp)]),

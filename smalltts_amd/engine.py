@@ -6,32 +6,25 @@ C ABI of libsmalltts_hip.so (include/smalltts_hip.h).  One HipEngine per GPU.
 from __future__ import annotations
 
 import ctypes as C
+import os
 from typing import Dict, Iterable, Optional
 
 import numpy as np
 import torch
 
 from . import _lib
+from ._lib import ACT, PRECISION, PRESETS, SITES, ptr as _p   # noqa: F401  (the codes stay importable from here)
+from .engine_hooks import EngineHooks
+from .operands import (ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS, distinct_slots, fade_len, frames_tokens, is_operand, out_1d, per_row,
+                       pool_slots, row_lengths, seg_gain, upload)
 from .weights import (DEFAULT_CODEC, CodecSpec, asr_param_specs, codec_decoder_param_specs, codec_encoder_param_specs,
                       dit_param_specs, init_rule, sv_param_specs, tensor_key)
 
 N_LAYERS, N_HEADS, HEAD_DIM, LATENT = 12, 8, 120, 64
-ACT = {"none": 0, "silu": 1, "gelu": 2, "mish": 3}
-PRECISION = {"bf16x3": 3, "f16": 2, "bf16": 1,   # presets of smtts_set_precision (include/smalltts_hip.h)
-             "f16x2": 4}                          # site value only (codec_conv): fp16 activations x fp16 hi + lo weights, two MFMA passes
-PRESETS = ("bf16x3", "f16", "bf16")              # what set_precision accepts in front of the site overrides
-SITES = {"dit_block": 0, "encoder": 1, "cross_kv": 2, "cond": 3, "codec_ffn": 4, "codec_conv": 5, "convpos": 6, "attn": 7}
 DEFAULT_PRECISION = "f16"
-
-
-ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS = 225, 198   # smtts_align_path: 30 s of codec frames, the phoneme window
 ASR_MAX_ROWS, ASR_UPSAMPLE, ASR_CLASSES = 64, 4, 198   # smtts_asr_logprobs: rows per call, frames per latent frame, phoneme classes
 CTC_ALIGN_MAX_FRAMES = 1024                            # smtts_ctc_align: frames of logp per row (its move table lives in LDS)
 SV_MAX_ROWS, SV_MIN_FRAMES, SV_DIM = 64, 6, 192       # smtts_sv_embed: rows per call, the shortest row with an embedding, its width
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else C.c_void_p(t.data_ptr())
 
 
 def _index_mask(sel, n: int, what: str) -> int:
@@ -69,7 +62,7 @@ def tap_selection(align, num_steps: int):
     return flags, _index_mask(layers, N_LAYERS, "layers"), _index_mask(heads, N_HEADS, "heads")
 
 
-class HipEngine:
+class HipEngine(EngineHooks):
     def __init__(self, device: int = 0, precision: str = DEFAULT_PRECISION):
         if not torch.cuda.is_available():
             raise RuntimeError("HipEngine needs a ROCm GPU (torch.cuda.is_available() is False)")
@@ -87,6 +80,8 @@ class HipEngine:
         self._banks: Dict[tuple, tuple] = {}   # (down, up) -> (polyphase bank on the device, width)
         self._demoted: Dict[str, str] = {}     # site -> why: sites the fp16 range guard moved to split-bf16 (sticky across set_precision)
         self.calibration: Optional[Dict[str, object]] = None   # last calibrate() report on the loaded weights
+        self.dual_stream = os.environ.get("SMTTS_SINGLE_STREAM", "") != "1"   # what the library starts with (set_dual_stream)
+        self.tuning, self.ln_fold, self._profiling = "latency", True, False
         self.set_precision(precision)
 
     # ---- plumbing ------------------------------------------------------------------------------
@@ -111,7 +106,7 @@ class HipEngine:
     def use_workspace(self, slot: Optional[str]):
         """Select a named scratch buffer for subsequent calls (ops running concurrently on different streams must
         not share scratch). None = the default buffer."""
-        if slot is not None and getattr(self, "_profiling", False):
+        if slot is not None and self._profiling:
             raise RuntimeError("per-kernel profiling is on: it pairs HIP events around every launch and assumes ONE call at a "
                                "time — no batches in flight (include/smalltts_hip.h, threading rule 3)")
         self._ws_slot = slot
@@ -132,30 +127,30 @@ class HipEngine:
             t = torch.from_numpy(t)
         return t.to(device=self.device, dtype=dtype).contiguous()
 
+    def _is(self, t, dtype, *shape, aligned: bool = False) -> bool:
+        """t is a contiguous `dtype` tensor of `shape` (None: any extent; no shape: any rank) on the engine's device."""
+        return is_operand(t, dtype, shape or None, self.device, aligned)
+
+    def _upload_i32(self, rows) -> torch.Tensor:
+        """Rows of host integers -> device int32 on the current stream (operands.upload)."""
+        return upload([[int(v) for v in r] for r in rows], np.int32, self.device)
+
+    def _upload_i64(self, rows) -> torch.Tensor:
+        return upload(rows, np.int64, self.device)
+
     def set_dual_stream(self, on: bool) -> bool:
         """Text encoder of cond_encode on the engine's side stream (default unless SMTTS_SINGLE_STREAM=1) or inline on the
         caller's stream.  Returns the previous setting so that callers can restore it."""
-        prev = getattr(self, "dual_stream", None)
-        if prev is None:
-            import os
-            prev = os.environ.get("SMTTS_SINGLE_STREAM", "") != "1"
+        prev = self.dual_stream
         self._ck(self.lib.smtts_set_dual_stream(self.h, int(bool(on))), "set_dual_stream")
         self.dual_stream = bool(on)
         return prev
 
     def set_tuning(self, mode: str) -> str:
         """"latency" (default) or "throughput" (several batches in flight on the caller's streams); returns the previous mode."""
-        prev = getattr(self, "tuning", "latency")
+        prev = self.tuning
         self._ck(self.lib.smtts_set_tuning(self.h, {"latency": 0, "throughput": 1}[mode]), "set_tuning")
         self.tuning = mode
-        return prev
-
-    def set_ln_fold(self, on: bool) -> bool:
-        """Test hook: the fused sampler's AdaLN between two DiT block GEMMs folded into their epilogues (default) or as separate
-        split-K reduce / ln_modulate launches.  Returns the previous setting."""
-        prev = getattr(self, "ln_fold", True)
-        self._ck(self.lib.smtts_test_set_ln_fold(self.h, int(bool(on))), "test_set_ln_fold")
-        self.ln_fold = bool(on)
         return prev
 
     def release_workspaces(self):
@@ -471,51 +466,43 @@ class HipEngine:
         if return_steps:   # a late start writes the slots from start_step on only: the others are zeros
             steps = (torch.zeros if pinned and start_step > 0 else torch.empty)(num_steps, B, N, LATENT, device=self.device)
         ws = self._workspace(self.lib.smtts_sample_workspace_bytes(self.h, B, N, R, P, num_steps, int(cfg)))
+        tap = align is not None and align is not False
+        flags, layers, heads = tap_selection(align, num_steps) if tap else (None, 0, 0)
+        if tap and P < 1:
+            raise ValueError("sample: align= needs text keys (P >= 1)")
+        mass = torch.empty(B, N, P, device=self.device) if tap else None
+        # what the three entries share; smtts_sample_align appends the tap, smtts_sample_pinned the tap (or none) and the pins
+        head = (self.h, self._stream(), 0 if pinned else {"dmd": 0, "ode": 1}[mode], num_steps, 0 if pinned else int(cfg), s_text, s_spk,
+                _p(mask_in), _p(cache["k_ref"]), _p(cache["v_ref"]), _p(cache["ref_mask"]), _p(cache["k_text"]), _p(cache["v_text"]),
+                _p(cache["ph_mask"]), B, N, R, P, _p(noise), C.c_uint64(seed), _p(x), _p(steps), _p(ws), ws.numel())
+        tap_args = (C.cast(flags, C.c_void_p) if tap else None, layers, heads, _p(mass))
         if pinned:
-            tap = align is not None and align is not False
-            flags, layers, heads = tap_selection(align, num_steps) if tap else (None, 0, 0)
-            if tap and P < 1:
-                raise ValueError("sample: align= needs text keys (P >= 1)")
-            mass = torch.empty(B, N, P, device=self.device) if tap else None
-            self._ck(self.lib.smtts_sample_pinned(self.h, self._stream(), 0, num_steps, 0, s_text, s_spk, _p(mask_in), _p(cache["k_ref"]),
-                                                  _p(cache["v_ref"]), _p(cache["ref_mask"]), _p(cache["k_text"]), _p(cache["v_text"]),
-                                                  _p(cache["ph_mask"]), B, N, R, P, _p(noise), C.c_uint64(seed), _p(x), _p(steps),
-                                                  _p(ws), ws.numel(), C.cast(flags, C.c_void_p) if tap else None, layers, heads, _p(mass),
-                                                  _p(x_pin), _p(pin), start_step), "sample_pinned")
-            res = (x,) + ((steps,) if return_steps else ()) + ((mass,) if tap else ())
-            return res if len(res) > 1 else x
-        if align is not None and align is not False:
-            flags, layers, heads = tap_selection(align, num_steps)
-            if P < 1:
-                raise ValueError("sample: align= needs text keys (P >= 1)")
-            mass = torch.empty(B, N, P, device=self.device)
-            self._ck(self.lib.smtts_sample_align(self.h, self._stream(), {"dmd": 0, "ode": 1}[mode], num_steps, int(cfg), s_text,
-                                                 s_spk, _p(mask_in), _p(cache["k_ref"]), _p(cache["v_ref"]),
-                                                 _p(cache["ref_mask"]), _p(cache["k_text"]), _p(cache["v_text"]),
-                                                 _p(cache["ph_mask"]), B, N, R, P, _p(noise), C.c_uint64(seed), _p(x), _p(steps),
-                                                 _p(ws), ws.numel(), C.cast(flags, C.c_void_p), layers, heads, _p(mass)), "sample_align")
-            return (x, steps, mass) if return_steps else (x, mass)
-        self._ck(self.lib.smtts_sample(self.h, self._stream(), {"dmd": 0, "ode": 1}[mode], num_steps, int(cfg), s_text,
-                                       s_spk, _p(mask_in), _p(cache["k_ref"]), _p(cache["v_ref"]),
-                                       _p(cache["ref_mask"]), _p(cache["k_text"]), _p(cache["v_text"]),
-                                       _p(cache["ph_mask"]), B, N, R, P, _p(noise), C.c_uint64(seed), _p(x), _p(steps),
-                                       _p(ws), ws.numel()), "sample")
-        return (x, steps) if return_steps else x
+            self._ck(self.lib.smtts_sample_pinned(*head, *tap_args, _p(x_pin), _p(pin), start_step), "sample_pinned")
+        elif tap:
+            self._ck(self.lib.smtts_sample_align(*head, *tap_args), "sample_align")
+        else:
+            self._ck(self.lib.smtts_sample(*head), "sample")
+        res = (x,) + ((steps,) if return_steps else ()) + ((mass,) if tap else ())
+        return res if len(res) > 1 else x
+
+    def _mass_front(self, what, mass, *spans):
+        """align_path / take_scores / repair_plan: mass fp32 (B,N,P) in the kernels' N / P range and, where given, its spans -> B, N, P."""
+        if not self._is(mass, torch.float32, None, None, None):
+            raise ValueError(f"{what}: mass must be a contiguous fp32 (B,N,P) tensor on the engine's device")
+        B, N, P = (int(v) for v in mass.shape)
+        frames_tokens(what, N, P)
+        if spans and not self._is(spans[0], torch.int32, B, P, 2):
+            raise ValueError(f"{what}: spans must be a contiguous int32 ({B},{P},2) tensor on the engine's device")
+        return B, N, P
 
     def align_path(self, mass: torch.Tensor, ns, p0, p1):
         """Monotone alignment of a text-mass buffer on the device (smtts_align_path; the definition: include/smalltts_hip.h).
         mass fp32 (B,N,P) contiguous on the device, N <= 225, P <= 198; ns frames per row, [p0[b], p1[b]) the tokens the audio
         speaks (host integers).  -> (spans int32 (B,P,2) = (first, last) frame per token, (-1,-1) outside the path; score fp32 (B)),
         both on the device.  One launch on the current stream, no synchronisation."""
-        if mass.dim() != 3 or mass.dtype != torch.float32 or not mass.is_contiguous() or mass.device != self.device:
-            raise ValueError("align_path: mass must be a contiguous fp32 (B,N,P) tensor on the engine's device")
-        B, N, P = (int(v) for v in mass.shape)
-        if not (1 <= N <= ALIGN_MAX_FRAMES and 1 <= P <= ALIGN_MAX_TOKENS):
-            raise ValueError(f"align_path: N = {N}, P = {P} outside the supported range N <= {ALIGN_MAX_FRAMES}, P <= {ALIGN_MAX_TOKENS}")
-        if B < 1 or len(ns) != B or len(p0) != B or len(p1) != B:
-            raise ValueError("align_path: one frame count and one token range per row")
-        tab = torch.from_numpy(np.ascontiguousarray([[int(v) for v in ns], [int(v) for v in p0], [int(v) for v in p1]], dtype=np.int32))
-        tab = tab.pin_memory().to(self.device, non_blocking=True)
+        B, N, P = self._mass_front("align_path", mass)
+        per_row("align_path", B, ns, p0, p1)
+        tab = self._upload_i32([ns, p0, p1])
         spans = torch.empty(B, P, 2, dtype=torch.int32, device=self.device)
         score = torch.empty(B, device=self.device)
         self._ck(self.lib.smtts_align_path(self.h, self._stream(), _p(mass), B, N, P, _p(tab[0]), _p(tab[1]), _p(tab[2]), _p(spans),
@@ -542,19 +529,18 @@ class HipEngine:
 
     def _score_latents(self, entry, part, part_name, x, ns, out, max_rows, min_frames, n_range, shape_of):
         """asr_logprobs / sv_embed: the operand checks, the result, the frame table and the workspace of smtts_<entry>."""
-        if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device or x.shape[2] != LATENT:
+        if not self._is(x, torch.float32, None, None, LATENT):
             raise ValueError(f"{entry}: x must be a contiguous fp32 (B,N,64) tensor on the engine's device")
         B, N = int(x.shape[0]), int(x.shape[1])
         if not (1 <= B <= max_rows and min_frames <= N <= ALIGN_MAX_FRAMES):
             raise ValueError(f"{entry}: B = {B}, N = {N} outside the supported range B <= {max_rows}, {n_range}")
-        if len(ns) != B:
-            raise ValueError(f"{entry}: one frame count per row")
+        per_row(entry, B, ns)
         if not self.has(part):
             raise ValueError(f"{entry}: this engine holds no {part_name} part")
         want = shape_of(B, N)
         if out is None:
             out = torch.empty(want, device=self.device)
-        elif out.dtype != torch.float32 or tuple(out.shape) != want or not out.is_contiguous() or out.device != self.device:
+        elif not self._is(out, torch.float32, *want):
             raise ValueError(f"{entry}: out must be a contiguous fp32 {want} tensor on the engine's device")
         tab = self._upload_i32([ns])
         ws = self._workspace(getattr(self.lib, f"smtts_{part}_workspace_bytes")(self.h, B, N))
@@ -566,7 +552,7 @@ class HipEngine:
         contiguous on the device, 1 <= K <= 16, D <= 1024.  -> cos fp32 (B) on the device, F.cosine_similarity's rule (each norm clamped
         at 1e-8: a zero row gives 0).  Needs no weights.  One launch on the current stream, no synchronisation."""
         for name, t in (("emb", emb), ("ref", ref)):
-            if t.dim() != 2 or t.dtype != torch.float32 or not t.is_contiguous() or t.device != self.device:
+            if not self._is(t, torch.float32, None, None):
                 raise ValueError(f"sv_cosine: {name} must be a contiguous fp32 2-d tensor on the engine's device")
         B, D = int(emb.shape[0]), int(emb.shape[1])
         K = int(K)
@@ -578,22 +564,26 @@ class HipEngine:
         self._ck(self.lib.smtts_sv_cosine(self.h, self._stream(), _p(emb), _p(ref), B, K, D, _p(cos)), "sv_cosine")
         return cos
 
+    def _ctc_front(self, what, logp, ts, tokens, p0, p1, t_max):
+        """ctc_score / ctc_align: the operand checks (t_max: the most frames, None for no limit) -> (B, T, P, C, the uploaded table)."""
+        if not self._is(logp, torch.float32, None, None, None):
+            raise ValueError(f"{what}: logp must be a contiguous fp32 (B,T,C) tensor on the engine's device")
+        B, T, Cn = (int(v) for v in logp.shape)
+        if not self._is(tokens, torch.int32, B, None):
+            raise ValueError(f"{what}: tokens must be a contiguous int32 ({B},P) tensor on the engine's device")
+        P = int(tokens.shape[1])
+        if not (1 <= T <= (t_max or T) and 1 <= P <= ALIGN_MAX_TOKENS and 2 <= Cn <= 256):
+            raise ValueError(f"{what}: T = {T}, P = {P}, C = {Cn} outside the supported range "
+                             f"{f'1 <= T <= {t_max}' if t_max else 'T >= 1'}, P <= {ALIGN_MAX_TOKENS}, 2 <= C <= 256")
+        per_row(what, B, ts, p0, p1)
+        return B, T, P, Cn, self._upload_i32([ts, p0, p1])
+
     def ctc_score(self, logp: torch.Tensor, ts, tokens: torch.Tensor, p0, p1) -> torch.Tensor:
         """CTC negative log-likelihood of every row (smtts_ctc_score; the definition: include/smalltts_hip.h).  logp fp32
         (B,T,C) and tokens int32 (B,P), contiguous on the device, P <= 198, C <= 256; ts the frames per row, [p0[b], p1[b]) the
         target tokens of row b (host integers).  -> nll fp32 (B) on the device: F.ctc_loss(blank=0, reduction='none'), +inf for an
         empty or infeasible row.  Needs no weights.  One launch on the current stream, no synchronisation."""
-        if logp.dim() != 3 or logp.dtype != torch.float32 or not logp.is_contiguous() or logp.device != self.device:
-            raise ValueError("ctc_score: logp must be a contiguous fp32 (B,T,C) tensor on the engine's device")
-        B, T, Cn = (int(v) for v in logp.shape)
-        if tokens.dim() != 2 or tokens.dtype != torch.int32 or not tokens.is_contiguous() or tokens.device != self.device or tokens.shape[0] != B:
-            raise ValueError(f"ctc_score: tokens must be a contiguous int32 ({B},P) tensor on the engine's device")
-        P = int(tokens.shape[1])
-        if not (T >= 1 and 1 <= P <= ALIGN_MAX_TOKENS and 2 <= Cn <= 256):
-            raise ValueError(f"ctc_score: T = {T}, P = {P}, C = {Cn} outside the supported range T >= 1, P <= {ALIGN_MAX_TOKENS}, 2 <= C <= 256")
-        if B < 1 or len(ts) != B or len(p0) != B or len(p1) != B:
-            raise ValueError("ctc_score: one frame count and one token range per row")
-        tab = self._upload_i32([ts, p0, p1])
+        B, T, P, Cn, tab = self._ctc_front("ctc_score", logp, ts, tokens, p0, p1, None)
         nll = torch.empty(B, device=self.device)
         self._ck(self.lib.smtts_ctc_score(self.h, self._stream(), _p(logp), _p(tab[0]), _p(tokens), _p(tab[1]), _p(tab[2]), B, T, P, Cn,
                                           _p(nll)), "ctc_score")
@@ -607,18 +597,7 @@ class HipEngine:
         frames and behind ts[b].  A row without frames or tokens, an infeasible row and a NaN score are not aligned: every span
         (-1, -1), tok_logp 0, frame_tok -1, score -inf (or the NaN).  All on the device.  Needs no weights.  One launch on the current
         stream, no synchronisation."""
-        if logp.dim() != 3 or logp.dtype != torch.float32 or not logp.is_contiguous() or logp.device != self.device:
-            raise ValueError("ctc_align: logp must be a contiguous fp32 (B,T,C) tensor on the engine's device")
-        B, T, Cn = (int(v) for v in logp.shape)
-        if tokens.dim() != 2 or tokens.dtype != torch.int32 or not tokens.is_contiguous() or tokens.device != self.device or tokens.shape[0] != B:
-            raise ValueError(f"ctc_align: tokens must be a contiguous int32 ({B},P) tensor on the engine's device")
-        P = int(tokens.shape[1])
-        if not (1 <= T <= CTC_ALIGN_MAX_FRAMES and 1 <= P <= ALIGN_MAX_TOKENS and 2 <= Cn <= 256):
-            raise ValueError(f"ctc_align: T = {T}, P = {P}, C = {Cn} outside the supported range 1 <= T <= {CTC_ALIGN_MAX_FRAMES}, "
-                             f"P <= {ALIGN_MAX_TOKENS}, 2 <= C <= 256")
-        if B < 1 or len(ts) != B or len(p0) != B or len(p1) != B:
-            raise ValueError("ctc_align: one frame count and one token range per row")
-        tab = self._upload_i32([ts, p0, p1])
+        B, T, P, Cn, tab = self._ctc_front("ctc_align", logp, ts, tokens, p0, p1, CTC_ALIGN_MAX_FRAMES)
         spans = torch.empty(B, P, 2, dtype=torch.int32, device=self.device)
         tok_logp = torch.empty(B, P, device=self.device)
         score = torch.empty(B, device=self.device)
@@ -631,23 +610,17 @@ class HipEngine:
         """Greedy CTC transcript of every row (smtts_ctc_greedy): per-frame argmax (lowest class on ties), runs collapsed, class 0
         dropped.  logp fp32 (B,T,C) contiguous on the device, T <= 4096; ts the frames per row (host integers).  -> (ids int32 (B,T),
         zeros behind the count; n_ids int32 (B)), on the device.  Needs no weights.  One launch, no synchronisation."""
-        if logp.dim() != 3 or logp.dtype != torch.float32 or not logp.is_contiguous() or logp.device != self.device:
+        if not self._is(logp, torch.float32, None, None, None):
             raise ValueError("ctc_greedy: logp must be a contiguous fp32 (B,T,C) tensor on the engine's device")
         B, T, Cn = (int(v) for v in logp.shape)
         if not (1 <= T <= 4096 and Cn >= 1):
             raise ValueError(f"ctc_greedy: T = {T}, C = {Cn} outside the supported range 1 <= T <= 4096, C >= 1")
-        if B < 1 or len(ts) != B:
-            raise ValueError("ctc_greedy: one frame count per row")
+        per_row("ctc_greedy", B, ts)
         tab = self._upload_i32([ts])
         ids = torch.empty(B, T, dtype=torch.int32, device=self.device)
         n_ids = torch.empty(B, dtype=torch.int32, device=self.device)
         self._ck(self.lib.smtts_ctc_greedy(self.h, self._stream(), _p(logp), _p(tab[0]), B, T, Cn, _p(ids), _p(n_ids)), "ctc_greedy")
         return ids, n_ids
-
-    def _upload_i32(self, rows) -> torch.Tensor:
-        """Small per-call host table -> device int32 on the current stream, through pinned staging (no synchronising copy)."""
-        t = torch.from_numpy(np.ascontiguousarray([[int(v) for v in r] for r in rows], dtype=np.int32))
-        return t.pin_memory().to(self.device, non_blocking=True)
 
     def take_scores(self, mass: torch.Tensor, spans: torch.Tensor, path_score: torch.Tensor, ns, p0, p1, takes):
         """The quality score of every row behind align_path (smtts_take_scores; the definition: include/smalltts_hip.h).
@@ -656,18 +629,10 @@ class HipEngine:
         .tau_frame (e.g. api.Takes).  -> (feat int32 (B,4) = (cells, skipped, longest, idle), total fp32 (B), lower is better, +inf
         for an empty row), both on the device.  One launch on the current stream, no synchronisation.  What the total is worth on
         trained weights is unvalidated (api.Takes)."""
-        if mass.dim() != 3 or mass.dtype != torch.float32 or not mass.is_contiguous() or mass.device != self.device:
-            raise ValueError("take_scores: mass must be a contiguous fp32 (B,N,P) tensor on the engine's device")
-        B, N, P = (int(v) for v in mass.shape)
-        if not (1 <= N <= ALIGN_MAX_FRAMES and 1 <= P <= ALIGN_MAX_TOKENS):
-            raise ValueError(f"take_scores: N = {N}, P = {P} outside the supported range N <= {ALIGN_MAX_FRAMES}, P <= {ALIGN_MAX_TOKENS}")
-        if spans.dtype != torch.int32 or tuple(spans.shape) != (B, P, 2) or not spans.is_contiguous() or spans.device != self.device:
-            raise ValueError(f"take_scores: spans must be a contiguous int32 ({B},{P},2) tensor on the engine's device")
-        if (path_score.dtype != torch.float32 or tuple(path_score.shape) != (B,) or not path_score.is_contiguous()
-                or path_score.device != self.device):
+        B, N, P = self._mass_front("take_scores", mass, spans)
+        if not self._is(path_score, torch.float32, B):
             raise ValueError(f"take_scores: path_score must be a contiguous fp32 ({B},) tensor on the engine's device")
-        if B < 1 or len(ns) != B or len(p0) != B or len(p1) != B:
-            raise ValueError("take_scores: one frame count and one token range per row")
+        per_row("take_scores", B, ns, p0, p1)
         w = [float(v) for v in takes.weights]
         tt, tf = float(takes.tau_token), float(takes.tau_frame)
         if len(w) != 4 or not all(v >= 0.0 for v in w) or tt != tt or tf != tf:
@@ -687,26 +652,22 @@ class HipEngine:
         as +inf).  -> (x_win (G,N,64), n_win int32 (G), spans_win (G,P,2) or None, mass_win (G,N,P) or None, winner int32 (G)), on the
         device, the winners' rows bit for bit.  One launch on the current stream, no synchronisation."""
         K = int(K)
-        if total.dim() != 1 or total.dtype != torch.float32 or not total.is_contiguous() or total.device != self.device:
+        if not self._is(total, torch.float32, None):
             raise ValueError("take_select: total must be a contiguous fp32 (B,) tensor on the engine's device")
         B = int(total.shape[0])
         if not 1 <= K <= 16 or B < 1 or B % K:
             raise ValueError(f"take_select: K must be in [1, 16] and divide the {B} rows")
         G = B // K
-        if x.dim() != 3 or tuple(x.shape[::2]) != (B, LATENT) or x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device:
+        if not self._is(x, torch.float32, B, None, LATENT):
             raise ValueError(f"take_select: x must be a contiguous fp32 ({B},N,{LATENT}) tensor on the engine's device")
         N = int(x.shape[1])
         P = int(spans.shape[1]) if spans is not None and spans.dim() == 3 else int(mass.shape[2]) if mass is not None and mass.dim() == 3 else 1
-        if not (1 <= N <= ALIGN_MAX_FRAMES and 1 <= P <= ALIGN_MAX_TOKENS):
-            raise ValueError(f"take_select: N = {N}, P = {P} outside the supported range N <= {ALIGN_MAX_FRAMES}, P <= {ALIGN_MAX_TOKENS}")
-        if spans is not None and (spans.dtype != torch.int32 or tuple(spans.shape) != (B, P, 2) or not spans.is_contiguous()
-                                  or spans.device != self.device):
+        frames_tokens("take_select", N, P)
+        if spans is not None and not self._is(spans, torch.int32, B, P, 2):
             raise ValueError(f"take_select: spans must be a contiguous int32 ({B},{P},2) tensor on the engine's device, or None")
-        if mass is not None and (mass.dtype != torch.float32 or tuple(mass.shape) != (B, N, P) or not mass.is_contiguous()
-                                 or mass.device != self.device):
+        if mass is not None and not self._is(mass, torch.float32, B, N, P):
             raise ValueError(f"take_select: mass must be a contiguous fp32 ({B},{N},{P}) tensor on the engine's device, or None")
-        if len(ns) != B:
-            raise ValueError("take_select: one frame count per row")
+        per_row("take_select", B, ns)
         tab = self._upload_i32([ns])
         dev = self.device
         x_win = torch.empty(G, N, LATENT, device=dev)
@@ -726,18 +687,10 @@ class HipEngine:
         the plan says.  -> (pin bool (B,N), what sample(pin=) takes: True = keep the frame; counts int32 (B,2) = (bad tokens, freed
         frames)), on the device.  One launch on the current stream, no synchronisation.  How well the freed frames are re-spoken is
         unvalidated on trained weights (api.Repair)."""
-        if mass.dim() != 3 or mass.dtype != torch.float32 or not mass.is_contiguous() or mass.device != self.device:
-            raise ValueError("repair_plan: mass must be a contiguous fp32 (B,N,P) tensor on the engine's device")
-        B, N, P = (int(v) for v in mass.shape)
-        if not (1 <= N <= ALIGN_MAX_FRAMES and 1 <= P <= ALIGN_MAX_TOKENS):
-            raise ValueError(f"repair_plan: N = {N}, P = {P} outside the supported range N <= {ALIGN_MAX_FRAMES}, P <= {ALIGN_MAX_TOKENS}")
-        if spans.dtype != torch.int32 or tuple(spans.shape) != (B, P, 2) or not spans.is_contiguous() or spans.device != self.device:
-            raise ValueError(f"repair_plan: spans must be a contiguous int32 ({B},{P},2) tensor on the engine's device")
-        if keep is not None and (keep.dtype not in (torch.bool, torch.uint8) or tuple(keep.shape) != (B, N) or not keep.is_contiguous()
-                                 or keep.device != self.device):
+        B, N, P = self._mass_front("repair_plan", mass, spans)
+        if keep is not None and not self._is(keep, (torch.bool, torch.uint8), B, N):
             raise ValueError(f"repair_plan: keep must be a contiguous bool or uint8 ({B},{N}) tensor on the engine's device, or None")
-        if B < 1 or len(ns) != B or len(p0) != B or len(p1) != B:
-            raise ValueError("repair_plan: one frame count and one token range per row")
+        per_row("repair_plan", B, ns, p0, p1)
         tt, span, margin = float(repair.tau_token), int(repair.max_span), int(repair.margin)
         if tt != tt or not 1 <= span <= ALIGN_MAX_FRAMES or not 0 <= margin <= 32:
             raise ValueError(f"repair_plan: a threshold that is not NaN, max_span in [1, {ALIGN_MAX_FRAMES}] and margin in [0, 32]")
@@ -758,29 +711,25 @@ class HipEngine:
         (G,4) (take_scores), counts int32 (G,2) (repair_plan), all contiguous on the device.  -> (total_out (G), feat_out (G,4), kept
         int32 (G)), fresh tensors: those of the row that stays, and the decision.  One launch on the current stream, no
         synchronisation."""
-        dev = self.device
-
-        def ok(t, dtype, shape):
-            return t.dtype == dtype and tuple(t.shape) == shape and t.is_contiguous() and t.device == dev
-        if total_cur.dim() != 1 or int(total_cur.shape[0]) < 1:
+        dev, ok = self.device, self._is
+        if not isinstance(total_cur, torch.Tensor) or total_cur.dim() != 1 or int(total_cur.shape[0]) < 1:
             raise ValueError("repair_keep: total_cur must be a contiguous fp32 (G,) tensor on the engine's device")
         G = int(total_cur.shape[0])
-        if not (ok(total_cur, torch.float32, (G,)) and ok(total_new, torch.float32, (G,))):
+        if not (ok(total_cur, torch.float32, G) and ok(total_new, torch.float32, G)):
             raise ValueError(f"repair_keep: total_cur and total_new must be contiguous fp32 ({G},) tensors on the engine's device")
-        if not (ok(counts, torch.int32, (G, 2)) and ok(feat_cur, torch.int32, (G, 4)) and ok(feat_new, torch.int32, (G, 4))):
+        if not (ok(counts, torch.int32, G, 2) and ok(feat_cur, torch.int32, G, 4) and ok(feat_new, torch.int32, G, 4)):
             raise ValueError(f"repair_keep: counts must be int32 ({G},2) and feat_cur / feat_new int32 ({G},4), contiguous on the engine's device")
-        if x_cur.dim() != 3 or not ok(x_cur, torch.float32, (G, int(x_cur.shape[1]), LATENT)) or not ok(x_new, torch.float32, tuple(x_cur.shape)):
+        if not ok(x_cur, torch.float32, G, None, LATENT) or not ok(x_new, torch.float32, *x_cur.shape):
             raise ValueError(f"repair_keep: x_cur and x_new must be contiguous fp32 ({G},N,{LATENT}) tensors on the engine's device")
         N = int(x_cur.shape[1])
         if (spans_cur is None) != (spans_new is None) or (mass_cur is None) != (mass_new is None):
             raise ValueError("repair_keep: spans_cur / spans_new and mass_cur / mass_new are given or None together")
         P = (int(spans_cur.shape[1]) if spans_cur is not None and spans_cur.dim() == 3
              else int(mass_cur.shape[2]) if mass_cur is not None and mass_cur.dim() == 3 else 1)
-        if not (1 <= N <= ALIGN_MAX_FRAMES and 1 <= P <= ALIGN_MAX_TOKENS):
-            raise ValueError(f"repair_keep: N = {N}, P = {P} outside the supported range N <= {ALIGN_MAX_FRAMES}, P <= {ALIGN_MAX_TOKENS}")
-        if spans_cur is not None and not (ok(spans_cur, torch.int32, (G, P, 2)) and ok(spans_new, torch.int32, (G, P, 2))):
+        frames_tokens("repair_keep", N, P)
+        if spans_cur is not None and not (ok(spans_cur, torch.int32, G, P, 2) and ok(spans_new, torch.int32, G, P, 2)):
             raise ValueError(f"repair_keep: spans_cur and spans_new must be contiguous int32 ({G},{P},2) tensors on the engine's device, or None")
-        if mass_cur is not None and not (ok(mass_cur, torch.float32, (G, N, P)) and ok(mass_new, torch.float32, (G, N, P))):
+        if mass_cur is not None and not (ok(mass_cur, torch.float32, G, N, P) and ok(mass_new, torch.float32, G, N, P)):
             raise ValueError(f"repair_keep: mass_cur and mass_new must be contiguous fp32 ({G},{N},{P}) tensors on the engine's device, or None")
         total_out = torch.empty(G, device=dev)
         feat_out = torch.empty(G, 4, dtype=torch.int32, device=dev)
@@ -831,16 +780,8 @@ class HipEngine:
         if lat.dim() != 3 or int(lat.shape[2]) != LATENT or int(lat.shape[0]) < 1 or int(lat.shape[1]) < 1:
             raise ValueError(f"codec_decode_stream: latents must be (B,T,{LATENT}) with B, T >= 1, got {tuple(lat.shape)}")
         B, T, _ = (int(v) for v in lat.shape)
-        sb = self.decode_state_bytes
-        if (not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 2 or int(state.shape[1]) != sb
-                or int(state.shape[0]) < 1 or not state.is_contiguous() or state.device != self.device or state.data_ptr() % 16):
-            raise ValueError(f"codec_decode_stream: state must be a contiguous, 16-byte aligned uint8 (n_slots,{sb}) tensor on the "
-                             "engine's device (decode_state())")
-        n_slots = int(state.shape[0])
-        sl = [int(v) for v in slots]
-        if len(sl) != B or len(set(sl)) != B or min(sl) < 0 or max(sl) >= n_slots:
-            raise ValueError(f"codec_decode_stream: {B} distinct slots in [0, {n_slots}) wanted, got {sl}")
-        tab = self._upload_i64(sl)
+        n_slots = pool_slots("codec_decode_stream", self.device, state, self.decode_state_bytes, "state", "decode_state")
+        tab = self._upload_i64(distinct_slots("codec_decode_stream", slots, B, n_slots))
         audio = torch.empty(B, 1, self.hop * T, device=self.device)
         ws = self._workspace(self.lib.smtts_decode_stream_workspace_bytes(self.h, B, T))
         self._ck(self.lib.smtts_codec_decode_stream(self.h, self._stream(), _p(lat), B, T, _p(state), n_slots, _p(tab), _p(audio),
@@ -869,11 +810,6 @@ class HipEngine:
         return out
 
     # ---- long-form synthesis: one voice, many rows (include/smalltts_hip.h) -----------------------------
-    def _upload_i64(self, rows) -> torch.Tensor:
-        """Small per-call host table -> device int64 on the current stream, through pinned staging (no synchronising copy)."""
-        t = torch.from_numpy(np.ascontiguousarray(rows, dtype=np.int64))
-        return t.pin_memory().to(self.device, non_blocking=True)
-
     def voice_expand(self, voices) -> Dict[str, torch.Tensor]:
         """B voices (objects with k_ref / v_ref (12,1,8,R_b,120) fp32 on this device, or such pairs) -> the reference half of a
         cross-KV cache: k_ref, v_ref (12,B,8,Rmax,120) and ref_mask (B,Rmax), bit-identical copies with zeros in the padding.
@@ -887,8 +823,7 @@ class HipEngine:
             R = int(k.shape[3])
             want = (N_LAYERS, 1, N_HEADS, R, HEAD_DIM)
             for t in (k, v):
-                if (tuple(t.shape) != want or t.dtype != torch.float32 or t.device != self.device or not t.is_contiguous()
-                        or R < 1):
+                if not self._is(t, torch.float32, *want) or R < 1:
                     raise ValueError(f"voice_expand: a voice's k_ref / v_ref must be contiguous fp32 {want} with R >= 1 on {self.device}, "
                                      f"got {tuple(t.shape)} {t.dtype} on {t.device}")
             rows.append((k.data_ptr(), v.data_ptr(), R))
@@ -921,16 +856,12 @@ class HipEngine:
         B = audio.shape[0]
         row = int(audio.shape[-1])
         lens = [self.hop * int(n) for n in ns]
-        if (audio.dtype != torch.float32 or not audio.is_contiguous() or audio.device != self.device or len(lens) != B
-                or len(offsets) != B or max(lens) > row):
+        if not self._is(audio, torch.float32) or len(lens) != B or len(offsets) != B or max(lens) > row:
             raise ValueError("stitch: audio must be contiguous fp32 (B,1,S) on the engine's device with hop * ns[b] <= S")
-        if out.dtype not in (torch.float32, torch.int16) or out.dim() != 1 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("stitch: out must be a contiguous 1-D fp32 or int16 tensor on the engine's device")
+        out_1d("stitch", self.device, out)
         if any(int(o) < 0 or int(o) + n > out.numel() for o, n in zip(offsets, lens)):
             raise ValueError("stitch: a row does not fit into out")
-        F = 0 if fade is None else int(fade.numel())
-        if F and (fade.dtype != torch.float32 or fade.device != self.device or not fade.is_contiguous()):
-            raise ValueError("stitch: fade must be a contiguous fp32 tensor on the engine's device")
+        F = fade_len("stitch", self.device, fade)
         tab = self._upload_i64([lens, [int(o) for o in offsets]])
         self._ck(self.lib.smtts_stitch(self.h, self._stream(), _p(audio), B, row, _p(tab[0]), _p(tab[1]), _p(fade) if F else None, F,
                                        _p(out), out.numel(), int(out.dtype == torch.int16)), "stitch")
@@ -948,8 +879,7 @@ class HipEngine:
         if (ns is None) == (lens is None):
             raise ValueError("endpoints: pass either ns (frames per row) or lens= (samples per row)")
         lens = [self.hop * int(n) for n in ns] if lens is None else [int(n) for n in lens]
-        if (audio.dtype != torch.float32 or not audio.is_contiguous() or audio.device != self.device or B < 1 or row < 1
-                or len(lens) != B or min(lens) < 0 or max(lens) > row):
+        if not self._is(audio, torch.float32) or B < 1 or row < 1 or len(lens) != B or min(lens) < 0 or max(lens) > row:
             raise ValueError("endpoints: audio must be contiguous fp32 (B,1,S) on the engine's device with 0 <= len[b] <= S")
         p = ep.kernel_params()
         W = int(p["W"])
@@ -973,22 +903,15 @@ class HipEngine:
         integers).  out[offsets[b] + i] = audio[b, 0, start_b + i] * gain[b] * g for i < n_b.  The windows are clamped into the row and
         samples outside `out` are dropped by the kernel: the host does not know n_b here."""
         B, row = int(audio.shape[0]), int(audio.shape[-1])
-        if audio.dtype != torch.float32 or not audio.is_contiguous() or audio.device != self.device or len(offsets) != B or row < 1:
+        if not self._is(audio, torch.float32) or len(offsets) != B or row < 1:
             raise ValueError("stitch_seg: audio must be contiguous fp32 (B,1,S) on the engine's device, one offset per row")
-        if seg.dtype != torch.int64 or tuple(seg.shape) != (B, 2) or not seg.is_contiguous() or seg.device != self.device:
-            raise ValueError("stitch_seg: seg must be a contiguous int64 (B,2) tensor on the engine's device")
-        if gain is not None and (gain.dtype != torch.float32 or tuple(gain.shape) != (B,) or not gain.is_contiguous()
-                                 or gain.device != self.device):
-            raise ValueError("stitch_seg: gain must be a contiguous fp32 (B,) tensor on the engine's device, or None")
-        if out.dtype not in (torch.float32, torch.int16) or out.dim() != 1 or not out.is_contiguous() or out.device != self.device:
-            raise ValueError("stitch_seg: out must be a contiguous 1-D fp32 or int16 tensor on the engine's device")
+        seg_gain("stitch_seg", self.device, B, seg, gain)
+        out_1d("stitch_seg", self.device, out)
         if out.numel() == 0:
             return out
         if any(int(o) < 0 or int(o) > out.numel() for o in offsets):
             raise ValueError("stitch_seg: an offset lies outside out")
-        F = 0 if fade is None else int(fade.numel())
-        if F and (fade.dtype != torch.float32 or fade.device != self.device or not fade.is_contiguous()):
-            raise ValueError("stitch_seg: fade must be a contiguous fp32 tensor on the engine's device")
+        F = fade_len("stitch_seg", self.device, fade)
         tab = self._upload_i64([[int(o) for o in offsets]])
         self._ck(self.lib.smtts_stitch_seg(self.h, self._stream(), _p(audio), B, row, _p(seg), _p(gain), _p(tab[0]),
                                            _p(fade) if F else None, F, _p(out), out.numel(), int(out.dtype == torch.int16)), "stitch_seg")
@@ -1012,18 +935,11 @@ class HipEngine:
         if audio.dim() != 3 or audio.shape[1] != 1:
             raise ValueError("join_stream: audio must be (B,1,S)")
         B, row = int(audio.shape[0]), int(audio.shape[-1])
-        if audio.dtype != torch.float32 or not audio.is_contiguous() or audio.device != self.device or B < 1 or row < 1:
+        if not self._is(audio, torch.float32) or B < 1 or row < 1:
             raise ValueError("join_stream: audio must be contiguous fp32 (B,1,S) on the engine's device")
-        if seg.dtype != torch.int64 or tuple(seg.shape) != (B, 2) or not seg.is_contiguous() or seg.device != self.device:
-            raise ValueError("join_stream: seg must be a contiguous int64 (B,2) tensor on the engine's device")
-        if gain is not None and (gain.dtype != torch.float32 or tuple(gain.shape) != (B,) or not gain.is_contiguous()
-                                 or gain.device != self.device):
-            raise ValueError("join_stream: gain must be a contiguous fp32 (B,) tensor on the engine's device, or None")
-        F = 0 if fade is None else int(fade.numel())
-        if F and (fade.dtype != torch.float32 or fade.device != self.device or not fade.is_contiguous()):
-            raise ValueError("join_stream: fade must be a contiguous fp32 tensor on the engine's device")
-        if (not isinstance(state, torch.Tensor) or state.dtype != torch.int64 or tuple(state.shape) != (2,) or not state.is_contiguous()
-                or state.device != self.device or state.data_ptr() % 16):
+        seg_gain("join_stream", self.device, B, seg, gain)
+        F = fade_len("join_stream", self.device, fade)
+        if not self._is(state, torch.int64, 2, aligned=True):
             raise ValueError("join_stream: state must be a contiguous, 16-byte aligned int64 (2,) tensor on the engine's device (join_state())")
         gap = int(gap)
         if gap < 0:
@@ -1117,59 +1033,55 @@ class HipEngine:
         into a scratch buffer in front of smtts_deliver (engine.watermark's launches, nothing else changes).  mark_state =
         watermark_state(...) carries the mark from chunk to chunk through the same `slots` and `n_before`, also at 24 kHz, where the
         delivery itself has no state; without it every row starts a stream of its own."""
-        from .audio import DELIVER_ENCODINGS, deliver_counts, deliver_max_count
-        if mark is None and mark_state is not None:
-            raise ValueError("deliver: mark_state= belongs to mark=")
-        if encoding not in DELIVER_ENCODINGS:
-            raise ValueError(f"deliver: encoding must be one of {DELIVER_ENCODINGS}, got {encoding!r}")
-        enc = DELIVER_ENCODINGS.index(encoding)
-        bank, up, down, width, klen = self.deliver_bank(rate, zeros)
-        if (not isinstance(audio, torch.Tensor) or audio.dtype != torch.float32 or audio.dim() != 3 or int(audio.shape[1]) != 1
-                or not audio.is_contiguous() or audio.device != self.device or int(audio.shape[0]) < 1 or int(audio.shape[2]) < 1):
-            raise ValueError("deliver: audio must be a contiguous fp32 (B,1,S) tensor on the engine's device with B, S >= 1")
-        B, row = int(audio.shape[0]), int(audio.shape[2])
-        ln = [int(v) for v in lens]
-        if len(ln) != B or min(ln) < 0 or max(ln) > row:
-            raise ValueError(f"deliver: {B} lengths in [0, {row}] wanted, got {ln}")
+        from .audio import deliver_counts
+        front = enc, bank, up, down, width, klen = self._deliver_front("deliver", rate, encoding, zeros, mark, mark_state)
+        B, row, ln = self._audio_rows("deliver", audio, lens)
         lasts = [bool(v) for v in last] if isinstance(last, (list, tuple)) else [bool(last)] * B
         nb = [0] * B if n_before is None else [int(v) for v in n_before]
         if len(lasts) != B or len(nb) != B or min(nb) < 0:
             raise ValueError(f"deliver: one non-negative n_before and one last flag per row wanted, got {nb}, {lasts}")
-        pooled = state is not None
-        if pooled and bank is None:
-            raise ValueError("deliver: 24 kHz is a pure encode and carries no state: pass state=None")
-        if pooled:
-            sb = int(self.lib.smtts_deliver_state_bytes(self.h, klen))
-            if (not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 2 or int(state.shape[1]) != sb
-                    or int(state.shape[0]) < 1 or not state.is_contiguous() or state.device != self.device or state.data_ptr() % 16):
-                raise ValueError(f"deliver: state must be a contiguous, 16-byte aligned uint8 (n_slots,{sb}) tensor on the engine's "
-                                 "device (deliver_state())")
-            n_slots = int(state.shape[0])
-            sl = [int(v) for v in (slots if slots is not None else [])]
-            if len(sl) != B or len(set(sl)) != B or min(sl) < 0 or max(sl) >= n_slots:
-                raise ValueError(f"deliver: {B} distinct slots in [0, {n_slots}) wanted, got {sl}")
+        n_slots = self._deliver_pool("deliver", state, bank, klen)
+        if state is not None:
+            sl = distinct_slots("deliver", slots, B, n_slots)
         else:
             if (slots is not None and mark_state is None) or (bank is not None and (any(nb) or not all(lasts))):
                 raise ValueError("deliver: without state every row starts and ends here: no slots, n_before = 0, last = True "
                                  "(24 kHz, a pure encode, takes any n_before and last and ignores them)")
-            n_slots, sl = 0, [0] * B
+            sl = [0] * B
         if mark_state is not None:
-            m_slots = self._watermark_pool(mark_state, "deliver")
-            sl = [int(v) for v in (slots if slots is not None else [])]
-            if len(sl) != B or len(set(sl)) != B or min(sl) < 0 or max(sl) >= m_slots:
-                raise ValueError(f"deliver: {B} distinct slots in [0, {m_slots}) wanted, got {sl}")
-        if bank is None:
-            counts, stride = list(ln), row
-        else:
-            counts = deliver_counts(nb, ln, lasts, up, down, width)
-            stride = max(1, deliver_max_count(row, up, down, width, pooled))
-        out = torch.empty(B, stride, dtype=(torch.float32, torch.int16, torch.uint8, torch.uint8)[enc], device=self.device)
+            sl = distinct_slots("deliver", slots, B, self._watermark_pool(mark_state, "deliver"))
+        counts = list(ln) if bank is None else deliver_counts(nb, ln, lasts, up, down, width)
         tab = self._upload_i64([[s, a, n, int(f)] for s, a, n, f in zip(sl, nb, ln, lasts)])
+        return self._deliver_table("deliver", audio, B, row, tab, front, state, n_slots, mark, mark_state), counts
+
+    def _deliver_front(self, what, rate, encoding, zeros, mark, mark_state):
+        """deliver / deliver_from_table: the encoding's code and the bank -> (enc, bank, up, down, width, klen)."""
+        from .audio import DELIVER_ENCODINGS
+        if mark is None and mark_state is not None:
+            raise ValueError(f"{what}: mark_state= belongs to mark=")
+        if encoding not in DELIVER_ENCODINGS:
+            raise ValueError(f"{what}: encoding must be one of {DELIVER_ENCODINGS}, got {encoding!r}")
+        return (DELIVER_ENCODINGS.index(encoding),) + tuple(self.deliver_bank(rate, zeros))
+
+    def _deliver_pool(self, what, state, bank, klen) -> int:
+        """The optional state pool of a delivery -> n_slots, 0 without one."""
+        if state is None:
+            return 0
+        if bank is None:
+            raise ValueError(f"{what}: 24 kHz is a pure encode and carries no state: pass state=None")
+        return pool_slots(what, self.device, state, int(self.lib.smtts_deliver_state_bytes(self.h, klen)), "state", "deliver_state")
+
+    def _deliver_table(self, what, audio, B, row, tab, front, state, n_slots, mark, mark_state) -> torch.Tensor:
+        """The result, the mark and smtts_deliver on a table that lies on the device."""
+        from .audio import deliver_max_count
+        enc, bank, up, down, width, klen = front
+        stride = row if bank is None else max(1, deliver_max_count(row, up, down, width, state is not None))
+        out = torch.empty(B, stride, dtype=(torch.float32, torch.int16, torch.uint8, torch.uint8)[enc], device=self.device)
         if mark is not None:
-            audio = self._watermark_table(audio, B, row, tab, mark, mark_state, "deliver")
-        self._ck(self.lib.smtts_deliver(self.h, self._stream(), _p(audio), B, row, _p(tab), _p(bank), up, down, klen, width,
-                                        _p(state) if pooled else None, n_slots, enc, _p(out), stride), "deliver")
-        return out, counts
+            audio = self._watermark_table(audio, B, row, tab, mark, mark_state, what)
+        self._ck(self.lib.smtts_deliver(self.h, self._stream(), _p(audio), B, row, _p(tab), _p(bank), up, down, klen, width, _p(state),
+                                        n_slots, enc, _p(out), stride), "deliver")
+        return out
 
     def deliver_from_table(self, chunk: torch.Tensor, dtable: torch.Tensor, rate: int, encoding: str = "f32", *,
                            state: Optional[torch.Tensor] = None, zeros: Optional[int] = None, mark=None,
@@ -1183,40 +1095,15 @@ class HipEngine:
         there is nothing to carry and state must be None).  On the current stream, no synchronisation.
         mark / mark_state: as in deliver(): the chunk is watermarked on the device-written dtable in front of smtts_deliver, so the
         mark follows the stream's absolute position without the host knowing the length."""
-        from .audio import DELIVER_ENCODINGS, deliver_max_count
-        if mark is None and mark_state is not None:
-            raise ValueError("deliver_from_table: mark_state= belongs to mark=")
-        if encoding not in DELIVER_ENCODINGS:
-            raise ValueError(f"deliver_from_table: encoding must be one of {DELIVER_ENCODINGS}, got {encoding!r}")
-        enc = DELIVER_ENCODINGS.index(encoding)
-        bank, up, down, width, klen = self.deliver_bank(rate, zeros)
-        if (not isinstance(chunk, torch.Tensor) or chunk.dtype != torch.float32 or chunk.dim() != 1 or not chunk.is_contiguous()
-                or chunk.device != self.device or int(chunk.numel()) < 1):
+        front = enc, bank, up, down, width, klen = self._deliver_front("deliver_from_table", rate, encoding, zeros, mark, mark_state)
+        if not self._is(chunk, torch.float32, None) or int(chunk.numel()) < 1:
             raise ValueError("deliver_from_table: chunk must be a contiguous 1-D fp32 tensor on the engine's device")
-        if (not isinstance(dtable, torch.Tensor) or dtable.dtype != torch.int64 or tuple(dtable.shape) != (4,) or not dtable.is_contiguous()
-                or dtable.device != self.device):
+        if not self._is(dtable, torch.int64, 4):
             raise ValueError("deliver_from_table: dtable must be a contiguous int64 (4,) tensor on the engine's device")
-        row = int(chunk.numel())
-        pooled = state is not None
-        if pooled and bank is None:
-            raise ValueError("deliver_from_table: 24 kHz is a pure encode and carries no state: pass state=None")
-        n_slots = 0
-        if pooled:
-            sb = int(self.lib.smtts_deliver_state_bytes(self.h, klen))
-            if (not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 2 or int(state.shape[1]) != sb
-                    or int(state.shape[0]) < 1 or not state.is_contiguous() or state.device != self.device or state.data_ptr() % 16):
-                raise ValueError(f"deliver_from_table: state must be a contiguous, 16-byte aligned uint8 (n_slots,{sb}) tensor on the "
-                                 "engine's device (deliver_state())")
-            n_slots = int(state.shape[0])
-        stride = row if bank is None else max(1, deliver_max_count(row, up, down, width, pooled))
-        out = torch.empty(1, stride, dtype=(torch.float32, torch.int16, torch.uint8, torch.uint8)[enc], device=self.device)
-        if mark is not None:
-            if mark_state is not None:
-                self._watermark_pool(mark_state, "deliver_from_table")
-            chunk = self._watermark_table(chunk, 1, row, dtable, mark, mark_state, "deliver_from_table")
-        self._ck(self.lib.smtts_deliver(self.h, self._stream(), _p(chunk), 1, row, _p(dtable), _p(bank), up, down, klen, width,
-                                        _p(state) if pooled else None, n_slots, enc, _p(out), stride), "deliver")
-        return out
+        n_slots = self._deliver_pool("deliver_from_table", state, bank, klen)
+        if mark_state is not None:
+            self._watermark_pool(mark_state, "deliver_from_table")
+        return self._deliver_table("deliver_from_table", chunk, 1, int(chunk.numel()), dtable, front, state, n_slots, mark, mark_state)
 
     # ---- watermark: key the 24 kHz stream, detect it (include/smalltts_hip.h smtts_watermark, DESIGN 8k) ----
     @staticmethod
@@ -1238,12 +1125,14 @@ class HipEngine:
         return torch.zeros(int(n_slots), int(self.lib.smtts_watermark_state_bytes(self.h)), dtype=torch.uint8, device=self.device)
 
     def _watermark_pool(self, state, what: str) -> int:
-        sb = int(self.lib.smtts_watermark_state_bytes(self.h))
-        if (not isinstance(state, torch.Tensor) or state.dtype != torch.uint8 or state.dim() != 2 or int(state.shape[1]) != sb
-                or int(state.shape[0]) < 1 or not state.is_contiguous() or state.device != self.device or state.data_ptr() % 16):
-            raise ValueError(f"{what}: the mark state must be a contiguous, 16-byte aligned uint8 (n_slots,{sb}) tensor on the engine's "
-                             "device (watermark_state())")
-        return int(state.shape[0])
+        return pool_slots(what, self.device, state, int(self.lib.smtts_watermark_state_bytes(self.h)), "the mark state", "watermark_state")
+
+    def _audio_rows(self, what, audio, lens):
+        """deliver / watermark: audio fp32 (B,1,S) and its B lengths -> (B, S, the lengths as ints)."""
+        if not self._is(audio, torch.float32, None, 1, None) or int(audio.shape[0]) < 1 or int(audio.shape[2]) < 1:
+            raise ValueError(f"{what}: audio must be a contiguous fp32 (B,1,S) tensor on the engine's device with B, S >= 1")
+        B, row = int(audio.shape[0]), int(audio.shape[2])
+        return B, row, row_lengths(what, lens, B, row)
 
     def _watermark_table(self, audio: torch.Tensor, B: int, row: int, tab: torch.Tensor, mark, state, what: str) -> torch.Tensor:
         """smtts_watermark on a table that already lies on the device -> the marked copy, shaped like audio."""
@@ -1259,21 +1148,12 @@ class HipEngine:
         holds lens[b] marked samples, nothing is written behind them (smtts_watermark).  Whole signals: state=None (every row starts
         a stream).  Streams: state=watermark_state(...), slots = B distinct slot indices, n_before = samples each stream has seen;
         the chunks' concatenation is the whole call's result, bit for bit.  On the current stream, no synchronisation."""
-        if (not isinstance(audio, torch.Tensor) or audio.dtype != torch.float32 or audio.dim() != 3 or int(audio.shape[1]) != 1
-                or not audio.is_contiguous() or audio.device != self.device or int(audio.shape[0]) < 1 or int(audio.shape[2]) < 1):
-            raise ValueError("watermark: audio must be a contiguous fp32 (B,1,S) tensor on the engine's device with B, S >= 1")
-        B, row = int(audio.shape[0]), int(audio.shape[2])
-        ln = [int(v) for v in lens]
-        if len(ln) != B or min(ln) < 0 or max(ln) > row:
-            raise ValueError(f"watermark: {B} lengths in [0, {row}] wanted, got {ln}")
+        B, row, ln = self._audio_rows("watermark", audio, lens)
         nb = [0] * B if n_before is None else [int(v) for v in n_before]
         if len(nb) != B or min(nb) < 0:
             raise ValueError(f"watermark: one non-negative n_before per row wanted, got {nb}")
         if state is not None:
-            n_slots = self._watermark_pool(state, "watermark")
-            sl = [int(v) for v in (slots if slots is not None else [])]
-            if len(sl) != B or len(set(sl)) != B or min(sl) < 0 or max(sl) >= n_slots:
-                raise ValueError(f"watermark: {B} distinct slots in [0, {n_slots}) wanted, got {sl}")
+            sl = distinct_slots("watermark", slots, B, self._watermark_pool(state, "watermark"))
         else:
             if slots is not None or any(nb):
                 raise ValueError("watermark: without state every row starts here: no slots, n_before = 0")
@@ -1286,13 +1166,10 @@ class HipEngine:
         u (B,S)]) on the device (smtts_watermark_detect): T[b][k] is the sign correlation at offset o_lo + k ("audio[j] is stream
         sample j + o"), best_off = o_lo + argmax, best_z = T / sqrt(den), about N(0, 1) where the key's mark is absent.  u is written
         below lens[b] only (zeros behind).  Needs no weights.  Three launches on the current stream, no synchronisation."""
-        if (not isinstance(audio, torch.Tensor) or audio.dtype != torch.float32 or audio.dim() != 2 or not audio.is_contiguous()
-                or audio.device != self.device or not 1 <= int(audio.shape[0]) <= 1024 or int(audio.shape[1]) < 1):
+        if not self._is(audio, torch.float32, None, None) or not 1 <= int(audio.shape[0]) <= 1024 or int(audio.shape[1]) < 1:
             raise ValueError("watermark_detect: audio must be a contiguous fp32 (B,S) tensor on the engine's device, 1 <= B <= 1024, S >= 1")
         B, row = int(audio.shape[0]), int(audio.shape[1])
-        ln = [int(v) for v in lens]
-        if len(ln) != B or min(ln) < 0 or max(ln) > row:
-            raise ValueError(f"watermark_detect: {B} lengths in [0, {row}] wanted, got {ln}")
+        ln = row_lengths("watermark_detect", lens, B, row)
         key, o_lo, n_off = int(key), int(o_lo), int(n_off)
         if not 0 <= key < 2 ** 64:
             raise ValueError(f"watermark_detect: the key must be in [0, 2^64), got {key}")
@@ -1333,171 +1210,3 @@ class HipEngine:
         a, s = C.c_float(), C.c_float()
         self.lib.smtts_alpha_sigma(C.c_float(t), C.byref(a), C.byref(s))
         return a.value, s.value
-
-    # ---- single-kernel hooks (tests) -------------------------------------------------------------
-    def test_gemm(self, A, W, bias=None, act="none", split=3, cfg=-1):
-        A = self._dev(A, torch.float32)
-        W = self._dev(W, torch.float32)
-        bias = None if bias is None else self._dev(bias, torch.float32)
-        M, K = A.shape
-        N = W.shape[0]
-        out = torch.empty(M, N, device=self.device)
-        self._ck(self.lib.smtts_test_gemm(self.h, self._stream(), _p(A), K, _p(W), _p(bias), M, N, K, ACT[act], split,
-                                          cfg, _p(out), N), "test_gemm")
-        return out
-
-    def test_gemm3(self, A, W, bias=None, act="none", split=3, cfg=-1):
-        A = self._dev(A, torch.float32)
-        W = self._dev(W, torch.float32)
-        bias = None if bias is None else self._dev(bias, torch.float32)
-        M, K = A.shape
-        N = W.shape[0]
-        out = torch.empty(M, N, device=self.device)
-        self._ck(self.lib.smtts_test_gemm3(self.h, self._stream(), _p(A), _p(W), _p(bias), M, N, K, ACT[act], split, cfg,
-                                           _p(out)), "test_gemm3")
-        return out
-
-    def test_ln_fold(self, x, A, Wp, scale, W1, W3, shift=None, bp=None, gate=None, row_mask=None, b1=None, b3=None,
-                     rms=False, fold=True, precision="f16", eps=1e-6, return_shift=False):
-        """One LN-fold step (include/smalltts_hip.h smtts_test_ln_fold): x += row_mask gate (A Wp^T + bp), then the LayerNorm
-        (1 + scale) + shift (rms=False) or RMSNorm * scale (rms=True) of x into [W1 | W3] and SwiGLU.  fold=True: the producer /
-        consumer epilogues; False: the norm launches.  Returns (updated x [M, D], hidden [M, F]) as fp32, and with return_shift=True
-        the row shift the consumer leaves for the next producer [M] (LayerNorm fold; zeros otherwise); x itself is not modified."""
-        f = lambda t: None if t is None else self._dev(t, torch.float32)
-        A, Wp, scale, W1, W3, shift, bp, gate, b1, b3 = map(f, (A, Wp, scale, W1, W3, shift, bp, gate, b1, b3))
-        x = self._dev(x, torch.float32).clone()
-        row_mask = None if row_mask is None else self._dev(row_mask, torch.uint8)
-        M, K = A.shape
-        D, F = Wp.shape[0], W1.shape[0]
-        hid = torch.empty(M, F, device=self.device)
-        shift_out = torch.empty(M, device=self.device) if return_shift else None
-        self._ck(self.lib.smtts_test_ln_fold(self.h, self._stream(), _p(A), _p(Wp), _p(bp), _p(gate), _p(row_mask), _p(scale),
-                                             _p(shift), _p(W1), _p(W3), _p(b1), _p(b3), M, K, D, F, eps, int(bool(rms)),
-                                             PRECISION[precision], int(bool(fold)), _p(x), _p(hid), _p(shift_out)), "test_ln_fold")
-        return (x, hid, shift_out) if return_shift else (x, hid)
-
-    def test_codec_stage(self, part, stage: int, what: int, x) -> torch.Tensor:
-        """One codec stage through the product's code (include/smalltts_hip.h smtts_test_codec_stage).  part: "decoder" / "encoder"
-        (or 1 / 2); what: 1 stem, 2 resampling into `stage`, 4 its blocks, 8 final norm + head (a run of these bits).  x: (B, T_in, C_in)
-        channels-last (encoder stem: (B, S) or (B, S, 1) audio).  Returns the device tensor (B, T_out, C_out); the decoder head's
-        audio comes back as (B, T_out, 1)."""
-        p = {"decoder": 1, "encoder": 2}.get(part, part)
-        x = self._dev(x, torch.float32)
-        if x.dim() == 2:
-            x = x[:, :, None].contiguous()
-        B, T, Cin = x.shape
-        t_out, c_out = C.c_int(0), C.c_int(0)
-        self._ck(self.lib.smtts_test_codec_stage(self.h, self._stream(), int(p), int(stage), int(what), _p(x), B, T, Cin, None,
-                                                 C.byref(t_out), C.byref(c_out)), "test_codec_stage")
-        out = torch.empty(B, t_out.value, c_out.value, device=self.device)
-        self._ck(self.lib.smtts_test_codec_stage(self.h, self._stream(), int(p), int(stage), int(what), _p(x), B, T, Cin, _p(out),
-                                                 C.byref(t_out), C.byref(c_out)), "test_codec_stage")
-        return out
-
-    def test_dit_stage(self, net: str, what: int, x=None, mask=None, l0: int = 0, l1: Optional[int] = None, path: str = "auto",
-                       twice: bool = False, t=None, mod=None, mod_row0: int = 0, mod_rstride: int = 0, k_ref=None, v_ref=None,
-                       ref_mask=None, k_text=None, v_text=None, ph_mask=None, rope=None) -> Dict[str, torch.Tensor]:
-        """DiT / condition-encoder stages through the product's code (include/smalltts_hip.h smtts_test_dit_stage).  net: "dit", "style"
-        or "text"; what: a run of the chain bits (DiT: 1 modulation from t, 2 embed, 4 blocks [l0, l1), 8 head; encoders: 1 input,
-        2 blocks, 4 output projection, 8 cross K / V).  path: "auto" (the operator's choice), "fold", "splitk" or "unsplit".
-        Returns the device tensors that apply: "x" residual, "img" the operand image the blocks leave (fp32), "shift" the fold's
-        row shift, "out" velocity / ref_seq / phoneme memory, "k" / "v", "mod" the modulation table."""
-        netc = {"dit": 0, "style": 1, "text": 2}[net]
-        pathc = {"auto": 0, "fold": 1, "splitk": 2, "unsplit": 3}[path]
-        dev, f = self.device, (lambda a: None if a is None else self._dev(a, torch.float32))
-        if x is not None:
-            x = self._dev(x, torch.int64 if (net == "text" and what & 1) else torch.float32)
-            B, S = x.shape[:2]
-        else:
-            B, S = 1, 1
-        if mask is not None:
-            mask = self._dev(mask, torch.bool)
-            B, S = mask.shape
-        t, mod, k_ref, v_ref, k_text, v_text, rope = map(f, (t, mod, k_ref, v_ref, k_text, v_text, rope))
-        ref_mask = None if ref_mask is None else self._dev(ref_mask, torch.bool)
-        ph_mask = None if ph_mask is None else self._dev(ph_mask, torch.bool)
-        rows = t.shape[0] if t is not None else mod.shape[0] if mod is not None else 0
-        R = 0 if k_ref is None else k_ref.shape[3]
-        P = 0 if k_text is None else k_text.shape[3]
-        dit = net == "dit"
-        D = 960 if dit else 512
-        if l1 is None:
-            l1 = N_LAYERS if net != "text" else 8
-        e = lambda *sh: torch.empty(*sh, device=dev)
-        res: Dict[str, torch.Tensor] = {}
-        if what & (6 if dit else 3):
-            res["x"] = e(B, S, D)
-        if what & (4 if dit else 2):
-            res["img"] = e(B, S, D)
-            if dit:
-                res["shift"] = e(B, S)
-        if dit and what & 8:
-            res["out"] = e(B, S, LATENT)
-        if not dit and what & 4:
-            res["out"] = e(B, S, 960)
-        if not dit and what & 8:
-            res["k"], res["v"] = e(N_LAYERS, B, N_HEADS, S, HEAD_DIM), e(N_LAYERS, B, N_HEADS, S, HEAD_DIM)
-        if dit and what & 1:
-            res["mod"] = e(rows, 71040)
-        self._ck(self.lib.smtts_test_dit_stage(self.h, self._stream(), netc, int(what), int(l0), int(l1), pathc, int(bool(twice)),
-                                               _p(x), _p(mask), B, S, _p(t), _p(mod), rows, int(mod_row0), int(mod_rstride),
-                                               _p(k_ref), _p(v_ref), _p(ref_mask), R, _p(k_text), _p(v_text), _p(ph_mask), P, _p(rope),
-                                               _p(res.get("x")), _p(res.get("img")), _p(res.get("shift")), _p(res.get("out")),
-                                               _p(res.get("k")), _p(res.get("v")), _p(res.get("mod"))), "test_dit_stage")
-        return res
-
-    def test_swiglu(self, A, W1, W3, b1=None, b3=None, split=3):
-        A, W1, W3 = (self._dev(x, torch.float32) for x in (A, W1, W3))
-        b1 = None if b1 is None else self._dev(b1, torch.float32)
-        b3 = None if b3 is None else self._dev(b3, torch.float32)
-        M, K = A.shape
-        F = W1.shape[0]
-        out = torch.empty(M, F, device=self.device)
-        self._ck(self.lib.smtts_test_swiglu(self.h, self._stream(), _p(A), _p(W1), _p(W3), _p(b1), _p(b3), M, F, K,
-                                            split, _p(out)), "test_swiglu")
-        return out
-
-    def test_attention(self, qkvg, qw, kw, eps, rope, rot_dim, H, dh, k_ref=None, v_ref=None, k_text=None, v_text=None,
-                       mask_self=None, mask_ref=None, mask_text=None, mfma=False):
-        qkvg = self._dev(qkvg, torch.float32)
-        B, N, _ = qkvg.shape
-        f = lambda x, dt=torch.float32: None if x is None else self._dev(x, dt)
-        qw, kw, rope, k_ref, v_ref, k_text, v_text = map(f, (qw, kw, rope, k_ref, v_ref, k_text, v_text))
-        mask_self, mask_ref, mask_text = (f(m, torch.bool) for m in (mask_self, mask_ref, mask_text))
-        R = 0 if k_ref is None else k_ref.shape[2]
-        P = 0 if k_text is None else k_text.shape[2]
-        out = torch.empty(B, N, H * dh, device=self.device)
-        fn = self.lib.smtts_test_attention_mfma if mfma else self.lib.smtts_test_attention
-        if mfma:   # "img" / "img:f16" / "img:bf16x3" / "img:bf16": the product's DMA + MFMA kernel on operand images at that precision
-            s = str(mfma)
-            self._ck(self.lib.smtts_set_site_precision(self.h, SITES["attn"], PRECISION[s.split(":")[1] if ":" in s else "bf16x3"]),
-                     "set_site_precision")
-        self._ck(fn(self.h, self._stream(), _p(qkvg), _p(qw), _p(kw), eps, _p(rope), rot_dim,
-                                               _p(k_ref), _p(v_ref), R, _p(k_text), _p(v_text), P, _p(mask_self),
-                                               _p(mask_ref), _p(mask_text), B, N, H, dh, _p(out)), "test_attention")
-        if mfma:
-            self.set_precision(self.precision)
-        return out
-
-    def test_attn_text_mass(self, qkvg, qw, kw, eps, rope, rot_dim, H, dh, k_ref=None, v_ref=None, k_text=None, v_text=None,
-                            mask_self=None, mask_ref=None, mask_text=None, fmt: str = "bf16x3"):
-        """The text-attention tap in isolation (smtts_test_attn_text_mass): the inputs of test_attention(mfma="img:<fmt>"), the same
-        operand images; -> mass fp32 (B,N,P), the mean over all heads of the softmax probability on each text key."""
-        qkvg = self._dev(qkvg, torch.float32)
-        B, N, _ = qkvg.shape
-        f = lambda x, dt=torch.float32: None if x is None else self._dev(x, dt)
-        qw, kw, rope, k_ref, v_ref, k_text, v_text = map(f, (qw, kw, rope, k_ref, v_ref, k_text, v_text))
-        mask_self, mask_ref, mask_text = (f(m, torch.bool) for m in (mask_self, mask_ref, mask_text))
-        if k_text is None:
-            raise ValueError("test_attn_text_mass: needs text keys")
-        R = 0 if k_ref is None else k_ref.shape[2]
-        P = k_text.shape[2]
-        mass = torch.empty(B, N, P, device=self.device)
-        self._ck(self.lib.smtts_set_site_precision(self.h, SITES["attn"], PRECISION[fmt]), "set_site_precision")
-        try:
-            self._ck(self.lib.smtts_test_attn_text_mass(self.h, self._stream(), _p(qkvg), _p(qw), _p(kw), eps, _p(rope), rot_dim,
-                                                        _p(k_ref), _p(v_ref), R, _p(k_text), _p(v_text), P, _p(mask_self),
-                                                        _p(mask_ref), _p(mask_text), B, N, H, dh, _p(mass)), "test_attn_text_mass")
-        finally:
-            self.set_precision(self.precision)
-        return mass
