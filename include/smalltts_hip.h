@@ -331,6 +331,27 @@ int smtts_ctc_align(smtts_handle h, void* stream, const float* logp, const int32
                     const int32_t* p1, int B, int T, int P, int C, int32_t* spans, float* tok_logp, int32_t* frame_tok /* or NULL */,
                     float* score);
 
+/* ---- Long alignment (DESIGN.md '8m. Long alignment'): smtts_ctc_align for recordings past 30 s -------------------------------------
+ * smtts_ctc_align_long: the definition is smtts_ctc_align's block above, word for word: the same clamping of t_len, p0, p1 and of every
+ * token, the same recursion of single fp32 operations with strict compares, the same end rule and "ALIGNED iff score > -inf", the same
+ * bounded trace, the same four outputs with the same values on a row that is not aligned.  Wherever both entries accept a call their
+ * outputs are equal bit for bit.  What differs is where the lattice lives: one workgroup per row, every thread keeps delta of 32
+ * neighbouring extended states in registers, the 2-bit moves go to the workspace (one 8-byte word pair per thread and step) and the
+ * trace reads them back through LDS in chunks of 256 steps; the state of every frame goes to the workspace too.
+ * ws: at least smtts_ctc_align_long_workspace_bytes(h, B, T, P) bytes = B * (align256(8 T ceil((2 P + 1) / 32)) + align256(2 T)), a
+ * multiple of 256 (512 MiB + 128 KiB per row at the limits), 256-byte aligned, contents irrelevant on entry: every byte the kernel
+ * reads it wrote in the same call.  The size query returns 0 outside the range.  Every output element of every row is written; nothing
+ * at or behind t_len[b] of a row of logp, and nothing outside the row, is read; no atomics: two runs, alone or inside any batch, return
+ * the same bits.
+ * 1 <= B <= 64, 1 <= T <= 65536 (36 min of recogniser frames), 1 <= P <= 16383 (S = 2 P + 1 <= 32767), 2 <= C <= 256.  Needs no
+ * weights: works on any handle.  One launch on one stream, no synchronisation; an argument error (a limit, a NULL required pointer, a
+ * workspace that is NULL, misaligned or too small) returns 1 with a message naming the entry before anything is enqueued.
+ * UNVALIDATED exactly as smtts_ctc_align: only the mechanism is verified. */
+size_t smtts_ctc_align_long_workspace_bytes(smtts_handle h, int B, int T, int P);
+int smtts_ctc_align_long(smtts_handle h, void* stream, const float* logp, const int32_t* t_len, const int32_t* tokens, const int32_t* p0,
+                         const int32_t* p1, int B, int T, int P, int C, int32_t* spans, float* tok_logp, int32_t* frame_tok /* or NULL */,
+                         float* score, void* ws, size_t ws_bytes);
+
 /* ---- Speaker score (DESIGN.md '8j. Speaker score'): the latent speaker verifier on the device ---------------------------------------
  * smtts_sv_embed replaces the reference's SV(192).forward (src/smalltts/models/sv/model.py:26-35: speechbrain's ECAPA_TDNN on the 64-dim
  * latents, lengths / max as its relative lengths) for an engine that was given the sv.* tensors (smtts_has_part(h, 4)).  x f32 (B,N,64)

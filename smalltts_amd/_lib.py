@@ -69,6 +69,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_ctc_score": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp]),
     "smtts_ctc_greedy": (i32, [vp, vp, vp, vp, i32, i32, i32, vp, vp]),
     "smtts_ctc_align": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp]),
+    "smtts_ctc_align_long_workspace_bytes": (sz, [vp, i32, i32, i32]),
+    "smtts_ctc_align_long": (i32, [vp, vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, vp, vp, vp, vp, vp, sz]),
     "smtts_sv_workspace_bytes": (sz, [vp, i32, i32]),
     "smtts_sv_embed": (i32, [vp, vp, vp, vp, i32, i32, vp, sz, vp]),
     "smtts_sv_cosine": (i32, [vp, vp, vp, vp, i32, i32, i32, vp]),

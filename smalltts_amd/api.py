@@ -21,7 +21,8 @@ from typing import Callable, Dict, Iterable, List, NamedTuple, Optional, Sequenc
 import numpy as np
 import torch
 
-from .engine import ASR_MAX_ROWS, ASR_UPSAMPLE, DEFAULT_PRECISION, SITES, SV_DIM, SV_MAX_ROWS, SV_MIN_FRAMES, HipEngine
+from .engine import (ASR_LONG_MAX_FRAMES, ASR_MAX_ROWS, ASR_UPSAMPLE, CTC_LONG_MAX_TOKENS, DEFAULT_PRECISION, SITES, SV_DIM, SV_MAX_ROWS,
+                     SV_MIN_FRAMES, HipEngine)
 from .weights import DEFAULT_CODEC, CodecSpec, all_param_specs, asr_param_specs, load_weight_file, sv_param_specs
 # the option records (options.py) and the host arithmetic (plans.py) live in modules of their own; every name stays importable from here
 from .options import (ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS, TAKE_JOIN_KEYS, Alignment, Delivery, Endpointing, Piece, Repair, Takes,
@@ -29,8 +30,9 @@ from .options import (ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS, TAKE_JOIN_KEYS, Alignm
                       marked_delivery, save_take)
 from .plans import (CHARS_PER_SECOND, CTC_HOP, HOP_SIZE, NUM_STEPS, SAMPLE_RATE, _CLAUSE_END, _SENTENCE_END, _check_pins,
                     _default_count_tokens, _frames, _hard_cut, _srt_time, _units, codec_spans, estimate_duration, fade_table,
-                    format_srt, frames_of_groups, group_confidence, phoneme_error_rate, piece_seed, plan_long, plan_packed,
-                    repair_seed, splice_pins, split_text, stream_chunks, stream_groups, take_seed, token_groups, word_times)
+                    format_srt, frames_of_groups, group_confidence, long_windows, phoneme_error_rate, piece_seed, plan_long, plan_packed,
+                    repair_seed, speaking_rate, splice_pins, split_text, stream_chunks, stream_groups, take_seed, token_groups,
+                    word_times)
 
 DEFAULT_WEIGHTS = os.environ.get("SMALLTTS_WEIGHTS", "assets/smalltts.smtts")
 
@@ -718,6 +720,90 @@ class SmallTTS:
             raise ValueError("align_wav: the clip is shorter than one codec hop")
         lat = Encoder(engine=self.engine).encode_reference(y.reshape(1, 1, -1))
         return self.align_words([lat[0].numpy()], [phoneme_ids])[0]
+
+    # ---- long recordings: one row of any length up to 36 min ---------------------------------------------------------
+    def _align_long(self, what: str, latents, phoneme_ids):
+        """One recording through engine.asr_logprobs_long and engine.ctc_align_long -> ((spans, tok_logp, score), tokens, frames)."""
+        eng = self.engine
+        if not eng.has("asr"):
+            raise ValueError(f"{what}: needs the recogniser part (SmallTTS(recogniser=True))")
+        x = latents.detach() if isinstance(latents, torch.Tensor) else np.asarray(latents, np.float32)
+        if x.ndim != 2 or int(x.shape[1]) != 64 or not 1 <= int(x.shape[0]) <= ASR_LONG_MAX_FRAMES:
+            raise ValueError(f"{what}: one recording of (N, 64) latents, 1 <= N <= {ASR_LONG_MAX_FRAMES}, got {tuple(x.shape)}")
+        toks = [int(t) for t in phoneme_ids]
+        if len(toks) > CTC_LONG_MAX_TOKENS:
+            raise ValueError(f"{what}: at most {CTC_LONG_MAX_TOKENS} tokens, got {len(toks)}")
+        N = int(x.shape[0])
+        tab = np.zeros((1, max(len(toks), 1)), np.int32)
+        tab[0, :len(toks)] = toks
+        logp = eng.asr_logprobs_long(eng._dev(x, torch.float32))
+        spans, tok_logp, score = eng.ctc_align_long(logp[None], [ASR_UPSAMPLE * N], eng._dev(tab, torch.int32), [0], [len(toks)])
+        spans, tok_logp, score = spans.cpu().numpy(), tok_logp.cpu().numpy(), score.cpu().numpy()
+        return (spans[0, :len(toks)].copy(), tok_logp[0, :len(toks)].copy(), float(score[0])), toks, N
+
+    def align_phonemes_long(self, latents, phoneme_ids: Sequence[int]) -> tuple:
+        """align_phonemes for ONE recording past its limits: latents (N, 64), N <= 16384 (36 min), and at most 16383
+        phoneme ids -> the (spans, tok_logp, score) of one row of align_phonemes.  The recogniser reads the recording in windows of
+        30 s (engine.asr_logprobs_long), the path is found by engine.ctc_align_long; a recording inside align_phonemes' limits gives
+        that call's bits.  A recogniser frame near a window cut has seen its 30 s window, not the whole recording.  UNVALIDATED on
+        trained weights like align_phonemes."""
+        return self._align_long("align_phonemes_long", latents, phoneme_ids)[0]
+
+    def align_words_long(self, latents, phoneme_ids: Sequence[int], return_spans: bool = False):
+        """align_words for ONE recording past its limits: [(index, kind, phonemes, start sample, end sample, confidence), ...], one
+        row of align_words (token_groups, word_times at hop 800, group_confidence).  return_spans: (that list, spans (len(ids), 2)),
+        e.g. for plans.speaking_rate.  Arguments and limits as align_phonemes_long."""
+        (spans, tok_logp, _score), toks, N = self._align_long("align_words_long", latents, phoneme_ids)
+        groups = token_groups(toks)
+        times = word_times(groups, spans, ASR_UPSAMPLE * N, token0=0, hop=CTC_HOP)
+        conf = group_confidence(groups, spans, tok_logp, token0=0)
+        words = [(i, kind, g[1], s, e, c) for (i, kind, s, e), g, c in zip(times, groups, conf)]
+        return (words, spans) if return_spans else words
+
+    def encode_wav_long(self, y: torch.Tensor, enc_frames: int = 1024, enc_context: int = 32) -> torch.Tensor:
+        """Latents (N, 64), on the device, of mono samples at 24 kHz (1-d, on the device), N = samples // hop.  At most enc_frames
+        codec frames: one codec encode.  Longer: segments of enc_frames frames; every segment but the first is encoded together
+        with the enc_context frames of audio in front of it, whose latents are dropped.  The encoder is causal, so context in
+        front is all a segment can miss; how far the default 32 frames reach into its receptive field: DESIGN 8m."""
+        eng = self.engine
+        enc_frames, enc_context = int(enc_frames), int(enc_context)
+        if enc_frames < 1 or enc_context < 0:
+            raise ValueError(f"encode_wav_long: enc_frames >= 1 and enc_context >= 0, got {enc_frames}, {enc_context}")
+        hop = eng.hop
+        n = int(y.numel()) // hop
+        if n <= enc_frames:
+            return eng.codec_encode(y[:n * hop].reshape(1, 1, -1))[0]
+        parts = []
+        for f0 in range(0, n, enc_frames):
+            f1, c = min(f0 + enc_frames, n), min(enc_context, f0)
+            parts.append(eng.codec_encode(y[(f0 - c) * hop:f1 * hop].reshape(1, 1, -1))[0, c:])
+        return torch.cat(parts)
+
+    def align_wav_long(self, audio, sr: int, phoneme_ids: Sequence[int], enc_frames: int = 1024, enc_context: int = 32,
+                       return_spans: bool = False):
+        """align_wav for a recording of up to 36 min (16384 codec frames): mono samples at `sr` Hz and the phoneme ids of what it
+        says (at most 16383) -> align_words_long's result, times in samples at 24 kHz.  The clip is resampled on the device,
+        encoded by encode_wav_long (one encode up to enc_frames frames, else segments with enc_context frames of context; not
+        through the reference cache) and aligned by align_words_long.  Samples behind the last whole codec hop are not aligned.
+        On a clip inside align_wav's limits and enc_frames the result is align_wav's."""
+        a = np.asarray(audio, np.float32)
+        if a.ndim != 1 and not (a.ndim == 2 and 1 in a.shape):
+            raise ValueError(f"align_wav_long: a mono recording, got an array of shape {a.shape}")
+        sr = int(sr)
+        if sr < 1 or a.size < 1:
+            raise ValueError(f"align_wav_long: at least one sample at a positive rate, got {a.size} samples at {sr} Hz")
+        if not self.engine.has("asr"):
+            raise ValueError("align_wav_long: needs the recogniser part (SmallTTS(recogniser=True))")
+        if a.size / sr * SAMPLE_RATE >= (ASR_LONG_MAX_FRAMES + 1) * HOP_SIZE:
+            raise ValueError(f"align_wav_long: at most {ASR_LONG_MAX_FRAMES} codec frames ({ASR_LONG_MAX_FRAMES * HOP_SIZE / SAMPLE_RATE / 60:.1f} "
+                             f"min) of audio, got {a.size / sr / 60:.1f} min")
+        y = self.engine.resample(a.reshape(-1), sr, SAMPLE_RATE)
+        n = int(y.numel()) // HOP_SIZE
+        if n < 1:
+            raise ValueError("align_wav_long: the clip is shorter than one codec hop")
+        if n > ASR_LONG_MAX_FRAMES:
+            y = y[:ASR_LONG_MAX_FRAMES * HOP_SIZE]
+        return self.align_words_long(self.encode_wav_long(y, enc_frames, enc_context), phoneme_ids, return_spans=return_spans)
 
     def realign(self, pieces: Sequence[Piece]) -> List[Piece]:
         """The Pieces of a take with `spans` replaced by the recogniser's: align_phonemes on every piece's latents and tokens (its

@@ -220,6 +220,24 @@ int smtts_ctc_align(smtts_handle h, void* stream, const float* logp, const int32
     return e == hipSuccess ? 0 : E.fail_hip(e, "ctc_align");
 }
 
+size_t smtts_ctc_align_long_workspace_bytes(smtts_handle h, int B, int T, int P) { NULLCHK0;
+    if (B < 1 || B > 64) return 0;
+    return ctc_align_long_ws_bytes(B, T, P);
+}
+int smtts_ctc_align_long(smtts_handle h, void* stream, const float* logp, const int32_t* t_len, const int32_t* tokens, const int32_t* p0,
+                         const int32_t* p1, int B, int T, int P, int C, int32_t* spans, float* tok_logp, int32_t* frame_tok, float* score,
+                         void* ws, size_t ws_bytes) { NULLCHK;
+    if (B < 1 || B > 64) return E.fail("smtts_ctc_align_long: B must be in [1, 64]");
+    if (T < 1 || T > 65536 || P < 1 || P > 16383 || C < 2 || C > 256)
+        return E.fail("smtts_ctc_align_long: T must be in [1, 65536], P in [1, 16383] and C in [2, 256] (32 extended states per thread of one workgroup)");
+    if (!logp || !t_len || !tokens || !p0 || !p1 || !spans || !tok_logp || !score) return E.fail("smtts_ctc_align_long: a required pointer is NULL");
+    if (!ws || ((uintptr_t)ws & 255)) return E.fail("smtts_ctc_align_long: the workspace must be 256-byte aligned");
+    if (ws_bytes < ctc_align_long_ws_bytes(B, T, P))
+        return E.fail("smtts_ctc_align_long: the workspace is smaller than smtts_ctc_align_long_workspace_bytes(h, B, T, P)");
+    hipError_t e = launch_ctc_align_long(logp, t_len, tokens, p0, p1, B, T, P, C, spans, tok_logp, frame_tok, score, ws, ST(stream));
+    return e == hipSuccess ? 0 : E.fail_hip(e, "ctc_align_long");
+}
+
 size_t smtts_sv_workspace_bytes(smtts_handle h, int B, int N) { NULLCHK0; return E.sv_workspace_bytes(B, N); }
 int smtts_sv_embed(smtts_handle h, void* stream, const float* x, const int32_t* n_len, int B, int N, void* ws, size_t ws_bytes,
                    float* emb) { NULLCHK;

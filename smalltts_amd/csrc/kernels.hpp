@@ -101,6 +101,14 @@ hipError_t launch_ctc_greedy(const float* logp, const int* t_len, int B, int T, 
 // per row, the 2-bit moves in dynamic LDS sized by T and P.  1 <= T <= 1024, 1 <= P <= 198, 2 <= C <= 256, else hipErrorInvalidValue.
 hipError_t launch_ctc_align(const float* logp, const int* t_len, const int* tokens, const int* p0, const int* p1, int B, int T, int P, int C,
                             int* spans, float* tok_logp, int* frame_tok, float* score, hipStream_t st);
+// ---- long CTC alignment (ctc_long.hip) -------------------------------------------------------------------------------------------------
+// launch_ctc_align's definition and outputs for rows past its limits: delta in registers (32 states per thread), the 2-bit moves in the
+// workspace table [t][thread], the trace through LDS in chunks of 256 steps.  ws: ctc_align_long_ws_bytes(B, T, P) bytes (a multiple of
+// 256, 0 outside the range), 256-byte aligned, contents irrelevant.  1 <= T <= 65536, 1 <= P <= 16383, 2 <= C <= 256, else
+// hipErrorInvalidValue.
+size_t ctc_align_long_ws_bytes(int B, int T, int P);
+hipError_t launch_ctc_align_long(const float* logp, const int* t_len, const int* tokens, const int* p0, const int* p1, int B, int T, int P,
+                                 int C, int* spans, float* tok_logp, int* frame_tok, float* score, void* ws, hipStream_t st);
 // ---- recogniser (asr.hip) -----------------------------------------------------------------------------------------------------------
 // Device pointers of the packed recogniser weights (Engine::finalize_asr): every 64 x 64 block of a product's weight transposed to
 // [k][n], 16-byte aligned; vectors as loaded.

@@ -15,6 +15,7 @@ import torch
 from . import _lib
 from ._lib import ACT, PRECISION, PRESETS, SITES, ptr as _p   # noqa: F401  (the codes stay importable from here)
 from .engine_hooks import EngineHooks
+from .plans import long_windows
 from .operands import (ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS, distinct_slots, fade_len, frames_tokens, is_operand, out_1d, per_row,
                        pool_slots, row_lengths, seg_gain, upload)
 from .weights import (DEFAULT_CODEC, CodecSpec, asr_param_specs, codec_decoder_param_specs, codec_encoder_param_specs,
@@ -24,6 +25,8 @@ N_LAYERS, N_HEADS, HEAD_DIM, LATENT = 12, 8, 120, 64
 DEFAULT_PRECISION = "f16"
 ASR_MAX_ROWS, ASR_UPSAMPLE, ASR_CLASSES = 64, 4, 198   # smtts_asr_logprobs: rows per call, frames per latent frame, phoneme classes
 CTC_ALIGN_MAX_FRAMES = 1024                            # smtts_ctc_align: frames of logp per row (its move table lives in LDS)
+CTC_LONG_MAX_ROWS, CTC_LONG_MAX_FRAMES, CTC_LONG_MAX_TOKENS = 64, 65536, 16383   # smtts_ctc_align_long (moves in the workspace)
+ASR_LONG_MAX_FRAMES = CTC_LONG_MAX_FRAMES // ASR_UPSAMPLE                       # asr_logprobs_long: latent frames of one recording
 SV_MAX_ROWS, SV_MIN_FRAMES, SV_DIM = 64, 6, 192       # smtts_sv_embed: rows per call, the shortest row with an embedding, its width
 
 
@@ -564,17 +567,20 @@ class HipEngine(EngineHooks):
         self._ck(self.lib.smtts_sv_cosine(self.h, self._stream(), _p(emb), _p(ref), B, K, D, _p(cos)), "sv_cosine")
         return cos
 
-    def _ctc_front(self, what, logp, ts, tokens, p0, p1, t_max):
-        """ctc_score / ctc_align: the operand checks (t_max: the most frames, None for no limit) -> (B, T, P, C, the uploaded table)."""
+    def _ctc_front(self, what, logp, ts, tokens, p0, p1, t_max, p_max=ALIGN_MAX_TOKENS, b_max=None):
+        """ctc_score / ctc_align / ctc_align_long: the operand checks (t_max: the most frames, b_max: the most rows, None for no
+        limit; p_max: the most tokens) -> (B, T, P, C, the uploaded table)."""
         if not self._is(logp, torch.float32, None, None, None):
             raise ValueError(f"{what}: logp must be a contiguous fp32 (B,T,C) tensor on the engine's device")
         B, T, Cn = (int(v) for v in logp.shape)
         if not self._is(tokens, torch.int32, B, None):
             raise ValueError(f"{what}: tokens must be a contiguous int32 ({B},P) tensor on the engine's device")
         P = int(tokens.shape[1])
-        if not (1 <= T <= (t_max or T) and 1 <= P <= ALIGN_MAX_TOKENS and 2 <= Cn <= 256):
+        if not (1 <= T <= (t_max or T) and 1 <= P <= p_max and 2 <= Cn <= 256):
             raise ValueError(f"{what}: T = {T}, P = {P}, C = {Cn} outside the supported range "
-                             f"{f'1 <= T <= {t_max}' if t_max else 'T >= 1'}, P <= {ALIGN_MAX_TOKENS}, 2 <= C <= 256")
+                             f"{f'1 <= T <= {t_max}' if t_max else 'T >= 1'}, P <= {p_max}, 2 <= C <= 256")
+        if b_max is not None and B > b_max:
+            raise ValueError(f"{what}: B = {B} rows, at most {b_max} per call")
         per_row(what, B, ts, p0, p1)
         return B, T, P, Cn, self._upload_i32([ts, p0, p1])
 
@@ -605,6 +611,52 @@ class HipEngine(EngineHooks):
         self._ck(self.lib.smtts_ctc_align(self.h, self._stream(), _p(logp), _p(tab[0]), _p(tokens), _p(tab[1]), _p(tab[2]), B, T, P, Cn,
                                           _p(spans), _p(tok_logp), _p(frame_tok), _p(score)), "ctc_align")
         return (spans, tok_logp, score, frame_tok) if frames else (spans, tok_logp, score)
+
+    def ctc_align_long(self, logp: torch.Tensor, ts, tokens: torch.Tensor, p0, p1, frames: bool = False):
+        """ctc_align for rows past its limits (smtts_ctc_align_long; the definition: smtts_ctc_align's): arguments and
+        results as ctc_align, B <= 64, T <= 65536, P <= 16383; wherever both accept a call the results are equal bit for bit.  The
+        moves of the lattice go to the engine's workspace: 8 T ceil((2 P + 1) / 32) + 2 T bytes per row, 512 MiB at the limits.
+        Needs no weights.  One launch on the current stream, no synchronisation."""
+        B, T, P, Cn, tab = self._ctc_front("ctc_align_long", logp, ts, tokens, p0, p1, CTC_LONG_MAX_FRAMES, CTC_LONG_MAX_TOKENS,
+                                           CTC_LONG_MAX_ROWS)
+        spans = torch.empty(B, P, 2, dtype=torch.int32, device=self.device)
+        tok_logp = torch.empty(B, P, device=self.device)
+        score = torch.empty(B, device=self.device)
+        frame_tok = torch.empty(B, T, dtype=torch.int32, device=self.device) if frames else None
+        ws = self._workspace(self.lib.smtts_ctc_align_long_workspace_bytes(self.h, B, T, P))
+        self._ck(self.lib.smtts_ctc_align_long(self.h, self._stream(), _p(logp), _p(tab[0]), _p(tokens), _p(tab[1]), _p(tab[2]), B, T, P,
+                                               Cn, _p(spans), _p(tok_logp), _p(frame_tok), _p(score), _p(ws), ws.numel()),
+                 "ctc_align_long")
+        return (spans, tok_logp, score, frame_tok) if frames else (spans, tok_logp, score)
+
+    def asr_logprobs_long(self, x: torch.Tensor, max_rows: int = ASR_MAX_ROWS) -> torch.Tensor:
+        """Per-frame phoneme log-probabilities of one recording of any length: x fp32 (N,64) contiguous on the device,
+        1 <= N <= 16384 -> logp fp32 (4 N, 198) on the device.  N <= 225: the bits of asr_logprobs.  Longer: windows of 225 latent
+        frames every 180 (the last one moved back to end at N, so every window is full; plans.long_windows), each computed as if
+        alone by smtts_asr_logprobs, max_rows (1 ... 64) windows per call, in order; latent frame n takes its four recogniser frames
+        from the window it lies deeper inside (the cuts are the midpoints of the overlaps).  The result does not depend on
+        max_rows.  A frame near a cut has seen its 30 s window, not the whole recording.  Needs the recogniser part.  Launches on
+        the current stream, no synchronisation."""
+        if not self._is(x, torch.float32, None, LATENT):
+            raise ValueError("asr_logprobs_long: x must be a contiguous fp32 (N,64) tensor on the engine's device")
+        N, max_rows = int(x.shape[0]), int(max_rows)
+        if not 1 <= N <= ASR_LONG_MAX_FRAMES:
+            raise ValueError(f"asr_logprobs_long: N = {N} outside the supported range 1 <= N <= {ASR_LONG_MAX_FRAMES}")
+        if not 1 <= max_rows <= ASR_MAX_ROWS:
+            raise ValueError(f"asr_logprobs_long: max_rows = {max_rows} outside [1, {ASR_MAX_ROWS}]")
+        starts, cuts, _ = long_windows(N)
+        if len(starts) == 1:
+            return self.asr_logprobs(x.unsqueeze(0), [N])[0]
+        Wn = ALIGN_MAX_FRAMES
+        out = torch.empty(ASR_UPSAMPLE * N, ASR_CLASSES, device=self.device)
+        for w0 in range(0, len(starts), max_rows):
+            w1 = min(w0 + max_rows, len(starts))
+            xs = torch.stack([x[a:a + Wn] for a in starts[w0:w1]])
+            lp = self.asr_logprobs(xs, [Wn] * (w1 - w0))
+            for w in range(w0, w1):
+                a, c0, c1 = starts[w], cuts[w], cuts[w + 1]
+                out[ASR_UPSAMPLE * c0:ASR_UPSAMPLE * c1] = lp[w - w0, ASR_UPSAMPLE * (c0 - a):ASR_UPSAMPLE * (c1 - a)]
+        return out
 
     def ctc_greedy(self, logp: torch.Tensor, ts):
         """Greedy CTC transcript of every row (smtts_ctc_greedy): per-frame argmax (lowest class on ties), runs collapsed, class 0

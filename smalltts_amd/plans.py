@@ -295,6 +295,60 @@ CTC_FRAMES_PER_CODEC_FRAME = 4                    # the recogniser runs at 4 fra
 CTC_HOP = HOP_SIZE // CTC_FRAMES_PER_CODEC_FRAME  # 800 samples, 33.3 ms: the resolution of a CTC alignment
 
 
+LONG_WINDOW, LONG_HOP = 225, 180                  # asr_logprobs_long: latent frames per recogniser window, and between window starts
+
+
+def long_windows(N: int) -> Tuple[List[int], List[int], np.ndarray]:
+    """The window table of engine.asr_logprobs_long for a recording of N latent frames -> (starts a_w, cuts c_0 .. c_{n_w},
+    src int32 (N,): the window of every frame).  N <= 225: one window [0, N).  Else n_w = 1 + ceil((N - 225) / 180) full windows,
+    a_w = min(180 w, N - 225); c_0 = 0, c_{n_w} = N, c_w = (a_{w-1} + 225 + a_w) // 2, the midpoint of the overlap of windows w - 1
+    and w: frame n in [c_w, c_{w+1}) comes from window w, at local frame n - a_w."""
+    N = int(N)
+    if N < 1:
+        raise ValueError(f"long_windows: N = {N} must be at least 1")
+    if N <= LONG_WINDOW:
+        return [0], [0, N], np.zeros((N,), np.int32)
+    n_w = 1 + -(-(N - LONG_WINDOW) // LONG_HOP)
+    starts = [min(w * LONG_HOP, N - LONG_WINDOW) for w in range(n_w)]
+    cuts = [0] + [(starts[w - 1] + LONG_WINDOW + starts[w]) // 2 for w in range(1, n_w)] + [N]
+    src = np.repeat(np.arange(n_w, dtype=np.int32), np.diff(np.asarray(cuts, np.int64)))
+    return starts, cuts, src
+
+
+def encoder_lookback(kernel: int, enc_ratios: Sequence[int], enc_depths: Sequence[int]) -> int:
+    """Samples of audio in front of a codec frame's own hop that the causal encoder reads for it (weights.CodecSpec: stem conv, per
+    stage a strided conv of kernel 2 r behind the first and `depth` blocks of one depthwise conv each, head conv; every conv padded
+    on the left by kernel - stride).  A conv whose input sits every j samples looks (kernel - stride) j samples back.  The default
+    codec: 185 562 samples, 58 codec frames (what align_wav_long's enc_context is measured against)."""
+    k, j = int(kernel), 1
+    back = (k - 1) * j + int(enc_depths[0]) * (k - 1) * j       # stem, stage 0
+    for r, depth in zip(enc_ratios, enc_depths[1:]):
+        back += int(r) * j                                      # kernel 2 r, stride r
+        j *= int(r)
+        back += int(depth) * (k - 1) * j
+    return back + (k - 1) * j                                   # head
+
+
+def speaking_rate(spans, max_pause: int = 6) -> Tuple[float, float]:
+    """(tokens per second, seconds of speech) of one aligned row: spans (tokens, 2) = (first, last) recogniser frame per token
+    (smtts_ctc_align, smtts_ctc_align_long), (-1, -1) off the path.  Over the aligned tokens in order: speech runs from the first
+    token's first frame to the last token's last frame, and every gap between consecutive tokens longer than max_pause frames (6 =
+    200 ms) counts as max_pause.  Frames are CTC_HOP = 800 samples at 24 kHz.  Fewer than two aligned tokens: (nan, 0.0)."""
+    sp = np.asarray(spans, np.int64)
+    if sp.ndim != 2 or sp.shape[1] != 2:
+        raise ValueError(f"speaking_rate: spans must be (tokens, 2), got {sp.shape}")
+    max_pause = int(max_pause)
+    if max_pause < 0:
+        raise ValueError(f"speaking_rate: max_pause must be >= 0, got {max_pause}")
+    sp = sp[(sp[:, 0] >= 0) & (sp[:, 1] >= sp[:, 0])]
+    if sp.shape[0] < 2:
+        return float("nan"), 0.0
+    gaps = sp[1:, 0] - sp[:-1, 1] - 1
+    frames = int(sp[-1, 1] - sp[0, 0] + 1 - np.maximum(gaps - max_pause, 0).sum())
+    seconds = frames * CTC_HOP / SAMPLE_RATE
+    return sp.shape[0] / seconds, seconds
+
+
 def codec_spans(spans) -> np.ndarray:
     """Token spans in recogniser frames (smtts_ctc_align) -> the codec frames they touch: (first // 4, last // 4) per token, (-1, -1)
     kept.  The result is what frames_of_groups, respeak and a Piece's `spans` count in."""

@@ -5,6 +5,9 @@ through the recogniser's reading of the audio's latents, 33.3 ms resolution (800
 --wav: a mono recording of at most 30 s and what it says (--text through the tokeniser, or --tokens) -> --words, a JSON list of
 {index, kind, phonemes, start, end (samples at 24 kHz), start_s, end_s, confidence}; confidence is the path's mean log-probability per
 frame over the group's tokens, null where the recording could not be aligned.  --srt: one subtitle cue per word group.
+--long: --wav of any length up to 36 min goes through api.SmallTTS.align_wav_long (the recogniser in 30 s windows, the path by
+smtts_ctc_align_long); --words then holds {"words": that list, "speaking_rate": {"tokens_per_second", "speech_seconds"}}
+(plans.speaking_rate over the aligned phonemes, pauses over 200 ms counted as 200 ms; null where fewer than two phonemes were aligned).
 --take: the pieces of a long take (scripts/longform.py --take) get the recogniser's token spans in place of the text-attention tap's,
 in codec frames, and are written to --out-take with the take's join parameters unchanged: scripts/respeak.py --groups then cuts
 where the recogniser heard the words.  A piece that could not be aligned keeps its spans.
@@ -13,7 +16,7 @@ import argparse
 import json
 from pathlib import Path
 
-from ..api import SAMPLE_RATE, SmallTTS, format_srt, load_take, save_take
+from ..api import SAMPLE_RATE, SmallTTS, format_srt, load_take, save_take, speaking_rate
 from ..audio import read_wav
 from ._common import add_engine_args, tokens_for
 
@@ -26,12 +29,21 @@ def words_json(words) -> str:
                        for i, kind, ph, s, e, c in words], ensure_ascii=False, indent=1)
 
 
+def long_json(words, spans) -> str:
+    """align_wav_long's words and spans -> the --words file of --long."""
+    rate, seconds = speaking_rate(spans)
+    return json.dumps({"words": json.loads(words_json(words)),
+                       "speaking_rate": {"tokens_per_second": round(rate, 4) if rate == rate else None, "speech_seconds": round(seconds, 4)}},
+                      ensure_ascii=False, indent=1)
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--wav", default=None, help="a mono recording of at most 30 s")
     ap.add_argument("--text", default=None, help="what the recording says (or --tokens)")
     ap.add_argument("--words", default=None, metavar="OUT.json", help="write the time of every word / punctuation mark / [event] (33 ms resolution)")
     ap.add_argument("--srt", default=None, metavar="OUT.srt", help="write one subtitle cue per word group")
+    ap.add_argument("--long", action="store_true", help="--wav of up to 36 min (align_wav_long); --words gains the speaking rate")
     ap.add_argument("--take", default=None, metavar="IN.npz", help="a long take (longform --take) to align again")
     ap.add_argument("--out-take", default=None, metavar="OUT.npz", help="where the take with the recogniser's spans goes")
     add_engine_args(ap)
@@ -42,6 +54,8 @@ def main(argv=None):
         ap.error("--wav needs --text or --tokens, and --words or --srt; --out-take belongs to --take")
     if args.take is not None and (not args.out_take or args.text or args.words or args.srt):
         ap.error("--take needs --out-take; --text, --words and --srt belong to --wav")
+    if args.long and args.wav is None:
+        ap.error("--long belongs to --wav")
     print("loading")
     tts = SmallTTS(weights=args.weights, device=args.device, precision=args.precision, num_steps=args.steps, seed=args.seed,
                    recogniser=True)
@@ -50,12 +64,15 @@ def main(argv=None):
         if y.ndim == 2:
             y = y.mean(axis=1)
         try:
-            words = tts.align_wav(y, sr, tokens_for(args, args.text or ""))
+            if args.long:
+                words, spans = tts.align_wav_long(y, sr, tokens_for(args, args.text or ""), return_spans=True)
+            else:
+                words = tts.align_wav(y, sr, tokens_for(args, args.text or ""))
         except ValueError as e:
             ap.error(str(e))
         if args.words:
             Path(args.words).parent.mkdir(parents=True, exist_ok=True)
-            Path(args.words).write_text(words_json(words), encoding="utf-8")
+            Path(args.words).write_text(long_json(words, spans) if args.long else words_json(words), encoding="utf-8")
             print(f"{args.words} ({len(words)} word groups)")
         if args.srt:
             Path(args.srt).parent.mkdir(parents=True, exist_ok=True)
