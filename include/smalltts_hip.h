@@ -53,7 +53,7 @@ int smtts_create(int device_id, smtts_handle* out);
 int smtts_destroy(smtts_handle h);
 const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation error */
 const char* smtts_version(void);
-/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, then smtts_take_scores and smtts_take_select, then the streamed decode entries, then smtts_deliver, then smtts_join_stream and smtts_peek_saturations, then the smtts_watermark entries, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
+/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, then smtts_take_scores and smtts_take_select, then the streamed decode entries, then smtts_deliver, then smtts_join_stream and smtts_peek_saturations, then the smtts_watermark entries, then smtts_retime, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
 #define SMTTS_ABI_VERSION 11
 int smtts_abi_version(void);
@@ -630,6 +630,41 @@ int smtts_stitch_seg(smtts_handle h, void* stream, const float* audio, int B, in
 int smtts_join_stream(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* seg,
                       const float* gain, const float* fade, int F, int64_t gap, int last, int64_t* state /* DEVICE (2): pos, k */,
                       void* chunk, int64_t chunk_cap, int pcm16, int64_t* off, int64_t* rec, int64_t* dtable, int64_t slot);
+/* retiming: time-scale modification of each row onto a table of (source, target) anchors by waveform-similarity
+ * overlap-add (WSOLA): the output is built from segments of H = hop samples; a segment is taken from where the previous one would
+ * have continued if that lies within D = delta samples of where the map says, else from the place within D of the map whose samples
+ * correlate best with that continuation, cross-faded with it.  Pitch is kept; a unit map returns the input's bits.
+ * In:   audio f32 (B,1,row_stride); len i64 (B) DEVICE; anchors i64 (B,A,2) DEVICE = (src, dst) sample positions; n_anchor i64 (B)
+ *       DEVICE; win f32 (2 H) DEVICE, the cross-fade window: win[i] weights the new place, win[H + i] the continuation.
+ * Samples: n = clamp(len[b], 0, row_stride); a source sample x[s] outside [0, n) reads as +0.0, and nothing behind n is loaded.
+ * Map:  m = clamp(n_anchor[b], 0, A) anchors (s_j, d_j) are in use; every entry is clamped as it is loaded, s_j into
+ *       [0, row_stride], d_j into [0, out_stride].  out_len = d_{m-1}; with m < 2 it is 0 and nothing is written.  For
+ *       d_j <= t < d_{j+1}: M(t) = s_j + ((t - d_j) * (s_{j+1} - s_j)) // (d_{j+1} - d_j), int64, // rounding down; for t >= d_{m-1}
+ *       (or where no pair is left): M(t) = s_{m-1} + (t - d_{m-1}); the result is clamped into [0, n].  M is evaluated at t = 0, H,
+ *       2 H, ... in order and the pair index never moves back: from the pair the previous evaluation ended at it advances to the
+ *       first j with d_{j+1} > d_j and d_j <= t < d_{j+1} (a pair with d_{j+1} <= d_j is skipped).  For a table with d_0 = 0 and
+ *       increasing d this is the plain piecewise map; for any other contents it is still defined, and the kernel stays inside its
+ *       buffers: the tables live on the device, so they are clamped, never trusted.
+ * Segments: K = ceil(out_len / H); segment k covers out[k H, min((k + 1) H, out_len)).
+ *       k = 0:  q_0 = M(0), out[i] = x[q_0 + i].
+ *       k >= 1: p = M(k H), c = q_{k-1} + H.  If |c - p| <= D: q_k = c and out[k H + i] = x[c + i], a copy (no arithmetic).
+ *               Else the lags l in [-D, D] with 0 <= p + l <= n are candidates (l = 0 always is one),
+ *               score(l) = sum over i < H of x[c + i] * x[p + l + i] in fp32, in any order, with or without fma; a score that
+ *               comes out NaN (NaN or Inf samples inside len) counts as -inf;
+ *               q_k = p + l*, l* the lag of the largest score, on equal scores the smaller |l|, then the negative lag;
+ *               q_k == c: the copy again; else out[k H + i] = fadd(fmul(x[c + i], win[H + i]), fmul(x[q_k + i], win[i])), three
+ *               separately rounded fp32 operations (no fma), which numpy reproduces bit for bit given q.
+ * Out:  out f32 (B,1,out_stride): row b holds out_len samples, nothing at or behind out_len is written; q i64 (B,Kmax) DEVICE or
+ *       NULL, Kmax = ceil(out_stride / H): q[b][k] = q_k for k < K, nothing at or behind K is written.  audio and out must not
+ *       overlap.
+ * One launch whatever B is, one workgroup per row (the segments of a row are a chain); no atomics, nothing depends on scheduling:
+ *       two calls on equal inputs return equal bits, and a row's results do not depend on its batch-mates.
+ * Refused with 1 and a message naming the entry, nothing enqueued: a NULL handle, audio, len, anchors, n_anchor, win or out; B
+ *       outside [1, 1024]; row_stride or out_stride outside [1, 2^31 - 1] (the map's products then fit int64); A outside [2, 65536];
+ *       hop outside [16, 512] or not a multiple of 4; delta outside [0, 512]. */
+int smtts_retime(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* len /* DEVICE (B) */,
+                 const int64_t* anchors /* DEVICE (B,A,2) */, const int64_t* n_anchor /* DEVICE (B) */, int A, const float* win,
+                 int hop, int delta, float* out, int64_t out_stride, int64_t* q);
 
 /* cond_encode runs the text encoder on a side stream owned by the engine, one per caller stream (fork / join with events; default
  * on: shortest latency for one batch at a time).  Callers that keep several batches in flight on their own streams should turn it

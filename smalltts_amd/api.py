@@ -25,14 +25,14 @@ from .engine import (ASR_LONG_MAX_FRAMES, ASR_MAX_ROWS, ASR_UPSAMPLE, CTC_LONG_M
                      SV_MIN_FRAMES, HipEngine)
 from .weights import DEFAULT_CODEC, CodecSpec, all_param_specs, asr_param_specs, load_weight_file, sv_param_specs
 # the option records (options.py) and the host arithmetic (plans.py) live in modules of their own; every name stays importable from here
-from .options import (ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS, TAKE_JOIN_KEYS, Alignment, Delivery, Endpointing, Piece, Repair, Takes,
-                      Watermark, _Frozen, as_alignment, as_delivery, as_endpointing, as_repair, as_takes, as_watermark, load_take,
-                      marked_delivery, save_take)
+from .options import (ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS, TAKE_JOIN_KEYS, Alignment, Delivery, Endpointing, Piece, Repair, Retime,
+                      Takes, Watermark, _Frozen, as_alignment, as_delivery, as_endpointing, as_repair, as_retime, as_takes, as_watermark,
+                      load_take, marked_delivery, save_take)
 from .plans import (CHARS_PER_SECOND, CTC_HOP, HOP_SIZE, NUM_STEPS, SAMPLE_RATE, _CLAUSE_END, _SENTENCE_END, _check_pins,
                     _default_count_tokens, _frames, _hard_cut, _srt_time, _units, codec_spans, estimate_duration, fade_table,
                     format_srt, frames_of_groups, group_confidence, long_windows, phoneme_error_rate, piece_seed, plan_long, plan_packed,
-                    repair_seed, speaking_rate, splice_pins, split_text, stream_chunks, stream_groups, take_seed, token_groups,
-                    word_times)
+                    repair_seed, retime_anchors, retime_rows, retime_times, speaking_rate, splice_pins, split_text, stream_chunks,
+                    stream_groups, take_seed, token_groups, word_times)
 
 DEFAULT_WEIGHTS = os.environ.get("SMALLTTS_WEIGHTS", "assets/smalltts.smtts")
 
@@ -316,6 +316,40 @@ def _to_output_samples(dv: Optional["Delivery"], segs: List[tuple], words: Optio
     segs = [(dv.samples(o), dv.samples(o + n) - dv.samples(o), dv.samples(st), g) for o, n, st, g in segs]
     words = None if words is None else [(i, kind, dv.samples(a), dv.samples(b)) for i, kind, a, b in words]
     return segs, words
+
+
+RETIME_MAX_ROWS = 64                                   # rows of a long retiming that ride in one engine.retime call
+
+
+def _retimed_words(words, table):
+    """Word rows (align_words' six columns or synthesize_long's four) with start and end mapped through retime_times."""
+    if words is None:
+        return None
+    k = lambda w: 3 if len(w) >= 6 else 2              # the column of the start
+    return [tuple(w[:k(w)]) + (int(retime_times(int(w[k(w)]), table)), int(retime_times(int(w[k(w) + 1]), table))) + tuple(w[k(w) + 2:])
+            for w in words]
+
+
+def _retimed_segments(segs, table):
+    """Segments (offset, n, start, gain) on the joined waveform -> on the retimed one: both ends through retime_times."""
+    out = []
+    for o, n, st, g in segs:
+        a, b = int(retime_times(int(o), table)), int(retime_times(int(o) + int(n), table))
+        out.append((a, b - a, st, g))
+    return out
+
+
+def _long_retime(what: str, retime, pcm16: bool) -> Optional["Retime"]:
+    """The retime= argument of synthesize_long and render_long: a speed or a duration for the joined waveform."""
+    rt = as_retime(retime)
+    if rt is None:
+        return None
+    if rt.to_words is not None:
+        raise ValueError(f"{what}: retime= takes a speed or a duration here; the words are not on the host before the join: align the "
+                         "waveform and call SmallTTS.retime(audio, Retime(to_words=...), words=...)")
+    if pcm16:
+        raise ValueError(f"{what}: retime= and pcm16=True exclude each other: ask for deliver=Delivery(24000, 'pcm16')")
+    return rt
 
 
 def _piece_rows(off, seg, gain, spans, latents, winner, toks, ns, seeds, n_prefix: int, ep: Optional["Endpointing"],
@@ -1200,7 +1234,7 @@ class SmallTTS:
                         fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3, pcm16: bool = False,
                         prefix_tokens: Optional[Sequence[int]] = None, trim=None, return_segments: bool = False,
                         return_words: bool = False, align=None, return_pieces: bool = False, takes=None, return_takes: bool = False,
-                        repair=None, return_repair: bool = False, deliver=None, watermark=None):
+                        repair=None, return_repair: bool = False, deliver=None, watermark=None, retime=None):
         """A whole text in one voice -> one waveform (1, S), fp32 or (pcm16=True) int16 PCM, S = sum(3200 * n_i) + (pieces - 1) *
         round(gap_ms * 24).
 
@@ -1256,13 +1290,21 @@ class SmallTTS:
         pcm16=True (ask for Delivery(rate, "pcm16")).  None is the call as it always was.
         `watermark` (a Watermark, a key or a (key, strength) pair): the JOINED waveform is marked on the device in front of
         the delivery, as one stream from sample 0; without `deliver` it means Delivery(24000, "f32").  24 kHz, f32 or pcm16 only.
+        `retime` (a Retime with a speed or a duration, or a number = a speed): the JOINED waveform is retimed on the device
+        (engine.retime: WSOLA, the pitch is kept) behind the join and in front of the watermark and the delivery, so that a mark is
+        embedded in the samples that leave.  Retime(duration=d) gives exactly round(d * 24000) samples at 24 kHz.  Segments and words
+        are mapped through plans.retime_times (a segment's start inside its piece stays a position in the piece).  Not with
+        pcm16=True; Retime(to_words=...) belongs to SmallTTS.retime.  None is the call as it always was, Retime(speed=1.0) its bits.
         Returns (waveform[, segments][, words][, pieces][, takes][, repair])."""
+        rt = _long_retime("synthesize_long", retime, pcm16)
         q = self._long_request("synthesize_long", voice, text, token_lists, durations, prefix_tokens, max_batch, pcm16, trim, align,
                                return_words, takes, repair, deliver, watermark, reports=(return_takes, return_repair))
         dv, ep, tk, K, toks, ns = q.dv, q.ep, q.tk, q.K, q.toks, q.ns
         groups, offsets, S = plan_long(ns, q.max_batch, gap_ms)
 
-        def result(out, segs, words, made, taken=None, mended=None):   # words None: not aligned
+        def result(out, segs, words, made, taken=None, mended=None, table=None):   # words None: not aligned
+            if table is not None:
+                segs, words = _retimed_segments(segs, table), _retimed_words(words, table)
             segs, words = _to_output_samples(dv, segs, words)
             res = ((out,) + ((segs,) if return_segments else ()) + ((words,) if words is not None else ())
                    + ((made,) if return_pieces else ()) + ((taken,) if return_takes else ()) + ((mended,) if return_repair else ()))
@@ -1274,7 +1316,7 @@ class SmallTTS:
         base = self._next_seed() if seed is None else int(seed)
         seeds = [piece_seed(base, i) for i in range(len(toks))]
         calls, _al_b = self._long_calls(voice, toks, ns, seeds, groups, len(q.prefix), ep, q.al, tk, q.rp, return_takes)
-        out, segs, pending = self._join_long(calls, groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16, dv, q.wm)
+        out, segs, pending, table = self._join_long(calls, groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16, dv, q.wm, rt)
         win = taken = None
         mended = _read_repair(pending) if return_repair else None   # one small read-back for the whole text
         if tk is not None and (return_takes or return_pieces):
@@ -1297,14 +1339,16 @@ class SmallTTS:
                                       None if win is None else [win[i] for i in g], [toks[i] for i in g], [ns[i] for i in g],
                                       [seeds[i] for i in g], len(q.prefix), ep, return_words, return_pieces, len(words or ()))
             words, made = (words + w if return_words else None), (made + m if return_pieces else None)
-        return result(out, segs, words, made, taken, mended)
+        return result(out, segs, words, made, taken, mended, table)
 
     def _join_long(self, calls, groups, ns, offsets, S, ep: Optional["Endpointing"], in_flight: int, gap_ms: float, fade_ms: float,
-                   pcm16: bool, dv: Optional["Delivery"] = None, wm: Optional["Watermark"] = None):
+                   pcm16: bool, dv: Optional["Delivery"] = None, wm: Optional["Watermark"] = None, rt: Optional["Retime"] = None):
         """The tail synthesize_long and render_long share: the deferred batches `calls` (one per group) run through _run_in_flight,
         their rows are joined on the device and copied out once.  With `ep` the records carry their endpoints (every batch enqueued
         them behind its decode, and so does its re-run): the tables are read back once and the join puts the speech windows `gap_ms`
-        apart, which replaces `offsets` and `S`.  -> (waveform (1, S), segments, the finished batches)."""
+        apart, which replaces `offsets` and `S`.  With `rt` the joined row is retimed behind the join, in front of the mark and the
+        delivery.  -> (waveform (1, S), segments on the JOINED waveform, the finished batches, the retiming's anchor table or
+        None: what maps the segments onto the waveform returned)."""
         eng = self.engine
         pending = self._run_in_flight(calls, in_flight)
         if ep is not None:
@@ -1323,19 +1367,83 @@ class SmallTTS:
                 eng.stitch(rec.audio, rec.ns, offs, fade, out)
             else:
                 eng.stitch_seg(rec.audio, rec.seg, rec.gain if ep.level_dbfs is not None else None, offs, fade, out)
+        table = None
+        if rt is not None and S > 0:
+            anchors, _clamped = retime_anchors(S, speed=rt.speed, duration=rt.duration)
+            out, table = self._retime_device(out, anchors, None, rt)
+            S = int(out.numel())
         if dv is not None:                                     # the joined waveform, one row, at the caller's rate and encoding
             if S == 0:
-                return np.zeros((1, 0), dv.dtype), segs, pending
+                return np.zeros((1, 0), dv.dtype), segs, pending, table
             d, cnt = eng.deliver(out.view(1, 1, S), [S], dv.rate, dv.encoding, mark=wm)
-            return d[:, :cnt[0]].cpu().numpy(), segs, pending
-        return out.cpu().numpy()[None], segs, pending
+            return d[:, :cnt[0]].cpu().numpy(), segs, pending, table
+        return out.cpu().numpy()[None], segs, pending, table
+
+    # ---- retiming: WSOLA on the device onto a speed, a length or word times --------------------------------------------
+    def _retime_device(self, y: torch.Tensor, anchors, words, rt: "Retime", max_row: int = 30 * SAMPLE_RATE):
+        """y: 24 kHz samples, 1-d fp32 on the device, and the anchor table of their retiming -> (the retimed samples, 1-d on the
+        device, the table in force).  Up to max_row samples in and out: one row, the table as given.  Longer: plans.retime_rows cuts
+        rows (in aligned pauses of `words` where there are any), RETIME_MAX_ROWS of them ride in one engine.retime call, and
+        engine.stitch_seg places them one behind the other (no fade, no gain); the table then holds the cuts.  Gathering a group is
+        a host-side loop: one zeroed (rows, 1, longest row) tensor and one device-to-device slice copy per row, up to 64 per group;
+        fine for rows of 30 s in a stage that is off by default, not built for throughput."""
+        eng = self.engine
+        rows, table = retime_rows(int(y.numel()), anchors, words, max_row=max_row)
+        if len(rows) == 1:
+            out, lens = eng.retime(y.view(1, 1, -1), [int(y.numel())], [rows[0][3]], hop=rt.hop, delta=rt.delta)
+            return out.view(-1)[:lens[0]], table
+        joined = torch.zeros(int(table[-1, 1]), device=eng.device)
+        for g0 in range(0, len(rows), RETIME_MAX_ROWS):
+            grp = rows[g0: g0 + RETIME_MAX_ROWS]
+            batch = torch.zeros(len(grp), 1, max(r[1] for r in grp), device=eng.device)
+            for b, (s0, sn, _d0, _tab) in enumerate(grp):
+                batch[b, 0, :sn] = y[s0: s0 + sn]
+            out, lens = eng.retime(batch, [r[1] for r in grp], [r[3] for r in grp], hop=rt.hop, delta=rt.delta)
+            seg = eng._upload_i64([[0, n] for n in lens])
+            eng.stitch_seg(out, seg, None, [r[2] for r in grp], None, joined)
+        return joined, table
+
+    def retime(self, audio, retime, *, words=None):
+        """Retimes 24 kHz mono audio of any length on the device (engine.retime: WSOLA, the pitch is kept) -> (waveform
+        (1, S_out) fp32, `words` mapped through plans.retime_times or None, the group indices of the words that were clamped).
+        `retime`: a Retime, or a number = a speed.  Retime(speed=) / Retime(duration=): S_out = round(n / speed) / round(duration *
+        24000).  Retime(to_words=rows): `words` says where the words are now (align_wav's or align_words' rows) and `rows` where they
+        shall lie (plans.retime_anchors); every word that is not reported as clamped then starts and ends exactly at its target
+        (reported is also a word that abuts the word in front or starts at sample 0 and was sent somewhere else).  Audio longer
+        than 30 s is cut into rows in the middle of aligned pauses of `words` (plans.retime_rows).  How retimed speech sounds is
+        untested: nobody has listened to it."""
+        rt = as_retime(retime)
+        if rt is None:
+            raise ValueError("retime: a Retime (or a speed) is needed")
+        a = audio.detach().cpu().numpy() if isinstance(audio, torch.Tensor) else np.asarray(audio)
+        a = a.astype(np.float32, copy=False)
+        if (a.ndim != 1 and not (a.ndim == 2 and 1 in a.shape)) or a.size < 1:
+            raise ValueError(f"retime: mono audio of at least one sample, got an array of shape {a.shape}")
+        if rt.to_words is not None and words is None:
+            raise ValueError("retime: Retime(to_words=...) needs words=, where the words are now")
+        n = int(a.size)
+        anchors, clamped = retime_anchors(n, speed=rt.speed, duration=rt.duration, words=words if rt.to_words is not None else None,
+                                          to_words=rt.to_words, min_rate=rt.min_rate, max_rate=rt.max_rate)
+        y = torch.from_numpy(np.ascontiguousarray(a.reshape(-1))).to(self.engine.device)
+        out, table = self._retime_device(y, anchors, words, rt)
+        return out.cpu().numpy()[None], _retimed_words(None if words is None else list(words), table), clamped
+
+    def retime_wav(self, audio, sr: int, phoneme_ids: Sequence[int], retime, long: bool = False):
+        """A recording and what it says, retimed: mono samples at `sr` Hz are resampled to 24 kHz on the device, aligned (align_wav,
+        or with long=True align_wav_long, for up to 36 min) and retimed -> retime()'s triple, the words being the alignment's rows
+        mapped onto the result.  Needs SmallTTS(recogniser=True), like the aligners."""
+        if not self.engine.has("asr"):
+            raise ValueError("retime_wav: needs the recogniser part (SmallTTS(recogniser=True))")
+        words = self.align_wav_long(audio, sr, phoneme_ids) if long else self.align_wav(audio, sr, phoneme_ids)
+        y = self.engine.resample(np.asarray(audio, np.float32).reshape(-1), int(sr), SAMPLE_RATE)
+        return self.retime(y.reshape(-1), retime, words=words)
 
     def synthesize_long_stream(self, voice: Voice, text: Optional[str] = None, *, token_lists: Optional[Sequence[Sequence[int]]] = None,
                                durations: Optional[Sequence[float]] = None, seed: Optional[int] = None, gap_ms: float = 120.0,
                                fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3, pcm16: bool = False,
                                prefix_tokens: Optional[Sequence[int]] = None, trim=None, align=None, return_words: bool = False,
                                return_pieces: bool = False, takes=None, repair=None, deliver=None,
-                               batch_sizes: Optional[Sequence[int]] = (1, 2, 4, 8), watermark=None):
+                               batch_sizes: Optional[Sequence[int]] = (1, 2, 4, 8), watermark=None, retime=None):
         """synthesize_long handed out batch by batch: a generator of LongChunk(audio, index, offset, segments, words,
         pieces), one per group of pieces, whose audio concatenated along axis 1 is the joined waveform.  The arguments are
         synthesize_long's (without the return_takes / return_repair reports; the segments always come, in the chunks).
@@ -1358,7 +1466,11 @@ class SmallTTS:
         chunk into the next; the last chunk flushes).
 
         Closing the generator early waits for what is in flight and leaves the engine as a finished call does.  Empty text yields
-        nothing.  Arguments are checked here, before the first next()."""
+        nothing.  Arguments are checked here, before the first next().  `retime` is refused: a chain's state is not carried across
+        chunks; retime the whole text with synthesize_long."""
+        if retime is not None:
+            raise ValueError("synthesize_long_stream: retime= is not streamed (no chain state is carried across chunks): use "
+                             "synthesize_long(retime=)")
         q = self._long_request("synthesize_long_stream", voice, text, token_lists, durations, prefix_tokens, max_batch, pcm16, trim,
                                align, return_words, takes, repair, deliver, watermark)
         toks, ns = q.toks, q.ns
@@ -1488,14 +1600,16 @@ class SmallTTS:
             eng.check_fp16_range("synthesize_long_stream")
 
     def render_long(self, pieces, *, gap_ms: float = 120.0, fade_ms: float = 5.0, max_batch: int = 8, in_flight: int = 3,
-                    pcm16: bool = False, trim=None, return_segments: bool = False):
+                    pcm16: bool = False, trim=None, return_segments: bool = False, retime=None):
         """The decode, endpoints and join half of synthesize_long for given latents: `pieces` are Pieces
         (synthesize_long(return_pieces=True)) or (n_i, 64) arrays, in order.  They are grouped as plan_long groups them, decoded
         through the same in-flight machinery under the same tuning and joined by the same kernels, so that the pieces of a take,
         rendered with the take's parameters, give the take's waveform again bit for bit; with one piece replaced by a re-spoken
         one of the same length every other piece's segment stays as it was (the decoder is causal and rows do not see each other).
         A replacement of another length changes the shape of its group's batch: the other rows of that group then agree within the
-        engine's batch-shape tolerance, not bit for bit.  -> waveform (1, S)[, segments] as synthesize_long."""
+        engine's batch-shape tolerance, not bit for bit.  `retime`: synthesize_long's, on the joined row.  -> waveform (1, S)[,
+        segments] as synthesize_long."""
+        rt = _long_retime("render_long", retime, pcm16)
         ep = as_endpointing(trim)
         lats = _piece_latents(pieces)
         ns = [int(l.shape[0]) for l in lats]
@@ -1518,7 +1632,10 @@ class SmallTTS:
                 return _Batch(audio, x, None, None, seg, gain, g_ns, run)
             return run
 
-        out, segs, _pending = self._join_long([decode_only(g) for g in groups], groups, ns, offsets, S, ep, in_flight, gap_ms, fade_ms, pcm16)
+        out, segs, _pending, table = self._join_long([decode_only(g) for g in groups], groups, ns, offsets, S, ep, in_flight, gap_ms,
+                                                     fade_ms, pcm16, rt=rt)
+        if table is not None:
+            segs = _retimed_segments(segs, table)
         return (out, segs) if return_segments else out
 
     def respeak(self, tokens: Sequence[int], latents, frames: Tuple[int, int], *, voice: Optional[Voice] = None, ref_latents=None,

@@ -15,7 +15,7 @@ import torch
 from . import _lib
 from ._lib import ACT, PRECISION, PRESETS, SITES, ptr as _p   # noqa: F401  (the codes stay importable from here)
 from .engine_hooks import EngineHooks
-from .plans import long_windows
+from .plans import long_windows, retime_window
 from .operands import (ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS, distinct_slots, fade_len, frames_tokens, is_operand, out_1d, per_row,
                        pool_slots, row_lengths, seg_gain, upload)
 from .weights import (DEFAULT_CODEC, CodecSpec, asr_param_specs, codec_decoder_param_specs, codec_encoder_param_specs,
@@ -81,6 +81,7 @@ class HipEngine(EngineHooks):
         self._ws_slot: Optional[str] = None   # set via use_workspace(): separate scratch per concurrent stream
         self.codec_spec: CodecSpec = DEFAULT_CODEC
         self._banks: Dict[tuple, tuple] = {}   # (down, up) -> (polyphase bank on the device, width)
+        self._retime_wins: Dict[int, torch.Tensor] = {}   # hop -> the cross-fade window on the device (plans.retime_window)
         self._demoted: Dict[str, str] = {}     # site -> why: sites the fp16 range guard moved to split-bf16 (sticky across set_precision)
         self.calibration: Optional[Dict[str, object]] = None   # last calibrate() report on the loaded weights
         self.dual_stream = os.environ.get("SMTTS_SINGLE_STREAM", "") != "1"   # what the library starts with (set_dual_stream)
@@ -1240,6 +1241,57 @@ class HipEngine(EngineHooks):
         self._ck(self.lib.smtts_watermark_detect(self.h, self._stream(), _p(audio), B, row, _p(lens_d), key, o_lo, n_off, _p(ws), need,
                                                  _p(u), _p(den), _p(T), _p(best_off), _p(best_z)), "watermark_detect")
         return (T, den, best_off, best_z, u) if return_u else (T, den, best_off, best_z)
+
+    # ---- retiming: WSOLA onto a table of anchors (include/smalltts_hip.h smtts_retime) ----
+    def retime(self, audio: torch.Tensor, lens, anchors, *, hop: int = 240, delta: int = 120, return_q: bool = False):
+        """audio (B,1,S) fp32 on the device, row b = lens[b] samples at 24 kHz; anchors: per row one integer array (m_b, 2) = (src,
+        dst) on the host (plans.retime_anchors) -> (out (B,1,S_out) fp32 on the device, out_lens[, q]): row b holds out_lens[b] =
+        its last dst samples, zeros behind; S_out is the largest of them.  q int64 (B, ceil(S_out / hop)): the source position every
+        segment was taken from (row b: ceil(out_lens[b] / hop) entries, zeros behind).  A table starts at dst 0, src and dst
+        increase strictly, 0 <= src <= lens[b], and between two anchors the source runs at 1/8 to 8 times the output's speed.
+        One launch on the current stream, no synchronisation."""
+        B, row, ln = self._audio_rows("retime", audio, lens)
+        hop, delta = int(hop), int(delta)
+        if B > 1024 or row > 2 ** 31 - 1:
+            raise ValueError(f"retime: at most 1024 rows of at most 2^31 - 1 samples, got {B} x {row}")
+        if not 16 <= hop <= 512 or hop % 4 or not 0 <= delta <= 512:
+            raise ValueError(f"retime: hop a multiple of 4 in [16, 512] and delta in [0, 512] wanted, got {hop}, {delta}")
+        if len(anchors) != B:
+            raise ValueError(f"retime: one anchor table per row wanted, got {len(anchors)} for {B} rows")
+        tabs = [np.asarray(a) for a in anchors]
+        for b, a in enumerate(tabs):
+            if a.ndim != 2 or a.shape[1] != 2 or not 2 <= a.shape[0] <= 65536 or a.dtype.kind not in "iu":
+                raise ValueError(f"retime: anchors[{b}] must be an integer (m, 2) array of (src, dst) with 2 <= m <= 65536, got "
+                                 f"{a.dtype} {a.shape}")
+        tabs = [a.astype(np.int64) for a in tabs]
+        for b, a in enumerate(tabs):
+            ds, dd = np.diff(a[:, 0]), np.diff(a[:, 1])
+            if a[0, 1] != 0:
+                raise ValueError(f"retime: anchors[{b}] must start at dst 0, got {int(a[0, 1])}")
+            if (ds <= 0).any() or (dd <= 0).any():
+                raise ValueError(f"retime: src and dst of anchors[{b}] must both increase strictly")
+            if a[0, 0] < 0 or a[-1, 0] > ln[b]:
+                raise ValueError(f"retime: src of anchors[{b}] must lie in [0, {ln[b]}], got [{int(a[0, 0])}, {int(a[-1, 0])}]")
+            if (ds > 8 * dd).any() or (dd > 8 * ds).any():
+                raise ValueError(f"retime: between two anchors of anchors[{b}] the source must run at 1/8 to 8 times the output's speed")
+            if a[-1, 1] > 2 ** 31 - 1:
+                raise ValueError(f"retime: anchors[{b}] ends behind 2^31 - 1 output samples")
+        A = max(a.shape[0] for a in tabs)
+        out_lens = [int(a[-1, 1]) for a in tabs]
+        S_out = max(out_lens)
+        padded = np.zeros((B, A, 2), np.int64)
+        for b, a in enumerate(tabs):
+            padded[b, :a.shape[0]] = a
+        tab = self._upload_i64(np.concatenate([np.asarray(ln, np.int64), np.asarray([a.shape[0] for a in tabs], np.int64),
+                                               padded.reshape(-1)]))
+        win = self._retime_wins.get(hop)
+        if win is None:
+            win = self._retime_wins[hop] = torch.from_numpy(retime_window(hop)).to(self.device)
+        out = torch.zeros(B, 1, S_out, device=self.device)     # a row's tail behind its own length is not written by the kernel
+        q = torch.zeros(B, (S_out + hop - 1) // hop, dtype=torch.int64, device=self.device) if return_q else None
+        self._ck(self.lib.smtts_retime(self.h, self._stream(), _p(audio), B, row, _p(tab[:B]), _p(tab[2 * B:]), _p(tab[B: 2 * B]), A,
+                                       _p(win), hop, delta, _p(out), S_out, _p(q)), "retime")
+        return (out, out_lens, q) if return_q else (out, out_lens)
 
     def profile(self, on, tagged: bool = False, shapes: bool = False):
         """on: False/True; tagged=True prefixes kernel names with the pipeline phase (enc, mod, dit, dec.s<i> ...); shapes=True

@@ -1,5 +1,5 @@
-"""The option records of the synthesis calls (api.py): what `trim=`, `align=`, `takes=`, `repair=`, `deliver=` and `watermark=`
-turn into, the Piece of a long take and its file.  Host only: no torch and no engine here."""
+"""The option records of the synthesis calls (api.py): what `trim=`, `align=`, `takes=`, `repair=`, `deliver=`, `watermark=` and
+`retime=` turn into, the Piece of a long take and its file.  Host only: no torch and no engine here."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -295,6 +295,51 @@ def marked_delivery(what: str, watermark, dv: Optional["Delivery"]):
         raise ValueError(f"{what}: watermark= needs 24000 Hz and f32 or pcm16 (the mark would not survive resampling or G.711), "
                          f"got {dv!r}")
     return wm, dv
+
+
+class Retime(_Record):
+    """A retiming of the 24 kHz waveform on the device (immutable; DESIGN 8n, include/smalltts_hip.h smtts_retime): WSOLA onto
+    exactly one target.  `speed` > 0: the audio runs `speed` times as fast, round(n / speed) samples; `duration` > 0 seconds: it
+    lasts round(duration * 24000) samples; `to_words`: word rows as align_words returns them, where every word shall lie
+    (SmallTTS.retime, together with the words' present times).  `hop` (a multiple of 4 in [16, 512]) is the segment, `delta` (0 ..
+    512) how far a segment's source may lie from where the map says.  `min_rate` / `max_rate` bound a word's rate (source samples
+    per output sample) under to_words; a word outside keeps its start, has its length clamped and is reported.  Pitch is kept; how
+    retimed speech sounds has never been listened to: only the signal properties of DESIGN 8n are tested."""
+    __slots__ = ("speed", "duration", "to_words", "hop", "delta", "min_rate", "max_rate")
+
+    def __init__(self, speed: Optional[float] = None, duration: Optional[float] = None, to_words=None, hop: int = 240, delta: int = 120,
+                 min_rate: float = 0.5, max_rate: float = 2.0) -> None:
+        if (speed is not None) + (duration is not None) + (to_words is not None) != 1:
+            raise ValueError("Retime: exactly one of speed, duration and to_words")
+        for name, v in (("speed", speed), ("duration", duration)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating))):
+                raise TypeError(f"Retime: {name} must be a number, got {type(v).__name__}")
+            if v is not None and not (np.isfinite(float(v)) and float(v) > 0.0):
+                raise ValueError(f"Retime: {name} must be a positive number, got {v!r}")
+        for name, v in (("hop", hop), ("delta", delta)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"Retime: {name} must be an integer, got {type(v).__name__}")
+        if not 16 <= int(hop) <= 512 or int(hop) % 4:
+            raise ValueError(f"Retime: hop must be a multiple of 4 in [16, 512], got {int(hop)}")
+        if not 0 <= int(delta) <= 512:
+            raise ValueError(f"Retime: delta must lie in [0, 512], got {int(delta)}")
+        if not (np.isfinite(float(min_rate)) and np.isfinite(float(max_rate)) and 0.0 < float(min_rate) <= float(max_rate)):
+            raise ValueError(f"Retime: 0 < min_rate <= max_rate wanted, got {min_rate!r}, {max_rate!r}")
+        if to_words is not None:
+            to_words = tuple(tuple(w) for w in to_words)
+            if not to_words or not all(len(w) >= 4 for w in to_words):
+                raise ValueError("Retime: to_words must be a non-empty list of word rows (align_words)")
+        self._set(speed=None if speed is None else float(speed), duration=None if duration is None else float(duration),
+                  to_words=to_words, hop=int(hop), delta=int(delta), min_rate=float(min_rate), max_rate=float(max_rate))
+
+
+def as_retime(retime) -> Optional["Retime"]:
+    """The `retime=` argument: None -> None (off: the call as it always was), a Retime -> itself, a number -> Retime(speed=number)."""
+    if retime is None or isinstance(retime, Retime):
+        return retime
+    if not isinstance(retime, bool) and isinstance(retime, (int, float, np.integer, np.floating)):
+        return Retime(speed=float(retime))
+    raise TypeError(f"retime must be None, a speed or a Retime, got {type(retime).__name__}")
 
 
 class Piece(_Frozen):

@@ -443,3 +443,204 @@ def repair_seed(seed: int, r: int) -> int:
     if int(r) < 1:
         raise ValueError(f"repair_seed: rounds count from 1, got {int(r)}")
     return int(np.random.SeedSequence([int(seed), int(r), 0x52455052]).generate_state(1, np.uint64)[0] >> 1)
+
+
+# ---- retiming (include/smalltts_hip.h smtts_retime): the anchor tables and the integer maps --------------------------
+RETIME_MIN_SLOPE, RETIME_MAX_SLOPE = 0.125, 8.0   # what engine.retime accepts between two anchors, source samples per output sample
+
+
+def retime_window(hop: int) -> np.ndarray:
+    """The cross-fade window of smtts_retime, (2 hop,) fp32: w[i] = 0.5 - 0.5 cos(2 pi (i + 0.5) / (2 hop)) in float64, rounded to
+    fp32 once.  w[i] rises over i < hop (the new place's weight), w[hop + i] falls (the continuation's); w[i] + w[hop + i] = 1 up to
+    rounding."""
+    hop = int(hop)
+    if hop < 1:
+        raise ValueError(f"retime_window: hop must be at least 1, got {hop}")
+    return (0.5 - 0.5 * np.cos(2.0 * np.pi * (np.arange(2 * hop, dtype=np.float64) + 0.5) / (2 * hop))).astype(np.float32)
+
+
+def _retime_table(what: str, anchors) -> np.ndarray:
+    a = np.asarray(anchors, np.int64)
+    if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 2:
+        raise ValueError(f"{what}: anchors must be (m, 2) = (src, dst) with m >= 2, got {a.shape}")
+    if a[0, 1] != 0 or (np.diff(a[:, 0]) <= 0).any() or (np.diff(a[:, 1]) <= 0).any() or a[0, 0] < 0:
+        raise ValueError(f"{what}: the first anchor must have dst 0, and src and dst must both increase strictly")
+    return a
+
+
+def _retime_piecewise(what: str, v, anchors, col: int, n=None):
+    """x -> y along the anchors, x read in column `col`: y_j + ((x - x_j) * (y_{j+1} - y_j)) // (x_{j+1} - x_j).  A Python int goes
+    through Python's integers, an array through int64: the products stay below 2^62 for positions below 2^31."""
+    a = _retime_table(what, anchors)
+    xs, ys = a[:, col], a[:, 1 - col]
+    if isinstance(v, (int, np.integer)):
+        v = int(v)
+        j = min(max(int(np.searchsorted(xs, v, side="right")) - 1, 0), len(xs) - 1)
+        if j == len(xs) - 1:
+            r = int(ys[j]) + (v - int(xs[j]))
+        else:
+            r = int(ys[j]) + ((v - int(xs[j])) * int(ys[j + 1] - ys[j])) // int(xs[j + 1] - xs[j])
+        return r if n is None else min(max(r, 0), int(n))
+    v = np.asarray(v, np.int64)
+    j = np.clip(np.searchsorted(xs, v, side="right") - 1, 0, len(xs) - 1)
+    j1 = np.minimum(j + 1, len(xs) - 1)
+    den = np.where(j1 > j, xs[j1] - xs[j], 1)
+    r = np.where(j1 > j, ys[j] + ((v - xs[j]) * (ys[j1] - ys[j])) // den, ys[j] + (v - xs[j]))
+    return r if n is None else np.clip(r, 0, int(n))
+
+
+def retime_src(t, anchors, n=None):
+    """The map M of smtts_retime for a valid table (dst from 0, src and dst strictly increasing): output position t -> source
+    position, s_j + ((t - d_j) * (s_{j+1} - s_j)) // (d_{j+1} - d_j) inside a pair, s_{m-1} + (t - d_{m-1}) behind the last anchor;
+    with `n` clamped into [0, n].  t: a Python int or an integer array (int64 arithmetic)."""
+    return _retime_piecewise("retime_src", t, anchors, 1, n)
+
+
+def retime_times(s, anchors):
+    """Where a source position lands: the forward map d_j + ((s - s_j) * (d_{j+1} - d_j)) // (s_{j+1} - s_j) for s_j <= s < s_{j+1},
+    clamped into [d_0, d_{m-1}] outside the anchors.  Monotone; anchors map onto anchors exactly; retime_times(retime_src(t)) <= t."""
+    a = _retime_table("retime_times", anchors)
+    r = _retime_piecewise("retime_times", s, a, 0)
+    lo, hi = int(a[0, 1]), int(a[-1, 1])
+    return min(max(r, lo), hi) if isinstance(r, int) else np.clip(r, lo, hi)
+
+
+def _word_span(w) -> Tuple[int, int]:
+    """(start, end) of a word row: align_words' (index, kind, phonemes, start, end, confidence) or synthesize_long's (index, kind,
+    start, end)."""
+    return (int(w[3]), int(w[4])) if len(w) >= 6 else (int(w[2]), int(w[3]))
+
+
+def _retime_words(what: str, words) -> List[Tuple[int, int, int]]:
+    out = [(int(w[0]),) + _word_span(w) for w in words if w[1] == "word"]
+    if any(e < s or s < 0 for _i, s, e in out) or any(b[1] < a[2] for a, b in zip(out, out[1:])):
+        raise ValueError(f"{what}: the words must be in order, each with 0 <= start <= end and no overlap")
+    return out
+
+
+def retime_anchors(n: int, *, speed: Optional[float] = None, duration: Optional[float] = None, words=None, to_words=None,
+                   min_rate: float = 0.5, max_rate: float = 2.0) -> Tuple[np.ndarray, List[int]]:
+    """The anchor table of a retiming of n source samples -> (anchors (m, 2) int64 = (src, dst), the group indices of the words that
+    were clamped).  Exactly one target.  `speed`: two anchors, (0, 0) and (n, round(n / speed)); `duration` seconds: (0, 0) and
+    (n, round(duration * 24000)).  `to_words` (with `words`, where the words are now): both lists as align_words returns them (or
+    synthesize_long's four-column rows), matched by group index over the groups of kind "word", equal counts required; anchors sit
+    at every word's start and end, (0, 0) in front, the end of the audio behind at the last pause's own speed 1.  A rate is source
+    samples per output sample.  A word whose rate would leave [min_rate, max_rate] keeps its start and has its length clamped, a
+    pause whose rate would leave engine.retime's [1/8, 8] has its end moved to the nearest place that does.  Anchors that would not
+    increase are dropped: a word that starts where the anchor in front already sits (at sample 0, or right behind the previous
+    word) starts where that anchor lies, and keeps its target length from there.  Reported is every word whose start or end does
+    not land on its target by retime_times, for whichever of these reasons: every word NOT reported lands exactly."""
+    n = int(n)
+    if n < 1:
+        raise ValueError(f"retime_anchors: n must be at least 1, got {n}")
+    if (speed is not None) + (duration is not None) + (to_words is not None) != 1:
+        raise ValueError("retime_anchors: exactly one of speed, duration and to_words")
+    if to_words is None:
+        if words is not None:
+            raise ValueError("retime_anchors: words belongs to to_words")
+        v = float(speed if speed is not None else duration)
+        if not (np.isfinite(v) and v > 0.0):
+            raise ValueError(f"retime_anchors: {'speed' if speed is not None else 'duration'} must be a positive number, got {v}")
+        d = int(round(n / v)) if speed is not None else int(round(v * SAMPLE_RATE))
+        if d < 1:
+            raise ValueError("retime_anchors: the target is shorter than one sample")
+        return np.asarray([[0, 0], [n, d]], np.int64), []
+    if words is None:
+        raise ValueError("retime_anchors: to_words needs words, where the words are now")
+    if not (0.0 < float(min_rate) <= float(max_rate)):
+        raise ValueError(f"retime_anchors: 0 < min_rate <= max_rate wanted, got {min_rate}, {max_rate}")
+    lo_w, hi_w = max(float(min_rate), RETIME_MIN_SLOPE), min(float(max_rate), RETIME_MAX_SLOPE)
+    src, dst = _retime_words("retime_anchors", words), _retime_words("retime_anchors", to_words)
+    if len(src) != len(dst) or [w[0] for w in src] != [w[0] for w in dst]:
+        raise ValueError(f"retime_anchors: words and to_words must hold the same word groups, got {len(src)} and {len(dst)}")
+    if src and src[-1][2] > n:
+        raise ValueError(f"retime_anchors: a word ends at {src[-1][2]}, behind the {n} samples of audio")
+    rows = [(0, 0)]
+
+    def put(s: int, d: int, lo: float, hi: float) -> None:
+        s0, d0 = rows[-1]
+        if s <= s0:                                             # the anchor would not increase: dropped
+            return
+        ds = s - s0
+        d_lo, d_hi = d0 + max(1, int(np.ceil(ds / hi))), d0 + max(1, int(np.floor(ds / lo)))   # the dst that keep the rate in [lo, hi]
+        rows.append((s, min(max(d, d_lo), d_hi)))
+
+    for (_gi, s, e), (_gj, ts, te) in zip(src, dst):
+        put(s, ts, RETIME_MIN_SLOPE, RETIME_MAX_SLOPE)          # the pause in front of the word
+        start_d = rows[-1][1]                                   # (rows[-1][0] == s: the words are in order and do not overlap)
+        put(e, start_d + (te - ts), lo_w, hi_w)                 # the word: its target length from where it starts
+    if n > rows[-1][0]:
+        rows.append((n, rows[-1][1] + (n - rows[-1][0])))
+    if len(rows) < 2:
+        raise ValueError("retime_anchors: no word to place")
+    table = np.asarray(rows, np.int64)
+    clamped = [gi for (gi, s, e), (_gj, ts, te) in zip(src, dst)
+               if (retime_times(s, table), retime_times(e, table)) != (ts, te)]
+    return table, clamped
+
+
+def retime_rows(n: int, anchors, words=None, max_row: int = 30 * SAMPLE_RATE, min_pause: int = 4800):
+    """Cuts a retiming of a long recording into rows that engine.retime takes side by side -> (rows, table).  `table` is `anchors`
+    with every cut inserted as an anchor; it is THE map of the cut retiming (a cut inside a pair re-rounds the pair's two halves),
+    and it agrees with `anchors` at every anchor.  rows = [(src offset, src length, dst offset, row anchors), ...]: each row's own
+    table starts at (0, 0) and ends at (src length, dst length); source and output length of a row are both at most max_row.  Rows
+    are independent chains; the result is their concatenation.  A cut lies in the middle of the last aligned pause of at least
+    min_pause samples (200 ms; between consecutive groups of `words`, any kind) that keeps the row within max_row; where there is
+    none, at the last anchor that does; where there is none either, at the furthest sample that does.
+    A cut inside a pair gets the dst retime_times gives it, moved into the range in which BOTH halves of the pair keep a rate within
+    engine.retime's [1/8, 8] and increase strictly; where rounding leaves no such dst (a pair at rate 8 cut at a source length that
+    is no multiple of 8), the cut itself moves by up to 8 samples, else to the pair's nearer end.  So a table whose pairs keep the
+    engine's limits is cut into rows that keep them."""
+    a = _retime_table("retime_rows", anchors)
+    n, max_row, min_pause = int(n), int(max_row), int(min_pause)
+    if max_row < 2 or min_pause < 0:
+        raise ValueError(f"retime_rows: max_row >= 2 and min_pause >= 0 wanted, got {max_row}, {min_pause}")
+    end_s, end_d = int(a[-1, 0]), int(a[-1, 1])
+    spans = sorted(_word_span(w) for w in (words or []))
+    pauses = [(e0 + s1) // 2 for (_s0, e0), (s1, _e1) in zip(spans, spans[1:]) if s1 - e0 >= min_pause]
+    table = [tuple(int(v) for v in r) for r in a]              # grows by the cuts: a later cut sees the earlier ones
+
+    def place(c: int) -> Optional[Tuple[int, int]]:
+        """A cut wanted at source sample c -> (cut, dst) on the table as it stands, or None outside it."""
+        if not table[0][0] <= c <= table[-1][0]:
+            return None
+        j = max(i for i, r in enumerate(table) if r[0] <= c)
+        if table[j][0] == c:
+            return table[j]
+        (sa, da), (sb, db) = table[j], table[j + 1]
+        for k in sorted(range(-8, 9), key=abs):
+            cc = c + k
+            if not sa < cc < sb:
+                continue
+            lo = max(da + -(-(cc - sa) // 8), db - 8 * (sb - cc))     # both halves: ds <= 8 dd and dd <= 8 ds, dd >= 1
+            hi = min(da + 8 * (cc - sa), db - -(-(sb - cc) // 8))
+            if lo <= hi:
+                return cc, min(max(int(retime_times(cc, np.asarray(table, np.int64))), lo), hi)
+        return table[j + 1] if sb - c <= c - sa else table[j]
+
+    def fits(s0: int, d0: int, cut: Optional[Tuple[int, int]]) -> bool:
+        return cut is not None and s0 < cut[0] <= s0 + max_row and 0 < cut[1] - d0 <= max_row
+
+    cuts, s0, d0 = [], 0, 0
+    while end_s - s0 > max_row or end_d - d0 > max_row:
+        cand = [cut for cut in map(place, pauses) if fits(s0, d0, cut)] or [r for r in table if fits(s0, d0, r)]
+        if not cand:                                            # no pause, no anchor: the furthest sample that keeps both lengths
+            now = np.asarray(table, np.int64)
+            lo, hi = s0 + 1, min(s0 + max_row, end_s - 1)
+            while lo < hi:
+                mid = (lo + hi + 1) // 2
+                lo, hi = (mid, hi) if retime_times(mid, now) - d0 <= max_row else (lo, mid - 1)
+            cand = [cut for cut in (place(c) for c in range(lo, max(lo - 17, s0), -1)) if fits(s0, d0, cut)][:1]
+            if not cand:
+                raise ValueError("retime_rows: max_row is too small for this table")
+        cut = cand[-1]
+        if cut not in table:
+            table = sorted(table + [cut])
+        cuts.append(cut[0])
+        s0, d0 = cut
+    table = np.asarray(table, np.int64)
+    rows, bounds = [], [0] + cuts + [end_s]
+    for c0, c1 in zip(bounds, bounds[1:]):
+        part = table[(table[:, 0] >= c0) & (table[:, 0] <= c1)]
+        rows.append((c0, c1 - c0, int(part[0, 1]), part - part[0]))
+    return rows, table

@@ -24,7 +24,9 @@ PCM16 only, with and without --stream); python -m smalltts_amd.scripts.detect --
 --stream: the WAV is written while the text is still being spoken (api.SmallTTS.synthesize_long_stream, audio.WavStreamWriter): one
 chunk per group of pieces, the first after one piece's work; the time to the first chunk and the total are printed.  --batch-sizes
 1,2,4,8 (the default ramp) or `none` (groups of --max-batch, the file --stream-less runs write, byte for byte).  --words / --srt /
---take are written at the end from what the chunks carried; the per-piece reports of --takes / --repair are not streamed."""
+--take are written at the end from what the chunks carried; the per-piece reports of --takes / --repair are not streamed.
+--speed X / --fit-seconds S: the joined waveform is retimed on the device behind the join (api.Retime, DESIGN 8n: WSOLA, the pitch is
+kept), X times as fast or to exactly S seconds; --words / --srt then count the retimed samples.  Not with --stream."""
 import argparse
 import json
 import time
@@ -32,7 +34,7 @@ from pathlib import Path
 
 import numpy as np
 
-from ..api import SAMPLE_RATE, Endpointing, Repair, SmallTTS, Takes, estimate_duration, format_srt, save_take, split_text, token_groups
+from ..api import SAMPLE_RATE, Endpointing, Repair, Retime, SmallTTS, Takes, estimate_duration, format_srt, save_take, split_text, token_groups
 from ..audio import WavStreamWriter, read_wav
 from ..phonemes import decode_token_ids, get_token_ids, parse_tokens_arg
 from ._common import add_delivery_args, add_engine_args, add_watermark_args, delivery_for, pcm16_host, watermark_for, write_output
@@ -131,10 +133,20 @@ def parse_args(argv=None):
     ap.add_argument("--stream", action="store_true", help="write the WAV chunk by chunk while the text is being spoken")
     ap.add_argument("--batch-sizes", default=None, metavar="N,N,...|none",
                     help="with --stream: pieces per group, the last value repeated (default 1,2,4,8); none = groups of --max-batch")
+    ap.add_argument("--speed", type=float, default=None, metavar="X", help="retime the joined waveform: X times as fast, the pitch kept")
+    ap.add_argument("--fit-seconds", type=float, default=None, metavar="S", help="retime the joined waveform to exactly S seconds")
     add_engine_args(ap)
     add_delivery_args(ap)
     add_watermark_args(ap)
     args = ap.parse_args(argv)
+    if args.speed is not None and args.fit_seconds is not None:
+        ap.error("--speed and --fit-seconds exclude each other")
+    if (args.speed is not None or args.fit_seconds is not None) and args.stream:
+        ap.error("--speed / --fit-seconds do not go with --stream (a retiming is not streamed)")
+    try:
+        args.retime = None if args.speed is None and args.fit_seconds is None else Retime(speed=args.speed, duration=args.fit_seconds)
+    except ValueError as e:
+        ap.error(str(e))
     args.mark, args.delivery = watermark_for(ap, args, delivery_for(args))   # --watermark: the joined waveform is marked on the device
     if args.batch_sizes is not None and not args.stream:
         ap.error("--batch-sizes needs --stream")
@@ -190,6 +202,8 @@ def main(argv=None):
         kw.update(deliver=dv)                              # the joined waveform leaves the device at that rate and encoding
     if args.mark is not None:
         kw.update(watermark=args.mark)
+    if args.retime is not None:
+        kw.update(retime=args.retime)                      # behind the join, in front of the mark and the delivery
     timed = bool(args.words or args.srt)
     if timed:
         kw.update(return_segments=True, return_words=True)
