@@ -53,7 +53,7 @@ int smtts_create(int device_id, smtts_handle* out);
 int smtts_destroy(smtts_handle h);
 const char* smtts_last_error(smtts_handle h); /* h may be NULL: last creation error */
 const char* smtts_version(void);
-/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, then smtts_take_scores and smtts_take_select, then the streamed decode entries, then smtts_deliver, then smtts_join_stream and smtts_peek_saturations, then the smtts_watermark entries, then smtts_retime, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
+/* bumped on every signature / default change: 11 = smtts_sample_align, smtts_align_path, smtts_test_attn_text_mass (+ smtts_sample_pinned, then smtts_take_scores and smtts_take_select, then the streamed decode entries, then smtts_deliver, then smtts_join_stream and smtts_peek_saturations, then the smtts_watermark entries, then smtts_retime, then smtts_pitch, additive: no existing signature or default changed, no bump); 10 = smtts_endpoints, smtts_stitch_seg; 9 = smtts_voice_expand, smtts_randn_rows, smtts_stitch; 8 = smtts_test_dit_stage; 7 = smtts_test_codec_stage; 6 = smtts_test_ln_fold; 5 = round 6 (smtts_test_set_ln_fold; one side stream per caller stream); 4 = round 4 (workspace queries take R and P, new handles default to preset 2,
  * smtts_get_saturations) */
 #define SMTTS_ABI_VERSION 11
 int smtts_abi_version(void);
@@ -665,6 +665,44 @@ int smtts_join_stream(smtts_handle h, void* stream, const float* audio, int B, i
 int smtts_retime(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* len /* DEVICE (B) */,
                  const int64_t* anchors /* DEVICE (B,A,2) */, const int64_t* n_anchor /* DEVICE (B) */, int A, const float* win,
                  int hop, int delta, float* out, int64_t out_stride, int64_t* q);
+/* pitch: an F0 track of each row.  Every frame of hop samples gets a normalised cross-correlation score (NCCF) per
+ * candidate lag, and the cheapest path through "unvoiced" and the lags (Viterbi, with a cost per octave of jump and per switch of
+ * voicing) gives one lag, or 0 for unvoiced, per frame.  The constants are the caller's; the defaults of the Python side are design
+ * choices checked on synthetic signals only, nothing here was tuned or validated on speech.
+ * In:   audio f32 (B,1,row_stride); len i64 (B) DEVICE; tab f32 (2,L) DEVICE: lg[0..L) then tilt[0..L), L = lmax - lmin + 1
+ *       (plans.pitch_tables: lg = log2 of the lag, tilt falls from 1 at lmin).  Every entry is clamped as it is loaded, lg into
+ *       [0, 16], tilt into [0, 2], a NaN reads as 0: the table lives on the device, so it is clamped, never trusted.
+ * Samples: n = clamp(len[b], 0, row_stride); x[i] outside [0, n) reads as +0.0, and nothing behind n is loaded.
+ *       F_b = ceil(n / hop) frames; frame f starts at s = f * hop.  Fmax = ceil(row_stride / hop).
+ * Scores for lag l in [lmin, lmax], column l - lmin:  r = sum_{i<win} x[s+i] * x[s+l+i],  e0 = sum_{i<win} x[s+i]^2,
+ *       e = sum_{i<win} x[s+l+i]^2,  S[f][l] = r / sqrtf(e0 * e + bias).  Each sum is fp32, in any order, with or without fma; the
+ *       product, the add, sqrtf and the divide are correctly rounded fp32 operations.  bias > 0 makes silence score 0 smoothly (no
+ *       energy gate, no discrete decision on a rounded sum); the Python side passes (win * floor_pow)^2.  Silence scores exactly 0.
+ * States: j = 0 is unvoiced, j = 1 .. L is lag lmin + j - 1.
+ * Local cost, every named operation one separately rounded fp32 operation (no fma):  loc(f, 0) = c_unv;
+ *       loc(f, j) = fsub(1, fmul(S[f][l], tilt[j-1])); a loc that comes out NaN (NaN or Inf samples inside len) counts as +inf.
+ *       State 0 is always finite, so a best path always exists.
+ * Transition:  0 -> 0 costs 0;  0 <-> j costs w_switch;  j' -> j costs fmul(w_jump, fabsf(fsub(lg[j-1], lg[j'-1]))).
+ * Recurrence:  D[0][j] = loc(0, j);  D[f][j] = fadd(loc(f, j), min over j' of fadd(D[f-1][j'], trans(j', j))), the argmin taking the
+ *       smallest j' on ties.  End: the smallest j among the minima of D[F_b - 1]; then the back pointers are followed.  The minimum
+ *       of a set of floats does not depend on the order it is taken in, so numpy reproduces lag bit for bit given S.
+ * Out:  lag i32 (B,Fmax): 0 for unvoiced, else the lag; peak f32 (B,Fmax,3) = (S[l-1], S[l], S[l+1]) copied from S, a neighbour
+ *       outside [lmin, lmax] being S[l]; (0, 0, 0) for unvoiced; nccf f32 (B,Fmax,L) or NULL: S for f < F_b.  Nothing at or behind
+ *       F_b is written in any output, F_b = 0 writes nothing.  audio and the outputs must not overlap.
+ * Workspace: smtts_pitch_workspace_bytes(B, row_stride, hop, lmin, lmax) bytes, 256-byte aligned: the scores (also when nccf is
+ *       given) and the back pointers, uint16 (B,Fmax,L+1).  What it holds before the call does not matter.
+ * Two launches whatever B is (scores: one workgroup per row and 8 frames; path: one workgroup per row, the frames of a row are a
+ *       chain); no atomics, nothing depends on scheduling: two calls on equal inputs return equal bits, and a row's results do not
+ *       depend on its batch-mates.
+ * Refused with 1 (the query: 0) and a message naming the entry, nothing enqueued: a NULL handle, audio, len, tab, lag, peak or ws; B
+ *       outside [1, 1024]; row_stride outside [1, 2^24]; hop outside [16, 1024] or not a multiple of 4; win outside [32, 2048] or not
+ *       a multiple of 4; lmin < 2, lmax <= lmin, lmax > 2048 or L > 1023; bias <= 0 or not finite; c_unv, w_jump or w_switch negative
+ *       or not finite; ws_bytes below the query, or ws not 256-byte aligned. */
+size_t smtts_pitch_workspace_bytes(smtts_handle h, int B, int64_t row_stride, int hop, int lmin, int lmax);
+int smtts_pitch(smtts_handle h, void* stream, const float* audio, int B, int64_t row_stride, const int64_t* len /* DEVICE (B) */,
+                const float* tab /* DEVICE f32 (2,L) */, int hop, int win, int lmin, int lmax, float bias, float c_unv, float w_jump,
+                float w_switch, int32_t* lag /* (B,Fmax) */, float* peak /* (B,Fmax,3) */, float* nccf /* (B,Fmax,L) or NULL */,
+                void* ws, size_t ws_bytes);
 
 /* cond_encode runs the text encoder on a side stream owned by the engine, one per caller stream (fork / join with events; default
  * on: shortest latency for one batch at a time).  Callers that keep several batches in flight on their own streams should turn it

@@ -106,6 +106,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_stitch_seg": (i32, [vp, vp, vp, i32, i64, vp, vp, vp, vp, i32, vp, i64, i32]),
     "smtts_join_stream": (i32, [vp, vp, vp, i32, i64, vp, vp, vp, i32, i64, i32, vp, vp, i64, i32, vp, vp, vp, i64]),
     "smtts_retime": (i32, [vp, vp, vp, i32, i64, vp, vp, vp, i32, vp, i32, i32, vp, i64, vp]),
+    "smtts_pitch_workspace_bytes": (sz, [vp, i32, i64, i32, i32, i32]),
+    "smtts_pitch": (i32, [vp, vp, vp, i32, i64, vp, vp, i32, i32, i32, i32, f32, f32, f32, f32, vp, vp, vp, vp, sz]),
     "smtts_alpha_sigma": (None, [f32, C.POINTER(f32), C.POINTER(f32)]),
     "smtts_profile_enable": (i32, [vp, i32]),
     "smtts_profile_report": (i32, [vp, C.c_char_p, sz]),

@@ -25,14 +25,87 @@ from .engine import (ASR_LONG_MAX_FRAMES, ASR_MAX_ROWS, ASR_UPSAMPLE, CTC_LONG_M
                      SV_MIN_FRAMES, HipEngine)
 from .weights import DEFAULT_CODEC, CodecSpec, all_param_specs, asr_param_specs, load_weight_file, sv_param_specs
 # the option records (options.py) and the host arithmetic (plans.py) live in modules of their own; every name stays importable from here
-from .options import (ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS, TAKE_JOIN_KEYS, Alignment, Delivery, Endpointing, Piece, Repair, Retime,
-                      Takes, Watermark, _Frozen, as_alignment, as_delivery, as_endpointing, as_repair, as_retime, as_takes, as_watermark,
-                      load_take, marked_delivery, save_take)
+from .options import (ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS, TAKE_JOIN_KEYS, Alignment, Delivery, Endpointing, Piece, Pitch, Repair, Retime,
+                      Takes, Watermark, _Frozen, as_alignment, as_delivery, as_endpointing, as_pitch, as_repair, as_retime, as_takes,
+                      as_watermark, load_take, marked_delivery, save_take)
 from .plans import (CHARS_PER_SECOND, CTC_HOP, HOP_SIZE, NUM_STEPS, SAMPLE_RATE, _CLAUSE_END, _SENTENCE_END, _check_pins,
                     _default_count_tokens, _frames, _hard_cut, _srt_time, _units, codec_spans, estimate_duration, fade_table,
-                    format_srt, frames_of_groups, group_confidence, long_windows, phoneme_error_rate, piece_seed, plan_long, plan_packed,
-                    repair_seed, retime_anchors, retime_rows, retime_times, speaking_rate, splice_pins, split_text, stream_chunks,
-                    stream_groups, take_seed, token_groups, word_times)
+                    format_srt, frames_of_groups, group_confidence, long_windows, phoneme_error_rate, piece_seed, pitch_f0,
+                    pitch_rows, pitch_word_stats, plan_long, plan_packed, repair_seed, retime_anchors, retime_rows, retime_times,
+                    speaking_rate, splice_pins, split_text, stream_chunks, stream_groups, take_seed, token_groups, word_times)
+
+PITCH_MAX_WORKSPACE = 256 << 20   # SmallTTS.pitch: rows ride in groups whose workspace stays below this
+
+
+class PitchTrack(NamedTuple):
+    """What SmallTTS.pitch returns: `f0` in Hz per frame (float64, 0 where unvoiced), `strength` (fp32, the score at the chosen lag, 0
+    where unvoiced); frame f starts at sample f * `hop` of the `sr` Hz audio."""
+    f0: np.ndarray
+    strength: np.ndarray
+    hop: int
+    sr: int
+
+
+def _pitch_device(eng: HipEngine, y: torch.Tensor, pt: "Pitch", max_row: Optional[int] = None):
+    """y: 24 kHz samples, 1-d fp32 on the device -> (lag (F,) int32, peak (F, 3) fp32) on the host, F = ceil(n / hop)."""
+    n = int(y.numel())
+    rows = pitch_rows(n, pt.hop) if max_row is None else pitch_rows(n, pt.hop, max_row=max_row)
+    F = -(-n // pt.hop)
+    lag, peak = np.zeros((F,), np.int32), np.zeros((F, 3), np.float32)
+    per_row = int(eng.lib.smtts_pitch_workspace_bytes(eng.h, 1, max(r[1] for r in rows), pt.hop, pt.lmin, pt.lmax))
+    if per_row <= 0:
+        raise ValueError(f"pitch: {eng.lib.smtts_last_error(eng.h).decode()}")
+    group = max(1, min(1024, PITCH_MAX_WORKSPACE // per_row))
+    for g0 in range(0, len(rows), group):
+        grp = rows[g0: g0 + group]
+        if len(grp) == 1:
+            batch = y[grp[0][0]: grp[0][0] + grp[0][1]].reshape(1, 1, -1).contiguous()
+        else:
+            batch = torch.zeros(len(grp), 1, max(r[1] for r in grp), device=eng.device)
+            for b, (s0, sn, _f0, _fn) in enumerate(grp):
+                batch[b, 0, :sn] = y[s0: s0 + sn]
+        lg, pk = eng.pitch(batch, [r[1] for r in grp], pt)
+        lg, pk = lg.cpu().numpy(), pk.cpu().numpy()
+        for b, (s0, _sn, f0, fn) in enumerate(grp):
+            k = f0 - s0 // pt.hop                              # the row's own index of the first frame it keeps
+            lag[f0: f0 + fn], peak[f0: f0 + fn] = lg[b, k: k + fn], pk[b, k: k + fn]
+    return lag, peak
+
+
+def pitch_track(engine: HipEngine, audio, pitch=None, words=None):
+    """The F0 track of 24 kHz mono audio of any length (engine.pitch: NCCF scores and a Viterbi path on the device) ->
+    PitchTrack(f0, strength, hop, sr), one entry per frame of `hop` samples, ceil(n / hop) of them (audio: an array, or a tensor on
+    any device; one on the engine's device is not copied); with `words` (align_words' or
+    align_wav's rows) -> (the track, [(row, dict(f0_median, f0_min, f0_max, voiced)), ...]) by plans.pitch_word_stats.  `pitch`: a
+    Pitch, None for its defaults.  Audio longer than 30 s is cut into rows that share 1 s with their neighbours (plans.pitch_rows);
+    the rows ride in groups whose workspace stays below 256 MiB.  Needs no weights: any HipEngine will do.  The constants were
+    checked on synthetic signals only: nothing is claimed about accuracy on speech."""
+    pt = as_pitch(pitch)
+    a = audio.detach() if isinstance(audio, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(audio), np.float32))
+    if (a.dim() != 1 and not (a.dim() == 2 and 1 in a.shape)) or a.numel() < 1:
+        raise ValueError(f"pitch: mono audio of at least one sample, got an array of shape {tuple(a.shape)}")
+    # a tensor that already lies on the engine's device (pitch_track_wav's resampled audio) is tracked where it is
+    lag, peak = _pitch_device(engine, a.reshape(-1).to(device=engine.device, dtype=torch.float32).contiguous(), pt)
+    f0, strength = pitch_f0(lag, peak, SAMPLE_RATE)
+    track = PitchTrack(f0, strength, pt.hop, SAMPLE_RATE)
+    if words is None:
+        return track
+    words = list(words)
+    return track, list(zip(words, pitch_word_stats(words, f0, pt.hop)))
+
+
+def pitch_track_wav(engine: HipEngine, audio, sr: int, pitch=None, words=None):
+    """pitch_track of a recording: mono samples at `sr` Hz are resampled to 24 kHz on the device first, as align_wav does; `words`
+    then count 24 kHz samples, as the aligners' rows do."""
+    a = np.asarray(audio, np.float32)
+    if a.ndim != 1 and not (a.ndim == 2 and 1 in a.shape):
+        raise ValueError(f"pitch_wav: a mono recording, got an array of shape {a.shape}")
+    sr = int(sr)
+    if sr < 1 or a.size < 1:
+        raise ValueError(f"pitch_wav: at least one sample at a positive rate, got {a.size} samples at {sr} Hz")
+    y = engine.resample(a.reshape(-1), sr, SAMPLE_RATE)
+    return pitch_track(engine, y.reshape(-1), pitch, words)
+
 
 DEFAULT_WEIGHTS = os.environ.get("SMALLTTS_WEIGHTS", "assets/smalltts.smtts")
 
@@ -1437,6 +1510,18 @@ class SmallTTS:
         words = self.align_wav_long(audio, sr, phoneme_ids) if long else self.align_wav(audio, sr, phoneme_ids)
         y = self.engine.resample(np.asarray(audio, np.float32).reshape(-1), int(sr), SAMPLE_RATE)
         return self.retime(y.reshape(-1), retime, words=words)
+
+    # ---- pitch: an F0 track on the device, f0 per word ---------------------------------------------------------------------
+    def pitch(self, audio, pitch=None, words=None):
+        """pitch_track on this instance's engine: the F0 track of 24 kHz mono audio of any length -> PitchTrack(f0, strength, hop, sr),
+        with `words` (align_words' or align_wav's rows) -> (the track, [(row, dict(f0_median, f0_min, f0_max, voiced)), ...]).
+        Checked on synthetic signals only: nothing is claimed about accuracy on speech."""
+        return pitch_track(self.engine, audio, pitch, words)
+
+    def pitch_wav(self, audio, sr: int, pitch=None, words=None):
+        """pitch() of a recording at `sr` Hz (pitch_track_wav): resampled to 24 kHz on the device first, as align_wav does.  It does
+        not need the recogniser."""
+        return pitch_track_wav(self.engine, audio, sr, pitch, words)
 
     def synthesize_long_stream(self, voice: Voice, text: Optional[str] = None, *, token_lists: Optional[Sequence[Sequence[int]]] = None,
                                durations: Optional[Sequence[float]] = None, seed: Optional[int] = None, gap_ms: float = 120.0,

@@ -15,7 +15,8 @@ import torch
 from . import _lib
 from ._lib import ACT, PRECISION, PRESETS, SITES, ptr as _p   # noqa: F401  (the codes stay importable from here)
 from .engine_hooks import EngineHooks
-from .plans import long_windows, retime_window
+from .options import as_pitch
+from .plans import long_windows, pitch_tables, retime_window
 from .operands import (ALIGN_MAX_FRAMES, ALIGN_MAX_TOKENS, distinct_slots, fade_len, frames_tokens, is_operand, out_1d, per_row,
                        pool_slots, row_lengths, seg_gain, upload)
 from .weights import (DEFAULT_CODEC, CodecSpec, asr_param_specs, codec_decoder_param_specs, codec_encoder_param_specs,
@@ -82,6 +83,7 @@ class HipEngine(EngineHooks):
         self.codec_spec: CodecSpec = DEFAULT_CODEC
         self._banks: Dict[tuple, tuple] = {}   # (down, up) -> (polyphase bank on the device, width)
         self._retime_wins: Dict[int, torch.Tensor] = {}   # hop -> the cross-fade window on the device (plans.retime_window)
+        self._pitch_tabs: Dict[tuple, torch.Tensor] = {}  # (lmin, lmax, tilt) -> lg / tilt on the device (plans.pitch_tables)
         self._demoted: Dict[str, str] = {}     # site -> why: sites the fp16 range guard moved to split-bf16 (sticky across set_precision)
         self.calibration: Optional[Dict[str, object]] = None   # last calibrate() report on the loaded weights
         self.dual_stream = os.environ.get("SMTTS_SINGLE_STREAM", "") != "1"   # what the library starts with (set_dual_stream)
@@ -1292,6 +1294,34 @@ class HipEngine(EngineHooks):
         self._ck(self.lib.smtts_retime(self.h, self._stream(), _p(audio), B, row, _p(tab[:B]), _p(tab[2 * B:]), _p(tab[B: 2 * B]), A,
                                        _p(win), hop, delta, _p(out), S_out, _p(q)), "retime")
         return (out, out_lens, q) if return_q else (out, out_lens)
+
+    # ---- pitch: NCCF scores and the best path through them (include/smalltts_hip.h smtts_pitch) ----
+    def pitch(self, audio: torch.Tensor, lens, pitch=None, return_nccf: bool = False):
+        """audio (B,1,S) fp32 on the device, row b = lens[b] samples at 24 kHz; pitch: an options.Pitch (None: its defaults) -> (lag
+        (B,Fmax) int32, peak (B,Fmax,3) fp32[, nccf (B,Fmax,L) fp32]) on the device, Fmax = ceil(S / hop): lag is 0 where a frame is
+        unvoiced, else its period in samples; peak holds the score at the lag and at its two neighbours (plans.pitch_f0 makes f0 and
+        strength of the two).  Row b holds ceil(lens[b] / hop) frames, zeros behind.  Two launches on the current stream, no
+        synchronisation.  Checked on synthetic signals only, not on speech."""
+        B, row, ln = self._audio_rows("pitch", audio, lens)
+        pt = as_pitch(pitch)
+        if B > 1024 or row > 2 ** 24:
+            raise ValueError(f"pitch: at most 1024 rows of at most 2^24 samples, got {B} x {row}")
+        need = int(self.lib.smtts_pitch_workspace_bytes(self.h, B, row, pt.hop, pt.lmin, pt.lmax))
+        if need <= 0:
+            raise RuntimeError(f"pitch: {self.lib.smtts_last_error(self.h).decode()}")
+        ws = self._workspace(need)
+        key = (pt.lmin, pt.lmax, pt.tilt)
+        tab = self._pitch_tabs.get(key)
+        if tab is None:
+            tab = self._pitch_tabs[key] = torch.from_numpy(pitch_tables(*key)).to(self.device)
+        Fmax, L = (row + pt.hop - 1) // pt.hop, pt.lmax - pt.lmin + 1
+        lag = torch.zeros(B, Fmax, dtype=torch.int32, device=self.device)   # a row's frames behind its own length are not written
+        peak = torch.zeros(B, Fmax, 3, device=self.device)
+        nccf = torch.zeros(B, Fmax, L, device=self.device) if return_nccf else None
+        lens_d = self._upload_i64(ln)
+        self._ck(self.lib.smtts_pitch(self.h, self._stream(), _p(audio), B, row, _p(lens_d), _p(tab), pt.hop, pt.win, pt.lmin, pt.lmax,
+                                      pt.bias, pt.c_unv, pt.w_jump, pt.w_switch, _p(lag), _p(peak), _p(nccf), _p(ws), need), "pitch")
+        return (lag, peak, nccf) if return_nccf else (lag, peak)
 
     def profile(self, on, tagged: bool = False, shapes: bool = False):
         """on: False/True; tagged=True prefixes kernel names with the pipeline phase (enc, mod, dit, dec.s<i> ...); shapes=True

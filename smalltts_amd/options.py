@@ -1,5 +1,5 @@
 """The option records of the synthesis calls (api.py): what `trim=`, `align=`, `takes=`, `repair=`, `deliver=`, `watermark=` and
-`retime=` turn into, the Piece of a long take and its file.  Host only: no torch and no engine here."""
+`retime=` turn into, the Pitch record of SmallTTS.pitch, the Piece of a long take and its file.  Host only: no torch and no engine here."""
 from __future__ import annotations
 
 from typing import Dict, List, Optional, Sequence, Tuple
@@ -340,6 +340,64 @@ def as_retime(retime) -> Optional["Retime"]:
     if not isinstance(retime, bool) and isinstance(retime, (int, float, np.integer, np.floating)):
         return Retime(speed=float(retime))
     raise TypeError(f"retime must be None, a speed or a Retime, got {type(retime).__name__}")
+
+
+class Pitch(_Record):
+    """How SmallTTS.pitch tracks F0 on the device (immutable; DESIGN 8o, include/smalltts_hip.h smtts_pitch).  Candidates are the lags
+    `lmin` = floor(24000 / fmax) .. `lmax` = ceil(24000 / fmin) samples; a frame starts every `hop` samples (a multiple of 4 in [16,
+    1024]) and correlates `win` samples (a multiple of 4 in [32, 2048]); `floor_pow` is the power below which a frame counts as
+    silence (the score's bias is (win * floor_pow)^2); `tilt` is how much of its score the longest lag loses against the shortest;
+    `c_unv` is the cost of an unvoiced frame (a voiced one costs 1 - score * tilt_l), `w_jump` the cost per octave of a jump between
+    consecutive voiced frames, `w_switch` the cost of a change of voicing.  The limits: 2 <= lmin < lmax <= 2048 and at most 1023
+    lags.  The constants are design choices checked on synthetic signals only (tones, noise, silence): they are NOT tuned on speech,
+    and nothing about accuracy on real speech is claimed."""
+    __slots__ = ("fmin", "fmax", "hop", "win", "floor_pow", "tilt", "c_unv", "w_jump", "w_switch", "lmin", "lmax")
+
+    def __init__(self, fmin: float = 60.0, fmax: float = 400.0, hop: int = 240, win: int = 480, floor_pow: float = 1e-6,
+                 tilt: float = 0.1, c_unv: float = 0.55, w_jump: float = 0.35, w_switch: float = 0.3) -> None:
+        nums = (("fmin", fmin), ("fmax", fmax), ("floor_pow", floor_pow), ("tilt", tilt), ("c_unv", c_unv), ("w_jump", w_jump),
+                ("w_switch", w_switch))
+        for name, v in nums:
+            if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)):
+                raise TypeError(f"Pitch: {name} must be a number, got {type(v).__name__}")
+            if not np.isfinite(float(v)):
+                raise ValueError(f"Pitch: {name} must be finite, got {v!r}")
+        for name, v in (("hop", hop), ("win", win)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)):
+                raise TypeError(f"Pitch: {name} must be an integer, got {type(v).__name__}")
+        if not 16 <= int(hop) <= 1024 or int(hop) % 4:
+            raise ValueError(f"Pitch: hop must be a multiple of 4 in [16, 1024], got {int(hop)}")
+        if not 32 <= int(win) <= 2048 or int(win) % 4:
+            raise ValueError(f"Pitch: win must be a multiple of 4 in [32, 2048], got {int(win)}")
+        if not 0.0 < float(fmin) < float(fmax):
+            raise ValueError(f"Pitch: 0 < fmin < fmax wanted, got {fmin!r}, {fmax!r}")
+        lmin, lmax = int(np.floor(24000.0 / float(fmax))), int(np.ceil(24000.0 / float(fmin)))
+        if lmin < 2 or lmax <= lmin or lmax > 2048 or lmax - lmin + 1 > 1023:
+            raise ValueError(f"Pitch: fmin = {fmin!r}, fmax = {fmax!r} give the lags {lmin} .. {lmax}; 2 <= lmin < lmax <= 2048 and at most "
+                             "1023 lags wanted")
+        if not float(floor_pow) > 0.0:
+            raise ValueError(f"Pitch: floor_pow must be positive, got {floor_pow!r}")
+        if not 0.0 <= float(tilt) < 1.0:
+            raise ValueError(f"Pitch: tilt must lie in [0, 1), got {tilt!r}")
+        for name, v in (("c_unv", c_unv), ("w_jump", w_jump), ("w_switch", w_switch)):
+            if float(v) < 0.0:
+                raise ValueError(f"Pitch: {name} must not be negative, got {v!r}")
+        self._set(fmin=float(fmin), fmax=float(fmax), hop=int(hop), win=int(win), floor_pow=float(floor_pow), tilt=float(tilt),
+                  c_unv=float(c_unv), w_jump=float(w_jump), w_switch=float(w_switch), lmin=lmin, lmax=lmax)
+
+    @property
+    def bias(self) -> float:
+        """What smtts_pitch adds under the root: (win * floor_pow)^2."""
+        return (self.win * self.floor_pow) ** 2
+
+
+def as_pitch(pitch) -> "Pitch":
+    """The `pitch=` argument: None -> Pitch() (the defaults), a Pitch -> itself."""
+    if pitch is None:
+        return Pitch()
+    if isinstance(pitch, Pitch):
+        return pitch
+    raise TypeError(f"pitch must be None or a Pitch, got {type(pitch).__name__}")
 
 
 class Piece(_Frozen):

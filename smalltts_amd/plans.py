@@ -2,7 +2,7 @@
 pins, seeds.  numpy only: nothing here touches the device or imports torch."""
 from __future__ import annotations
 
-from typing import Callable, List, Optional, Sequence, Tuple
+from typing import Callable, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
 
@@ -644,3 +644,79 @@ def retime_rows(n: int, anchors, words=None, max_row: int = 30 * SAMPLE_RATE, mi
         part = table[(table[:, 0] >= c0) & (table[:, 0] <= c1)]
         rows.append((c0, c1 - c0, int(part[0, 1]), part - part[0]))
     return rows, table
+
+
+# ---- pitch (include/smalltts_hip.h smtts_pitch): the tables, f0 from the lags, per-word statistics, rows ---------------
+PITCH_MAX_ROW, PITCH_CONTEXT = 30 * SAMPLE_RATE, SAMPLE_RATE   # samples of a row of SmallTTS.pitch, and what neighbours share
+
+
+def pitch_tables(lmin: int, lmax: int, tilt: float = 0.1) -> np.ndarray:
+    """The table of smtts_pitch, (2, L) fp32 with L = lmax - lmin + 1: row 0 lg = float32(log2(l)), row 1 tilt_l = float32(1 - tilt *
+    (l - lmin) / (lmax - lmin)), both computed in float64 and rounded once.  The tilt makes a short lag win over its multiples, which
+    score as high on a periodic signal."""
+    lmin, lmax, tilt = int(lmin), int(lmax), float(tilt)
+    if lmin < 1 or lmax <= lmin or not 0.0 <= tilt < 1.0:
+        raise ValueError(f"pitch_tables: 1 <= lmin < lmax and 0 <= tilt < 1 wanted, got {lmin}, {lmax}, {tilt}")
+    l = np.arange(lmin, lmax + 1, dtype=np.float64)
+    return np.stack([np.log2(l), 1.0 - tilt * (l - lmin) / (lmax - lmin)]).astype(np.float32)
+
+
+def pitch_f0(lag, peak, sr: float = SAMPLE_RATE) -> Tuple[np.ndarray, np.ndarray]:
+    """smtts_pitch's lag (..., ) and peak (..., 3) -> (f0 in Hz, strength), float64 and float32 arrays of lag's shape.  f0 = sr /
+    (l + d): d is the vertex of the parabola through the triple (S[l-1], S[l], S[l+1]), 0.5 (a - c) / (a - 2 b + c), clamped to
+    [-0.5, 0.5], and 0 where the triple is flat or its middle is no maximum.  f0 is 0 where the frame is unvoiced (lag 0).  The
+    strength is the score at the lag, peak[..., 1]."""
+    lag = np.asarray(lag)
+    pk = np.asarray(peak, np.float32)
+    if pk.shape != lag.shape + (3,):
+        raise ValueError(f"pitch_f0: peak must be lag's shape + (3,), got {pk.shape} for {lag.shape}")
+    a, b, c = (pk[..., i].astype(np.float64) for i in range(3))
+    curv = a - 2.0 * b + c
+    ok = (curv < 0.0) & (b >= a) & (b >= c)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        d = np.where(ok, 0.5 * (a - c) / np.where(ok, curv, 1.0), 0.0)
+    d = np.clip(np.where(np.isfinite(d), d, 0.0), -0.5, 0.5)
+    voiced = lag > 0
+    f0 = np.where(voiced, float(sr) / np.where(voiced, lag.astype(np.float64) + d, 1.0), 0.0)
+    return f0, pk[..., 1].copy()
+
+
+def pitch_word_stats(words, f0, hop: int) -> List[Dict[str, Optional[float]]]:
+    """Per row of `words` (align_words' six columns or synthesize_long's four) one dict(f0_median, f0_min, f0_max, voiced): the median,
+    the smallest and the largest f0 over the voiced frames (f0 > 0) whose start f * hop lies in [start, end), and the share of those
+    frames that is voiced.  The three f0 values are None where no such frame is voiced; voiced is 0.0 where the span holds no frame."""
+    f0, hop = np.asarray(f0, np.float64).reshape(-1), int(hop)
+    if hop < 1:
+        raise ValueError(f"pitch_word_stats: hop must be at least 1, got {hop}")
+    out = []
+    for w in words:
+        s, e = _word_span(w)
+        lo, hi = min(max(-(-s // hop), 0), f0.size), min(max(-(-e // hop), 0), f0.size)
+        seg = f0[lo:hi] if hi > lo else f0[:0]
+        v = seg[seg > 0.0]
+        if v.size:
+            out.append(dict(f0_median=float(np.median(v)), f0_min=float(v.min()), f0_max=float(v.max()), voiced=float(v.size / seg.size)))
+        else:
+            out.append(dict(f0_median=None, f0_min=None, f0_max=None, voiced=0.0))
+    return out
+
+
+def pitch_rows(n: int, hop: int, max_row: int = PITCH_MAX_ROW, context: int = PITCH_CONTEXT) -> List[Tuple[int, int, int, int]]:
+    """Cuts n samples into the rows SmallTTS.pitch tracks side by side -> [(first sample, samples, first frame kept, frames kept), ...],
+    frames counted over the whole signal at `hop` (frame f starts at f * hop; there are ceil(n / hop)).  Up to max_row samples: one
+    row.  Longer: rows of R = max_row // hop frames (the last one shorter) whose neighbours share O = context // hop frames (made
+    even), so every cut lies on a multiple of hop and a row's frames ARE the signal's frames.  Every frame is kept from the row in which
+    it lies further from a cut: the shared frames are split in the middle.  Every frame is kept exactly once, in order."""
+    n, hop, max_row, context = int(n), int(hop), int(max_row), int(context)
+    if n < 1 or hop < 1:
+        raise ValueError(f"pitch_rows: n >= 1 and hop >= 1 wanted, got {n}, {hop}")
+    F, R, O = -(-n // hop), max_row // hop, (context // hop) // 2 * 2
+    if R < 4 or not 2 <= O <= R // 2:
+        raise ValueError(f"pitch_rows: max_row {max_row} and context {context} do not make rows at hop {hop}")
+    if F <= R:
+        return [(0, n, 0, F)]
+    starts = [0]
+    while starts[-1] + R < F:
+        starts.append(starts[-1] + R - O)
+    own = [0] + [s + O // 2 for s in starts[1:]] + [F]
+    return [(s * hop, min(R * hop, n - s * hop), own[k], own[k + 1] - own[k]) for k, s in enumerate(starts)]
