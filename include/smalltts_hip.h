@@ -778,6 +778,26 @@ int smtts_test_dit_stage(smtts_handle h, void* stream, int net, int what, int l0
                          const float* k_ref, const float* v_ref, const uint8_t* ref_mask, int R, const float* k_text,
                          const float* v_text, const uint8_t* ph_mask, int P, const float* rope, float* x_out, float* img_out,
                          float* shift_out, float* out, float* k_out, float* v_out, float* mod_out);
+/* Every launch of one scorer call, tapped.  net 0: smtts_asr_logprobs (out = logp (B, 4 N, 198)); net 1: smtts_sv_embed (out = emb
+ * (B, 192)).  The hook calls the product's own launcher with a tap sink (null in every product call): behind each launch the whole
+ * per-call buffer that launch wrote is copied, on the same stream, to the launch's slot of `taps`, before a later launch overwrites
+ * it (the recogniser's residual is updated in place, the verifier reuses three buffers per block and lays the pooling logits over
+ * them).  The workspace is this hook's own: the product's size function, filled with 0xff first, so that a launch which read what
+ * nobody wrote leaves NaN in its tap; rows at and behind a row's length hold that NaN, they are nobody's to write.
+ * Slots, one per launch in launch order, each the fp32 buffer named (T = 4 N):
+ *   net 0 (44): 0 upsample (B, T, 64); for layer l = 0 .. 6 at 1 + 6 l: ffn1 (B, T, 64), qkv (B, T, 192: q times 0.5, k, v), attn
+ *               (B, T, 64), proj (B, T, 64), conv (B, T, 64), ffn2 with the final LayerNorm (B, T, 64); 43 head = logp (B, T, 198)
+ *   net 1 (23): 0 blocks.0 (B, N, 768); for block i = 0 .. 2 at 1 + 5 i: tdnn1 (B, N, 768), res2net (B, N, 768), tdnn2 (B, N, 768),
+ *               se gate (B, 768), se apply + residual (B, N, 768); 16 mfa (B, N, 2304), 17 uniform [mean ; std] (B, 4608), 18 the
+ *               attention's row constant (B, 192), 19 attention tanh (B, N, 192), 20 pooling logits (B, N, 2304), 21 pooled behind
+ *               asp_bn (B, 4608), 22 fc = emb (B, 192)
+ * smtts_test_scorer_tap_bytes: the size of the tap buffer (0 when refused); off, when not NULL, holds cap >= 44 (net 0) / 23 (net 1)
+ * entries and receives the byte offset of every slot (multiples of 256, in launch order).
+ * smtts_test_scorer_taps refuses what the entry itself refuses (no such part, B, N, NULL or misaligned x / n_len / out), a NULL or
+ * not 256-byte aligned `taps` and tap_bytes under that size, each with an error and nothing enqueued.  Synchronises the stream. */
+size_t smtts_test_scorer_tap_bytes(smtts_handle h, int net, int B, int N, size_t* off, int cap);
+int smtts_test_scorer_taps(smtts_handle h, void* stream, int net, const float* x, const int32_t* n_len, int B, int N, float* out,
+                           void* taps, size_t tap_bytes);
 /* codec blocks: 1 (default) = fused mixer and fused FFN kernels (C <= 256), 0 = separate norm / conv / two-GEMM path */
 int smtts_test_set_fused_ffn(smtts_handle h, int on);
 /* fused sampler: 1 (default) = the AdaLN between two DiT block GEMMs folded into their epilogues (reference dit.py:19-25,197-212

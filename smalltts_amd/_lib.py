@@ -118,6 +118,8 @@ SIGNATURES: Dict[str, Tuple[object, List[object]]] = {
     "smtts_test_codec_stage": (i32, [vp, vp, i32, i32, i32, vp, i32, i32, i32, vp, C.POINTER(i32), C.POINTER(i32)]),
     "smtts_test_dit_stage": (i32, [vp, vp, i32, i32, i32, i32, i32, i32, vp, vp, i32, i32, vp, vp, i32, i32, i32, vp, vp, vp, i32, vp,
                                    vp, vp, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "smtts_test_scorer_tap_bytes": (sz, [vp, i32, i32, i32, C.POINTER(sz), i32]),
+    "smtts_test_scorer_taps": (i32, [vp, vp, i32, vp, vp, i32, i32, vp, vp, sz]),
     "smtts_test_set_fused_ffn": (i32, [vp, i32]),
     "smtts_test_set_ln_fold": (i32, [vp, i32]),
     "smtts_test_gemm": (i32, [vp, vp, vp, i32, vp, vp, i32, i32, i32, i32, i32, i32, vp, i32]),

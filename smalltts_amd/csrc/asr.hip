@@ -359,7 +359,16 @@ size_t asr_ws_bytes(int B, int N) {
     return 3 * up256(rows * A_D * 4) + up256(rows * 3 * A_D * 4);
 }
 
-hipError_t launch_asr_logprobs(const AsrW& w, const float* x, const int* n_len, int B, int N, void* ws, float* logp, hipStream_t st) {
+// launch order: upsample; per layer ffn1, qkv, attn, proj, conv, ffn2; head
+size_t asr_tap_bytes(int B, int N, int slot) {
+    if (slot < 0 || slot >= ASR_TAPS) return 0;
+    const size_t rows = (size_t)B * 4 * N;
+    if (slot == ASR_TAPS - 1) return rows * A_C * 4;
+    return (slot - 1) % 6 == 1 && slot > 0 ? rows * 3 * A_D * 4 : rows * A_D * 4;
+}
+
+hipError_t launch_asr_logprobs(const AsrW& w, const float* x, const int* n_len, int B, int N, void* ws, float* logp, hipStream_t st,
+                               const ScorerTaps* taps) {
     if (B < 1 || N < 1 || 4 * N > AT_MAXT) return hipErrorInvalidValue;
     const int T = 4 * N;
     const size_t rows = (size_t)B * T;
@@ -370,40 +379,57 @@ hipError_t launch_asr_logprobs(const AsrW& w, const float* x, const int* n_len, 
     float* qkv = reinterpret_cast<float*>(p);
     const dim3 wg(A_NT), tiles((T + A_TM - 1) / A_TM, B);
     const double fr = (double)rows;
+    int slot = 0;
+    hipError_t te = hipSuccess;
+    auto tap = [&](const float* buf) {   // (tests only) what the launch just enqueued wrote, into its slot
+        if (!taps) return;
+        const hipError_t e = hipMemcpyAsync(taps->base + taps->off[slot], buf, asr_tap_bytes(B, N, slot), hipMemcpyDeviceToDevice, st);
+        if (te == hipSuccess) te = e;
+        ++slot;
+    };
     {
         ProfScope ps(st, "asr_upsample", 2.0 * fr * A_D, 5.0 * fr * A_D);
         hipLaunchKernelGGL(asr_upsample_kernel, dim3((T * A_D + A_NT - 1) / A_NT, B), wg, 0, st, x, n_len, N, w.up_w, w.up_b, xa);
     }
+    tap(xa);
     for (int l = 0; l < 7; ++l) {
         const AsrLayerW& L = w.layer[l];
         {
             ProfScope ps(st, "asr_ffn", 4.0 * fr * A_D * A_FF, 8.0 * fr * A_D);
             hipLaunchKernelGGL((asr_ffn_kernel<false>), tiles, wg, 0, st, xa, xa, n_len, N, L.ffn1, nullptr, nullptr);
         }
+        tap(xa);
         {
             ProfScope ps(st, "asr_qkv", 6.0 * fr * A_D * A_D, 16.0 * fr * A_D);
             hipLaunchKernelGGL(asr_qkv_kernel, tiles, wg, 0, st, xa, n_len, N, L.aln_w, L.aln_b, L.wqkv_t, L.bqkv, qkv);
         }
+        tap(qkv);
         {
             ProfScope ps(st, "asr_attn", 4.0 * fr * T * A_D, 16.0 * fr * A_D);
             hipLaunchKernelGGL(asr_attn_kernel, dim3((T + A_NT - 1) / A_NT, A_HEADS, B), wg, 0, st, qkv, n_len, N, ob);
         }
+        tap(ob);
         {
             ProfScope ps(st, "asr_proj", 2.0 * fr * A_D * A_D, 12.0 * fr * A_D);
             hipLaunchKernelGGL(asr_proj_kernel, tiles, wg, 0, st, ob, n_len, N, L.wo_t, L.bo, xa);
         }
+        tap(xa);
         {
             ProfScope ps(st, "asr_conv", 6.0 * fr * A_D * A_D, 8.0 * fr * A_D);
             hipLaunchKernelGGL(asr_conv_kernel, dim3((T + A_CONV_OUT - 1) / A_CONV_OUT, B), wg, 0, st, xa, xb, n_len, N, L.conv);
         }
+        tap(xb);
         {
             ProfScope ps(st, "asr_ffn", 4.0 * fr * A_D * A_FF, 8.0 * fr * A_D);
             hipLaunchKernelGGL((asr_ffn_kernel<true>), tiles, wg, 0, st, xb, xa, n_len, N, L.ffn2, L.fln_w, L.fln_b);
         }
+        tap(xa);
     }
     {
         ProfScope ps(st, "asr_head", 2.0 * fr * A_D * 256, 4.0 * fr * (A_D + A_C));
         hipLaunchKernelGGL(asr_head_kernel, tiles, wg, 0, st, xa, n_len, N, w.proj_t, w.proj_b, logp);
     }
-    return hipGetLastError();
+    tap(logp);
+    const hipError_t le = hipGetLastError();
+    return le != hipSuccess ? le : te;
 }

@@ -389,6 +389,13 @@ int smtts_test_dit_stage(smtts_handle h, void* stream, int net, int what, int l0
     return E.test_dit_stage(ST(stream), net, what, l0, l1, path, twice, x, mask, B, S, t, mod, mod_rows, mod_row0, mod_rstride, k_ref,
                             v_ref, ref_mask, R, k_text, v_text, ph_mask, P, rope, x_out, img_out, shift_out, out, k_out, v_out, mod_out);
 }
+size_t smtts_test_scorer_tap_bytes(smtts_handle h, int net, int B, int N, size_t* off, int cap) { NULLCHK0;
+    return E.test_scorer_tap_bytes(net, B, N, off, cap);
+}
+int smtts_test_scorer_taps(smtts_handle h, void* stream, int net, const float* x, const int32_t* n_len, int B, int N, float* out,
+                           void* taps, size_t tap_bytes) { NULLCHK;
+    return E.test_scorer_taps(ST(stream), net, x, n_len, B, N, out, taps, tap_bytes);
+}
 int smtts_test_set_fused_ffn(smtts_handle h, int on) { NULLCHK; E.set_fused_ffn(on != 0); return 0; }
 int smtts_test_set_ln_fold(smtts_handle h, int on) { NULLCHK; E.set_ln_fold(on != 0); return 0; }
 int smtts_test_set_attention_mfma(smtts_handle h, int mode) { NULLCHK;   // 0: fp32 projection + qk_prep + the fp32 VALU reference kernel; else (default): producer-written operand images + the DMA / MFMA kernel

@@ -253,6 +253,11 @@ class Engine {
                        const uint8_t* ph_mask, int P, const float* rope, float* x_out, float* img_out, float* shift_out, float* out,
                        float* k_out, float* v_out, float* mod_out);
 
+    // every launch of one recogniser (net 0) / verifier (net 1) call, tapped: include/smalltts_hip.h smtts_test_scorer_taps
+    size_t test_scorer_tap_bytes(int net, int B, int N, size_t* off, int cap);
+    int test_scorer_taps(hipStream_t st, int net, const float* x, const int32_t* n_len, int B, int N, float* out, void* taps,
+                         size_t tap_bytes);
+
     // fp16 range guard: per-site count of values that fp16 producers clamped to +-65504 since the last reset (device counters,
     // common.hpp sat_note) + the static part: codec FFN blocks whose fused kernels' hidden / input bound could not be certified
     // below the fp16 range at finalize() (those kernels do not count at run time: they are VALU-bound, see finalize_codec).

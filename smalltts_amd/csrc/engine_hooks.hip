@@ -114,6 +114,60 @@ int Engine::test_codec_stage(hipStream_t st, int part, int stage, int what, cons
     return 0;
 }
 
+// Every launch of one scorer call, tapped (include/smalltts_hip.h smtts_test_scorer_taps): the product's own launcher with a tap sink, on
+// a workspace of the product's own size function filled with 0xff first.  The size of the tap buffer (0 when refused); off (one entry
+// per slot, or NULL) receives the byte offset of every slot.
+size_t Engine::test_scorer_tap_bytes(int net, int B, int N, size_t* off, int cap) {
+    if (net < 0 || net > 1) { fail("test_scorer_tap_bytes: net must be 0 (recogniser) or 1 (speaker verifier)"); return 0; }
+    if (B < 1 || B > 64 || N < (net ? 6 : 1) || N > 225) {
+        fail(std::string("test_scorer_tap_bytes: B must be in [1, 64] and N in [") + (net ? "6" : "1") + ", 225]");
+        return 0;
+    }
+    const int n = net ? SV_TAPS : ASR_TAPS;
+    if (off && cap < n) { fail("test_scorer_tap_bytes: the offset table needs one entry per slot"); return 0; }
+    size_t at = 0;
+    for (int i = 0; i < n; ++i) {
+        if (off) off[i] = at;
+        at += ((net ? sv_tap_bytes(B, N, i) : asr_tap_bytes(B, N, i)) + 255) & ~size_t(255);
+    }
+    return at;
+}
+
+int Engine::test_scorer_taps(hipStream_t st, int net, const float* x, const int32_t* n_len, int B, int N, float* out, void* taps,
+                             size_t tap_bytes) {
+    if (net < 0 || net > 1) return fail("test_scorer_taps: net must be 0 (recogniser) or 1 (speaker verifier)");
+    size_t (*const need)(int, int) = net ? sv_ws_bytes : asr_ws_bytes;
+    // what the entry itself refuses; the workspace is this hook's own (checked as an aligned one of the size the entry asks for)
+    void* const aligned = reinterpret_cast<void*>(uintptr_t(256));
+    if (net ? scorer_entry("test_scorer_taps", "sv", "speaker verifier", "emb", sv_ready_, 6, need, x, n_len, B, N, aligned, need(B < 1 ? 1 : B, N < 6 ? 6 : N), out)
+            : scorer_entry("test_scorer_taps", "asr", "recogniser", "logp", asr_ready_, 1, need, x, n_len, B, N, aligned, need(B < 1 ? 1 : B, N < 1 ? 1 : N), out))
+        return 1;
+    size_t off[ASR_TAPS];
+    static_assert(SV_TAPS <= ASR_TAPS, "off[] holds either table");
+    const size_t need_taps = test_scorer_tap_bytes(net, B, N, off, ASR_TAPS);
+    if (!need_taps) return 1;
+    if (!taps) return fail("smtts_test_scorer_taps: a required pointer is NULL");
+    if ((uintptr_t)taps & 255) return fail("smtts_test_scorer_taps: the tap buffer must be 256-byte aligned");
+    if (tap_bytes < need_taps) return fail("smtts_test_scorer_taps: tap buffer too small (smtts_test_scorer_tap_bytes)");
+    HIPC(hipSetDevice(device_));
+    const size_t bytes = need(B, N);
+    Scratch scratch;
+    void* const ws = scratch.take<char>(bytes);
+    if (!ws) return fail_hip(scratch.err, "hipMalloc(&ws, bytes)");
+    hipError_t e = hipMemsetAsync(ws, 0xff, bytes, st);   // NaN: a launch that read what nobody wrote shows up in its tap
+    if (e == hipSuccess) {
+        ProfTag tag(net ? "sv" : "asr");
+        const ScorerTaps sink{static_cast<char*>(taps), off};
+        e = net ? launch_sv_embed(sv_, x, n_len, B, N, ws, out, st, &sink) : launch_asr_logprobs(asr_, x, n_len, B, N, ws, out, st, &sink);
+    }
+    const hipError_t es = hipStreamSynchronize(st);
+    const hipError_t ef = scratch.release();
+    if (e != hipSuccess) return fail_hip(e, "test_scorer_taps");
+    if (es != hipSuccess) return fail_hip(es, "test_scorer_taps: stream");
+    if (ef != hipSuccess) return fail_hip(ef, "test_scorer_taps: free");
+    return 0;
+}
+
 // DiT / encoder stages through the code of denoise_step / sample / cond_encode (include/smalltts_hip.h smtts_test_dit_stage).  The
 // workspace is planned by the product's own planners (DitWs, EncWs) and filled with 0xff first.
 int Engine::test_dit_stage(hipStream_t st, int net, int what, int l0, int l1, int path, int twice, const void* xin,

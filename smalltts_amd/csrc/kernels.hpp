@@ -129,9 +129,17 @@ struct AsrW {
     const float *proj_t /* [4][64][64], classes >= 198 zero */, *proj_b /* [256] */;
 };
 size_t asr_ws_bytes(int B, int N);
+// A tap sink (tests only; NULL in every product call, and then a launcher enqueues exactly its kernels).  When set, the launcher copies
+// the whole per-call buffer each launch wrote into the sink's slot for that launch (hipMemcpyAsync on the same stream, right behind the
+// launch, before a later launch overwrites the buffer): slot i is launch i, in launch order, at off[i] bytes behind base.
+struct ScorerTaps { char* base; const size_t* off; };
+constexpr int ASR_TAPS = 44, SV_TAPS = 23;
+// bytes launch `slot` of a call writes into (the whole buffer, rows behind a row's length included); 0 outside [0, *_TAPS)
+size_t asr_tap_bytes(int B, int N, int slot);
 // x f32 (B, N, 64), n_len i32 (B) (clamped into [0, N]) -> logp f32 (B, 4 N, 198), 0.0 at and behind frame 4 n_b; ws: asr_ws_bytes, 256-byte
 // aligned, may hold anything.  1 <= N <= 225.
-hipError_t launch_asr_logprobs(const AsrW& w, const float* x, const int* n_len, int B, int N, void* ws, float* logp, hipStream_t st);
+hipError_t launch_asr_logprobs(const AsrW& w, const float* x, const int* n_len, int B, int N, void* ws, float* logp, hipStream_t st,
+                               const ScorerTaps* taps = nullptr);
 // ---- speaker verifier (sv.hip) ---------------------------------------------------------------------------------------------------------
 // Device pointers of the packed verifier weights (Engine::finalize_sv).  A product's weight (n_out, k_in): 64 x 64 blocks, each transposed
 // to [k][n], outputs outer, inputs inner; a k = 3 convolution has k_in = tap * channels + channel.  scale / shift: the BatchNorm (eval)
@@ -154,7 +162,9 @@ struct SvW {
 size_t sv_ws_bytes(int B, int N);
 // x f32 (B, N, 64), n_len i32 (B) (clamped into [0, N]) -> emb f32 (B, 192), every row as if alone in its batch; 0.0 for a row under 6
 // frames.  ws: sv_ws_bytes, 256-byte aligned, may hold anything.  6 <= N <= 225, else hipErrorInvalidValue.
-hipError_t launch_sv_embed(const SvW& w, const float* x, const int* n_len, int B, int N, void* ws, float* emb, hipStream_t st);
+size_t sv_tap_bytes(int B, int N, int slot);   // as asr_tap_bytes
+hipError_t launch_sv_embed(const SvW& w, const float* x, const int* n_len, int B, int N, void* ws, float* emb, hipStream_t st,
+                           const ScorerTaps* taps = nullptr);
 // cos f32 (B): row b of emb (B, D) against row b / K of ref (B / K, D), each norm clamped at 1e-8 (a zero row gives 0).  One wave per row.
 hipError_t launch_sv_cosine(const float* emb, const float* ref, int B, int K, int D, float* cos, hipStream_t st);
 // ---- repair (repair.hip) ----------------------------------------------------------------------------------------------------------

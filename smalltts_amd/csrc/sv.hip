@@ -312,7 +312,17 @@ size_t sv_ws_bytes(int B, int N) {
            2 * up256((size_t)B * S_POOL * 4) + up256((size_t)B * S_ATT * 4);
 }
 
-hipError_t launch_sv_embed(const SvW& w, const float* x, const int* n_len, int B, int N, void* ws, float* emb, hipStream_t st) {
+// launch order: blocks.0; per block tdnn1, res2net, tdnn2, se_squeeze, se_apply; mfa, stats, row constant, attention, logits, pool, fc
+size_t sv_tap_bytes(int B, int N, int slot) {
+    if (slot < 0 || slot >= SV_TAPS) return 0;
+    const size_t fr = (size_t)B * N;
+    if (slot < 16) return slot && (slot - 1) % 5 == 3 ? (size_t)B * S_C * 4 : fr * S_C * 4;
+    static const int per_frame[7] = {S_MFA, 0, 0, S_ATT, S_MFA, 0, 0}, per_row[7] = {0, S_POOL, S_ATT, 0, 0, S_POOL, S_EMB};
+    return (fr * per_frame[slot - 16] + (size_t)B * per_row[slot - 16]) * 4;
+}
+
+hipError_t launch_sv_embed(const SvW& w, const float* x, const int* n_len, int B, int N, void* ws, float* emb, hipStream_t st,
+                           const ScorerTaps* taps) {
     if (B < 1 || N < S_MIN || N > S_MAXN) return hipErrorInvalidValue;
     hipError_t e = g_sv_once.ensure([] {
         return hipFuncSetAttribute(reinterpret_cast<const void*>(sv_res2net_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)R_LDS);
@@ -333,47 +343,69 @@ hipError_t launch_sv_embed(const SvW& w, const float* x, const int* n_len, int B
     float* const crow = take((size_t)B * S_ATT * 4);
     float* const logit = h0;   // fr * 2304 floats = h0 + t1 + r2, all dead once mfa is written
     const double frd = (double)fr;
+    int slot = 0;
+    hipError_t te = hipSuccess;
+    auto tap = [&](const float* buf) {   // (tests only) what the launch just enqueued wrote, into its slot
+        if (!taps) return;
+        const hipError_t e = hipMemcpyAsync(taps->base + taps->off[slot], buf, sv_tap_bytes(B, N, slot), hipMemcpyDeviceToDevice, st);
+        if (te == hipSuccess) te = e;
+        ++slot;
+    };
     tdnn<1>(st, "sv_tdnn", x, nullptr, nullptr, S_IN, 1, 3, 1, 3 * S_IN, n_len, B, N, w.in, nullptr, h0, S_C);
+    tap(h0);
     for (int i = 0; i < 3; ++i) {
         const SvBlockW& bw = w.block[i];
         const float* const in = i ? ob[i - 1] : h0;
         tdnn<1>(st, "sv_tdnn", in, nullptr, nullptr, S_C, S_C / 64, 1, 1, S_C, n_len, B, N, bw.tdnn1, nullptr, t1, S_C);
+        tap(t1);
         {
             ProfScope ps(st, "sv_res2net", 2.0 * frd * (S_NBAND - 1) * R_K * S_BAND, 8.0 * frd * S_C);
             hipLaunchKernelGGL(sv_res2net_kernel, dim3(B), dim3(R_NT), R_LDS, st, t1, r2, n_len, N, bw);
         }
+        tap(r2);
         tdnn<1>(st, "sv_tdnn", r2, nullptr, nullptr, S_C, S_C / 64, 1, 1, S_C, n_len, B, N, bw.tdnn2, nullptr, t1, S_C);
+        tap(t1);
         {
             ProfScope ps(st, "sv_se_squeeze", 4.0 * B * S_C * S_SE + frd * S_C, 4.0 * frd * S_C);
             hipLaunchKernelGGL(sv_se_squeeze_kernel, dim3(B), dim3(S_C), 0, st, t1, n_len, N, bw, gate);
         }
+        tap(gate);
         {
             ProfScope ps(st, "sv_se_apply", 2.0 * frd * S_C, 12.0 * frd * S_C);
             hipLaunchKernelGGL(sv_se_apply_kernel, dim3((N * (S_C / 4) + S_NT - 1) / S_NT, B), dim3(S_NT), 0, st, t1, in, gate, n_len, N,
                                ob[i]);
         }
+        tap(ob[i]);
     }
     tdnn<1>(st, "sv_tdnn", ob[0], ob[1], ob[2], S_C, S_C / 64, 1, 1, S_MFA, n_len, B, N, w.mfa, nullptr, mfa, S_MFA);
+    tap(mfa);
     {
         ProfScope ps(st, "sv_asp_stats", 5.0 * frd * S_MFA, 8.0 * frd * S_MFA);
         hipLaunchKernelGGL(sv_asp_stats_kernel, dim3(S_MFA / S_NT, B), dim3(S_NT), 0, st, mfa, n_len, N, ms);
     }
+    tap(ms);
     {
         ProfScope ps(st, "sv_asp_const", 2.0 * B * S_POOL * S_ATT, 4.0 * S_POOL * S_ATT);
         hipLaunchKernelGGL(sv_rowvec_kernel, dim3(B), dim3(V_NT), 0, st, ms, w.att_ct, nullptr, n_len, N, 0, crow);
     }
+    tap(crow);
     tdnn<2>(st, "sv_tdnn", mfa, nullptr, nullptr, S_MFA, S_MFA / 64, 1, 1, S_MFA, n_len, B, N, w.att, crow, att, S_ATT);
+    tap(att);
     tdnn<0>(st, "sv_tdnn", att, nullptr, nullptr, S_ATT, S_ATT / 64, 1, 1, S_ATT, n_len, B, N, w.logit, nullptr, logit, S_MFA);
+    tap(logit);
     {
         ProfScope ps(st, "sv_asp_pool", 12.0 * frd * S_MFA, 8.0 * frd * S_MFA);
         hipLaunchKernelGGL(sv_asp_pool_kernel, dim3(S_MFA / S_NT, B), dim3(S_NT), 0, st, logit, mfa, n_len, N, w.pool_scale, w.pool_shift,
                            pooled);
     }
+    tap(pooled);
     {
         ProfScope ps(st, "sv_fc", 2.0 * B * S_POOL * S_EMB, 4.0 * S_POOL * S_EMB);
         hipLaunchKernelGGL(sv_rowvec_kernel, dim3(B), dim3(V_NT), 0, st, pooled, w.fc_t, w.fc_b, n_len, N, 1, emb);
     }
-    return hipGetLastError();
+    tap(emb);
+    const hipError_t le = hipGetLastError();
+    return le != hipSuccess ? le : te;
 }
 
 hipError_t launch_sv_cosine(const float* emb, const float* ref, int B, int K, int D, float* cos, hipStream_t st) {

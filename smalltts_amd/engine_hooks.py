@@ -12,6 +12,26 @@ from ._lib import ACT, PRECISION, SITES, ptr as _p
 from .weights import HEAD_DIM, LATENT_DIM as LATENT, N_BLOCKS as N_LAYERS, N_HEADS
 
 
+SCORER_NETS = {"asr": 0, "sv": 1}
+_ASR_LAYER = ("ffn1", "qkv", "attn", "proj", "conv", "ffn2")
+_SV_BLOCK = ("tdnn1", "res2net", "tdnn2", "gate", "out")
+# the slots of smtts_test_scorer_taps: one per launch, in launch order
+SCORER_TAPS = {
+    "asr": ["upsample"] + [f"layers.{l}.{s}" for l in range(7) for s in _ASR_LAYER] + ["logp"],
+    "sv": ["blocks.0"] + [f"blocks.{i}.{s}" for i in (1, 2, 3) for s in _SV_BLOCK] + ["mfa", "stats", "crow", "att", "logit", "pooled", "emb"],
+}
+
+
+def scorer_tap_shapes(net: str, B: int, N: int) -> Dict[str, tuple]:
+    """the fp32 shape of every slot of SCORER_TAPS[net]"""
+    if net == "asr":
+        T = 4 * N
+        return {n: (B, T, 198) if n == "logp" else (B, T, 192) if n.endswith(".qkv") else (B, T, 64) for n in SCORER_TAPS[net]}
+    row = {"stats": 4608, "crow": 192, "pooled": 4608, "emb": 192}
+    frame = {"mfa": 2304, "att": 192, "logit": 2304}
+    return {n: (B, row[n]) if n in row else (B, 768) if n.endswith(".gate") else (B, N, frame.get(n, 768)) for n in SCORER_TAPS[net]}
+
+
 class EngineHooks:
     def set_ln_fold(self, on: bool) -> bool:
         """Test hook: the fused sampler's AdaLN between two DiT block GEMMs folded into their epilogues (default) or as separate
@@ -127,6 +147,35 @@ class EngineHooks:
                                                _p(k_ref), _p(v_ref), _p(ref_mask), R, _p(k_text), _p(v_text), _p(ph_mask), P, _p(rope),
                                                _p(res.get("x")), _p(res.get("img")), _p(res.get("shift")), _p(res.get("out")),
                                                _p(res.get("k")), _p(res.get("v")), _p(res.get("mod"))), "test_dit_stage")
+        return res
+
+    def test_scorer_tap_slots(self, net: str, B: int, N: int):
+        """-> (byte offset of every slot of smtts_test_scorer_taps, the tap buffer's size in bytes)"""
+        off = (C.c_size_t * len(SCORER_TAPS[net]))()
+        total = int(self.lib.smtts_test_scorer_tap_bytes(self.h, SCORER_NETS[net], int(B), int(N), off, len(off)))
+        if not total:
+            self._ck(1, "test_scorer_tap_bytes")
+        return list(off), total
+
+    def test_scorer_taps(self, net: str, x, ns) -> Dict[str, torch.Tensor]:
+        """Every launch of one scorer call, tapped (include/smalltts_hip.h smtts_test_scorer_taps).  net: "asr" or "sv"; x fp32
+        (B, N, 64), ns the rows' lengths.  -> {slot name of SCORER_TAPS[net]: the buffer that launch wrote, a device tensor}; the last
+        slot is the call's result.  Elements nobody wrote (at and behind a row's length) are NaN."""
+        x = self._dev(x, torch.float32)
+        B, N = x.shape[:2]
+        n_len = self._dev(torch.as_tensor([int(v) for v in ns], dtype=torch.int32), torch.int32)
+        off, total = self.test_scorer_tap_slots(net, B, N)
+        names = SCORER_TAPS[net]
+        shapes = scorer_tap_shapes(net, B, N)
+        buf = torch.empty(total, dtype=torch.uint8, device=self.device)
+        out = torch.empty(shapes[names[-1]], device=self.device)
+        self._ck(self.lib.smtts_test_scorer_taps(self.h, self._stream(), SCORER_NETS[net], _p(x), _p(n_len), B, N, _p(out), _p(buf),
+                                                 total), "test_scorer_taps")
+        res = {}
+        for name, o in zip(names, off):
+            sh = shapes[name]
+            nb = 4 * int(torch.Size(sh).numel())
+            res[name] = buf[o:o + nb].view(torch.float32).view(sh)
         return res
 
     def test_swiglu(self, A, W1, W3, b1=None, b3=None, split=3):

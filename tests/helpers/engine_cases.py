@@ -429,6 +429,8 @@ CASES = [
                                    rope=o.rope, **{k: v for k, v in o.cache.items()}), {}),
     ("test_dit_stage text input blocks", lambda e, o: e.test_dit_stage("text", 3, x=o.ids, mask=o.ph_mask), {}),
     ("test_dit_stage style projection kv", lambda e, o: e.test_dit_stage("style", 12, x=f32(B, R, 512), mask=boolean(B, R), path="unsplit"), {}),
+    ("test_scorer_taps sv", lambda e, o: e.test_scorer_taps("sv", f32(B, 7, 64), [7, 6]), {}),
+    ("test_scorer_taps asr", lambda e, o: e.test_scorer_taps("asr", f32(B, 3, 64), [3, 1]), {}),
     ("test_swiglu", lambda e, o: e.test_swiglu(f32(4, 8), f32(6, 8), f32(6, 8)), {}),
     ("test_swiglu biases split", lambda e, o: e.test_swiglu(f32(4, 8), f32(6, 8), f32(6, 8), b1=f32(6), b3=f32(6), split=1), {}),
     ("test_attention", lambda e, o: attention(e, o, "test_attention"), {}),

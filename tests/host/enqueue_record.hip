@@ -205,6 +205,15 @@ static void operators(const Bufs& b, const std::string& cfgname) {
             call(tag("sv_embed B2 N" + std::to_string(N)), [&] { return smtts_sv_embed(H, nullptr, x, n_len, B, N, ws, n, emb); });
         }
         call(tag("sv_embed B2 N70 workspace one byte short"), [&] { return smtts_sv_embed(H, nullptr, x, n_len, B, 70, ws, n - 1, emb); });
+        // the tap hook: the same launches with a copy behind each, in front of them the fill of its own workspace
+        size_t tb = smtts_test_scorer_tap_bytes(H, 0, B, 5, nullptr, 0);
+        char* taps = dev<char>(tb);
+        call(tag("test_scorer_taps asr B2 N5"), [&] { return smtts_test_scorer_taps(H, nullptr, 0, x, n_len, B, 5, logp, taps, tb); });
+        call(tag("test_scorer_taps asr B2 N5 taps one byte short"), [&] { return smtts_test_scorer_taps(H, nullptr, 0, x, n_len, B, 5, logp, taps, tb - 1); });
+        tb = smtts_test_scorer_tap_bytes(H, 1, B, 6, nullptr, 0);
+        taps = dev<char>(tb);
+        call(tag("test_scorer_taps sv B2 N6"), [&] { return smtts_test_scorer_taps(H, nullptr, 1, x, n_len, B, 6, emb, taps, tb); });
+        call(tag("test_scorer_taps sv B2 N6 taps one byte short"), [&] { return smtts_test_scorer_taps(H, nullptr, 1, x, n_len, B, 6, emb, taps, tb - 1); });
     }
 }
 

@@ -3,7 +3,8 @@ against recording stand-ins for the HIP runtime (tests/host/hip_record.hpp), reg
 codec, the recogniser and the verifier), and makes the operator calls of its list under both tunings and two presets: the condition
 encoder with and without its fork, denoise_step with and without a caller rope table, the samplers (plain, on a second caller stream,
 N = 8, CFG, tap, pins, refused calls followed by a plain one), the DiT / encoder stage hook, the codec (decode, encode, two streamed
-chunks, one stage of each half through its hook) and the two scorers (with one refused call each).  Every kernel launch, memset, copy, event record / wait and stream / event creation is one line,
+chunks, one stage of each half through its hook), the two scorers (with one refused call each) and their tap hook (the same, and
+refused with a tap buffer one byte short).  Every kernel launch, memset, copy, event record / wait and stream / event creation is one line,
 with the stream it went to.  The lines must equal tests/golden/enqueue_table.txt.gz, recorded at the commit its first line names."""
 import gzip
 import os
@@ -34,8 +35,9 @@ def _inventory(specs):
 # the codec, recogniser and verifier sections of every configuration; the refused ones enqueue nothing
 PARTS_OK = ("codec_decode B2 T3", "codec_encode B2 one hop", "codec_decode_stream B2 T2 chunk0", "codec_decode_stream B2 T2 chunk1",
             "test_codec_stage decoder stage1 what6 T3", "test_codec_stage encoder stage6 what6 T8", "asr_logprobs B2 N5", "sv_embed B2 N6",
-            "sv_embed B2 N70")
-PARTS_REFUSED = ("asr_logprobs B2 N5 workspace one byte short", "sv_embed B2 N70 workspace one byte short")
+            "sv_embed B2 N70", "test_scorer_taps asr B2 N5", "test_scorer_taps sv B2 N6")
+PARTS_REFUSED = ("asr_logprobs B2 N5 workspace one byte short", "sv_embed B2 N70 workspace one byte short",
+                 "test_scorer_taps asr B2 N5 taps one byte short", "test_scorer_taps sv B2 N6 taps one byte short")
 
 
 def test_every_engine_call_enqueues_the_recorded_sequence(tmp_path):
@@ -67,6 +69,11 @@ def test_every_engine_call_enqueues_the_recorded_sequence(tmp_path):
         assert sum(" cfg_combine" in l for l in body[f"== sample mode1 cfg1 N9 [{cfg}]"]) == 2
         assert all(len(body[f"== {p} [{cfg}]"]) > 1 and body[f"== {p} [{cfg}]"][-1] == "rc=0" for p in PARTS_OK)
         assert all(len(body[f"== {p} [{cfg}]"]) == 1 and body[f"== {p} [{cfg}]"][0].startswith("rc=1 ") for p in PARTS_REFUSED)
+        # the tap hook runs the product's launcher: its own workspace filled first, then the product's lines, each with one copy behind it
+        for hook, entry, n in (("test_scorer_taps asr B2 N5", "asr_logprobs B2 N5", 44), ("test_scorer_taps sv B2 N6", "sv_embed B2 N6", 23)):
+            tapped, product = body[f"== {hook} [{cfg}]"], body[f"== {entry} [{cfg}]"]
+            assert tapped[0] == "main memset whole" and len(product) == n + 1
+            assert tapped[1::2] == product and all(l.startswith("main memcpy ") and l.endswith(" d2d") for l in tapped[2:-1:2])
     lat = {h: b for h, b in _sections(want) if h.endswith("[latency f16]")}
     assert lat["== cond_encode B2 R3 P5 [latency f16]"][:5] == ["create side0", "create ev0", "create ev1", "main record ev0", "side0 wait ev0"]
     assert not any(l.startswith(("side", "create")) for l in lat["== cond_encode B2 R3 P0 [latency f16]"])
